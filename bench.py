@@ -70,7 +70,13 @@ def parse_args():
                     help="functional test only: every rank uses GPU 0 (needs --dist-backend gloo)")
     ap.add_argument("--dump-records", default="", help="rank 0 saves the gathered [world * pairs, 32] result records of the last "
                     "step here (.npy); slots [30], [31] of every record carry the rank and the device ordinal that produced it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the LAST timed step returned to DIR/<name>.npy (float32 / float64): poses [pairs, 4, 4] and the "
+                         "per-level optimizer statistics [pairs, levels]; at N > 1 the poses, iterations and status of the whole job from the "
+                         "gathered records")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     if a.interp != "linear":
         a.over = {"interp": {"cosine": 1, "cubic": 2, "cubic_hermite": 3}[a.interp]}
     return a
@@ -111,6 +117,22 @@ def cpu_baseline(args, batch, n_sample):
                       "host_cores": os.cpu_count(),
                       "note": "OpenMP over the 8 channels / range-split reduction = the reference's TBB decomposition (max 8-way)"},
     }
+
+
+def dump_outputs(out_dir, poses, stats, gathered):
+    """What the timed path handed its caller in the last timed step, one .npy per array (float32 / float64; 1024 pairs: < 200 KB).
+    At N > 1 rank 0 holds only its own shard's statistics: the job's poses, iterations and status come from the gathered records."""
+    from bpvo_amd.distributed import records_to_poses
+    os.makedirs(out_dir, exist_ok=True)
+    if gathered is not None and gathered.shape[0] != poses.shape[0]:
+        gp, iters, status = records_to_poses(gathered)
+        arrays = {"poses": gp, "num_iterations": iters, "status": status}
+    else:
+        arrays = {"poses": poses, "num_iterations": stats["numIterations"], "final_error": stats["finalError"],
+                  "first_order_optimality": stats["firstOrderOptimality"], "status": stats["status"]}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def launch_ranks(args):
@@ -327,6 +349,8 @@ def main():
             assert gp.shape[0] == n_pairs_total and np.array_equal(gp[:P, :3, :], poses[:, :3, :])
             if args.dump_records:
                 np.save(args.dump_records, gathered.detach().cpu().numpy())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, poses, stats, gathered)
 
         roofline = None
 

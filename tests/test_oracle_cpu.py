@@ -914,18 +914,15 @@ def _latch_numpy(img, nbytes, K, rotation):
 
 
 def test_latch_tables_agree():
-    """The two data copies of the sampling table (product, oracle) hold the same 3072 integers — and, where the reference checkout
-    exists, they are `sampling_points_arr` of bpvo/latch_descriptor.cc."""
+    """The two data copies of the sampling table (product, oracle) hold the same 3072 integers, and they are `sampling_points_arr` of
+    bpvo/latch_descriptor.cc (stored in tests/golden/reference/pins.npz by tests/golden/make_reference_pins.py)."""
     import re
     t = _latch_table()
     assert t.shape == (3072,) and t.min() == -24 and t.max() == 24
     prod = open(os.path.join(ROOT, "bpvo_amd", "csrc", "latch_table.h")).read().split("kLatchTable[kLatchTableInts] = {")[1].split("};")[0]
     assert np.array_equal(t, np.array([int(v) for v in re.findall(r"-?\d+", prod)]))
-    ref = "/root/reference/bpvo/latch_descriptor.cc"
-    if os.path.exists(ref):
-        txt = open(ref).read()
-        a = txt.index("{", txt.index("sampling_points_arr[]"))
-        assert np.array_equal(t, np.array([int(v) for v in re.findall(r"-?\d+", txt[a: txt.index("};", a)])]))
+    with np.load(os.path.join(ROOT, "tests", "golden", "reference", "pins.npz")) as z:
+        assert np.array_equal(t, z["latch_sampling_points"])
 
 
 def test_latch_rotated_offsets_are_insensitive_to_the_last_bit_of_the_cosine():
