@@ -374,6 +374,71 @@ class Context:
             self.call("get_trajectory", out.ctypes.data_as(C.c_void_p))
         return out
 
+    # -- many independent VisualOdometry sequences (bpvo_hip_add_frames)
+    @staticmethod
+    def _result_dict(r):
+        return dict(pose=np.array(r.pose, np.float32).reshape(4, 4), covariance=np.array(r.covariance, np.float32).reshape(6, 6),
+                    stats=[dict(numIterations=s.numIterations, finalError=s.finalError,
+                                firstOrderOptimality=s.firstOrderOptimality, status=s.status)
+                           for s in r.optimizerStatistics[: r.numLevels]],
+                    isKeyFrame=bool(r.isKeyFrame), keyFramingReason=r.keyFramingReason, hasPointCloud=bool(r.hasPointCloud))
+
+    @staticmethod
+    def _seq_ids(n, seq):
+        if seq is None:
+            return None, None
+        ids = np.ascontiguousarray(seq, dtype=np.int32).reshape(-1)
+        assert ids.shape[0] == n, "one sequence id per frame"
+        return ids, ids.ctypes.data_as(C.c_void_p)
+
+    def add_frames(self, images, disps, seq=None):
+        """Frame i of images [n, rows, cols] u8 / disps [n, rows, cols] f32 is the next frame of sequence seq[i] (None: 0 .. n-1);
+        returns a list of n dicts in add_frame's format."""
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        disps = _f32(disps)
+        n = images.shape[0]
+        assert images.shape == (n, self.rows, self.cols) and disps.shape == images.shape
+        ids, p_ids = self._seq_ids(n, seq)
+        res = (Result * n)()
+        self.call("add_frames", n, p_ids, images.ctypes.data_as(C.c_void_p), disps.ctypes.data_as(C.c_void_p), 0, res)
+        return [self._result_dict(r) for r in res]
+
+    def add_frames_device(self, n, d_images_ptr, d_disps_ptr, seq=None):
+        """add_frames with the n images / disparities already in device memory (contiguous [n][rows*cols])."""
+        ids, p_ids = self._seq_ids(n, seq)
+        res = (Result * n)()
+        self.call("add_frames", int(n), p_ids, C.c_void_p(d_images_ptr), C.c_void_p(d_disps_ptr), 1, res)
+        return [self._result_dict(r) for r in res]
+
+    def seq_capacity(self):
+        n = C.c_int()
+        self.call("seq_capacity", C.byref(n))
+        return n.value
+
+    def seq_reset(self, s):
+        self.call("seq_reset", int(s))
+
+    def seq_num_points_at_level(self, s, level=-1):
+        n = C.c_int()
+        self.call("seq_num_points_at_level", int(s), int(level), C.byref(n))
+        return n.value
+
+    def seq_point_cloud(self, s):
+        n = C.c_size_t()
+        pose = np.empty((4, 4), np.float32)
+        self.call("seq_get_point_cloud", int(s), None, C.byref(n), pose.ctypes.data_as(C.c_void_p))
+        pts = np.zeros(n.value, POINT_WITH_INFO)
+        self.call("seq_get_point_cloud", int(s), pts.ctypes.data_as(C.c_void_p), C.byref(n), pose.ctypes.data_as(C.c_void_p))
+        return pts, pose
+
+    def seq_trajectory(self, s):
+        n = C.c_int()
+        self.call("seq_trajectory_size", int(s), C.byref(n))
+        out = np.empty((n.value, 4, 4), np.float32)
+        if n.value:
+            self.call("seq_get_trajectory", int(s), out.ctypes.data_as(C.c_void_p))
+        return out
+
     # -- batches
     def _stats_array(self, st, n_pairs):
         a = np.ctypeslib.as_array(C.cast(st, C.POINTER(C.c_int32)), shape=(n_pairs, self.L, 4)).copy()

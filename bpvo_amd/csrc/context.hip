@@ -679,6 +679,8 @@ void bpvo_hip_destroy(bpvo_hip_ctx* c)
   (void) hipFree(c->d_count); (void) hipFree(c->d_counters); (void) hipFree(c->d_tickets); (void) hipFree(c->d_trace);
   (void) hipFree(c->st_left); (void) hipFree(c->st_right); (void) hipFree(c->st_left_pre); (void) hipFree(c->st_right_pre); (void) hipFree(c->st_disp);
   (void) hipFree(c->st_sgm);
+  (void) hipFree(c->d_seq_cloud); (void) hipFree(c->d_seq_jobs); (void) hipFree(c->d_cloud_jobs); (void) hipFree(c->d_seq_cnt);
+  (void) hipHostFree(c->h_seq_jobs); (void) hipHostFree(c->h_cloud_jobs); (void) hipHostFree(c->h_seq_cnt);
   for(auto st : c->up_streams) if(st) { (void) hipStreamSynchronize(st); (void) hipStreamDestroy(st); }
   for(auto p : c->up_pinned) (void) hipHostFree(p);
   for(auto e : c->up_slot_free) if(e) (void) hipEventDestroy(e);

@@ -472,7 +472,8 @@ int upload_single_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int level)
   return BPVO_OK;
 }
 
-void trajectory_push(bpvo_hip_ctx* c, const M44& T)   // Trajectory::push_back + InvertPose (bpvo/trajectory.cc:30-50)
+void trajectory_push(bpvo_hip_ctx* c, const M44& T) { trajectory_push(c->trajectory, T); }
+void trajectory_push(std::vector<M44>& trajectory, const M44& T)   // Trajectory::push_back + InvertPose (bpvo/trajectory.cc:30-50)
 {
   M44 Ti = m44_identity();
   for(int i = 0; i < 3; ++i)
@@ -483,8 +484,8 @@ void trajectory_push(bpvo_hip_ctx* c, const M44& T)   // Trajectory::push_back +
     s += Ti.m[2 * 4 + i] * T.m[11];
     Ti.m[i * 4 + 3] = -s;
   }
-  if(!c->trajectory.empty()) c->trajectory.push_back(m44_mul(c->trajectory.back(), Ti));
-  else c->trajectory.push_back(Ti);
+  if(!trajectory.empty()) trajectory.push_back(m44_mul(trajectory.back(), Ti));
+  else trajectory.push_back(Ti);
 }
 
 // Fused path of the estimate loops: the residual / valid buffers of a workspace may lag behind its last linearisation

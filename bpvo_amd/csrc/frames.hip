@@ -11,13 +11,13 @@ FrameRun ctx_run(bpvo_hip_ctx* c) { return FrameRun{c->stream, &c->lanes[0], 0, 
 
 // which: 0 = table of the setData stage, 1 = table of the setTemplate stage (two tables, so that queueing the template stage does not
 // have to wait for the descriptor kernels that still read the first).  Returns the device table through *tab (row fr.tab of level 0).
-int upload_frame_jobs(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr, int which, const FrameJob** tab)
+int upload_frame_jobs_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr, int which, const FrameJob** tab)
 {
   const size_t table = (size_t) which * c->L * c->n_frames;
   FR_CK(c, fr, hipEventSynchronize(fr.ln->staging_ev[which]));   // the pinned rows may still feed the copy of an earlier call
   for(int l = 0; l < c->L; ++l) {
     FrameJob* row = c->h_fjobs + table + (size_t) l * c->n_frames + fr.tab;
-    for(int i = 0; i < count; ++i) row[i] = make_frame_job(c, c->frames[first + i * stride], l);
+    for(int i = 0; i < count; ++i) row[i] = make_frame_job(c, c->frames[slots[i]], l);
   }
   // rows [tab, tab + count) of every level in one copy
   const size_t pitch = sizeof(FrameJob) * (size_t) c->n_frames;
@@ -32,21 +32,32 @@ int upload_frame_jobs(bpvo_hip_ctx* c, int first, int stride, int count, const F
   *tab = c->d_fjobs + table + fr.tab;
   return BPVO_OK;
 }
+std::vector<int> strided_slots(int first, int stride, int count)
+{
+  std::vector<int> v((size_t) std::max(count, 0));
+  for(int i = 0; i < count; ++i) v[i] = first + i * stride;
+  return v;
+}
+int upload_frame_jobs(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr, int which, const FrameJob** tab)
+{
+  const std::vector<int> slots = strided_slots(first, stride, count);
+  return upload_frame_jobs_slots(c, slots.data(), count, fr, which, tab);
+}
 
 // VisualOdometryFrame::setData (reference: bpvo/vo_frame.cc:48-55) for `count` frames at once
 // skip_odd_disp: the frames are the (A, B) frames of pairs, in that order: B (odd i) only ever serves as the CURRENT frame of its pair,
 // whose disparity nothing reads (the reference copies what it is handed, bpvo/vo_frame.cc:50-51; estimatePose never looks at it) — it is
 // neither uploaded nor copied: 40 % of a pair's input bytes
 // (2: as 1, with the device-resident disparities packed for the even frames only — the staging area of the upload pipeline)
-int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uint8_t* images, const float* disps, bool on_device,
-                    const FrameRun& fr, int skip_odd_disp)
+int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const uint8_t* images, const float* disps, bool on_device,
+                          const FrameRun& fr, int skip_odd_disp)
 {
   if(count <= 0) return BPVO_OK;
   const size_t npix = c->geom[0].npix;
   hipStream_t s = fr.stream;
   if(!on_device) {
     for(int i = 0; i < count; ++i) {
-      FrameSlot& f = c->frames[first + i * stride];
+      FrameSlot& f = c->frames[slots[i]];
       FR_CK(c, fr, hipMemcpyAsync(f.img[0], images + (size_t) i * npix, npix, hipMemcpyHostToDevice, s));
       if(!(skip_odd_disp && (i & 1)) && !fr.skip_disparity_upload)
         FR_CK(c, fr, hipMemcpyAsync(f.disp, disps + (size_t) i * npix, npix * sizeof(float), hipMemcpyHostToDevice, s));
@@ -54,15 +65,15 @@ int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uin
   }
   // pair batches: the compact channel-0 plane serves the saliency map of TEMPLATE frames only; the current frames' descriptor kernel
   // skips its store (the selection reads channel 0 from the records should such a frame be made a template later)
-  for(int i = 0; i < count; ++i) c->frames[first + i * stride].ch0_valid = !(skip_odd_disp && (i & 1));
+  for(int i = 0; i < count; ++i) c->frames[slots[i]].ch0_valid = !(skip_odd_disp && (i & 1));
   // ... and the TEMPLATE frames (A, even) of a pair batch keep no records at the NMS levels (FrameSlot::lazy): bit-planes with the census
   // fused into the blur kernel, CD3 gradients.  Every other frame, and every frame set through the frame API, is dense.
   const bool lazy_ok = skip_odd_disp != 0 && c->lazy_template && c->params.descriptor == BPVO_DESC_BITPLANES && c->C == 8 &&
                        !(c->params.sigmaPriorToCensusTransform > 0.0f) && c->params.sigmaBitPlanes > 0.0f && c->params.gradientEstimation == BPVO_GRAD_CD3;
   for(int i = 0; i < count; ++i)
-    for(int l = 0; l < c->L; ++l) c->frames[first + i * stride].lazy[l] = lazy_ok && !(i & 1) && c->geom[l].nms_radius > 0;
+    for(int l = 0; l < c->L; ++l) c->frames[slots[i]].lazy[l] = lazy_ok && !(i & 1) && c->geom[l].nms_radius > 0;
   const FrameJob* tab = nullptr;
-  int rc = upload_frame_jobs(c, first, stride, count, fr, 0, &tab);
+  int rc = upload_frame_jobs_slots(c, slots, count, fr, 0, &tab);
   if(rc) return rc;
   const int NF = c->n_frames;
   if(on_device) launch_ingest(s, tab, images, disps, npix, count, skip_odd_disp);   // one launch instead of 2 copies per frame
@@ -129,11 +140,17 @@ int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uin
   }
   FR_CK(c, fr, hipGetLastError());
   for(int i = 0; i < count; ++i) {
-    FrameSlot& f = c->frames[first + i * stride];
+    FrameSlot& f = c->frames[slots[i]];
     f.has_data = true;
     f.has_disp = !(skip_odd_disp && (i & 1));
   }
   return BPVO_OK;
+}
+int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uint8_t* images, const float* disps, bool on_device,
+                    const FrameRun& fr, int skip_odd_disp)
+{
+  const std::vector<int> slots = strided_slots(first, stride, count);
+  return frames_set_data_slots(c, slots.data(), count, images, disps, on_device, fr, skip_odd_disp);
 }
 // the disparity of a slot whose data stage ran with FrameRun::skip_disparity_upload, from the caller's host buffer, on the context's copy stream; the
 // context's stream waits for it (whatever is queued there later sees the disparity).  A copy from pageable memory holds the host until it is done
@@ -158,12 +175,12 @@ int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uin
 }
 
 // VisualOdometryFrame::setTemplate (reference: bpvo/vo_frame.cc:61-93 -> bpvo/template_data.cc:37-142) for `count` frames
-int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr)
+int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr)
 {
   if(count <= 0) return BPVO_OK;
   hipStream_t s = fr.stream;
   for(int i = 0; i < count; ++i) {
-    FrameSlot& f = c->frames[first + i * stride];
+    FrameSlot& f = c->frames[slots[i]];
     if(f.tmpl_slab) continue;
     size_t total = 0;
     FrameSlot tmp;
@@ -173,7 +190,7 @@ int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count, const
     carve_frame_tmpl(c, f, (unsigned char*) f.tmpl_slab, nullptr);
   }
   const FrameJob* tab = nullptr;
-  int rc = upload_frame_jobs(c, first, stride, count, fr, 1, &tab);
+  int rc = upload_frame_jobs_slots(c, slots, count, fr, 1, &tab);
   if(rc) return rc;
   const int NF = c->n_frames;
   int* const h_ints = c->h_ints + (size_t) fr.tab * kMaxLevels;
@@ -268,7 +285,7 @@ int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count, const
   std::vector<int> max_n(c->L, 0);
   double pts = 0;
   for(int i = 0; i < count; ++i) {
-    FrameSlot& f = c->frames[first + i * stride];
+    FrameSlot& f = c->frames[slots[i]];
     for(int l = 0; l < c->L; ++l) {
       f.n_host[l] = (l >= p.maxTestLevel) ? h_ints[(size_t) i * kMaxLevels + l] : 0;
       max_n[l] = std::max(max_n[l], f.n_host[l]);
@@ -297,8 +314,13 @@ int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count, const
     FR_CK(c, fr, hipGetLastError());
     resolve_events(c);
   }
-  for(int i = 0; i < count; ++i) c->frames[first + i * stride].has_template = true;
+  for(int i = 0; i < count; ++i) c->frames[slots[i]].has_template = true;
   return BPVO_OK;
+}
+int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr)
+{
+  const std::vector<int> slots = strided_slots(first, stride, count);
+  return frames_set_template_slots(c, slots.data(), count, fr);
 }
 int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count)
 {

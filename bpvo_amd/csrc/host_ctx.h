@@ -76,6 +76,15 @@ struct FrameSlot {
   int n_host[kMaxLevels] = {};
 };
 
+// One sequence of bpvo_hip_add_frames (vo.hip): the VisualOdometry state of bpvo/vo.cc:45-52 for frame slots 3s .. 3s+2 and workspace s
+struct SeqState {
+  int ref = 0, cur = 1, prev = 2;   // slot roles (the single path's vo_ref / vo_cur / vo_prev)
+  M44 T_kf;
+  std::vector<M44> trajectory;
+  size_t cloud_n = 0;               // the point cloud of the sequence's last Result: records [s * cap, s * cap + cloud_n) of bpvo_hip_ctx::d_seq_cloud
+  M44 cloud_pose;
+};
+
 struct Workspace {
   float* r = nullptr;
   uint8_t* valid = nullptr;
@@ -178,6 +187,16 @@ struct bpvo_hip_ctx {
   size_t d_cloud_cap = 0;
   size_t cloud_n = 0;
   M44 cloud_pose;
+  // many independent VisualOdometry sequences (bpvo_hip_add_frames, vo.hip): vo_mode 0 = not yet decided, 1 = bpvo_hip_add_frame, 2 = bpvo_hip_add_frames
+  int vo_mode = 0;
+  std::vector<SeqState> seqs;                      // [seq_capacity], created by the first bpvo_hip_add_frames
+  bpvo_hip_point_with_info* d_seq_cloud = nullptr; // [seq_capacity][geom[maxTestLevel].cap] point clouds
+  PairJob* h_seq_jobs = nullptr;                   // pinned [seq_capacity]: the jobs of the fraction-of-good-points count and the point clouds
+  PairJob* d_seq_jobs = nullptr;
+  CloudJob* h_cloud_jobs = nullptr;                // pinned [seq_capacity]
+  CloudJob* d_cloud_jobs = nullptr;
+  unsigned* h_seq_cnt = nullptr;                   // pinned [seq_capacity]: good-point counters
+  unsigned* d_seq_cnt = nullptr;
   // measurement
   double points_fused = 0;     // points linearised through the fused path since the last counter reset
   int fast_warp = 0;           // bpvo_hip_set_warp_formulation
@@ -406,6 +425,12 @@ PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l);
 void resolve_events(bpvo_hip_ctx* c);
 FrameRun ctx_run(bpvo_hip_ctx* c);
 int upload_frame_jobs(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr, int which, const FrameJob** tab);
+// the frame stages over any list of slots (the strided forms above and below build the list first, slots[i] = first + i * stride)
+std::vector<int> strided_slots(int first, int stride, int count);
+int upload_frame_jobs_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr, int which, const FrameJob** tab);
+int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const uint8_t* images, const float* disps, bool on_device, const FrameRun& fr,
+                          int skip_odd_disp = 0);
+int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr);
 int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uint8_t* images, const float* disps, bool on_device, const FrameRun& fr,
                     int skip_odd_disp = 0);
 int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uint8_t* images, const float* disps, bool on_device, int skip_odd_disp = 0);
@@ -466,6 +491,7 @@ size_t tiled_floats(int n, int floats_per_point);
 int refresh_counters(bpvo_hip_ctx* c);
 int upload_single_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int level);
 void trajectory_push(bpvo_hip_ctx* c, const M44& T);
+void trajectory_push(std::vector<M44>& trajectory, const M44& T);
 int ensure_residuals(bpvo_hip_ctx* c, int ws);
 int fraction_good(bpvo_hip_ctx* c, int ws, float thr, float* frac);
 int get_weights_host(bpvo_hip_ctx* c, int ws, std::vector<float>& w_cm, int* n_out);

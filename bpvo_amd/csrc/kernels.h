@@ -212,6 +212,15 @@ void launch_count_good(hipStream_t s, const PairJob* job, int n, int C, int loss
 // the key frame's point cloud (bpvo/vo.cc:250-281) as 32-byte records on the device; K: the level's intrinsics, img: the key frame's level-0 image
 void launch_point_cloud(hipStream_t s, const PairJob* job, int n, int C, int loss, const uint8_t* img, int rows, int cols, const float K[9], int dspace,
                         bpvo_hip_point_with_info* out);
+// the same two for a table of jobs in one launch each (bpvo_hip_add_frames): counts[k] (zeroed by the caller) of entry k; max_n: the most points of an entry
+void launch_count_good_batch(hipStream_t s, const PairJob* jobs, int n_jobs, int max_n, int C, int loss, float thr, unsigned int* counts);
+struct CloudJob {
+  const PairJob* job;       // device: the job of the key frame's last linearisation
+  const uint8_t* img;       // the key frame's level-0 image
+  size_t out_offset;        // first record of this entry in the output
+};
+void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int loss, int rows, int cols, const float K[9], int dspace,
+                              bpvo_hip_point_with_info* out);
 void launch_pack_records(hipStream_t s, const PairJob* jobs, int n, int L, float* records, const GNState* d_states = nullptr, GNState* h_states = nullptr,
                          const unsigned* d_ctl = nullptr, unsigned* h_ctl = nullptr, int ctl_words = 0, unsigned* zero = nullptr);   // h_states / h_ctl (pinned host): copied out by the same launch; zero: a word cleared by it
 // a few pairs: job table upload (from the pinned host rows) + initial poses + cleared control words in one launch

@@ -550,11 +550,8 @@ __global__ __launch_bounds__(256) void count_good_wide_kernel(const PairJob* job
 // order; DisparitySpaceWarp: disparity_space_warp.h:73-76), and weights[i] of the last linearisation, i.e. the weight of CHANNEL 0's residual
 // (the reference indexes the channel-major weight array with the point index).  The records stay on the device until somebody asks for them.
 struct CloudArgs { float K[9]; int rows, cols, dspace, C, loss; };
-__global__ __launch_bounds__(256) void point_cloud_kernel(const PairJob* job, const uint8_t* __restrict__ img, CloudArgs a, bpvo_hip_point_with_info* __restrict__ out)
+__device__ __forceinline__ bpvo_hip_point_with_info cloud_record(const PairJob& j, int i, const uint8_t* __restrict__ img, const CloudArgs& a)
 {
-  const PairJob& j = *job;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if(i >= j.n) return;
   const float4 X = j.pts[i];
   float x[3];
 #pragma unroll
@@ -576,7 +573,24 @@ __global__ __launch_bounds__(256) void point_cloud_kernel(const PairJob* job, co
   pw.weight = mest_weight_rt(a.loss, r0, 1.0f / j.st->scale);
 #pragma unroll
   for(int k = 0; k < 8; ++k) pw.pad[k] = 0;
-  out[i] = pw;
+  return pw;
+}
+__global__ __launch_bounds__(256) void point_cloud_kernel(const PairJob* job, const uint8_t* __restrict__ img, CloudArgs a, bpvo_hip_point_with_info* __restrict__ out)
+{
+  const PairJob& j = *job;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if(i >= j.n) return;
+  out[i] = cloud_record(j, i, img, a);
+}
+// ... for a table of sequences that key-frame in one bpvo_hip_add_frames call: blockIdx.y = entry of the table, each with its own job, key frame
+// image and place in the output pool (the same records, byte for byte, as point_cloud_kernel's for that job)
+__global__ __launch_bounds__(256) void point_cloud_batch_kernel(const CloudJob* __restrict__ jobs, CloudArgs a, bpvo_hip_point_with_info* __restrict__ out)
+{
+  const CloudJob cj = jobs[blockIdx.y];
+  const PairJob& j = *cj.job;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if(i >= j.n) return;
+  out[cj.out_offset + i] = cloud_record(j, i, cj.img, a);
 }
 
 // (grid-stride over the points and ONE add per workgroup: a thousand workgroups of four waves adding to one word took 55 us on a
@@ -607,6 +621,55 @@ __global__ __launch_bounds__(256) void count_good_kernel(const PairJob* job, flo
   if(threadIdx.x == 0) {
     const unsigned t = s_good[0] + s_good[1] + s_good[2] + s_good[3];
     if(t) atomicAdd(count, t);
+  }
+}
+
+// count_good_kernel for a table of jobs: blockIdx.y = entry of the table, counts[blockIdx.y] its counter (zeroed before the launch); still one
+// atomic add per workgroup.  Integer counts: the result does not depend on the order of the adds.
+template <int C, int LOSS>
+__global__ __launch_bounds__(256) void count_good_batch_kernel(const PairJob* __restrict__ jobs, float thr, unsigned int* __restrict__ counts)
+{
+  const PairJob* job = jobs + blockIdx.y;
+  unsigned good = 0;
+  const int n = job->n;
+  const float sigma_inv = 1.0f / job->st->scale;
+  for(int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    if constexpr(C == 8) {
+      const float4* q = reinterpret_cast<const float4*>(job->r.get());
+      const float4 a = q[tile_index<2>(i, 0)], b = q[tile_index<2>(i, 1)];
+      good += (mest_weight<LOSS>(a.x, sigma_inv) > thr) + (mest_weight<LOSS>(a.y, sigma_inv) > thr) +
+              (mest_weight<LOSS>(a.z, sigma_inv) > thr) + (mest_weight<LOSS>(a.w, sigma_inv) > thr) +
+              (mest_weight<LOSS>(b.x, sigma_inv) > thr) + (mest_weight<LOSS>(b.y, sigma_inv) > thr) +
+              (mest_weight<LOSS>(b.z, sigma_inv) > thr) + (mest_weight<LOSS>(b.w, sigma_inv) > thr);
+    } else {
+#pragma unroll
+      for(int c = 0; c < C; ++c) good += mest_weight<LOSS>(job->r[(size_t) i * C + c], sigma_inv) > thr;
+    }
+  }
+  __shared__ unsigned s_good[4];
+  good = wave_sum_u32(good);
+  if((threadIdx.x & 63) == 0) s_good[threadIdx.x >> 6] = good;
+  __syncthreads();
+  if(threadIdx.x == 0) {
+    const unsigned t = s_good[0] + s_good[1] + s_good[2] + s_good[3];
+    if(t) atomicAdd(counts + blockIdx.y, t);
+  }
+}
+// ... and for descriptors of more than 48 channels (count_good_wide_kernel per entry)
+__global__ __launch_bounds__(256) void count_good_batch_wide_kernel(const PairJob* __restrict__ jobs, int C, int loss, float thr, unsigned int* __restrict__ counts)
+{
+  const PairJob* job = jobs + blockIdx.y;
+  const size_t total = (size_t) job->n * C;
+  const float sigma_inv = 1.0f / job->st->scale;
+  unsigned good = 0;
+  for(size_t k = (size_t) blockIdx.x * 256 + threadIdx.x; k < total; k += (size_t) gridDim.x * 256) good += mest_weight_rt(loss, job->r[k], sigma_inv) > thr ? 1u : 0u;
+  __shared__ unsigned s_good[4];
+  good = wave_sum_u32(good);
+  if((threadIdx.x & 63) == 0) s_good[threadIdx.x >> 6] = good;
+  __syncthreads();
+  if(threadIdx.x == 0) {
+    const unsigned t = s_good[0] + s_good[1] + s_good[2] + s_good[3];
+    if(t) atomicAdd(counts + blockIdx.y, t);
   }
 }
 
@@ -821,6 +884,35 @@ void launch_count_good(hipStream_t s, const PairJob* job, int n, int C, int loss
   if(n <= 0) return;
   if(C > 48) { hipLaunchKernelGGL(count_good_wide_kernel, dim3((unsigned) std::min<size_t>(((size_t) n * C + 255) / 256, 1024)), dim3(256), 0, s, job, C, loss, thr, count); return; }
   dispatch_channels(C, [&](auto c) { launch_count_good_c<decltype(c)::value>(s, job, n, loss, thr, count); });
+}
+template <int C>
+static void launch_count_good_batch_c(hipStream_t s, const PairJob* jobs, int n_jobs, int max_n, int loss, float thr, unsigned int* counts)
+{
+  const dim3 grid(std::min((max_n + 255) / 256, 64), n_jobs);
+  switch(loss) {
+    case BPVO_LOSS_HUBER: hipLaunchKernelGGL((count_good_batch_kernel<C, BPVO_LOSS_HUBER>), grid, dim3(256), 0, s, jobs, thr, counts); break;
+    case BPVO_LOSS_TUKEY: hipLaunchKernelGGL((count_good_batch_kernel<C, BPVO_LOSS_TUKEY>), grid, dim3(256), 0, s, jobs, thr, counts); break;
+    default: hipLaunchKernelGGL((count_good_batch_kernel<C, BPVO_LOSS_L2>), grid, dim3(256), 0, s, jobs, thr, counts); break;
+  }
+}
+void launch_count_good_batch(hipStream_t s, const PairJob* jobs, int n_jobs, int max_n, int C, int loss, float thr, unsigned int* counts)
+{
+  if(n_jobs <= 0 || max_n <= 0) return;
+  if(C > 48) {
+    const dim3 grid((unsigned) std::min<size_t>(((size_t) max_n * C + 255) / 256, 256), n_jobs);
+    hipLaunchKernelGGL(count_good_batch_wide_kernel, grid, dim3(256), 0, s, jobs, C, loss, thr, counts);
+    return;
+  }
+  dispatch_channels(C, [&](auto c) { launch_count_good_batch_c<decltype(c)::value>(s, jobs, n_jobs, max_n, loss, thr, counts); });
+}
+void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int loss, int rows, int cols, const float K[9], int dspace,
+                              bpvo_hip_point_with_info* out)
+{
+  if(n_jobs <= 0 || max_n <= 0) return;
+  CloudArgs a;
+  for(int k = 0; k < 9; ++k) a.K[k] = K[k];
+  a.rows = rows; a.cols = cols; a.dspace = dspace; a.C = C; a.loss = loss;
+  hipLaunchKernelGGL(point_cloud_batch_kernel, dim3((max_n + 255) / 256, n_jobs), dim3(256), 0, s, jobs, a, out);
 }
 void launch_pack_records(hipStream_t s, const PairJob* jobs, int n, int L, float* records, const GNState* d_states, GNState* h_states, const unsigned* d_ctl,
                          unsigned* h_ctl, int ctl_words, unsigned* zero)

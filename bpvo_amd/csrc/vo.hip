@@ -8,17 +8,26 @@ using namespace bpvo_hip_host;
 extern "C" {
 
 // ---- VisualOdometry -------------------------------------------------------------------------------------------------
-static int should_keyframe(bpvo_hip_ctx* c, const M44& pose, int* reason)   // reference: bpvo/vo.cc:199-224
+// the translation and rotation criteria of the key-frame decision (reference: bpvo/vo.cc:199-216): BPVO_KF_LARGE_TRANSLATION, BPVO_KF_LARGE_ROTATION,
+// or BPVO_KF_NO_KEYFRAMING when the fraction of good points decides.  Host floats (asin, sqrt) on purpose: the single and the many-sequence paths
+// decide with the same code.
+static int keyframe_by_motion(const bpvo_hip_params& p, const M44& pose)
 {
-  const bpvo_hip_params& p = c->params;
   const float t_norm = pose.m[3] * pose.m[3] + pose.m[7] * pose.m[7] + pose.m[11] * pose.m[11];
-  if(t_norm > p.minTranslationMagToKeyFrame * p.minTranslationMagToKeyFrame) { *reason = BPVO_KF_LARGE_TRANSLATION; return BPVO_OK; }
+  if(t_norm > p.minTranslationMagToKeyFrame * p.minTranslationMagToKeyFrame) return BPVO_KF_LARGE_TRANSLATION;
   // math::RotationMatrixToEulerAngles (bpvo/math_utils.h:203-216); compared in radians (Q17)
   const float R00 = pose.m[0], R10 = pose.m[4], R20 = pose.m[8], R21 = pose.m[9];
   const float eta = (float) (1.0 / (std::sqrt(R00 * R00 + R10 * R10)));
   const float rz = std::asin(eta * R10), ry = std::asin(-R20), rx = std::asin(eta * R21);
   const float r_norm = rx * rx + ry * ry + rz * rz;
-  if(r_norm > p.minRotationMagToKeyFrame * p.minRotationMagToKeyFrame) { *reason = BPVO_KF_LARGE_ROTATION; return BPVO_OK; }
+  if(r_norm > p.minRotationMagToKeyFrame * p.minRotationMagToKeyFrame) return BPVO_KF_LARGE_ROTATION;
+  return BPVO_KF_NO_KEYFRAMING;
+}
+static int should_keyframe(bpvo_hip_ctx* c, const M44& pose, int* reason)   // reference: bpvo/vo.cc:199-224
+{
+  const bpvo_hip_params& p = c->params;
+  *reason = keyframe_by_motion(p, pose);
+  if(*reason != BPVO_KF_NO_KEYFRAMING) return BPVO_OK;
   float frac = 0.0f;
   int rc = fraction_good(c, 0, p.goodPointThreshold, &frac);
   if(rc) return rc;
@@ -247,6 +256,8 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
 {
   if(!ret) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
   if(c->n_frames < 3) return fail(c, BPVO_ERR_INVALID_ARG, "add_frame needs a ctx with n_frames >= 3");
+  if(c->vo_mode == 2) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frames: a context serves either add_frame or add_frames");
+  c->vo_mode = 1;
   (void) hipSetDevice(c->device);
   const M44 I = m44_identity();
   std::memset(ret, 0, sizeof(*ret));
@@ -382,5 +393,316 @@ int bpvo_hip_get_trajectory(bpvo_hip_ctx* c, float* poses)
   for(size_t i = 0; i < c->trajectory.size(); ++i) std::memcpy(poses + 16 * i, c->trajectory[i].m, 64);
   return BPVO_OK;
 }
+
+// ---- many independent VisualOdometry sequences in one context (bpvo/vo.cc:125-224 per sequence) ---------------------------------------------
+// Sequence s owns frame slots 3s .. 3s+2 and workspace s.  One call runs every phase of addFrame once for all the sequences it advances: one data
+// stage over their current slots, one template stage for the first frames, one estimate, one count of good points, one point-cloud launch and
+// one template stage for the key frames, one estimate against the new key frames.  Each sequence sees the same kernels on the same inputs as
+// the single path's addFrame (the frame stages, the estimate and the counts do not depend on the batch a frame or pair is in), and the host
+// decides with the same float code: the results are the single path's, bit for bit.
+static int seq_capacity(const bpvo_hip_ctx* c) { return std::max(0, std::min(c->n_frames / 3, c->n_pairs)); }
+static void seq_reset_state(bpvo_hip_ctx* c, int s)
+{
+  SeqState& q = c->seqs[s];
+  q.ref = 3 * s; q.cur = 3 * s + 1; q.prev = 3 * s + 2;
+  for(int k = 0; k < 3; ++k) { c->frames[3 * s + k].has_data = false; c->frames[3 * s + k].has_template = false; }
+  q.T_kf = m44_identity();
+  q.trajectory.clear();
+  q.cloud_n = 0;
+  q.cloud_pose = m44_identity();
+  Workspace& w = c->ws[s];
+  w.last_ref = w.last_cur = w.last_level = -1;
+}
+static int seq_storage(bpvo_hip_ctx* c)
+{
+  if(!c->seqs.empty()) return BPVO_OK;
+  const size_t S = (size_t) seq_capacity(c), cap = (size_t) c->geom[c->params.maxTestLevel].cap;
+  if(!c->d_seq_cloud) HIP_CK(c, hipMalloc((void**) &c->d_seq_cloud, S * cap * sizeof(bpvo_hip_point_with_info)));
+  if(!c->d_seq_jobs) HIP_CK(c, hipMalloc((void**) &c->d_seq_jobs, S * sizeof(PairJob)));
+  if(!c->h_seq_jobs) HIP_CK(c, hipHostMalloc((void**) &c->h_seq_jobs, S * sizeof(PairJob)));
+  if(!c->d_cloud_jobs) HIP_CK(c, hipMalloc((void**) &c->d_cloud_jobs, S * sizeof(CloudJob)));
+  if(!c->h_cloud_jobs) HIP_CK(c, hipHostMalloc((void**) &c->h_cloud_jobs, S * sizeof(CloudJob)));
+  if(!c->d_seq_cnt) HIP_CK(c, hipMalloc((void**) &c->d_seq_cnt, S * sizeof(unsigned)));
+  if(!c->h_seq_cnt) HIP_CK(c, hipHostMalloc((void**) &c->h_seq_cnt, S * sizeof(unsigned)));
+  c->seqs.resize(S);
+  for(int s = 0; s < (int) S; ++s) seq_reset_state(c, s);
+  return BPVO_OK;
+}
+static int seq_fail(bpvo_hip_ctx* c, int code, int seq, const char* what)
+{
+  c->err = "sequence " + std::to_string(seq) + ": " + what;
+  return code;
+}
+static void init_result(const bpvo_hip_ctx* c, bpvo_hip_result* ret)      // what add_frame_impl hands back before it knows anything
+{
+  const M44 I = m44_identity();
+  std::memset(ret, 0, sizeof(*ret));
+  std::memcpy(ret->pose, I.m, 64);
+  for(int i = 0; i < 36; ++i) ret->covariance[i] = (i % 7 == 0) ? 1.0f : 0.0f;   // Q16
+  ret->numLevels = c->L;
+  for(int l = 0; l < kMaxLevels; ++l) ret->optimizerStatistics[l] = bpvo_hip_stats{0, -1.0f, -1.0f, BPVO_STATUS_SOLVER_ERROR};
+  ret->isKeyFrame = 0;
+  ret->keyFramingReason = BPVO_KF_NO_KEYFRAMING;
+  ret->hasPointCloud = 0;
+}
+static int add_frames_impl(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* images, const float* disparities, bool on_device,
+                           bpvo_hip_result* results)
+{
+  // 1. every check before any state changes
+  if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a context serves either add_frame or add_frames");
+  const int S = seq_capacity(c);
+  if(S < 1) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames needs a ctx with n_frames >= 3 and n_pairs >= 1");
+  if(n < 1 || n > S) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames: n must be within 1 .. the sequence capacity");
+  if(!images || !disparities) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image/disparity");   // bpvo/vo.cc:68-69
+  if(!results) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
+  std::vector<int> ids((size_t) n);
+  std::vector<char> seen((size_t) S, 0);
+  for(int i = 0; i < n; ++i) {
+    ids[i] = seq ? seq[i] : i;
+    if(ids[i] < 0 || ids[i] >= S) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "no such sequence (n_frames >= 3 S and n_pairs >= S serve sequences 0 .. S-1)");
+    if(seen[ids[i]]) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "appears twice in one call");
+    seen[ids[i]] = 1;
+  }
+  const bpvo_hip_params& p = c->params;
+  if(!c->seqs.empty())
+    for(int i = 0; i < n; ++i) {
+      const FrameSlot& ref = c->frames[c->seqs[ids[i]].ref];
+      if(!ref.has_template) continue;
+      for(int l = p.maxTestLevel; l < c->L; ++l)      // template_data.cc:177 (check_template_not_empty)
+        if(ref.n_host[l] <= 0) return seq_fail(c, BPVO_ERR_NO_TEMPLATE, ids[i], "the key frame's template is empty (you should call setData before calling computeResiduals)");
+    }
+  (void) hipSetDevice(c->device);
+  int rc = seq_storage(c);
+  if(rc) return rc;
+  c->vo_mode = 2;
+  const M44 I = m44_identity();
+  for(int i = 0; i < n; ++i) {
+    init_result(c, results + i);
+    SeqState& q = c->seqs[ids[i]];
+    q.cloud_n = 0;                  // the point cloud belongs to one Result (bpvo/types.h:549-563)
+    q.cloud_pose = I;
+  }
+  auto drain = [&](int code) { (void) hipStreamSynchronize(c->stream); return code; };
+
+  // 2. _cur_frame->setData (vo.cc:131) of every sequence: one data stage over their current slots
+  std::vector<int> slots((size_t) n);
+  for(int i = 0; i < n; ++i) slots[i] = c->seqs[ids[i]].cur;
+  rc = frames_set_data_slots(c, slots.data(), n, images, disparities, on_device, ctx_run(c), 0);
+  if(rc) return drain(rc);
+
+  // 3. first frames (vo.cc:133-139): their templates in one stage
+  std::vector<int> est;           // entries of the call that estimate
+  slots.clear();
+  for(int i = 0; i < n; ++i) {
+    SeqState& q = c->seqs[ids[i]];
+    if(c->frames[q.ref].has_template) { est.push_back(i); continue; }
+    std::swap(q.ref, q.cur);
+    slots.push_back(q.ref);
+  }
+  if(!slots.empty()) {
+    rc = frames_set_template_slots(c, slots.data(), (int) slots.size(), ctx_run(c));
+    if(rc) return drain(rc);
+    for(int i = 0; i < n; ++i) {
+      SeqState& q = c->seqs[ids[i]];
+      if(std::find(est.begin(), est.end(), i) != est.end()) continue;
+      trajectory_push(q.trajectory, q.T_kf);
+      results[i].isKeyFrame = 1;
+      results[i].keyFramingReason = BPVO_KF_FIRST_FRAME;
+    }
+  }
+  const int m = (int) est.size();
+  if(m == 0) return BPVO_OK;
+
+  // 4. estimatePose(ref, cur, T_kf) of the others in one estimate
+  const int L = c->L, lvl = p.maxTestLevel;
+  std::vector<int> wss(m), refs(m), curs(m);
+  std::vector<float> T_init((size_t) m * 16), T_est((size_t) m * 16);
+  std::vector<bpvo_hip_stats> stats((size_t) m * L);
+  for(int k = 0; k < m; ++k) {
+    const SeqState& q = c->seqs[ids[est[k]]];
+    wss[k] = ids[est[k]]; refs[k] = q.ref; curs[k] = q.cur;
+    std::memcpy(&T_init[(size_t) k * 16], q.T_kf.m, 64);
+  }
+  rc = estimate_batch(c, m, wss.data(), refs.data(), curs.data(), T_init.data(), T_est.data(), stats.data());
+  if(rc) return drain(rc);
+  for(int k = 0; k < m; ++k) std::memcpy(results[est[k]].optimizerStatistics, &stats[(size_t) k * L], sizeof(bpvo_hip_stats) * L);
+
+  // 5. the key-frame decision (vo.cc:199-224): motion on the host, the fraction of good points of every estimated sequence in one count
+  int max_n = 0;
+  for(int k = 0; k < m; ++k) {
+    c->h_seq_jobs[k] = make_pair_job(c, wss[k], refs[k], curs[k], lvl);      // the workspace's last linearisation (estimate_batch: level maxTestLevel)
+    max_n = std::max(max_n, c->h_seq_jobs[k].n);
+  }
+  HIP_CK(c, hipMemcpyAsync(c->d_seq_jobs, c->h_seq_jobs, sizeof(PairJob) * (size_t) m, hipMemcpyHostToDevice, c->stream));
+  {
+    GNLaunch gr;      // (fused path: the residual buffers may lag behind the last linearisation — ensure_residuals)
+    gr.jobs = c->d_seq_jobs; gr.npairs = m; gr.max_points = max_n; gr.C = c->C;
+    launch_refresh_residuals(c->stream, gr);
+  }
+  HIP_CK(c, hipMemsetAsync(c->d_seq_cnt, 0, sizeof(unsigned) * (size_t) m, c->stream));
+  launch_count_good_batch(c->stream, c->d_seq_jobs, m, max_n, c->C, p.lossFunction, p.goodPointThreshold, c->d_seq_cnt);
+  HIP_CK(c, hipMemcpyAsync(c->h_seq_cnt, c->d_seq_cnt, sizeof(unsigned) * (size_t) m, hipMemcpyDeviceToHost, c->stream));
+  HIP_CK(c, hipStreamSynchronize(c->stream));
+  HIP_CK(c, hipGetLastError());
+  std::vector<int> kf;            // entries of est that key-frame
+  for(int k = 0; k < m; ++k) {
+    M44 T;
+    std::memcpy(T.m, &T_est[(size_t) k * 16], 64);
+    int reason = keyframe_by_motion(p, T);
+    if(reason == BPVO_KF_NO_KEYFRAMING) {
+      const int npts = c->h_seq_jobs[k].n;
+      const float frac = c->h_seq_cnt[k] / static_cast<float>((size_t) npts * c->C);   // fraction_good (vo_pose_estimator.cc:105-106)
+      reason = (frac < p.maxFractionOfGoodPointsToKeyFrame) ? BPVO_KF_SMALL_FRAC_GOOD : BPVO_KF_NO_KEYFRAMING;
+    }
+    results[est[k]].keyFramingReason = reason;
+    results[est[k]].isKeyFrame = reason != BPVO_KF_NO_KEYFRAMING;
+    if(reason != BPVO_KF_NO_KEYFRAMING) kf.push_back(k);
+  }
+
+  // 6. key frames: the point clouds from the old key frames and the last linearisations (build_point_cloud), then the new templates, then the
+  // estimate against them of the sequences that had a previous frame (vo.cc:161-188)
+  const int nk = (int) kf.size();
+  std::vector<int> re;            // entries of est that estimate again
+  std::vector<float> T_again;
+  if(nk) {
+    const size_t cap = (size_t) c->geom[lvl].cap;
+    int max_c = 0;
+    for(int j = 0; j < nk; ++j) {
+      const int k = kf[j];
+      const int npts = c->h_seq_jobs[k].n;
+      if((size_t) npts > cap) return seq_fail(c, BPVO_ERR_INVALID_ARG, wss[k], "size mismatch");
+      c->h_cloud_jobs[j] = CloudJob{c->d_seq_jobs + k, c->frames[refs[k]].img[0], (size_t) wss[k] * cap};
+      max_c = std::max(max_c, npts);
+    }
+    HIP_CK(c, hipMemcpyAsync(c->d_cloud_jobs, c->h_cloud_jobs, sizeof(CloudJob) * (size_t) nk, hipMemcpyHostToDevice, c->stream));
+    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, nk, max_c, c->C, p.lossFunction, c->rows, c->cols, c->geom[lvl].K, c->dspace, c->d_seq_cloud);
+    HIP_CK(c, hipGetLastError());
+    slots.clear();
+    for(int j = 0; j < nk; ++j) {
+      const int k = kf[j];
+      SeqState& q = c->seqs[wss[k]];
+      q.cloud_n = (size_t) c->h_seq_jobs[k].n;
+      results[est[k]].hasPointCloud = 1;
+      if(!c->frames[q.prev].has_data) {               // vo.cc:161-173
+        std::swap(q.cur, q.ref);
+      } else {                                        // vo.cc:174-188
+        std::swap(q.prev, q.ref);
+        c->frames[q.prev].has_data = false;
+        c->frames[q.prev].has_template = false;
+        re.push_back(j);
+      }
+      slots.push_back(q.ref);
+    }
+    rc = frames_set_template_slots(c, slots.data(), nk, ctx_run(c));
+    if(rc) return drain(rc);
+    if(!re.empty()) {
+      const int mr = (int) re.size();
+      std::vector<int> w2(mr), r2(mr), c2(mr);
+      std::vector<float> I2((size_t) mr * 16);
+      std::vector<bpvo_hip_stats> st2((size_t) mr * L);
+      T_again.resize((size_t) mr * 16);
+      for(int t = 0; t < mr; ++t) {
+        const SeqState& q = c->seqs[wss[kf[re[t]]]];
+        w2[t] = wss[kf[re[t]]]; r2[t] = q.ref; c2[t] = q.cur;
+        std::memcpy(&I2[(size_t) t * 16], I.m, 64);
+      }
+      rc = estimate_batch(c, mr, w2.data(), r2.data(), c2.data(), I2.data(), T_again.data(), st2.data());
+      if(rc) return drain(rc);
+      for(int t = 0; t < mr; ++t) std::memcpy(results[est[kf[re[t]]]].optimizerStatistics, &st2[(size_t) t * L], sizeof(bpvo_hip_stats) * L);
+    }
+  }
+
+  // 7. poses, T_kf and trajectories (add_frame_impl)
+  std::vector<int> again_of((size_t) m, -1);
+  for(int t = 0; t < (int) re.size(); ++t) again_of[kf[re[t]]] = t;
+  for(int k = 0; k < m; ++k) {
+    bpvo_hip_result& ret = results[est[k]];
+    SeqState& q = c->seqs[wss[k]];
+    M44 T;
+    std::memcpy(T.m, &T_est[(size_t) k * 16], 64);
+    M44 pose;
+    if(!ret.isKeyFrame) {
+      std::swap(q.prev, q.cur);
+      pose = m44_mul(T, m44_inverse(q.T_kf));
+      q.T_kf = T;
+    } else if(again_of[k] < 0) {
+      pose = m44_mul(T, m44_inverse(q.T_kf));
+      q.T_kf = I;
+    } else {
+      std::memcpy(pose.m, &T_again[(size_t) again_of[k] * 16], 64);
+      q.T_kf = pose;
+    }
+    std::memcpy(ret.pose, pose.m, 64);
+    trajectory_push(q.trajectory, pose);
+    if(ret.hasPointCloud) q.cloud_pose = q.trajectory.back();
+  }
+  return BPVO_OK;
+}
+
+int bpvo_hip_add_frames(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* results)
+{
+  CHECK_CTX(c);
+  return add_frames_impl(c, n, seq, images, disparities, on_device != 0, results);
+}
+int bpvo_hip_seq_capacity(const bpvo_hip_ctx* c, int* n_sequences)
+{
+  if(!c || !n_sequences) return BPVO_ERR_INVALID_ARG;
+  *n_sequences = seq_capacity(c);
+  return BPVO_OK;
+}
+#define CHECK_SEQ(c, s) if((s) < 0 || (s) >= seq_capacity(c)) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "no such sequence")
+int bpvo_hip_seq_reset(bpvo_hip_ctx* c, int seq)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  if(!c->seqs.empty()) seq_reset_state(c, seq);
+  return BPVO_OK;
+}
+int bpvo_hip_seq_num_points_at_level(bpvo_hip_ctx* c, int seq, int level, int* n)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  if(!n) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr count");
+  if(level < 0) level = c->params.maxTestLevel;
+  if(level >= c->L) return fail(c, BPVO_ERR_INVALID_ARG, "bad level");
+  *n = 0;
+  if(!c->seqs.empty()) {
+    const FrameSlot& ref = c->frames[c->seqs[seq].ref];
+    if(ref.has_template) *n = ref.n_host[level];
+  }
+  return BPVO_OK;
+}
+int bpvo_hip_seq_get_point_cloud(bpvo_hip_ctx* c, int seq, bpvo_hip_point_with_info* pts, size_t* n, float pose[16])
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  const size_t cnt = c->seqs.empty() ? 0 : c->seqs[seq].cloud_n;
+  if(n) *n = cnt;
+  if(pts && cnt) {
+    (void) hipSetDevice(c->device);
+    const size_t off = (size_t) seq * (size_t) c->geom[c->params.maxTestLevel].cap;
+    HIP_CK(c, hipMemcpyAsync(pts, c->d_seq_cloud + off, cnt * sizeof(bpvo_hip_point_with_info), hipMemcpyDeviceToHost, c->stream));
+    HIP_CK(c, hipStreamSynchronize(c->stream));
+  }
+  if(pose) {
+    const M44 P = c->seqs.empty() ? m44_identity() : c->seqs[seq].cloud_pose;
+    std::memcpy(pose, P.m, 64);
+  }
+  return BPVO_OK;
+}
+int bpvo_hip_seq_trajectory_size(bpvo_hip_ctx* c, int seq, int* n)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  if(!n) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr count");
+  *n = c->seqs.empty() ? 0 : (int) c->seqs[seq].trajectory.size();
+  return BPVO_OK;
+}
+int bpvo_hip_seq_get_trajectory(bpvo_hip_ctx* c, int seq, float* poses)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  if(c->seqs.empty()) return BPVO_OK;
+  const std::vector<M44>& t = c->seqs[seq].trajectory;
+  if(!poses && !t.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr poses");
+  for(size_t i = 0; i < t.size(); ++i) std::memcpy(poses + 16 * i, t[i].m, 64);
+  return BPVO_OK;
+}
+#undef CHECK_SEQ
 
 }  // extern "C"

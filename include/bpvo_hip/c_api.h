@@ -229,6 +229,24 @@ int bpvo_hip_get_point_cloud(bpvo_hip_ctx* ctx, bpvo_hip_point_with_info* pts, s
 int bpvo_hip_trajectory_size(bpvo_hip_ctx* ctx, int* n);                                      /* trajectory.cc:42-50 */
 int bpvo_hip_get_trajectory(bpvo_hip_ctx* ctx, float* poses /*[n][16]*/);
 
+/* ---- many independent VisualOdometry sequences in one context (bpvo/vo.cc:125-224 per sequence).
+ * Sequence s owns frame slots 3s, 3s+1, 3s+2 and workspace s: a ctx created with n_frames >= 3 S and n_pairs >= S serves
+ * sequences 0 .. S-1.  A context serves either bpvo_hip_add_frame or these entry points, never both (BPVO_ERR_INVALID_ARG).
+ * bpvo_hip_add_frames advances sequences seq[0 .. n-1] (distinct ids; NULL = 0 .. n-1) by one frame each: images[i] / disparities[i]
+ * are the next frame of sequence seq[i], host memory (on_device = 0) or device memory (1), and results[i] is what bpvo_hip_add_frame
+ * would return for that frame on a context of the sequence's own — bit for bit, point clouds and trajectories included.  Any subset of
+ * the sequences in any order; every argument error, and every per-sequence error (an empty key-frame template: BPVO_ERR_NO_TEMPLATE,
+ * template_data.cc:177), is reported before any sequence changes, with the sequence named in bpvo_hip_last_error. */
+int bpvo_hip_add_frames(bpvo_hip_ctx* ctx, int n, const int* seq /*[n] distinct ids, NULL = 0..n-1*/,
+                        const uint8_t* images /*[n][rows*cols]*/, const float* disparities /*[n][rows*cols]*/,
+                        int on_device, bpvo_hip_result* results /*[n]*/);
+int bpvo_hip_seq_capacity(const bpvo_hip_ctx* ctx, int* n_sequences);                                      /* min(n_frames / 3, n_pairs) */
+int bpvo_hip_seq_reset(bpvo_hip_ctx* ctx, int seq);                       /* next frame of seq is a first frame again */
+int bpvo_hip_seq_num_points_at_level(bpvo_hip_ctx* ctx, int seq, int level, int* n);                       /* vo.cc:226-238 */
+int bpvo_hip_seq_get_point_cloud(bpvo_hip_ctx* ctx, int seq, bpvo_hip_point_with_info* pts, size_t* n, float pose[16]);  /* vo.cc:260-281 */
+int bpvo_hip_seq_trajectory_size(bpvo_hip_ctx* ctx, int seq, int* n);                                      /* trajectory.cc:42-50 */
+int bpvo_hip_seq_get_trajectory(bpvo_hip_ctx* ctx, int seq, float* poses /*[n][16]*/);
+
 /* ---- batches of independent frame pairs (BASELINE.json config 5).
  * Pair p uses frame slots 2p (reference/template frame A) and 2p+1 (current frame B) and workspace p.
  * For each pair: A.setData, A.setTemplate, B.setData, estimatePose(A, B, Identity) -> poses[p].

@@ -5,6 +5,7 @@
  *   bpvo::VisualOdometry                (reference: bpvo/vo.h:31-105, bpvo/vo.cc:66-94)
  *   bpvo::VisualOdometryFrame           (reference: bpvo/vo_frame.h:21-90)
  *   bpvo::VisualOdometryPoseEstimator   (reference: bpvo/vo_pose_estimator.h:34-64)
+ *   bpvo::VisualOdometrySequences       many independent VisualOdometry sequences in one context (no counterpart in the reference)
  *   bpvo::AlgorithmParameters, Result, OptimizerStatistics, PointWithInfo, PointCloud, Trajectory, ImageSize, enums
  *                                       (reference: bpvo/types.h:127-589, bpvo/point_cloud.h, bpvo/trajectory.h)
  *
@@ -137,6 +138,7 @@ class Trajectory {                                              // bpvo/trajecto
   }
  private:
   friend class VisualOdometry;
+  friend class VisualOdometrySequences;
   std::vector<Matrix44> _poses;
 };
 
@@ -375,6 +377,74 @@ class VisualOdometry {
   int _max_test_level;
   Trajectory _trajectory;
   mutable PointVector _points;
+};
+
+/* Many independent VisualOdometry sequences (cameras of a rig, the sequences of an evaluation, a parameter sweep) advanced together by one
+ * device context: addFrames runs addFrame for each of them, and every sequence's results equal, bit for bit, those of a VisualOdometry of
+ * its own fed the same frames.  No counterpart in the reference. */
+class VisualOdometrySequences {
+ public:
+  VisualOdometrySequences(const Matrix33& K, float baseline, ImageSize image_size, int num_sequences,
+                          const AlgorithmParameters& params = AlgorithmParameters(), int device = 0)
+      : _dev(std::make_shared<detail::Device>(K, baseline, image_size, params, 3 * num_sequences, num_sequences, device)),
+        _trajectories((size_t) (num_sequences > 0 ? num_sequences : 0)) {}
+
+  int numSequences() const { int n = 0; _dev->check(bpvo_hip_seq_capacity(_dev->ctx(), &n)); return n; }
+
+  /* images / disparities: n frames of rows * cols pixels, back to back; frame i is the next frame of sequence seq[i] (seq = nullptr:
+   * sequences 0 .. n-1; n = -1: every sequence).  Each Result carries its point cloud, as VisualOdometry::addFrame's does. */
+  std::vector<Result> addFrames(const uint8_t* images, const float* disparities, const int* seq = nullptr, int n = -1)
+  {
+    if(images == nullptr || disparities == nullptr) throw Error("nullptr image/disparity");
+    if(n < 0) n = numSequences();
+    std::vector<bpvo_hip_result> r((size_t) n);
+    _dev->check(bpvo_hip_add_frames(_dev->ctx(), n, seq, images, disparities, 0, r.data()));
+    std::vector<Result> ret;
+    for(int i = 0; i < n; ++i) ret.push_back(makeResult(seq ? seq[i] : i, r[i]));
+    return ret;
+  }
+
+  const Trajectory& trajectory(int s) const { return _trajectories.at((size_t) s); }
+  int numPointsAtLevel(int s, int level = -1) const
+  {
+    int n = 0;
+    _dev->check(bpvo_hip_seq_num_points_at_level(_dev->ctx(), s, level, &n));
+    return n;
+  }
+  /* the next frame of sequence s starts it again (a first frame: Result::keyFramingReason == KeyFramingReason::kFirstFrame) */
+  void reset(int s)
+  {
+    _dev->check(bpvo_hip_seq_reset(_dev->ctx(), s));
+    _trajectories.at((size_t) s)._poses.clear();
+  }
+  void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  double getOption(const std::string& name) const { return _dev->getOption(name); }
+
+ private:
+  Result makeResult(int s, const bpvo_hip_result& r)
+  {
+    Result ret;
+    std::memcpy(ret.pose.data(), r.pose, sizeof(r.pose));
+    std::memcpy(ret.covariance.data(), r.covariance, sizeof(r.covariance));
+    for(int i = 0; i < r.numLevels; ++i) ret.optimizerStatistics.push_back(OptimizerStatistics(r.optimizerStatistics[i]));
+    ret.isKeyFrame = r.isKeyFrame != 0;
+    ret.keyFramingReason = static_cast<KeyFramingReason>(r.keyFramingReason);
+    if(r.hasPointCloud) {
+      size_t n = 0;
+      _dev->check(bpvo_hip_seq_get_point_cloud(_dev->ctx(), s, nullptr, &n, nullptr));
+      ret.pointCloud.reset(new PointCloud);
+      ret.pointCloud->points().resize(n);
+      _dev->check(bpvo_hip_seq_get_point_cloud(_dev->ctx(), s, ret.pointCloud->points().data(), &n, ret.pointCloud->pose().data()));
+    }
+    int nt = 0;
+    _dev->check(bpvo_hip_seq_trajectory_size(_dev->ctx(), s, &nt));
+    Trajectory& t = _trajectories.at((size_t) s);
+    t._poses.resize(nt);
+    if(nt) _dev->check(bpvo_hip_seq_get_trajectory(_dev->ctx(), s, t._poses[0].data()));
+    return ret;
+  }
+  std::shared_ptr<detail::Device> _dev;
+  std::vector<Trajectory> _trajectories;
 };
 
 }  // namespace bpvo
