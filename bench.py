@@ -17,6 +17,12 @@ Launch: `python bench.py` (1 GPU), `python bench.py --gpus N` (this process star
 touches the GPU, and passes rank 0's line through), or the ranks started from outside:
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N`.
 Every rank checks WORLD_SIZE == --gpus; the line carries `ranks_seen` (an all-reduced count) and the RCCL version.
+
+A plain run does what the headline figure needs and nothing else: it renders the inputs, sets up, warms up, times the steps,
+writes --dump-outputs if asked, and prints the line.  `--full` adds everything that takes runs of its own: the single-lane pass
+behind `kernels` and the two rooflines, the CPU baseline (`cpu_baseline`, `pose_vs_cpu`), the other configurations and the
+config-5 shards (`other_configs`, `config5_shards`, `single_pair`, `projected_strong_scaling`), and the full record as a second
+JSON line on stderr (also written to --details FILE).
 """
 from __future__ import annotations
 
@@ -32,7 +38,7 @@ if ROOT not in sys.path:
 
 import numpy as np  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak
 
 
 def parse_args():
@@ -55,13 +61,16 @@ def parse_args():
                     help="default = AlgorithmParameters() (1e-7 / 1e-6 / 1e-8); timing = the reference's conf/perf_*.cfg (1e-6 / 1e-4 / 1e-6)")
     ap.add_argument("--fixed-iters", type=int, default=0,
                     help="throughput mode: tolerances 0 and maxIterations=K (K+2 linearisations per level); 0 = converge")
-    ap.add_argument("--cpu-pairs", type=int, default=40, help="bounded sample for the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (single-lane kernel pass and rooflines, CPU baseline, other configurations)")
+    ap.add_argument("--details", default="", metavar="FILE", help="with --full: write the full record (the stderr JSON line) to FILE as well")
+    ap.add_argument("--cpu-pairs", type=int, default=40, help="bounded sample for the CPU baseline (0 = skip); --full only")
     ap.add_argument("--no-profile", action="store_true", help="do not record HIP events at all")
     ap.add_argument("--profile-all", action="store_true", help="HIP events around every kernel (diagnostics, slower)")
     ap.add_argument("--gen-workers", type=int, default=0)
     ap.add_argument("--other-configs", type=int, default=256,
                     help="pairs per batch for the extra lines of BASELINE.json's other single-GPU configs (640x480 intensity/Huber, "
-                         "640x480 bit-planes/Tukey) and the B = 1 latency of the headline config; 0 = skip; N = 1 only")
+                         "640x480 bit-planes/Tukey) and the B = 1 latency of the headline config; 0 = skip; N = 1 and --full only")
     ap.add_argument("--input-cache", default="", help="directory holding the rendered synthetic inputs of this exact shard; "
                     "written on first use (lets the rocprofv3 runs skip the CPU rendering, which must not fork under the profiler)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -198,7 +207,7 @@ def main():
     # inputs of the extra configs are rendered now as well: the fork pool must not run after the GPU is initialised
     other_batch = None
     seq640 = None
-    if world == 1 and args.other_configs > 0 and (args.rows, args.cols) == (376, 1241):
+    if args.full and world == 1 and args.other_configs > 0 and (args.rows, args.cols) == (376, 1241):
         other_batch = synth.make_batch(480, 640, args.other_configs, first_index=0, workers=workers)
         seq640 = synth.make_sequence(480, 640, 25, index=21, step_rot=0.004, step_trans=0.03)
         # rectified pairs for the stereo front-end lines (rendered now: no CPU rendering after the GPU is up)
@@ -283,11 +292,11 @@ def main():
     kstats = all_kstats if not args.no_profile else {}
     # The timed steps run the batch on several estimation lanes (streams; three for bit-planes, two for intensity): faster, but the per-launch durations of one lane then
     # include time shared with the other lane's kernels.  The roofline of warp_residual is therefore taken from ONE more,
-    # untimed step of the same workload on a single lane (same kernels, same launches, HIP events on the library's stream);
-    # what the events saw inside the timed region is reported next to it (roofline_timed_region).
+    # untimed step of the same workload on a single lane (same kernels, same launches, HIP events on the library's stream), run with
+    # --full only; what the events saw inside the timed region is reported next to it (roofline_timed_region), in a plain run too.
     kstats_1lane = {}
     fused_1lane = (0, 0)
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         ctx.set_max_lanes(1)
         ctx.profiling(2 if args.profile_all else 3)     # 3: every warp_residual and irls_reduce launch, so that the averages are rocprofv3's
         ctx.batch_run_device(P, d_images.data_ptr(), d_disps.data_ptr())
@@ -455,7 +464,7 @@ def main():
 
         cpu = None
         pose_vs_cpu = None
-        if args.cpu_pairs > 0 and world == 1:      # the CPU leg runs at N = 1 only (the other ranks would wait for it)
+        if args.full and args.cpu_pairs > 0 and world == 1:      # the CPU leg runs at N = 1 only (the other ranks would wait for it)
             cpu = cpu_baseline(args, batch, args.cpu_pairs)
             # pose agreement of the GPU path with the CPU path on the pairs both ran (BASELINE.json: "pose RMSE vs ref")
             cp = cpu.pop("_poses").astype(np.float64)
@@ -537,10 +546,10 @@ def main():
             "setup": {"synth_seconds": t_gen, "gen_workers": workers},
             "ranks": diags,
         }
-        # ONE JSON line on stdout (the contract), short enough (< 7 KB) that a tail of the output holds all of it: the contract's keys, `roofline`
-        # (warp + residual, the kernel north_star names, with the dominant kernel's figures inside), `cpu_baseline`, what every rank did, the
-        # config-5 shards, the single pair, the other configurations as one number each.  The full record (kernel tables, notes, every
-        # other_configs line) goes to stderr as a second JSON line and to gpurun_out/bench_details.json.
+        # ONE JSON line on stdout (the contract), short enough (< 7 KB) that a tail of the output holds all of it: the contract's keys, the
+        # timed region's figures and what every rank did; with --full also `roofline` (warp + residual, the kernel north_star names, with the
+        # dominant kernel's figures inside), `cpu_baseline`, the config-5 shards, the single pair, the other configurations as one number each.
+        # With --full the full record (kernel tables, notes, every other_configs line) goes to stderr as a second JSON line (and to --details).
         def rnd(x, nd=4):
             if isinstance(x, float):
                 return float(("%." + str(nd) + "g") % x)
@@ -557,21 +566,22 @@ def main():
         head["fused_path"] = {k: out["fused_path"][k] for k in ("points", "of")}
         if roofline_timed is not None:
             head["roofline_timed_region"] = {k: roofline_timed[k] for k in ("achieved", "frac", "avg_launch_ms")}
-        head["kernels"] = {n_: {"launches": v["launches"], "avg_ms": v["avg_ms"], "algorithmic_GBps": v["algorithmic_GBps"]} for n_, v in kernels_1lane.items()}
-        if roofline is not None:
-            rl = dict(roofline)
-            rl["measured"] = "HIP events around every launch, one untimed single-lane step"
-            head["roofline"] = rl
-        else:
-            head["roofline"] = None
-        if cpu is not None:
-            head["cpu_baseline"] = {"value": cpu["value"], "unit": cpu["unit"], "cores": cpu["cores"], "kind": cpu["kind"],
-                                    "sample": f"{min(args.cpu_pairs, P)} pairs of the same workload, oracle/ restatement, 1 thread",
-                                    "all_cores": {"value": cpu["all_cores"]["value"], "cores": cpu["all_cores"]["cores"]}}
-        else:
-            head["cpu_baseline"] = None
-        if pose_vs_cpu is not None:
-            head["pose_vs_cpu"] = {k: pose_vs_cpu[k] for k in ("pairs", "rot_max_rad", "trans_max_m")}
+        if args.full:
+            head["kernels"] = {n_: {"launches": v["launches"], "avg_ms": v["avg_ms"], "algorithmic_GBps": v["algorithmic_GBps"]} for n_, v in kernels_1lane.items()}
+            if roofline is not None:
+                rl = dict(roofline)
+                rl["measured"] = "HIP events around every launch, one untimed single-lane step"
+                head["roofline"] = rl
+            else:
+                head["roofline"] = None
+            if cpu is not None:
+                head["cpu_baseline"] = {"value": cpu["value"], "unit": cpu["unit"], "cores": cpu["cores"], "kind": cpu["kind"],
+                                        "sample": f"{min(args.cpu_pairs, P)} pairs of the same workload, oracle/ restatement, 1 thread",
+                                        "all_cores": {"value": cpu["all_cores"]["value"], "cores": cpu["all_cores"]["cores"]}}
+            else:
+                head["cpu_baseline"] = None
+            if pose_vs_cpu is not None:
+                head["pose_vs_cpu"] = {k: pose_vs_cpu[k] for k in ("pairs", "rot_max_rad", "trans_max_m")}
         ms = [d["ms_per_step"] for d in diags]
         head["ranks"] = {"ms_per_step_min": min(ms), "ms_per_step_max": max(ms), "slowest_rank": int(np.argmax(ms)), "dist_backend": out["dist_backend"],
                          "ranks_seen": ranks_seen, "rccl_version": rccl_version,
@@ -598,16 +608,14 @@ def main():
                     brief[k.replace("the parameters of ", "")] = e
             head["config5_shards"] = shards
             head["other_configs"] = brief
-        head["details"] = "second JSON line on stderr; gpurun_out/bench_details.json"
-        line = json.dumps(rnd(head))
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_details.json"), "w") as f:
-                f.write(json.dumps(out) + "\n")
-        except OSError:
-            pass
-        print(json.dumps({"details": out}), file=sys.stderr, flush=True)
-        print(line, flush=True)
+        if args.full:
+            head["details"] = "second JSON line on stderr" + (f"; {args.details}" if args.details else "")
+            if args.details:
+                os.makedirs(os.path.dirname(os.path.abspath(args.details)), exist_ok=True)
+                with open(args.details, "w") as f:
+                    f.write(json.dumps(out) + "\n")
+            print(json.dumps({"details": out}), file=sys.stderr, flush=True)
+        print(json.dumps(rnd(head)), flush=True)
 
     if ctx.h:
         ctx.close()

@@ -18,10 +18,10 @@ cd /tmp && export TMPDIR=/tmp
 # the GPU before python starts), and the profiled runs read them back from /tmp
 CACHE=/tmp/bpvo_bench_inputs
 timeout 300 python3 "$R/bench.py" --steps 1 --warmup 0 --cpu-pairs 0 --other-configs 0 --no-profile --input-cache $CACHE > /dev/null 2> "$O/cache_default.err"; echo "inputs rc=$?"
-timeout 400 rocprofv3 --kernel-trace --stats -d "$O/trace" -- python3 "$R/bench.py" --steps 3 --warmup 1 --cpu-pairs 0 --other-configs 0 --gen-workers 1 --input-cache $CACHE \
+timeout 400 rocprofv3 --kernel-trace --stats -d "$O/trace" -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --cpu-pairs 0 --other-configs 0 --gen-workers 1 --input-cache $CACHE \
     > "$O/trace_bench.json" 2> "$O/trace.err"; echo "trace rc=$?"
 export BPVO_HIP_OPTIONS=lanes=1
-timeout 400 rocprofv3 --kernel-trace --stats -d "$O/trace1" -- python3 "$R/bench.py" --steps 3 --warmup 1 --cpu-pairs 0 --other-configs 0 --gen-workers 1 --input-cache $CACHE \
+timeout 400 rocprofv3 --kernel-trace --stats -d "$O/trace1" -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --cpu-pairs 0 --other-configs 0 --gen-workers 1 --input-cache $CACHE \
     > "$O/trace1_bench.json" 2> "$O/trace1.err"; echo "trace (one lane) rc=$?"
 i=0
 for CNT in "FETCH_SIZE" "WRITE_SIZE" \

@@ -24,7 +24,7 @@ for sub, suffix, env in (("trace", "", ""), ("trace1", "_1lane", "BPVO_HIP_OPTIO
     if not db:
         continue
     rows = list(db.execute("select name,total_calls,total_duration,average,percentage from top_kernels"))
-    lines = [env + "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --cpu-pairs 0 --other-configs 0 --gen-workers 1 --input-cache /tmp/bpvo_bench_inputs   (durations in us)",
+    lines = [env + "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 3 --warmup 1 --cpu-pairs 0 --other-configs 0 --gen-workers 1 --input-cache <dir>   (durations in us)",
              "%-100s %8s %16s %12s %7s" % ("kernel", "calls", "total_us", "avg_us", "%")]
     for r in rows:
         lines.append("%-100s %8d %16.1f %12.2f %7.2f" % (r[0][:100], r[1], r[2], r[3], r[4]))

@@ -10,7 +10,7 @@ O=/tmp/bpvo_interp_$TAG
 rm -rf "$O"; mkdir -p "$O" "$R/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
 CACHE=/tmp/bpvo_bench_inputs_interp
-ARGS="--pairs 256 --interp cubic --steps 2 --warmup 1 --cpu-pairs 0 --other-configs 0"
+ARGS="--full --pairs 256 --interp cubic --steps 2 --warmup 1 --cpu-pairs 0 --other-configs 0"
 export BPVO_HIP_OPTIONS=lanes=1
 timeout 300 python3 "$R/bench.py" $ARGS --no-profile --input-cache $CACHE > /dev/null 2> "$O/cache.err"; echo "inputs rc=$?"
 timeout 400 rocprofv3 --kernel-trace --stats -d "$O/trace" -- python3 "$R/bench.py" $ARGS --gen-workers 1 --input-cache $CACHE > "$O/trace_bench.json" 2> "$O/trace.err"; echo "trace rc=$?"

@@ -21,7 +21,7 @@ try:
     bench = json.loads([l for l in open(os.path.join(src, "trace_bench.json")) if l.startswith("{")][-1])
 except Exception as e:  # noqa: BLE001
     print("(no bench line: %s)" % e)
-print("BPVO_HIP_OPTIONS=lanes=1 rocprofv3 --kernel-trace --stats -- python3 bench.py --pairs 256 --interp cubic --steps 2 --warmup 1 --cpu-pairs 0 --other-configs 0   (durations in us)")
+print("BPVO_HIP_OPTIONS=lanes=1 rocprofv3 --kernel-trace --stats -- python3 bench.py --full --pairs 256 --interp cubic --steps 2 --warmup 1 --cpu-pairs 0 --other-configs 0   (durations in us)")
 db = db_of("trace")
 if db:
     print("%-104s %8s %14s %10s %7s" % ("kernel", "calls", "total_us", "avg_us", "%"))

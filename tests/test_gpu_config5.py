@@ -294,6 +294,30 @@ def test_bench_gpus_flag_starts_the_ranks_itself(tmp_path):
     assert r.returncode != 0 and "--gpus 1 but the launcher started 2" in (r.stdout + r.stderr)
 
 
+def test_bench_plain_run_and_full(tmp_path):
+    """A plain run prints the headline and the timed region's figures only; --full adds the single-lane kernel pass, the rooflines, the
+    CPU baseline and the full record on stderr (and in --details).  Both time the same steps on the same inputs: the dumped outputs agree."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--pairs", "3",
+            "--cpu-pairs", "2", "--other-configs", "0", "--gen-workers", "2"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    runs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--details", str(tmp_path / "details.json")])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / mode)], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        runs[mode] = (json.loads(line_of(r.stdout)), [ln for ln in r.stderr.splitlines() if ln.startswith('{"details"')])
+    (plain, plain_err), (full, full_err) = runs["plain"], runs["full"]
+    for out in (plain, full):
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and out["higher_is_better"] is True and out["steps"] == 1 and out["warmup"] == 0
+        assert out["unit"] == "GN iterations/s" and out["config"]["pairs_per_gpu"] == 3 and out["ranks"]["per_rank"][0]["gave_up"] == 0
+    assert not plain_err and not {"kernels", "roofline", "cpu_baseline", "pose_vs_cpu", "details"} & set(plain)
+    assert full["kernels"]["pyramid"]["launches"] > 0 and "roofline" in full      # (3 pairs take the team kernel: no warp_residual launches)
+    assert full["cpu_baseline"]["value"] > 0 and full["pose_vs_cpu"]["pairs"] == 2
+    assert len(full_err) == 1 and json.loads(full_err[0])["details"] == json.load(open(tmp_path / "details.json"))
+    assert plain["gn_iterations_per_step"] == full["gn_iterations_per_step"]
+    for name in ("poses", "num_iterations", "status"):
+        assert np.array_equal(np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy")))
+
+
 # ---- bounded soak (tests/tools/soak_parity.py in the suite) ----------------------------------------------------------
 @pytest.mark.parametrize("rows,cols,descriptor,loss,n", [pytest.param(376, 1241, "bitplanes", "tukey", 64, id="kitti-bitplanes-tukey-64"),
                                                          pytest.param(480, 640, "intensity", "huber", 64, id="640x480-intensity-huber-64")])
