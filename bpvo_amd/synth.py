@@ -8,6 +8,11 @@ poses.  Frame A sits at the identity pose and also gets its disparity map ``b*fx
 Calibrations: 640x480 -> fx=fy=615, c=(320,240), b=0.1 (reference: apps/vo_example.cc:60-61);
 1241x376 -> KITTI seq-00 style fx=fy=718.856, c=(607.1928,185.2157), b=0.5372.
 Everything is seeded: seed = 1000 + pair index.
+
+scene="layered" (every generator takes it; the default "plane" is the scene above, unchanged): a slanted background plane behind three
+or four bounded planar patches at their own depths, ray-cast the same way (nearest hit inside a layer's bounds), each layer with its own
+texture and brightness offset.  Its disparity maps carry holes (value-noise blobs and a band along every depth edge, filled with 0, -1
+and 600), frame B carries sensor noise, and the pair also returns depthA, the layer label maps and the occlusion mask of A.
 """
 from __future__ import annotations
 
@@ -114,13 +119,180 @@ def _render(K, b, rows, cols, T_cam_from_A, seed, z0, plane):
     return img, disp
 
 
-def make_pair(rows: int, cols: int, index: int = 0, max_rot: float = 0.01, max_trans: float = 0.05):
-    """One synthetic pair. Returns dict(K, b, imgA, dispA, imgB, dispB, T_gt (float64 4x4), seed)."""
+# ---- the layered scene ---------------------------------------------------------------------------------------------------------------
+HOLE_VALUES = (0.0, -1.0, 600.0)          # what a hole of a layered disparity map holds (600 > maxValidDisparity = 512)
+NOISE_SIGMA = 2.0                         # grey levels of sensor noise on frame B of a layered pair
+
+
+def default_disp_range(rows: int, cols: int):
+    """Front-surface disparities (px) of the layered scene: 15..96 at 1241x376 (below the stereo tests' 128), 3..30 at 640x480, in
+    proportion to the width elsewhere."""
+    if (rows, cols) == (376, 1241):
+        return (15.0, 96.0)
+    s = cols / 640.0
+    return (3.0 * s, 30.0 * s)
+
+
+def _layered_geometry(K, b, rows, cols, seed, disp_range):
+    """The layers of one layered scene, drawn from a stream of their own (the pose stream stays make_pair's).  Layer 0 is the background
+    plane Z = z + a X + b Y over the whole view; layers 1.. are patches Z = z + a (X - X0) + b (Y - Y0), bounded by a rectangle
+    (|X - X0| <= hx, |Y - Y0| <= hy) or a disc ((X - X0)^2 + (Y - Y0)^2 <= r^2) in their own coordinates.  Patches 1 and 2 overlap in A."""
+    rng = np.random.default_rng([seed, 0x1A7E])
+    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    bfx = b * fx
+    lo, hi = disp_range
+    layers = []
+    # background: its farthest point over the view (A's corners) at disparity lo
+    a, bb = rng.choice([-1.0, 1.0]) * rng.uniform(0.15, 0.3), rng.uniform(-0.1, 0.1)
+    xs = np.array([-cx, cols - 1 - cx]) / fx
+    ys = np.array([-cy, rows - 1 - cy]) / fy
+    den_min = min(1.0 - a * x - bb * y for x in xs for y in ys)
+    layers.append(dict(z=bfx / lo * den_min, a=a, b=bb, X0=0.0, Y0=0.0, shape="all"))
+    n_patch = int(rng.integers(3, 5))
+    # centre disparities: the nearest patch at ~0.88 hi, the others spread (log-uniformly) down to ~2.2 lo
+    dl = np.exp(np.linspace(np.log(0.88 * hi), np.log(2.2 * lo), n_patch)) * rng.uniform(0.95, 1.05, n_patch)
+    dl = dl[rng.permutation(n_patch)]
+    area = rows * cols
+    u1 = rng.uniform(0.3, 0.45) * cols
+    for k in range(n_patch):
+        frac = rng.uniform(0.08, 0.16)                     # share of frame A the patch's bounds would cover unoccluded
+        if k == 0:
+            uc, vc = u1, rng.uniform(0.4, 0.6) * rows
+        elif k == 1:                                      # overlaps patch 1: centre shifted by about its half width
+            uc, vc = layers[1]["uc"] + rng.choice([-1.0, 1.0]) * rng.uniform(0.12, 0.18) * cols, rng.uniform(0.3, 0.7) * rows
+        else:
+            uc, vc = rng.uniform(0.12, 0.88) * cols, rng.uniform(0.3, 0.7) * rows
+        z = bfx / dl[k]
+        X0, Y0 = (uc - cx) / fx * z, (vc - cy) / fy * z
+        pa, pb = rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3)
+        if rng.uniform() < 0.5:
+            r_px = np.sqrt(frac * area / np.pi)
+            geo = dict(shape="disc", r=r_px * z / fx)
+        else:
+            aspect = rng.uniform(0.6, 1.6)
+            h_px = min(np.sqrt(frac * area / aspect), 0.8 * rows)
+            w_px = frac * area / h_px
+            geo = dict(shape="rect", hx=0.5 * w_px * z / fx, hy=0.5 * h_px * z / fy)
+        layers.append(dict(z=z, a=pa, b=pb, X0=X0, Y0=Y0, uc=uc, **geo))
+    offsets = rng.permutation(np.array([-40.0, -20.0, 0.0, 20.0, 40.0])[: n_patch + 1])
+    for k, L in enumerate(layers):
+        L["offset"] = float(offsets[k])
+        L["tex_seed"] = 100000 + 16 * seed + k
+    return layers
+
+
+def _cast(K, layers, T_cam_from_A, xs, ys):
+    """Cast the rays through pixels (xs, ys) of a camera with X_cam = T * X_A: depth of the nearest hit (inf where none), its layer label
+    (-1 where none) and the hit in frame-A coordinates."""
+    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    Tinv = np.linalg.inv(T_cam_from_A)
+    R, t = Tinv[:3, :3], Tinv[:3, 3]
+    d_cam = np.stack([(xs - cx) / fx, (ys - cy) / fy, np.ones_like(xs)], axis=-1)
+    d_A = d_cam @ R.T
+    depth = np.full(xs.shape, np.inf)
+    label = np.full(xs.shape, -1, np.int8)
+    for k, L in enumerate(layers):
+        n = np.array([-L["a"], -L["b"], 1.0])             # n . X_A = z - a X0 - b Y0
+        c = L["z"] - L["a"] * L["X0"] - L["b"] * L["Y0"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s = (c - float(n @ t)) / (d_A @ n)
+        X = s[..., None] * d_A + t
+        inside = s > 0
+        if L["shape"] == "disc":
+            inside &= (X[..., 0] - L["X0"]) ** 2 + (X[..., 1] - L["Y0"]) ** 2 <= L["r"] ** 2
+        elif L["shape"] == "rect":
+            inside &= (np.abs(X[..., 0] - L["X0"]) <= L["hx"]) & (np.abs(X[..., 1] - L["Y0"]) <= L["hy"])
+        win = inside & (s < depth)
+        depth = np.where(win, s, depth)
+        label[win] = k
+    X_A = depth[..., None] * d_A + t
+    return depth, label, X_A
+
+
+def _grid(rows, cols):
+    return np.meshgrid(np.arange(cols, dtype=np.float64), np.arange(rows, dtype=np.float64))
+
+
+def _shade(K, layers, depth, label, X_A):
+    """Texture of every pixel from its own layer (texture coordinates = the hit's X, Y in frame A), plus the layer's brightness offset."""
+    fx = float(K[0, 0])
+    img = np.zeros(depth.shape)
+    for k, L in enumerate(layers):
+        m = label == k
+        if m.any():
+            img[m] = _texture(X_A[m, 0], X_A[m, 1], L["tex_seed"], L["z"] / fx) + L["offset"]
+    return img
+
+
+def _holes(disp, label, seed, salt):
+    """Punch holes into a disparity map in place: value-noise blobs (6 % of the pixels) and a 2 px band along every label change (depth
+    edge), filled with a per-pixel mix of HOLE_VALUES."""
+    rows, cols = disp.shape
+    xs, ys = _grid(rows, cols)
+    blob = _value_noise(xs, ys, 0.05 * cols, seed * 7919 + salt) + 0.35 * _value_noise(xs, ys, 0.0125 * cols, seed * 7919 + salt + 1)
+    hole = blob > np.quantile(blob, 0.94)
+    dx = label[:, 1:] != label[:, :-1]
+    dy = label[1:, :] != label[:-1, :]
+    hole[:, 1:] |= dx
+    hole[:, :-1] |= dx
+    hole[1:, :] |= dy
+    hole[:-1, :] |= dy
+    pick = np.minimum((_hash01(xs, ys, seed * 7919 + salt + 2) * 3).astype(np.int64), 2)
+    disp[hole] = np.asarray(HOLE_VALUES, np.float32)[pick[hole]]
+    return disp
+
+
+def _render_layered(K, b, rows, cols, T_cam_from_A, seed, layers, noise_stream=None, hole_salt=None):
+    """One view of a layered scene: (u8 image, f32 disparity b*fx/depth, depth, labels, hits in frame A).  noise_stream: add Gaussian
+    noise of NOISE_SIGMA grey levels from that RNG stream before rounding; hole_salt: punch holes into the disparity map."""
+    xs, ys = _grid(rows, cols)
+    depth, label, X_A = _cast(K, layers, T_cam_from_A, xs, ys)
+    assert (label >= 0).all(), "the background plane covers every view"
+    img = _shade(K, layers, depth, label, X_A)
+    if noise_stream is not None:
+        img = img + np.random.default_rng([seed, noise_stream]).normal(0.0, NOISE_SIGMA, img.shape)
+    img = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    disp = (b * float(K[0, 0]) / depth).astype(np.float32)
+    if hole_salt is not None:
+        _holes(disp, label, seed, hole_salt)
+    return img, disp, depth, label, X_A
+
+
+def _occluded(K, layers, T_gt, rows, cols, labelA, X_A):
+    """A pixel of A is occluded when its 3-D point falls outside B or is hidden there: the ray of B through the point's exact (sub-pixel)
+    projection first hits another layer."""
+    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    X_B = X_A @ T_gt[:3, :3].T + T_gt[:3, 3]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = fx * X_B[..., 0] / X_B[..., 2] + cx
+        v = fy * X_B[..., 1] / X_B[..., 2] + cy
+    inside = (X_B[..., 2] > 0) & (u >= 0) & (u <= cols - 1) & (v >= 0) & (v <= rows - 1)
+    _, lab_B, _ = _cast(K, layers, T_gt, np.where(inside, u, cx), np.where(inside, v, cy))
+    return ~inside | (lab_B != labelA)
+
+
+def _check_scene(scene):
+    if scene not in ("plane", "layered"):
+        raise ValueError(f"unknown scene {scene!r} (plane | layered)")
+
+
+def make_pair(rows: int, cols: int, index: int = 0, max_rot: float = 0.01, max_trans: float = 0.05, scene: str = "plane", disp_range=None):
+    """One synthetic pair. Returns dict(K, b, imgA, dispA, imgB, dispB, T_gt (float64 4x4), seed).  scene="layered": the layered scene
+    (same T_gt for the same index), disparity front surfaces over disp_range (default_disp_range), with holes; the dict also holds depthA
+    (float64), layerA, layerB (int8 labels, 0 = background) and occluded (bool, A's pixels whose point is hidden in B or falls outside it)."""
     seed = 1000 + int(index)
     rng = np.random.default_rng(seed)
     K, b = calibration(rows, cols)
     twist = np.concatenate([rng.uniform(-max_rot, max_rot, 3), rng.uniform(-max_trans, max_trans, 3)])
     T_gt = twist_to_matrix(twist)
+    if scene == "layered":
+        layers = _layered_geometry(K, b, rows, cols, seed, disp_range or default_disp_range(rows, cols))
+        imgA, dispA, depthA, layerA, X_A = _render_layered(K, b, rows, cols, np.eye(4), seed, layers, hole_salt=11)
+        imgB, dispB, _, layerB, _ = _render_layered(K, b, rows, cols, T_gt, seed, layers, noise_stream=1, hole_salt=23)
+        occluded = _occluded(K, layers, T_gt, rows, cols, layerA, X_A)
+        return dict(K=K, b=b, imgA=imgA, dispA=dispA, imgB=imgB, dispB=dispB, T_gt=T_gt, seed=seed, twist=twist, depthA=depthA,
+                    layerA=layerA, layerB=layerB, occluded=occluded)
+    _check_scene(scene)
     z0 = 10.0
     plane = (0.1, -0.15)
     imgA, dispA = _render(K, b, rows, cols, np.eye(4), seed, z0, plane)
@@ -128,11 +300,22 @@ def make_pair(rows: int, cols: int, index: int = 0, max_rot: float = 0.01, max_t
     return dict(K=K, b=b, imgA=imgA, dispA=dispA, imgB=imgB, dispB=dispB, T_gt=T_gt, seed=seed, twist=twist)
 
 
-def make_stereo_pair(rows: int, cols: int, index: int = 0, z0: float = 10.0):
+def make_stereo_pair(rows: int, cols: int, index: int = 0, z0: float = 10.0, scene: str = "plane", disp_range=None):
     """A rectified stereo pair of the plane scene: left image, right image (camera shifted by the baseline along +x), and the
-    true disparity of the left image.  Returns dict(K, b, left, right, disp)."""
+    true disparity of the left image.  Returns dict(K, b, left, right, disp).  scene="layered": the layered scene of make_pair (z0 is
+    not used; disp_range sets the depths), noise on the right image, disp without holes, plus layer (left labels) and occluded (left
+    pixels hidden from the right camera or outside its view)."""
     seed = 1000 + int(index)
     K, b = calibration(rows, cols)
+    if scene == "layered":
+        layers = _layered_geometry(K, b, rows, cols, seed, disp_range or default_disp_range(rows, cols))
+        T_right = np.eye(4)
+        T_right[0, 3] = -b
+        left, disp, _, layer, X_A = _render_layered(K, b, rows, cols, np.eye(4), seed, layers)
+        right, _, _, _, _ = _render_layered(K, b, rows, cols, T_right, seed, layers, noise_stream=1)
+        occluded = _occluded(K, layers, T_right, rows, cols, layer, X_A)
+        return dict(K=K, b=b, left=left, right=right, disp=disp, seed=seed, layer=layer, occluded=occluded)
+    _check_scene(scene)
     plane = (0.1, -0.15)
     left, disp = _render(K, b, rows, cols, np.eye(4), seed, z0, plane)
     T_right = np.eye(4)
@@ -141,15 +324,25 @@ def make_stereo_pair(rows: int, cols: int, index: int = 0, z0: float = 10.0):
     return dict(K=K, b=b, left=left, right=right, disp=disp, seed=seed)
 
 
-def make_sequence(rows: int, cols: int, n_frames: int, index: int = 0, step_rot: float = 0.004, step_trans: float = 0.03):
-    """A short camera trajectory over the same plane for addFrame tests: list of (img, disp) and absolute poses."""
+def make_sequence(rows: int, cols: int, n_frames: int, index: int = 0, step_rot: float = 0.004, step_trans: float = 0.03, scene: str = "plane",
+                  disp_range=None):
+    """A short camera trajectory over the same plane for addFrame tests: list of (img, disp) and absolute poses.  scene="layered": over the
+    layered scene of make_pair instead (the same trajectory), every disparity map with holes of its own, noise on every frame after the
+    first."""
     seed = 1000 + int(index)
     rng = np.random.default_rng(seed)
     K, b = calibration(rows, cols)
+    if scene == "layered":
+        layers = _layered_geometry(K, b, rows, cols, seed, disp_range or default_disp_range(rows, cols))
+    else:
+        _check_scene(scene)
     T = np.eye(4)
     frames, poses = [], []
-    for _ in range(n_frames):
-        img, disp = _render(K, b, rows, cols, T, seed, 10.0, (0.1, -0.15))
+    for f in range(n_frames):
+        if scene == "layered":
+            img, disp, _, _, _ = _render_layered(K, b, rows, cols, T, seed, layers, noise_stream=(f if f else None), hole_salt=11 + 12 * f)
+        else:
+            img, disp = _render(K, b, rows, cols, T, seed, 10.0, (0.1, -0.15))
         frames.append((img, disp))
         poses.append(T.copy())
         tw = np.concatenate([rng.uniform(-step_rot, step_rot, 3), rng.uniform(-step_trans, step_trans, 3)])
@@ -172,20 +365,21 @@ def make_stereo_sequence(rows: int, cols: int, n_frames: int, index: int = 0, st
 
 
 def _pair_for_batch(args):
-    rows, cols, idx = args
-    d = make_pair(rows, cols, idx)
+    rows, cols, idx, scene = args
+    d = make_pair(rows, cols, idx, scene=scene)
     return d["imgA"], d["imgB"], d["dispA"], d["dispB"], d["T_gt"]
 
 
-def make_batch(rows: int, cols: int, n_pairs: int, first_index: int = 0, workers: int = 1):
+def make_batch(rows: int, cols: int, n_pairs: int, first_index: int = 0, workers: int = 1, scene: str = "plane"):
     """n_pairs pairs packed as the batch API wants them: images [2n, R, W] = A0,B0,A1,B1,..., disparities likewise.
 
-    workers > 1 renders the pairs in a process pool (fork; call it before anything initialises the GPU)."""
+    workers > 1 renders the pairs in a process pool (fork; call it before anything initialises the GPU).  scene: as make_pair's."""
+    _check_scene(scene)
     imgs = np.empty((2 * n_pairs, rows, cols), dtype=np.uint8)
     disps = np.empty((2 * n_pairs, rows, cols), dtype=np.float32)
     T_gt = np.empty((n_pairs, 4, 4), dtype=np.float64)
     K, b = calibration(rows, cols)
-    jobs = [(rows, cols, first_index + p) for p in range(n_pairs)]
+    jobs = [(rows, cols, first_index + p, scene) for p in range(n_pairs)]
     if workers > 1 and n_pairs > 1:
         import multiprocessing as mp
         with mp.get_context("fork").Pool(min(workers, n_pairs)) as pool:

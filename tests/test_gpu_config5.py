@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 from bpvo_amd import capi, synth
-from util import ROT_TOL, TRANS_TOL, make_params, pose_error
+from util import ROT_TOL, TRANS_TOL, make_params, oracle_pairs as _oracle_pairs, pose_error
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,28 +29,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS, COLS, LEVELS = 376, 1241, 4
 SHARD = 128            # pairs per GPU of config 5 at G = 8
 N_ORACLE = 32          # pairs of the shard also run through the CPU oracle (every 4th)
-
-
-def _oracle_pairs(orc, batch, picks, p_kw, trace=False, chunks=1, f64=0):
-    """The picked pairs of `batch`, one at a time through the oracle.  chunks = 1: the serial sums of the reference's default build;
-    chunks = n: the normal equations summed as n contiguous chunks, the decomposition of the reference's tbb::parallel_reduce
-    (WITH_TBB, bpvo/linear_system_builder.cc:91-131,233-237); f64: the same terms accumulated in double (an instrument)."""
-    out = []
-    p = make_params(orc, **p_kw)
-    ctx = orc.create(batch["K"], batch["b"], ROWS, COLS, p, n_frames=2, n_pairs=1)
-    ctx.call("set_num_threads", chunks)
-    ctx.call("set_reduction", f64)
-    for k in picks:
-        ctx.frame_set_data(0, batch["images"][2 * k], batch["disparities"][2 * k])
-        ctx.frame_set_template(0)
-        ctx.frame_set_data(1, batch["images"][2 * k + 1], batch["disparities"][2 * k + 1])
-        if trace:
-            T, st, rec = ctx.estimate_pose_trace(0, 0, 1)
-        else:
-            (T, st), rec = ctx.estimate_pose(0, 0, 1), None
-        out.append(dict(T=T, its=[s["numIterations"] for s in st], status=[s["status"] for s in st], trace=rec))
-    ctx.close()
-    return out
 
 
 @pytest.fixture(scope="module")

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from bpvo_amd import capi, synth
-from util import ROT_TOL, bits_equal, make_params, pose_error, setup_pair, trans_tol, set_options
+from util import ROT_TOL, assert_trace_reproduced, both, bits_equal, make_params, normal_equations_f64, perturbed_pose as _perturbed_pose, pose_error, setup_pair, trans_tol, set_options
 
 pytestmark = pytest.mark.gpu
 
@@ -19,12 +19,6 @@ SIZES = [
     pytest.param(376, 1241, 4, id="kitti-1241x376-L4"),
     pytest.param(480, 640, 4, id="640x480-L4"),
 ]
-
-
-def both(hip, orc, rows, cols, levels, **kw):
-    ch, d, _ = setup_pair(hip, rows, cols, levels=levels, **kw)
-    co, _, _ = setup_pair(orc, rows, cols, levels=levels, **kw)
-    return ch, co, d
 
 
 @pytest.mark.parametrize("rows,cols,levels", SIZES)
@@ -54,21 +48,6 @@ def test_template_bit_exact(hip, orc, rows, cols, levels, descriptor):
         assert bits_equal(ch.get_pixels(0, l), co.get_pixels(0, l)), f"pixels level {l}"
         Jh, Jo = ch.get_jacobians(0, l), co.get_jacobians(0, l)
         assert bits_equal(Jh, Jo), f"jacobians level {l}: max |d| = {np.abs(Jh - Jo).max()}"
-
-
-def normal_equations_f64(J, r, w, valid, C):
-    """J^T W J, J^T W r, sqrt(sum w r^2) in float64 from the reference-layout arrays ([C*N][6], [C*N], [C*N], [N])."""
-    J = np.asarray(J, np.float64).reshape(-1, 6)
-    r = np.asarray(r, np.float64).reshape(-1)
-    wv = np.asarray(w, np.float64).reshape(-1) * np.tile(np.asarray(valid, np.float64), C)
-    H = (J * wv[:, None]).T @ J
-    G = J.T @ (wv * r)
-    return H, G, float(np.sqrt(np.sum(wv * r * r)))
-
-
-def _perturbed_pose(scale):
-    tw = np.array([0.004, -0.003, 0.002, 0.02, -0.015, 0.03]) * scale
-    return synth.twist_to_matrix(tw).astype(np.float32)
 
 
 @pytest.mark.parametrize("rows,cols,levels", SIZES)
@@ -125,29 +104,7 @@ def test_estimate_pose_parity(hip, orc, rows, cols, levels, descriptor, loss):
     # against ground truth both must be reasonable (sanity of the synthetic scene, not a parity bar)
     rg, tg = pose_error(Th, d["T_gt"])
     assert rg < 1e-2 and tg < 1e-1, (rg, tg)
-    # per-iteration trace: linearise the HIP path at the poses the oracle visited.  The robust scale of a later linearisation of a level
-    # depends on the estimator's freeze history (Q6), which a pose alone does not reproduce — so the oracle's OWN sigma of that
-    # linearisation is handed to the HIP side (bpvo_hip_linearize_at_scale): valid count, H, G and f_norm are then compared at
-    # EVERY sampled pose; on the first linearisation of each level sigma itself is estimated on both sides and must be equal.
-    step = max(1, len(trace) // 24)
-    first_of_level = {int(l): int(np.flatnonzero(trace[:, 67] == l)[0]) for l in np.unique(trace[:, 67])}
-    picks = sorted(set(range(0, len(trace), step)) | set(first_of_level.values()))
-    for i in picks:
-        rec = trace[i]
-        T = rec[:16].reshape(4, 4)
-        level = int(rec[67])
-        if i == first_of_level[level]:
-            a = ch.linearize(0, 0, 1, level, T, reset_scale=True)
-            assert a["sigma"] == rec[59], (level, a["sigma"], rec[59])          # exact median, both sides from sigma = 1
-        else:
-            a = ch.linearize_at_scale(0, 0, 1, level, T, float(rec[59]))
-        assert a["num_valid"] == int(rec[60]), (level, i, a["num_valid"], rec[60])
-        Ho, Go = rec[16:52].reshape(6, 6), rec[52:58]
-        scale = np.abs(Ho).max()
-        # the oracle sums serially in f32 (within 2e-4 of an f64 evaluation, test_linearize_parity); the GPU within 4e-6
-        assert abs(a["f_norm"] - rec[58]) <= 1e-3 * max(rec[58], 1e-6), (level, i, a["f_norm"], rec[58])
-        assert np.abs(a["H"] - Ho).max() <= 2e-4 * scale, (level, i)
-        assert np.abs(a["G"] - Go).max() <= 2e-4 * max(np.abs(Go).max(), 1e-3 * scale), (level, i)
+    assert_trace_reproduced(ch, trace)
 
 
 def test_estimate_pose_nonzero_workspace_and_init(hip, orc):

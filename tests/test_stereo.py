@@ -670,3 +670,49 @@ def test_hip_sgbm_reference_constructor_call_batch_errors_and_add_frame(hip, orc
         ra = a.add_frame_stereo(left, right, sps)
         rc = c.add_frame(left, orc_sgbm(orc, left, right, ndisp=32, wsz=7))
         assert np.array_equal(ra["pose"].view(np.uint32), rc["pose"].view(np.uint32)) and ra["isKeyFrame"] == rc["isKeyFrame"] and ra["stats"] == rc["stats"]
+
+
+# ---- layered scenes (synth scene="layered"): depth discontinuities, occlusions, a wide disparity range, noise on the right image ----------
+LAYERED_SMALL = [pytest.param(41, 96, 32, (4.0, 26.0), 0, id="96x41-ndisp32"), pytest.param(40, 90, 16, (2.0, 13.0), 1, id="90x40-ndisp16"),
+                 pytest.param(47, 110, 32, (3.0, 28.0), 2, id="110x47-ndisp32")]
+
+
+def _layered_stereo(rows, cols, disp_range, index):
+    d = synth.make_stereo_pair(rows, cols, index, scene="layered", disp_range=disp_range)
+    assert d["occluded"].any() and len(np.unique(d["layer"])) >= 2
+    return d["left"], d["right"]
+
+
+@pytest.mark.parametrize("rows,cols,ndisp,disp_range,index", LAYERED_SMALL)
+@pytest.mark.parametrize("wsz", [9, 15])
+def test_block_matching_oracle_matches_the_definition_on_layered_pairs(orc, rows, cols, ndisp, disp_range, index, wsz):
+    """uniqueness and texture tests where the windows straddle depth edges and occluded strips"""
+    left, right = _layered_stereo(rows, cols, disp_range, index)
+    got = orc_bm(orc, left, right, wsz=wsz, ndisp=ndisp, mind=0)
+    want = np_bm(np_prefilter(left, 31), np_prefilter(right, 31), wsz, ndisp, 0, 31, 10, 15)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
+    assert (got == -1).any() and (got > 0).any()
+
+
+@pytest.mark.parametrize("rows,cols,ndisp,disp_range,index", LAYERED_SMALL)
+@pytest.mark.parametrize("kw", [dict(), dict(crad=1, wrad=1, p1=60, p2=900, thr=2)], ids=["default", "small-windows"])
+def test_sgm_oracle_matches_the_definition_on_layered_pairs(orc, rows, cols, ndisp, disp_range, index, kw):
+    """the left-right consistency check and the speckle filter where occlusions make them act"""
+    left, right = _layered_stereo(rows, cols, disp_range, index)
+    q = dict(SGM_DEFAULT, ndisp=ndisp, **kw)
+    got = orc_sgm(orc, left, right, **dict(kw, ndisp=ndisp))
+    want = np_sgm(left, right, q["ndisp"], q["cap"], q["crad"], q["wrad"], q["p1"], q["p2"], q["thr"], q["factor"], q["cw"])
+    assert np.array_equal(got, want), (np.argwhere(got != want)[:6], got[got != want][:6], want[got != want][:6])
+    assert (got == 0).any() and (got > 0).mean() > 0.3
+
+
+@pytest.mark.parametrize("rows,cols,ndisp,disp_range,index", LAYERED_SMALL)
+@pytest.mark.parametrize("kw", [dict(wsz=7), dict(wsz=5, p1=24, p2=96, cap=31, uniq=5, spw=20, spr=2, d12=1), dict(wsz=3, p1=8, p2=32, uniq=10, d12=1)],
+                         ids=["kitti_seq_0", "speckles-lr-check", "uniqueness"])
+def test_sgbm_oracle_matches_the_definition_on_layered_pairs(orc, rows, cols, ndisp, disp_range, index, kw):
+    """uniqueness, disp12MaxDiff and speckle filtering at depth discontinuities"""
+    left, right = _layered_stereo(rows, cols, disp_range, index)
+    got = orc_sgbm(orc, left, right, ndisp=ndisp, **kw)
+    want = np_sgbm(left, right, ndisp=ndisp, **kw)
+    assert got is not None and np.array_equal(got, want), (np.argwhere(got != want)[:8], got[got != want][:8], want[got != want][:8])
+    assert (got == -1).any() and (got > -1).mean() > 0.2
