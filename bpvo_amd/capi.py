@@ -54,6 +54,52 @@ class Result(C.Structure):
                 ("numLevels", C.c_int), ("isKeyFrame", C.c_int), ("keyFramingReason", C.c_int), ("hasPointCloud", C.c_int)]
 
 
+class Camera(C.Structure):
+    """bpvo_hip_camera: one sequence's calibration and image size (bpvo_hip_create_sequences, bpvo_hip_seq_set_camera)."""
+    _fields_ = [("K", C.c_float * 9), ("baseline", C.c_float), ("rows", C.c_int), ("cols", C.c_int)]
+
+
+def camera(K, baseline, rows, cols) -> Camera:
+    """A Camera from a 3x3 K (any float array), a baseline and an image size."""
+    cam = Camera()
+    cam.K[:] = [float(v) for v in np.asarray(K, dtype=np.float32).reshape(9)]
+    cam.baseline, cam.rows, cam.cols = float(baseline), int(rows), int(cols)
+    return cam
+
+
+def _as_camera(c) -> Camera:
+    return c if isinstance(c, Camera) else camera(*c)
+
+
+def pack_frames(images, disps):
+    """Frames of possibly different sizes back to back, as bpvo_hip_add_frames takes them: (u8 [sum of pixels], f32 [sum of pixels],
+    [(rows, cols)] per frame)."""
+    assert len(images) == len(disps), "one disparity per image"
+    shapes = []
+    for im, d in zip(images, disps):
+        assert np.ndim(im) == 2 and np.shape(im) == np.shape(d), "frames are 2-D, image and disparity of one shape"
+        shapes.append(tuple(int(v) for v in np.shape(im)))
+    total = sum(r * w for r, w in shapes)
+    img = np.empty(total, np.uint8)
+    disp = np.empty(total, np.float32)
+    at = 0
+    for (r, w), im, d in zip(shapes, images, disps):
+        img[at:at + r * w] = np.asarray(im, dtype=np.uint8).reshape(-1)
+        disp[at:at + r * w] = np.asarray(d, dtype=np.float32).reshape(-1)
+        at += r * w
+    return img, disp, shapes
+
+
+def unpack_frames(img, disp, shapes):
+    """pack_frames' inverse: lists of [rows, cols] arrays."""
+    out_i, out_d, at = [], [], 0
+    for r, w in shapes:
+        out_i.append(np.asarray(img[at:at + r * w]).reshape(r, w))
+        out_d.append(np.asarray(disp[at:at + r * w]).reshape(r, w))
+        at += r * w
+    return out_i, out_d
+
+
 class StereoParams(C.Structure):
     """bpvo_hip_stereo_params: the CvStereoBMState fields the reference sets (utils/stereo_algorithm.cc:63-82)."""
     _fields_ = [("preFilterCap", C.c_int), ("SADWindowSize", C.c_int), ("minDisparity", C.c_int), ("numberOfDisparities", C.c_int),
@@ -108,20 +154,35 @@ class Binding:
     def create(self, K, baseline, rows, cols, params: Params, device=0, n_frames=3, n_pairs=1) -> "Context":
         return Context(self, K, baseline, rows, cols, params, device, n_frames, n_pairs)
 
+    def create_sequences(self, cameras, params: Params, device=0) -> "Context":
+        """bpvo_hip_create_sequences: a context for len(cameras) add_frames sequences, sequence s with cameras[s] (a Camera or
+        (K, baseline, rows, cols))."""
+        cams = (Camera * len(cameras))(*[_as_camera(c) for c in cameras])
+        h = C.c_void_p()
+        rc = self.fn("create_sequences")(C.byref(h), len(cameras), cams, C.byref(params), int(device))
+        if rc != 0:
+            msg = self.fn("last_error", C.c_char_p)(None)
+            raise BpvoError(f"{self.prefix}create_sequences failed ({rc}): {msg.decode() if msg else ''}")
+        S = len(cameras)
+        return Context(self, None, None, max(c.rows for c in cams), max(c.cols for c in cams), params, device, 3 * S, S, handle=h)
+
 
 class Context:
     """One bpvo_*_ctx. Methods mirror the C ABI one to one and return numpy arrays in the reference layouts."""
 
-    def __init__(self, b: Binding, K, baseline, rows, cols, params, device, n_frames, n_pairs):
+    def __init__(self, b: Binding, K, baseline, rows, cols, params, device, n_frames, n_pairs, handle=None):
         self.b = b
         self.h = C.c_void_p()
         self.rows, self.cols = int(rows), int(cols)
-        Kf = _f32(K).reshape(9)
-        rc = b.fn("create")(C.byref(self.h), Kf.ctypes.data_as(C.c_void_p), C.c_float(baseline), int(rows), int(cols),
-                            C.byref(params), int(device), int(n_frames), int(n_pairs))
-        if rc != 0:
-            msg = b.fn("last_error", C.c_char_p)(None)
-            raise BpvoError(f"{b.prefix}create failed ({rc}): {msg.decode() if msg else ''}")
+        if handle is not None:      # (Binding.create_sequences: the context exists already)
+            self.h = handle
+        else:
+            Kf = _f32(K).reshape(9)
+            rc = b.fn("create")(C.byref(self.h), Kf.ctypes.data_as(C.c_void_p), C.c_float(baseline), int(rows), int(cols),
+                                C.byref(params), int(device), int(n_frames), int(n_pairs))
+            if rc != 0:
+                msg = b.fn("last_error", C.c_char_p)(None)
+                raise BpvoError(f"{b.prefix}create failed ({rc}): {msg.decode() if msg else ''}")
         self.n_frames, self.n_pairs = n_frames, n_pairs
         self.L = b.fn("num_levels")(self.h)
         self.Cn = b.fn("num_channels")(self.h)
@@ -393,7 +454,22 @@ class Context:
 
     def add_frames(self, images, disps, seq=None):
         """Frame i of images [n, rows, cols] u8 / disps [n, rows, cols] f32 is the next frame of sequence seq[i] (None: 0 .. n-1);
-        returns a list of n dicts in add_frame's format."""
+        returns a list of n dicts in add_frame's format.  Sequences with cameras of their own (create_sequences, seq_set_camera): lists
+        of 2-D arrays, frame i of its sequence's size, packed back to back (pack_frames)."""
+        if isinstance(images, (list, tuple)):
+            n = len(images)
+            ids, p_ids = self._seq_ids(n, seq)
+            for i in range(n):
+                s = int(ids[i]) if ids is not None else i
+                want = (self.rows, self.cols)
+                if self.b.has("seq_get_camera") and 0 <= s < self.seq_capacity():
+                    cam = self.seq_get_camera(s)
+                    want = (cam.rows, cam.cols)
+                assert np.shape(images[i]) == want, f"frame {i}: sequence {s} takes {want[0]}x{want[1]} frames"
+            img, disp, _ = pack_frames(images, disps)
+            res = (Result * n)()
+            self.call("add_frames", n, p_ids, img.ctypes.data_as(C.c_void_p), disp.ctypes.data_as(C.c_void_p), 0, res)
+            return [self._result_dict(r) for r in res]
         images = np.ascontiguousarray(images, dtype=np.uint8)
         disps = _f32(disps)
         n = images.shape[0]
@@ -404,7 +480,8 @@ class Context:
         return [self._result_dict(r) for r in res]
 
     def add_frames_device(self, n, d_images_ptr, d_disps_ptr, seq=None):
-        """add_frames with the n images / disparities already in device memory (contiguous [n][rows*cols])."""
+        """add_frames with the n images / disparities already in device memory (contiguous [n][rows*cols]; sequences with cameras of their
+        own: frame i of its sequence's size, the frames back to back as pack_frames lays them out)."""
         ids, p_ids = self._seq_ids(n, seq)
         res = (Result * n)()
         self.call("add_frames", int(n), p_ids, C.c_void_p(d_images_ptr), C.c_void_p(d_disps_ptr), 1, res)
@@ -417,6 +494,16 @@ class Context:
 
     def seq_reset(self, s):
         self.call("seq_reset", int(s))
+
+    def seq_set_camera(self, s, cam):
+        """bpvo_hip_seq_set_camera: cam is a Camera or (K, baseline, rows, cols); only while sequence s holds no frame."""
+        cam = _as_camera(cam)
+        self.call("seq_set_camera", int(s), C.byref(cam))
+
+    def seq_get_camera(self, s) -> Camera:
+        cam = Camera()
+        self._ck(self.b.fn("seq_get_camera")(self.h, int(s), C.byref(cam)))
+        return cam
 
     def seq_num_points_at_level(self, s, level=-1):
         n = C.c_int()

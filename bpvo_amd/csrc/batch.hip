@@ -254,6 +254,8 @@ int bpvo_hip_batch_run(bpvo_hip_ctx* c, int n_pairs, const uint8_t* images, cons
 {
   CHECK_CTX(c);
   if(n_pairs < 0 || 2 * n_pairs > c->n_frames || n_pairs > c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "batch exceeds ctx capacity");
+  for(int i = 0; i < 2 * n_pairs; ++i)
+    if(c->frames[i].own_geom) return fail(c, BPVO_ERR_UNSUPPORTED, "pair batches run the context's camera: its slots carry per-sequence cameras (bpvo_hip_seq_set_camera)");
   (void) hipSetDevice(c->device);
   if(n_pairs > 0 && (!images || !disparities)) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image/disparity");
   // host buffers: batches of at least two chunks go through the upload pipeline

@@ -103,7 +103,7 @@ int ensure_template_storage(bpvo_hip_ctx* c, FrameSlot& f)
 
 FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l)
 {
-  const LevelGeom& g = c->geom[l];
+  const LevelGeom& g = slot_geom(c, f, l);
   FrameJob j;
   std::memset(&j, 0, sizeof(j));
   j.img = f.img[l];
@@ -122,7 +122,7 @@ FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l)
   j.pix = f.pix[l];
   j.grad = f.grad[l];
   j.nrm = f.nrm ? f.nrm + 4 * l : nullptr;
-  j.rows = g.rows; j.cols = g.cols; j.level = l; j.disp_cols = c->cols;
+  j.rows = g.rows; j.cols = g.cols; j.level = l; j.disp_cols = slot_geom(c, f, 0).cols;
   j.cap = g.cap;
   j.nms_radius = g.nms_radius;
   std::memcpy(j.K, g.K, sizeof(j.K));
@@ -136,7 +136,7 @@ PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l)
 {
   FrameSlot& fr = c->frames[ref];
   FrameSlot& fc = c->frames[cur];
-  const LevelGeom& g = c->geom[l];
+  const LevelGeom& g = slot_geom(c, fr, l);
   PairJob j;
   std::memset(&j, 0, sizeof(j));
   j.pts = fr.pts[l];
@@ -399,8 +399,41 @@ void bpvo_hip_default_params(bpvo_hip_params* p)   // AlgorithmParameters() (ref
   p->withNormalization = 1;
 }
 
-int bpvo_hip_create(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, int cols, const bpvo_hip_params* p,
-                    int device, int n_frames, int n_pairs)
+}  // extern "C"
+
+namespace bpvo_hip_host {
+
+const char* level_geometry(const float K[9], float baseline, int rows, int cols, int L, const bpvo_hip_params& p, LevelGeom* geom)
+{
+  int r = rows, w = cols;
+  float Kp[9];
+  std::memcpy(Kp, K, sizeof(Kp));
+  float bp = baseline;
+  for(int l = 0; l < L; ++l) {
+    if(l > 0) {
+      r = (r + 1) / 2; w = (w + 1) / 2;
+      for(int k = 0; k < 9; ++k) Kp[k] *= 0.5f;
+      Kp[8] = 1.0f;
+      bp *= 2.0f;
+    }
+    LevelGeom& g = geom[l];
+    g.rows = r; g.cols = w; g.npix = (size_t) r * w;
+    g.nblk = (int) ((g.npix + 255) / 256);
+    const bool nms = (r * w >= p.minNumPixelsForNonMaximaSuppression) && p.nonMaxSuppRadius > 0;   // template_data.cc:43-49
+    g.nms_radius = nms ? p.nonMaxSuppRadius : -1;
+    // strict local maxima: at most one per 2x2 block (two adjacent pixels cannot both be strict maxima)
+    const size_t cap = nms ? (size_t) ((r + 1) / 2) * ((w + 1) / 2) : g.npix;
+    g.cap = (int) ((cap + kTile - 1) / kTile * kTile);   // whole 64-point tiles (tiled per-point layout, types.h)
+    std::memcpy(g.K, Kp, sizeof(Kp));
+    g.b = bp;
+    if(r < 8 || w < 8) return "pyramid level smaller than 8 pixels";
+  }
+  return nullptr;
+}
+
+// bpvo_hip_create; min_caps (bpvo_hip_create_sequences): per level, a template capacity the context must hold at least
+int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, int cols, const bpvo_hip_params* p, int device, int n_frames, int n_pairs,
+                const int* min_caps)
 {
   if(!out || !K || !p || rows < 8 || cols < 8 || n_frames < 1 || n_pairs < 1) {
     g_create_error = "invalid argument";
@@ -427,6 +460,7 @@ int bpvo_hip_create(bpvo_hip_ctx** out, const float K[9], float baseline, int ro
   c->baseline = baseline;
   c->rows = rows; c->cols = cols; c->device = device;
   c->n_frames = n_frames; c->n_pairs = n_pairs;
+  c->auto_levels = c->params.numPyramidLevels <= 0;
   if(c->params.numPyramidLevels <= 0)   // bpvo/vo.cc:101-105
     c->params.numPyramidLevels = 1 + (int) std::round(std::log2(std::min(rows, cols) / (double) p->minImageDimensionForPyramid));
   c->L = c->params.numPyramidLevels;
@@ -524,32 +558,10 @@ int bpvo_hip_create(bpvo_hip_ctx** out, const float K[9], float baseline, int ro
     gaussian_taps(imsmooth_taps(1.75f), 1.75f, &c->latch_after);
   }
 
-  // level geometry (bpvo/vo_frame.cc:21-28: K *= 0.5, K(2,2) = 1, b *= 2; pyrDown sizes)
-  {
-    int r = rows, w = cols;
-    float Kp[9];
-    std::memcpy(Kp, K, sizeof(Kp));
-    float bp = baseline;
-    for(int l = 0; l < c->L; ++l) {
-      if(l > 0) {
-        r = (r + 1) / 2; w = (w + 1) / 2;
-        for(int k = 0; k < 9; ++k) Kp[k] *= 0.5f;
-        Kp[8] = 1.0f;
-        bp *= 2.0f;
-      }
-      LevelGeom& g = c->geom[l];
-      g.rows = r; g.cols = w; g.npix = (size_t) r * w;
-      g.nblk = (int) ((g.npix + 255) / 256);
-      const bool nms = (r * w >= c->params.minNumPixelsForNonMaximaSuppression) && c->params.nonMaxSuppRadius > 0;   // template_data.cc:43-49
-      g.nms_radius = nms ? c->params.nonMaxSuppRadius : -1;
-      // strict local maxima: at most one per 2x2 block (two adjacent pixels cannot both be strict maxima)
-      const size_t cap = nms ? (size_t) ((r + 1) / 2) * ((w + 1) / 2) : g.npix;
-      g.cap = (int) ((cap + kTile - 1) / kTile * kTile);   // whole 64-point tiles (tiled per-point layout, types.h)
-      std::memcpy(g.K, Kp, sizeof(Kp));
-      g.b = bp;
-      c->cap_max = std::max(c->cap_max, g.cap);
-      if(r < 8 || w < 8) return unsupported("pyramid level smaller than 8 pixels");
-    }
+  if(const char* why = level_geometry(K, baseline, rows, cols, c->L, c->params, c->geom)) return unsupported(why);
+  for(int l = 0; l < c->L; ++l) {
+    if(min_caps) c->geom[l].cap = std::max(c->geom[l].cap, min_caps[l]);   // (bpvo_hip_create_sequences: room for every camera's template)
+    c->cap_max = std::max(c->cap_max, c->geom[l].cap);
   }
 
   bpvo_hip_ctx* cp = c.get();
@@ -664,6 +676,16 @@ int bpvo_hip_create(bpvo_hip_ctx** out, const float K[9], float baseline, int ro
   cp->counted_live = true;
   *out = c.release();
   return BPVO_OK;
+}
+
+}  // namespace bpvo_hip_host
+
+extern "C" {
+
+int bpvo_hip_create(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, int cols, const bpvo_hip_params* p,
+                    int device, int n_frames, int n_pairs)
+{
+  return create_impl(out, K, baseline, rows, cols, p, device, n_frames, n_pairs, nullptr);
 }
 
 void bpvo_hip_destroy(bpvo_hip_ctx* c)

@@ -50,17 +50,23 @@ int upload_frame_jobs(bpvo_hip_ctx* c, int first, int stride, int count, const F
 // neither uploaded nor copied: 40 % of a pair's input bytes
 // (2: as 1, with the device-resident disparities packed for the even frames only — the staging area of the upload pipeline)
 int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const uint8_t* images, const float* disps, bool on_device,
-                          const FrameRun& fr, int skip_odd_disp)
+                          const FrameRun& fr, int skip_odd_disp, const size_t* offsets)
 {
   if(count <= 0) return BPVO_OK;
-  const size_t npix = c->geom[0].npix;
+  // the launch-wide sizes: those of the stage's slots (the context's, or one camera size of bpvo_hip_add_frames)
+  const LevelGeom* geom = c->frames[slots[0]].own_geom ? c->frames[slots[0]].geom : c->geom;
+  for(int i = 1; i < count; ++i)
+    if(slot_geom(c, c->frames[slots[i]], 0).rows != geom[0].rows || slot_geom(c, c->frames[slots[i]], 0).cols != geom[0].cols)
+      return fail(c, BPVO_ERR_INVALID_ARG, "frame stage over slots of different sizes");
+  const size_t npix = geom[0].npix;
   hipStream_t s = fr.stream;
   if(!on_device) {
     for(int i = 0; i < count; ++i) {
       FrameSlot& f = c->frames[slots[i]];
-      FR_CK(c, fr, hipMemcpyAsync(f.img[0], images + (size_t) i * npix, npix, hipMemcpyHostToDevice, s));
+      const size_t at = offsets ? offsets[i] : (size_t) i * npix;
+      FR_CK(c, fr, hipMemcpyAsync(f.img[0], images + at, npix, hipMemcpyHostToDevice, s));
       if(!(skip_odd_disp && (i & 1)) && !fr.skip_disparity_upload)
-        FR_CK(c, fr, hipMemcpyAsync(f.disp, disps + (size_t) i * npix, npix * sizeof(float), hipMemcpyHostToDevice, s));
+        FR_CK(c, fr, hipMemcpyAsync(f.disp, disps + at, npix * sizeof(float), hipMemcpyHostToDevice, s));
     }
   }
   // pair batches: the compact channel-0 plane serves the saliency map of TEMPLATE frames only; the current frames' descriptor kernel
@@ -71,33 +77,41 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
   const bool lazy_ok = skip_odd_disp != 0 && c->lazy_template && c->params.descriptor == BPVO_DESC_BITPLANES && c->C == 8 &&
                        !(c->params.sigmaPriorToCensusTransform > 0.0f) && c->params.sigmaBitPlanes > 0.0f && c->params.gradientEstimation == BPVO_GRAD_CD3;
   for(int i = 0; i < count; ++i)
-    for(int l = 0; l < c->L; ++l) c->frames[slots[i]].lazy[l] = lazy_ok && !(i & 1) && c->geom[l].nms_radius > 0;
+    for(int l = 0; l < c->L; ++l) c->frames[slots[i]].lazy[l] = lazy_ok && !(i & 1) && geom[l].nms_radius > 0;
   const FrameJob* tab = nullptr;
   int rc = upload_frame_jobs_slots(c, slots, count, fr, 0, &tab);
   if(rc) return rc;
   const int NF = c->n_frames;
-  if(on_device) launch_ingest(s, tab, images, disps, npix, count, skip_odd_disp);   // one launch instead of 2 copies per frame
+  if(on_device && offsets) {
+    // (entries at arbitrary places of the packed inputs: their offsets travel in rows [tab, tab + count) of the sequences' offset table)
+    size_t* h_off = c->h_seq_off + fr.tab;
+    for(int i = 0; i < count; ++i) h_off[i] = offsets[i];
+    FR_CK(c, fr, hipMemcpyAsync(c->d_seq_off + fr.tab, h_off, sizeof(size_t) * (size_t) count, hipMemcpyHostToDevice, s));
+    launch_ingest_at(s, tab, images, disps, c->d_seq_off + fr.tab, npix, count);
+  } else if(on_device) {
+    launch_ingest(s, tab, images, disps, npix, count, skip_odd_disp);   // one launch instead of 2 copies per frame
+  }
   {
     double px = 0;
-    for(int l = 1; l < c->L; ++l) px += (double) c->geom[l].npix * count;
+    for(int l = 1; l < c->L; ++l) px += (double) geom[l].npix * count;
     ScopedTimer t(c, KC_PYRAMID, px, fr.ln);
     // ImagePyramid::compute (bpvo/image_pyramid.cc:43-50).  Few frames: up to three levels per launch (kernels_frame.hip pyramid_levels_kernel)
     bool grouped = count <= c->merge_levels_max_frames;
-    for(int l = 0; l < c->L; ++l) grouped = grouped && c->geom[l].cols >= 8 && c->geom[l].rows >= 8;
+    for(int l = 0; l < c->L; ++l) grouped = grouped && geom[l].cols >= 8 && geom[l].rows >= 8;
     for(int l = 1; l < c->L;) {
       const int steps = grouped ? std::min(3, c->L - l) : 0;
       if(steps >= 2) {
-        launch_pyramid_levels(s, tab + (size_t) (l - 1) * NF, NF, steps, c->geom[l + steps - 1].cols, c->geom[l + steps - 1].rows, count);
+        launch_pyramid_levels(s, tab + (size_t) (l - 1) * NF, NF, steps, geom[l + steps - 1].cols, geom[l + steps - 1].rows, count);
         l += steps;
       } else {
-        launch_pyrdown(s, tab + (size_t) (l - 1) * NF, tab + (size_t) l * NF, c->geom[l].cols, c->geom[l].rows, count);
+        launch_pyrdown(s, tab + (size_t) (l - 1) * NF, tab + (size_t) l * NF, geom[l].cols, geom[l].rows, count);
         l += 1;
       }
     }
   }
   {
     double px = 0;
-    for(int l = c->L - 1; l >= c->params.maxTestLevel; --l) px += (double) c->geom[l].npix * count;
+    for(int l = c->L - 1; l >= c->params.maxTestLevel; --l) px += (double) geom[l].npix * count;
     ScopedTimer t(c, KC_DESCRIPTOR, px, fr.ln);
     // few frames, bit-planes with the census fused: every level in ONE launch (kernels_frame.hip level_job)
     const bool fused_bp = c->C == 8 && c->params.descriptor == BPVO_DESC_BITPLANES && !(c->params.sigmaPriorToCensusTransform > 0.0f) && c->params.sigmaBitPlanes > 0.0f;
@@ -107,16 +121,16 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
     const bool plain_intensity = c->C == 1 && c->params.descriptor != BPVO_DESC_LAPLACIAN;
     const bool one_launch = (fused_bp || smoothed_bp || plain_intensity) && count <= c->merge_levels_max_frames && c->L - l_lo > 1;
     if(one_launch && fused_bp) {
-      launch_bitplanes(s, tab + (size_t) l_lo * NF, c->geom[l_lo].cols, c->geom[l_lo].rows, count, c->params.sigmaBitPlanes, c->gauss_k, 1, c->L - l_lo, NF);
+      launch_bitplanes(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->params.sigmaBitPlanes, c->gauss_k, 1, c->L - l_lo, NF);
     } else if(one_launch && smoothed_bp) {
-      launch_census(s, tab + (size_t) l_lo * NF, c->geom[l_lo].cols, c->geom[l_lo].rows, count, c->census_taps, c->L - l_lo, NF);
-      launch_bitplanes(s, tab + (size_t) l_lo * NF, c->geom[l_lo].cols, c->geom[l_lo].rows, count, c->params.sigmaBitPlanes, c->gauss_k, 0, c->L - l_lo, NF);
+      launch_census(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->census_taps, c->L - l_lo, NF);
+      launch_bitplanes(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->params.sigmaBitPlanes, c->gauss_k, 0, c->L - l_lo, NF);
     } else if(one_launch) {
-      launch_intensity(s, tab + (size_t) l_lo * NF, c->geom[l_lo].cols, c->geom[l_lo].rows, count, c->L - l_lo, NF);
+      launch_intensity(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->L - l_lo, NF);
     }
     for(int l = c->L - 1; l >= c->params.maxTestLevel && !one_launch; --l) {   // DenseDescriptorPyramid::init (dense_descriptor_pyramid.cc:67-71)
       const FrameJob* jobs = tab + (size_t) l * NF;
-      const LevelGeom& g = c->geom[l];
+      const LevelGeom& g = geom[l];
       if(c->params.descriptor == BPVO_DESC_CENTRAL_DIFFERENCE) {
         launch_central_difference(s, jobs, g.cols, g.rows, count, c->params.centralDifferenceRadius, c->cd_before, c->cd_after);
       } else if(c->params.descriptor == BPVO_DESC_LATCH) {
@@ -161,7 +175,7 @@ int upload_disparity(bpvo_hip_ctx* c, int slot, const float* disparity)
     HIP_CK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     HIP_CK(c, hipEventCreateWithFlags(&c->copy_ev, hipEventDisableTiming));
   }
-  HIP_CK(c, hipMemcpyAsync(c->frames[slot].disp, disparity, c->geom[0].npix * sizeof(float), hipMemcpyHostToDevice, c->copy_stream));
+  HIP_CK(c, hipMemcpyAsync(c->frames[slot].disp, disparity, slot_geom(c, c->frames[slot], 0).npix * sizeof(float), hipMemcpyHostToDevice, c->copy_stream));
   HIP_CK(c, hipEventRecord(c->copy_ev, c->copy_stream));
   HIP_CK(c, hipStreamWaitEvent(c->stream, c->copy_ev, 0));
   return BPVO_OK;
@@ -178,6 +192,11 @@ int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uin
 int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr)
 {
   if(count <= 0) return BPVO_OK;
+  // the launch-wide sizes: those of the stage's slots (the context's, or one camera size of bpvo_hip_add_frames); storage: the context's
+  const LevelGeom* geom = c->frames[slots[0]].own_geom ? c->frames[slots[0]].geom : c->geom;
+  for(int i = 1; i < count; ++i)
+    if(slot_geom(c, c->frames[slots[i]], 0).rows != geom[0].rows || slot_geom(c, c->frames[slots[i]], 0).cols != geom[0].cols)
+      return fail(c, BPVO_ERR_INVALID_ARG, "frame stage over slots of different sizes");
   hipStream_t s = fr.stream;
   for(int i = 0; i < count; ++i) {
     FrameSlot& f = c->frames[slots[i]];
@@ -199,7 +218,7 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
   const int border = std::max(p.nonMaxSuppRadius, 3);   // template_data.cc:51
   // few frames, every level on the tiled path (NMS radius <= 1): the levels in ONE launch of each of its three kernels (kernels_frame.hip level_job)
   bool tiled = true;
-  for(int l = p.maxTestLevel; l < c->L; ++l) tiled = tiled && c->geom[l].nms_radius <= 1;
+  for(int l = p.maxTestLevel; l < c->L; ++l) tiled = tiled && geom[l].nms_radius <= 1;
   const bool one_launch = tiled && count <= c->merge_levels_max_frames && c->L - p.maxTestLevel > 1;
   hipEvent_t counts_ev = fr.ln ? fr.ln->round_ev[0] : nullptr;      // (the lane's round events are idle outside its estimation)
   // The normalisation — sequential sums in the reference's order, a latency chain of one workgroup per (frame, level): 0.2 ms whatever the
@@ -224,15 +243,15 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
   const bool defer = side && fr.defer_finest_nrm && c->nrm_defer && c->L - p.maxTestLevel > 1 && !c->nrm_pending && !c->nrm_pending_finest;
   if(one_launch) {
     double px = 0;
-    for(int l = p.maxTestLevel; l < c->L; ++l) px += (double) c->geom[l].npix * count;
+    for(int l = p.maxTestLevel; l < c->L; ++l) px += (double) geom[l].npix * count;
     ScopedTimer t(c, KC_SALIENCY_SELECT, px, fr.ln);
-    const LevelGeom& g = c->geom[p.maxTestLevel];
+    const LevelGeom& g = geom[p.maxTestLevel];
     launch_saliency_select(s, tab + (size_t) p.maxTestLevel * NF, c->C, g.cols, g.rows, count, 1, p.minSaliency, p.minValidDisparity, p.maxValidDisparity, border,
                            c->L - p.maxTestLevel, NF);
   }
   for(int l = c->L - 1; l >= p.maxTestLevel && !one_launch; --l) {
     const FrameJob* jobs = tab + (size_t) l * NF;
-    const LevelGeom& g = c->geom[l];
+    const LevelGeom& g = geom[l];
     ScopedTimer t(c, KC_SALIENCY_SELECT, (double) g.npix * count, fr.ln);
     launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, p.minSaliency, p.minValidDisparity, p.maxValidDisparity, border);
   }

@@ -74,6 +74,10 @@ struct FrameSlot {
   float* nrm = nullptr;    // [L][4]
   int* n_dev = nullptr;    // [L]
   int n_host[kMaxLevels] = {};
+  // the slot's camera when it is not the context's own (a sequence of bpvo_hip_add_frames with bpvo_hip_seq_set_camera / create_sequences):
+  // its level geometry, sizes within the context's storage geometry; slot_geom below picks it
+  bool own_geom = false;
+  LevelGeom geom[kMaxLevels];
 };
 
 // One sequence of bpvo_hip_add_frames (vo.hip): the VisualOdometry state of bpvo/vo.cc:45-52 for frame slots 3s .. 3s+2 and workspace s
@@ -151,6 +155,7 @@ struct bpvo_hip_ctx {
   float K[9];
   float baseline;
   int rows, cols, L, C, device;
+  bool auto_levels = false;     // numPyramidLevels <= 0 at creation: L is the automatic count of the image size (bpvo/vo.cc:101-105)
   int n_frames, n_pairs;
   LevelGeom geom[kMaxLevels];
   float gauss_k[3];
@@ -197,6 +202,8 @@ struct bpvo_hip_ctx {
   CloudJob* d_cloud_jobs = nullptr;
   unsigned* h_seq_cnt = nullptr;                   // pinned [seq_capacity]: good-point counters
   unsigned* d_seq_cnt = nullptr;
+  size_t* h_seq_off = nullptr;                     // pinned [seq_capacity]: pixel offsets of the frames of a mixed-size call in the packed device inputs
+  size_t* d_seq_off = nullptr;
   // measurement
   double points_fused = 0;     // points linearised through the fused path since the last counter reset
   int fast_warp = 0;           // bpvo_hip_set_warp_formulation
@@ -411,6 +418,16 @@ struct FrameRun {
     }                                                                                       \
   } while(0)
 
+// the level geometry of a camera (bpvo/vo_frame.cc:21-28: K *= 0.5, K(2,2) = 1, b *= 2; pyrDown sizes; the NMS rule of template_data.cc:43-49;
+// the template capacity) — the one derivation for bpvo_hip_create, bpvo_hip_create_sequences and bpvo_hip_seq_set_camera.  Returns nullptr, or
+// why it is unsupported (a level under 8 pixels).
+const char* level_geometry(const float K[9], float baseline, int rows, int cols, int L, const bpvo_hip_params& p, LevelGeom* g);
+// bpvo_hip_create; min_caps (bpvo_hip_create_sequences): per level, a template capacity the context must hold at least
+int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, int cols, const bpvo_hip_params* p, int device, int n_frames, int n_pairs,
+                const int* min_caps);
+// a frame slot's geometry at level l: its camera's, or the context's
+inline const LevelGeom& slot_geom(const bpvo_hip_ctx* c, const FrameSlot& f, int l) { return f.own_geom ? f.geom[l] : c->geom[l]; }
+
 // ---- shared between the translation units (definitions: see the table at the top)
 int fail(bpvo_hip_ctx* c, int code, const char* msg);
 void gaussian_kernel5(double sigma, float k[3]);
@@ -428,8 +445,10 @@ int upload_frame_jobs(bpvo_hip_ctx* c, int first, int stride, int count, const F
 // the frame stages over any list of slots (the strided forms above and below build the list first, slots[i] = first + i * stride)
 std::vector<int> strided_slots(int first, int stride, int count);
 int upload_frame_jobs_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr, int which, const FrameJob** tab);
+// offsets: null, or the pixel offset of each entry's image / disparity in `images` / `disps` (otherwise entry i is at i x its level-0 pixels).  Every
+// slot of one stage has the same sizes (slot_geom); mixed sizes run a stage per size
 int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const uint8_t* images, const float* disps, bool on_device, const FrameRun& fr,
-                          int skip_odd_disp = 0);
+                          int skip_odd_disp = 0, const size_t* offsets = nullptr);
 int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr);
 int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uint8_t* images, const float* disps, bool on_device, const FrameRun& fr,
                     int skip_odd_disp = 0);

@@ -56,6 +56,8 @@ struct GaussTaps { int n = 0; float k[kMaxGaussTaps] = {}; int ki[kMaxGaussTaps]
 
 // per-frame stage (batched over frames)
 void launch_ingest(hipStream_t s, const FrameJob* jobs_level0, const uint8_t* d_images, const float* d_disps, size_t npix, int nframes, int skip_odd_disp = 0);
+// ... frame z at pixel offset d_offsets[z] (device) of both packed buffers
+void launch_ingest_at(hipStream_t s, const FrameJob* jobs_level0, const uint8_t* d_images, const float* d_disps, const size_t* d_offsets, size_t npix, int nframes);
 void launch_pyrdown(hipStream_t s, const FrameJob* src, const FrameJob* dst, int dW, int dR, int nframes);
 // few frames: `steps` (1..3) pyrDown steps in one launch — src_row is the source level's row of the table [level][job_pitch], dW x dR the COARSEST level of the group
 void launch_pyramid_levels(hipStream_t s, const FrameJob* src_row, int job_pitch, int steps, int dW, int dR, int nframes);
@@ -218,9 +220,10 @@ struct CloudJob {
   const PairJob* job;       // device: the job of the key frame's last linearisation
   const uint8_t* img;       // the key frame's level-0 image
   size_t out_offset;        // first record of this entry in the output
+  float K[9];               // the intrinsics of the level the estimate ended on (each sequence its own camera)
+  int rows, cols;           // the size of img
 };
-void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int loss, int rows, int cols, const float K[9], int dspace,
-                              bpvo_hip_point_with_info* out);
+void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int loss, int dspace, bpvo_hip_point_with_info* out);
 void launch_pack_records(hipStream_t s, const PairJob* jobs, int n, int L, float* records, const GNState* d_states = nullptr, GNState* h_states = nullptr,
                          const unsigned* d_ctl = nullptr, unsigned* h_ctl = nullptr, int ctl_words = 0, unsigned* zero = nullptr);   // h_states / h_ctl (pinned host): copied out by the same launch; zero: a word cleared by it
 // a few pairs: job table upload (from the pinned host rows) + initial poses + cleared control words in one launch

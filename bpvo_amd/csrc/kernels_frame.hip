@@ -24,12 +24,16 @@ __device__ __forceinline__ const FrameJob& level_job(const FrameJob* jobs, unsig
   return jobs[(size_t) lvl * job_pitch + (z - lvl * (unsigned) nframes)];
 }
 
-__global__ __launch_bounds__(256) void ingest_kernel(const FrameJob* jobs, const uint8_t* images, const float* disps, size_t npix, int skip_odd_disp)
+// AT: frame z's image and disparity begin at pixel offs[z] of the packed buffers (bpvo_hip_add_frames over cameras of different sizes: one
+// launch per size, its frames wherever the call put them), not at z x npix
+template <bool AT>
+__global__ __launch_bounds__(256) void ingest_kernel(const FrameJob* jobs, const uint8_t* images, const float* disps, size_t npix, int skip_odd_disp,
+                                                     const size_t* __restrict__ offs)
 {
   const FrameJob& j = jobs[blockIdx.z];
-  const uint8_t* __restrict__ si = images + (size_t) blockIdx.z * npix;
+  const uint8_t* __restrict__ si = images + (AT ? offs[blockIdx.z] : (size_t) blockIdx.z * npix);
   // skip_odd_disp 2: the disparities are packed for the even frames only ([frame / 2][npix]: the upload pipeline of host batches)
-  const float* __restrict__ sd = disps + (size_t) (skip_odd_disp == 2 ? blockIdx.z / 2 : blockIdx.z) * npix;
+  const float* __restrict__ sd = disps + (AT ? offs[blockIdx.z] : (size_t) (skip_odd_disp == 2 ? blockIdx.z / 2 : blockIdx.z) * npix);
   uint8_t* __restrict__ di = const_cast<uint8_t*>(j.img.get());
   float* __restrict__ dd = const_cast<float*>(j.disp.get());
   const size_t t = (size_t) blockIdx.x * 256 + threadIdx.x, stride = (size_t) gridDim.x * 256;
@@ -1588,7 +1592,12 @@ static inline dim3 grid2d_rows(int W, int R, int nz) { return dim3((W + 63) / 64
 void launch_ingest(hipStream_t s, const FrameJob* jobs_level0, const uint8_t* d_images, const float* d_disps, size_t npix, int nframes, int skip_odd_disp)
 {
   const int blocks = (int) std::min<size_t>(256, (npix / 4 + 255) / 256);
-  hipLaunchKernelGGL(ingest_kernel, dim3(blocks, 1, nframes), dim3(256), 0, s, jobs_level0, d_images, d_disps, npix, skip_odd_disp);
+  hipLaunchKernelGGL(ingest_kernel<false>, dim3(blocks, 1, nframes), dim3(256), 0, s, jobs_level0, d_images, d_disps, npix, skip_odd_disp, nullptr);
+}
+void launch_ingest_at(hipStream_t s, const FrameJob* jobs_level0, const uint8_t* d_images, const float* d_disps, const size_t* d_offsets, size_t npix, int nframes)
+{
+  const int blocks = (int) std::min<size_t>(256, (npix / 4 + 255) / 256);
+  hipLaunchKernelGGL(ingest_kernel<true>, dim3(blocks, 1, nframes), dim3(256), 0, s, jobs_level0, d_images, d_disps, npix, 0, d_offsets);
 }
 void launch_pyrdown(hipStream_t s, const FrameJob* src, const FrameJob* dst, int dW, int dR, int nframes)
 {

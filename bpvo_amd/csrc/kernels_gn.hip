@@ -583,13 +583,16 @@ __global__ __launch_bounds__(256) void point_cloud_kernel(const PairJob* job, co
   out[i] = cloud_record(j, i, img, a);
 }
 // ... for a table of sequences that key-frame in one bpvo_hip_add_frames call: blockIdx.y = entry of the table, each with its own job, key frame
-// image and place in the output pool (the same records, byte for byte, as point_cloud_kernel's for that job)
+// image, camera (K, image size) and place in the output pool (the same records, byte for byte, as point_cloud_kernel's for that job)
 __global__ __launch_bounds__(256) void point_cloud_batch_kernel(const CloudJob* __restrict__ jobs, CloudArgs a, bpvo_hip_point_with_info* __restrict__ out)
 {
-  const CloudJob cj = jobs[blockIdx.y];
+  const CloudJob& cj = jobs[blockIdx.y];
   const PairJob& j = *cj.job;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if(i >= j.n) return;
+#pragma unroll
+  for(int k = 0; k < 9; ++k) a.K[k] = cj.K[k];
+  a.rows = cj.rows; a.cols = cj.cols;
   out[cj.out_offset + i] = cloud_record(j, i, cj.img, a);
 }
 
@@ -905,13 +908,11 @@ void launch_count_good_batch(hipStream_t s, const PairJob* jobs, int n_jobs, int
   }
   dispatch_channels(C, [&](auto c) { launch_count_good_batch_c<decltype(c)::value>(s, jobs, n_jobs, max_n, loss, thr, counts); });
 }
-void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int loss, int rows, int cols, const float K[9], int dspace,
-                              bpvo_hip_point_with_info* out)
+void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int loss, int dspace, bpvo_hip_point_with_info* out)
 {
   if(n_jobs <= 0 || max_n <= 0) return;
-  CloudArgs a;
-  for(int k = 0; k < 9; ++k) a.K[k] = K[k];
-  a.rows = rows; a.cols = cols; a.dspace = dspace; a.C = C; a.loss = loss;
+  CloudArgs a = {};      // (K, rows, cols: each entry's own, from its CloudJob)
+  a.dspace = dspace; a.C = C; a.loss = loss;
   hipLaunchKernelGGL(point_cloud_batch_kernel, dim3((max_n + 255) / 256, n_jobs), dim3(256), 0, s, jobs, a, out);
 }
 void launch_pack_records(hipStream_t s, const PairJob* jobs, int n, int L, float* records, const GNState* d_states, GNState* h_states, const unsigned* d_ctl,

@@ -424,6 +424,8 @@ static int seq_storage(bpvo_hip_ctx* c)
   if(!c->h_cloud_jobs) HIP_CK(c, hipHostMalloc((void**) &c->h_cloud_jobs, S * sizeof(CloudJob)));
   if(!c->d_seq_cnt) HIP_CK(c, hipMalloc((void**) &c->d_seq_cnt, S * sizeof(unsigned)));
   if(!c->h_seq_cnt) HIP_CK(c, hipHostMalloc((void**) &c->h_seq_cnt, S * sizeof(unsigned)));
+  if(!c->d_seq_off) HIP_CK(c, hipMalloc((void**) &c->d_seq_off, S * sizeof(size_t)));
+  if(!c->h_seq_off) HIP_CK(c, hipHostMalloc((void**) &c->h_seq_off, S * sizeof(size_t)));
   c->seqs.resize(S);
   for(int s = 0; s < (int) S; ++s) seq_reset_state(c, s);
   return BPVO_OK;
@@ -445,6 +447,42 @@ static void init_result(const bpvo_hip_ctx* c, bpvo_hip_result* ret)      // wha
   ret->keyFramingReason = BPVO_KF_NO_KEYFRAMING;
   ret->hasPointCloud = 0;
 }
+}  // extern "C"
+
+// The frame stages of a call run once per camera size among its slots (their kernels take launch-wide sizes; the intrinsics they read from the
+// jobs), each group on its own rows [tab, tab + count) of the job tables.  One size — every context without per-sequence cameras of several
+// sizes — is one stage over all the slots, as before.  offsets (the data stage): each entry's pixel offset in the packed inputs, or null.
+template <class F>
+static int for_each_size(bpvo_hip_ctx* c, const std::vector<int>& slots, const std::vector<size_t>* offsets, F&& stage)
+{
+  const int n = (int) slots.size();
+  auto size_of = [&](int i) { const LevelGeom& g = slot_geom(c, c->frames[slots[i]], 0); return std::make_pair(g.rows, g.cols); };
+  bool uniform = true;
+  for(int i = 1; i < n && uniform; ++i) uniform = size_of(i) == size_of(0);
+  if(uniform) return stage(slots.data(), n, (const size_t*) nullptr, ctx_run(c));
+  std::vector<char> done((size_t) n, 0);
+  int tab = 0;
+  for(int i = 0; i < n; ++i) {
+    if(done[i]) continue;
+    std::vector<int> gs;
+    std::vector<size_t> go;
+    for(int k = i; k < n; ++k)
+      if(!done[k] && size_of(k) == size_of(i)) {
+        done[k] = 1;
+        gs.push_back(slots[k]);
+        if(offsets) go.push_back((*offsets)[k]);
+      }
+    FrameRun fr = ctx_run(c);
+    fr.tab = tab;
+    const int rc = stage(gs.data(), (int) gs.size(), offsets ? (const size_t*) go.data() : (const size_t*) nullptr, fr);
+    if(rc) return rc;
+    tab += (int) gs.size();
+  }
+  return BPVO_OK;
+}
+
+extern "C" {
+
 static int add_frames_impl(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* images, const float* disparities, bool on_device,
                            bpvo_hip_result* results)
 {
@@ -485,9 +523,19 @@ static int add_frames_impl(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t
   auto drain = [&](int code) { (void) hipStreamSynchronize(c->stream); return code; };
 
   // 2. _cur_frame->setData (vo.cc:131) of every sequence: one data stage over their current slots
+  // (frame i: slot_geom(cur, 0).npix pixels at the sum of the frames' before it)
   std::vector<int> slots((size_t) n);
-  for(int i = 0; i < n; ++i) slots[i] = c->seqs[ids[i]].cur;
-  rc = frames_set_data_slots(c, slots.data(), n, images, disparities, on_device, ctx_run(c), 0);
+  std::vector<size_t> offsets((size_t) n);
+  size_t at = 0;
+  for(int i = 0; i < n; ++i) {
+    slots[i] = c->seqs[ids[i]].cur;
+    offsets[i] = at;
+    at += slot_geom(c, c->frames[slots[i]], 0).npix;
+  }
+  auto template_stage = [&](const int* sl, int count, const size_t*, const FrameRun& fr) { return frames_set_template_slots(c, sl, count, fr); };
+  rc = for_each_size(c, slots, &offsets, [&](const int* sl, int count, const size_t* off, const FrameRun& fr) {
+    return frames_set_data_slots(c, sl, count, images, disparities, on_device, fr, 0, off);
+  });
   if(rc) return drain(rc);
 
   // 3. first frames (vo.cc:133-139): their templates in one stage
@@ -500,7 +548,7 @@ static int add_frames_impl(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t
     slots.push_back(q.ref);
   }
   if(!slots.empty()) {
-    rc = frames_set_template_slots(c, slots.data(), (int) slots.size(), ctx_run(c));
+    rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
     for(int i = 0; i < n; ++i) {
       SeqState& q = c->seqs[ids[i]];
@@ -571,11 +619,15 @@ static int add_frames_impl(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t
       const int k = kf[j];
       const int npts = c->h_seq_jobs[k].n;
       if((size_t) npts > cap) return seq_fail(c, BPVO_ERR_INVALID_ARG, wss[k], "size mismatch");
-      c->h_cloud_jobs[j] = CloudJob{c->d_seq_jobs + k, c->frames[refs[k]].img[0], (size_t) wss[k] * cap};
+      const FrameSlot& kfr = c->frames[refs[k]];
+      CloudJob& cj = c->h_cloud_jobs[j];
+      cj.job = c->d_seq_jobs + k; cj.img = kfr.img[0]; cj.out_offset = (size_t) wss[k] * cap;
+      std::memcpy(cj.K, slot_geom(c, kfr, lvl).K, sizeof(cj.K));      // (build_point_cloud: the context's size and level intrinsics; here the sequence's)
+      cj.rows = slot_geom(c, kfr, 0).rows; cj.cols = slot_geom(c, kfr, 0).cols;
       max_c = std::max(max_c, npts);
     }
     HIP_CK(c, hipMemcpyAsync(c->d_cloud_jobs, c->h_cloud_jobs, sizeof(CloudJob) * (size_t) nk, hipMemcpyHostToDevice, c->stream));
-    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, nk, max_c, c->C, p.lossFunction, c->rows, c->cols, c->geom[lvl].K, c->dspace, c->d_seq_cloud);
+    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, nk, max_c, c->C, p.lossFunction, c->dspace, c->d_seq_cloud);
     HIP_CK(c, hipGetLastError());
     slots.clear();
     for(int j = 0; j < nk; ++j) {
@@ -593,7 +645,7 @@ static int add_frames_impl(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t
       }
       slots.push_back(q.ref);
     }
-    rc = frames_set_template_slots(c, slots.data(), nk, ctx_run(c));
+    rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
     if(!re.empty()) {
       const int mr = (int) re.size();
@@ -701,6 +753,115 @@ int bpvo_hip_seq_get_trajectory(bpvo_hip_ctx* c, int seq, float* poses)
   const std::vector<M44>& t = c->seqs[seq].trajectory;
   if(!poses && !t.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr poses");
   for(size_t i = 0; i < t.size(); ++i) std::memcpy(poses + 16 * i, t[i].m, 64);
+  return BPVO_OK;
+}
+
+// ---- per-sequence cameras ----------------------------------------------------------------------------------------------------------------
+// A camera's level geometry (level_geometry: the one derivation bpvo_hip_create uses) for L levels, after the checks every camera passes.
+// Returns the status, with what failed in *why.
+static int camera_geometry(const bpvo_hip_camera& cam, const bpvo_hip_params& p, bool auto_levels, int L, LevelGeom* g, std::string* why)
+{
+  for(int k = 0; k < 9; ++k)
+    if(!std::isfinite(cam.K[k])) { *why = "camera: K must be finite"; return BPVO_ERR_INVALID_ARG; }
+  if(!(cam.K[0] > 0.0f) || !(cam.K[4] > 0.0f)) { *why = "camera: fx and fy must be positive"; return BPVO_ERR_INVALID_ARG; }
+  if(cam.K[8] != 1.0f) { *why = "camera: K[8] must be 1"; return BPVO_ERR_INVALID_ARG; }
+  if(!std::isfinite(cam.baseline) || !(cam.baseline > 0.0f)) { *why = "camera: the baseline must be positive"; return BPVO_ERR_INVALID_ARG; }
+  if(cam.rows < 8 || cam.cols < 8 || cam.rows > 65535 || cam.cols > 65535 || (long long) cam.rows * cam.cols * 8 > 0x7fffffffLL) {
+    *why = "camera: image size out of range (8 .. 65535 rows and cols, at most 2^28 pixels)";
+    return BPVO_ERR_INVALID_ARG;
+  }
+  if(auto_levels) {      // bpvo/vo.cc:101-105, as bpvo_hip_create counts them
+    const int own = 1 + (int) std::round(std::log2(std::min(cam.rows, cam.cols) / (double) p.minImageDimensionForPyramid));
+    if(own != L) {
+      *why = "camera " + std::to_string(cam.cols) + "x" + std::to_string(cam.rows) + ": its automatic pyramid has " + std::to_string(own) +
+             " levels, the context's " + std::to_string(L);
+      return BPVO_ERR_UNSUPPORTED;
+    }
+  }
+  if(const char* w = level_geometry(cam.K, cam.baseline, cam.rows, cam.cols, L, p, g)) { *why = std::string("camera: ") + w; return BPVO_ERR_UNSUPPORTED; }
+  return BPVO_OK;
+}
+static bool same_geometry(const LevelGeom* a, const LevelGeom* b, int L)
+{
+  for(int l = 0; l < L; ++l)
+    if(a[l].rows != b[l].rows || a[l].cols != b[l].cols || a[l].npix != b[l].npix || a[l].nblk != b[l].nblk || a[l].cap != b[l].cap ||
+       a[l].nms_radius != b[l].nms_radius || a[l].b != b[l].b || std::memcmp(a[l].K, b[l].K, sizeof(a[l].K)) != 0)
+      return false;
+  return true;
+}
+// the camera of sequence s = the geometry of its three slots (a camera whose geometry is the context's own: none, the plain path)
+static void assign_camera(bpvo_hip_ctx* c, int s, const LevelGeom* g)
+{
+  const bool own = !same_geometry(g, c->geom, c->L);
+  for(int k = 0; k < 3; ++k) {
+    FrameSlot& f = c->frames[3 * s + k];
+    f.own_geom = own;
+    for(int l = 0; l < kMaxLevels; ++l) f.geom[l] = own && l < c->L ? g[l] : LevelGeom{};
+  }
+}
+
+int bpvo_hip_create_sequences(bpvo_hip_ctx** out, int n_sequences, const bpvo_hip_camera* cams, const bpvo_hip_params* p, int device)
+{
+  if(!out || n_sequences < 1 || !cams || !p) {
+    g_create_error = "invalid argument";
+    return BPVO_ERR_INVALID_ARG;
+  }
+  int rows = 0, cols = 0;
+  for(int s = 0; s < n_sequences; ++s) { rows = std::max(rows, cams[s].rows); cols = std::max(cols, cams[s].cols); }
+  const bool auto_levels = p->numPyramidLevels <= 0;
+  int L = p->numPyramidLevels;
+  if(auto_levels && rows >= 8 && cols >= 8) L = 1 + (int) std::round(std::log2(std::min(rows, cols) / (double) p->minImageDimensionForPyramid));
+  if(L < 1 || L > kMaxLevels) {
+    g_create_error = "numPyramidLevels out of range (1..8)";
+    return BPVO_ERR_UNSUPPORTED;
+  }
+  // every camera's geometry, and per level the largest template capacity among them
+  std::vector<LevelGeom> geoms((size_t) n_sequences * kMaxLevels);
+  int min_caps[kMaxLevels] = {};
+  for(int s = 0; s < n_sequences; ++s) {
+    std::string why;
+    const int rc = camera_geometry(cams[s], *p, auto_levels, L, &geoms[(size_t) s * kMaxLevels], &why);
+    if(rc) { g_create_error = "sequence " + std::to_string(s) + ": " + why; return rc; }
+    for(int l = 0; l < L; ++l) min_caps[l] = std::max(min_caps[l], geoms[(size_t) s * kMaxLevels + l].cap);
+  }
+  bpvo_hip_ctx* c = nullptr;
+  const int rc = create_impl(&c, cams[0].K, cams[0].baseline, rows, cols, p, device, 3 * n_sequences, n_sequences, min_caps);
+  if(rc) return rc;
+  for(int s = 0; s < n_sequences; ++s) assign_camera(c, s, &geoms[(size_t) s * kMaxLevels]);
+  c->vo_mode = 2;      // (its slots carry the sequences' cameras: bpvo_hip_add_frame would read frames of the context's size into them)
+  *out = c;
+  return BPVO_OK;
+}
+int bpvo_hip_seq_set_camera(bpvo_hip_ctx* c, int seq, const bpvo_hip_camera* cam)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  if(!cam) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr camera");
+  if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: per-sequence cameras serve bpvo_hip_add_frames");
+  for(int k = 0; k < 3; ++k)
+    if(c->frames[3 * seq + k].has_data || c->frames[3 * seq + k].has_template)
+      return seq_fail(c, BPVO_ERR_INVALID_ARG, seq, "holds frames: its camera changes only while it is fresh or after bpvo_hip_seq_reset");
+  LevelGeom g[kMaxLevels];
+  std::string why;
+  int rc = camera_geometry(*cam, c->params, c->auto_levels, c->L, g, &why);
+  if(rc) return seq_fail(c, rc, seq, why.c_str());
+  if(cam->rows > c->rows || cam->cols > c->cols)
+    return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, ("camera " + std::to_string(cam->cols) + "x" + std::to_string(cam->rows) + " larger than the context's " +
+                                                   std::to_string(c->cols) + "x" + std::to_string(c->rows)).c_str());
+  for(int l = 0; l < c->L; ++l)
+    if(g[l].cap > c->geom[l].cap)
+      return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, ("camera needs a template capacity of " + std::to_string(g[l].cap) + " points at level " + std::to_string(l) +
+                                                     ", the context holds " + std::to_string(c->geom[l].cap)).c_str());
+  assign_camera(c, seq, g);
+  c->vo_mode = 2;      // a context with per-sequence cameras serves bpvo_hip_add_frames
+  return BPVO_OK;
+}
+int bpvo_hip_seq_get_camera(const bpvo_hip_ctx* c, int seq, bpvo_hip_camera* cam)
+{
+  if(!c || !cam || seq < 0 || seq >= seq_capacity(c)) return BPVO_ERR_INVALID_ARG;
+  const LevelGeom& g = slot_geom(c, c->frames[3 * seq], 0);
+  std::memcpy(cam->K, g.K, sizeof(cam->K));
+  cam->baseline = g.b;
+  cam->rows = g.rows; cam->cols = g.cols;
   return BPVO_OK;
 }
 #undef CHECK_SEQ

@@ -325,13 +325,16 @@ def make_stereo_pair(rows: int, cols: int, index: int = 0, z0: float = 10.0, sce
 
 
 def make_sequence(rows: int, cols: int, n_frames: int, index: int = 0, step_rot: float = 0.004, step_trans: float = 0.03, scene: str = "plane",
-                  disp_range=None):
+                  disp_range=None, camera=None):
     """A short camera trajectory over the same plane for addFrame tests: list of (img, disp) and absolute poses.  scene="layered": over the
     layered scene of make_pair instead (the same trajectory), every disparity map with holes of its own, noise on every frame after the
-    first."""
+    first.  camera=(K 3x3, baseline): render with that camera (disparity = fx * b / Z) instead of calibration(rows, cols)."""
     seed = 1000 + int(index)
     rng = np.random.default_rng(seed)
-    K, b = calibration(rows, cols)
+    if camera is None:
+        K, b = calibration(rows, cols)
+    else:
+        K, b = np.asarray(camera[0], dtype=np.float32).reshape(3, 3), float(camera[1])
     if scene == "layered":
         layers = _layered_geometry(K, b, rows, cols, seed, disp_range or default_disp_range(rows, cols))
     else:

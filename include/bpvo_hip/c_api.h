@@ -247,6 +247,30 @@ int bpvo_hip_seq_get_point_cloud(bpvo_hip_ctx* ctx, int seq, bpvo_hip_point_with
 int bpvo_hip_seq_trajectory_size(bpvo_hip_ctx* ctx, int seq, int* n);                                      /* trajectory.cc:42-50 */
 int bpvo_hip_seq_get_trajectory(bpvo_hip_ctx* ctx, int seq, float* poses /*[n][16]*/);
 
+/* ---- per-sequence cameras: each sequence of bpvo_hip_add_frames with its own calibration and image size.
+ * A sequence whose camera is the context's own runs exactly what it runs without one.  Frame i of a bpvo_hip_add_frames call then takes
+ * rows_s x cols_s pixels of images / disparities, s = seq[i], the frames back to back in call order (all cameras of the context's size:
+ * the [n][rows*cols] layout above).  Each sequence's results equal bit for bit those of a bpvo_hip_create context of its camera.
+ * bpvo_hip_create_sequences: a context for n_sequences sequences (n_frames = 3 S, n_pairs = S); sequence s starts with camera cams[s].
+ *   Its image size is the largest rows and the largest cols over the cameras; per pyramid level, its template capacity is the largest of
+ *   the cameras' own (a camera whose level falls below minNumPixelsForNonMaximaSuppression keeps a dense capacity there).  The context's
+ *   own camera, the one the single-context entry points use, is cams[0] grown to that size.  With numPyramidLevels <= 0 (automatic,
+ *   vo.cc:101-105) every camera's own level count must equal the context's (BPVO_ERR_UNSUPPORTED otherwise).
+ * bpvo_hip_seq_set_camera: only while the sequence holds no frame (fresh, or after bpvo_hip_seq_reset; BPVO_ERR_INVALID_ARG otherwise), not
+ *   on a context that runs bpvo_hip_add_frame.  Both commit the context to bpvo_hip_add_frames (bpvo_hip_add_frame then refuses it).  The camera must fit the context's storage, which never grows: rows, cols and every level's
+ *   template capacity within the context's (BPVO_ERR_UNSUPPORTED, with the level and both capacities in bpvo_hip_last_error).
+ * Every camera is checked before anything changes: finite K, fx > 0, fy > 0, K[8] = 1, baseline > 0 (BPVO_ERR_INVALID_ARG), no pyramid
+ * level under 8 pixels and the context's level count (BPVO_ERR_UNSUPPORTED). */
+typedef struct bpvo_hip_camera {
+  float K[9];
+  float baseline;
+  int rows, cols;
+} bpvo_hip_camera;
+int bpvo_hip_create_sequences(bpvo_hip_ctx** out, int n_sequences, const bpvo_hip_camera* cams /*[n_sequences]*/, const bpvo_hip_params* p,
+                              int device);
+int bpvo_hip_seq_set_camera(bpvo_hip_ctx* ctx, int seq, const bpvo_hip_camera* cam);
+int bpvo_hip_seq_get_camera(const bpvo_hip_ctx* ctx, int seq, bpvo_hip_camera* cam);
+
 /* ---- batches of independent frame pairs (BASELINE.json config 5).
  * Pair p uses frame slots 2p (reference/template frame A) and 2p+1 (current frame B) and workspace p.
  * For each pair: A.setData, A.setTemplate, B.setData, estimatePose(A, B, Identity) -> poses[p].

@@ -19,6 +19,7 @@
 #ifndef BPVO_HIP_VO_HPP
 #define BPVO_HIP_VO_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstring>
 #include <memory>
@@ -151,6 +152,13 @@ class Device {
   {
     const int rc = bpvo_hip_create(&_ctx, K.data(), baseline, size.rows, size.cols, &p, device, n_frames, n_pairs);
     if(rc != BPVO_OK) throw Error(std::string("bpvo_hip_create: ") + bpvo_hip_last_error(nullptr));
+  }
+  /* bpvo_hip_create_sequences: one camera per sequence; the context's size is the largest of theirs */
+  Device(const std::vector<bpvo_hip_camera>& cams, const AlgorithmParameters& p, int device = 0) : _ctx(nullptr), _size()
+  {
+    const int rc = bpvo_hip_create_sequences(&_ctx, (int) cams.size(), cams.data(), &p, device);
+    if(rc != BPVO_OK) throw Error(std::string("bpvo_hip_create_sequences: ") + bpvo_hip_last_error(nullptr));
+    for(const bpvo_hip_camera& c : cams) { _size.rows = std::max(_size.rows, c.rows); _size.cols = std::max(_size.cols, c.cols); }
   }
   ~Device() { bpvo_hip_destroy(_ctx); }
   Device(const Device&) = delete;
@@ -384,15 +392,41 @@ class VisualOdometry {
  * its own fed the same frames.  No counterpart in the reference. */
 class VisualOdometrySequences {
  public:
+  /* one calibration and image size of a sequence (bpvo_hip_camera) */
+  struct Camera {
+    Matrix33 K;
+    float baseline;
+    ImageSize size;
+    Camera() : K(), baseline(0.0f), size() {}
+    Camera(const Matrix33& K_, float b, ImageSize s) : K(K_), baseline(b), size(s) {}
+  };
+
   VisualOdometrySequences(const Matrix33& K, float baseline, ImageSize image_size, int num_sequences,
                           const AlgorithmParameters& params = AlgorithmParameters(), int device = 0)
       : _dev(std::make_shared<detail::Device>(K, baseline, image_size, params, 3 * num_sequences, num_sequences, device)),
         _trajectories((size_t) (num_sequences > 0 ? num_sequences : 0)) {}
+  /* sequence s with cameras[s] (bpvo_hip_create_sequences: the context's image size is the largest rows and cols among them) */
+  VisualOdometrySequences(const std::vector<Camera>& cameras, const AlgorithmParameters& params = AlgorithmParameters(), int device = 0)
+      : _dev(std::make_shared<detail::Device>(toC(cameras), params, device)), _trajectories(cameras.size()) {}
 
   int numSequences() const { int n = 0; _dev->check(bpvo_hip_seq_capacity(_dev->ctx(), &n)); return n; }
 
-  /* images / disparities: n frames of rows * cols pixels, back to back; frame i is the next frame of sequence seq[i] (seq = nullptr:
-   * sequences 0 .. n-1; n = -1: every sequence).  Each Result carries its point cloud, as VisualOdometry::addFrame's does. */
+  /* the camera of sequence s, changed only while it holds no frame (new, or after reset(s)) and within the context's size */
+  void setCamera(int s, const Camera& cam) { const bpvo_hip_camera c = toC(cam); _dev->check(bpvo_hip_seq_set_camera(_dev->ctx(), s, &c)); }
+  Camera camera(int s) const
+  {
+    bpvo_hip_camera c;
+    _dev->check(bpvo_hip_seq_get_camera(_dev->ctx(), s, &c));
+    Camera r;
+    std::memcpy(r.K.data(), c.K, sizeof(c.K));
+    r.baseline = c.baseline;
+    r.size = ImageSize(c.rows, c.cols);
+    return r;
+  }
+
+  /* images / disparities: n frames back to back, frame i of its sequence's size (camera(seq[i]).size; one context-wide camera: rows * cols
+   * pixels each); frame i is the next frame of sequence seq[i] (seq = nullptr: sequences 0 .. n-1; n = -1: every sequence).  Each Result
+   * carries its point cloud, as VisualOdometry::addFrame's does. */
   std::vector<Result> addFrames(const uint8_t* images, const float* disparities, const int* seq = nullptr, int n = -1)
   {
     if(images == nullptr || disparities == nullptr) throw Error("nullptr image/disparity");
@@ -421,6 +455,20 @@ class VisualOdometrySequences {
   double getOption(const std::string& name) const { return _dev->getOption(name); }
 
  private:
+  static bpvo_hip_camera toC(const Camera& cam)
+  {
+    bpvo_hip_camera c;
+    std::memcpy(c.K, cam.K.data(), sizeof(c.K));
+    c.baseline = cam.baseline;
+    c.rows = cam.size.rows; c.cols = cam.size.cols;
+    return c;
+  }
+  static std::vector<bpvo_hip_camera> toC(const std::vector<Camera>& cams)
+  {
+    std::vector<bpvo_hip_camera> v;
+    for(const Camera& c : cams) v.push_back(toC(c));
+    return v;
+  }
   Result makeResult(int s, const bpvo_hip_result& r)
   {
     Result ret;
