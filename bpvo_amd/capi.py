@@ -90,6 +90,21 @@ def pack_frames(images, disps):
     return img, disp, shapes
 
 
+def pack_images(images):
+    """u8 frames of possibly different sizes back to back (the left or the right images of a stereo call): (u8 [sum of pixels],
+    [(rows, cols)] per frame) — pack_frames' layout without the disparities."""
+    shapes = []
+    for im in images:
+        assert np.ndim(im) == 2, "frames are 2-D"
+        shapes.append(tuple(int(v) for v in np.shape(im)))
+    out = np.empty(sum(r * w for r, w in shapes), np.uint8)
+    at = 0
+    for (r, w), im in zip(shapes, images):
+        out[at:at + r * w] = np.asarray(im, dtype=np.uint8).reshape(-1)
+        at += r * w
+    return out, shapes
+
+
 def unpack_frames(img, disp, shapes):
     """pack_frames' inverse: lists of [rows, cols] arrays."""
     out_i, out_d, at = [], [], 0
@@ -400,9 +415,7 @@ class Context:
         right = np.ascontiguousarray(right, dtype=np.uint8)
         r = Result()
         self.call("add_frame_stereo", left.ctypes.data_as(C.c_void_p), right.ctypes.data_as(C.c_void_p), C.byref(sp), C.byref(r))
-        return dict(pose=np.array(r.pose, np.float32).reshape(4, 4), stats=[dict(numIterations=s.numIterations, finalError=s.finalError,
-                    firstOrderOptimality=s.firstOrderOptimality, status=s.status) for s in r.optimizerStatistics[: r.numLevels]],
-                    isKeyFrame=bool(r.isKeyFrame), keyFramingReason=r.keyFramingReason, hasPointCloud=bool(r.hasPointCloud))
+        return self._result_dict(r)
 
     def add_frame_null(self):
         """addFrame(nullptr, nullptr) — must fail like THROW_ERROR_IF at bpvo/vo.cc:68-69."""
@@ -485,6 +498,71 @@ class Context:
         ids, p_ids = self._seq_ids(n, seq)
         res = (Result * n)()
         self.call("add_frames", int(n), p_ids, C.c_void_p(d_images_ptr), C.c_void_p(d_disps_ptr), 1, res)
+        return [self._result_dict(r) for r in res]
+
+    # -- the stereo front-end for many cameras (bpvo_hip_stereo_frames, bpvo_hip_add_frames_stereo)
+    @staticmethod
+    def _camera_array(cams_or_sizes):
+        """Cameras, (K, baseline, rows, cols) tuples or bare (rows, cols) sizes -> a ctypes array (the stereo front-end reads rows / cols only)."""
+        if isinstance(cams_or_sizes, C.Array):      # (one made earlier: a caller that times the call builds it once)
+            return cams_or_sizes
+        out = (Camera * len(cams_or_sizes))()
+        for i, c in enumerate(cams_or_sizes):
+            if isinstance(c, Camera):
+                out[i] = c
+            elif len(c) == 2:
+                out[i] = camera(np.eye(3), 1.0, c[0], c[1])
+            else:
+                out[i] = camera(*c)
+        return out
+
+    def stereo_frames(self, cams_or_sizes, lefts, rights, sp):
+        """bpvo_hip_stereo_frames: pair i (2-D u8 arrays lefts[i], rights[i]) has the size of cams_or_sizes[i] (a Camera, a (K, baseline, rows,
+        cols) tuple or a bare (rows, cols)); returns the list of f32 disparity maps, each of its pair's shape."""
+        n = len(cams_or_sizes)
+        assert len(lefts) == n and len(rights) == n, "one pair per camera"
+        cams = self._camera_array(cams_or_sizes)
+        for i in range(n):
+            want = (cams[i].rows, cams[i].cols)
+            assert np.shape(lefts[i]) == want and np.shape(rights[i]) == want, f"pair {i}: camera {i} takes {want[0]}x{want[1]} images"
+        left, shapes = pack_images(lefts)
+        right, _ = pack_images(rights)
+        out = np.empty(left.size, np.float32)
+        self.call("stereo_frames", n, cams, left.ctypes.data_as(C.c_void_p), right.ctypes.data_as(C.c_void_p), 0, C.byref(sp), out.ctypes.data_as(C.c_void_p), 0)
+        maps, at = [], 0
+        for r, w in shapes:
+            maps.append(out[at:at + r * w].reshape(r, w))
+            at += r * w
+        return maps
+
+    def stereo_frames_device(self, cams_or_sizes, d_left_ptr, d_right_ptr, sp, d_disp_ptr):
+        """stereo_frames with the packed images already in device memory, the packed f32 maps written to device memory."""
+        cams = self._camera_array(cams_or_sizes)
+        self.call("stereo_frames", len(cams), cams, C.c_void_p(d_left_ptr), C.c_void_p(d_right_ptr), 1, C.byref(sp), C.c_void_p(d_disp_ptr), 1)
+
+    def add_frames_stereo(self, lefts, rights, sp, seq=None):
+        """bpvo_hip_add_frames_stereo: pair i (2-D u8 arrays, or stacks [n, rows, cols]) is the next frame of sequence seq[i] (None: 0 .. n-1),
+        of that sequence's camera size; the disparities are computed on the device.  Returns n dicts in add_frame's format."""
+        n = len(lefts)
+        assert len(rights) == n, "one right image per left image"
+        ids, p_ids = self._seq_ids(n, seq)
+        for i in range(n):
+            s = int(ids[i]) if ids is not None else i
+            if 0 <= s < self.seq_capacity():
+                cam = self.seq_get_camera(s)
+                want = (cam.rows, cam.cols)
+                assert np.shape(lefts[i]) == want and np.shape(rights[i]) == want, f"pair {i}: sequence {s} takes {want[0]}x{want[1]} images"
+        left, _ = pack_images(lefts)
+        right, _ = pack_images(rights)
+        res = (Result * n)()
+        self.call("add_frames_stereo", n, p_ids, left.ctypes.data_as(C.c_void_p), right.ctypes.data_as(C.c_void_p), 0, C.byref(sp), res)
+        return [self._result_dict(r) for r in res]
+
+    def add_frames_stereo_device(self, n, d_left_ptr, d_right_ptr, sp, seq=None):
+        """add_frames_stereo with the n packed pairs already in device memory."""
+        ids, p_ids = self._seq_ids(n, seq)
+        res = (Result * n)()
+        self.call("add_frames_stereo", int(n), p_ids, C.c_void_p(d_left_ptr), C.c_void_p(d_right_ptr), 1, C.byref(sp), res)
         return [self._result_dict(r) for r in res]
 
     def seq_capacity(self):

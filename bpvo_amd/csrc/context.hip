@@ -299,6 +299,10 @@ const std::vector<OptionDef>& option_table()
     OPT_INT("team_join_from_pairs", team_join_from_pairs, 0, 1 << 20),
     OPT_INT("team_spares", team_spares, 0, 1),
     OPT_INT("vo_disparity_late", vo_disparity_late, 0, 1),
+    OPT_INT("stereo_frames_per_launch", stereo_frames_per_launch, 0, 65535),
+    // read-only (bpvo_hip_get_option): the frames per launch of the last SGM call and the free device memory (MiB) its rule saw
+    OptionDef{"stereo_frames_per_launch_seen", 0, 0, [](bpvo_hip_ctx* c) { return (double) c->st_frames_per_launch_seen; }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
+    OptionDef{"stereo_free_mib_seen", 0, 0, [](bpvo_hip_ctx* c) { return (double) (c->st_free_seen >> 20); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
     OPT_INT("normalization_side_stream", nrm_side_stream, 0, 1),
     OPT_INT("normalization_form", nrm_dpp_asm, 0, 4),
     OPT_INT("small_batch_fused", small_batch_fused, 0, 1),
@@ -701,6 +705,8 @@ void bpvo_hip_destroy(bpvo_hip_ctx* c)
   (void) hipFree(c->d_count); (void) hipFree(c->d_counters); (void) hipFree(c->d_tickets); (void) hipFree(c->d_trace);
   (void) hipFree(c->st_left); (void) hipFree(c->st_right); (void) hipFree(c->st_left_pre); (void) hipFree(c->st_right_pre); (void) hipFree(c->st_disp);
   (void) hipFree(c->st_sgm);
+  (void) hipFree(c->d_st_frames); (void) hipHostFree(c->h_st_frames);
+  if(c->st_tab_ev) (void) hipEventDestroy(c->st_tab_ev);
   (void) hipFree(c->d_seq_cloud); (void) hipFree(c->d_seq_jobs); (void) hipFree(c->d_cloud_jobs); (void) hipFree(c->d_seq_cnt);
   (void) hipHostFree(c->h_seq_jobs); (void) hipHostFree(c->h_cloud_jobs); (void) hipHostFree(c->h_seq_cnt);
   for(auto st : c->up_streams) if(st) { (void) hipStreamSynchronize(st); (void) hipStreamDestroy(st); }

@@ -277,12 +277,22 @@ struct bpvo_hip_ctx {
   float* d_trace = nullptr;
   int trace_cap = 0, trace_ws = -1;
   int max_lanes_now = 1 << 30; // bpvo_hip_set_max_lanes: measurement runs that need per-launch timings without overlap
-  // stereo front-end scratch (lazily sized for the largest frame count seen): raw and pre-filtered u8 pairs, f32 disparities
+  // stereo front-end scratch (lazily sized for the most pixels a call has held, the sum over its frames): raw and pre-filtered u8 pairs, f32 disparities
   uint8_t* st_left = nullptr; uint8_t* st_right = nullptr; uint8_t* st_left_pre = nullptr; uint8_t* st_right_pre = nullptr;
   float* st_disp = nullptr;
-  int st_frames = 0;
-  void* st_sgm = nullptr;      // scratch of the semi-global matcher (cost volumes: sized for the largest disparity range seen)
+  size_t st_pixels = 0;
+  void* st_sgm = nullptr;      // scratch of the semi-global matchers (cost volumes: the largest frame x disparity range x frames per launch seen)
   size_t st_sgm_bytes = 0;
+  // calls whose frames differ in size: the block matcher's frame table (kernels.h StereoFrame), filled in pinned memory and copied on the
+  // stream; st_tab_ev: behind the last copy (the pinned rows are rewritten only once it has passed)
+  StereoFrame* h_st_frames = nullptr; StereoFrame* d_st_frames = nullptr;
+  int st_tab_cap = 0;
+  hipEvent_t st_tab_ev = nullptr;
+  // option "stereo_frames_per_launch": SGM frames of one size that go through each kernel together; 0: as many as fit a third of the device
+  // memory that was free when the SGM scratch was first needed (st_sgm_budget, read once per context), 1: one after the other, k: at most k
+  int stereo_frames_per_launch = 0;
+  size_t st_sgm_budget = 0, st_free_seen = 0;
+  int st_frames_per_launch_seen = 0;      // what the last SGM launch used (measurement: option "stereo_frames_per_launch_seen")
   // Upload pipeline of pair batches handed over in HOST buffers (bpvo_hip_batch_run, on_device = 0): worker threads stage chunks of
   // kUploadChunkPairs pairs in pinned memory and copy them on a stream of their own into a device staging area, chunk after chunk in lane
   // order, while the lanes already work on the chunks that have landed (upload_pipeline below).  Option "upload_workers" (0 = off).

@@ -88,14 +88,20 @@ void launch_template_build(hipStream_t s, const FrameJob* jobs, int C, int max_p
                            int job_pitch = 0);   // gauss_k: the bit-planes blur taps (lazy levels)
 
 // stereo front-end (kernels_stereo.hip): OpenCV 2.4 block matching with the reference's parameters, batched over frames
+// A frame of a call whose frames differ in size: its size and where its pixels start in the packed images and maps (device table, a row per frame)
+struct StereoFrame { int rows, cols; size_t offset; };
 struct StereoLaunch {
   const uint8_t* left_pre;    // [nframes][rows*cols] pre-filtered images
   const uint8_t* right_pre;
   float* disp;                // [nframes][rows*cols]
   int rows, cols, nframes;
+  const StereoFrame* frames = nullptr;   // non-null: the table form — frame f is frames[f], rows x cols the largest of them, total_pixels their sum
+  size_t total_pixels = 0;
   int wsz, ndisp, mindisp, cap, texture_threshold, uniqueness_ratio;
 };
 void launch_stereo_prefilter(hipStream_t s, const uint8_t* src, uint8_t* dst, int rows, int cols, int cap, int nframes);
+void launch_stereo_prefilter_frames(hipStream_t s, const uint8_t* src, uint8_t* dst, const StereoFrame* frames /*device*/, int max_rows, int max_cols,
+                                    int cap, int nframes);
 bool launch_stereo_bm(hipStream_t s, const StereoLaunch& g);   // false: window size / disparity range outside what the kernel serves
 
 // semi-global matching (kernels_sgm.hip): the reference's in-tree SgmStereo (utils/sgm.cc)
@@ -103,8 +109,9 @@ struct SgmLaunch {
   const uint8_t* left;      // [nframes][rows*cols]
   const uint8_t* right;
   float* disp;              // [nframes][rows*cols]
-  void* scratch;            // sgm_scratch_bytes(rows, cols, ndisp) bytes, shared by the frames (processed one after the other)
+  void* scratch;            // frames_per_launch x sgm_scratch_bytes(rows, cols, ndisp) bytes: a slice per frame of a launch, reused by the next launch
   int rows, cols, nframes;
+  int frames_per_launch = 1; // frames that go through every kernel together (the grid's last dimension); 1: one frame after the other
   int ndisp, sobel_cap, census_radius, window_radius, P1, P2, consistency_threshold;
   double disparity_factor, census_weight;
 };
@@ -112,7 +119,9 @@ size_t sgm_scratch_bytes(int rows, int cols, int ndisp);
 bool launch_stereo_sgm(hipStream_t s, const SgmLaunch& g);   // false: disparity range outside what the kernels serve (multiple of 16, <= 256)
 // filterSpeckles on a u16 map whose invalid value is 0 (kernels_sgm.hip's union-find kernels): 4-connected regions (neighbours both non-zero,
 // |difference| <= max_diff) of at most max_size pixels are zeroed; lab / size: rows * cols ints each
-void launch_speckle_filter_u16(hipStream_t s, uint16_t* img, int* lab, int* size, int rows, int cols, int max_diff, int max_size);
+// nframes > 1: frame f on the pointers advanced by f * frame_bytes bytes, in the same launches
+void launch_speckle_filter_u16(hipStream_t s, uint16_t* img, int* lab, int* size, int rows, int cols, int max_diff, int max_size, int nframes = 1,
+                               size_t frame_bytes = 0);
 
 // semi-global block matching (kernels_sgbm.hip): cv::StereoSGBM of OpenCV 2.4, single-pass mode, + medianBlur(3) + filterSpeckles + / 16
 struct SgbmLaunch {

@@ -31,12 +31,24 @@ namespace {
 
 __device__ __forceinline__ int sat16(int v) { return min(32767, max(-32768, v)); }
 
+// Frame f of a launch (the grid's last dimension): the images and the f32 map advance by the frame's pixels, every scratch pointer by ONE
+// stride in bytes — frame f works on the f-th copy of the whole scratch layout (sgm_scratch_bytes, a multiple of 256).  What a kernel
+// indexes stays relative to its own frame: the labels of the union-find are pixel indices of the frame, its atomics never leave it.
+template <class T>
+__device__ __forceinline__ T* sgm_frame(T* p, size_t stride_bytes, unsigned f)
+{
+  return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + stride_bytes * f);
+}
+
 __global__ __launch_bounds__(256) void sgm_census_sobel_kernel(const uint8_t* __restrict__ img, uint8_t* __restrict__ sobel, int* __restrict__ census,
-                                                              int rows, int cols, int pitch, int cap, int crad, int flip)
+                                                              int rows, int cols, int pitch, int cap, int crad, int flip, size_t fs)
 {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if(y >= rows) return;
+  img += (size_t) rows * cols * blockIdx.z;
+  sobel = sgm_frame(sobel, fs, blockIdx.z);
+  census = sgm_frame(census, fs, blockIdx.z);
   // the row pitch is wider than the image: the padding (and the image border) holds `cap` (memset in the original)
   if(x >= cols) {
     if(x < pitch) sobel[(size_t) pitch * y + x] = (uint8_t) cap;
@@ -83,8 +95,10 @@ __device__ __forceinline__ void half_minmax(const uint8_t* __restrict__ row, int
 constexpr int SPC_TX = 32, SPC_MAXD = 256;
 __global__ __launch_bounds__(256) void sgm_pixel_cost_tile_kernel(const uint8_t* __restrict__ sl, const uint8_t* __restrict__ sr, const int* __restrict__ cl,
                                                                    const int* __restrict__ cr, uint8_t* __restrict__ pc, int rows, int cols, int pitch, int D,
-                                                                   double cweight)
+                                                                   double cweight, size_t fs)
 {
+  sl = sgm_frame(sl, fs, blockIdx.z); sr = sgm_frame(sr, fs, blockIdx.z); cl = sgm_frame(cl, fs, blockIdx.z); cr = sgm_frame(cr, fs, blockIdx.z);
+  pc = sgm_frame(pc, fs, blockIdx.z);
   __shared__ uint8_t s_lc[SPC_TX], s_lmin[SPC_TX], s_lmax[SPC_TX];
   __shared__ int s_cl[SPC_TX];
   __shared__ uint8_t s_rc[SPC_TX + SPC_MAXD], s_rmin[SPC_TX + SPC_MAXD], s_rmax[SPC_TX + SPC_MAXD];
@@ -147,8 +161,10 @@ __global__ __launch_bounds__(256) void sgm_pixel_cost_tile_kernel(const uint8_t*
 // window's columns first (u16, at most (2r+1) * 255), then over its rows — 2 (2r+1) reads per output instead of (2r+1)^2; integer sums,
 // any order (round 3 evaluated the 25 clamped taps per output directly: 0.6 ms per 1241 x 376 x 128 frame, profiles/r03_stereo.txt).
 // A thread owns four consecutive disparities of one pixel: 4-byte / 8-byte accesses, coalesced along d.
-__global__ __launch_bounds__(256) void sgm_box_rows_kernel(const uint8_t* __restrict__ pc, uint16_t* __restrict__ rowsum, int rows, int cols, int D, int wrad)
+__global__ __launch_bounds__(256) void sgm_box_rows_kernel(const uint8_t* __restrict__ pc, uint16_t* __restrict__ rowsum, int rows, int cols, int D, int wrad, size_t fs)
 {
+  pc = sgm_frame(pc, fs, blockIdx.y);
+  rowsum = sgm_frame(rowsum, fs, blockIdx.y);
   const size_t t = (size_t) blockIdx.x * 256 + threadIdx.x;          // (pixel, group of 4 disparities)
   const int dq = D >> 2;
   const size_t p = t / dq;
@@ -164,8 +180,10 @@ __global__ __launch_bounds__(256) void sgm_box_rows_kernel(const uint8_t* __rest
   }
   *reinterpret_cast<ushort4*>(rowsum + p * D + d) = make_ushort4((uint16_t) s0, (uint16_t) s1, (uint16_t) s2, (uint16_t) s3);
 }
-__global__ __launch_bounds__(256) void sgm_box_cols_kernel(const uint16_t* __restrict__ rowsum, uint16_t* __restrict__ cost, int rows, int cols, int D, int wrad)
+__global__ __launch_bounds__(256) void sgm_box_cols_kernel(const uint16_t* __restrict__ rowsum, uint16_t* __restrict__ cost, int rows, int cols, int D, int wrad, size_t fs)
 {
+  rowsum = sgm_frame(rowsum, fs, blockIdx.y);
+  cost = sgm_frame(cost, fs, blockIdx.y);
   const size_t t = (size_t) blockIdx.x * 256 + threadIdx.x;
   const int dq = D >> 2;
   const size_t p = t / dq;
@@ -183,8 +201,10 @@ __global__ __launch_bounds__(256) void sgm_box_cols_kernel(const uint16_t* __res
   *reinterpret_cast<ushort4*>(cost + p * D + d) = make_ushort4((uint16_t) s0, (uint16_t) s1, (uint16_t) s2, (uint16_t) s3);
 }
 
-__global__ void sgm_right_cost_kernel(const uint16_t* __restrict__ lcost, uint16_t* __restrict__ rcost, int rows, int cols, int D)
+__global__ void sgm_right_cost_kernel(const uint16_t* __restrict__ lcost, uint16_t* __restrict__ rcost, int rows, int cols, int D, size_t fs)
 {
+  lcost = sgm_frame(lcost, fs, blockIdx.z);
+  rcost = sgm_frame(rcost, fs, blockIdx.z);
   const int x = blockIdx.x, y = blockIdx.y, d = threadIdx.x;
   if(d >= D) return;
   const int dd = min(d, cols - 1 - x);                         // past the image the last valid disparity's cost repeats
@@ -195,8 +215,10 @@ __global__ void sgm_right_cost_kernel(const uint16_t* __restrict__ lcost, uint16
 // the volume in requests: profiles/r04_stereo_pmc.txt).  Here a workgroup fetches the SRC_TX + D - 1 rows its SRC_TX pixels reach as
 // whole rows (16-byte loads; neighbouring tiles share most of them in the L2) and reads the diagonal from LDS.
 constexpr int SRC_TX = 64, SRC_MAXD = 128, SRC_PITCH = SRC_MAXD + 8;      // halfwords per staged row: 272 bytes, 16-byte aligned, banks spread along the diagonal
-__global__ __launch_bounds__(256) void sgm_right_cost_tile_kernel(const uint16_t* __restrict__ lcost, uint16_t* __restrict__ rcost, int rows, int cols, int D)
+__global__ __launch_bounds__(256) void sgm_right_cost_tile_kernel(const uint16_t* __restrict__ lcost, uint16_t* __restrict__ rcost, int rows, int cols, int D, size_t fs)
 {
+  lcost = sgm_frame(lcost, fs, blockIdx.y);
+  rcost = sgm_frame(rcost, fs, blockIdx.y);
   __shared__ __attribute__((aligned(16))) uint16_t s_rows[(SRC_TX + SRC_MAXD - 1) * SRC_PITCH];
   // Workgroups are handed to the XCDs round robin, and every XCD has its own L2: consecutive tiles of a row, which share all but SRC_TX of
   // their rows, go to ONE XCD (each takes a contiguous eighth of the tiles): 563 -> 119.5 MB read per 1241 x 376 x 128 frame, the volume itself.
@@ -251,9 +273,10 @@ __device__ __forceinline__ sgm_s16x2 sgm_pk(unsigned u) { return __builtin_bit_c
 __device__ __forceinline__ unsigned sgm_bits(sgm_s16x2 v) { return __builtin_bit_cast(unsigned, v); }
 template <int NP>
 __global__ __launch_bounds__(64) void sgm_path_packed_kernel(const uint16_t* __restrict__ cost_l, const uint16_t* __restrict__ cost_r, int16_t* __restrict__ Lvol,
-                                                             int rows, int cols, int D, int P1, int P2)
+                                                             int rows, int cols, int D, int P1, int P2, size_t fs)
 {
   constexpr int PF = SGM_PF, V = 2 * NP;
+  cost_l = sgm_frame(cost_l, fs, blockIdx.y); cost_r = sgm_frame(cost_r, fs, blockIdx.y); Lvol = sgm_frame(Lvol, fs, blockIdx.y);
   // dispatch order: the rows of both cost volumes first (with cols > rows the longest chains of the launch), then the columns
   int side, path, line;
   {
@@ -360,8 +383,10 @@ __device__ __forceinline__ int sgm_sum4(const int16_t* __restrict__ L, size_t vo
   return sat16(s + (int) L[3 * vol + i]);
 }
 template <int V>
-__global__ __launch_bounds__(256) void sgm_wta_kernel(const int16_t* __restrict__ L4, uint16_t* __restrict__ disp, size_t npix, int D, double factor)
+__global__ __launch_bounds__(256) void sgm_wta_kernel(const int16_t* __restrict__ L4, uint16_t* __restrict__ disp, size_t npix, int D, double factor, size_t fs)
 {
+  L4 = sgm_frame(L4, fs, blockIdx.y);
+  disp = sgm_frame(disp, fs, blockIdx.y);
   const size_t p = (size_t) blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if(p >= npix) return;
@@ -435,8 +460,9 @@ __device__ __forceinline__ void uf_union(int* __restrict__ lab, int a, int b)
 // linking every neighbour pair (round 3: 0.27 ms per launch on a 1241 x 376 plane, every pixel of which is one component).
 __device__ __forceinline__ bool sgm_connected(int a, int b, int max_diff) { return a != 0 && b != 0 && abs(a - b) <= max_diff; }
 __global__ __launch_bounds__(256) void sgm_cc_init_kernel(const uint16_t* __restrict__ img, int* __restrict__ lab, int* __restrict__ size, int rows, int cols,
-                                                         int max_diff)
+                                                         int max_diff, size_t fs)
 {
+  img = sgm_frame(img, fs, blockIdx.y); lab = sgm_frame(lab, fs, blockIdx.y); size = sgm_frame(size, fs, blockIdx.y);
   const int p = blockIdx.x * 256 + threadIdx.x;
   const int npix = rows * cols;
   const int lane = threadIdx.x & 63;
@@ -450,8 +476,10 @@ __global__ __launch_bounds__(256) void sgm_cc_init_kernel(const uint16_t* __rest
   lab[p] = v != 0 ? p - (lane - first) : -1;
   size[p] = 0;
 }
-__global__ __launch_bounds__(256) void sgm_cc_merge_kernel(const uint16_t* __restrict__ img, int* __restrict__ lab, int rows, int cols, int max_diff)
+__global__ __launch_bounds__(256) void sgm_cc_merge_kernel(const uint16_t* __restrict__ img, int* __restrict__ lab, int rows, int cols, int max_diff, size_t fs)
 {
+  img = sgm_frame(img, fs, blockIdx.y);
+  lab = sgm_frame(lab, fs, blockIdx.y);
   const int p = blockIdx.x * 256 + threadIdx.x;
   if(p >= rows * cols) return;
   const int v = img[p];
@@ -471,8 +499,10 @@ __global__ __launch_bounds__(256) void sgm_cc_merge_kernel(const uint16_t* __res
     }
   }
 }
-__global__ __launch_bounds__(256) void sgm_cc_count_kernel(int* __restrict__ lab, int* __restrict__ size, int npix)
+__global__ __launch_bounds__(256) void sgm_cc_count_kernel(int* __restrict__ lab, int* __restrict__ size, int npix, size_t fs)
 {
+  lab = sgm_frame(lab, fs, blockIdx.y);
+  size = sgm_frame(size, fs, blockIdx.y);
   const int p = blockIdx.x * 256 + threadIdx.x;
   int r = -1;
   if(p < npix && lab[p] >= 0) {
@@ -501,8 +531,9 @@ __global__ __launch_bounds__(256) void sgm_cc_count_kernel(int* __restrict__ lab
   if(threadIdx.x == 0 && s_cnt > 0) atomicAdd(&size[wg_root], s_cnt);
 }
 __global__ __launch_bounds__(256) void sgm_cc_apply_kernel(uint16_t* __restrict__ img, const int* __restrict__ lab, const int* __restrict__ size, int npix,
-                                                          int max_size)
+                                                          int max_size, size_t fs)
 {
+  img = sgm_frame(img, fs, blockIdx.y); lab = sgm_frame(lab, fs, blockIdx.y); size = sgm_frame(size, fs, blockIdx.y);
   const int p = blockIdx.x * 256 + threadIdx.x;
   if(p >= npix || lab[p] < 0) return;
   if(size[lab[p]] <= max_size) img[p] = 0;
@@ -510,8 +541,11 @@ __global__ __launch_bounds__(256) void sgm_cc_apply_kernel(uint16_t* __restrict_
 
 // enforceLeftRightConsistency (left half) + disparity / factor -> float
 __global__ __launch_bounds__(256) void sgm_lr_check_kernel(const uint16_t* __restrict__ dl, const uint16_t* __restrict__ dr, float* __restrict__ out, int rows,
-                                                          int cols, double factor, int thresh)
+                                                          int cols, double factor, int thresh, size_t fs)
 {
+  dl = sgm_frame(dl, fs, blockIdx.y);
+  dr = sgm_frame(dr, fs, blockIdx.y);
+  out += (size_t) rows * cols * blockIdx.y;
   const int p = blockIdx.x * 256 + threadIdx.x;
   if(p >= rows * cols) return;
   const int x = p % cols;
@@ -529,14 +563,15 @@ __global__ __launch_bounds__(256) void sgm_lr_check_kernel(const uint16_t* __res
 
 }  // namespace
 
-void launch_speckle_filter_u16(hipStream_t s, uint16_t* img, int* lab, int* size, int rows, int cols, int max_diff, int max_size)
+void launch_speckle_filter_u16(hipStream_t s, uint16_t* img, int* lab, int* size, int rows, int cols, int max_diff, int max_size, int nframes,
+                               size_t frame_bytes)
 {
   const size_t npix = (size_t) rows * cols;
-  const unsigned nb = (unsigned) ((npix + 255) / 256);
-  hipLaunchKernelGGL(sgm_cc_init_kernel, dim3(nb), dim3(256), 0, s, img, lab, size, rows, cols, max_diff);
-  hipLaunchKernelGGL(sgm_cc_merge_kernel, dim3(nb), dim3(256), 0, s, img, lab, rows, cols, max_diff);
-  hipLaunchKernelGGL(sgm_cc_count_kernel, dim3(nb), dim3(256), 0, s, lab, size, (int) npix);
-  hipLaunchKernelGGL(sgm_cc_apply_kernel, dim3(nb), dim3(256), 0, s, img, lab, size, (int) npix, max_size);
+  const dim3 nb((unsigned) ((npix + 255) / 256), (unsigned) nframes);
+  hipLaunchKernelGGL(sgm_cc_init_kernel, nb, dim3(256), 0, s, img, lab, size, rows, cols, max_diff, frame_bytes);
+  hipLaunchKernelGGL(sgm_cc_merge_kernel, nb, dim3(256), 0, s, img, lab, rows, cols, max_diff, frame_bytes);
+  hipLaunchKernelGGL(sgm_cc_count_kernel, nb, dim3(256), 0, s, lab, size, (int) npix, frame_bytes);
+  hipLaunchKernelGGL(sgm_cc_apply_kernel, nb, dim3(256), 0, s, img, lab, size, (int) npix, max_size, frame_bytes);
 }
 
 size_t sgm_scratch_bytes(int rows, int cols, int D)
@@ -546,8 +581,10 @@ size_t sgm_scratch_bytes(int rows, int cols, int D)
   return 2 * up(pitch * rows) + 2 * up(npix * 4) + up(npix * D) + 2 * up(npix * D * 2) + up(8 * npix * D * 2) + 2 * up(npix * 2) + 2 * up(npix * 4);
 }
 
-// SGMStereo::compute (utils/sgm.cc:250-285) for `nframes` rectified pairs, one after the other on the stream (the cost volumes of a
-// 1241 x 376 x 128 frame are 120 MB each: the scratch is per context, not per frame)
+// SGMStereo::compute (utils/sgm.cc:250-285) for `nframes` rectified pairs of one size, in chunks of `frames_per_launch` frames: every kernel
+// takes a chunk in one launch, frame f of it on the f-th slice of the scratch (sgm_frame).  One frame per launch is one frame after the other
+// on one slice (the cost volumes of a 1241 x 376 x 128 frame are 120 MB each, and they fill the chip); small frames — a rig of 320 x 240
+// cameras: 2 (2 rows + 2 cols) single-wave scanlines per frame — share the launches.  Integer arithmetic per frame: same maps either way.
 bool launch_stereo_sgm(hipStream_t s, const SgmLaunch& g)
 {
   const int rows = g.rows, cols = g.cols, D = g.ndisp;
@@ -568,44 +605,47 @@ bool launch_stereo_sgm(hipStream_t s, const SgmLaunch& g)
   uint16_t* disp_r = (uint16_t*) w; w += up(npix * 2);
   int* lab = (int*) w; w += up(npix * 4);
   int* size = (int*) w; w += up(npix * 4);
+  const size_t fs = sgm_scratch_bytes(rows, cols, D);           // = w - scratch: the stride from a frame's slice to the next
   const int cap = (std::min(std::max(g.sobel_cap, 15), 127)) | 1;
   const int dthreads = (D + 63) / 64 * 64;
-  const dim3 gpix((pitch + 63) / 64, (rows + 3) / 4), gxy(cols, rows);
   const unsigned nb = (unsigned) ((npix + 255) / 256);
-  for(int f = 0; f < g.nframes; ++f) {
-    const uint8_t* L = g.left + npix * f;
-    const uint8_t* R = g.right + npix * f;
-    hipLaunchKernelGGL(sgm_census_sobel_kernel, gpix, dim3(256), 0, s, L, sob_l, cen_l, rows, cols, pitch, cap, g.census_radius, 0);
-    hipLaunchKernelGGL(sgm_census_sobel_kernel, gpix, dim3(256), 0, s, R, sob_r, cen_r, rows, cols, pitch, cap, g.census_radius, 1);
-    hipLaunchKernelGGL(sgm_pixel_cost_tile_kernel, dim3((cols + SPC_TX - 1) / SPC_TX, rows), dim3(256), 0, s, sob_l, sob_r, cen_l, cen_r, pc, rows, cols, pitch, D,
-                       g.census_weight);
+  const int per = std::max(1, std::min(g.frames_per_launch, 65535));      // (the frame is a grid's y or z)
+  for(int f0 = 0; f0 < g.nframes; f0 += per) {
+    const unsigned F = (unsigned) std::min(per, g.nframes - f0);
+    const uint8_t* L = g.left + npix * f0;
+    const uint8_t* R = g.right + npix * f0;
+    const dim3 gpix((pitch + 63) / 64, (rows + 3) / 4, F);
+    hipLaunchKernelGGL(sgm_census_sobel_kernel, gpix, dim3(256), 0, s, L, sob_l, cen_l, rows, cols, pitch, cap, g.census_radius, 0, fs);
+    hipLaunchKernelGGL(sgm_census_sobel_kernel, gpix, dim3(256), 0, s, R, sob_r, cen_r, rows, cols, pitch, cap, g.census_radius, 1, fs);
+    hipLaunchKernelGGL(sgm_pixel_cost_tile_kernel, dim3((cols + SPC_TX - 1) / SPC_TX, rows, F), dim3(256), 0, s, sob_l, sob_r, cen_l, cen_r, pc, rows, cols, pitch, D,
+                       g.census_weight, fs);
     {
       // (the row sums borrow the first path-cost volume: the scanline kernel overwrites it later on the same stream)
       uint16_t* rowsum = reinterpret_cast<uint16_t*>(Lvol);
-      const unsigned nbq = (unsigned) ((npix * (size_t) (D / 4) + 255) / 256);
-      hipLaunchKernelGGL(sgm_box_rows_kernel, dim3(nbq), dim3(256), 0, s, pc, rowsum, rows, cols, D, g.window_radius);
-      hipLaunchKernelGGL(sgm_box_cols_kernel, dim3(nbq), dim3(256), 0, s, rowsum, cost_l, rows, cols, D, g.window_radius);
+      const dim3 nbq((unsigned) ((npix * (size_t) (D / 4) + 255) / 256), F);
+      hipLaunchKernelGGL(sgm_box_rows_kernel, nbq, dim3(256), 0, s, pc, rowsum, rows, cols, D, g.window_radius, fs);
+      hipLaunchKernelGGL(sgm_box_cols_kernel, nbq, dim3(256), 0, s, rowsum, cost_l, rows, cols, D, g.window_radius, fs);
     }
-    if(D <= SRC_MAXD) hipLaunchKernelGGL(sgm_right_cost_tile_kernel, dim3(8u * (unsigned) (((cols + SRC_TX - 1) / SRC_TX * rows + 7) / 8)), dim3(256), 0, s, cost_l, cost_r, rows, cols, D);
-    else hipLaunchKernelGGL(sgm_right_cost_kernel, gxy, dim3(dthreads), 0, s, cost_l, cost_r, rows, cols, D);
+    if(D <= SRC_MAXD) hipLaunchKernelGGL(sgm_right_cost_tile_kernel, dim3(8u * (unsigned) (((cols + SRC_TX - 1) / SRC_TX * rows + 7) / 8), F), dim3(256), 0, s, cost_l, cost_r, rows, cols, D, fs);
+    else hipLaunchKernelGGL(sgm_right_cost_kernel, dim3(cols, rows, F), dim3(dthreads), 0, s, cost_l, cost_r, rows, cols, D, fs);
     {
-      const dim3 gp((unsigned) (2 * (2 * rows + 2 * cols)));
-      if(D <= 128) hipLaunchKernelGGL(sgm_path_packed_kernel<1>, gp, dim3(64), 0, s, cost_l, cost_r, Lvol, rows, cols, D, g.P1, g.P2);
-      else hipLaunchKernelGGL(sgm_path_packed_kernel<2>, gp, dim3(64), 0, s, cost_l, cost_r, Lvol, rows, cols, D, g.P1, g.P2);
+      const dim3 gp((unsigned) (2 * (2 * rows + 2 * cols)), F);
+      if(D <= 128) hipLaunchKernelGGL(sgm_path_packed_kernel<1>, gp, dim3(64), 0, s, cost_l, cost_r, Lvol, rows, cols, D, g.P1, g.P2, fs);
+      else hipLaunchKernelGGL(sgm_path_packed_kernel<2>, gp, dim3(64), 0, s, cost_l, cost_r, Lvol, rows, cols, D, g.P1, g.P2, fs);
     }
     for(int side = 0; side < 2; ++side) {
       uint16_t* disp = side == 0 ? disp_l : disp_r;
       const int16_t* L4 = Lvol + (size_t) side * 4 * npix * D;
       {
-        const dim3 gw((unsigned) ((npix + 3) / 4));
-        if(D <= 64) hipLaunchKernelGGL(sgm_wta_kernel<1>, gw, dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor);
-        else if(D <= 128) hipLaunchKernelGGL(sgm_wta_kernel<2>, gw, dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor);
-        else hipLaunchKernelGGL(sgm_wta_kernel<4>, gw, dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor);
+        const dim3 gw((unsigned) ((npix + 3) / 4), F);
+        if(D <= 64) hipLaunchKernelGGL(sgm_wta_kernel<1>, gw, dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor, fs);
+        else if(D <= 128) hipLaunchKernelGGL(sgm_wta_kernel<2>, gw, dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor, fs);
+        else hipLaunchKernelGGL(sgm_wta_kernel<4>, gw, dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor, fs);
       }
       // speckleFilter(100, 2 * factor) (utils/sgm.cc:898)
-      launch_speckle_filter_u16(s, disp, lab, size, rows, cols, (int) (2 * g.disparity_factor), 100);
+      launch_speckle_filter_u16(s, disp, lab, size, rows, cols, (int) (2 * g.disparity_factor), 100, (int) F, fs);
     }
-    hipLaunchKernelGGL(sgm_lr_check_kernel, dim3(nb), dim3(256), 0, s, disp_l, disp_r, g.disp + npix * f, rows, cols, g.disparity_factor, g.consistency_threshold);
+    hipLaunchKernelGGL(sgm_lr_check_kernel, dim3(nb, F), dim3(256), 0, s, disp_l, disp_r, g.disp + npix * f0, rows, cols, g.disparity_factor, g.consistency_threshold, fs);
   }
   return true;
 }

@@ -26,14 +26,11 @@ constexpr int ST_MAX_WSZ = 21;
 
 // prefilterXSobel: [1 2 1]^T x [-1 0 1] with rows reflected (101), clipped to [-cap, cap] + cap; first / last column and an
 // unpaired last row = cap (the original walks the rows in pairs)
-__global__ __launch_bounds__(256) void stereo_prefilter_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows, int cols, int cap,
-                                                              size_t frame_stride)
+__device__ __forceinline__ void stereo_prefilter_pixel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows, int cols, int cap)
 {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if(x >= cols || y >= rows) return;
-  src += frame_stride * blockIdx.z;
-  dst += frame_stride * blockIdx.z;
   uint8_t out = (uint8_t) cap;
   const bool unpaired = (rows & 1) && y == rows - 1;
   if(!unpaired && x > 0 && x < cols - 1) {
@@ -45,6 +42,20 @@ __global__ __launch_bounds__(256) void stereo_prefilter_kernel(const uint8_t* __
     out = (uint8_t) (min(max(v, -cap), cap) + cap);
   }
   dst[(size_t) y * cols + x] = out;
+}
+__global__ __launch_bounds__(256) void stereo_prefilter_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows, int cols, int cap,
+                                                              size_t frame_stride)
+{
+  stereo_prefilter_pixel(src + frame_stride * blockIdx.z, dst + frame_stride * blockIdx.z, rows, cols, cap);
+}
+// Frames of different sizes in one launch: frame blockIdx.z has the size and the place in the packed images that its table row names (a
+// uniform row: scalar loads), the grid covers the largest frame, and the workgroups beyond their own frame leave at once.
+__global__ __launch_bounds__(256) void stereo_prefilter_frames_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                                     const StereoFrame* __restrict__ frames, int cap)
+{
+  const StereoFrame fr = frames[blockIdx.z];
+  if((int) blockIdx.x * 64 >= fr.cols || (int) blockIdx.y * 4 >= fr.rows) return;
+  stereo_prefilter_pixel(src + fr.offset, dst + fr.offset, fr.rows, fr.cols, cap);
 }
 
 // inclusive scan over the 64 lanes on the VALU: DPP row shifts inside the rows of 16 (lanes without a source add 0), then the two row
@@ -61,9 +72,8 @@ __device__ __forceinline__ int wave_incl_scan(int v)
 }
 
 template <int WSZ>
-__global__ __launch_bounds__(64 * ST_WAVES) void stereo_bm_kernel(const uint8_t* __restrict__ Lp, const uint8_t* __restrict__ Rp, float* __restrict__ disp,
-                                                                   int rows, int cols, int ndisp, int mindisp, int cap, int texture_threshold,
-                                                                   int uniqueness_ratio, size_t frame_stride)
+__device__ __forceinline__ void stereo_bm_frame(const uint8_t* __restrict__ Lp, const uint8_t* __restrict__ Rp, float* __restrict__ disp, int rows, int cols,
+                                                int ndisp, int mindisp, int cap, int texture_threshold, int uniqueness_ratio)
 {
   constexpr int W2 = WSZ / 2;
   constexpr int OUTW = 64 - 2 * W2;                 // output columns per wavefront
@@ -73,9 +83,6 @@ __global__ __launch_bounds__(64 * ST_WAVES) void stereo_bm_kernel(const uint8_t*
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   uint8_t* Lt = smem + (size_t) wave * TR * (64 + rw);
   uint8_t* Rt = Lt + TR * 64;
-  Lp += frame_stride * blockIdx.z;
-  Rp += frame_stride * blockIdx.z;
-  disp += frame_stride * blockIdx.z;
 
   const int lofs = max(ndisp - 1 + mindisp, 0);     // (rofs = 0: minDisparity >= 1 - ndisp is checked by the host)
   const int width1 = min(cols - ndisp + 1, cols - lofs);   // (the original overruns the row by minDisparity columns: cut at the last one)
@@ -182,6 +189,28 @@ __global__ __launch_bounds__(64 * ST_WAVES) void stereo_bm_kernel(const uint8_t*
   }
 }
 
+template <int WSZ>
+__global__ __launch_bounds__(64 * ST_WAVES) void stereo_bm_kernel(const uint8_t* __restrict__ Lp, const uint8_t* __restrict__ Rp, float* __restrict__ disp,
+                                                                   int rows, int cols, int ndisp, int mindisp, int cap, int texture_threshold,
+                                                                   int uniqueness_ratio, size_t frame_stride)
+{
+  stereo_bm_frame<WSZ>(Lp + frame_stride * blockIdx.z, Rp + frame_stride * blockIdx.z, disp + frame_stride * blockIdx.z, rows, cols, ndisp, mindisp, cap,
+                       texture_threshold, uniqueness_ratio);
+}
+// The matcher over frames of different sizes (stereo_prefilter_frames_kernel): same registers and LDS per workgroup as the launch-wide form —
+// the tile is sized by the window and the disparity range, not by the image — and a workgroup whose rows or columns lie outside its own
+// frame returns before it touches LDS or reaches a barrier, so the small frames of a rig cost their own workgroups only.
+template <int WSZ>
+__global__ __launch_bounds__(64 * ST_WAVES) void stereo_bm_frames_kernel(const uint8_t* __restrict__ Lp, const uint8_t* __restrict__ Rp, float* __restrict__ disp,
+                                                                          const StereoFrame* __restrict__ frames, int ndisp, int mindisp, int cap,
+                                                                          int texture_threshold, int uniqueness_ratio)
+{
+  const StereoFrame fr = frames[blockIdx.z];
+  const int width1 = min(fr.cols - ndisp + 1, fr.cols - max(ndisp - 1 + mindisp, 0));
+  if((int) blockIdx.y * (ST_ROWS * ST_WAVES) >= fr.rows || (int) blockIdx.x * (64 - 2 * (WSZ / 2)) >= width1) return;
+  stereo_bm_frame<WSZ>(Lp + fr.offset, Rp + fr.offset, disp + fr.offset, fr.rows, fr.cols, ndisp, mindisp, cap, texture_threshold, uniqueness_ratio);
+}
+
 __global__ __launch_bounds__(256) void stereo_fill_kernel(float* __restrict__ disp, size_t n, float v)
 {
   const size_t i = (size_t) blockIdx.x * 256 + threadIdx.x;
@@ -194,6 +223,12 @@ void launch_stereo_prefilter(hipStream_t s, const uint8_t* src, uint8_t* dst, in
                      (size_t) rows * cols);
 }
 
+void launch_stereo_prefilter_frames(hipStream_t s, const uint8_t* src, uint8_t* dst, const StereoFrame* frames, int max_rows, int max_cols, int cap, int nframes)
+{
+  hipLaunchKernelGGL(stereo_prefilter_frames_kernel, dim3((max_cols + 63) / 64, (max_rows + 3) / 4, nframes), dim3(256), 0, s, src, dst, frames, cap);
+}
+
+// g.frames: the table form, g.rows x g.cols the largest frame of the table
 template <int WSZ>
 static bool launch_bm_w(hipStream_t s, const StereoLaunch& g)
 {
@@ -204,18 +239,24 @@ static bool launch_bm_w(hipStream_t s, const StereoLaunch& g)
   static bool attr_set = false;      // (one attribute per instantiation; harmless to repeat)
   if(!attr_set && lds > 64 * 1024) {
     (void) hipFuncSetAttribute((const void*) stereo_bm_kernel<WSZ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void) hipFuncSetAttribute((const void*) stereo_bm_frames_kernel<WSZ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set = true;
   }
   const dim3 grid((width1 + OUTW - 1) / OUTW, (g.rows + ST_ROWS * ST_WAVES - 1) / (ST_ROWS * ST_WAVES), g.nframes);
-  hipLaunchKernelGGL(stereo_bm_kernel<WSZ>, grid, dim3(64 * ST_WAVES), lds, s, g.left_pre, g.right_pre, g.disp, g.rows, g.cols, g.ndisp, g.mindisp, g.cap,
-                     g.texture_threshold, g.uniqueness_ratio, (size_t) g.rows * g.cols);
+  if(g.frames)
+    hipLaunchKernelGGL(stereo_bm_frames_kernel<WSZ>, grid, dim3(64 * ST_WAVES), lds, s, g.left_pre, g.right_pre, g.disp, g.frames, g.ndisp, g.mindisp, g.cap,
+                       g.texture_threshold, g.uniqueness_ratio);
+  else
+    hipLaunchKernelGGL(stereo_bm_kernel<WSZ>, grid, dim3(64 * ST_WAVES), lds, s, g.left_pre, g.right_pre, g.disp, g.rows, g.cols, g.ndisp, g.mindisp, g.cap,
+                       g.texture_threshold, g.uniqueness_ratio, (size_t) g.rows * g.cols);
   return true;
 }
 
 // the whole disparity map: invalid value everywhere, then the matcher over the columns that have all disparities
 bool launch_stereo_bm(hipStream_t s, const StereoLaunch& g)
 {
-  const size_t n = (size_t) g.rows * g.cols * g.nframes;
+  // (the maps of a call lie back to back whatever their sizes: one fill over all their pixels)
+  const size_t n = g.frames ? g.total_pixels : (size_t) g.rows * g.cols * g.nframes;
   const float filtered = (float) ((g.mindisp - 1) << 4) * (1.0f / 16.0f);
   hipLaunchKernelGGL(stereo_fill_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, g.disp, n, filtered);
   const int lofs = g.ndisp - 1 + g.mindisp, width1 = std::min(g.cols - g.ndisp + 1, g.cols - lofs);

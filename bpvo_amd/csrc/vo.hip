@@ -67,7 +67,8 @@ static int build_point_cloud(bpvo_hip_ctx* c)
 }
 
 // ---- stereo front-end (reference: utils/stereo_algorithm.cc:63-82,98-111 -> OpenCV 2.4 cvFindStereoCorrespondenceBM) ----
-static int stereo_check(bpvo_hip_ctx* c, const bpvo_hip_stereo_params* sp)
+// (rows x cols: the frame the parameters are checked for — the context's size, or a camera's)
+static int stereo_check(bpvo_hip_ctx* c, const bpvo_hip_stereo_params* sp, int rows, int cols)
 {
   // the argument checks of cvFindStereoCorrespondenceBM (stereobm.cpp) + what the kernel serves
   if(!sp) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr stereo parameters");
@@ -83,7 +84,7 @@ static int stereo_check(bpvo_hip_ctx* c, const bpvo_hip_stereo_params* sp)
     if(sp->numberOfDisparities > 256) return fail(c, BPVO_ERR_UNSUPPORTED, "SGM: numberOfDisparities <= 256 are on the device path");
     // (2r+1)^2 * 255 must stay below 2^15: the original's sliding sums are int16 saturating additions (_mm_adds_epi16) and the cost is read
     // back as int16; up to radius 5 (121 * 255 = 30855) nothing saturates and the plain integer sums of the device path are the same numbers
-    if(sp->windowRadius < 0 || sp->windowRadius > 5 || c->rows <= sp->windowRadius) return fail(c, BPVO_ERR_UNSUPPORTED, "SGM: windowRadius 0..5 (and fewer than image rows) are on the device path");
+    if(sp->windowRadius < 0 || sp->windowRadius > 5 || rows <= sp->windowRadius) return fail(c, BPVO_ERR_UNSUPPORTED, "SGM: windowRadius 0..5 (and fewer than image rows) are on the device path");
     // int16 path costs: the sums of four paths stay clear of saturation for penalties below this (the original saturates silently)
     if(sp->smoothnessPenaltyLarge > 4000) return fail(c, BPVO_ERR_UNSUPPORTED, "SGM: smoothnessPenaltyLarge <= 4000 on the device path");
     return BPVO_OK;
@@ -91,7 +92,7 @@ static int stereo_check(bpvo_hip_ctx* c, const bpvo_hip_stereo_params* sp)
   if(sp->algorithm == BPVO_STEREO_SGBM) {
     if(sp->numberOfDisparities <= 0 || sp->numberOfDisparities % 16) return fail(c, BPVO_ERR_INVALID_ARG, "numberOfDisparities must be a positive multiple of 16");   // CV_Assert(D % 16 == 0)
     SgbmLaunch g = {};
-    g.rows = c->rows; g.cols = c->cols;
+    g.rows = rows; g.cols = cols;
     g.min_disp = sp->minDisparity; g.ndisp = sp->numberOfDisparities; g.sad_window = sp->SADWindowSize; g.P1 = sp->P1; g.P2 = sp->P2;
     g.disp12_max_diff = sp->disp12MaxDiff; g.pre_filter_cap = sp->preFilterCap; g.uniqueness_ratio = sp->uniquenessRatio;
     g.speckle_window = sp->speckleWindowSize; g.speckle_range = sp->speckleRange; g.full_dp = sp->fullDP;
@@ -101,7 +102,7 @@ static int stereo_check(bpvo_hip_ctx* c, const bpvo_hip_stereo_params* sp)
   }
   if(sp->algorithm != BPVO_STEREO_BLOCK_MATCHING) return fail(c, BPVO_ERR_UNSUPPORTED, "StereoAlgorithm: BlockMatching, SGM and SGBM are on the device path (RSGM is GPL-gated in the reference and not built)");
   if(sp->preFilterCap < 1 || sp->preFilterCap > 63) return fail(c, BPVO_ERR_INVALID_ARG, "preFilterCap must be within 1..63");
-  if(sp->SADWindowSize < 5 || sp->SADWindowSize > 255 || sp->SADWindowSize % 2 == 0 || sp->SADWindowSize >= std::min(c->cols, c->rows))
+  if(sp->SADWindowSize < 5 || sp->SADWindowSize > 255 || sp->SADWindowSize % 2 == 0 || sp->SADWindowSize >= std::min(cols, rows))
     return fail(c, BPVO_ERR_INVALID_ARG, "SADWindowSize must be odd, be within 5..255 and be not larger than image width or height");
   if(sp->numberOfDisparities <= 0 || sp->numberOfDisparities % 16 != 0) return fail(c, BPVO_ERR_INVALID_ARG, "numberOfDisparities must be positive and divisble by 16");
   if(sp->textureThreshold < 0) return fail(c, BPVO_ERR_INVALID_ARG, "texture threshold must be non-negative");
@@ -110,29 +111,80 @@ static int stereo_check(bpvo_hip_ctx* c, const bpvo_hip_stereo_params* sp)
   if(sp->minDisparity < 0 || sp->numberOfDisparities > 256) return fail(c, BPVO_ERR_UNSUPPORTED, "minDisparity >= 0 and numberOfDisparities <= 256 are on the device path");
   return BPVO_OK;
 }
-static int stereo_reserve(bpvo_hip_ctx* c, int count)
+static int stereo_reserve(bpvo_hip_ctx* c, size_t npix)      // npix: the pixels of a call, the sum over its frames
 {
-  if(count <= c->st_frames) return BPVO_OK;
+  if(npix <= c->st_pixels) return BPVO_OK;
   HIP_CK(c, hipStreamSynchronize(c->stream));
   (void) hipFree(c->st_left); (void) hipFree(c->st_right); (void) hipFree(c->st_left_pre); (void) hipFree(c->st_right_pre); (void) hipFree(c->st_disp);
-  c->st_left = c->st_right = c->st_left_pre = c->st_right_pre = nullptr; c->st_disp = nullptr; c->st_frames = 0;
-  const size_t npix = c->geom[0].npix * (size_t) count;
+  c->st_left = c->st_right = c->st_left_pre = c->st_right_pre = nullptr; c->st_disp = nullptr; c->st_pixels = 0;
   HIP_CK(c, hipMalloc((void**) &c->st_left, npix)); HIP_CK(c, hipMalloc((void**) &c->st_right, npix));
   HIP_CK(c, hipMalloc((void**) &c->st_left_pre, npix)); HIP_CK(c, hipMalloc((void**) &c->st_right_pre, npix));
   HIP_CK(c, hipMalloc((void**) &c->st_disp, npix * sizeof(float)));
-  c->st_frames = count;
+  c->st_pixels = npix;
   return BPVO_OK;
 }
-// disparities of `count` rectified pairs into c->st_disp (device); d_left: where the left images are on the device afterwards
-static int stereo_run(bpvo_hip_ctx* c, int count, const uint8_t* left, const uint8_t* right, bool on_device, const bpvo_hip_stereo_params* sp,
-                      const uint8_t** d_left)
+static int stereo_scratch(bpvo_hip_ctx* c, size_t need)      // the semi-global matchers' scratch, at least `need` bytes
 {
-  int rc = stereo_check(c, sp);
+  if(need <= c->st_sgm_bytes) return BPVO_OK;
+  HIP_CK(c, hipStreamSynchronize(c->stream));
+  (void) hipFree(c->st_sgm);
+  c->st_sgm = nullptr; c->st_sgm_bytes = 0;
+  HIP_CK(c, hipMalloc(&c->st_sgm, need));
+  c->st_sgm_bytes = need;
+  return BPVO_OK;
+}
+static int seq_capacity(const bpvo_hip_ctx* c);
+struct StereoSize { int rows, cols; };
+static bool operator==(const StereoSize& a, const StereoSize& b) { return a.rows == b.rows && a.cols == b.cols; }
+// The checks of a call's stereo stage, once per size among its frames; nothing is touched.  *bad: the first frame whose size fails.
+static int stereo_check_sizes(bpvo_hip_ctx* c, int n, const StereoSize* sz, const bpvo_hip_stereo_params* sp, int* bad)
+{
+  *bad = -1;
+  if(!sp) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr stereo parameters");
+  for(int i = 0; i < n; ++i) {
+    bool seen = false;
+    for(int k = 0; k < i && !seen; ++k) seen = sz[k] == sz[i];
+    if(seen) continue;
+    const int rc = stereo_check(c, sp, sz[i].rows, sz[i].cols);
+    if(rc) { *bad = i; return rc; }
+  }
+  return BPVO_OK;
+}
+// SGM frames of one size per launch (option "stereo_frames_per_launch"): as many as a third of the free device memory holds — the rule of
+// the 4x4 tap cache (estimate.hip) —, the free memory read once per context, when the scratch is first needed; never fewer than one (whose
+// allocation is then attempted as before).
+static int sgm_frames_per_launch(bpvo_hip_ctx* c, size_t per_frame, int count)
+{
+  if(c->stereo_frames_per_launch == 1 || count <= 1) return 1;
+  if(c->st_sgm_budget == 0) {
+    size_t free_b = 0, total_b = 0;
+    if(hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void) hipGetLastError(); free_b = 0; }
+    c->st_free_seen = free_b + c->st_sgm_bytes;      // (a scratch this context already holds is given back before a larger one is taken)
+    c->st_sgm_budget = std::max<size_t>(1, c->st_free_seen / 3);
+  }
+  int F = (int) std::min<size_t>((size_t) count, std::max<size_t>(1, c->st_sgm_budget / per_frame));
+  if(c->stereo_frames_per_launch > 1) F = std::min(F, c->stereo_frames_per_launch);
+  return F;
+}
+// Disparities of n rectified pairs into c->st_disp (device), pair i of sz[i].rows x sz[i].cols pixels, images and maps back to back in call
+// order; d_left: where the left images are on the device afterwards.  The caller has run stereo_check_sizes.
+// Block matching takes all the frames in one launch per stage: the launch-wide kernels where they share one size, the table forms
+// otherwise.  The semi-global matchers' kernels take launch-wide sizes: they serve runs of neighbouring frames of one size (neighbours in
+// the call lie back to back in memory), SGM in chunks of sgm_frames_per_launch frames per launch, SGBM frame after frame.
+static int stereo_run_sizes(bpvo_hip_ctx* c, int n, const StereoSize* sz, const uint8_t* left, const uint8_t* right, bool on_device,
+                            const bpvo_hip_stereo_params* sp, const uint8_t** d_left)
+{
+  if(n <= 0 || !left || !right) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image");
+  size_t npix = 0;
+  bool uniform = true;
+  int max_rows = 0, max_cols = 0;
+  for(int i = 0; i < n; ++i) {
+    npix += (size_t) sz[i].rows * sz[i].cols;
+    uniform = uniform && sz[i] == sz[0];
+    max_rows = std::max(max_rows, sz[i].rows); max_cols = std::max(max_cols, sz[i].cols);
+  }
+  int rc = stereo_reserve(c, npix);
   if(rc) return rc;
-  if(count <= 0 || !left || !right) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image");
-  rc = stereo_reserve(c, count);
-  if(rc) return rc;
-  const size_t npix = c->geom[0].npix * (size_t) count;
   const uint8_t* dl = left;
   const uint8_t* dr = right;
   if(!on_device) {
@@ -140,57 +192,94 @@ static int stereo_run(bpvo_hip_ctx* c, int count, const uint8_t* left, const uin
     HIP_CK(c, hipMemcpyAsync(c->st_right, right, npix, hipMemcpyHostToDevice, c->stream));
     dl = c->st_left; dr = c->st_right;
   }
-  if(sp->algorithm == BPVO_STEREO_SGM) {
-    const size_t need = sgm_scratch_bytes(c->rows, c->cols, sp->numberOfDisparities);
-    if(need > c->st_sgm_bytes) {
-      HIP_CK(c, hipStreamSynchronize(c->stream));
-      (void) hipFree(c->st_sgm);
-      c->st_sgm = nullptr; c->st_sgm_bytes = 0;
-      HIP_CK(c, hipMalloc(&c->st_sgm, need));
-      c->st_sgm_bytes = need;
+  if(d_left) *d_left = dl;
+  if(sp->algorithm == BPVO_STEREO_SGM || sp->algorithm == BPVO_STEREO_SGBM) {
+    const bool sgm = sp->algorithm == BPVO_STEREO_SGM;
+    // runs of neighbouring frames of one size: [first, first + count) at pixel offset `at`; the scratch is sized for the largest need of the call
+    struct Run { int first, count, per_launch; size_t at; };
+    std::vector<Run> runs;
+    size_t at = 0, need = 0;
+    for(int i = 0; i < n;) {
+      int k = i + 1;
+      while(k < n && sz[k] == sz[i]) ++k;
+      const size_t per = sgm ? sgm_scratch_bytes(sz[i].rows, sz[i].cols, sp->numberOfDisparities)
+                             : sgbm_scratch_bytes(sz[i].rows, sz[i].cols, sp->minDisparity, sp->numberOfDisparities);
+      const int F = sgm ? sgm_frames_per_launch(c, per, k - i) : 1;
+      need = std::max(need, per * (size_t) F);
+      runs.push_back(Run{i, k - i, F, at});
+      at += (size_t) (k - i) * sz[i].rows * sz[i].cols;
+      i = k;
     }
-    SgmLaunch g;
-    g.left = dl; g.right = dr; g.disp = c->st_disp; g.scratch = c->st_sgm;
-    g.rows = c->rows; g.cols = c->cols; g.nframes = count;
-    g.ndisp = sp->numberOfDisparities; g.sobel_cap = sp->sobelCapValue; g.census_radius = sp->censusRadius; g.window_radius = sp->windowRadius;
-    g.P1 = sp->smoothnessPenaltySmall; g.P2 = sp->smoothnessPenaltyLarge; g.consistency_threshold = sp->consistencyThreshold;
-    g.disparity_factor = sp->disparityFactor; g.census_weight = sp->censusWeightFactor;
-    if(!launch_stereo_sgm(c->stream, g)) return fail(c, BPVO_ERR_UNSUPPORTED, "semi-global matching: disparity range not served by the kernels");
-    HIP_CK(c, hipGetLastError());
-    if(d_left) *d_left = dl;
+    rc = stereo_scratch(c, need);
+    if(rc) return rc;
+    for(const Run& r : runs) {
+      const StereoSize& q = sz[r.first];
+      if(sgm) {
+        SgmLaunch g;
+        g.left = dl + r.at; g.right = dr + r.at; g.disp = c->st_disp + r.at; g.scratch = c->st_sgm;
+        g.rows = q.rows; g.cols = q.cols; g.nframes = r.count; g.frames_per_launch = r.per_launch;
+        g.ndisp = sp->numberOfDisparities; g.sobel_cap = sp->sobelCapValue; g.census_radius = sp->censusRadius; g.window_radius = sp->windowRadius;
+        g.P1 = sp->smoothnessPenaltySmall; g.P2 = sp->smoothnessPenaltyLarge; g.consistency_threshold = sp->consistencyThreshold;
+        g.disparity_factor = sp->disparityFactor; g.census_weight = sp->censusWeightFactor;
+        c->st_frames_per_launch_seen = r.per_launch;
+        if(!launch_stereo_sgm(c->stream, g)) return fail(c, BPVO_ERR_UNSUPPORTED, "semi-global matching: disparity range not served by the kernels");
+      } else {
+        SgbmLaunch g = {};
+        g.left = dl + r.at; g.right = dr + r.at; g.disp = c->st_disp + r.at; g.scratch = c->st_sgm;
+        g.rows = q.rows; g.cols = q.cols; g.nframes = r.count;
+        g.min_disp = sp->minDisparity; g.ndisp = sp->numberOfDisparities; g.sad_window = sp->SADWindowSize; g.P1 = sp->P1; g.P2 = sp->P2;
+        g.disp12_max_diff = sp->disp12MaxDiff; g.pre_filter_cap = sp->preFilterCap; g.uniqueness_ratio = sp->uniquenessRatio;
+        g.speckle_window = sp->speckleWindowSize; g.speckle_range = sp->speckleRange; g.full_dp = sp->fullDP;
+        if(!launch_stereo_sgbm(c->stream, g)) return fail(c, BPVO_ERR_UNSUPPORTED, "semi-global block matching: parameters not served by the kernels");
+      }
+      HIP_CK(c, hipGetLastError());
+    }
     return BPVO_OK;
   }
-  if(sp->algorithm == BPVO_STEREO_SGBM) {
-    const size_t need = sgbm_scratch_bytes(c->rows, c->cols, sp->minDisparity, sp->numberOfDisparities);
-    if(need > c->st_sgm_bytes) {
-      HIP_CK(c, hipStreamSynchronize(c->stream));
-      (void) hipFree(c->st_sgm);
-      c->st_sgm = nullptr; c->st_sgm_bytes = 0;
-      HIP_CK(c, hipMalloc(&c->st_sgm, need));
-      c->st_sgm_bytes = need;
-    }
-    SgbmLaunch g = {};
-    g.left = dl; g.right = dr; g.disp = c->st_disp; g.scratch = c->st_sgm;
-    g.rows = c->rows; g.cols = c->cols; g.nframes = count;
-    g.min_disp = sp->minDisparity; g.ndisp = sp->numberOfDisparities; g.sad_window = sp->SADWindowSize; g.P1 = sp->P1; g.P2 = sp->P2;
-    g.disp12_max_diff = sp->disp12MaxDiff; g.pre_filter_cap = sp->preFilterCap; g.uniqueness_ratio = sp->uniquenessRatio;
-    g.speckle_window = sp->speckleWindowSize; g.speckle_range = sp->speckleRange; g.full_dp = sp->fullDP;
-    if(!launch_stereo_sgbm(c->stream, g)) return fail(c, BPVO_ERR_UNSUPPORTED, "semi-global block matching: parameters not served by the kernels");
-    HIP_CK(c, hipGetLastError());
-    if(d_left) *d_left = dl;
-    return BPVO_OK;
-  }
-  launch_stereo_prefilter(c->stream, dl, c->st_left_pre, c->rows, c->cols, sp->preFilterCap, count);
-  launch_stereo_prefilter(c->stream, dr, c->st_right_pre, c->rows, c->cols, sp->preFilterCap, count);
   StereoLaunch g;
   g.left_pre = c->st_left_pre; g.right_pre = c->st_right_pre; g.disp = c->st_disp;
-  g.rows = c->rows; g.cols = c->cols; g.nframes = count;
+  g.rows = max_rows; g.cols = max_cols; g.nframes = n;
   g.wsz = sp->SADWindowSize; g.ndisp = sp->numberOfDisparities; g.mindisp = sp->minDisparity; g.cap = sp->preFilterCap;
   g.texture_threshold = sp->textureThreshold; g.uniqueness_ratio = sp->uniquenessRatio;
+  if(uniform) {
+    launch_stereo_prefilter(c->stream, dl, c->st_left_pre, max_rows, max_cols, sp->preFilterCap, n);
+    launch_stereo_prefilter(c->stream, dr, c->st_right_pre, max_rows, max_cols, sp->preFilterCap, n);
+  } else {
+    if(n > c->st_tab_cap) {
+      HIP_CK(c, hipStreamSynchronize(c->stream));
+      (void) hipFree(c->d_st_frames); (void) hipHostFree(c->h_st_frames);
+      c->d_st_frames = c->h_st_frames = nullptr; c->st_tab_cap = 0;
+      const int cap = std::max(n, seq_capacity(c));
+      HIP_CK(c, hipMalloc((void**) &c->d_st_frames, (size_t) cap * sizeof(StereoFrame)));
+      HIP_CK(c, hipHostMalloc((void**) &c->h_st_frames, (size_t) cap * sizeof(StereoFrame)));
+      c->st_tab_cap = cap;
+    }
+    if(!c->st_tab_ev) HIP_CK(c, hipEventCreateWithFlags(&c->st_tab_ev, hipEventDisableTiming));
+    else HIP_CK(c, hipEventSynchronize(c->st_tab_ev));      // (the last call's copy has read the pinned rows)
+    size_t at = 0;
+    for(int i = 0; i < n; ++i) {
+      c->h_st_frames[i] = StereoFrame{sz[i].rows, sz[i].cols, at};
+      at += (size_t) sz[i].rows * sz[i].cols;
+    }
+    HIP_CK(c, hipMemcpyAsync(c->d_st_frames, c->h_st_frames, (size_t) n * sizeof(StereoFrame), hipMemcpyHostToDevice, c->stream));
+    HIP_CK(c, hipEventRecord(c->st_tab_ev, c->stream));
+    launch_stereo_prefilter_frames(c->stream, dl, c->st_left_pre, c->d_st_frames, max_rows, max_cols, sp->preFilterCap, n);
+    launch_stereo_prefilter_frames(c->stream, dr, c->st_right_pre, c->d_st_frames, max_rows, max_cols, sp->preFilterCap, n);
+    g.frames = c->d_st_frames; g.total_pixels = npix;
+  }
   if(!launch_stereo_bm(c->stream, g)) return fail(c, BPVO_ERR_UNSUPPORTED, "stereo block matching: window / disparity range not served by the kernel");
   HIP_CK(c, hipGetLastError());
-  if(d_left) *d_left = dl;
   return BPVO_OK;
+}
+// `count` pairs of the context's size
+static int stereo_run(bpvo_hip_ctx* c, int count, const uint8_t* left, const uint8_t* right, bool on_device, const bpvo_hip_stereo_params* sp,
+                      const uint8_t** d_left)
+{
+  int rc = stereo_check(c, sp, c->rows, c->cols);
+  if(rc) return rc;
+  if(count <= 0 || !left || !right) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image");
+  const std::vector<StereoSize> sz((size_t) count, StereoSize{c->rows, c->cols});
+  return stereo_run_sizes(c, count, sz.data(), left, right, on_device, sp, d_left);
 }
 
 void bpvo_hip_default_stereo_params(bpvo_hip_stereo_params* p)   // utils/stereo_algorithm.cc:63-82 (numberOfDisparities has no default there)
@@ -483,17 +572,17 @@ static int for_each_size(bpvo_hip_ctx* c, const std::vector<int>& slots, const s
 
 extern "C" {
 
-static int add_frames_impl(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* images, const float* disparities, bool on_device,
-                           bpvo_hip_result* results)
+// 1. every check of a call before any state changes; ids: the sequences it advances
+static int add_frames_check(bpvo_hip_ctx* c, int n, const int* seq, const void* images, const void* second, const char* what_null, bpvo_hip_result* results,
+                            std::vector<int>& ids)
 {
-  // 1. every check before any state changes
   if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a context serves either add_frame or add_frames");
   const int S = seq_capacity(c);
   if(S < 1) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames needs a ctx with n_frames >= 3 and n_pairs >= 1");
   if(n < 1 || n > S) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames: n must be within 1 .. the sequence capacity");
-  if(!images || !disparities) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image/disparity");   // bpvo/vo.cc:68-69
+  if(!images || !second) return fail(c, BPVO_ERR_INVALID_ARG, what_null);   // bpvo/vo.cc:68-69
   if(!results) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
-  std::vector<int> ids((size_t) n);
+  ids.assign((size_t) n, 0);
   std::vector<char> seen((size_t) S, 0);
   for(int i = 0; i < n; ++i) {
     ids[i] = seq ? seq[i] : i;
@@ -509,6 +598,12 @@ static int add_frames_impl(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t
       for(int l = p.maxTestLevel; l < c->L; ++l)      // template_data.cc:177 (check_template_not_empty)
         if(ref.n_host[l] <= 0) return seq_fail(c, BPVO_ERR_NO_TEMPLATE, ids[i], "the key frame's template is empty (you should call setData before calling computeResiduals)");
     }
+  return BPVO_OK;
+}
+static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, const uint8_t* images, const float* disparities, bool on_device,
+                          bpvo_hip_result* results)
+{
+  const bpvo_hip_params& p = c->params;
   (void) hipSetDevice(c->device);
   int rc = seq_storage(c);
   if(rc) return rc;
@@ -694,7 +789,69 @@ static int add_frames_impl(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t
 int bpvo_hip_add_frames(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* results)
 {
   CHECK_CTX(c);
-  return add_frames_impl(c, n, seq, images, disparities, on_device != 0, results);
+  std::vector<int> ids;
+  const int rc = add_frames_check(c, n, seq, images, disparities, "nullptr image/disparity", results, ids);
+  if(rc) return rc;
+  return add_frames_run(c, n, ids, images, disparities, on_device != 0, results);
+}
+// StereoAlgorithm::run + addFrame of every sequence of the call (apps/vo_app.cc per camera): the front-end once over all the pairs, each in
+// its sequence's camera geometry, into the context's own maps, which the frame stages then read where they lie — no host synchronisation
+// and no copy between the two; left images from host memory are uploaded once, for both.
+int bpvo_hip_add_frames_stereo(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* left, const uint8_t* right, int on_device,
+                               const bpvo_hip_stereo_params* sp, bpvo_hip_result* results)
+{
+  CHECK_CTX(c);
+  std::vector<int> ids;
+  int rc = add_frames_check(c, n, seq, left, right, "nullptr image", results, ids);
+  if(rc) return rc;
+  std::vector<StereoSize> sz((size_t) n);
+  for(int i = 0; i < n; ++i) {
+    const LevelGeom& g = slot_geom(c, c->frames[3 * ids[i]], 0);
+    sz[i] = StereoSize{g.rows, g.cols};
+  }
+  int bad = -1;
+  rc = stereo_check_sizes(c, n, sz.data(), sp, &bad);
+  if(rc) {
+    if(bad >= 0) c->err = "sequence " + std::to_string(ids[bad]) + ": " + c->err;
+    return rc;
+  }
+  (void) hipSetDevice(c->device);
+  const uint8_t* d_left = nullptr;
+  rc = stereo_run_sizes(c, n, sz.data(), left, right, on_device != 0, sp, &d_left);
+  if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
+  return add_frames_run(c, n, ids, d_left, c->st_disp, true, results);
+}
+int bpvo_hip_stereo_frames(bpvo_hip_ctx* c, int n, const bpvo_hip_camera* cams, const uint8_t* left, const uint8_t* right, int on_device,
+                           const bpvo_hip_stereo_params* sp, float* disparity, int disparity_on_device)
+{
+  CHECK_CTX(c);
+  if(!disparity) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr disparity");
+  if(n < 1 || !cams) return fail(c, BPVO_ERR_INVALID_ARG, "stereo_frames: n >= 1 cameras");
+  if(!left || !right) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image");
+  std::vector<StereoSize> sz((size_t) n);
+  size_t npix = 0;
+  for(int i = 0; i < n; ++i) {
+    sz[i] = StereoSize{cams[i].rows, cams[i].cols};
+    if(sz[i].rows < 1 || sz[i].cols < 1) return seq_fail(c, BPVO_ERR_INVALID_ARG, i, "camera: image size out of range");
+    if(sz[i].rows > c->rows || sz[i].cols > c->cols)
+      return seq_fail(c, BPVO_ERR_UNSUPPORTED, i, ("camera " + std::to_string(sz[i].cols) + "x" + std::to_string(sz[i].rows) + " larger than the context's " +
+                                                   std::to_string(c->cols) + "x" + std::to_string(c->rows)).c_str());
+    npix += (size_t) sz[i].rows * sz[i].cols;
+  }
+  int bad = -1;
+  int rc = stereo_check_sizes(c, n, sz.data(), sp, &bad);
+  if(rc) {
+    if(bad >= 0) c->err = "sequence " + std::to_string(bad) + ": " + c->err;
+    return rc;
+  }
+  for(int i = 0; i < n; ++i)      // (what bpvo_hip_create admits, after the parameters have been held against every size)
+    if(sz[i].rows < 8 || sz[i].cols < 8) return seq_fail(c, BPVO_ERR_INVALID_ARG, i, "camera: image size out of range (at least 8 rows and cols)");
+  (void) hipSetDevice(c->device);
+  rc = stereo_run_sizes(c, n, sz.data(), left, right, on_device != 0, sp, nullptr);
+  if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
+  HIP_CK(c, hipMemcpyAsync(disparity, c->st_disp, npix * sizeof(float), disparity_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  HIP_CK(c, hipStreamSynchronize(c->stream));
+  return BPVO_OK;
 }
 int bpvo_hip_seq_capacity(const bpvo_hip_ctx* c, int* n_sequences)
 {

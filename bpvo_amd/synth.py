@@ -353,10 +353,11 @@ def make_sequence(rows: int, cols: int, n_frames: int, index: int = 0, step_rot:
     return dict(K=K, b=b, frames=frames, poses=poses)
 
 
-def make_stereo_sequence(rows: int, cols: int, n_frames: int, index: int = 0, step_rot: float = 0.004, step_trans: float = 0.03):
+def make_stereo_sequence(rows: int, cols: int, n_frames: int, index: int = 0, step_rot: float = 0.004, step_trans: float = 0.03, camera=None):
     """make_sequence with the right image of every frame (the rig's right camera sits the baseline along +x of the left one):
-    list of (left, right) and the true left disparities — input of the stereo front-end + addFrame."""
-    seq = make_sequence(rows, cols, n_frames, index, step_rot, step_trans)
+    list of (left, right) and the true left disparities — input of the stereo front-end + addFrame.  camera=(K 3x3, baseline): as
+    make_sequence's — both images rendered with that K, the right one that baseline away."""
+    seq = make_sequence(rows, cols, n_frames, index, step_rot, step_trans, camera=camera)
     seed = 1000 + int(index)
     shift = np.eye(4)
     shift[0, 3] = -seq["b"]

@@ -356,6 +356,28 @@ int bpvo_hip_stereo_bm(bpvo_hip_ctx* ctx, int count, const uint8_t* left, const 
 /* VisualOdometry::addFrame(left, StereoAlgorithm::run(left, right)): the disparity map stays on the device */
 int bpvo_hip_add_frame_stereo(bpvo_hip_ctx* ctx, const uint8_t* left, const uint8_t* right, const bpvo_hip_stereo_params* sp,
                               bpvo_hip_result* result);
+/* ---- the stereo front-end for many cameras (apps/vo_app.cc per camera: StereoAlgorithm::run on the rectified pair, then addFrame).
+ * One sp serves a call; the frames are packed as for bpvo_hip_add_frames with per-sequence cameras: frame i has rows_i x cols_i pixels, the
+ * left images back to back in call order, the right images likewise.  Every check — the parameters against every camera's size (SGM:
+ * rows > windowRadius; block matching: SADWindowSize below rows and cols; SGBM: its own limits), the arguments, for
+ * bpvo_hip_add_frames_stereo also every check of bpvo_hip_add_frames — comes before anything changes, with the sequence (for
+ * bpvo_hip_stereo_frames: the frame's index) named in bpvo_hip_last_error where one is at fault; after an error every sequence goes on as
+ * if the call had not been made.
+ * Block matching runs all the frames of a call in one launch per stage whatever their sizes; SGM runs neighbouring frames of one size
+ * together, option "stereo_frames_per_launch" at a time; SGBM runs frame after frame.  The maps do not depend on any of that.
+ *
+ * StereoAlgorithm::run for n rectified pairs of n cameras' sizes: pair i has cams[i].rows x cams[i].cols pixels, the left images back to
+ * back in call order, the right images likewise, the f32 disparities likewise.  Only rows / cols of a camera are read.  Each map equals,
+ * bit for bit, what bpvo_hip_stereo_bm returns on a bpvo_hip_create context of that size.  Every size must fit the context's
+ * (rows <= ctx rows, cols <= ctx cols; BPVO_ERR_UNSUPPORTED). */
+int bpvo_hip_stereo_frames(bpvo_hip_ctx* ctx, int n, const bpvo_hip_camera* cams /*[n]*/, const uint8_t* left, const uint8_t* right,
+                           int on_device, const bpvo_hip_stereo_params* sp, float* disparity, int disparity_on_device);
+/* bpvo_hip_add_frames fed by the stereo front-end: results[i] is what bpvo_hip_add_frame_stereo(left_i, right_i, sp) returns for that
+ * frame on a bpvo_hip_create context of sequence seq[i]'s camera, bit for bit.  The disparities are computed on the device in each
+ * camera's own geometry and stay there; left images from host memory are uploaded once.  A context may mix bpvo_hip_add_frames and
+ * bpvo_hip_add_frames_stereo calls freely, also within one sequence. */
+int bpvo_hip_add_frames_stereo(bpvo_hip_ctx* ctx, int n, const int* seq /*[n] distinct ids, NULL = 0..n-1*/, const uint8_t* left,
+                               const uint8_t* right, int on_device, const bpvo_hip_stereo_params* sp, bpvo_hip_result* results /*[n]*/);
 
 /* Pyramid levels that were run by the persistent single-launch Gauss-Newton kernel (groups of BPVO_HIP_PERSIST_MAX_WS or fewer
  * pairs) since the context was created, and whether such a launch ever gave up at a grid barrier (the
@@ -435,6 +457,11 @@ int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* ctx, uint64_t out[4]);
  *                                      estimate is queued: the copy from pageable memory holds the host for 90 us (640x480), which then lie under the
  *                                      Gauss-Newton kernels — where the estimate is the persistent kernel's launch per level, queued in one go (0, and on
  *                                      the chain, whose rounds the host paces: in the data stage)
+ *   "stereo_frames_per_launch" 0       SGM frames of one size that go through every kernel of the matcher in one launch (each on its own slice of the
+ *                                      scratch): 0 = as many as fit a third of the device memory that was free when the scratch was first needed, 1 = one
+ *                                      frame after the other, k = at most k.  Same maps.
+ *   "stereo_frames_per_launch_seen" (read-only) the frames per launch the last SGM call used
+ *   "stereo_free_mib_seen"   (read-only) the free device memory, MiB, the rule above saw when this context first needed the SGM scratch
  *   "normalization_form"     4         the sequential (reference-order) Hartley sums: 1 = hand-scheduled DPP add chains (170 us for a 1241x376 template,
  *                                      2.28 ms for a dense 640x480 one); 0 = the compiler's DPP form (281 us / 3.6 ms); 2 = every lane of a row reads the same
  *                                      four consecutive elements from LDS and adds them with plain adds — no cross-lane traffic, no asm (311 us / 4.0 ms);

@@ -438,6 +438,20 @@ class VisualOdometrySequences {
     return ret;
   }
 
+  /* The same from rectified pairs, as the reference's apps feed every camera (apps/vo_app.cc: StereoAlgorithm::run(left, right), then
+   * addFrame): left / right hold n images back to back, pair i of its sequence's size; the disparities are computed on the device in
+   * each camera's own geometry and stay there (bpvo_hip_add_frames_stereo).  One StereoParameters serves the call. */
+  std::vector<Result> addFrames(const uint8_t* left, const uint8_t* right, const StereoParameters& stereo, const int* seq = nullptr, int n = -1)
+  {
+    if(left == nullptr || right == nullptr) throw Error("nullptr image");
+    if(n < 0) n = numSequences();
+    std::vector<bpvo_hip_result> r((size_t) n);
+    _dev->check(bpvo_hip_add_frames_stereo(_dev->ctx(), n, seq, left, right, 0, &stereo, r.data()));
+    std::vector<Result> ret;
+    for(int i = 0; i < n; ++i) ret.push_back(makeResult(seq ? seq[i] : i, r[i]));
+    return ret;
+  }
+
   const Trajectory& trajectory(int s) const { return _trajectories.at((size_t) s); }
   int numPointsAtLevel(int s, int level = -1) const
   {
