@@ -578,6 +578,16 @@ class Context:
         cam = _as_camera(cam)
         self.call("seq_set_camera", int(s), C.byref(cam))
 
+    def seq_set_params(self, s, params: Params):
+        """bpvo_hip_seq_set_params: sequence s runs with its own Params (loss, iteration limit, tolerances, key-frame thresholds, minSaliency,
+        disparity gate); only while it holds no frame."""
+        self.call("seq_set_params", int(s), C.byref(params))
+
+    def seq_get_params(self, s) -> Params:
+        p = Params()
+        self._ck(self.b.fn("seq_get_params")(self.h, int(s), C.byref(p)))
+        return p
+
     def seq_get_camera(self, s) -> Camera:
         cam = Camera()
         self._ck(self.b.fn("seq_get_camera")(self.h, int(s), C.byref(cam)))

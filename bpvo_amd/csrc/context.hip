@@ -129,6 +129,9 @@ FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l)
   j.b = g.b;
   j.dspace = c->dspace;
   j.lazy = f.lazy[l] ? 1 : 0;
+  // the selection thresholds: those of the slot's sequence (bpvo_hip_seq_set_params), or the context's
+  const bpvo_hip_params& sp = f.seq_params ? *f.seq_params : c->params;
+  j.min_saliency = sp.minSaliency; j.min_disp = sp.minValidDisparity; j.max_disp = sp.maxValidDisparity;
   return j;
 }
 
@@ -164,7 +167,16 @@ PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l)
   j.pitch = c->C;
   j.n_groups = c->G;
   j.med_tot = (int) med_totals_at(c);
+  // PoseEstimatorParameters(AlgorithmParameters) (bpvo/pose_estimator_params.cc:27-33): maxFuncEvals stays 6*200 (Q4); the low-res parameter
+  // set equals the full-res one (Q3).  The context's parameters; a sequence with its own: pair_job_set_params
+  pair_job_set_params(j, c->params);
   return j;
+}
+void pair_job_set_params(PairJob& j, const bpvo_hip_params& p)
+{
+  j.prm = GNParams{p.maxIterations, kMaxFunEvals, p.parameterTolerance, p.functionTolerance, p.gradientTolerance};
+  j.loss = p.lossFunction;
+  j.good_thr = p.goodPointThreshold;
 }
 
 // channel group k (0 .. G-1) of a whole job: the same point set, the descriptor / template / residual records entered at the group's first

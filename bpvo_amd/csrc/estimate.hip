@@ -65,11 +65,19 @@ static bool templates_suit_teams(const bpvo_hip_ctx* c, int n, const int* refs)
 // allow_persistent: only a group that has the device to itself (a batch on ONE lane) may take the persistent kernel — two
 // hand-barrier grids of concurrent lanes must not be co-scheduled.
 int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* refs, const int* curs, const float* T_init,
-                   float* poses, bpvo_hip_stats* stats, float* d_records_out, bool allow_persistent)
+                   float* poses, bpvo_hip_stats* stats, float* d_records_out, bool allow_persistent, const bpvo_hip_params* const* prms)
 {
   if(n <= 0) return BPVO_OK;
   (void) hipSetDevice(c->device);
   const bpvo_hip_params& p = c->params;
+  // the group's loss (one per group: estimate_batch) and the largest iteration limit among its entries: the host sizes its rounds by it, the
+  // device enforces each workspace's own (PairJob::prm)
+  const int loss = prms ? prms[0]->lossFunction : p.lossFunction;
+  int max_iterations = p.maxIterations;
+  if(prms) {
+    max_iterations = prms[0]->maxIterations;
+    for(int i = 1; i < n; ++i) max_iterations = std::max(max_iterations, prms[i]->maxIterations);
+  }
   const int NP = c->n_pairs;
   // (the pinned staging of a lane is free here: every call that uses it ends with a synchronisation of the lane's stream)
   std::vector<int> max_pts(c->L, 0);
@@ -78,6 +86,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
     for(int i = 0; i < n; ++i) {
       PairJob& pj = ln->h_pjobs[(size_t) l * NP + i];
       pj = make_pair_job(c, wss[i], refs[i], curs[i], l);
+      if(prms) pair_job_set_params(pj, *prms[i]);
       for(int k = 0; k < c->G && c->G > 1; ++k) ln->h_pjobs[(size_t) (1 + k) * table + (size_t) l * NP + i] = group_pair_job(c, pj, k);
       // Dense levels (no non-maximum suppression: most pixels are template points) gather their taps straight from the descriptor:
       // neighbouring points share three quarters of their footprints, so the 32-byte records are fetched about once per pixel
@@ -115,9 +124,6 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
     launch_set_pose(ln->stream, ln->d_pjobs + (size_t) (c->L - 1) * NP, dT, n, persistent ? ln->d_pk_ctl : nullptr, persistent ? kPkCtlWords * kMaxLevels : 0);
   }
 
-  // PoseEstimatorParameters(AlgorithmParameters) (bpvo/pose_estimator_params.cc:27-33): maxFuncEvals stays 6*200 (Q4);
-  // the low-res parameter set equals the full-res one (Q3).
-  const int max_fun_evals = 6 * 200;
   // Small batches: the whole level loop in ONE launch, a team of workgroups per pair (gn_team_kernel)
   bool team_ran = false;
   // the normalisation of the levels below the coarsest, of the template stage queued just before (frames.hip, ctx->nrm_pending), may still be
@@ -146,8 +152,8 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
       if(int rcj = join_normalization(-1)) return rcj;
     GNTeamLaunch t;
     t.jobs_all = ln->d_pjobs; t.job_pitch = NP; t.n_pairs = n; t.level_hi = c->L - 1; t.level_lo = p.maxTestLevel;
-    t.C = c->C; t.loss = p.lossFunction; t.fuse_frozen = c->fuse_frozen;
-    t.scale_is_moot = (p.lossFunction == BPVO_LOSS_L2 && c->C == 8 && c->fuse_frozen) ? 1 : 0;
+    t.C = c->C; t.loss = loss; t.fuse_frozen = c->fuse_frozen;
+    t.scale_is_moot = (loss == BPVO_LOSS_L2 && c->C == 8 && c->fuse_frozen) ? 1 : 0;
     const TeamPlan plan = team_plan(c, n);      // (the same plan team_serves judged)
     t.team_size = plan.team_size;
     t.n_teams = plan.n_teams;
@@ -160,7 +166,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
     hipError_t te;
     if(team_split) {
       t.level_lo = c->L - 1;
-      te = launch_gn_team(ln->stream, t, p.maxIterations, max_fun_evals, p.parameterTolerance, p.functionTolerance, p.gradientTolerance);
+      te = launch_gn_team(ln->stream, t);
       if(te == hipSuccess) {
         // (the first launch's control words: its abort word and join count are looked at with the second's)
         LANE_CK(ln, hipMemcpyAsync(ln->h_team_ctl + 32, ln->d_team_ctl, sizeof(unsigned) * 32, hipMemcpyDeviceToHost, ln->stream));
@@ -168,9 +174,9 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
       }
       if(int rcj = join_normalization(-1)) return rcj;
       t.level_hi = c->L - 2; t.level_lo = p.maxTestLevel;
-      if(te == hipSuccess) te = launch_gn_team(ln->stream, t, p.maxIterations, max_fun_evals, p.parameterTolerance, p.functionTolerance, p.gradientTolerance);
+      if(te == hipSuccess) te = launch_gn_team(ln->stream, t);
     } else {
-      te = launch_gn_team(ln->stream, t, p.maxIterations, max_fun_evals, p.parameterTolerance, p.functionTolerance, p.gradientTolerance);
+      te = launch_gn_team(ln->stream, t);
     }
     if(te == hipSuccess) {
       team_ran = true;
@@ -187,18 +193,17 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
     g.npairs = n;
     g.max_points = max_pts[l];
     g.C = c->C;
-    g.loss = p.lossFunction;
+    g.loss = loss;
     g.fast_warp = c->fast_warp;
     g.interp = p.interp;
     g.fuse_frozen = fuse_frozen;
     g.step_in_reduce = (n <= c->step_in_reduce_max && !ref_mode && c->G == 1) ? 1 : 0;
     g.reference_reduction = ref_mode ? 1 : 0;
     g.dense_candidates = dense_candidates(c, g.max_points);
-    g.step_prm = GNParams{p.maxIterations, max_fun_evals, p.parameterTolerance, p.functionTolerance, p.gradientTolerance};
     return g;
   };
   // kL2: the weights are 1 whatever the robust scale — with the fused path every linearisation is irls_reduce + gn_step only
-  const bool l2_moot = p.lossFunction == BPVO_LOSS_L2 && c->C == 8 && fuse_frozen && !c->fast_warp && p.interp == BPVO_INTERP_LINEAR;
+  const bool l2_moot = loss == BPVO_LOSS_L2 && c->C == 8 && fuse_frozen && !c->fast_warp && p.interp == BPVO_INTERP_LINEAR;
   bool begun = false;      // this level's start was left to its persistent kernel (its tap-cache keys invalidated by the kernel of the level before)
   for(int l = c->L - 1; l >= p.maxTestLevel && !team_ran; --l) {
     GNLaunch g = level_launch(l);
@@ -214,8 +219,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
       g.begin_level = was_begun ? l : -1;
       g.begin_moot = l2_moot ? 1 : 0;
       g.next_jobs = next_too ? ln->d_pjobs + (size_t) (l - 1) * NP : nullptr;
-      const hipError_t pe = launch_gn_persistent(ln->stream, g, p.maxIterations, max_fun_evals, p.parameterTolerance, p.functionTolerance, p.gradientTolerance,
-                                                 ln->d_pk_ctl + (size_t) l * kPkCtlWords, gn_persistent_grid(g, c->persist_grid), c->persist_timeout);
+      const hipError_t pe = launch_gn_persistent(ln->stream, g, ln->d_pk_ctl + (size_t) l * kPkCtlWords, gn_persistent_grid(g, c->persist_grid), c->persist_timeout);
       if(pe == hipSuccess) {
         c->persistent_levels.fetch_add(1);
         begun = next_too;
@@ -235,7 +239,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
     // as those have landed — the device never waits for the host (a synchronisation per round was a ~30 us bubble: 7 % of a
     // round at 128 pairs, 11 % for a single pair).  Workspaces that finished in between are still dispatched for one more
     // round (their workgroups exit on the first load), and the level ends with one round of empty launches.
-    const int max_lin = std::min(p.maxIterations + 2, max_fun_evals);
+    const int max_lin = std::min(std::max(max_iterations, 0) + 2, kMaxFunEvals);
     const int kItersPerSync = 4;
     const int max_rounds = (max_lin + kItersPerSync - 1) / kItersPerSync + 2;
     constexpr unsigned kProfileEvery = 5;   // co-prime with kItersPerSync: no phase lock with the host round trips
@@ -268,7 +272,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
         }
         if(!g.step_in_reduce) {
           ScopedTimer t(c, KC_GN_STEP, 0.0, ln, c->profile_all);
-          launch_gn_step(ln->stream, g, 0, p.maxIterations, max_fun_evals, p.parameterTolerance, p.functionTolerance, p.gradientTolerance);
+          launch_gn_step(ln->stream, g, 0);
         }
       }
       const int slot = round % 3;
@@ -349,7 +353,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
   if(team_ran && (ln->h_team_ctl[1] != 0 || (team_split && ln->h_team_ctl[32 + 1] != 0))) {
     // a team barrier timed out (teams not co-resident): rerun the group through the four-kernel chain and stay on it
     c->persistent_failed.store(true);
-    return estimate_group(c, ln, n, wss, refs, curs, T_init, poses, stats, d_records_out, false);
+    return estimate_group(c, ln, n, wss, refs, curs, T_init, poses, stats, d_records_out, false, prms);
   }
   if(pk_group) {
     bool gave_up = false;
@@ -358,7 +362,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
       // a barrier timed out: the states of that level were not written back.  Rerun the group through the four-kernel chain
       // (same results) and keep this context on it.
       c->persistent_failed.store(true);
-      return estimate_group(c, ln, n, wss, refs, curs, T_init, poses, stats, d_records_out, false);
+      return estimate_group(c, ln, n, wss, refs, curs, T_init, poses, stats, d_records_out, false, prms);
     }
   }
   for(int i = 0; i < n; ++i) {
@@ -370,8 +374,46 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
   return BPVO_OK;
 }
 
-int estimate_batch(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses,
-                   bpvo_hip_stats* stats)
+// Entries with parameters of their own (bpvo_hip_add_frames): the loss is a template parameter of the reduction, persistent and team kernels, so
+// the entries of a call are PARTITIONED by loss — at most three estimates, one per loss present and never one per sequence, each over the
+// entries of that loss in call order; everything else a sequence may own travels in its jobs.  One loss (every call without per-sequence
+// parameters): the one estimate there has always been.  (The alternative, a loss read per workspace inside the kernels: DESIGN.md §5.)
+static int estimate_one_loss(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses, bpvo_hip_stats* stats,
+                             const bpvo_hip_params* const* prms);
+int estimate_batch(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses, bpvo_hip_stats* stats,
+                   const bpvo_hip_params* const* prms)
+{
+  bool one_loss = true;
+  for(int i = 1; i < n && prms && one_loss; ++i) one_loss = prms[i]->lossFunction == prms[0]->lossFunction;
+  if(!prms || one_loss) return estimate_one_loss(c, n, wss, refs, curs, T_init, poses, stats, prms);
+  std::vector<char> done((size_t) n, 0);
+  for(int i = 0; i < n; ++i) {
+    if(done[i]) continue;
+    std::vector<int> at, w, r, cu;
+    std::vector<const bpvo_hip_params*> pp;
+    for(int k = i; k < n; ++k)
+      if(!done[k] && prms[k]->lossFunction == prms[i]->lossFunction) {
+        done[k] = 1;
+        at.push_back(k); w.push_back(wss[k]); r.push_back(refs[k]); cu.push_back(curs[k]); pp.push_back(prms[k]);
+      }
+    const int m = (int) at.size();
+    std::vector<float> Ti, To((size_t) m * 16);
+    std::vector<bpvo_hip_stats> st((size_t) m * c->L);
+    if(T_init) {
+      Ti.resize((size_t) m * 16);
+      for(int k = 0; k < m; ++k) std::memcpy(&Ti[(size_t) k * 16], T_init + 16 * (size_t) at[k], 64);
+    }
+    const int rc = estimate_one_loss(c, m, w.data(), r.data(), cu.data(), T_init ? Ti.data() : nullptr, To.data(), st.data(), pp.data());
+    if(rc) return rc;
+    for(int k = 0; k < m; ++k) {
+      if(poses) std::memcpy(poses + 16 * (size_t) at[k], &To[(size_t) k * 16], 64);
+      if(stats) std::memcpy(stats + (size_t) at[k] * c->L, &st[(size_t) k * c->L], sizeof(bpvo_hip_stats) * (size_t) c->L);
+    }
+  }
+  return BPVO_OK;
+}
+static int estimate_one_loss(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses, bpvo_hip_stats* stats,
+                             const bpvo_hip_params* const* prms)
 {
   if(n <= 0) return BPVO_OK;
   if(n > c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "more pairs than workspaces");
@@ -398,7 +440,7 @@ int estimate_batch(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, cons
     const int lo = (int) ((long long) n * k / nl), hi = (int) ((long long) n * (k + 1) / nl);
     rcs[k] = estimate_group(c, &c->lanes[k], hi - lo, wss + lo, refs + lo, curs + lo, T_init ? T_init + 16 * (size_t) lo : nullptr,
                             poses ? poses + 16 * (size_t) lo : nullptr, stats ? stats + (size_t) lo * c->L : nullptr,
-                            c->d_records + (size_t) kRecordFloats * lo, nl == 1);
+                            c->d_records + (size_t) kRecordFloats * lo, nl == 1, prms ? prms + lo : nullptr);
   };
   if(nl == 1) {
     run(0);
@@ -589,7 +631,7 @@ static int linearize_impl(bpvo_hip_ctx* c, int ws, int ref_slot, int cur_slot, i
     if(g.reference_reduction) launch_irls_reduce(c->stream, g);
     else for_each_group(c, g, 1, [&](const GNLaunch& gg) { launch_irls_reduce(c->stream, gg); });
   }
-  { ScopedTimer t(c, KC_GN_STEP, 0.0); launch_gn_step(c->stream, g, 1, 0, 0, 0, 0, 0); }
+  { ScopedTimer t(c, KC_GN_STEP, 0.0); launch_gn_step(c->stream, g, 1); }
   HIP_CK(c, hipMemcpyAsync(l0.h_states, c->d_states + ws, sizeof(GNState), hipMemcpyDeviceToHost, c->stream));
   HIP_CK(c, hipStreamSynchronize(c->stream));
   HIP_CK(c, hipGetLastError());
@@ -708,7 +750,7 @@ int bpvo_hip_estimate_pose_trace(bpvo_hip_ctx* c, int ws, int ref_slot, int cur_
   if(int rc = check_template_not_empty(c, ref_slot)) return rc;
   (void) hipSetDevice(c->device);
   // at most min(maxIterations + 2, maxFuncEvals) linearisations per level (pose_estimator_base.h:373-393)
-  const int cap = c->L * (std::min(std::max(c->params.maxIterations, 0) + 2, 6 * 200) + 1);
+  const int cap = c->L * (std::min(std::max(c->params.maxIterations, 0) + 2, kMaxFunEvals) + 1);
   if(cap > c->trace_cap) {
     HIP_CK(c, hipStreamSynchronize(c->stream));
     (void) hipFree(c->d_trace);

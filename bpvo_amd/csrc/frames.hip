@@ -246,14 +246,14 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
     for(int l = p.maxTestLevel; l < c->L; ++l) px += (double) geom[l].npix * count;
     ScopedTimer t(c, KC_SALIENCY_SELECT, px, fr.ln);
     const LevelGeom& g = geom[p.maxTestLevel];
-    launch_saliency_select(s, tab + (size_t) p.maxTestLevel * NF, c->C, g.cols, g.rows, count, 1, p.minSaliency, p.minValidDisparity, p.maxValidDisparity, border,
+    launch_saliency_select(s, tab + (size_t) p.maxTestLevel * NF, c->C, g.cols, g.rows, count, 1, border,
                            c->L - p.maxTestLevel, NF);
   }
   for(int l = c->L - 1; l >= p.maxTestLevel && !one_launch; --l) {
     const FrameJob* jobs = tab + (size_t) l * NF;
     const LevelGeom& g = geom[l];
     ScopedTimer t(c, KC_SALIENCY_SELECT, (double) g.npix * count, fr.ln);
-    launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, p.minSaliency, p.minValidDisparity, p.maxValidDisparity, border);
+    launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, border);
   }
   if(side) {
     FR_CK(c, fr, hipEventRecord(c->side_ev[0], s));

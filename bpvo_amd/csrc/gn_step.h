@@ -209,14 +209,15 @@ __device__ __forceinline__ void gn_sum_partials(const PairJob& j, int pts_per_bl
 // one thread, on an LDS copy `st` of the state: the step that consumes the linearisation summed in s_sum.  `stats`: this copy
 // is the one that keeps the workspace's measurement counters (the persistent kernel runs the step redundantly in every workgroup)
 __device__ __forceinline__ void gn_serial_step(const PairJob& j, GNState* st, const float* s_nrm, const float* s_sum, SolveScratch* scratch,
-                                               int mode, int max_iterations, int max_fun_evals, float p_tol, float f_tol, float g_tol_param,
-                                               int fuse_frozen, bool stats)
+                                               int mode, int fuse_frozen, bool stats)
 {
+  // the workspace's own limits and tolerances: GNState::prm, with the rest of the state in LDS (set_pose copied them from PairJob::prm)
+  const GNParams prm = st->prm;
   // the linearisation consumed here was taken at st->T; with the fused path its residuals were never written
   for(int i = 0; i < 16; ++i) st->T_lin[i] = st->T[i];
   const bool fused_lin = fuse_frozen && !(st->delta_scale > 1e-6f);
   st->r_stale = fused_lin ? 1 : 0;
-  const bool again = gn_logic(st, s_nrm, s_sum, scratch, mode, max_iterations, max_fun_evals, p_tol, f_tol, g_tol_param);
+  const bool again = gn_logic(st, s_nrm, s_sum, scratch, mode, prm.max_iterations, prm.max_fun_evals, prm.p_tol, prm.f_tol, prm.g_tol);
   (void) again;   // who is still active is read from st->active (compact_active_kernel once per host round / the persistent loop)
   if(stats && mode == 0 && j.trace) {
     // bpvo_hip_estimate_pose_trace: the linearisation just consumed (pose, system, function value, scale, valid count) and the step
@@ -258,7 +259,7 @@ __device__ __forceinline__ void wave_lds_sync()      // LDS written by some lane
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 template <bool COHERENT>
-__device__ __forceinline__ void gn_step_wave(const PairJob& j, GNStepLds& s, int pts_per_block, int mode, const GNParams& prm, int fuse_frozen)
+__device__ __forceinline__ void gn_step_wave(const PairJob& j, GNStepLds& s, int pts_per_block, int mode, int fuse_frozen)
 {
   constexpr int kWords = (int) (sizeof(GNState) / sizeof(uint32_t));
   const int lane = threadIdx.x;
@@ -269,8 +270,7 @@ __device__ __forceinline__ void gn_step_wave(const PairJob& j, GNStepLds& s, int
   gn_sum_partials<COHERENT>(j, pts_per_block, lane, s.sum, j.partials);
   wave_lds_sync();
   if(lane == 0)
-    gn_serial_step(j, reinterpret_cast<GNState*>(s.state), s.nrm, s.sum, &s.scratch, mode, prm.max_iterations, prm.max_fun_evals, prm.p_tol, prm.f_tol,
-                   prm.g_tol, fuse_frozen, true);
+    gn_serial_step(j, reinterpret_cast<GNState*>(s.state), s.nrm, s.sum, &s.scratch, mode, fuse_frozen, true);
   wave_lds_sync();
   for(int i = lane; i < kWords; i += 64) reinterpret_cast<uint32_t*>(gst)[i] = s.state[i];
 }

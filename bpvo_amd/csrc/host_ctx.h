@@ -78,6 +78,9 @@ struct FrameSlot {
   // its level geometry, sizes within the context's storage geometry; slot_geom below picks it
   bool own_geom = false;
   LevelGeom geom[kMaxLevels];
+  // the algorithm parameters of the slot's sequence when they are not the context's own (bpvo_hip_seq_set_params: SeqState::params), else null;
+  // the frame stages take the selection thresholds from them (make_frame_job)
+  const bpvo_hip_params* seq_params = nullptr;
 };
 
 // One sequence of bpvo_hip_add_frames (vo.hip): the VisualOdometry state of bpvo/vo.cc:45-52 for frame slots 3s .. 3s+2 and workspace s
@@ -87,6 +90,10 @@ struct SeqState {
   std::vector<M44> trajectory;
   size_t cloud_n = 0;               // the point cloud of the sequence's last Result: records [s * cap, s * cap + cloud_n) of bpvo_hip_ctx::d_seq_cloud
   M44 cloud_pose;
+  // the sequence's algorithm parameters (bpvo_hip_seq_set_params; the context's until then) — they outlive bpvo_hip_seq_reset, like its camera.
+  // own_params: they differ from the context's in a field the library reads (only then do the sequence's jobs and decisions take them from here)
+  bpvo_hip_params params;
+  bool own_params = false;
 };
 
 struct Workspace {
@@ -143,6 +150,7 @@ constexpr int kDefaultLanesNarrow = 2;
 constexpr int kMinPairsPerLane = 8;
 constexpr int kPkCtlWords = 32;    // one 128-byte line per level
 constexpr int kMaxTeams = 1024;
+constexpr int kMaxFunEvals = 6 * 200;   // PoseEstimatorParameters::maxFuncEvals, which AlgorithmParameters does not reach (Q4)
 
 }  // namespace bpvo_hip_host
 
@@ -448,7 +456,8 @@ void carve_frame_data(bpvo_hip_ctx* c, FrameSlot& f, unsigned char* base, size_t
 void carve_frame_tmpl(bpvo_hip_ctx* c, FrameSlot& f, unsigned char* base, size_t* total);
 int ensure_template_storage(bpvo_hip_ctx* c, FrameSlot& f);
 FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l);
-PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l);
+PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l);      // (with the context's parameters)
+void pair_job_set_params(PairJob& j, const bpvo_hip_params& p);              // ... and a sequence's own in their place
 void resolve_events(bpvo_hip_ctx* c);
 FrameRun ctx_run(bpvo_hip_ctx* c);
 int upload_frame_jobs(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr, int which, const FrameJob** tab);
@@ -512,9 +521,13 @@ inline bool single_pair_is_queued_at_once(const bpvo_hip_ctx* c)
 }
 inline int dense_candidates(const bpvo_hip_ctx* c, int max_points) { return (c->G == 1 && max_points >= c->dense_candidates_from) ? 1 : 0; }
 inline bpvo_hip::GNLaunch median_launch(const bpvo_hip_ctx* c, bpvo_hip::GNLaunch g) { if(c->G > 1) g.C = c->Cg; return g; }
+// prms: null (every entry runs with the context's parameters: the batch entry points, the single-sequence path), or each entry's own parameters
+// (bpvo_hip_add_frames).  estimate_batch runs one estimate per loss among them — the loss instantiates the kernels —, so every entry of an
+// estimate_group call has the same loss; limits and tolerances travel in the entries' jobs.
 int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses,
-                   bpvo_hip_stats* stats, float* d_records_out, bool allow_persistent);
-int estimate_batch(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses, bpvo_hip_stats* stats);
+                   bpvo_hip_stats* stats, float* d_records_out, bool allow_persistent, const bpvo_hip_params* const* prms = nullptr);
+int estimate_batch(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses, bpvo_hip_stats* stats,
+                   const bpvo_hip_params* const* prms = nullptr);
 void detile_to_channel_major(const float* src, int n, int C, int E, int V, float* out);
 size_t tiled_floats(int n, int floats_per_point);
 int refresh_counters(bpvo_hip_ctx* c);

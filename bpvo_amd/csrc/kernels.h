@@ -76,8 +76,8 @@ void launch_census(hipStream_t s, const FrameJob* jobs, int W, int R, int nframe
 // levels in one launch (kernels_frame.hip level_job)
 void launch_bitplanes(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, float sigma, const float k[3], int from_image, int nlevels = 1,
                       int job_pitch = 0);
-void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, float min_saliency,
-                            float min_disp, float max_disp, int border, int nlevels = 1, int job_pitch = 0);
+// (minSaliency and the disparity gate: each frame's own, FrameJob::min_saliency / min_disp / max_disp)
+void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, int nlevels = 1, int job_pitch = 0);
 void launch_copy_rows(hipStream_t s, void* dst, const void* src_host_pinned, size_t pitch_bytes, size_t width_bytes, int rows);   // multiples of 8 bytes
 void launch_gather_counts(hipStream_t s, const FrameJob* jobs /*[L][job_pitch]*/, int job_pitch, int nframes, int first_level, int num_levels,
                           int* out /*[nframes][kMaxLevels]*/);
@@ -163,9 +163,8 @@ struct GNLaunch {
   int dense_candidates = 0;
   int fast_warp = 0;     // 1: projectPoints / BilinearInterp all-f32 formulation (bpvo_hip_set_warp_formulation)
   // 1: the tile of a workspace that stores its partial LAST in an irls_reduce launch also takes the Gauss-Newton step (what
-  // gn_step_kernel does, with step_prm) — the chain is then three kernels per iteration and launch_gn_step is not called
+  // gn_step_kernel does) — the chain is then three kernels per iteration and launch_gn_step is not called
   int step_in_reduce = 0;
-  GNParams step_prm = {0, 0, 0.0f, 0.0f, 0.0f};
   // gn_persistent_kernel only: begin_level >= 0 — the kernel takes the level's start itself (level_begin_kernel's state reset; the tap-cache
   // keys were invalidated by the kernel of the level before, which was handed this level's jobs as next_jobs)
   int begin_level = -1, begin_moot = 0;
@@ -187,15 +186,14 @@ void launch_median(hipStream_t s, const GNLaunch& g);
 void launch_irls_reduce(hipStream_t s, const GNLaunch& g);
 void launch_reference_reduce(hipStream_t s, const GNLaunch& g);   // what launch_irls_reduce does with g.reference_reduction (kernels_gn_ref.hip)
 // mode 0: full PoseEstimatorBase::run step (solve, update, convergence); mode 1: linearize only (H, G, f_norm)
-void launch_gn_step(hipStream_t s, const GNLaunch& g, int mode, int max_iterations, int max_fun_evals, float p_tol,
-                    float f_tol, float g_tol);
+// The limits and tolerances of the state machine are each workspace's own, PairJob::prm — here and in the persistent and team kernels below
+void launch_gn_step(hipStream_t s, const GNLaunch& g, int mode);
 // Persistent kernel for small groups: one launch runs a whole level of up to kPersistMaxWs workspaces (kernels_gn.hip).  ctl: two
 // zeroed words {arrivals, abort}; after the launch ctl[1] != 0 says the kernel gave up (states untouched: rerun the chain).
 constexpr int kPersistMaxWs = 8;
 bool gn_persistent_serves(const GNLaunch& g);
 int  gn_persistent_grid(const GNLaunch& g, int max_grid);
-hipError_t launch_gn_persistent(hipStream_t s, const GNLaunch& g, int max_iterations, int max_fun_evals, float p_tol, float f_tol, float g_tol,
-                                unsigned* ctl, int grid, long long timeout_ticks);
+hipError_t launch_gn_persistent(hipStream_t s, const GNLaunch& g, unsigned* ctl, int grid, long long timeout_ticks);
 // Team-persistent kernel for small batches (kernels_gn.hip, gn_team_kernel): ONE launch runs every pair of the group through all its
 // pyramid levels; grid = team_size x n_teams workgroups, one per CU, all co-resident.  ctl: gn_team_ctl_words(n_teams) zeroed words;
 // after the launch ctl[1] != 0 says a team barrier gave up (rerun the group on the chain).
@@ -213,7 +211,7 @@ struct GNTeamLaunch {
 int  gn_team_ctl_words(int n_teams);
 void launch_team_ctl_reset_keep_abort(hipStream_t s, unsigned* ctl, int n_teams);   // between the launches of a split run: every control word to 0 but the abort word
 int  gn_team_max_size();       // teams stop admitting newcomers at this size
-hipError_t launch_gn_team(hipStream_t s, const GNTeamLaunch& t, int max_iterations, int max_fun_evals, float p_tol, float f_tol, float g_tol);
+hipError_t launch_gn_team(hipStream_t s, const GNTeamLaunch& t);
 void launch_prepare_linearize(hipStream_t s, const PairJob* job, const float* T /*device [16]*/, int reset_scale, int level, float given_scale = 0.0f);
 int  gn_pts_per_block(int C);
 int  gn_partials_entries(int cap, int C);   // kPartialStride-float entries of a workspace's (double-buffered) tile partials
@@ -225,14 +223,17 @@ void launch_point_cloud(hipStream_t s, const PairJob* job, int n, int C, int los
                         bpvo_hip_point_with_info* out);
 // the same two for a table of jobs in one launch each (bpvo_hip_add_frames): counts[k] (zeroed by the caller) of entry k; max_n: the most points of an entry
 void launch_count_good_batch(hipStream_t s, const PairJob* jobs, int n_jobs, int max_n, int C, int loss, float thr, unsigned int* counts);
+// ... with each entry's own loss and threshold (PairJob::loss / good_thr: sequences with parameters of their own)
+void launch_count_good_jobs(hipStream_t s, const PairJob* jobs, int n_jobs, int max_n, int C, unsigned int* counts);
 struct CloudJob {
   const PairJob* job;       // device: the job of the key frame's last linearisation
   const uint8_t* img;       // the key frame's level-0 image
   size_t out_offset;        // first record of this entry in the output
   float K[9];               // the intrinsics of the level the estimate ended on (each sequence its own camera)
   int rows, cols;           // the size of img
+  int loss;                 // the loss the weights are taken with (each sequence its own parameters)
 };
-void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int loss, int dspace, bpvo_hip_point_with_info* out);
+void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int dspace, bpvo_hip_point_with_info* out);
 void launch_pack_records(hipStream_t s, const PairJob* jobs, int n, int L, float* records, const GNState* d_states = nullptr, GNState* h_states = nullptr,
                          const unsigned* d_ctl = nullptr, unsigned* h_ctl = nullptr, int ctl_words = 0, unsigned* zero = nullptr);   // h_states / h_ctl (pinned host): copied out by the same launch; zero: a word cleared by it
 // a few pairs: job table upload (from the pinned host rows) + initial poses + cleared control words in one launch

@@ -676,10 +676,10 @@ __device__ __forceinline__ bool is_local_max(const float* __restrict__ S, int W,
 constexpr int SEL_PX = SEL_PX_VALUE;            // pixels per thread (4, 8 or 16; measured: 8 is 3-7 % slower, 16 12-24 %)
 constexpr int SEL_BLOCK_PX = 256 * SEL_PX;      // pixels per workgroup
 constexpr int SEL_GROUP = 256 / SEL_PX;         // lanes that share one 256-pixel chunk (64, 32 or 16)
-__global__ __launch_bounds__(256) void select_flag_kernel(const FrameJob* jobs, float min_saliency, float min_disp,
-                                                          float max_disp, int border)
+__global__ __launch_bounds__(256) void select_flag_kernel(const FrameJob* jobs, int border)
 {
   const FrameJob& j = jobs[blockIdx.z];
+  const float min_saliency = j.min_saliency, min_disp = j.min_disp, max_disp = j.max_disp;      // the frame's own thresholds
   const int W = j.cols, R = j.rows;
   const int npix = W * R;
   const int p0 = blockIdx.x * SEL_BLOCK_PX + threadIdx.x * SEL_PX;
@@ -868,7 +868,7 @@ __device__ __forceinline__ float saliency_generic(const FrameJob& j, int x, int 
 }
 
 template <int C>
-__global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJob* jobs, float min_saliency, float min_disp, float max_disp, int border, int nframes, int job_pitch)
+__global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJob* jobs, int border, int nframes, int job_pitch)
 {
   __shared__ float s_ch[ST_CH_ROWS][ST_CH_PITCH];
   __shared__ float s_sal[ST_S_ROWS][ST_S_PITCH];
@@ -919,6 +919,7 @@ __global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJo
     full[q] = fmaxf(side[q], t[1]);
   }
   bool ok[ST_ROWS_PER_WAVE];
+  const float min_saliency = j.min_saliency;      // the frame's own thresholds (one frame per workgroup: uniform)
 #pragma unroll
   for(int q = 0; q < ST_ROWS_PER_WAVE; ++q) {
     const int y = y0 + ry0 + q;
@@ -933,6 +934,7 @@ __global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJo
   for(int q = 0; q < ST_ROWS_PER_WAVE; ++q)
     dv[q] = ok[q] ? j.disp[(size_t) (1 << j.level) * ((size_t) (y0 + ry0 + q) * j.disp_cols + x)] : 0.0f;
   unsigned long long words = 0;      // lane q keeps the word of row q
+  const float min_disp = j.min_disp, max_disp = j.max_disp;
 #pragma unroll
   for(int q = 0; q < ST_ROWS_PER_WAVE; ++q) {
     const unsigned long long m = __ballot(ok[q] && dv[q] >= min_disp && dv[q] <= max_disp);
@@ -1629,15 +1631,14 @@ void launch_bitplanes(hipStream_t s, const FrameJob* jobs, int W, int R, int nfr
   else
     hipLaunchKernelGGL(bitplanes_noblur_kernel, dim3((W * R + 255) / 256, 1, nframes), dim3(256), 0, s, jobs);
 }
-void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, float min_saliency,
-                            float min_disp, float max_disp, int border, int nlevels, int job_pitch)
+void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, int nlevels, int job_pitch)
 {
   if(nms_radius <= 1) {
     // tiles: saliency + NMS + gate in one pass, candidate bits, word scan, lane-per-pixel compaction
     const int WPR = (W + 63) / 64, nw = R * WPR;
     auto tile = [&](auto c) {
       hipLaunchKernelGGL(saliency_select_tile_kernel<decltype(c)::value>, dim3(WPR, (R + ST_H - 1) / ST_H, nframes * nlevels), dim3(256), 0, s, jobs,
-                         min_saliency, min_disp, max_disp, border, nframes, job_pitch);
+                         border, nframes, job_pitch);
     };
     if(C <= 48 || !dispatch_wide_channels(C, tile)) dispatch_channels(C, tile);
     hipLaunchKernelGGL(select_words_scan_kernel, dim3(nframes * nlevels), dim3(1024), 0, s, jobs, nframes, job_pitch);
@@ -1649,7 +1650,7 @@ void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, i
   auto plain = [&](auto c) { hipLaunchKernelGGL(saliency_kernel<decltype(c)::value>, grid2d_rows(W, R, nframes), dim3(256), 0, s, jobs); };
   if(C <= 48 || !dispatch_wide_channels(C, plain)) dispatch_channels(C, plain);
   const int nblk = (W * R + SEL_BLOCK_PX - 1) / SEL_BLOCK_PX;
-  hipLaunchKernelGGL(select_flag_kernel, dim3(nblk, 1, nframes), dim3(256), 0, s, jobs, min_saliency, min_disp, max_disp, border);
+  hipLaunchKernelGGL(select_flag_kernel, dim3(nblk, 1, nframes), dim3(256), 0, s, jobs, border);
   hipLaunchKernelGGL(select_scan_kernel, dim3(nframes), dim3(1024), 0, s, jobs);
   hipLaunchKernelGGL(select_write_kernel, dim3(nblk, 1, nframes), dim3(256), 0, s, jobs);
 }

@@ -321,7 +321,7 @@ __global__ __launch_bounds__(NT) void median_finish_kernel(const PairJob* __rest
 // true (136 VGPRs instead of 103: kept out of the plain kernel's register budget) the frozen ones.
 // step.on (only without fuse_frozen, where one launch serves every workspace): the last tile of a workspace takes the Gauss-Newton
 // step (gn_last_tile); a workspace without points still has its tile 0 for that.
-struct GNStepArgs { int on; GNParams prm; };
+struct GNStepArgs { int on; };
 // (waves per SIMD the reduction had on its own: left alone the compiler gives the step's serial code 180 registers, and the whole
 // launch its occupancy)
 constexpr int irls_min_waves(int C) { return C <= 10 ? 4 : C <= 24 ? 3 : 2; }
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(GN_BLOCK, irls_min_waves(C)) void irls_reduce_kerne
   irls_block<C, LOSS, FUSED>(j, st, pts_per_block, true);
   if(threadIdx.x >= 64) return;
   __shared__ GNStepLds s_step;
-  if(gn_last_tile(j, tiles)) gn_step_wave<true>(j, s_step, pts_per_block, 0, step.prm, 0);
+  if(gn_last_tile(j, tiles)) gn_step_wave<true>(j, s_step, pts_per_block, 0, 0);
 }
 // ... or ONE launch serves both kinds with a per-workspace branch (C = 8): every workgroup then runs at the fused form's
 // register budget (3 waves per SIMD instead of 4), but small launches — the 128-pair shard of config 5, single pairs — do not
@@ -361,20 +361,17 @@ __global__ __launch_bounds__(GN_BLOCK, K8_BOTH_WAVES) void irls_reduce_both_kern
   else irls_block<8, LOSS, true>(j, st, pts_per_block, step.on != 0);
   if(!step.on || threadIdx.x >= 64) return;
   __shared__ GNStepLds s_step;
-  if(gn_last_tile(j, tiles)) gn_step_wave<true>(j, s_step, pts_per_block, 0, step.prm, 1);
+  if(gn_last_tile(j, tiles)) gn_step_wave<true>(j, s_step, pts_per_block, 0, 1);
 }
 
-__global__ __launch_bounds__(64, 4) void gn_step_kernel(const PairJob* __restrict__ jobs, int pts_per_block, int mode,
-                                                     int max_iterations, int max_fun_evals, float p_tol, float f_tol,
-                                                     float g_tol_param, ActiveSet act, int fuse_frozen)
+__global__ __launch_bounds__(64, 4) void gn_step_kernel(const PairJob* __restrict__ jobs, int pts_per_block, int mode, ActiveSet act, int fuse_frozen)
 {
   const PairJob& j = jobs[active_workspace(act, blockIdx.x)];
   GNState* gst = j.st;
   if(!gst->active) return;
 
   __shared__ GNStepLds s_step;
-  const GNParams prm = {max_iterations, max_fun_evals, p_tol, f_tol, g_tol_param};
-  gn_step_wave<false>(j, s_step, pts_per_block, mode, prm, fuse_frozen);
+  gn_step_wave<false>(j, s_step, pts_per_block, mode, fuse_frozen);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -421,6 +418,7 @@ __global__ void set_pose_kernel(const PairJob* jobs, const float* T_init, int n,
   GNState* st = jobs[p].st;
   for(int i = 0; i < 16; ++i) st->T_out[i] = T_init ? T_init[p * 16 + i] : ((i % 5 == 0) ? 1.0f : 0.0f);
   st->trace_n = 0;
+  st->prm = jobs[p].prm;      // this estimate's limits and tolerances: the workspace's own (every level's job carries the same)
   for(int l = 0; l < kMaxLevels; ++l) {                 // OptimizerStatistics() defaults (bpvo/types.cc:306-310)
     st->stats[l].numIterations = 0;
     st->stats[l].finalError = -1.0f;
@@ -443,6 +441,7 @@ __global__ __launch_bounds__(256) void set_pose_upload_kernel(unsigned long long
   GNState* st = h_jobs_coarsest[p].st;
   for(int i = 0; i < 16; ++i) st->T_out[i] = T_init ? T_init[p * 16 + i] : ((i % 5 == 0) ? 1.0f : 0.0f);
   st->trace_n = 0;
+  st->prm = h_jobs_coarsest[p].prm;
   for(int l = 0; l < kMaxLevels; ++l) {                 // OptimizerStatistics() defaults (bpvo/types.cc:306-310)
     st->stats[l].numIterations = 0;
     st->stats[l].finalError = -1.0f;
@@ -592,7 +591,7 @@ __global__ __launch_bounds__(256) void point_cloud_batch_kernel(const CloudJob* 
   if(i >= j.n) return;
 #pragma unroll
   for(int k = 0; k < 9; ++k) a.K[k] = cj.K[k];
-  a.rows = cj.rows; a.cols = cj.cols;
+  a.rows = cj.rows; a.cols = cj.cols; a.loss = cj.loss;
   out[cj.out_offset + i] = cloud_record(j, i, cj.img, a);
 }
 
@@ -666,6 +665,41 @@ __global__ __launch_bounds__(256) void count_good_batch_wide_kernel(const PairJo
   const float sigma_inv = 1.0f / job->st->scale;
   unsigned good = 0;
   for(size_t k = (size_t) blockIdx.x * 256 + threadIdx.x; k < total; k += (size_t) gridDim.x * 256) good += mest_weight_rt(loss, job->r[k], sigma_inv) > thr ? 1u : 0u;
+  __shared__ unsigned s_good[4];
+  good = wave_sum_u32(good);
+  if((threadIdx.x & 63) == 0) s_good[threadIdx.x >> 6] = good;
+  __syncthreads();
+  if(threadIdx.x == 0) {
+    const unsigned t = s_good[0] + s_good[1] + s_good[2] + s_good[3];
+    if(t) atomicAdd(counts + blockIdx.y, t);
+  }
+}
+
+// ... and for entries that differ in loss or threshold (sequences with parameters of their own): both from the entry's job.  A workgroup serves
+// one entry, so the choice of the weight function is uniform over it; the weights are mest_weight<LOSS>'s, the counts those of
+// count_good_batch_kernel<C, LOSS> with the entry's threshold.  Point-major records for C > 48 and the plain layouts, tiles for C = 8.
+template <int C>
+__global__ __launch_bounds__(256) void count_good_jobs_kernel(const PairJob* __restrict__ jobs, int C_rt, unsigned int* __restrict__ counts)
+{
+  const PairJob* job = jobs + blockIdx.y;
+  const int loss = job->loss;
+  const float thr = job->good_thr;
+  const float sigma_inv = 1.0f / job->st->scale;
+  unsigned good = 0;
+  if constexpr(C == 8) {
+    const int n = job->n;
+    const float4* q = reinterpret_cast<const float4*>(job->r.get());
+    for(int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+      const float4 a = q[tile_index<2>(i, 0)], b = q[tile_index<2>(i, 1)];
+      good += (mest_weight_rt(loss, a.x, sigma_inv) > thr) + (mest_weight_rt(loss, a.y, sigma_inv) > thr) +
+              (mest_weight_rt(loss, a.z, sigma_inv) > thr) + (mest_weight_rt(loss, a.w, sigma_inv) > thr) +
+              (mest_weight_rt(loss, b.x, sigma_inv) > thr) + (mest_weight_rt(loss, b.y, sigma_inv) > thr) +
+              (mest_weight_rt(loss, b.z, sigma_inv) > thr) + (mest_weight_rt(loss, b.w, sigma_inv) > thr);
+    }
+  } else {
+    const size_t total = (size_t) job->n * C_rt;
+    for(size_t k = (size_t) blockIdx.x * 256 + threadIdx.x; k < total; k += (size_t) gridDim.x * 256) good += mest_weight_rt(loss, job->r[k], sigma_inv) > thr ? 1u : 0u;
+  }
   __shared__ unsigned s_good[4];
   good = wave_sum_u32(good);
   if((threadIdx.x & 63) == 0) s_good[threadIdx.x >> 6] = good;
@@ -806,7 +840,6 @@ static void launch_irls_c(hipStream_t s, const GNLaunch& g, int ppb)
   const int fuse = (C == 8 && g.fuse_frozen && !g.fast_warp && g.interp == BPVO_INTERP_LINEAR) ? 1 : 0;
   GNStepArgs step;
   step.on = g.step_in_reduce;
-  step.prm = g.step_prm;
   if constexpr(C == 8) {
     if(fuse) {      // one launch serves the workspaces with a moving scale and the frozen ones (per-workspace branch)
       switch(g.loss) {
@@ -834,14 +867,12 @@ void launch_compact_active(hipStream_t s, const PairJob* jobs, ActiveSet in, int
 {
   hipLaunchKernelGGL(compact_active_kernel, dim3(1), dim3(1024), 0, s, jobs, in, n_in, out_list, out_count);
 }
-void launch_gn_step(hipStream_t s, const GNLaunch& g, int mode, int max_iterations, int max_fun_evals, float p_tol,
-                    float f_tol, float g_tol)
+void launch_gn_step(hipStream_t s, const GNLaunch& g, int mode)
 {
   // (reference_reduction: ONE partial per workspace whatever its size — a tile that holds every point)
   const int ppb = g.reference_reduction ? (1 << 30) : gn_pts_per_block(g.C);
   const int fuse = (g.C == 8 && g.fuse_frozen && !g.fast_warp && g.interp == BPVO_INTERP_LINEAR && !g.reference_reduction) ? 1 : 0;
-  hipLaunchKernelGGL(gn_step_kernel, dim3(g.npairs), dim3(64), 0, s, g.jobs, ppb, mode, max_iterations, max_fun_evals, p_tol,
-                     f_tol, g_tol, g.active, fuse);
+  hipLaunchKernelGGL(gn_step_kernel, dim3(g.npairs), dim3(64), 0, s, g.jobs, ppb, mode, g.active, fuse);
 }
 void launch_prepare_linearize(hipStream_t s, const PairJob* job, const float* T, int reset_scale, int level, float given_scale)
 {
@@ -908,11 +939,21 @@ void launch_count_good_batch(hipStream_t s, const PairJob* jobs, int n_jobs, int
   }
   dispatch_channels(C, [&](auto c) { launch_count_good_batch_c<decltype(c)::value>(s, jobs, n_jobs, max_n, loss, thr, counts); });
 }
-void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int loss, int dspace, bpvo_hip_point_with_info* out)
+void launch_count_good_jobs(hipStream_t s, const PairJob* jobs, int n_jobs, int max_n, int C, unsigned int* counts)
 {
   if(n_jobs <= 0 || max_n <= 0) return;
-  CloudArgs a = {};      // (K, rows, cols: each entry's own, from its CloudJob)
-  a.dspace = dspace; a.C = C; a.loss = loss;
+  if(C == 8) {
+    hipLaunchKernelGGL((count_good_jobs_kernel<8>), dim3(std::min((max_n + 255) / 256, 64), n_jobs), dim3(256), 0, s, jobs, C, counts);
+    return;
+  }
+  const dim3 grid((unsigned) std::min<size_t>(((size_t) max_n * C + 255) / 256, 256), n_jobs);
+  hipLaunchKernelGGL((count_good_jobs_kernel<0>), grid, dim3(256), 0, s, jobs, C, counts);
+}
+void launch_point_cloud_batch(hipStream_t s, const CloudJob* jobs, int n_jobs, int max_n, int C, int dspace, bpvo_hip_point_with_info* out)
+{
+  if(n_jobs <= 0 || max_n <= 0) return;
+  CloudArgs a = {};      // (K, rows, cols, loss: each entry's own, from its CloudJob)
+  a.dspace = dspace; a.C = C;
   hipLaunchKernelGGL(point_cloud_batch_kernel, dim3((max_n + 255) / 256, n_jobs), dim3(256), 0, s, jobs, a, out);
 }
 void launch_pack_records(hipStream_t s, const PairJob* jobs, int n, int L, float* records, const GNState* d_states, GNState* h_states, const unsigned* d_ctl,

@@ -273,7 +273,7 @@ __device__ __forceinline__ void pk_irls_phase(const PairJob* __restrict__ jobs, 
 }
 
 // gn_step: wave w sums the partials of workspace w, its lane 0 runs the serial step on this workgroup's copy of the state
-__device__ __attribute__((noinline)) void pk_step_phase(const PairJob* __restrict__ jobs, int nws, int pts_per_block, GNParams prm, int fuse, bool stats_wg,
+__device__ __attribute__((noinline)) void pk_step_phase(const PairJob* __restrict__ jobs, int nws, int pts_per_block, int fuse, bool stats_wg,
                                                         unsigned parity)
 {
   const int ws = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -287,8 +287,7 @@ __device__ __attribute__((noinline)) void pk_step_phase(const PairJob* __restric
   if(threadIdx.x == 0) GN_SUBTICK(4);
 #endif
   if(mine && lane == 0)
-    gn_serial_step(jobs[ws], pk_st(ws), pk_nrm[ws], pk_sum[ws], &pk_scratch[ws], 0, prm.max_iterations, prm.max_fun_evals, prm.p_tol, prm.f_tol,
-                   prm.g_tol, fuse, stats_wg);
+    gn_serial_step(jobs[ws], pk_st(ws), pk_nrm[ws], pk_sum[ws], &pk_scratch[ws], 0, fuse, stats_wg);
   __syncthreads();
 }
 
@@ -324,7 +323,7 @@ __device__ __attribute__((noinline)) bool pk_grid_barrier(unsigned* ctl, unsigne
 }
 
 template <int C, int LOSS>
-__global__ __launch_bounds__(PK_THREADS) void gn_persistent_kernel(const PairJob* __restrict__ jobs, int nws, int pts_per_block, GNParams prm,
+__global__ __launch_bounds__(PK_THREADS) void gn_persistent_kernel(const PairJob* __restrict__ jobs, int nws, int pts_per_block,
                                                                    int fuse_frozen, unsigned* ctl, long long timeout, int begin_level, int begin_moot,
                                                                    const PairJob* __restrict__ next_jobs)
 {
@@ -406,7 +405,7 @@ __global__ __launch_bounds__(PK_THREADS) void gn_persistent_kernel(const PairJob
     ok = pk_grid_barrier(ctl, ++epoch, timeout, true);
     PK_TICK(4);
     if(!ok) break;
-    pk_step_phase(jobs, nws, pts_per_block, prm, fuse ? 1 : 0, stats_wg, epoch_it);
+    pk_step_phase(jobs, nws, pts_per_block, fuse ? 1 : 0, stats_wg, epoch_it);
     PK_TICK(5);
     ++epoch_it;
   }
@@ -475,7 +474,7 @@ __shared__ int pk_size_seen;      // the team's size word — size | (iteration 
 // What the team kernel needs now and then (barrier budget, solver tolerances, the shape of the launch) lives in LDS, not in scalar registers
 // held across the reduction phase: that phase is inlined and takes every register there is — with the join logic's operands alive across
 // it the kernel spilled 55 vector registers (324 B of scratch per lane) and lost 2 % (profiles/r05_team_join.txt).
-struct TeamCfg { long long timeout; unsigned* abort_word; GNParams prm; int n_pairs, n_teams, team_size, level_lo, scale_is_moot, local_ok, join_mode; unsigned xcc_bit; };
+struct TeamCfg { long long timeout; unsigned* abort_word; int n_pairs, n_teams, team_size, level_lo, scale_is_moot, local_ok, join_mode; unsigned xcc_bit; };
 __shared__ TeamCfg pk_cfg;
 __device__ __attribute__((noinline)) bool pk_team_barrier(unsigned* team_ctl, unsigned target, int mode = 0)
 {
@@ -574,7 +573,7 @@ __device__ __attribute__((noinline)) bool pk_team_barrier_fixed(unsigned* team_c
 template <int C, int LOSS>
 __global__ __launch_bounds__(PK_THREADS) void gn_team_fixed_kernel(const PairJob* __restrict__ jobs_all /*[levels][job_pitch]*/, int job_pitch, int n_pairs,
                                                              int team_size, int n_teams, int level_hi, int level_lo, int pts_per_block,
-                                                             GNParams prm, int fuse_frozen, int scale_is_moot, unsigned* ctl, long long timeout, int local_ok)
+                                                             int fuse_frozen, int scale_is_moot, unsigned* ctl, long long timeout, int local_ok)
 {
   constexpr bool kCanFuse = (C == 8);
   const int tid = threadIdx.x;
@@ -667,7 +666,7 @@ __global__ __launch_bounds__(PK_THREADS) void gn_team_fixed_kernel(const PairJob
         TEAM_TICK(3);
         if(!pk_team_barrier_fixed(team_ctl, global_ctl + 1, ++epoch, timeout, 1)) return;      // (only the partials cross: light)
         TEAM_TICK(4);
-        pk_step_phase(jobs, 1, pts_per_block, prm, fuse ? 1 : 0, stats_wg, epoch_it);
+        pk_step_phase(jobs, 1, pts_per_block, fuse ? 1 : 0, stats_wg, epoch_it);
         TEAM_TICK(5);
         ++epoch_it;
       }
@@ -950,7 +949,7 @@ __device__ __forceinline__ bool team_run_pair_body(const TeamPairArgs a)
       if(admission_turn && stats_wg && tid == 0) pk_publish_admission(team_ctl, pair, level, epoch_it, arrivals);
       if(!TEAM_BARRIER(1)) return false;      // (only the partials cross: light)
       TEAM_TICK(4);
-      pk_step_phase(jobs, 1, pts_per_block, pk_cfg.prm, fuse ? 1 : 0, stats_wg, epoch_it);
+      pk_step_phase(jobs, 1, pts_per_block, fuse ? 1 : 0, stats_wg, epoch_it);
       TEAM_TICK(5);
       ++epoch_it;
       if(admission_turn) {
@@ -984,7 +983,7 @@ __device__ __attribute__((noinline)) bool team_run_pair(const TeamPairArgs a) { 
 template <int C, int LOSS, bool JOIN>
 __global__ __launch_bounds__(PK_THREADS) void gn_team_kernel(const PairJob* __restrict__ jobs_all /*[levels][job_pitch]*/, int job_pitch, int n_pairs,
                                                              int team_size, int n_teams, int level_hi, int level_lo, int pts_per_block,
-                                                             GNParams prm, int fuse_frozen, int scale_is_moot, unsigned* ctl, long long timeout, int local_ok,
+                                                             int fuse_frozen, int scale_is_moot, unsigned* ctl, long long timeout, int local_ok,
                                                              int join_mode)
 {
   constexpr bool kCanFuse = (C == 8);
@@ -1011,7 +1010,7 @@ __global__ __launch_bounds__(PK_THREADS) void gn_team_kernel(const PairJob* __re
   if(__hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
   if(tid == 0) {
     pk_member = member; pk_nwg = team_size; pk_arrivals = 0u;
-    pk_cfg.timeout = timeout; pk_cfg.abort_word = ctl + 1; pk_cfg.prm = prm; pk_cfg.n_pairs = n_pairs; pk_cfg.n_teams = n_teams; pk_cfg.team_size = team_size;
+    pk_cfg.timeout = timeout; pk_cfg.abort_word = ctl + 1; pk_cfg.n_pairs = n_pairs; pk_cfg.n_teams = n_teams; pk_cfg.team_size = team_size;
     pk_cfg.level_lo = level_lo; pk_cfg.scale_is_moot = scale_is_moot; pk_cfg.local_ok = local_ok; pk_cfg.join_mode = join_mode;
     pk_cfg.xcc_bit = 1u << (__builtin_amdgcn_s_getreg(63508) & 0xf);
   }
@@ -1090,7 +1089,7 @@ int gn_persistent_grid(const GNLaunch& g, int max_grid)
   return std::max(1, std::min(max_grid, (chunks + PK_VB - 1) / PK_VB));
 }
 template <int C>
-static hipError_t launch_gn_persistent_c(hipStream_t s, const GNLaunch& g, const GNParams& prm, unsigned* ctl, int grid, long long timeout)
+static hipError_t launch_gn_persistent_c(hipStream_t s, const GNLaunch& g, unsigned* ctl, int grid, long long timeout)
 {
   const int ppb = gn_pts_per_block(C);
   const int fuse = (C == 8 && g.fuse_frozen) ? 1 : 0;
@@ -1109,7 +1108,7 @@ static hipError_t launch_gn_persistent_c(hipStream_t s, const GNLaunch& g, const
       if(status[dev] == hipSuccess && per_cu < 1) status[dev] = hipErrorLaunchOutOfResources;
     });
     if(status[dev] != hipSuccess) return status[dev];
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(PK_THREADS), kMedianLds, s, g.jobs, g.npairs, ppb, prm, fuse, ctl, timeout, g.begin_level, g.begin_moot, g.next_jobs);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(PK_THREADS), kMedianLds, s, g.jobs, g.npairs, ppb, fuse, ctl, timeout, g.begin_level, g.begin_moot, g.next_jobs);
     return hipGetLastError();
   };
   switch(g.loss) {
@@ -1118,14 +1117,11 @@ static hipError_t launch_gn_persistent_c(hipStream_t s, const GNLaunch& g, const
     default: return go(gn_persistent_kernel<C, BPVO_LOSS_L2>);
   }
 }
-hipError_t launch_gn_persistent(hipStream_t s, const GNLaunch& g, int max_iterations, int max_fun_evals, float p_tol, float f_tol, float g_tol,
-                                unsigned* ctl, int grid, long long timeout_ticks)
+hipError_t launch_gn_persistent(hipStream_t s, const GNLaunch& g, unsigned* ctl, int grid, long long timeout_ticks)
 {
   if(g.max_points <= 0) return hipSuccess;
-  GNParams prm;
-  prm.max_iterations = max_iterations; prm.max_fun_evals = max_fun_evals; prm.p_tol = p_tol; prm.f_tol = f_tol; prm.g_tol = g_tol;
-  if(g.C == 8) return launch_gn_persistent_c<8>(s, g, prm, ctl, grid, timeout_ticks);
-  return launch_gn_persistent_c<1>(s, g, prm, ctl, grid, timeout_ticks);
+  if(g.C == 8) return launch_gn_persistent_c<8>(s, g, ctl, grid, timeout_ticks);
+  return launch_gn_persistent_c<1>(s, g, ctl, grid, timeout_ticks);
 }
 // ---- team-persistent kernel for small batches
 int gn_team_ctl_words(int n_teams) { return (1 + n_teams) * kTeamCtlWords; }
@@ -1143,7 +1139,7 @@ void launch_team_ctl_reset_keep_abort(hipStream_t s, unsigned* ctl, int n_teams)
 }
 int gn_team_max_size() { return kTeamMaxSize; }
 template <int C>
-static hipError_t launch_gn_team_c(hipStream_t s, const GNTeamLaunch& t, const GNParams& prm)
+static hipError_t launch_gn_team_c(hipStream_t s, const GNTeamLaunch& t)
 {
   const int ppb = gn_pts_per_block(C);
   const int fuse = (C == 8 && t.fuse_frozen) ? 1 : 0;
@@ -1163,7 +1159,7 @@ static hipError_t launch_gn_team_c(hipStream_t s, const GNTeamLaunch& t, const G
     });
     if(status[dev] != hipSuccess) return status[dev];
     hipLaunchKernelGGL(kern, dim3(t.team_size * t.n_teams + t.spare_workgroups), dim3(PK_THREADS), lds, s, t.jobs_all, t.job_pitch, t.n_pairs, t.team_size, t.n_teams, t.level_hi,
-                       t.level_lo, ppb, prm, fuse, t.scale_is_moot, t.ctl, t.timeout_ticks, t.local_barriers, t.join_mode);
+                       t.level_lo, ppb, fuse, t.scale_is_moot, t.ctl, t.timeout_ticks, t.local_barriers, t.join_mode);
     return hipGetLastError();
   };
   if(t.join_mode) {
@@ -1187,7 +1183,7 @@ static hipError_t launch_gn_team_c(hipStream_t s, const GNTeamLaunch& t, const G
     });
     if(status[dev] != hipSuccess) return status[dev];
     hipLaunchKernelGGL(kern, dim3(t.team_size * t.n_teams), dim3(PK_THREADS), lds, s, t.jobs_all, t.job_pitch, t.n_pairs, t.team_size, t.n_teams, t.level_hi,
-                       t.level_lo, ppb, prm, fuse, t.scale_is_moot, t.ctl, t.timeout_ticks, t.local_barriers);
+                       t.level_lo, ppb, fuse, t.scale_is_moot, t.ctl, t.timeout_ticks, t.local_barriers);
     return hipGetLastError();
   };
   switch(t.loss) {
@@ -1196,11 +1192,9 @@ static hipError_t launch_gn_team_c(hipStream_t s, const GNTeamLaunch& t, const G
     default: return go_fixed(gn_team_fixed_kernel<C, BPVO_LOSS_L2>);
   }
 }
-hipError_t launch_gn_team(hipStream_t s, const GNTeamLaunch& t, int max_iterations, int max_fun_evals, float p_tol, float f_tol, float g_tol)
+hipError_t launch_gn_team(hipStream_t s, const GNTeamLaunch& t)
 {
-  GNParams prm;
-  prm.max_iterations = max_iterations; prm.max_fun_evals = max_fun_evals; prm.p_tol = p_tol; prm.f_tol = f_tol; prm.g_tol = g_tol;
-  if(t.C == 8) return launch_gn_team_c<8>(s, t, prm);
-  return launch_gn_team_c<1>(s, t, prm);
+  if(t.C == 8) return launch_gn_team_c<8>(s, t);
+  return launch_gn_team_c<1>(s, t);
 }
 }  // namespace bpvo_hip

@@ -86,6 +86,9 @@ __host__ __device__ inline void dspace_jac_row(float x, float y, float d, float 
 // phases of the device-side PoseEstimatorBase::run state machine (gn_step kernel)
 enum { PHASE_FIRST = 0, PHASE_LOOP = 1, PHASE_DONE = 2 };
 
+// PoseEstimatorParameters as the device-side state machine reads them (gn_step.h)
+struct GNParams { int max_iterations, max_fun_evals; float p_tol, f_tol, g_tol; };
+
 // PoseEstimatorBase + PoseEstimatorData_ + AutoScaleEstimator state of ONE estimation workspace
 // (reference: bpvo/pose_estimator_base.h:67-151,190-206; bpvo/mestimator.h:62-88), device resident.
 struct GNState {
@@ -111,10 +114,10 @@ struct GNState {
   float T_lin[16];
   int   r_stale;
   int   trace_n;                             // records written to PairJob::trace since set_pose (bpvo_hip_estimate_pose_trace)
+  // the limits and tolerances of the estimate under way: PairJob::prm of the workspace's jobs, copied here by set_pose when the estimate starts.
+  // The step reads them from ITS copy of the state — LDS in every Gauss-Newton kernel — so they cost the serial path no access to the job table
+  GNParams prm;
 };
-
-// PoseEstimatorParameters as the device-side state machine reads them (gn_step.h)
-struct GNParams { int max_iterations, max_fun_evals; float p_tol, f_tol, g_tol; };
 
 // Streaming (non-temporal) 16-byte accesses for data that is read or written exactly once per launch and is far larger
 // than the caches: keeps such streams from evicting each other in L2 (measured +15 % on the access pattern of
@@ -204,6 +207,12 @@ struct PairJob {
   int           pitch;
   int           n_groups;
   int           med_tot;   // entry of med_blk (uint4 units) that holds the four totals of the dense bracket form (bracket_chunk<C, true>): behind every chunk's counters
+  // The algorithm parameters of the workspace's sequence (bpvo_hip_seq_set_params; the context's everywhere else): the limits and tolerances the
+  // device-side state machine enforces (no launch carries them: set_pose copies them into the workspace's state, GNState::prm), the loss, and the
+  // weight above which a residual counts as good (the key-frame decision's fraction of good points, count_good_jobs_kernel)
+  GNParams      prm;
+  int           loss;      // BPVO_LOSS_*: every workspace of one Gauss-Newton launch has the launch's loss (estimate.hip partitions a call by loss)
+  float         good_thr;  // goodPointThreshold
 };
 
 // selection / template-build job for one (frame, level)
@@ -232,6 +241,9 @@ struct FrameJob {
   float          K[9];
   float          b;
   int            dspace;    // 1: DisparitySpaceWarp points / raw gradients (see PairJob)
+  // the selection thresholds of the frame's sequence (bpvo_hip_seq_set_params; the context's everywhere else): minSaliency and the disparity gate
+  // [minValidDisparity, maxValidDisparity] — read from here by the selection kernels, so that one launch serves frames of several parameter sets
+  float          min_saliency, min_disp, max_disp;
   int            lazy;      // 1 (C = 8 bit-planes, template frames of a pair batch at the NMS levels): the level's 32-byte records are NOT
                             // stored — `cen` holds the census bytes and `ch0` channel 0 (all the selection needs); template_build
                             // forms the records of its stencils from the census bytes (kernels_frame.hip)

@@ -502,9 +502,20 @@ static void seq_reset_state(bpvo_hip_ctx* c, int s)
   Workspace& w = c->ws[s];
   w.last_ref = w.last_cur = w.last_level = -1;
 }
+// the sequences' host state (no device storage: bpvo_hip_seq_set_params may come before the first frame); every sequence starts with the context's parameters
+static void seq_states(bpvo_hip_ctx* c)
+{
+  if(!c->seqs.empty()) return;
+  const int S = seq_capacity(c);
+  c->seqs.resize((size_t) S);
+  for(int s = 0; s < S; ++s) {
+    c->seqs[s].params = c->params;
+    seq_reset_state(c, s);
+  }
+}
 static int seq_storage(bpvo_hip_ctx* c)
 {
-  if(!c->seqs.empty()) return BPVO_OK;
+  if(c->h_seq_off) return BPVO_OK;      // (the last of the allocations below)
   const size_t S = (size_t) seq_capacity(c), cap = (size_t) c->geom[c->params.maxTestLevel].cap;
   if(!c->d_seq_cloud) HIP_CK(c, hipMalloc((void**) &c->d_seq_cloud, S * cap * sizeof(bpvo_hip_point_with_info)));
   if(!c->d_seq_jobs) HIP_CK(c, hipMalloc((void**) &c->d_seq_jobs, S * sizeof(PairJob)));
@@ -515,8 +526,6 @@ static int seq_storage(bpvo_hip_ctx* c)
   if(!c->h_seq_cnt) HIP_CK(c, hipHostMalloc((void**) &c->h_seq_cnt, S * sizeof(unsigned)));
   if(!c->d_seq_off) HIP_CK(c, hipMalloc((void**) &c->d_seq_off, S * sizeof(size_t)));
   if(!c->h_seq_off) HIP_CK(c, hipHostMalloc((void**) &c->h_seq_off, S * sizeof(size_t)));
-  c->seqs.resize(S);
-  for(int s = 0; s < (int) S; ++s) seq_reset_state(c, s);
   return BPVO_OK;
 }
 static int seq_fail(bpvo_hip_ctx* c, int code, int seq, const char* what)
@@ -605,6 +614,7 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
 {
   const bpvo_hip_params& p = c->params;
   (void) hipSetDevice(c->device);
+  seq_states(c);
   int rc = seq_storage(c);
   if(rc) return rc;
   c->vo_mode = 2;
@@ -661,12 +671,18 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
   std::vector<int> wss(m), refs(m), curs(m);
   std::vector<float> T_init((size_t) m * 16), T_est((size_t) m * 16);
   std::vector<bpvo_hip_stats> stats((size_t) m * L);
+  // each estimating sequence's parameters — handed on only when one of them has its own: a call of uniform parameters runs exactly what it ran
+  // before there were any (null: the context's, from the launches' one source)
+  std::vector<const bpvo_hip_params*> prms((size_t) m);
+  bool own = false;
   for(int k = 0; k < m; ++k) {
     const SeqState& q = c->seqs[ids[est[k]]];
     wss[k] = ids[est[k]]; refs[k] = q.ref; curs[k] = q.cur;
     std::memcpy(&T_init[(size_t) k * 16], q.T_kf.m, 64);
+    prms[k] = &q.params;
+    own = own || q.own_params;
   }
-  rc = estimate_batch(c, m, wss.data(), refs.data(), curs.data(), T_init.data(), T_est.data(), stats.data());
+  rc = estimate_batch(c, m, wss.data(), refs.data(), curs.data(), T_init.data(), T_est.data(), stats.data(), own ? prms.data() : nullptr);
   if(rc) return drain(rc);
   for(int k = 0; k < m; ++k) std::memcpy(results[est[k]].optimizerStatistics, &stats[(size_t) k * L], sizeof(bpvo_hip_stats) * L);
 
@@ -674,6 +690,7 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
   int max_n = 0;
   for(int k = 0; k < m; ++k) {
     c->h_seq_jobs[k] = make_pair_job(c, wss[k], refs[k], curs[k], lvl);      // the workspace's last linearisation (estimate_batch: level maxTestLevel)
+    if(own) pair_job_set_params(c->h_seq_jobs[k], *prms[k]);
     max_n = std::max(max_n, c->h_seq_jobs[k].n);
   }
   HIP_CK(c, hipMemcpyAsync(c->d_seq_jobs, c->h_seq_jobs, sizeof(PairJob) * (size_t) m, hipMemcpyHostToDevice, c->stream));
@@ -683,7 +700,8 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
     launch_refresh_residuals(c->stream, gr);
   }
   HIP_CK(c, hipMemsetAsync(c->d_seq_cnt, 0, sizeof(unsigned) * (size_t) m, c->stream));
-  launch_count_good_batch(c->stream, c->d_seq_jobs, m, max_n, c->C, p.lossFunction, p.goodPointThreshold, c->d_seq_cnt);
+  if(own) launch_count_good_jobs(c->stream, c->d_seq_jobs, m, max_n, c->C, c->d_seq_cnt);      // (each entry's loss and threshold, from its job)
+  else launch_count_good_batch(c->stream, c->d_seq_jobs, m, max_n, c->C, p.lossFunction, p.goodPointThreshold, c->d_seq_cnt);
   HIP_CK(c, hipMemcpyAsync(c->h_seq_cnt, c->d_seq_cnt, sizeof(unsigned) * (size_t) m, hipMemcpyDeviceToHost, c->stream));
   HIP_CK(c, hipStreamSynchronize(c->stream));
   HIP_CK(c, hipGetLastError());
@@ -691,11 +709,12 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
   for(int k = 0; k < m; ++k) {
     M44 T;
     std::memcpy(T.m, &T_est[(size_t) k * 16], 64);
-    int reason = keyframe_by_motion(p, T);
+    const bpvo_hip_params& sp = *prms[k];      // the sequence's thresholds (the context's unless it was given its own)
+    int reason = keyframe_by_motion(sp, T);
     if(reason == BPVO_KF_NO_KEYFRAMING) {
       const int npts = c->h_seq_jobs[k].n;
       const float frac = c->h_seq_cnt[k] / static_cast<float>((size_t) npts * c->C);   // fraction_good (vo_pose_estimator.cc:105-106)
-      reason = (frac < p.maxFractionOfGoodPointsToKeyFrame) ? BPVO_KF_SMALL_FRAC_GOOD : BPVO_KF_NO_KEYFRAMING;
+      reason = (frac < sp.maxFractionOfGoodPointsToKeyFrame) ? BPVO_KF_SMALL_FRAC_GOOD : BPVO_KF_NO_KEYFRAMING;
     }
     results[est[k]].keyFramingReason = reason;
     results[est[k]].isKeyFrame = reason != BPVO_KF_NO_KEYFRAMING;
@@ -719,10 +738,11 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
       cj.job = c->d_seq_jobs + k; cj.img = kfr.img[0]; cj.out_offset = (size_t) wss[k] * cap;
       std::memcpy(cj.K, slot_geom(c, kfr, lvl).K, sizeof(cj.K));      // (build_point_cloud: the context's size and level intrinsics; here the sequence's)
       cj.rows = slot_geom(c, kfr, 0).rows; cj.cols = slot_geom(c, kfr, 0).cols;
+      cj.loss = prms[k]->lossFunction;
       max_c = std::max(max_c, npts);
     }
     HIP_CK(c, hipMemcpyAsync(c->d_cloud_jobs, c->h_cloud_jobs, sizeof(CloudJob) * (size_t) nk, hipMemcpyHostToDevice, c->stream));
-    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, nk, max_c, c->C, p.lossFunction, c->dspace, c->d_seq_cloud);
+    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, nk, max_c, c->C, c->dspace, c->d_seq_cloud);
     HIP_CK(c, hipGetLastError());
     slots.clear();
     for(int j = 0; j < nk; ++j) {
@@ -747,13 +767,15 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
       std::vector<int> w2(mr), r2(mr), c2(mr);
       std::vector<float> I2((size_t) mr * 16);
       std::vector<bpvo_hip_stats> st2((size_t) mr * L);
+      std::vector<const bpvo_hip_params*> p2((size_t) mr);
       T_again.resize((size_t) mr * 16);
       for(int t = 0; t < mr; ++t) {
         const SeqState& q = c->seqs[wss[kf[re[t]]]];
         w2[t] = wss[kf[re[t]]]; r2[t] = q.ref; c2[t] = q.cur;
         std::memcpy(&I2[(size_t) t * 16], I.m, 64);
+        p2[t] = &q.params;
       }
-      rc = estimate_batch(c, mr, w2.data(), r2.data(), c2.data(), I2.data(), T_again.data(), st2.data());
+      rc = estimate_batch(c, mr, w2.data(), r2.data(), c2.data(), I2.data(), T_again.data(), st2.data(), own ? p2.data() : nullptr);
       if(rc) return drain(rc);
       for(int t = 0; t < mr; ++t) std::memcpy(results[est[kf[re[t]]]].optimizerStatistics, &st2[(size_t) t * L], sizeof(bpvo_hip_stats) * L);
     }
@@ -1019,6 +1041,73 @@ int bpvo_hip_seq_get_camera(const bpvo_hip_ctx* c, int seq, bpvo_hip_camera* cam
   std::memcpy(cam->K, g.K, sizeof(cam->K));
   cam->baseline = g.b;
   cam->rows = g.rows; cam->cols = g.cols;
+  return BPVO_OK;
+}
+
+// ---- per-sequence algorithm parameters ---------------------------------------------------------------------------------------------------
+// What a sequence may own is what travels in its jobs (the Gauss-Newton limits and tolerances, the loss, the good-point threshold: PairJob; the
+// selection thresholds: FrameJob) or is decided on the host per sequence (the key-frame thresholds).  What sizes the context's storage or
+// instantiates its kernels — the pyramid, the descriptor, the gradient and interpolation forms, the non-maximum suppression, maxTestLevel — is
+// fixed at creation: a difference there is BPVO_ERR_UNSUPPORTED, named in the error string.
+static bool structural_difference(const bpvo_hip_ctx* c, int seq, const bpvo_hip_params& p, std::string* why)
+{
+  const bpvo_hip_params& q = c->params;
+  auto differs = [&](const char* name, const std::string& a, const std::string& b) {
+    *why = std::string(name) + " = " + a + " differs from the context's " + b + " (it fixes the context's storage or kernels: set at creation only)";
+    return true;
+  };
+  auto fstr = [](float v) { char buf[48]; std::snprintf(buf, sizeof(buf), "%.9g", (double) v); return std::string(buf); };
+#define SP_INT(field) if(p.field != q.field) return differs(#field, std::to_string(p.field), std::to_string(q.field))
+#define SP_FLT(field) if(std::memcmp(&p.field, &q.field, sizeof(float)) != 0) return differs(#field, fstr(p.field), fstr(q.field))
+  SP_INT(minImageDimensionForPyramid);
+  {
+    // numPyramidLevels after resolution (bpvo/vo.cc:101-105, for the sequence's own image size, as bpvo_hip_create counts them)
+    const LevelGeom& g = slot_geom(c, c->frames[3 * seq], 0);
+    const int own = p.numPyramidLevels > 0 ? p.numPyramidLevels : 1 + (int) std::round(std::log2(std::min(g.rows, g.cols) / (double) p.minImageDimensionForPyramid));
+    if(own != c->L) return differs("numPyramidLevels", std::to_string(own), std::to_string(c->L));
+  }
+  SP_INT(descriptor);
+  SP_FLT(sigmaPriorToCensusTransform); SP_FLT(sigmaBitPlanes); SP_FLT(dfSigma1); SP_FLT(dfSigma2);
+  SP_INT(latchNumBytes); SP_INT(latchRotationInvariance); SP_INT(latchHalfSsdSize);
+  SP_INT(centralDifferenceRadius); SP_FLT(centralDifferenceSigmaBefore); SP_FLT(centralDifferenceSigmaAfter);
+  SP_INT(laplacianKernelSize);
+  SP_INT(gradientEstimation); SP_INT(interp); SP_INT(withNormalization);
+  SP_INT(nonMaxSuppRadius); SP_INT(minNumPixelsForNonMaximaSuppression);
+  SP_INT(maxTestLevel);
+#undef SP_INT
+#undef SP_FLT
+  return false;
+}
+int bpvo_hip_seq_set_params(bpvo_hip_ctx* c, int seq, const bpvo_hip_params* p)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  if(!p) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr parameters");
+  if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: per-sequence parameters serve bpvo_hip_add_frames");
+  for(int k = 0; k < 3; ++k)
+    if(c->frames[3 * seq + k].has_data || c->frames[3 * seq + k].has_template)
+      return seq_fail(c, BPVO_ERR_INVALID_ARG, seq, "holds frames: its parameters change only while it is fresh or after bpvo_hip_seq_reset");
+  std::string why;
+  if(structural_difference(c, seq, *p, &why)) return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, why.c_str());
+  if(p->lossFunction != BPVO_LOSS_HUBER && p->lossFunction != BPVO_LOSS_TUKEY && p->lossFunction != BPVO_LOSS_L2)
+    return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, "unknown lossFunction");      // (bpvo_hip_create's answer)
+  seq_states(c);
+  SeqState& q = c->seqs[seq];
+  const bpvo_hip_params& o = c->params;
+  q.params = *p;
+  // does anything the library reads differ from the context's?  (No: the sequence stays on the plain path, whatever the unread fields say)
+  q.own_params = p->lossFunction != o.lossFunction || p->maxIterations != o.maxIterations || p->parameterTolerance != o.parameterTolerance ||
+                 p->functionTolerance != o.functionTolerance || p->gradientTolerance != o.gradientTolerance ||
+                 p->minTranslationMagToKeyFrame != o.minTranslationMagToKeyFrame || p->minRotationMagToKeyFrame != o.minRotationMagToKeyFrame ||
+                 p->maxFractionOfGoodPointsToKeyFrame != o.maxFractionOfGoodPointsToKeyFrame || p->goodPointThreshold != o.goodPointThreshold ||
+                 p->minSaliency != o.minSaliency || p->minValidDisparity != o.minValidDisparity || p->maxValidDisparity != o.maxValidDisparity;
+  for(int k = 0; k < 3; ++k) c->frames[3 * seq + k].seq_params = q.own_params ? &q.params : nullptr;
+  c->vo_mode = 2;      // a context with per-sequence parameters serves bpvo_hip_add_frames
+  return BPVO_OK;
+}
+int bpvo_hip_seq_get_params(const bpvo_hip_ctx* c, int seq, bpvo_hip_params* p)
+{
+  if(!c || !p || seq < 0 || seq >= seq_capacity(c)) return BPVO_ERR_INVALID_ARG;
+  *p = c->seqs.empty() ? c->params : c->seqs[seq].params;
   return BPVO_OK;
 }
 #undef CHECK_SEQ

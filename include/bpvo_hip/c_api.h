@@ -271,6 +271,24 @@ int bpvo_hip_create_sequences(bpvo_hip_ctx** out, int n_sequences, const bpvo_hi
 int bpvo_hip_seq_set_camera(bpvo_hip_ctx* ctx, int seq, const bpvo_hip_camera* cam);
 int bpvo_hip_seq_get_camera(const bpvo_hip_ctx* ctx, int seq, bpvo_hip_camera* cam);
 
+/* ---- per-sequence algorithm parameters: each sequence of bpvo_hip_add_frames with its own bpvo_hip_params (a parameter sweep over one
+ * dataset in one context).  results[i] of every bpvo_hip_add_frames / bpvo_hip_add_frames_stereo call equals, bit for bit, what
+ * bpvo_hip_add_frame(_stereo) returns for that frame on a bpvo_hip_create context of the sequence's camera AND the sequence's parameters.
+ * A sequence that was never given parameters has the context's; one whose parameters equal the context's runs exactly what it runs without.
+ * A sequence may own: lossFunction, maxIterations, parameterTolerance, functionTolerance, gradientTolerance, minTranslationMagToKeyFrame,
+ *   minRotationMagToKeyFrame, maxFractionOfGoodPointsToKeyFrame, goodPointThreshold, minSaliency, minValidDisparity, maxValidDisparity — and
+ *   the fields the library stores but never reads (relaxTolerancesForCoarseLevels, minNumPixelsToWork, verbosity), returned as set.
+ * Fixed by the context (they size its storage or instantiate its kernels) and therefore equal to its own: numPyramidLevels (after the
+ *   automatic count is resolved), minImageDimensionForPyramid, descriptor and every descriptor parameter (the sigmas, the LATCH fields,
+ *   centralDifference*, laplacianKernelSize), gradientEstimation, interp, withNormalization, nonMaxSuppRadius,
+ *   minNumPixelsForNonMaximaSuppression, maxTestLevel.  A difference: BPVO_ERR_UNSUPPORTED, with the name of the first differing field and
+ *   both values in bpvo_hip_last_error.  A value bpvo_hip_create refuses (an unknown lossFunction) is refused with bpvo_hip_create's code.
+ * bpvo_hip_seq_set_params: only while the sequence holds no frame (fresh, or after bpvo_hip_seq_reset, which keeps the parameters;
+ *   BPVO_ERR_INVALID_ARG otherwise), not on a context that runs bpvo_hip_add_frame; it commits the context to bpvo_hip_add_frames.  Every
+ *   check comes before anything changes: after an error bpvo_hip_seq_get_params returns what it returned before. */
+int bpvo_hip_seq_set_params(bpvo_hip_ctx* ctx, int seq, const bpvo_hip_params* p);
+int bpvo_hip_seq_get_params(const bpvo_hip_ctx* ctx, int seq, bpvo_hip_params* p);
+
 /* ---- batches of independent frame pairs (BASELINE.json config 5).
  * Pair p uses frame slots 2p (reference/template frame A) and 2p+1 (current frame B) and workspace p.
  * For each pair: A.setData, A.setTemplate, B.setData, estimatePose(A, B, Identity) -> poses[p].

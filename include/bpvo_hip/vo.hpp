@@ -408,6 +408,15 @@ class VisualOdometrySequences {
   /* sequence s with cameras[s] (bpvo_hip_create_sequences: the context's image size is the largest rows and cols among them) */
   VisualOdometrySequences(const std::vector<Camera>& cameras, const AlgorithmParameters& params = AlgorithmParameters(), int device = 0)
       : _dev(std::make_shared<detail::Device>(toC(cameras), params, device)), _trajectories(cameras.size()) {}
+  /* ... and with parameters[s] (a parameter sweep): the context is created with parameters[0], which fixes the pyramid, the descriptor and the
+   * other structural fields for all of them (setParameters) */
+  VisualOdometrySequences(const std::vector<Camera>& cameras, const std::vector<AlgorithmParameters>& parameters, int device = 0)
+      : _dev(std::make_shared<detail::Device>(toC(cameras), parameters.empty() ? AlgorithmParameters() : parameters[0], device)),
+        _trajectories(cameras.size())
+  {
+    if(parameters.size() != cameras.size()) throw Error("one AlgorithmParameters per camera");
+    for(size_t s = 1; s < parameters.size(); ++s) setParameters((int) s, parameters[s]);
+  }
 
   int numSequences() const { int n = 0; _dev->check(bpvo_hip_seq_capacity(_dev->ctx(), &n)); return n; }
 
@@ -422,6 +431,17 @@ class VisualOdometrySequences {
     r.baseline = c.baseline;
     r.size = ImageSize(c.rows, c.cols);
     return r;
+  }
+
+  /* the algorithm parameters of sequence s (bpvo_hip_seq_set_params), changed only while it holds no frame: loss, iteration limit, tolerances,
+   * key-framing thresholds, minSaliency and the disparity gate are the sequence's own; the structural fields (pyramid, descriptor, gradient,
+   * interpolation, non-maximum suppression, maxTestLevel) must equal the context's */
+  void setParameters(int s, const AlgorithmParameters& p) { _dev->check(bpvo_hip_seq_set_params(_dev->ctx(), s, &p)); }
+  AlgorithmParameters parameters(int s) const
+  {
+    AlgorithmParameters p;
+    _dev->check(bpvo_hip_seq_get_params(_dev->ctx(), s, &p));
+    return p;
   }
 
   /* images / disparities: n frames back to back, frame i of its sequence's size (camera(seq[i]).size; one context-wide camera: rows * cols
