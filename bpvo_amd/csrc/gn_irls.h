@@ -83,9 +83,10 @@ __device__ __forceinline__ void irls_tile(const PairJob& j, const GNState* __res
   for(int i = p_begin + vtid; i < p_end; i += GN_BLOCK) {
     float rr[C], Ix[C], Iy[C];
     float v;
+    float4 Pt;      // fused: the point as warp_point loaded it (ONE request per point)
     if constexpr(fused) {
       bool hit;
-      v = warp_point<8, false, true>(j, P, i, true, rr, hit) ? 1.0f : 0.0f;
+      v = warp_point<8, false, true>(j, P, i, true, rr, hit, &Pt) ? 1.0f : 0.0f;
       acc[29] += hit ? 1.0f : 0.0f;
     } else {
       v = (float) j.valid[i];
@@ -101,7 +102,7 @@ __device__ __forceinline__ void irls_tile(const PairJob& j, const GNState* __res
     // Per (point, channel) that is 6 multiply-adds instead of the 27 of the reference's rankUpdatePoint; the 6x6 outer
     // products are formed once per point.  Algebraically identical, rounding differs at the 1e-7 level like any other
     // summation order (H, G are tolerance-compared).
-    const float4 Pt = load_stream(j.pts + i);
+    if constexpr(!fused) Pt = load_stream(j.pts + i);
     if constexpr(C == 8) {
       const float4* qr = reinterpret_cast<const float4*>(j.r.get());
       const float4* qg = reinterpret_cast<const float4*>(j.grad.get());
