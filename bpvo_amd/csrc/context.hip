@@ -478,7 +478,7 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
   c->n_frames = n_frames; c->n_pairs = n_pairs;
   c->auto_levels = c->params.numPyramidLevels <= 0;
   if(c->params.numPyramidLevels <= 0)   // bpvo/vo.cc:101-105
-    c->params.numPyramidLevels = 1 + (int) std::round(std::log2(std::min(rows, cols) / (double) p->minImageDimensionForPyramid));
+    c->params.numPyramidLevels = auto_pyramid_levels(rows, cols, p->minImageDimensionForPyramid);
   c->L = c->params.numPyramidLevels;
   auto unsupported = [&](const char* m) { g_create_error = m; return BPVO_ERR_UNSUPPORTED; };
   if(c->L < 1 || c->L > kMaxLevels) return unsupported("numPyramidLevels out of range (1..8)");
@@ -686,8 +686,8 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
   CREATE_CK(hipHostMalloc((void**) &cp->h_ints, sizeof(int) * std::max((size_t) n_frames * kMaxLevels, (size_t) 16)));
   CREATE_CK(hipMalloc((void**) &cp->d_ints, sizeof(int) * std::max((size_t) n_frames * kMaxLevels, (size_t) 16)));
 #undef CREATE_CK
-  cp->T_kf = m44_identity();
-  cp->cloud_pose = m44_identity();
+  cp->vo.params = cp->params;
+  vo_reset(cp->vo, 0);
   g_live_ctx[device & 63].fetch_add(1);
   cp->counted_live = true;
   *out = c.release();

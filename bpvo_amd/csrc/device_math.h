@@ -3,10 +3,14 @@
 // library is built with -ffp-contract=off so that no a*b+c is fused on either side.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <math.h>
 
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
 #define BPVO_HD __host__ __device__ inline
+#else      // a plain C++ compiler (vo_state.h and its host-only test harness): the same functions, host only
+#define BPVO_HD inline
+#endif
 
 namespace bpvo_hip {
 

@@ -514,22 +514,6 @@ int upload_single_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int level)
   return BPVO_OK;
 }
 
-void trajectory_push(bpvo_hip_ctx* c, const M44& T) { trajectory_push(c->trajectory, T); }
-void trajectory_push(std::vector<M44>& trajectory, const M44& T)   // Trajectory::push_back + InvertPose (bpvo/trajectory.cc:30-50)
-{
-  M44 Ti = m44_identity();
-  for(int i = 0; i < 3; ++i)
-    for(int j = 0; j < 3; ++j) Ti.m[i * 4 + j] = T.m[j * 4 + i];
-  for(int i = 0; i < 3; ++i) {
-    float s = Ti.m[0 * 4 + i] * T.m[3];
-    s += Ti.m[1 * 4 + i] * T.m[7];
-    s += Ti.m[2 * 4 + i] * T.m[11];
-    Ti.m[i * 4 + 3] = -s;
-  }
-  if(!trajectory.empty()) trajectory.push_back(m44_mul(trajectory.back(), Ti));
-  else trajectory.push_back(Ti);
-}
-
 // Fused path of the estimate loops: the residual / valid buffers of a workspace may lag behind its last linearisation
 // (GNState::r_stale).  Everything that reads them goes through here first; the check itself happens on the device.
 int ensure_residuals(bpvo_hip_ctx* c, int ws)
@@ -550,7 +534,7 @@ int fraction_good(bpvo_hip_ctx* c, int ws, float thr, float* frac)
   if(w.last_ref < 0) return fail(c, BPVO_ERR_NO_DATA, "no linearisation has run on this workspace");
   const int n = c->frames[w.last_ref].n_host[w.last_level];
   if(c->frac_valid && c->frac_ws == ws && c->frac_thr == thr && c->frac_n == n) {      // queued behind the estimate by addFrame
-    *frac = c->frac_cnt / static_cast<float>((size_t) n * c->C);
+    *frac = vo_fraction_good(c->frac_cnt, n, c->C);
     return BPVO_OK;
   }
   int rc = ensure_residuals(c, ws);
@@ -563,7 +547,7 @@ int fraction_good(bpvo_hip_ctx* c, int ws, float thr, float* frac)
   HIP_CK(c, hipMemcpyAsync(c->h_ints, c->d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
   HIP_CK(c, hipStreamSynchronize(c->stream));
   cnt = (unsigned int) c->h_ints[0];
-  *frac = cnt / static_cast<float>((size_t) n * c->C);   // vo_pose_estimator.cc:105-106
+  *frac = vo_fraction_good(cnt, n, c->C);
   return BPVO_OK;
 }
 

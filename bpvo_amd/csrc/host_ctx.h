@@ -1,7 +1,8 @@
 // libbpvo_hip, host side: the context and what its translation units share (internal header; the interface is include/bpvo_hip/c_api.h).
 //   context.hip   create / destroy, storage, job tables, per-context options            frames.hip    setData / setTemplate stages + accessors
 //   estimate.hip  estimatePose: the Gauss-Newton drivers (chain, persistent, team)       batch.hip     pair batches, the upload pipeline
-//   vo.hip        VisualOdometry::addFrame, point cloud, trajectory, stereo front-end    measure.hip   profiling, counters, diagnostics
+//   vo.hip        the addFrame drivers (one frame, many sequences), point cloud,          measure.hip   profiling, counters, diagnostics
+//                 stereo front-end                                                       vo_state.h    addFrame's state machine (host only, no HIP)
 // The host keeps bpvo's object model (frames with a descriptor pyramid and a template pyramid, a pose estimator with per-level
 // Gauss-Newton runs, the VisualOdometry keyframe state machine) but every O(pixels) / O(points) array lives in HBM; per GN iteration the
 // host sees one 4-byte "pairs still active" counter.  See DESIGN.md.
@@ -25,6 +26,7 @@
 
 #include "kernels.h"
 #include "latch_table.h"
+#include "vo_state.h"
 
 using namespace bpvo_hip;
 #include "latch_table.h"
@@ -81,19 +83,6 @@ struct FrameSlot {
   // the algorithm parameters of the slot's sequence when they are not the context's own (bpvo_hip_seq_set_params: SeqState::params), else null;
   // the frame stages take the selection thresholds from them (make_frame_job)
   const bpvo_hip_params* seq_params = nullptr;
-};
-
-// One sequence of bpvo_hip_add_frames (vo.hip): the VisualOdometry state of bpvo/vo.cc:45-52 for frame slots 3s .. 3s+2 and workspace s
-struct SeqState {
-  int ref = 0, cur = 1, prev = 2;   // slot roles (the single path's vo_ref / vo_cur / vo_prev)
-  M44 T_kf;
-  std::vector<M44> trajectory;
-  size_t cloud_n = 0;               // the point cloud of the sequence's last Result: records [s * cap, s * cap + cloud_n) of bpvo_hip_ctx::d_seq_cloud
-  M44 cloud_pose;
-  // the sequence's algorithm parameters (bpvo_hip_seq_set_params; the context's until then) — they outlive bpvo_hip_seq_reset, like its camera.
-  // own_params: they differ from the context's in a field the library reads (only then do the sequence's jobs and decisions take them from here)
-  bpvo_hip_params params;
-  bool own_params = false;
 };
 
 struct Workspace {
@@ -192,14 +181,9 @@ struct bpvo_hip_ctx {
   int* h_ints = nullptr;           // [max(n_frames*kMaxLevels, 16)] pinned
   int* d_ints = nullptr;           // same size, device
   int cap_max = 0;
-  // VisualOdometry state (bpvo/vo.cc:45-52)
-  int vo_ref = 0, vo_cur = 1, vo_prev = 2;
-  M44 T_kf;
-  std::vector<M44> trajectory;
+  SeqState vo;                     // bpvo_hip_add_frame's VisualOdometry state (vo_state.h) on frame slots 0 .. 2 and workspace 0
   bpvo_hip_point_with_info* d_cloud = nullptr;   // the last key frame's point cloud: built on the device (vo.hip build_point_cloud), copied out when asked for
   size_t d_cloud_cap = 0;
-  size_t cloud_n = 0;
-  M44 cloud_pose;
   // many independent VisualOdometry sequences (bpvo_hip_add_frames, vo.hip): vo_mode 0 = not yet decided, 1 = bpvo_hip_add_frame, 2 = bpvo_hip_add_frames
   int vo_mode = 0;
   std::vector<SeqState> seqs;                      // [seq_capacity], created by the first bpvo_hip_add_frames
@@ -373,6 +357,11 @@ namespace bpvo_hip_host {
   } while(0)
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+// the automatic pyramid level count of an image size (numPyramidLevels <= 0; bpvo/vo.cc:101-105)
+inline int auto_pyramid_levels(int rows, int cols, int minImageDimensionForPyramid)
+{
+  return 1 + (int) std::round(std::log2(std::min(rows, cols) / (double) minImageDimensionForPyramid));
+}
 
 struct Carver {
   unsigned char* base;
@@ -532,8 +521,6 @@ void detile_to_channel_major(const float* src, int n, int C, int E, int V, float
 size_t tiled_floats(int n, int floats_per_point);
 int refresh_counters(bpvo_hip_ctx* c);
 int upload_single_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int level);
-void trajectory_push(bpvo_hip_ctx* c, const M44& T);
-void trajectory_push(std::vector<M44>& trajectory, const M44& T);
 int ensure_residuals(bpvo_hip_ctx* c, int ws);
 int fraction_good(bpvo_hip_ctx* c, int ws, float thr, float* frac);
 int get_weights_host(bpvo_hip_ctx* c, int ws, std::vector<float>& w_cm, int* n_out);

@@ -528,22 +528,6 @@ __global__ __launch_bounds__(256) void weights_wide_kernel(const PairJob* job, i
   if(k >= (size_t) job->n * C) return;
   w_out[k] = mest_weight_rt(loss, job->r[k], 1.0f / job->st->scale);
 }
-__global__ __launch_bounds__(256) void count_good_wide_kernel(const PairJob* job, int C, int loss, float thr, unsigned int* count)
-{
-  const size_t total = (size_t) job->n * C;
-  const float sigma_inv = 1.0f / job->st->scale;
-  unsigned good = 0;
-  for(size_t k = (size_t) blockIdx.x * 256 + threadIdx.x; k < total; k += (size_t) gridDim.x * 256) good += mest_weight_rt(loss, job->r[k], sigma_inv) > thr ? 1u : 0u;
-  __shared__ unsigned s_good[4];
-  good = wave_sum_u32(good);
-  if((threadIdx.x & 63) == 0) s_good[threadIdx.x >> 6] = good;
-  __syncthreads();
-  if(threadIdx.x == 0) {
-    const unsigned t = s_good[0] + s_good[1] + s_good[2] + s_good[3];
-    if(t) atomicAdd(count, t);
-  }
-}
-
 // getPointCloudFromRefFrame + GetColor (reference: bpvo/vo.cc:250-281) on the device: one 32-byte PointWithInfo per template point of the level the
 // estimate ended on — the point, the key frame's grey value at its projection (getImagePoint, bpvo/rigid_body_warp.h:123-128: x = K X in f32, index
 // order; DisparitySpaceWarp: disparity_space_warp.h:73-76), and weights[i] of the last linearisation, i.e. the weight of CHANNEL 0's residual
@@ -595,27 +579,44 @@ __global__ __launch_bounds__(256) void point_cloud_batch_kernel(const CloudJob* 
   out[cj.out_offset + i] = cloud_record(j, i, cj.img, a);
 }
 
-// (grid-stride over the points and ONE add per workgroup: a thousand workgroups of four waves adding to one word took 55 us on a
-// 300 k-point template — the adds serialise at the L2 — where the points take 5)
+// ---- the fraction of good points (the key-frame decision; VisualOdometryPoseEstimator::getFractionOfGoodPoints, vo_pose_estimator.cc:101-107) ----
+// The residuals of one job whose weight exceeds thr, this thread's share of a grid-stride walk (gridDim.x workgroups per job).
+//   C = 8: the tiles;  another compile-time C: point-major records, a point per step;  C = 0: point-major records of C_rt floats, a residual per
+//   step (descriptors of more than 48 channels, and the run-time-loss form of every plain layout)
+//   LOSS >= 0: mest_weight<LOSS>;  LOSS < 0: the run-time `loss` (the same weights)
 template <int C, int LOSS>
-__global__ __launch_bounds__(256) void count_good_kernel(const PairJob* job, float thr, unsigned int* count)
+__device__ __forceinline__ unsigned count_good_of_job(const PairJob* job, int C_rt, int loss, float thr)
 {
-  unsigned good = 0;
-  const int n = job->n;
+  auto weight = [&](float r, float sigma_inv) {
+    if constexpr(LOSS < 0) return mest_weight_rt(loss, r, sigma_inv);
+    else return mest_weight<LOSS>(r, sigma_inv);
+  };
   const float sigma_inv = 1.0f / job->st->scale;
-  for(int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    if constexpr(C == 8) {
-      const float4* q = reinterpret_cast<const float4*>(job->r.get());
-      const float4 a = q[tile_index<2>(i, 0)], b = q[tile_index<2>(i, 1)];
-      good += (mest_weight<LOSS>(a.x, sigma_inv) > thr) + (mest_weight<LOSS>(a.y, sigma_inv) > thr) +
-              (mest_weight<LOSS>(a.z, sigma_inv) > thr) + (mest_weight<LOSS>(a.w, sigma_inv) > thr) +
-              (mest_weight<LOSS>(b.x, sigma_inv) > thr) + (mest_weight<LOSS>(b.y, sigma_inv) > thr) +
-              (mest_weight<LOSS>(b.z, sigma_inv) > thr) + (mest_weight<LOSS>(b.w, sigma_inv) > thr);
-    } else {
+  unsigned good = 0;
+  if constexpr(C == 0) {
+    const size_t total = (size_t) job->n * C_rt;
+    for(size_t k = (size_t) blockIdx.x * 256 + threadIdx.x; k < total; k += (size_t) gridDim.x * 256) good += weight(job->r[k], sigma_inv) > thr ? 1u : 0u;
+  } else {
+    const int n = job->n;
+    for(int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+      if constexpr(C == 8) {
+        const float4* q = reinterpret_cast<const float4*>(job->r.get());
+        const float4 a = q[tile_index<2>(i, 0)], b = q[tile_index<2>(i, 1)];
+        good += (weight(a.x, sigma_inv) > thr) + (weight(a.y, sigma_inv) > thr) + (weight(a.z, sigma_inv) > thr) + (weight(a.w, sigma_inv) > thr) +
+                (weight(b.x, sigma_inv) > thr) + (weight(b.y, sigma_inv) > thr) + (weight(b.z, sigma_inv) > thr) + (weight(b.w, sigma_inv) > thr);
+      } else {
 #pragma unroll
-      for(int c = 0; c < C; ++c) good += mest_weight<LOSS>(job->r[(size_t) i * C + c], sigma_inv) > thr;
+        for(int c = 0; c < C; ++c) good += weight(job->r[(size_t) i * C + c], sigma_inv) > thr;
+      }
     }
   }
+  return good;
+}
+// ... and the workgroup's sum into the job's counter (zeroed before the launch): ONE add per workgroup — a thousand workgroups of four waves
+// adding to one word took 55 us on a 300 k-point template, the adds serialise at the L2, where the points take 5.  Integer counts: the result
+// does not depend on the order of the adds.
+__device__ __forceinline__ void count_good_commit(unsigned good, unsigned int* count)
+{
   __shared__ unsigned s_good[4];
   good = wave_sum_u32(good);
   if((threadIdx.x & 63) == 0) s_good[threadIdx.x >> 6] = good;
@@ -625,89 +626,25 @@ __global__ __launch_bounds__(256) void count_good_kernel(const PairJob* job, flo
     if(t) atomicAdd(count, t);
   }
 }
-
-// count_good_kernel for a table of jobs: blockIdx.y = entry of the table, counts[blockIdx.y] its counter (zeroed before the launch); still one
-// atomic add per workgroup.  Integer counts: the result does not depend on the order of the adds.
+// The entries: blockIdx.y = entry of a table of jobs, counts[blockIdx.y] its counter (one job and its counter: a table of one).  With the
+// launch's loss and threshold:
 template <int C, int LOSS>
-__global__ __launch_bounds__(256) void count_good_batch_kernel(const PairJob* __restrict__ jobs, float thr, unsigned int* __restrict__ counts)
+__global__ __launch_bounds__(256) void count_good_kernel(const PairJob* __restrict__ jobs, float thr, unsigned int* __restrict__ counts)
 {
-  const PairJob* job = jobs + blockIdx.y;
-  unsigned good = 0;
-  const int n = job->n;
-  const float sigma_inv = 1.0f / job->st->scale;
-  for(int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    if constexpr(C == 8) {
-      const float4* q = reinterpret_cast<const float4*>(job->r.get());
-      const float4 a = q[tile_index<2>(i, 0)], b = q[tile_index<2>(i, 1)];
-      good += (mest_weight<LOSS>(a.x, sigma_inv) > thr) + (mest_weight<LOSS>(a.y, sigma_inv) > thr) +
-              (mest_weight<LOSS>(a.z, sigma_inv) > thr) + (mest_weight<LOSS>(a.w, sigma_inv) > thr) +
-              (mest_weight<LOSS>(b.x, sigma_inv) > thr) + (mest_weight<LOSS>(b.y, sigma_inv) > thr) +
-              (mest_weight<LOSS>(b.z, sigma_inv) > thr) + (mest_weight<LOSS>(b.w, sigma_inv) > thr);
-    } else {
-#pragma unroll
-      for(int c = 0; c < C; ++c) good += mest_weight<LOSS>(job->r[(size_t) i * C + c], sigma_inv) > thr;
-    }
-  }
-  __shared__ unsigned s_good[4];
-  good = wave_sum_u32(good);
-  if((threadIdx.x & 63) == 0) s_good[threadIdx.x >> 6] = good;
-  __syncthreads();
-  if(threadIdx.x == 0) {
-    const unsigned t = s_good[0] + s_good[1] + s_good[2] + s_good[3];
-    if(t) atomicAdd(counts + blockIdx.y, t);
-  }
+  count_good_commit(count_good_of_job<C, LOSS>(jobs + blockIdx.y, C, LOSS, thr), counts + blockIdx.y);
 }
-// ... and for descriptors of more than 48 channels (count_good_wide_kernel per entry)
-__global__ __launch_bounds__(256) void count_good_batch_wide_kernel(const PairJob* __restrict__ jobs, int C, int loss, float thr, unsigned int* __restrict__ counts)
+// ... the same for descriptors of more than 48 channels ...
+__global__ __launch_bounds__(256) void count_good_wide_kernel(const PairJob* __restrict__ jobs, int C, int loss, float thr, unsigned int* __restrict__ counts)
 {
-  const PairJob* job = jobs + blockIdx.y;
-  const size_t total = (size_t) job->n * C;
-  const float sigma_inv = 1.0f / job->st->scale;
-  unsigned good = 0;
-  for(size_t k = (size_t) blockIdx.x * 256 + threadIdx.x; k < total; k += (size_t) gridDim.x * 256) good += mest_weight_rt(loss, job->r[k], sigma_inv) > thr ? 1u : 0u;
-  __shared__ unsigned s_good[4];
-  good = wave_sum_u32(good);
-  if((threadIdx.x & 63) == 0) s_good[threadIdx.x >> 6] = good;
-  __syncthreads();
-  if(threadIdx.x == 0) {
-    const unsigned t = s_good[0] + s_good[1] + s_good[2] + s_good[3];
-    if(t) atomicAdd(counts + blockIdx.y, t);
-  }
+  count_good_commit(count_good_of_job<0, -1>(jobs + blockIdx.y, C, loss, thr), counts + blockIdx.y);
 }
-
-// ... and for entries that differ in loss or threshold (sequences with parameters of their own): both from the entry's job.  A workgroup serves
-// one entry, so the choice of the weight function is uniform over it; the weights are mest_weight<LOSS>'s, the counts those of
-// count_good_batch_kernel<C, LOSS> with the entry's threshold.  Point-major records for C > 48 and the plain layouts, tiles for C = 8.
+// ... and each entry's own, from its job (sequences with parameters of their own).  A workgroup serves one entry, so the choice of the weight
+// function is uniform over it.  C = 8: the tiles; C = 0: every other layout.
 template <int C>
 __global__ __launch_bounds__(256) void count_good_jobs_kernel(const PairJob* __restrict__ jobs, int C_rt, unsigned int* __restrict__ counts)
 {
   const PairJob* job = jobs + blockIdx.y;
-  const int loss = job->loss;
-  const float thr = job->good_thr;
-  const float sigma_inv = 1.0f / job->st->scale;
-  unsigned good = 0;
-  if constexpr(C == 8) {
-    const int n = job->n;
-    const float4* q = reinterpret_cast<const float4*>(job->r.get());
-    for(int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-      const float4 a = q[tile_index<2>(i, 0)], b = q[tile_index<2>(i, 1)];
-      good += (mest_weight_rt(loss, a.x, sigma_inv) > thr) + (mest_weight_rt(loss, a.y, sigma_inv) > thr) +
-              (mest_weight_rt(loss, a.z, sigma_inv) > thr) + (mest_weight_rt(loss, a.w, sigma_inv) > thr) +
-              (mest_weight_rt(loss, b.x, sigma_inv) > thr) + (mest_weight_rt(loss, b.y, sigma_inv) > thr) +
-              (mest_weight_rt(loss, b.z, sigma_inv) > thr) + (mest_weight_rt(loss, b.w, sigma_inv) > thr);
-    }
-  } else {
-    const size_t total = (size_t) job->n * C_rt;
-    for(size_t k = (size_t) blockIdx.x * 256 + threadIdx.x; k < total; k += (size_t) gridDim.x * 256) good += mest_weight_rt(loss, job->r[k], sigma_inv) > thr ? 1u : 0u;
-  }
-  __shared__ unsigned s_good[4];
-  good = wave_sum_u32(good);
-  if((threadIdx.x & 63) == 0) s_good[threadIdx.x >> 6] = good;
-  __syncthreads();
-  if(threadIdx.x == 0) {
-    const unsigned t = s_good[0] + s_good[1] + s_good[2] + s_good[3];
-    if(t) atomicAdd(counts + blockIdx.y, t);
-  }
+  count_good_commit(count_good_of_job<C, -1>(job, C_rt, job->loss, job->good_thr), counts + blockIdx.y);
 }
 
 // 32-float result record per pair for the RCCL gather: pose 3x4 (12), numIterations per level (8), status per level (8),
@@ -895,13 +832,12 @@ void launch_weights(hipStream_t s, const PairJob* job, int n, int C, int loss, f
   dispatch_channels(C, [&](auto c) { launch_weights_c<decltype(c)::value>(s, job, n, loss, w_out); });
 }
 template <int C>
-static void launch_count_good_c(hipStream_t s, const PairJob* job, int n, int loss, float thr, unsigned int* count)
+static void launch_count_good_c(hipStream_t s, const PairJob* jobs, dim3 grid, int loss, float thr, unsigned int* counts)
 {
-  const dim3 grid(std::min((n + 255) / 256, 256));
   switch(loss) {
-    case BPVO_LOSS_HUBER: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_HUBER>), grid, dim3(256), 0, s, job, thr, count); break;
-    case BPVO_LOSS_TUKEY: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_TUKEY>), grid, dim3(256), 0, s, job, thr, count); break;
-    default: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_L2>), grid, dim3(256), 0, s, job, thr, count); break;
+    case BPVO_LOSS_HUBER: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_HUBER>), grid, dim3(256), 0, s, jobs, thr, counts); break;
+    case BPVO_LOSS_TUKEY: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_TUKEY>), grid, dim3(256), 0, s, jobs, thr, counts); break;
+    default: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_L2>), grid, dim3(256), 0, s, jobs, thr, counts); break;
   }
 }
 void launch_point_cloud(hipStream_t s, const PairJob* job, int n, int C, int loss, const uint8_t* img, int rows, int cols, const float K[9], int dspace,
@@ -917,27 +853,17 @@ void launch_count_good(hipStream_t s, const PairJob* job, int n, int C, int loss
 {
   if(n <= 0) return;
   if(C > 48) { hipLaunchKernelGGL(count_good_wide_kernel, dim3((unsigned) std::min<size_t>(((size_t) n * C + 255) / 256, 1024)), dim3(256), 0, s, job, C, loss, thr, count); return; }
-  dispatch_channels(C, [&](auto c) { launch_count_good_c<decltype(c)::value>(s, job, n, loss, thr, count); });
-}
-template <int C>
-static void launch_count_good_batch_c(hipStream_t s, const PairJob* jobs, int n_jobs, int max_n, int loss, float thr, unsigned int* counts)
-{
-  const dim3 grid(std::min((max_n + 255) / 256, 64), n_jobs);
-  switch(loss) {
-    case BPVO_LOSS_HUBER: hipLaunchKernelGGL((count_good_batch_kernel<C, BPVO_LOSS_HUBER>), grid, dim3(256), 0, s, jobs, thr, counts); break;
-    case BPVO_LOSS_TUKEY: hipLaunchKernelGGL((count_good_batch_kernel<C, BPVO_LOSS_TUKEY>), grid, dim3(256), 0, s, jobs, thr, counts); break;
-    default: hipLaunchKernelGGL((count_good_batch_kernel<C, BPVO_LOSS_L2>), grid, dim3(256), 0, s, jobs, thr, counts); break;
-  }
+  dispatch_channels(C, [&](auto c) { launch_count_good_c<decltype(c)::value>(s, job, dim3(std::min((n + 255) / 256, 256)), loss, thr, count); });
 }
 void launch_count_good_batch(hipStream_t s, const PairJob* jobs, int n_jobs, int max_n, int C, int loss, float thr, unsigned int* counts)
 {
   if(n_jobs <= 0 || max_n <= 0) return;
   if(C > 48) {
     const dim3 grid((unsigned) std::min<size_t>(((size_t) max_n * C + 255) / 256, 256), n_jobs);
-    hipLaunchKernelGGL(count_good_batch_wide_kernel, grid, dim3(256), 0, s, jobs, C, loss, thr, counts);
+    hipLaunchKernelGGL(count_good_wide_kernel, grid, dim3(256), 0, s, jobs, C, loss, thr, counts);
     return;
   }
-  dispatch_channels(C, [&](auto c) { launch_count_good_batch_c<decltype(c)::value>(s, jobs, n_jobs, max_n, loss, thr, counts); });
+  dispatch_channels(C, [&](auto c) { launch_count_good_c<decltype(c)::value>(s, jobs, dim3(std::min((max_n + 255) / 256, 64), n_jobs), loss, thr, counts); });
 }
 void launch_count_good_jobs(hipStream_t s, const PairJob* jobs, int n_jobs, int max_n, int C, unsigned int* counts)
 {

@@ -7,43 +7,16 @@ using namespace bpvo_hip_host;
 
 extern "C" {
 
-// ---- VisualOdometry -------------------------------------------------------------------------------------------------
-// the translation and rotation criteria of the key-frame decision (reference: bpvo/vo.cc:199-216): BPVO_KF_LARGE_TRANSLATION, BPVO_KF_LARGE_ROTATION,
-// or BPVO_KF_NO_KEYFRAMING when the fraction of good points decides.  Host floats (asin, sqrt) on purpose: the single and the many-sequence paths
-// decide with the same code.
-static int keyframe_by_motion(const bpvo_hip_params& p, const M44& pose)
-{
-  const float t_norm = pose.m[3] * pose.m[3] + pose.m[7] * pose.m[7] + pose.m[11] * pose.m[11];
-  if(t_norm > p.minTranslationMagToKeyFrame * p.minTranslationMagToKeyFrame) return BPVO_KF_LARGE_TRANSLATION;
-  // math::RotationMatrixToEulerAngles (bpvo/math_utils.h:203-216); compared in radians (Q17)
-  const float R00 = pose.m[0], R10 = pose.m[4], R20 = pose.m[8], R21 = pose.m[9];
-  const float eta = (float) (1.0 / (std::sqrt(R00 * R00 + R10 * R10)));
-  const float rz = std::asin(eta * R10), ry = std::asin(-R20), rx = std::asin(eta * R21);
-  const float r_norm = rx * rx + ry * ry + rz * rz;
-  if(r_norm > p.minRotationMagToKeyFrame * p.minRotationMagToKeyFrame) return BPVO_KF_LARGE_ROTATION;
-  return BPVO_KF_NO_KEYFRAMING;
-}
-static int should_keyframe(bpvo_hip_ctx* c, const M44& pose, int* reason)   // reference: bpvo/vo.cc:199-224
-{
-  const bpvo_hip_params& p = c->params;
-  *reason = keyframe_by_motion(p, pose);
-  if(*reason != BPVO_KF_NO_KEYFRAMING) return BPVO_OK;
-  float frac = 0.0f;
-  int rc = fraction_good(c, 0, p.goodPointThreshold, &frac);
-  if(rc) return rc;
-  *reason = (frac < p.maxFractionOfGoodPointsToKeyFrame) ? BPVO_KF_SMALL_FRAC_GOOD : BPVO_KF_NO_KEYFRAMING;
-  return BPVO_OK;
-}
-
+// ---- VisualOdometry: one frame (the state machine both drivers run: vo_state.h) -----------------------------------------------------------
 // getPointCloudFromRefFrame + GetColor (reference: bpvo/vo.cc:250-281)
-static int build_point_cloud(bpvo_hip_ctx* c)
+static int build_point_cloud(bpvo_hip_ctx* c, size_t* cloud_points)
 {
   // One kernel over the template points of the level the estimate ended on; nothing crosses the bus here: the 32-byte records wait in HBM for
   // bpvo_hip_get_point_cloud (the reference's Result owns its cloud; here the caller fetches it — vo.hpp does, into the Result's vector).
   // (Before: every channel's weights + the points + the image copied out and a host loop over the points — 5 - 9 ms per key frame of a dense
   // 640 x 480 template, more than the estimate itself.)
   const int lvl = c->params.maxTestLevel;
-  FrameSlot& ref = c->frames[c->vo_ref];
+  FrameSlot& ref = c->frames[c->vo.ref];
   const int n = ref.n_host[lvl];
   Workspace& w = c->ws[0];
   if(w.last_ref < 0) return fail(c, BPVO_ERR_NO_DATA, "no linearisation has run on this workspace");
@@ -62,11 +35,30 @@ static int build_point_cloud(bpvo_hip_ctx* c)
   }
   launch_point_cloud(c->stream, c->d_job1, n, c->C, c->params.lossFunction, ref.img[0], c->rows, c->cols, c->geom[lvl].K, c->dspace, c->d_cloud);
   HIP_CK(c, hipGetLastError());
-  c->cloud_n = (size_t) n;
+  *cloud_points = (size_t) n;
   return BPVO_OK;
 }
 
 // ---- stereo front-end (reference: utils/stereo_algorithm.cc:63-82,98-111 -> OpenCV 2.4 cvFindStereoCorrespondenceBM) ----
+// the parameter fields of the semi-global matchers' launches for frames of rows x cols (pointers and frame counts: the caller's)
+static SgbmLaunch sgbm_launch_of(const bpvo_hip_stereo_params& sp, int rows, int cols)
+{
+  SgbmLaunch g = {};
+  g.rows = rows; g.cols = cols;
+  g.min_disp = sp.minDisparity; g.ndisp = sp.numberOfDisparities; g.sad_window = sp.SADWindowSize; g.P1 = sp.P1; g.P2 = sp.P2;
+  g.disp12_max_diff = sp.disp12MaxDiff; g.pre_filter_cap = sp.preFilterCap; g.uniqueness_ratio = sp.uniquenessRatio;
+  g.speckle_window = sp.speckleWindowSize; g.speckle_range = sp.speckleRange; g.full_dp = sp.fullDP;
+  return g;
+}
+static SgmLaunch sgm_launch_of(const bpvo_hip_stereo_params& sp, int rows, int cols)
+{
+  SgmLaunch g = {};
+  g.rows = rows; g.cols = cols;
+  g.ndisp = sp.numberOfDisparities; g.sobel_cap = sp.sobelCapValue; g.census_radius = sp.censusRadius; g.window_radius = sp.windowRadius;
+  g.P1 = sp.smoothnessPenaltySmall; g.P2 = sp.smoothnessPenaltyLarge; g.consistency_threshold = sp.consistencyThreshold;
+  g.disparity_factor = sp.disparityFactor; g.census_weight = sp.censusWeightFactor;
+  return g;
+}
 // (rows x cols: the frame the parameters are checked for — the context's size, or a camera's)
 static int stereo_check(bpvo_hip_ctx* c, const bpvo_hip_stereo_params* sp, int rows, int cols)
 {
@@ -91,13 +83,8 @@ static int stereo_check(bpvo_hip_ctx* c, const bpvo_hip_stereo_params* sp, int r
   }
   if(sp->algorithm == BPVO_STEREO_SGBM) {
     if(sp->numberOfDisparities <= 0 || sp->numberOfDisparities % 16) return fail(c, BPVO_ERR_INVALID_ARG, "numberOfDisparities must be a positive multiple of 16");   // CV_Assert(D % 16 == 0)
-    SgbmLaunch g = {};
-    g.rows = rows; g.cols = cols;
-    g.min_disp = sp->minDisparity; g.ndisp = sp->numberOfDisparities; g.sad_window = sp->SADWindowSize; g.P1 = sp->P1; g.P2 = sp->P2;
-    g.disp12_max_diff = sp->disp12MaxDiff; g.pre_filter_cap = sp->preFilterCap; g.uniqueness_ratio = sp->uniquenessRatio;
-    g.speckle_window = sp->speckleWindowSize; g.speckle_range = sp->speckleRange; g.full_dp = sp->fullDP;
     const char* why = nullptr;
-    if(!sgbm_serves(g, &why)) return fail(c, BPVO_ERR_UNSUPPORTED, why);
+    if(!sgbm_serves(sgbm_launch_of(*sp, rows, cols), &why)) return fail(c, BPVO_ERR_UNSUPPORTED, why);
     return BPVO_OK;
   }
   if(sp->algorithm != BPVO_STEREO_BLOCK_MATCHING) return fail(c, BPVO_ERR_UNSUPPORTED, "StereoAlgorithm: BlockMatching, SGM and SGBM are on the device path (RSGM is GPL-gated in the reference and not built)");
@@ -136,17 +123,18 @@ static int stereo_scratch(bpvo_hip_ctx* c, size_t need)      // the semi-global 
 static int seq_capacity(const bpvo_hip_ctx* c);
 struct StereoSize { int rows, cols; };
 static bool operator==(const StereoSize& a, const StereoSize& b) { return a.rows == b.rows && a.cols == b.cols; }
-// The checks of a call's stereo stage, once per size among its frames; nothing is touched.  *bad: the first frame whose size fails.
-static int stereo_check_sizes(bpvo_hip_ctx* c, int n, const StereoSize* sz, const bpvo_hip_stereo_params* sp, int* bad)
+// The checks of a call's stereo stage, once per size among its frames; nothing is touched.  ids: null (the context's own size: stereo_run), or the
+// sequence of each frame — a failure names the first frame's whose size fails.
+static int stereo_check_sizes(bpvo_hip_ctx* c, int n, const StereoSize* sz, const bpvo_hip_stereo_params* sp, const int* ids)
 {
-  *bad = -1;
   if(!sp) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr stereo parameters");
   for(int i = 0; i < n; ++i) {
     bool seen = false;
     for(int k = 0; k < i && !seen; ++k) seen = sz[k] == sz[i];
     if(seen) continue;
     const int rc = stereo_check(c, sp, sz[i].rows, sz[i].cols);
-    if(rc) { *bad = i; return rc; }
+    if(rc && ids) c->err = "sequence " + std::to_string(ids[i]) + ": " + c->err;
+    if(rc) return rc;
   }
   return BPVO_OK;
 }
@@ -215,21 +203,15 @@ static int stereo_run_sizes(bpvo_hip_ctx* c, int n, const StereoSize* sz, const 
     for(const Run& r : runs) {
       const StereoSize& q = sz[r.first];
       if(sgm) {
-        SgmLaunch g;
+        SgmLaunch g = sgm_launch_of(*sp, q.rows, q.cols);
         g.left = dl + r.at; g.right = dr + r.at; g.disp = c->st_disp + r.at; g.scratch = c->st_sgm;
-        g.rows = q.rows; g.cols = q.cols; g.nframes = r.count; g.frames_per_launch = r.per_launch;
-        g.ndisp = sp->numberOfDisparities; g.sobel_cap = sp->sobelCapValue; g.census_radius = sp->censusRadius; g.window_radius = sp->windowRadius;
-        g.P1 = sp->smoothnessPenaltySmall; g.P2 = sp->smoothnessPenaltyLarge; g.consistency_threshold = sp->consistencyThreshold;
-        g.disparity_factor = sp->disparityFactor; g.census_weight = sp->censusWeightFactor;
+        g.nframes = r.count; g.frames_per_launch = r.per_launch;
         c->st_frames_per_launch_seen = r.per_launch;
         if(!launch_stereo_sgm(c->stream, g)) return fail(c, BPVO_ERR_UNSUPPORTED, "semi-global matching: disparity range not served by the kernels");
       } else {
-        SgbmLaunch g = {};
+        SgbmLaunch g = sgbm_launch_of(*sp, q.rows, q.cols);
         g.left = dl + r.at; g.right = dr + r.at; g.disp = c->st_disp + r.at; g.scratch = c->st_sgm;
-        g.rows = q.rows; g.cols = q.cols; g.nframes = r.count;
-        g.min_disp = sp->minDisparity; g.ndisp = sp->numberOfDisparities; g.sad_window = sp->SADWindowSize; g.P1 = sp->P1; g.P2 = sp->P2;
-        g.disp12_max_diff = sp->disp12MaxDiff; g.pre_filter_cap = sp->preFilterCap; g.uniqueness_ratio = sp->uniquenessRatio;
-        g.speckle_window = sp->speckleWindowSize; g.speckle_range = sp->speckleRange; g.full_dp = sp->fullDP;
+        g.nframes = r.count;
         if(!launch_stereo_sgbm(c->stream, g)) return fail(c, BPVO_ERR_UNSUPPORTED, "semi-global block matching: parameters not served by the kernels");
       }
       HIP_CK(c, hipGetLastError());
@@ -271,14 +253,14 @@ static int stereo_run_sizes(bpvo_hip_ctx* c, int n, const StereoSize* sz, const 
   HIP_CK(c, hipGetLastError());
   return BPVO_OK;
 }
-// `count` pairs of the context's size
+// `count` pairs of the context's size: the sized path's uniform case (the parameters are held against the size before the images are looked at)
 static int stereo_run(bpvo_hip_ctx* c, int count, const uint8_t* left, const uint8_t* right, bool on_device, const bpvo_hip_stereo_params* sp,
                       const uint8_t** d_left)
 {
-  int rc = stereo_check(c, sp, c->rows, c->cols);
+  const StereoSize size{c->rows, c->cols};
+  const int rc = stereo_check_sizes(c, 1, &size, sp, nullptr);
   if(rc) return rc;
-  if(count <= 0 || !left || !right) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image");
-  const std::vector<StereoSize> sz((size_t) count, StereoSize{c->rows, c->cols});
+  const std::vector<StereoSize> sz((size_t) std::max(count, 0), size);
   return stereo_run_sizes(c, count, sz.data(), left, right, on_device, sp, d_left);
 }
 
@@ -341,6 +323,7 @@ int bpvo_hip_add_frame_stereo(bpvo_hip_ctx* c, const uint8_t* left, const uint8_
   if(rc) return rc;
   return add_frame_impl(c, d_left, c->st_disp, true, ret);
 }
+static void slot_clear(bpvo_hip_ctx* c, int slot) { c->frames[slot].has_data = false; c->frames[slot].has_template = false; }
 static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* disparity, bool on_device, bpvo_hip_result* ret)
 {
   if(!ret) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
@@ -348,28 +331,19 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
   if(c->vo_mode == 2) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frames: a context serves either add_frame or add_frames");
   c->vo_mode = 1;
   (void) hipSetDevice(c->device);
-  const M44 I = m44_identity();
-  std::memset(ret, 0, sizeof(*ret));
-  std::memcpy(ret->pose, I.m, 64);
-  for(int i = 0; i < 36; ++i) ret->covariance[i] = (i % 7 == 0) ? 1.0f : 0.0f;   // Q16
-  ret->numLevels = c->L;
-  for(int l = 0; l < kMaxLevels; ++l) ret->optimizerStatistics[l] = bpvo_hip_stats{0, -1.0f, -1.0f, BPVO_STATUS_SOLVER_ERROR};
-  ret->isKeyFrame = 0;
-  ret->keyFramingReason = BPVO_KF_NO_KEYFRAMING;
-  ret->hasPointCloud = 0;
-  c->cloud_n = 0;                   // the point cloud belongs to one Result (bpvo/types.h:549-563)
-  c->cloud_pose = I;
+  SeqState& q = c->vo;
+  vo_begin_frame(q, c->L, ret);
 
   // _cur_frame->setData (vo.cc:131).  No host synchronisation behind it: the estimate queues behind the data stage on the same stream and ends
   // with one (every copy from the caller's buffers is complete when this function returns — its early returns synchronise themselves).  The
   // disparity of a host frame, which only a later template stage reads, is uploaded once the estimate is queued (upload_disparity): the copy
   // from pageable memory holds the host for 90 us, which then lie under the Gauss-Newton kernels instead of in front of them.
-  if(c->vo_cur < 0 || c->vo_cur >= c->n_frames) return fail(c, BPVO_ERR_INVALID_ARG, "bad frame slot range");
+  if(q.cur < 0 || q.cur >= c->n_frames) return fail(c, BPVO_ERR_INVALID_ARG, "bad frame slot range");
   FrameRun data_run = ctx_run(c);
   data_run.skip_disparity_upload = !on_device && c->vo_disparity_late && single_pair_is_queued_at_once(c);
-  int rc = frames_set_data(c, c->vo_cur, 1, 1, image, disparity, on_device, data_run, 0);
+  int rc = frames_set_data(c, q.cur, 1, 1, image, disparity, on_device, data_run, 0);
   if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
-  const int data_slot = c->vo_cur;
+  const int data_slot = q.cur;
   bool disparity_pending = data_run.skip_disparity_upload;
   auto upload_now = [&]() -> int {
     c->before_final_sync = nullptr;
@@ -378,127 +352,123 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
     return upload_disparity(c, data_slot, disparity);
   };
 
-  if(!c->frames[c->vo_ref].has_template) {            // first frame (vo.cc:133-139)
-    std::swap(c->vo_ref, c->vo_cur);
+  if(!c->frames[q.ref].has_template) {                // first frame (vo.cc:133-139)
+    const int slot = vo_first_frame(q);
     rc = upload_now();                                 // (its template stage reads the disparity)
-    if(rc == BPVO_OK) rc = frames_set_template(c, c->vo_ref, 1, 1);
+    if(rc == BPVO_OK) rc = frames_set_template(c, slot, 1, 1);
     if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
-    trajectory_push(c, c->T_kf);
-    ret->isKeyFrame = 1;
-    ret->keyFramingReason = BPVO_KF_FIRST_FRAME;
+    vo_first_frame_done(q, ret);
     return BPVO_OK;
   }
 
-  M44 T_est;
+  M44 T_est, T_again;
   const int ws0 = 0;
-  rc = check_template_not_empty(c, c->vo_ref);
+  rc = check_template_not_empty(c, q.ref);
   if(rc) { (void) upload_now(); (void) hipStreamSynchronize(c->stream); return rc; }
-  c->prefetch_frac_thr = c->params.goodPointThreshold;      // should_keyframe's fraction of good points rides behind the estimate
+  c->prefetch_frac_thr = c->params.goodPointThreshold;      // the decision's fraction of good points rides behind the estimate
   if(disparity_pending) c->before_final_sync = [&]() { return upload_now(); };
-  rc = estimate_batch(c, 1, &ws0, &c->vo_ref, &c->vo_cur, c->T_kf.m, T_est.m, ret->optimizerStatistics);
+  rc = estimate_batch(c, 1, &ws0, &q.ref, &q.cur, q.T_kf.m, T_est.m, ret->optimizerStatistics);
   c->prefetch_frac_thr = -1.0f;
   {      // (an estimate that did not come by its final synchronisation — an error on the way, another path — : now)
     const int rcu = upload_now();
     if(rc == BPVO_OK) rc = rcu;
   }
   if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
-  int reason = BPVO_KF_NO_KEYFRAMING;
-  rc = should_keyframe(c, T_est, &reason);
-  if(rc) return rc;
-  ret->keyFramingReason = reason;
-  ret->isKeyFrame = reason != BPVO_KF_NO_KEYFRAMING;
-
-  M44 pose;
-  if(!ret->isKeyFrame) {
-    std::swap(c->vo_prev, c->vo_cur);
-    pose = m44_mul(T_est, m44_inverse(c->T_kf));
-    c->T_kf = T_est;
-  } else {
-    rc = build_point_cloud(c);
+  // the key-frame decision (vo.cc:199-224).  The fraction of good points is fetched only where the motion leaves the decision to it: an estimate
+  // that could not take the count along pays a launch and a round trip for it.
+  float frac = 0.0f;
+  if(keyframe_by_motion(c->params, T_est) == BPVO_KF_NO_KEYFRAMING) {
+    rc = fraction_good(c, 0, c->params.goodPointThreshold, &frac);
     if(rc) return rc;
-    ret->hasPointCloud = 1;
-    if(!c->frames[c->vo_prev].has_data) {               // vo.cc:161-173
-      std::swap(c->vo_cur, c->vo_ref);
-      rc = frames_set_template(c, c->vo_ref, 1, 1);
+  }
+  bool again = false;
+  if(vo_decide(c->params, T_est, frac, ret)) {
+    size_t cloud_points = 0;
+    rc = build_point_cloud(c, &cloud_points);
+    if(rc) return rc;
+    const KeyFrameSlots kf = vo_keyframe(q, c->frames[q.prev].has_data, cloud_points, ret);
+    if(kf.clear_slot >= 0) slot_clear(c, kf.clear_slot);
+    if(!kf.reestimate) {                                // vo.cc:161-173
+      rc = frames_set_template(c, kf.template_slot, 1, 1);
       if(rc) return rc;
-      pose = m44_mul(T_est, m44_inverse(c->T_kf));
-      c->T_kf = m44_identity();
     } else {                                            // vo.cc:174-188
-      std::swap(c->vo_prev, c->vo_ref);
-      c->frames[c->vo_prev].has_data = false;
-      c->frames[c->vo_prev].has_template = false;
       // the estimate against the new key frame follows on the same stream: the template stage ends without a host round trip of its own and
       // leaves the normalisation sums of the levels below the coarsest on the side streams, under the Gauss-Newton iterations of the levels
       // above them (a dense 640x480 template, conf/tsukuba.cfg: 2.3 ms of dependent adds for the finest level)
       FrameRun fr = ctx_run(c);
       fr.no_final_sync = !c->profiling;
       fr.defer_finest_nrm = true;
-      rc = frames_set_template(c, c->vo_ref, 1, 1, fr);
-      if(rc == BPVO_OK) rc = estimate_batch(c, 1, &ws0, &c->vo_ref, &c->vo_cur, I.m, T_est.m, ret->optimizerStatistics);
+      rc = frames_set_template(c, kf.template_slot, 1, 1, fr);
+      const M44 I = m44_identity();
+      if(rc == BPVO_OK) rc = estimate_batch(c, 1, &ws0, &q.ref, &q.cur, I.m, T_again.m, ret->optimizerStatistics);
       // (an error on the way: nothing of this call stays in flight)
       if(c->nrm_pending) { (void) hipEventSynchronize(c->nrm_pending); c->nrm_pending = nullptr; }
       if(c->nrm_pending_finest) { (void) hipEventSynchronize(c->nrm_pending_finest); c->nrm_pending_finest = nullptr; }
       if(rc) return rc;
-      pose = T_est;
-      c->T_kf = T_est;
+      again = true;
     }
   }
-  std::memcpy(ret->pose, pose.m, 64);
-  trajectory_push(c, pose);
-  if(ret->hasPointCloud) c->cloud_pose = c->trajectory.back();
+  vo_finish(q, T_est, again ? &T_again : nullptr, ret);
   return BPVO_OK;
 }
 
-int bpvo_hip_vo_num_points_at_level(bpvo_hip_ctx* c, int level, int* n)
+// The accessors of a VisualOdometry state, for bpvo_hip_add_frame's and for a sequence's (q: null while the sequences have no state yet)
+static int vo_num_points_at_level(bpvo_hip_ctx* c, const SeqState* q, int level, int* n)
 {
-  CHECK_CTX(c);
   if(level < 0) level = c->params.maxTestLevel;
   if(level >= c->L) return fail(c, BPVO_ERR_INVALID_ARG, "bad level");
-  *n = c->frames[c->vo_ref].has_template ? c->frames[c->vo_ref].n_host[level] : 0;
+  *n = q && c->frames[q->ref].has_template ? c->frames[q->ref].n_host[level] : 0;
   return BPVO_OK;
 }
+static int vo_get_point_cloud(bpvo_hip_ctx* c, const SeqState* q, const bpvo_hip_point_with_info* d_cloud, bpvo_hip_point_with_info* pts, size_t* n,
+                              float pose[16])
+{
+  const size_t cnt = q ? q->cloud_n : 0;
+  if(n) *n = cnt;
+  if(pts && cnt) {
+    (void) hipSetDevice(c->device);
+    HIP_CK(c, hipMemcpyAsync(pts, d_cloud, cnt * sizeof(bpvo_hip_point_with_info), hipMemcpyDeviceToHost, c->stream));
+    HIP_CK(c, hipStreamSynchronize(c->stream));
+  }
+  if(pose) {
+    const M44 P = q ? q->cloud_pose : m44_identity();
+    std::memcpy(pose, P.m, 64);
+  }
+  return BPVO_OK;
+}
+static int vo_trajectory_size(const SeqState* q) { return q ? (int) q->trajectory.size() : 0; }
+static void vo_get_trajectory(const SeqState* q, float* poses)
+{
+  for(size_t i = 0; q && i < q->trajectory.size(); ++i) std::memcpy(poses + 16 * i, q->trajectory[i].m, 64);
+}
+
+int bpvo_hip_vo_num_points_at_level(bpvo_hip_ctx* c, int level, int* n) { CHECK_CTX(c); return vo_num_points_at_level(c, &c->vo, level, n); }
 int bpvo_hip_vo_points_at_level(bpvo_hip_ctx* c, int level, float* xyzw)
 {
   CHECK_CTX(c);
   if(level < 0) level = c->params.maxTestLevel;
-  return bpvo_hip_get_points(c, c->vo_ref, level, xyzw);
+  return bpvo_hip_get_points(c, c->vo.ref, level, xyzw);
 }
 int bpvo_hip_get_point_cloud(bpvo_hip_ctx* c, bpvo_hip_point_with_info* pts, size_t* n, float pose[16])
 {
   CHECK_CTX(c);
-  if(n) *n = c->cloud_n;
-  if(pts && c->cloud_n) {
-    (void) hipSetDevice(c->device);
-    HIP_CK(c, hipMemcpyAsync(pts, c->d_cloud, c->cloud_n * sizeof(bpvo_hip_point_with_info), hipMemcpyDeviceToHost, c->stream));
-    HIP_CK(c, hipStreamSynchronize(c->stream));
-  }
-  if(pose) std::memcpy(pose, c->cloud_pose.m, 64);
-  return BPVO_OK;
+  return vo_get_point_cloud(c, &c->vo, c->d_cloud, pts, n, pose);
 }
-int bpvo_hip_trajectory_size(bpvo_hip_ctx* c, int* n) { CHECK_CTX(c); *n = (int) c->trajectory.size(); return BPVO_OK; }
-int bpvo_hip_get_trajectory(bpvo_hip_ctx* c, float* poses)
-{
-  CHECK_CTX(c);
-  for(size_t i = 0; i < c->trajectory.size(); ++i) std::memcpy(poses + 16 * i, c->trajectory[i].m, 64);
-  return BPVO_OK;
-}
+int bpvo_hip_trajectory_size(bpvo_hip_ctx* c, int* n) { CHECK_CTX(c); *n = vo_trajectory_size(&c->vo); return BPVO_OK; }
+int bpvo_hip_get_trajectory(bpvo_hip_ctx* c, float* poses) { CHECK_CTX(c); vo_get_trajectory(&c->vo, poses); return BPVO_OK; }
 
 // ---- many independent VisualOdometry sequences in one context (bpvo/vo.cc:125-224 per sequence) ---------------------------------------------
 // Sequence s owns frame slots 3s .. 3s+2 and workspace s.  One call runs every phase of addFrame once for all the sequences it advances: one data
 // stage over their current slots, one template stage for the first frames, one estimate, one count of good points, one point-cloud launch and
 // one template stage for the key frames, one estimate against the new key frames.  Each sequence sees the same kernels on the same inputs as
 // the single path's addFrame (the frame stages, the estimate and the counts do not depend on the batch a frame or pair is in), and the host
-// decides with the same float code: the results are the single path's, bit for bit.
+// decides with the same float code — every decision and every change of a sequence's state is a call into vo_state.h, the calls add_frame_impl
+// makes —: the results are the single path's, bit for bit.
 static int seq_capacity(const bpvo_hip_ctx* c) { return std::max(0, std::min(c->n_frames / 3, c->n_pairs)); }
 static void seq_reset_state(bpvo_hip_ctx* c, int s)
 {
-  SeqState& q = c->seqs[s];
-  q.ref = 3 * s; q.cur = 3 * s + 1; q.prev = 3 * s + 2;
-  for(int k = 0; k < 3; ++k) { c->frames[3 * s + k].has_data = false; c->frames[3 * s + k].has_template = false; }
-  q.T_kf = m44_identity();
-  q.trajectory.clear();
-  q.cloud_n = 0;
-  q.cloud_pose = m44_identity();
+  vo_reset(c->seqs[s], 3 * s);
+  for(int k = 0; k < 3; ++k) slot_clear(c, 3 * s + k);
   Workspace& w = c->ws[s];
   w.last_ref = w.last_cur = w.last_level = -1;
 }
@@ -533,17 +503,19 @@ static int seq_fail(bpvo_hip_ctx* c, int code, int seq, const char* what)
   c->err = "sequence " + std::to_string(seq) + ": " + what;
   return code;
 }
-static void init_result(const bpvo_hip_ctx* c, bpvo_hip_result* ret)      // what add_frame_impl hands back before it knows anything
+// the failures the camera and parameter setters share
+static int camera_too_large(bpvo_hip_ctx* c, int seq, int rows, int cols)
 {
-  const M44 I = m44_identity();
-  std::memset(ret, 0, sizeof(*ret));
-  std::memcpy(ret->pose, I.m, 64);
-  for(int i = 0; i < 36; ++i) ret->covariance[i] = (i % 7 == 0) ? 1.0f : 0.0f;   // Q16
-  ret->numLevels = c->L;
-  for(int l = 0; l < kMaxLevels; ++l) ret->optimizerStatistics[l] = bpvo_hip_stats{0, -1.0f, -1.0f, BPVO_STATUS_SOLVER_ERROR};
-  ret->isKeyFrame = 0;
-  ret->keyFramingReason = BPVO_KF_NO_KEYFRAMING;
-  ret->hasPointCloud = 0;
+  return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, ("camera " + std::to_string(cols) + "x" + std::to_string(rows) + " larger than the context's " +
+                                                 std::to_string(c->cols) + "x" + std::to_string(c->rows)).c_str());
+}
+// BPVO_OK while none of the sequence's slots holds a frame, else the failure; what: "camera changes" / "parameters change"
+static int seq_is_fresh(bpvo_hip_ctx* c, int seq, const char* what)
+{
+  for(int k = 0; k < 3; ++k)
+    if(c->frames[3 * seq + k].has_data || c->frames[3 * seq + k].has_template)
+      return seq_fail(c, BPVO_ERR_INVALID_ARG, seq, ("holds frames: its " + std::string(what) + " only while it is fresh or after bpvo_hip_seq_reset").c_str());
+  return BPVO_OK;
 }
 }  // extern "C"
 
@@ -619,12 +591,7 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
   if(rc) return rc;
   c->vo_mode = 2;
   const M44 I = m44_identity();
-  for(int i = 0; i < n; ++i) {
-    init_result(c, results + i);
-    SeqState& q = c->seqs[ids[i]];
-    q.cloud_n = 0;                  // the point cloud belongs to one Result (bpvo/types.h:549-563)
-    q.cloud_pose = I;
-  }
+  for(int i = 0; i < n; ++i) vo_begin_frame(c->seqs[ids[i]], c->L, results + i);
   auto drain = [&](int code) { (void) hipStreamSynchronize(c->stream); return code; };
 
   // 2. _cur_frame->setData (vo.cc:131) of every sequence: one data stage over their current slots
@@ -649,18 +616,14 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
   for(int i = 0; i < n; ++i) {
     SeqState& q = c->seqs[ids[i]];
     if(c->frames[q.ref].has_template) { est.push_back(i); continue; }
-    std::swap(q.ref, q.cur);
-    slots.push_back(q.ref);
+    slots.push_back(vo_first_frame(q));
   }
   if(!slots.empty()) {
     rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
     for(int i = 0; i < n; ++i) {
-      SeqState& q = c->seqs[ids[i]];
       if(std::find(est.begin(), est.end(), i) != est.end()) continue;
-      trajectory_push(q.trajectory, q.T_kf);
-      results[i].isKeyFrame = 1;
-      results[i].keyFramingReason = BPVO_KF_FIRST_FRAME;
+      vo_first_frame_done(c->seqs[ids[i]], &results[i]);
     }
   }
   const int m = (int) est.size();
@@ -709,23 +672,15 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
   for(int k = 0; k < m; ++k) {
     M44 T;
     std::memcpy(T.m, &T_est[(size_t) k * 16], 64);
-    const bpvo_hip_params& sp = *prms[k];      // the sequence's thresholds (the context's unless it was given its own)
-    int reason = keyframe_by_motion(sp, T);
-    if(reason == BPVO_KF_NO_KEYFRAMING) {
-      const int npts = c->h_seq_jobs[k].n;
-      const float frac = c->h_seq_cnt[k] / static_cast<float>((size_t) npts * c->C);   // fraction_good (vo_pose_estimator.cc:105-106)
-      reason = (frac < sp.maxFractionOfGoodPointsToKeyFrame) ? BPVO_KF_SMALL_FRAC_GOOD : BPVO_KF_NO_KEYFRAMING;
-    }
-    results[est[k]].keyFramingReason = reason;
-    results[est[k]].isKeyFrame = reason != BPVO_KF_NO_KEYFRAMING;
-    if(reason != BPVO_KF_NO_KEYFRAMING) kf.push_back(k);
+    // with the sequence's thresholds (the context's unless it was given its own)
+    if(vo_decide(*prms[k], T, vo_fraction_good(c->h_seq_cnt[k], c->h_seq_jobs[k].n, c->C), &results[est[k]])) kf.push_back(k);
   }
 
   // 6. key frames: the point clouds from the old key frames and the last linearisations (build_point_cloud), then the new templates, then the
   // estimate against them of the sequences that had a previous frame (vo.cc:161-188)
   const int nk = (int) kf.size();
   std::vector<int> re;            // entries of est that estimate again
-  std::vector<float> T_again;
+  std::vector<float> T_again_all;
   if(nk) {
     const size_t cap = (size_t) c->geom[lvl].cap;
     int max_c = 0;
@@ -748,17 +703,10 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
     for(int j = 0; j < nk; ++j) {
       const int k = kf[j];
       SeqState& q = c->seqs[wss[k]];
-      q.cloud_n = (size_t) c->h_seq_jobs[k].n;
-      results[est[k]].hasPointCloud = 1;
-      if(!c->frames[q.prev].has_data) {               // vo.cc:161-173
-        std::swap(q.cur, q.ref);
-      } else {                                        // vo.cc:174-188
-        std::swap(q.prev, q.ref);
-        c->frames[q.prev].has_data = false;
-        c->frames[q.prev].has_template = false;
-        re.push_back(j);
-      }
-      slots.push_back(q.ref);
+      const KeyFrameSlots ks = vo_keyframe(q, c->frames[q.prev].has_data, (size_t) c->h_seq_jobs[k].n, &results[est[k]]);
+      if(ks.clear_slot >= 0) slot_clear(c, ks.clear_slot);
+      if(ks.reestimate) re.push_back(j);
+      slots.push_back(ks.template_slot);
     }
     rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
@@ -768,42 +716,27 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
       std::vector<float> I2((size_t) mr * 16);
       std::vector<bpvo_hip_stats> st2((size_t) mr * L);
       std::vector<const bpvo_hip_params*> p2((size_t) mr);
-      T_again.resize((size_t) mr * 16);
+      T_again_all.resize((size_t) mr * 16);
       for(int t = 0; t < mr; ++t) {
         const SeqState& q = c->seqs[wss[kf[re[t]]]];
         w2[t] = wss[kf[re[t]]]; r2[t] = q.ref; c2[t] = q.cur;
         std::memcpy(&I2[(size_t) t * 16], I.m, 64);
         p2[t] = &q.params;
       }
-      rc = estimate_batch(c, mr, w2.data(), r2.data(), c2.data(), I2.data(), T_again.data(), st2.data(), own ? p2.data() : nullptr);
+      rc = estimate_batch(c, mr, w2.data(), r2.data(), c2.data(), I2.data(), T_again_all.data(), st2.data(), own ? p2.data() : nullptr);
       if(rc) return drain(rc);
       for(int t = 0; t < mr; ++t) std::memcpy(results[est[kf[re[t]]]].optimizerStatistics, &st2[(size_t) t * L], sizeof(bpvo_hip_stats) * L);
     }
   }
 
-  // 7. poses, T_kf and trajectories (add_frame_impl)
+  // 7. poses, T_kf and trajectories
   std::vector<int> again_of((size_t) m, -1);
   for(int t = 0; t < (int) re.size(); ++t) again_of[kf[re[t]]] = t;
   for(int k = 0; k < m; ++k) {
-    bpvo_hip_result& ret = results[est[k]];
-    SeqState& q = c->seqs[wss[k]];
-    M44 T;
+    M44 T, T_again;
     std::memcpy(T.m, &T_est[(size_t) k * 16], 64);
-    M44 pose;
-    if(!ret.isKeyFrame) {
-      std::swap(q.prev, q.cur);
-      pose = m44_mul(T, m44_inverse(q.T_kf));
-      q.T_kf = T;
-    } else if(again_of[k] < 0) {
-      pose = m44_mul(T, m44_inverse(q.T_kf));
-      q.T_kf = I;
-    } else {
-      std::memcpy(pose.m, &T_again[(size_t) again_of[k] * 16], 64);
-      q.T_kf = pose;
-    }
-    std::memcpy(ret.pose, pose.m, 64);
-    trajectory_push(q.trajectory, pose);
-    if(ret.hasPointCloud) q.cloud_pose = q.trajectory.back();
+    if(again_of[k] >= 0) std::memcpy(T_again.m, &T_again_all[(size_t) again_of[k] * 16], 64);
+    vo_finish(c->seqs[wss[k]], T, again_of[k] >= 0 ? &T_again : nullptr, &results[est[k]]);
   }
   return BPVO_OK;
 }
@@ -831,12 +764,8 @@ int bpvo_hip_add_frames_stereo(bpvo_hip_ctx* c, int n, const int* seq, const uin
     const LevelGeom& g = slot_geom(c, c->frames[3 * ids[i]], 0);
     sz[i] = StereoSize{g.rows, g.cols};
   }
-  int bad = -1;
-  rc = stereo_check_sizes(c, n, sz.data(), sp, &bad);
-  if(rc) {
-    if(bad >= 0) c->err = "sequence " + std::to_string(ids[bad]) + ": " + c->err;
-    return rc;
-  }
+  rc = stereo_check_sizes(c, n, sz.data(), sp, ids.data());
+  if(rc) return rc;
   (void) hipSetDevice(c->device);
   const uint8_t* d_left = nullptr;
   rc = stereo_run_sizes(c, n, sz.data(), left, right, on_device != 0, sp, &d_left);
@@ -851,21 +780,17 @@ int bpvo_hip_stereo_frames(bpvo_hip_ctx* c, int n, const bpvo_hip_camera* cams, 
   if(n < 1 || !cams) return fail(c, BPVO_ERR_INVALID_ARG, "stereo_frames: n >= 1 cameras");
   if(!left || !right) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image");
   std::vector<StereoSize> sz((size_t) n);
+  std::vector<int> ids((size_t) n);
   size_t npix = 0;
   for(int i = 0; i < n; ++i) {
+    ids[i] = i;
     sz[i] = StereoSize{cams[i].rows, cams[i].cols};
     if(sz[i].rows < 1 || sz[i].cols < 1) return seq_fail(c, BPVO_ERR_INVALID_ARG, i, "camera: image size out of range");
-    if(sz[i].rows > c->rows || sz[i].cols > c->cols)
-      return seq_fail(c, BPVO_ERR_UNSUPPORTED, i, ("camera " + std::to_string(sz[i].cols) + "x" + std::to_string(sz[i].rows) + " larger than the context's " +
-                                                   std::to_string(c->cols) + "x" + std::to_string(c->rows)).c_str());
+    if(sz[i].rows > c->rows || sz[i].cols > c->cols) return camera_too_large(c, i, sz[i].rows, sz[i].cols);
     npix += (size_t) sz[i].rows * sz[i].cols;
   }
-  int bad = -1;
-  int rc = stereo_check_sizes(c, n, sz.data(), sp, &bad);
-  if(rc) {
-    if(bad >= 0) c->err = "sequence " + std::to_string(bad) + ": " + c->err;
-    return rc;
-  }
+  int rc = stereo_check_sizes(c, n, sz.data(), sp, ids.data());
+  if(rc) return rc;
   for(int i = 0; i < n; ++i)      // (what bpvo_hip_create admits, after the parameters have been held against every size)
     if(sz[i].rows < 8 || sz[i].cols < 8) return seq_fail(c, BPVO_ERR_INVALID_ARG, i, "camera: image size out of range (at least 8 rows and cols)");
   (void) hipSetDevice(c->device);
@@ -888,50 +813,30 @@ int bpvo_hip_seq_reset(bpvo_hip_ctx* c, int seq)
   if(!c->seqs.empty()) seq_reset_state(c, seq);
   return BPVO_OK;
 }
+static const SeqState* seq_state(const bpvo_hip_ctx* c, int seq) { return c->seqs.empty() ? nullptr : &c->seqs[seq]; }
 int bpvo_hip_seq_num_points_at_level(bpvo_hip_ctx* c, int seq, int level, int* n)
 {
   CHECK_CTX(c); CHECK_SEQ(c, seq);
   if(!n) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr count");
-  if(level < 0) level = c->params.maxTestLevel;
-  if(level >= c->L) return fail(c, BPVO_ERR_INVALID_ARG, "bad level");
-  *n = 0;
-  if(!c->seqs.empty()) {
-    const FrameSlot& ref = c->frames[c->seqs[seq].ref];
-    if(ref.has_template) *n = ref.n_host[level];
-  }
-  return BPVO_OK;
+  return vo_num_points_at_level(c, seq_state(c, seq), level, n);
 }
 int bpvo_hip_seq_get_point_cloud(bpvo_hip_ctx* c, int seq, bpvo_hip_point_with_info* pts, size_t* n, float pose[16])
 {
   CHECK_CTX(c); CHECK_SEQ(c, seq);
-  const size_t cnt = c->seqs.empty() ? 0 : c->seqs[seq].cloud_n;
-  if(n) *n = cnt;
-  if(pts && cnt) {
-    (void) hipSetDevice(c->device);
-    const size_t off = (size_t) seq * (size_t) c->geom[c->params.maxTestLevel].cap;
-    HIP_CK(c, hipMemcpyAsync(pts, c->d_seq_cloud + off, cnt * sizeof(bpvo_hip_point_with_info), hipMemcpyDeviceToHost, c->stream));
-    HIP_CK(c, hipStreamSynchronize(c->stream));
-  }
-  if(pose) {
-    const M44 P = c->seqs.empty() ? m44_identity() : c->seqs[seq].cloud_pose;
-    std::memcpy(pose, P.m, 64);
-  }
-  return BPVO_OK;
+  return vo_get_point_cloud(c, seq_state(c, seq), c->d_seq_cloud + (size_t) seq * (size_t) c->geom[c->params.maxTestLevel].cap, pts, n, pose);
 }
 int bpvo_hip_seq_trajectory_size(bpvo_hip_ctx* c, int seq, int* n)
 {
   CHECK_CTX(c); CHECK_SEQ(c, seq);
   if(!n) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr count");
-  *n = c->seqs.empty() ? 0 : (int) c->seqs[seq].trajectory.size();
+  *n = vo_trajectory_size(seq_state(c, seq));
   return BPVO_OK;
 }
 int bpvo_hip_seq_get_trajectory(bpvo_hip_ctx* c, int seq, float* poses)
 {
   CHECK_CTX(c); CHECK_SEQ(c, seq);
-  if(c->seqs.empty()) return BPVO_OK;
-  const std::vector<M44>& t = c->seqs[seq].trajectory;
-  if(!poses && !t.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr poses");
-  for(size_t i = 0; i < t.size(); ++i) std::memcpy(poses + 16 * i, t[i].m, 64);
+  if(!poses && vo_trajectory_size(seq_state(c, seq)) > 0) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr poses");
+  vo_get_trajectory(seq_state(c, seq), poses);
   return BPVO_OK;
 }
 
@@ -950,7 +855,7 @@ static int camera_geometry(const bpvo_hip_camera& cam, const bpvo_hip_params& p,
     return BPVO_ERR_INVALID_ARG;
   }
   if(auto_levels) {      // bpvo/vo.cc:101-105, as bpvo_hip_create counts them
-    const int own = 1 + (int) std::round(std::log2(std::min(cam.rows, cam.cols) / (double) p.minImageDimensionForPyramid));
+    const int own = auto_pyramid_levels(cam.rows, cam.cols, p.minImageDimensionForPyramid);
     if(own != L) {
       *why = "camera " + std::to_string(cam.cols) + "x" + std::to_string(cam.rows) + ": its automatic pyramid has " + std::to_string(own) +
              " levels, the context's " + std::to_string(L);
@@ -989,7 +894,7 @@ int bpvo_hip_create_sequences(bpvo_hip_ctx** out, int n_sequences, const bpvo_hi
   for(int s = 0; s < n_sequences; ++s) { rows = std::max(rows, cams[s].rows); cols = std::max(cols, cams[s].cols); }
   const bool auto_levels = p->numPyramidLevels <= 0;
   int L = p->numPyramidLevels;
-  if(auto_levels && rows >= 8 && cols >= 8) L = 1 + (int) std::round(std::log2(std::min(rows, cols) / (double) p->minImageDimensionForPyramid));
+  if(auto_levels && rows >= 8 && cols >= 8) L = auto_pyramid_levels(rows, cols, p->minImageDimensionForPyramid);
   if(L < 1 || L > kMaxLevels) {
     g_create_error = "numPyramidLevels out of range (1..8)";
     return BPVO_ERR_UNSUPPORTED;
@@ -1016,16 +921,13 @@ int bpvo_hip_seq_set_camera(bpvo_hip_ctx* c, int seq, const bpvo_hip_camera* cam
   CHECK_CTX(c); CHECK_SEQ(c, seq);
   if(!cam) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr camera");
   if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: per-sequence cameras serve bpvo_hip_add_frames");
-  for(int k = 0; k < 3; ++k)
-    if(c->frames[3 * seq + k].has_data || c->frames[3 * seq + k].has_template)
-      return seq_fail(c, BPVO_ERR_INVALID_ARG, seq, "holds frames: its camera changes only while it is fresh or after bpvo_hip_seq_reset");
+  int rc = seq_is_fresh(c, seq, "camera changes");
+  if(rc) return rc;
   LevelGeom g[kMaxLevels];
   std::string why;
-  int rc = camera_geometry(*cam, c->params, c->auto_levels, c->L, g, &why);
+  rc = camera_geometry(*cam, c->params, c->auto_levels, c->L, g, &why);
   if(rc) return seq_fail(c, rc, seq, why.c_str());
-  if(cam->rows > c->rows || cam->cols > c->cols)
-    return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, ("camera " + std::to_string(cam->cols) + "x" + std::to_string(cam->rows) + " larger than the context's " +
-                                                   std::to_string(c->cols) + "x" + std::to_string(c->rows)).c_str());
+  if(cam->rows > c->rows || cam->cols > c->cols) return camera_too_large(c, seq, cam->rows, cam->cols);
   for(int l = 0; l < c->L; ++l)
     if(g[l].cap > c->geom[l].cap)
       return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, ("camera needs a template capacity of " + std::to_string(g[l].cap) + " points at level " + std::to_string(l) +
@@ -1063,7 +965,7 @@ static bool structural_difference(const bpvo_hip_ctx* c, int seq, const bpvo_hip
   {
     // numPyramidLevels after resolution (bpvo/vo.cc:101-105, for the sequence's own image size, as bpvo_hip_create counts them)
     const LevelGeom& g = slot_geom(c, c->frames[3 * seq], 0);
-    const int own = p.numPyramidLevels > 0 ? p.numPyramidLevels : 1 + (int) std::round(std::log2(std::min(g.rows, g.cols) / (double) p.minImageDimensionForPyramid));
+    const int own = p.numPyramidLevels > 0 ? p.numPyramidLevels : auto_pyramid_levels(g.rows, g.cols, p.minImageDimensionForPyramid);
     if(own != c->L) return differs("numPyramidLevels", std::to_string(own), std::to_string(c->L));
   }
   SP_INT(descriptor);
@@ -1083,9 +985,8 @@ int bpvo_hip_seq_set_params(bpvo_hip_ctx* c, int seq, const bpvo_hip_params* p)
   CHECK_CTX(c); CHECK_SEQ(c, seq);
   if(!p) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr parameters");
   if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: per-sequence parameters serve bpvo_hip_add_frames");
-  for(int k = 0; k < 3; ++k)
-    if(c->frames[3 * seq + k].has_data || c->frames[3 * seq + k].has_template)
-      return seq_fail(c, BPVO_ERR_INVALID_ARG, seq, "holds frames: its parameters change only while it is fresh or after bpvo_hip_seq_reset");
+  const int rc = seq_is_fresh(c, seq, "parameters change");
+  if(rc) return rc;
   std::string why;
   if(structural_difference(c, seq, *p, &why)) return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, why.c_str());
   if(p->lossFunction != BPVO_LOSS_HUBER && p->lossFunction != BPVO_LOSS_TUKEY && p->lossFunction != BPVO_LOSS_L2)

@@ -1,0 +1,152 @@
+// libbpvo_hip, host side: the state machine of VisualOdometry::addFrame (reference: bpvo/vo.cc:125-224) for bpvo_hip_add_frame and for every
+// sequence of bpvo_hip_add_frames.  No HIP header: the drivers (vo.hip) queue the GPU work and keep the frame slots' flags; every decision and
+// every change of a SeqState is made here, once, for both (tests/test_vo_state_cpu.py compiles this header with a plain C++ compiler).
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "../../include/bpvo_hip/c_api.h"
+#include "device_math.h"
+
+namespace bpvo_hip_host {
+using namespace bpvo_hip;
+
+// The VisualOdometry state of bpvo/vo.cc:45-52: bpvo_hip_ctx::vo for bpvo_hip_add_frame (frame slots 0 .. 2, workspace 0), bpvo_hip_ctx::seqs[s]
+// for sequence s of bpvo_hip_add_frames (frame slots 3s .. 3s+2, workspace s)
+struct SeqState {
+  int ref = 0, cur = 1, prev = 2;   // slot roles
+  M44 T_kf;
+  std::vector<M44> trajectory;
+  size_t cloud_n = 0;               // the point cloud of the last Result: bpvo_hip_ctx::d_cloud, or records [s * cap, s * cap + cloud_n) of d_seq_cloud
+  M44 cloud_pose;
+  // the sequence's algorithm parameters (bpvo_hip_seq_set_params; the context's until then) — they outlive bpvo_hip_seq_reset, like its camera.
+  // own_params: they differ from the context's in a field the library reads (only then do the sequence's jobs and decisions take them from here)
+  bpvo_hip_params params;
+  bool own_params = false;
+};
+// a fresh VisualOdometry on slots first_slot .. first_slot + 2 (the slots' flags are the caller's)
+inline void vo_reset(SeqState& q, int first_slot)
+{
+  q.ref = first_slot; q.cur = first_slot + 1; q.prev = first_slot + 2;
+  q.T_kf = m44_identity();
+  q.trajectory.clear();
+  q.cloud_n = 0;
+  q.cloud_pose = m44_identity();
+}
+
+// what addFrame hands back before it knows anything
+inline void vo_init_result(int numLevels, bpvo_hip_result* ret)
+{
+  const M44 I = m44_identity();
+  std::memset(ret, 0, sizeof(*ret));
+  std::memcpy(ret->pose, I.m, 64);
+  for(int i = 0; i < 36; ++i) ret->covariance[i] = (i % 7 == 0) ? 1.0f : 0.0f;   // Q16
+  ret->numLevels = numLevels;
+  for(int l = 0; l < BPVO_HIP_MAX_LEVELS; ++l) ret->optimizerStatistics[l] = bpvo_hip_stats{0, -1.0f, -1.0f, BPVO_STATUS_SOLVER_ERROR};
+  ret->isKeyFrame = 0;
+  ret->keyFramingReason = BPVO_KF_NO_KEYFRAMING;
+  ret->hasPointCloud = 0;
+}
+inline void vo_begin_frame(SeqState& q, int numLevels, bpvo_hip_result* ret)      // (the point cloud belongs to one Result: bpvo/types.h:549-563)
+{
+  vo_init_result(numLevels, ret);
+  q.cloud_n = 0;
+  q.cloud_pose = m44_identity();
+}
+inline void trajectory_push(std::vector<M44>& trajectory, const M44& T)   // Trajectory::push_back + InvertPose (bpvo/trajectory.cc:30-50)
+{
+  M44 Ti = m44_identity();
+  for(int i = 0; i < 3; ++i)
+    for(int j = 0; j < 3; ++j) Ti.m[i * 4 + j] = T.m[j * 4 + i];
+  for(int i = 0; i < 3; ++i) {
+    float s = Ti.m[0 * 4 + i] * T.m[3];
+    s += Ti.m[1 * 4 + i] * T.m[7];
+    s += Ti.m[2 * 4 + i] * T.m[11];
+    Ti.m[i * 4 + 3] = -s;
+  }
+  if(!trajectory.empty()) trajectory.push_back(m44_mul(trajectory.back(), Ti));
+  else trajectory.push_back(Ti);
+}
+
+// ---- the key-frame decision (bpvo/vo.cc:199-224).  Its translation and rotation criteria: BPVO_KF_LARGE_TRANSLATION, BPVO_KF_LARGE_ROTATION, or
+// BPVO_KF_NO_KEYFRAMING when the fraction of good points decides.  Host floats (asin, sqrt) on purpose.
+inline int keyframe_by_motion(const bpvo_hip_params& p, const M44& pose)
+{
+  const float t_norm = pose.m[3] * pose.m[3] + pose.m[7] * pose.m[7] + pose.m[11] * pose.m[11];
+  if(t_norm > p.minTranslationMagToKeyFrame * p.minTranslationMagToKeyFrame) return BPVO_KF_LARGE_TRANSLATION;
+  // math::RotationMatrixToEulerAngles (bpvo/math_utils.h:203-216); compared in radians (Q17)
+  const float R00 = pose.m[0], R10 = pose.m[4], R20 = pose.m[8], R21 = pose.m[9];
+  const float eta = (float) (1.0 / (std::sqrt(R00 * R00 + R10 * R10)));
+  const float rz = std::asin(eta * R10), ry = std::asin(-R20), rx = std::asin(eta * R21);
+  const float r_norm = rx * rx + ry * ry + rz * rz;
+  if(r_norm > p.minRotationMagToKeyFrame * p.minRotationMagToKeyFrame) return BPVO_KF_LARGE_ROTATION;
+  return BPVO_KF_NO_KEYFRAMING;
+}
+// the fraction of good points from their count over the n_points x C residuals of the last linearisation (vo_pose_estimator.cc:105-106)
+inline float vo_fraction_good(unsigned good_count, int n_points, int C) { return good_count / static_cast<float>((size_t) n_points * C); }
+// The decision: the motion, then the fraction of good points — read only where the motion leaves the decision to it (bpvo_hip_add_frame
+// fetches its count only then; bpvo_hip_add_frames has every sequence's from one launch)
+inline int vo_keyframe_reason(const bpvo_hip_params& p, const M44& T_est, float fraction_good)
+{
+  const int reason = keyframe_by_motion(p, T_est);
+  if(reason != BPVO_KF_NO_KEYFRAMING) return reason;
+  return (fraction_good < p.maxFractionOfGoodPointsToKeyFrame) ? BPVO_KF_SMALL_FRAC_GOOD : BPVO_KF_NO_KEYFRAMING;
+}
+inline bool vo_decide(const bpvo_hip_params& p, const M44& T_est, float fraction_good, bpvo_hip_result* ret)
+{
+  ret->keyFramingReason = vo_keyframe_reason(p, T_est, fraction_good);
+  ret->isKeyFrame = ret->keyFramingReason != BPVO_KF_NO_KEYFRAMING;
+  return ret->isKeyFrame != 0;
+}
+
+// ---- the transitions, one per branch of bpvo/vo.cc:133-188.  First frame (vo.cc:133-139): the frame just read becomes the key frame.  Returns
+// the slot whose template the caller builds; once that is queued, vo_first_frame_done.
+inline int vo_first_frame(SeqState& q) { std::swap(q.ref, q.cur); return q.ref; }
+inline void vo_first_frame_done(SeqState& q, bpvo_hip_result* ret)
+{
+  trajectory_push(q.trajectory, q.T_kf);
+  ret->isKeyFrame = 1;
+  ret->keyFramingReason = BPVO_KF_FIRST_FRAME;
+}
+// Key frame (vo.cc:157-188), after its point cloud of cloud_points records has been queued: the slot rotation.
+//   template_slot: the new key frame, whose template the caller builds
+//   clear_slot:    -1, or the slot whose has_data / has_template flags the caller clears (the old key frame; vo.cc:176 _prev_frame->clear())
+//   reestimate:    the previous frame had data: it is the new key frame, and the caller estimates (template_slot, q.cur) again from the identity
+struct KeyFrameSlots { int template_slot, clear_slot; bool reestimate; };
+inline KeyFrameSlots vo_keyframe(SeqState& q, bool prev_has_data, size_t cloud_points, bpvo_hip_result* ret)
+{
+  q.cloud_n = cloud_points;
+  ret->hasPointCloud = 1;
+  if(!prev_has_data) {               // vo.cc:161-173
+    std::swap(q.cur, q.ref);
+    return KeyFrameSlots{q.ref, -1, false};
+  }
+  std::swap(q.prev, q.ref);          // vo.cc:174-188
+  return KeyFrameSlots{q.ref, q.prev, true};
+}
+// The end of every addFrame but the first: the slot advance of a frame that is no key frame (vo.cc:149-155), the pose, T_kf, the trajectory and
+// the cloud's pose.  T_est: the estimate against the key frame the call began with; T_again: null, or the estimate against the new key frame
+// (KeyFrameSlots::reestimate).
+inline void vo_finish(SeqState& q, const M44& T_est, const M44* T_again, bpvo_hip_result* ret)
+{
+  M44 pose;
+  if(!ret->isKeyFrame) {
+    std::swap(q.prev, q.cur);
+    pose = m44_mul(T_est, m44_inverse(q.T_kf));
+    q.T_kf = T_est;
+  } else if(!T_again) {
+    pose = m44_mul(T_est, m44_inverse(q.T_kf));
+    q.T_kf = m44_identity();
+  } else {
+    pose = *T_again;
+    q.T_kf = *T_again;
+  }
+  std::memcpy(ret->pose, pose.m, 64);
+  trajectory_push(q.trajectory, pose);
+  if(ret->hasPointCloud) q.cloud_pose = q.trajectory.back();
+}
+
+}  // namespace bpvo_hip_host

@@ -139,6 +139,36 @@ def test_a_sweep_equals_contexts_of_its_own(hip, desc, mode):
         m.ctx.close()
 
 
+# The good-point count of a table of jobs and the point clouds for the plain layouts besides C = 1 and for wide descriptors, each sequence with a
+# loss and a threshold of its own: the sweeps above run bit-planes (tiles, C = 8) and intensity (C = 1) only.  Small frames, three levels.
+COUNT_FORMS = {"gradient": {}, "fields2": {}, "centraldiff": dict(centralDifferenceRadius=4)}      # C = 3 and 10 (plain), 80 (wide)
+COUNT_SETS = [
+    dict(lossFunction="tukey", **KF),
+    dict(lossFunction="huber", minTranslationMagToKeyFrame=10, minRotationMagToKeyFrame=2.5, maxFractionOfGoodPointsToKeyFrame=0.9, goodPointThreshold=0.9),
+    dict(lossFunction="l2", **KF2),
+]
+
+
+@pytest.mark.parametrize("desc", sorted(COUNT_FORMS))
+def test_count_and_cloud_forms_with_parameters_of_their_own(hip, desc):
+    """The CPU oracle on these inputs, for all three descriptors: set 1 key-frames by translation at frames 3 and 5 (frame 3: a key frame with
+    a second estimate), set 2 by the fraction of good points at every frame (frame 1: a key frame without a previous frame; Huber weights
+    against 0.9), set 3 (L2: every weight is 1) never after the first frame."""
+    rows, cols = 120, 160
+    frames, K, b = sweep_frames(rows, cols, 6)
+    base = make_params(hip, descriptor=desc, loss="tukey", levels=3, **KF, **COUNT_FORMS[desc])
+    params = [params_of(hip, base, s, frames) for s in COUNT_SETS]
+    singles = singles_of(hip, K, b, rows, cols, params, frames)
+    kfs = [[f["res"]["keyFramingReason"] for f in o[0]] for o in singles]
+    print("key-framing reasons:", kfs)
+    assert all(k[0] == capi.KF_FIRST_FRAME for k in kfs), kfs
+    assert capi.KF_LARGE_TRANSLATION in kfs[0] and capi.KF_SMALL_FRAC_GOOD in kfs[1], kfs
+    assert all(r == capi.KF_NO_KEYFRAMING for r in kfs[2][1:]), kfs
+    m = run_sweep(hip, K, b, rows, cols, base, params, frames)
+    check(m, singles)
+    m.ctx.close()
+
+
 def test_an_empty_template_names_its_sequence_and_leaves_the_others(hip):
     """bit-planes with conf/kitti_bitplanes.cfg's minSaliency of 2.5, which no bit-planes saliency reaches: the first frame is accepted
     (vo.cc:133-139), the estimate against its empty template is refused before any sequence changes, and the others go on as if it had never
