@@ -80,6 +80,7 @@ void carve_frame_tmpl(bpvo_hip_ctx* c, FrameSlot& f, unsigned char* base, size_t
     f.flag[l] = (uint8_t*) cv.take<unsigned long long>((std::max(g.npix, nwords * 8) + 7) / 8);
     f.blk_count[l] = cv.take<int>(std::max((size_t) g.nblk, nwords));
     f.pts[l] = cv.take<float4>(g.cap);
+    f.ptc[l] = cv.take<float2>(g.cap);
     f.inds[l] = cv.take<int>(g.cap);
     f.pix[l] = cv.take<float>((size_t) g.cap * c->C);
     f.grad[l] = cv.take<float>((size_t) g.cap * c->C * 2);
@@ -118,6 +119,7 @@ FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l)
   j.n_out = f.n_dev ? f.n_dev + l : nullptr;
   j.disp = f.disp;
   j.pts = f.pts[l];
+  j.ptc = f.ptc[l];
   j.inds = f.inds[l];
   j.pix = f.pix[l];
   j.grad = f.grad[l];
@@ -143,6 +145,7 @@ PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l)
   PairJob j;
   std::memset(&j, 0, sizeof(j));
   j.pts = fr.pts[l];
+  j.ptc = fr.ptc[l];
   j.pix = fr.pix[l];
   j.grad = fr.grad[l];
   j.nrm = fr.nrm + 4 * l;
@@ -151,6 +154,7 @@ PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l)
   j.rows = g.rows; j.cols = g.cols;
   std::memcpy(j.K, g.K, sizeof(j.K));
   j.b = g.b;
+  j.f_inv[0] = 1.0f / g.K[0]; j.f_inv[1] = 1.0f / g.K[4];
   j.dspace = c->dspace;
   j.r = c->ws[ws].r;
   j.valid = c->ws[ws].valid;
@@ -329,6 +333,7 @@ const std::vector<OptionDef>& option_table()
     OPT_INT("upload_workers", up_workers, 0, 32),
     OPT_INT("keep_current_disparity", keep_current_disparity, 0, 1),
     OPT_INT("lazy_template_descriptor", lazy_template, 0, 1),
+    OPT_INT("points_from_compact_stream", points_from_compact, 0, 1),
     OptionDef{"tapcache_max_density", 0.0, 1e9, [](bpvo_hip_ctx* c) { return c->tapcache_max_density; },
               [](bpvo_hip_ctx* c, double v) { c->tapcache_max_density = v; return BPVO_OK; }},
     OptionDef{"upload_plan_first", 0.0, 0.9, [](bpvo_hip_ctx* c) { return c->up_plan[0]; },

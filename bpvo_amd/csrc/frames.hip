@@ -485,6 +485,16 @@ int bpvo_hip_num_points(bpvo_hip_ctx* c, int slot, int level, int* n_out) { TMPL
 int bpvo_hip_get_points(bpvo_hip_ctx* c, int slot, int level, float* xyzw)
 {
   TMPL(c, slot, level);
+  if(n && c->points_from_compact) {      // debug: the points as the Gauss-Newton kernels rebuild them from the 8-byte records (load_point)
+    float4* d_out = nullptr;
+    HIP_CK(c, hipMalloc((void**) &d_out, sizeof(float4) * n));
+    launch_rebuild_points(c->stream, make_pair_job(c, 0, slot, slot, level), d_out);
+    hipError_t e = hipMemcpyAsync(xyzw, d_out, sizeof(float4) * n, hipMemcpyDeviceToHost, c->stream);
+    if(e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void) hipFree(d_out);
+    HIP_CK(c, e);
+    return BPVO_OK;
+  }
   if(n) HIP_CK(c, hipMemcpyAsync(xyzw, f.pts[level], sizeof(float4) * n, hipMemcpyDeviceToHost, c->stream));
   HIP_CK(c, hipStreamSynchronize(c->stream));
   return BPVO_OK;

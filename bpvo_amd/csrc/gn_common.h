@@ -94,6 +94,20 @@ __device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned x)
 }
 __device__ __forceinline__ unsigned wave_sum_u32(unsigned x) { return (unsigned) __builtin_amdgcn_readlane((int) wave_incl_scan_u32(x), 63); }
 
+// The template point of the per-iteration kernels: rebuilt from its 8-byte record (PairJob::ptc: Z or d, x | y << 16) with exactly the
+// operations and operand order of the selection kernels that stored the float4 (kernels_frame.hip: X = ((float) x - cx) * Z * (1.0f / fx),
+// Y likewise; DisparitySpaceWarp: (x - cx, y - cy, d)), so it IS PairJob::pts[i], bit for bit — no multiply feeds an add, nothing to
+// contract — for half the bytes.  cx, cy and the two reciprocals (PairJob::f_inv) are fields of the job: scalar loads, scalar registers.
+template <bool NT>
+__device__ __forceinline__ float4 load_point(const PairJob& j, int i)
+{
+  const float2 c = load_v2<NT>(j.ptc + i);
+  const unsigned xy = __float_as_uint(c.y);
+  const float xs = (float) (int) (xy & 0xffffu) - j.K[2], ys = (float) (int) (xy >> 16) - j.K[5];
+  if(j.dspace) return make_float4(xs, ys, c.x, 1.0f);
+  return make_float4(xs * c.x * j.f_inv[0], ys * c.x * j.f_inv[1], c.x, 1.0f);
+}
+
 // workspace of a workgroup: k-th entry of the active list, or k itself without a list
 __device__ __forceinline__ int active_workspace(const ActiveSet& a, int k) { return a.list ? a.list[k] : k; }
 

@@ -58,7 +58,8 @@ __device__ __forceinline__ void irls_tile(const PairJob& j, const GNState* __res
 {
   // Fused path (C = 8): the robust scale is frozen for the rest of the level, so nothing separates the residuals from
   // their weights any more — they are recomputed here exactly as warp_residual does (same warp_point, same tap cache) and
-  // never written: the r write + read, the second point read and the valid byte (82 of 341 B per point and iteration)
+  // never written: the r write + read, the second point read and the valid byte (74 of the 310 B a plain point-iteration moves; the
+  // point is an 8-byte record in both kernels, load_point)
   // disappear.  Same values, same accumulation order as the two-kernel form.
   constexpr bool fused = FUSED && (C == 8);
   float P[12];
@@ -83,7 +84,7 @@ __device__ __forceinline__ void irls_tile(const PairJob& j, const GNState* __res
   for(int i = p_begin + vtid; i < p_end; i += GN_BLOCK) {
     float rr[C], Ix[C], Iy[C];
     float v;
-    float4 Pt;      // fused: the point as warp_point loaded it (ONE request per point)
+    float4 Pt;      // fused: the point as warp_point rebuilt it (ONE request, one rebuild per point)
     if constexpr(fused) {
       bool hit;
       v = warp_point<8, false, true>(j, P, i, true, rr, hit, &Pt) ? 1.0f : 0.0f;
@@ -92,7 +93,7 @@ __device__ __forceinline__ void irls_tile(const PairJob& j, const GNState* __res
       v = (float) j.valid[i];
     }
     acc[28] += v;
-    // per point: 16 B point + 2*C gradient floats + C residuals (all tiled / coalesced), ALL issued before the first use
+    // per point: the 8 B point record + 2*C gradient floats + C residuals (all tiled / coalesced), ALL issued before the first use
     // (7 independent 16-byte loads in flight per lane for C = 8).
     //
     // Rank-2 structure: every channel's 1x6 Jacobian row at a point is J_c = Ix_c * A + Iy_c * B with A, B depending on
@@ -102,7 +103,7 @@ __device__ __forceinline__ void irls_tile(const PairJob& j, const GNState* __res
     // Per (point, channel) that is 6 multiply-adds instead of the 27 of the reference's rankUpdatePoint; the 6x6 outer
     // products are formed once per point.  Algebraically identical, rounding differs at the 1e-7 level like any other
     // summation order (H, G are tolerance-compared).
-    if constexpr(!fused) Pt = load_stream(j.pts + i);
+    if constexpr(!fused) Pt = load_point<true>(j, i);
     if constexpr(C == 8) {
       const float4* qr = reinterpret_cast<const float4*>(j.r.get());
       const float4* qg = reinterpret_cast<const float4*>(j.grad.get());
@@ -206,6 +207,8 @@ struct IrlsPointLat {
 template <bool FUSED>
 __device__ __forceinline__ void irls_lat_load(const PairJob& j, int i, IrlsPointLat& d)
 {
+  // (the float4 stream, not the compact record load_point rebuilds: these launches are latency-bound on a working set the L2s hold — the bytes
+  // buy nothing — and the team kernel, at 256 registers, pays the rebuild's temporaries with 16 more bytes of scratch per lane)
   d.Pt = load_v4<false>(j.pts + i);
   const float4* qg = reinterpret_cast<const float4*>(j.grad.get());
   if constexpr(FUSED) {

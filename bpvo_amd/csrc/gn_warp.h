@@ -52,7 +52,7 @@ __device__ __forceinline__ void dspace_matrix(const PairJob& j, const float* __r
 // `in_block` gates the tap-cache update (lanes past the end of a block redo the last point, loads only).  Returns valid.
 // HALF (C = 8, f64 formulation): the taps are fetched and consumed in two groups of four channels, which halves the
 // registers they occupy — for the fused path of irls_reduce, where the 29 accumulators are live as well.
-// `X_out` (optional): receives the point as loaded here, for a caller that needs it as well — the fused path's Jacobian — so that it is
+// `X_out` (optional): receives the point as rebuilt here, for a caller that needs it as well — the fused path's Jacobian — so that it is
 // requested from memory once per point, not twice (streaming loads: the second request went out to HBM again, 3.8 % of irls_reduce_both's bytes).
 template <int C, bool FAST, bool HALF = false, bool NT = true>
 __device__ __forceinline__ bool warp_point(const PairJob& j, const float (&P)[12], int i, bool in_block, float (&res)[C], bool& cache_hit,
@@ -60,7 +60,7 @@ __device__ __forceinline__ bool warp_point(const PairJob& j, const float (&P)[12
 {
   cache_hit = false;
   const int W = j.cols, R = j.rows;
-  const float4 X = load_v4<NT>(j.pts + i);
+  const float4 X = load_point<NT>(j, i);
   if(X_out) *X_out = X;
   // C = 1: the launches are short and latency-bound, so the key, the cached taps and the template pixel are requested
   // together with the point instead of after the projection (16 speculative bytes per point; for C = 8 the same

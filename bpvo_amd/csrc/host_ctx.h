@@ -70,6 +70,7 @@ struct FrameSlot {
   uint8_t* flag[kMaxLevels] = {};
   int* blk_count[kMaxLevels] = {};
   float4* pts[kMaxLevels] = {};
+  float2* ptc[kMaxLevels] = {};   // compact point records (PairJob::ptc)
   int* inds[kMaxLevels] = {};
   float* pix[kMaxLevels] = {};
   float* grad[kMaxLevels] = {};
@@ -306,6 +307,7 @@ struct bpvo_hip_ctx {
   // host batches on two lanes: the pairs are cut into a SMALL first group (lane 0 starts its Gauss-Newton stage while most of the batch
   // is still crossing the bus), a large second one for lane 1, and the rest for lane 0 again (host_groups_plan); fractions of the batch
   double up_plan[2] = {0.19, 0.50};      // options "upload_plan_first" / "upload_plan_second"; first = 0: two equal groups.  Measured: profiles/r03_host_buffers_plan.txt
+  int points_from_compact = 0;           // option "points_from_compact_stream" (debug): bpvo_hip_get_points returns load_point's rebuilt points
   int lazy_template = 1;                 // option "lazy_template_descriptor": the template frames (A) of a pair batch keep census bytes + channel 0 at the NMS
                                          // levels instead of 32-byte records nobody reads (bit-planes, CD3); template_build forms its stencils from the census
   int keep_current_disparity = 0;        // option: pair batches store the disparity of the CURRENT frames (B) too, so that a B slot can be made

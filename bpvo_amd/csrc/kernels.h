@@ -219,6 +219,7 @@ int  gn_partials_entries(int cap, int C);   // kPartialStride-float entries of a
 void launch_weights(hipStream_t s, const PairJob* job, int n, int C, int loss, float* w_out /*[n][C]*/);
 void launch_count_good(hipStream_t s, const PairJob* job, int n, int C, int loss, float thr, unsigned int* count);
 // the key frame's point cloud (bpvo/vo.cc:250-281) as 32-byte records on the device; K: the level's intrinsics, img: the key frame's level-0 image
+void launch_rebuild_points(hipStream_t s, const PairJob& job, float4* out);      // out[i] = load_point(job, i), i < job.n (a debug accessor)
 void launch_point_cloud(hipStream_t s, const PairJob* job, int n, int C, int loss, const uint8_t* img, int rows, int cols, const float K[9], int dspace,
                         bpvo_hip_point_with_info* out);
 // the same two for a table of jobs in one launch each (bpvo_hip_add_frames): counts[k] (zeroed by the caller) of entry k; max_n: the most points of an entry

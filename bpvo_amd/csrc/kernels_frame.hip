@@ -831,6 +831,7 @@ __global__ __launch_bounds__(256) void select_write_kernel(const FrameJob* jobs)
     const float Y = ((float) y - cy) * Z * (1.0f / fy);
     // DisparitySpaceWarp::makePoint (bpvo/disparity_space_warp.h:31-34): (x - cx, y - cy, d, 1)
     j.pts[r] = j.dspace ? make_float4((float) x - cx, (float) y - cy, d, 1.0f) : make_float4(X, Y, Z, 1.0f);
+    j.ptc[r] = compact_point(j.dspace ? d : Z, x, y);      // what the Gauss-Newton kernels stream: load_point rebuilds the float4 from it
     j.inds[r] = p;
   }
 }
@@ -1057,6 +1058,7 @@ __global__ __launch_bounds__(256) void select_words_write_kernel(const FrameJob*
     const float Y = ((float) y - cy) * Z * (1.0f / fy);
     // DisparitySpaceWarp::makePoint (bpvo/disparity_space_warp.h:31-34): (x - cx, y - cy, d, 1)
     j.pts[r] = j.dspace ? make_float4((float) x - cx, (float) y - cy, d, 1.0f) : make_float4(X, Y, Z, 1.0f);
+    j.ptc[r] = compact_point(j.dspace ? d : Z, x, y);      // what the Gauss-Newton kernels stream: load_point rebuilds the float4 from it
     j.inds[r] = y * W + x;
   }
 }

@@ -121,7 +121,7 @@ __global__ __launch_bounds__(K6_BLOCK) void warp_residual_interp_kernel(const Pa
   const bool in_block = i_raw < n;
   const int i = in_block ? i_raw : n - 1;
   const int W = j.cols, R = j.rows;
-  const float4 X = j.pts[i];
+  const float4 X = load_point<false>(j, i);
   constexpr bool two_tap = interp == BPVO_INTERP_COSINE;
   constexpr int border_lo = two_tap ? 0 : 1, border_hi = two_tap ? 1 : 3;
   int xi = 0, yi = 0;
@@ -848,6 +848,17 @@ void launch_point_cloud(hipStream_t s, const PairJob* job, int n, int C, int los
   for(int k = 0; k < 9; ++k) a.K[k] = K[k];
   a.rows = rows; a.cols = cols; a.dspace = dspace; a.C = C; a.loss = loss;
   hipLaunchKernelGGL(point_cloud_kernel, dim3((n + 255) / 256), dim3(256), 0, s, job, img, a, out);
+}
+// debug option "points_from_compact_stream": the points of a template level as the Gauss-Newton kernels see them — load_point over the compact records
+__global__ __launch_bounds__(256) void rebuild_points_kernel(PairJob j, float4* __restrict__ out)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if(i < j.n) out[i] = load_point<false>(j, i);
+}
+void launch_rebuild_points(hipStream_t s, const PairJob& job, float4* out)
+{
+  if(job.n <= 0) return;
+  hipLaunchKernelGGL(rebuild_points_kernel, dim3((job.n + 255) / 256), dim3(256), 0, s, job, out);
 }
 void launch_count_good(hipStream_t s, const PairJob* job, int n, int C, int loss, float thr, unsigned int* count)
 {

@@ -142,7 +142,7 @@ __device__ __attribute__((noinline)) void pk_warp_phase_staged(const PairJob* __
       s[u].in_block = s[u].has && i_raw < n;
       const int i = s[u].in_block ? i_raw : n - 1;
       s[u].i = i;
-      s[u].X = load_v4<NT>(j.pts + i);
+      s[u].X = load_v4<NT>(j.pts + i);      // (the float4 stream: with load_point's rebuild this function, at 248 registers, spills two more — see irls_lat_load)
       s[u].px[0] = load_v4<NT>(p0 + tile_index<2>(i, 0));
       s[u].px[1] = load_v4<NT>(p0 + tile_index<2>(i, 1));
       if(cached) {

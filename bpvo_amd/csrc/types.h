@@ -134,6 +134,19 @@ __device__ __forceinline__ void store_stream(float4* p, const float4& a)
   bpvo_v4f v; v.x = a.x; v.y = a.y; v.z = a.z; v.w = a.w;
   __builtin_nontemporal_store(v, reinterpret_cast<bpvo_v4f*>(p));
 }
+// The compact point record (PairJob::ptc): Z (DisparitySpaceWarp: d) and the pixel the point was selected at, x | y << 16 as bits.  The
+// float4 point is a function of these and of the level's intrinsics alone (selection kernels, kernels_frame.hip), so the per-iteration
+// kernels stream 8 bytes per point instead of 16 and rebuild it (load_point, gn_common.h).  Image sizes above 65535 are refused at creation.
+__device__ __forceinline__ float2 compact_point(float z, int x, int y) { return make_float2(z, __uint_as_float((unsigned) x | ((unsigned) y << 16))); }
+typedef float bpvo_v2f __attribute__((ext_vector_type(2)));
+template <bool NT>
+__device__ __forceinline__ float2 load_v2(const float2* p)
+{
+  if constexpr(NT) {
+    const bpvo_v2f v = __builtin_nontemporal_load(reinterpret_cast<const bpvo_v2f*>(p));
+    return make_float2(v.x, v.y);
+  } else return *p;
+}
 // ... and the choice as a template parameter: launches that are latency-bound on a working set that fits the L2s (the persistent
 // single-pair kernel: 6 MB at the finest level of a 1241x376 pair) want the lines kept — non-temporal accesses there cost 8 % of an
 // estimatePose (profiles/r02_persistent_phases.txt)
@@ -166,7 +179,9 @@ static_assert(sizeof(GPtr<float>) == sizeof(float*) && alignof(GPtr<float>) == a
 // everything a kernel needs to know about one (workspace, level) linearisation
 struct PairJob {
   // template (reference frame) at this level
-  GPtr<const float4> pts;      // [N] (X,Y,Z,1)
+  GPtr<const float4> pts;      // [N] (X,Y,Z,1): what the once-per-template kernels and the checker read
+  GPtr<const float2> ptc;      // [N] the same points as 8-byte records {Z (dspace: d), bits of x | y << 16}: what the Gauss-Newton kernels
+                               // stream every iteration (load_point, gn_common.h, rebuilds the float4 bit for bit)
   GPtr<const float> pix;      // [N][C] tiled (see tile_index)
   GPtr<const float> grad;     // [N][2][C] tiled: (fx*Ix[c]), (fy*Iy[c]) — the 1x6 Jacobians are recomputed from these
   GPtr<const float> nrm;      // (s, c1, c2, c3) Hartley normalisation of the level
@@ -176,6 +191,7 @@ struct PairJob {
   int           rows, cols;
   float         K[9];     // level intrinsics (K * 0.5^l, K(2,2) = 1)
   float         b;        // level baseline (b * 2^l)
+  float         f_inv[2]; // 1.0f / fx, 1.0f / fy of the level: the reciprocals the selection kernels multiply with (IEEE divisions, host and device alike)
   int           dspace;   // 1: DisparitySpaceWarp (BPVO_WARP_DISPARITY_SPACE_F32): pts = (x - cx, y - cy, d, 1), grad = raw (Ix, Iy)
   // workspace
   GPtr<float> r;        // [N][C] residuals, tiled
@@ -231,6 +247,7 @@ struct FrameJob {
   GPtr<int> n_out;     // device: number of points kept (multiple of 16)
   GPtr<const float> disp;      // full-resolution disparity
   GPtr<float4> pts;
+  GPtr<float2> ptc;       // compact point records (PairJob::ptc)
   GPtr<int> inds;
   GPtr<float> pix;
   GPtr<float> grad;

@@ -509,6 +509,8 @@ int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* ctx, uint64_t out[4]);
  *                                      one pixel in ~18 is a template point there, template_build forms the records of its stencils from the census
  *                                      bytes (same operations, same bits).  The accessors and a later estimate with such a slot as the CURRENT frame
  *                                      rebuild the records on demand.
+ *   "points_from_compact_stream" 0     debug: bpvo_hip_get_points returns the points as the Gauss-Newton kernels rebuild them from the 8-byte records
+ *                                      they stream ({Z or d, x | y << 16}: DESIGN.md 3) instead of the stored (X, Y, Z, 1) — the same bits
  *   "reference_reduction"    0         VALIDATION MODE (the one option that changes numbers).  1: H, G and the squared residual norm of every
  *                                      linearisation are accumulated exactly as the reference's default (serial, WITH_TBB OFF) build does —
  *                                      f32, in index order over the channel-major arrays, w' = w * float(valid), (w' J_a) J_b, (w' r) J, (w' r) r,
