@@ -188,14 +188,15 @@ void launch_reference_reduce(hipStream_t s, const GNLaunch& g);   // what launch
 // mode 0: full PoseEstimatorBase::run step (solve, update, convergence); mode 1: linearize only (H, G, f_norm)
 // The limits and tolerances of the state machine are each workspace's own, PairJob::prm — here and in the persistent and team kernels below
 void launch_gn_step(hipStream_t s, const GNLaunch& g, int mode);
-// Persistent kernel for small groups: one launch runs a whole level of up to kPersistMaxWs workspaces (kernels_gn.hip).  ctl: two
+// Persistent kernel for small groups: one launch runs a whole level of up to kPersistMaxWs workspaces (kernels_gn_team.hip).  ctl: two
 // zeroed words {arrivals, abort}; after the launch ctl[1] != 0 says the kernel gave up (states untouched: rerun the chain).
 constexpr int kPersistMaxWs = 8;
 bool gn_persistent_serves(const GNLaunch& g);
 int  gn_persistent_grid(const GNLaunch& g, int max_grid);
 hipError_t launch_gn_persistent(hipStream_t s, const GNLaunch& g, unsigned* ctl, int grid, long long timeout_ticks);
-// Team-persistent kernel for small batches (kernels_gn.hip, gn_team_kernel): ONE launch runs every pair of the group through all its
-// pyramid levels; grid = team_size x n_teams workgroups, one per CU, all co-resident.  ctl: gn_team_ctl_words(n_teams) zeroed words;
+// Team-persistent kernels for small batches (kernels_gn_team.hip: gn_team_kernel, whose teams grow, with join_mode != 0; gn_team_fixed_kernel
+// with join_mode 0): ONE launch runs every pair of the group through all its pyramid levels; grid = team_size x n_teams (+ spare_workgroups)
+// workgroups, one per CU, all co-resident.  ctl: gn_team_ctl_words(n_teams) zeroed words;
 // after the launch ctl[1] != 0 says a team barrier gave up (rerun the group on the chain).
 struct GNTeamLaunch {
   const PairJob* jobs_all;   // device [levels][job_pitch]

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 
 #include "gn_common.h"
 #include "gn_warp.h"
@@ -54,9 +55,20 @@ __shared__ BracketLds pk_br[PK_VB];
 __shared__ IrlsPartLds pk_part[PK_VB];
 __shared__ int pk_ok;
 // this workgroup's place in its group: member index and number of workgroups that share a pair's chunks / tiles and meet at its
-// barriers (gn_persistent_kernel: blockIdx.x of gridDim.x; gn_team_kernel: see team_geometry)
+// barriers (gn_persistent_kernel: blockIdx.x of gridDim.x; the team kernels: team_geometry, and pk_take_seat / pk_admit once a team grows)
 __shared__ int pk_member, pk_nwg;
 __device__ __forceinline__ GNState* pk_st(int ws) { return reinterpret_cast<GNState*>(pk_state[ws]); }
+// a workspace's state: HBM -> this workgroup's LDS copy, and back (one copy; the others are identical)
+__device__ __forceinline__ void pk_state_load(int ws, const GNState* state)
+{
+  const uint32_t* g = reinterpret_cast<const uint32_t*>(state);
+  for(int i = threadIdx.x; i < kStateWords; i += PK_THREADS) pk_state[ws][i] = g[i];
+}
+__device__ __forceinline__ void pk_state_store(int ws, GNState* state)
+{
+  uint32_t* g = reinterpret_cast<uint32_t*>(state);
+  for(int i = threadIdx.x; i < kStateWords; i += PK_THREADS) g[i] = pk_state[ws][i];
+}
 
 // warp_residual (+ bracket step) of workspace ws: chunk c goes to workgroup c % nwg, virtual block (c / nwg) % PK_VB
 template <int C>
@@ -271,6 +283,18 @@ __device__ __forceinline__ void pk_irls_phase(const PairJob* __restrict__ jobs, 
     __syncthreads();
   }
 }
+// which form: with the fused path a workspace whose robust scale is frozen recomputes its residuals inside the reduction (asked after the
+// median: the chain's rule)
+template <int C, int LOSS>
+__device__ __forceinline__ void pk_irls(const PairJob* __restrict__ jobs, int ws, bool fuse, int pts_per_block, unsigned parity)
+{
+  if constexpr(C == 8) {
+    if(fuse && !(pk_st(ws)->delta_scale > 1e-6f)) pk_irls_phase<C, LOSS, true>(jobs, ws, pts_per_block, parity);
+    else pk_irls_phase<C, LOSS, false>(jobs, ws, pts_per_block, parity);
+  } else {
+    pk_irls_phase<C, LOSS, false>(jobs, ws, pts_per_block, parity);
+  }
+}
 
 // gn_step: wave w sums the partials of workspace w, its lane 0 runs the serial step on this workgroup's copy of the state
 __device__ __attribute__((noinline)) void pk_step_phase(const PairJob* __restrict__ jobs, int nws, int pts_per_block, int fuse, bool stats_wg,
@@ -291,35 +315,57 @@ __device__ __attribute__((noinline)) void pk_step_phase(const PairJob* __restric
   __syncthreads();
 }
 
-// returns false when the barrier gave up (timeout, or another workgroup's abort)
-// `light`: what crosses the barrier was stored through the caches and will be read past them (the reduction's partials): arrival and
-// departure only, no release / acquire of the L2
-__device__ __attribute__((noinline)) bool pk_grid_barrier(unsigned* ctl, unsigned epoch, long long timeout, bool light = false)
+// ---- the barriers: every workgroup that shares `counter` arrives, thread 0 polls until the count reaches the target.  false: the barrier
+// gave up (timeout, or another workgroup's abort).
+// mode 0: release / acquire at agent scope — the L2 of the workgroup's XCD written back before the arrival, invalidated after the
+//   departure: what crosses the barrier may be read by a workgroup on another XCD through plain loads.
+// mode 1 (light): what crosses was stored through the caches and is read past them (the reduction's partials): arrival and departure only.
+// mode 2 (local): every workgroup of the team sits on ONE XCD (verified at the start of the kernel from the hardware's XCC id): they share
+//   its L2, so the writers' plain stores only have to have arrived there (the explicit s_waitcnt vmcnt(0) every wave executes ahead of
+//   the workgroup barrier below: the vector L1 is write-through) — no L2 write-back — and the readers drop what their L1 holds with the acquire's own invalidation (buffer_inv sc1).
+//   (The workgroup-scope form, buffer_inv sc0, was 5 % faster still and is NOT enough: the one-channel team test read stale residuals.)
+// Word: what one poll reads — the arrival counter (unsigned), or the counter together with the word behind it (unsigned long long: one
+// aligned 8-byte load, the upper half left in pk_size_seen).  target_of(): the count that completes THIS barrier, asked behind the release;
+// budget_of(): abort word and timeout, asked behind the arrival (off the path of the workgroups that wait for this one).
+struct PkBudget { unsigned* abort_word; long long timeout; };
+__shared__ int pk_size_seen;      // the team's size word — size | (iteration it applies to) << 16, published by the leader — as read with the count that completed the last barrier
+template <class Word, class Target, class Budget>
+__device__ __forceinline__ bool pk_barrier(unsigned* counter, int mode, Target&& target_of, Budget&& budget_of)
 {
   // EVERY wave waits for its own global stores to have left (the vector L1 is write-through: vmcnt(0) = they are in the L2) before
   // the workgroup barrier: s_barrier alone does not wait for vmcnt, and thread 0's wait below covers thread 0's wave only.
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if(threadIdx.x == 0) {
-    if(!light) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if(mode == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned target = epoch * (unsigned) pk_nwg;
-    __hip_atomic_fetch_add(ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned target = target_of();
+    __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const PkBudget b = budget_of();
     const long long t0 = wall_clock64();
     int ok = 1;
     unsigned spins = 0;
-    while(__hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+    Word seen;
+    while((unsigned) (seen = __hip_atomic_load(reinterpret_cast<Word*>(counter), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < target) {
       __builtin_amdgcn_s_sleep(1);
-      if((++spins & 63u) == 0u || timeout < 64) {     // (tiny budgets: the tests of this path)
-        if(__hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = 0; break; }
-        if(wall_clock64() - t0 > timeout) { __hip_atomic_store(ctl + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = 0; break; }
+      if((++spins & 63u) == 0u || b.timeout < 64) {     // (tiny budgets: the tests of this path)
+        if(__hip_atomic_load(b.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = 0; break; }
+        if(wall_clock64() - t0 > b.timeout) { __hip_atomic_store(b.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = 0; break; }
       }
     }
-    if(!light) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if(mode == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    else if(mode == 2) asm volatile("buffer_inv sc1" ::: "memory");
     pk_ok = ok;
+    if constexpr(sizeof(Word) == 8) pk_size_seen = (int) (seen >> 32);
   }
   __syncthreads();
   return pk_ok != 0;
+}
+// groups of constant size (gn_persistent_kernel: the grid, modes 0 and 1; gn_team_fixed_kernel: a team): the epoch-th barrier completes at
+// epoch * size arrivals
+__device__ __attribute__((noinline)) bool pk_epoch_barrier(unsigned* counter, unsigned* abort_word, unsigned epoch, long long timeout, int mode = 0)
+{
+  return pk_barrier<unsigned>(counter, mode, [&] { return epoch * (unsigned) pk_nwg; }, [&] { return PkBudget{abort_word, timeout}; });
 }
 
 template <int C, int LOSS>
@@ -334,8 +380,7 @@ __global__ __launch_bounds__(PK_THREADS) void gn_persistent_kernel(const PairJob
   if(tid == 0) { pk_member = (int) blockIdx.x; pk_nwg = (int) gridDim.x; }
 
   for(int ws = 0; ws < nws; ++ws) {
-    const uint32_t* g = reinterpret_cast<const uint32_t*>(jobs[ws].st.get());
-    for(int i = tid; i < kStateWords; i += PK_THREADS) pk_state[ws][i] = g[i];
+    pk_state_load(ws, jobs[ws].st.get());
     if(tid < 4) pk_nrm[ws][tid] = jobs[ws].nrm[tid];
     if(tid == 4) pk_nrm[ws][4] = jobs[ws].dspace ? 1.0f : 0.0f;
   }
@@ -380,7 +425,7 @@ __global__ __launch_bounds__(PK_THREADS) void gn_persistent_kernel(const PairJob
         if(st->active && (!fuse || st->delta_scale > 1e-6f)) pk_warp_phase<C>(jobs, ws, stats_wg);
       }
       PK_TICK(0);
-      ok = pk_grid_barrier(ctl, ++epoch, timeout);
+      ok = pk_epoch_barrier(ctl, ctl + 1, ++epoch, timeout);
       PK_TICK(1);
       if(!ok) break;
       // ... and their exact median + robust scale, every workgroup on its own copy of the state
@@ -392,17 +437,10 @@ __global__ __launch_bounds__(PK_THREADS) void gn_persistent_kernel(const PairJob
     }
     // weights + normal equations per tile (frozen scale with the fused path: residuals recomputed there)
     for(int ws = 0; ws < nws; ++ws) {
-      const GNState* st = pk_st(ws);
-      if(!st->active) continue;
-      if constexpr(kCanFuse) {
-        if(fuse && !(st->delta_scale > 1e-6f)) pk_irls_phase<C, LOSS, true>(jobs, ws, pts_per_block, epoch_it);
-        else pk_irls_phase<C, LOSS, false>(jobs, ws, pts_per_block, epoch_it);
-      } else {
-        pk_irls_phase<C, LOSS, false>(jobs, ws, pts_per_block, epoch_it);
-      }
+      if(pk_st(ws)->active) pk_irls<C, LOSS>(jobs, ws, fuse, pts_per_block, epoch_it);
     }
     PK_TICK(3);
-    ok = pk_grid_barrier(ctl, ++epoch, timeout, true);
+    ok = pk_epoch_barrier(ctl, ctl + 1, ++epoch, timeout, 1);      // (only the partials cross: light)
     PK_TICK(4);
     if(!ok) break;
     pk_step_phase(jobs, nws, pts_per_block, fuse ? 1 : 0, stats_wg, epoch_it);
@@ -418,10 +456,7 @@ __global__ __launch_bounds__(PK_THREADS) void gn_persistent_kernel(const PairJob
 #endif
 
   if(ok && blockIdx.x == 0) {
-    for(int ws = 0; ws < nws; ++ws) {
-      uint32_t* g = reinterpret_cast<uint32_t*>(jobs[ws].st.get());
-      for(int i = tid; i < kStateWords; i += PK_THREADS) g[i] = pk_state[ws][i];
-    }
+    for(int ws = 0; ws < nws; ++ws) pk_state_store(ws, jobs[ws].st.get());
   }
   // the tap-cache keys of the NEXT level's points (one key array per workspace, shared by the levels): nobody reads a key after the last
   // barrier of the last iteration, the next level's kernel starts behind this one
@@ -460,52 +495,19 @@ constexpr int kTeamCtlWords = 32;       // one 128-byte line per team: [0] arriv
 __shared__ int pk_next_pair;
 __shared__ unsigned pk_team_xccs;      // XCDs the team's workgroups run on (bit mask)
 
-// mode 0: release / acquire at agent scope — the L2 of the workgroup's XCD written back before the arrival, invalidated after the
-//   departure: what crosses the barrier may be read by a workgroup on another XCD through plain loads.
-// mode 1 (light): what crosses was stored through the caches and is read past them (the reduction's partials): arrival and departure only.
-// mode 2 (local): every workgroup of the team sits on ONE XCD (verified at the start of the kernel from the hardware's XCC id): they share
-//   its L2, so the writers' plain stores only have to have arrived there (the explicit s_waitcnt vmcnt(0) every wave executes ahead of
-//   the workgroup barrier below: the vector L1 is write-through) — no L2 write-back — and the readers drop what their L1 holds with the acquire's own invalidation (buffer_inv sc1).
-//   (The workgroup-scope form, buffer_inv sc0, was 5 % faster still and is NOT enough: the one-channel team test read stale residuals.)
 // `target`: the value the team's arrival counter reaches when every member of the team has arrived at THIS barrier — the running sum of the
 // team sizes over its barriers so far (pk_arrivals: a team grows when idle workgroups join it, see pk_join_team).
 __shared__ unsigned pk_arrivals;
-__shared__ int pk_size_seen;      // the team's size word — size | (iteration it applies to) << 16, published by the leader — as read with the count that completed the last barrier
 // What the team kernel needs now and then (barrier budget, solver tolerances, the shape of the launch) lives in LDS, not in scalar registers
 // held across the reduction phase: that phase is inlined and takes every register there is — with the join logic's operands alive across
 // it the kernel spilled 55 vector registers (324 B of scratch per lane) and lost 2 % (profiles/r05_team_join.txt).
 struct TeamCfg { long long timeout; unsigned* abort_word; int n_pairs, n_teams, team_size, level_lo, scale_is_moot, local_ok, join_mode; unsigned xcc_bit; };
 __shared__ TeamCfg pk_cfg;
+// the arrival counter and the team size its leader has published sit in one aligned 8-byte word: ONE load per poll reads both, and the
+// size read together with the count that completes the barrier is the one the leader wrote ahead of its own arrival (pk_publish_admission)
 __device__ __attribute__((noinline)) bool pk_team_barrier(unsigned* team_ctl, unsigned target, int mode = 0)
 {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave's stores in the L2 before the arrival (see pk_grid_barrier)
-  __syncthreads();
-  if(threadIdx.x == 0) {
-    if(mode == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_fetch_add(team_ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned* const abort_word = pk_cfg.abort_word;      // (read behind the arrival: off the path of the workgroups that wait for this one)
-    const long long timeout = pk_cfg.timeout;
-    const long long t0 = wall_clock64();
-    int ok = 1;
-    unsigned spins = 0;
-    // the arrival counter and the team size its leader has published sit in one aligned 8-byte word: ONE load per poll reads both, and the
-    // size read together with the count that completes the barrier is the one the leader wrote ahead of its own arrival (pk_publish_admission)
-    unsigned long long both;
-    while((unsigned) (both = __hip_atomic_load(reinterpret_cast<unsigned long long*>(team_ctl), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if((++spins & 63u) == 0u || timeout < 64) {
-        if(__hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = 0; break; }
-        if(wall_clock64() - t0 > timeout) { __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = 0; break; }
-      }
-    }
-    if(mode == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    else if(mode == 2) asm volatile("buffer_inv sc1" ::: "memory");
-    pk_ok = ok;
-    pk_size_seen = (int) (both >> 32);
-  }
-  __syncthreads();
-  return pk_ok != 0;
+  return pk_barrier<unsigned long long>(team_ctl, mode, [&] { return target; }, [] { return PkBudget{pk_cfg.abort_word, pk_cfg.timeout}; });
 }
 
 // PoseEstimatorBase::reset + the head of run() on this workgroup's LDS copy (level_begin_kernel's body), and this workgroup's share
@@ -517,100 +519,132 @@ __device__ __forceinline__ void pk_level_begin(const PairJob& j, int level, int 
     for(int i = pk_member * PK_THREADS + (int) threadIdx.x; i < j.n; i += nthreads_team) j.tapkey[i] = 0xffffffffu;
   if(threadIdx.x < 4) pk_nrm[0][threadIdx.x] = j.nrm[threadIdx.x];
   if(threadIdx.x == 4) pk_nrm[0][4] = j.dspace ? 1.0f : 0.0f;
-  if(threadIdx.x == 0) {
-    GNState* st = pk_st(0);
-    st->scale = 1.0f;
-    st->delta_scale = scale_is_moot ? 0.0f : 1e10f;
-    st->f_norm_prev = 0.0f;
-    st->g_tol = 0.0f;
-    st->g_norm = 0.0f;
-    st->num_fun_evals = 0;
-    st->num_iterations = 0;
-    st->status = BPVO_STATUS_MAX_ITERATIONS;
-    st->phase = PHASE_FIRST;
-    st->has_converged = 0;
-    st->level = level;
-    st->median_valid = 0;
-    st->last_median = 0.0f;
-    for(int i = 0; i < 16; ++i) st->T[i] = st->T_out[i];
-    for(int i = 0; i < 6; ++i) st->dp[i] = 0.0f;
-    st->active = (j.n > 0) ? 1 : 0;
+  if(threadIdx.x == 0) gn_level_reset(pk_st(0), level, scale_is_moot, j.n);
+}
+
+// Block -> team and member.  Grid: 1-D, n_teams * team_size workgroups.  Workgroups are dealt to the XCDs round robin by their linear
+// index (guide: block b runs on XCD b % 8 — observed, for speed only); when the teams divide evenly over the 8 XCDs a team's workgroups are
+// taken from ONE XCD so that the pair's taps, residuals and partials stay in that XCD's L2 between phases.  Any mapping is correct (the
+// barriers are agent-scope).
+// SPARE workgroups: the grid of the growing form may be larger than n_teams * team_size (the launcher fills the chip: 96 pairs as teams of 2
+// leave 64 CUs over) — what is beyond the teams starts as a helper and joins a team at its first admission.
+struct TeamPlace { int team, member; bool spare; };
+__device__ __forceinline__ TeamPlace team_geometry(int n_teams, int team_size)
+{
+  const int b = (int) blockIdx.x;
+  if(b >= n_teams * team_size) return {b % n_teams /* where its search for a team starts */, -1, true};
+  if((n_teams & 7) == 0) {
+    const int xcd = b & 7, slot = b >> 3;            // slot-th workgroup of its XCD
+    return {xcd * (n_teams >> 3) + slot / team_size, slot % team_size, false};
   }
+  return {b / team_size, b % team_size, false};
+}
+
+// BPVO_PK_TIMING: the first workgroup of team 0 accumulates the 100 MHz ticks of its phases, per pyramid level, in ctl[4 .. 31]: 7 words
+// per level {warp, barrier1, median, irls, barrier2, step, iterations}
+struct TeamTicks {
+#ifdef BPVO_PK_TIMING
+  long long tk = wall_clock64();
+  int level = 0;
+  unsigned acc_t[kMaxLevels][7] = {};
+  __device__ void iteration(int l) { level = l; tk = wall_clock64(); acc_t[l][6] += 1; }
+  __device__ void operator()(int k) { __syncthreads(); const long long t_ = wall_clock64(); acc_t[level][k] += (unsigned) (t_ - tk); tk = t_; }
+  __device__ void add_to(unsigned* global_ctl) const      // words 4 .. 31 of the global line, summed over the team's pairs
+  {
+    for(int l = 0; l < 4; ++l) for(int k = 0; k < 7; ++k) global_ctl[4 + l * 7 + k] += acc_t[l][k];
+  }
+#else
+  __device__ void iteration(int) {}
+  __device__ void operator()(int) {}
+  __device__ void add_to(unsigned*) const {}
+#endif
+};
+
+// One pair on this workgroup's team, from level `level_first` down: the loops of BOTH team kernels.  An iteration is warp and median while the
+// robust scale moves (or without the fused path), reduction, step.  What the two forms differ in is the Team (FixedTeam, GrowingTeam below):
+// its barrier, its barrier mode, and what it has to do at the start of a level, ahead of the barrier between reduction and step, and behind
+// the step.  resume: this workgroup has just joined the team in the middle of level_first.  false: a barrier gave up.
+// (The whole loop nest and not the iteration alone: with the loops in the callers and the body inlined into them, every give-up leaves the
+// body before it leaves the loops, the loops come out in another shape, and team_run_pair — at the register limit — took 2 more VGPRs (C = 1)
+// and 16 more bytes of scratch per lane (C = 8); like this its registers and scratch are what they were with the loops written out.  For the
+// same reason jobs_all is not __restrict__ HERE: as a parameter's qualifier it lets the compiler vectorise pk_level_begin's key loop, + 2 VGPRs
+// in team_run_pair<1>.  profiles/team_refactor_kernel_resources.txt)
+template <int C, int LOSS, class Team>
+__device__ __forceinline__ bool pk_team_levels(const PairJob* jobs_all, int job_pitch, int pair, int level_first, int level_lo, bool resume, int scale_is_moot,
+                                               bool fuse, bool stats_wg, int pts_per_block, unsigned& epoch_it, Team& team, TeamTicks& tick)
+{
+  for(int level = level_first; level >= level_lo; --level) {
+    const PairJob* __restrict__ jobs = jobs_all + (size_t) level * job_pitch + pair;      // jobs[0]: this pair at this level
+    if(!resume) {
+      __syncthreads();      // every wave has read `active` of the level it leaves before thread 0 rewrites the LDS state
+      pk_level_begin(jobs[0], level, scale_is_moot);
+      team.level_begins(level);
+      if(!team.barrier(team.mode)) return false;         // keys reset before any phase reads them
+    }
+    resume = false;
+    for(;;) {
+      const GNState* st = pk_st(0);
+      if(!st->active) break;
+      const bool moving = st->delta_scale > 1e-6f;
+      tick.iteration(level);
+      if(!fuse || moving) {
+        if constexpr(C == 8) pk_warp_phase_staged<TEAM_WARP_U, TEAM_NT>(jobs, 0, stats_wg);
+        else pk_warp_phase<C>(jobs, 0, stats_wg);
+        tick(0);
+        if(!team.barrier(team.mode)) return false;
+        tick(1);
+        if(moving) pk_median_phase<C>(jobs, 0, stats_wg);
+        tick(2);
+      }
+      pk_irls<C, LOSS>(jobs, 0, fuse, pts_per_block, epoch_it);
+      tick(3);
+      team.before_reduce_barrier(level, epoch_it);
+      if(!team.barrier(1)) return false;      // (only the partials cross: light)
+      tick(4);
+      pk_step_phase(jobs, 1, pts_per_block, fuse ? 1 : 0, stats_wg, epoch_it);
+      tick(5);
+      ++epoch_it;
+      if(!team.after_step(epoch_it - 1u)) return false;
+    }
+  }
+  return true;
 }
 
 // ---- the team kernel with teams of FIXED size (rounds 3 - 4), kept for the launches in which no team can grow — teams that start at the
-// admission cap (batches of up to 16 pairs), a single team — and for the batches below kTeamJoinFromPairs, where the growing form's
-// bookkeeping costs more than the little imbalance of a few large teams gives back (8 / 16 / 32 pairs: 3 - 4 % slower, 64: + 2 %, 80: + 5 %,
-// 128: + 7 %; profiles/r05_team_join.txt).  Same phases, same chunk and tile indices.  Its barrier counts epochs of a constant team size.
-__device__ __attribute__((noinline)) bool pk_team_barrier_fixed(unsigned* team_ctl, unsigned* abort_word, unsigned epoch, long long timeout, int mode = 0)
-{
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave's stores in the L2 before the arrival (see pk_grid_barrier)
-  __syncthreads();
-  if(threadIdx.x == 0) {
-    if(mode == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned target = epoch * (unsigned) pk_nwg;
-    __hip_atomic_fetch_add(team_ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const long long t0 = wall_clock64();
-    int ok = 1;
-    unsigned spins = 0;
-    while(__hip_atomic_load(team_ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if((++spins & 63u) == 0u || timeout < 64) {
-        if(__hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = 0; break; }
-        if(wall_clock64() - t0 > timeout) { __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = 0; break; }
-      }
-    }
-    if(mode == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    else if(mode == 2) asm volatile("buffer_inv sc1" ::: "memory");
-    pk_ok = ok;
-  }
-  __syncthreads();
-  return pk_ok != 0;
-}
-
-
+// admission cap (batches of up to 16 pairs), a single team — and for the batches below the option team_join_from_pairs, where the growing
+// form's bookkeeping costs more than the little imbalance of a few large teams gives back (8 / 16 / 32 pairs: 3 - 4 % slower, 64: + 2 %,
+// 80: + 5 %, 128: + 7 %; profiles/r05_team_join.txt).  Same phases, same chunk and tile indices.  Its barrier counts epochs of a constant
+// team size (pk_epoch_barrier).
+struct FixedTeam {
+  unsigned* team_ctl; unsigned* abort_word; long long timeout;
+  unsigned epoch;      // barriers passed
+  int mode;            // of the barriers that carry plain stores: 2 when the team sits on one XCD (pk_barrier)
+  __device__ bool barrier(int m) { return pk_epoch_barrier(team_ctl, abort_word, ++epoch, timeout, m); }
+  __device__ void level_begins(int) {}
+  __device__ void before_reduce_barrier(int, unsigned) {}
+  __device__ bool after_step(unsigned) { return true; }
+};
 template <int C, int LOSS>
 __global__ __launch_bounds__(PK_THREADS) void gn_team_fixed_kernel(const PairJob* __restrict__ jobs_all /*[levels][job_pitch]*/, int job_pitch, int n_pairs,
                                                              int team_size, int n_teams, int level_hi, int level_lo, int pts_per_block,
                                                              int fuse_frozen, int scale_is_moot, unsigned* ctl, long long timeout, int local_ok)
 {
-  constexpr bool kCanFuse = (C == 8);
   const int tid = threadIdx.x;
-  int team, member;
-  {
-    const int b = (int) blockIdx.x;
-    if((n_teams & 7) == 0) {
-      const int xcd = b & 7, slot = b >> 3;            // slot-th workgroup of its XCD
-      team = xcd * (n_teams >> 3) + slot / team_size;
-      member = slot % team_size;
-    } else {
-      team = b / team_size;
-      member = b % team_size;
-    }
-  }
+  const TeamPlace place = team_geometry(n_teams, team_size);
+  const int team = place.team, member = place.member;
   // (the second launch of a split run — estimate.hip — behind a first one that gave up: its abort word was carried over, nothing to do here)
   if(__hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
   if(tid == 0) { pk_member = member; pk_nwg = team_size; }
   const bool stats_wg = member == 0;
-  const bool fuse = kCanFuse && fuse_frozen;
+  const bool fuse = C == 8 && fuse_frozen;
   unsigned* const global_ctl = ctl;                                           // [1] abort, [2] next pair to hand out
   unsigned* const team_ctl = ctl + (size_t) (1 + team) * kTeamCtlWords;       // [0] arrivals, [1] pair slot
-  unsigned epoch = 0, epoch_it = 0;
+  unsigned epoch_it = 0;
+  FixedTeam fixed_team = {team_ctl, global_ctl + 1, timeout, 0u, 0};
   // which XCD this workgroup runs on (HW_REG_XCC_ID, bits 3:0), registered in the team's line [2] before the first barrier; behind it every
-  // member knows whether the team shares one L2 (team_mode 2: pk_team_barrier) — whatever the dispatcher did with the grid
+  // member knows whether the team shares one L2 (mode 2: pk_barrier) — whatever the dispatcher did with the grid
   if(tid == 0) (void) __hip_atomic_fetch_or(team_ctl + 2, 1u << (__builtin_amdgcn_s_getreg(63508) & 0xf), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  int team_mode = 0;
-  // BPVO_PK_TIMING: workgroup 0 of team 0 accumulates the 100 MHz ticks of its phases, per pyramid level, in ctl[4 .. 31]: 7 words per level
-  // {warp, barrier1, median, irls, barrier2, step, iterations}
-#ifdef BPVO_PK_TIMING
-  long long tk = wall_clock64();
-  unsigned acc_t[kMaxLevels][7];
-  for(int l = 0; l < kMaxLevels; ++l) for(int k = 0; k < 7; ++k) acc_t[l][k] = 0;
-#define TEAM_TICK(k) do { __syncthreads(); const long long t_ = wall_clock64(); acc_t[level][k] += (unsigned) (t_ - tk); tk = t_; } while(0)
-#else
-#define TEAM_TICK(k) do { } while(0)
-#endif
+  TeamTicks ticks;
 
   for(;;) {
     // next pair of this team: its workgroup 0 draws, the barrier publishes the draw to the others
@@ -620,66 +654,24 @@ __global__ __launch_bounds__(PK_THREADS) void gn_team_fixed_kernel(const PairJob
       const unsigned p = __hip_atomic_fetch_add(global_ctl + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(team_ctl + 1, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if(!pk_team_barrier_fixed(team_ctl, global_ctl + 1, ++epoch, timeout)) return;
+    if(!fixed_team.barrier(0)) return;
     if(tid == 0) {
       pk_next_pair = (int) __hip_atomic_load(team_ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       pk_team_xccs = __hip_atomic_load(team_ctl + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
-    team_mode = (local_ok && __popc(pk_team_xccs) == 1) ? 2 : 0;
+    fixed_team.mode = (local_ok && __popc(pk_team_xccs) == 1) ? 2 : 0;
     const int pair = pk_next_pair;
     if(pair >= n_pairs) return;
 
-    {   // the pair's state: HBM -> this workgroup's LDS copy (set_pose_kernel has run: T_out, statistics defaults)
-      const uint32_t* g = reinterpret_cast<const uint32_t*>(jobs_all[(size_t) level_hi * job_pitch + pair].st.get());
-      for(int i = tid; i < kStateWords; i += PK_THREADS) pk_state[0][i] = g[i];
-    }
+    GNState* const pair_state = jobs_all[(size_t) level_hi * job_pitch + pair].st.get();
+    pk_state_load(0, pair_state);      // (set_pose_kernel has run: T_out, statistics defaults)
     __syncthreads();
 
-    for(int level = level_hi; level >= level_lo; --level) {
-      const PairJob* __restrict__ jobs = jobs_all + (size_t) level * job_pitch + pair;      // jobs[0]: this pair at this level
-      __syncthreads();      // every wave has read `active` of the level it leaves before thread 0 rewrites the LDS state
-      pk_level_begin(jobs[0], level, scale_is_moot);
-      if(!pk_team_barrier_fixed(team_ctl, global_ctl + 1, ++epoch, timeout, team_mode)) return;         // keys reset before any phase reads them
-      for(;;) {
-        const GNState* st = pk_st(0);
-        if(!st->active) break;
-        const bool moving = st->delta_scale > 1e-6f;
-#ifdef BPVO_PK_TIMING
-        tk = wall_clock64(); acc_t[level][6] += 1;
-#endif
-        if(!fuse || moving) {
-          if constexpr(C == 8) pk_warp_phase_staged<TEAM_WARP_U, TEAM_NT>(jobs, 0, stats_wg);
-          else pk_warp_phase<C>(jobs, 0, stats_wg);
-          TEAM_TICK(0);
-          if(!pk_team_barrier_fixed(team_ctl, global_ctl + 1, ++epoch, timeout, team_mode)) return;
-          TEAM_TICK(1);
-          if(moving) pk_median_phase<C>(jobs, 0, stats_wg);
-          TEAM_TICK(2);
-        }
-        if constexpr(kCanFuse) {
-          if(fuse && !(pk_st(0)->delta_scale > 1e-6f)) pk_irls_phase<C, LOSS, true>(jobs, 0, pts_per_block, epoch_it);   // (after the median: the chain's rule)
-          else pk_irls_phase<C, LOSS, false>(jobs, 0, pts_per_block, epoch_it);
-        } else {
-          pk_irls_phase<C, LOSS, false>(jobs, 0, pts_per_block, epoch_it);
-        }
-        TEAM_TICK(3);
-        if(!pk_team_barrier_fixed(team_ctl, global_ctl + 1, ++epoch, timeout, 1)) return;      // (only the partials cross: light)
-        TEAM_TICK(4);
-        pk_step_phase(jobs, 1, pts_per_block, fuse ? 1 : 0, stats_wg, epoch_it);
-        TEAM_TICK(5);
-        ++epoch_it;
-      }
-    }
-#ifdef BPVO_PK_TIMING
-    if(team == 0 && member == 0 && tid == 0)
-      for(int l = 0; l < 4; ++l) for(int k = 0; k < 7; ++k) global_ctl[4 + l * 7 + k] += acc_t[l][k];      // words 4 .. 31 of the global line, summed over the team's pairs
-#endif
-    // the pair is done: its state back to HBM (one copy; the others are identical)
-    if(stats_wg) {
-      uint32_t* g = reinterpret_cast<uint32_t*>(jobs_all[(size_t) level_hi * job_pitch + pair].st.get());
-      for(int i = tid; i < kStateWords; i += PK_THREADS) g[i] = pk_state[0][i];
-    }
+    if(!pk_team_levels<C, LOSS>(jobs_all, job_pitch, pair, level_hi, level_lo, false, scale_is_moot, fuse, stats_wg, pts_per_block, epoch_it, fixed_team, ticks)) return;
+    if(team == 0 && member == 0 && tid == 0) ticks.add_to(global_ctl);
+    // the pair is done: its state back to HBM
+    if(stats_wg) pk_state_store(0, pair_state);
     __syncthreads();
   }
 }
@@ -867,9 +859,6 @@ __device__ __attribute__((noinline)) bool pk_admit(unsigned* team_ctl, GNState* 
   return true;
 }
 
-// Grid: 1-D, n_teams * team_size workgroups.  Workgroups are dealt to the XCDs round robin by their linear index (guide: block b runs on
-// XCD b % 8 — observed, for speed only); when the teams divide evenly over the 8 XCDs a team's workgroups are taken from ONE XCD so that
-// the pair's taps, residuals and partials stay in that XCD's L2 between phases.  Any mapping is correct (the barriers are agent-scope).
 // (A WIDE form of this kernel — every phase under 128 VGPRs and 68 KB of LDS, two workgroups per CU — was built and measured in round 4:
 // slower at every batch size, profiles/r04_team_wide_rejected.txt.)
 // One pair from `level` down, on this workgroup's team.  A function of its own, NOT inlined into the kernel's pair / join loop: the
@@ -877,12 +866,38 @@ __device__ __attribute__((noinline)) bool pk_admit(unsigned* team_ctl, GNState* 
 // newcomer) alive across it the kernel spilled 50 vector registers; here those are plain arguments, fixed for the call, and the
 // call's save / restore is paid once per pair.  resume: this workgroup has just joined the team in the middle of `level`.
 // Returns false when a barrier gave up.
+// (Inlined into the kernel, as the pair's loops were before teams could grow, and without the admission turns, this was 3 % faster at
+// 8 pairs, where an iteration lasts 12 us: the launches in which nobody can join anybody take gn_team_fixed_kernel.)
+// The growing form's team as pk_team_levels sees it.  arrivals: what the team's counter reads once every member has arrived at the barrier
+// passed last (the running sum of the team sizes over its barriers); nwg: the team's size.  Register copies of pk_arrivals / pk_nwg, which
+// the admission code updates.
+struct GrowingTeam {
+  const PairJob* jobs_all; unsigned* team_ctl; int job_pitch, level_hi, pair, join_mode, nwg, mode; bool leader; unsigned arrivals;
+  __device__ bool barrier(int m) { return pk_team_barrier(team_ctl, arrivals += (unsigned) nwg, m); }
+  __device__ void level_begins(int level)
+  {
+    if(leader && threadIdx.x == 0) __hip_atomic_store(team_ctl + 10, (unsigned) level, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ bool admission_turn(unsigned epoch_it) const { return join_mode && (epoch_it & (kTeamAdmitEvery - 1u)) == 0u; }      // (every member has the same epoch_it)
+  __device__ void before_reduce_barrier(int level, unsigned epoch_it)
+  {
+    if(admission_turn(epoch_it) && leader && threadIdx.x == 0) pk_publish_admission(team_ctl, pair, level, epoch_it, arrivals);
+  }
+  __device__ bool after_step(unsigned epoch_it)
+  {
+    if(!admission_turn(epoch_it)) return true;
+    if(threadIdx.x == 0) pk_arrivals = arrivals;
+    if(!pk_admit(team_ctl, jobs_all[(size_t) level_hi * job_pitch + pair].st.get(), leader, epoch_it)) return false;
+    arrivals = (unsigned) __builtin_amdgcn_readfirstlane((int) pk_arrivals); nwg = __builtin_amdgcn_readfirstlane(pk_nwg);
+    mode = (pk_cfg.local_ok && __popc(pk_team_xccs) == 1) ? 2 : 0;
+    return true;
+  }
+};
 struct TeamPairArgs { const PairJob* jobs_all; unsigned* team_ctl; int job_pitch, level_hi, pts_per_block, fuse, pair, level, leader, team_mode, resume; unsigned epoch_it; };
 __shared__ unsigned pk_epoch_it_out;
-template <int C, int LOSS, bool JOIN>
-__device__ __forceinline__ bool team_run_pair_body(const TeamPairArgs a)
+template <int C, int LOSS>
+__device__ __attribute__((noinline)) bool team_run_pair(const TeamPairArgs a)
 {
-  constexpr bool kCanFuse = (C == 8);
   const int tid = threadIdx.x;
   // Arguments of a non-inlined device function arrive in VECTOR registers: the compiler no longer knows that they are the same in every
   // lane, and everything derived from them — the job's fields, every address of the phases — would be computed and loaded per lane (the
@@ -896,116 +911,30 @@ __device__ __forceinline__ bool team_run_pair_body(const TeamPairArgs a)
   unsigned* const team_ctl = reinterpret_cast<unsigned*>(uni_ptr(a.team_ctl));
   const bool stats_wg = uni(a.leader) != 0, fuse = uni(a.fuse) != 0;
   const int pair = uni(a.pair), pts_per_block = uni(a.pts_per_block), job_pitch = uni(a.job_pitch), level_hi = uni(a.level_hi);
-  int team_mode = uni(a.team_mode);
-  bool resume = uni(a.resume) != 0;
   unsigned epoch_it = (unsigned) uni((int) a.epoch_it);
-  // arrivals: what the team's counter reads once every member has arrived at the barrier passed last (the running sum of the team
-  // sizes over its barriers); nwg: the team's size.  Register copies of pk_arrivals / pk_nwg, which the admission code updates.
-  unsigned arrivals = (unsigned) uni((int) pk_arrivals);
-  int nwg = uni(pk_nwg);
-#define TEAM_BARRIER(mode_) pk_team_barrier(team_ctl, arrivals += (unsigned) nwg, mode_)
-#ifdef BPVO_PK_TIMING
-  long long tk = wall_clock64();
-  unsigned acc_t[kMaxLevels][7];
-  for(int l = 0; l < kMaxLevels; ++l) for(int k = 0; k < 7; ++k) acc_t[l][k] = 0;
-#define TEAM_TICK(k) do { __syncthreads(); const long long t_ = wall_clock64(); acc_t[level][k] += (unsigned) (t_ - tk); tk = t_; } while(0)
-#else
-#define TEAM_TICK(k) do { } while(0)
-#endif
-  const int level_lo = uni(pk_cfg.level_lo), scale_is_moot = uni(pk_cfg.scale_is_moot), join_mode = JOIN ? uni(pk_cfg.join_mode) : 0;
-  for(int level = uni(a.level); level >= level_lo; --level) {
-    const PairJob* __restrict__ jobs = jobs_all + (size_t) level * job_pitch + pair;      // jobs[0]: this pair at this level
-    if(!resume) {
-      __syncthreads();      // every wave has read `active` of the level it leaves before thread 0 rewrites the LDS state
-      pk_level_begin(jobs[0], level, scale_is_moot);
-      if(stats_wg && tid == 0) __hip_atomic_store(team_ctl + 10, (unsigned) level, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if(!TEAM_BARRIER(team_mode)) return false;         // keys reset before any phase reads them
-    }
-    resume = false;
-    for(;;) {
-      const GNState* st = pk_st(0);
-      if(!st->active) break;
-      const bool moving = st->delta_scale > 1e-6f;
-#ifdef BPVO_PK_TIMING
-      tk = wall_clock64(); acc_t[level][6] += 1;
-#endif
-      if(!fuse || moving) {
-        if constexpr(C == 8) pk_warp_phase_staged<TEAM_WARP_U, TEAM_NT>(jobs, 0, stats_wg);
-        else pk_warp_phase<C>(jobs, 0, stats_wg);
-        TEAM_TICK(0);
-        if(!TEAM_BARRIER(team_mode)) return false;
-        TEAM_TICK(1);
-        if(moving) pk_median_phase<C>(jobs, 0, stats_wg);
-        TEAM_TICK(2);
-      }
-      if constexpr(kCanFuse) {
-        if(fuse && !(pk_st(0)->delta_scale > 1e-6f)) pk_irls_phase<C, LOSS, true>(jobs, 0, pts_per_block, epoch_it);   // (after the median: the chain's rule)
-        else pk_irls_phase<C, LOSS, false>(jobs, 0, pts_per_block, epoch_it);
-      } else {
-        pk_irls_phase<C, LOSS, false>(jobs, 0, pts_per_block, epoch_it);
-      }
-      TEAM_TICK(3);
-      const bool admission_turn = JOIN && join_mode && (epoch_it & (kTeamAdmitEvery - 1u)) == 0u;      // (every member has the same epoch_it)
-      if(admission_turn && stats_wg && tid == 0) pk_publish_admission(team_ctl, pair, level, epoch_it, arrivals);
-      if(!TEAM_BARRIER(1)) return false;      // (only the partials cross: light)
-      TEAM_TICK(4);
-      pk_step_phase(jobs, 1, pts_per_block, fuse ? 1 : 0, stats_wg, epoch_it);
-      TEAM_TICK(5);
-      ++epoch_it;
-      if(admission_turn) {
-        if(tid == 0) pk_arrivals = arrivals;
-        if(!pk_admit(team_ctl, jobs_all[(size_t) level_hi * job_pitch + pair].st.get(), stats_wg, epoch_it - 1u)) return false;
-        arrivals = (unsigned) uni((int) pk_arrivals); nwg = uni(pk_nwg);
-        team_mode = (pk_cfg.local_ok && __popc(pk_team_xccs) == 1) ? 2 : 0;
-      }
-    }
-  }
-#ifdef BPVO_PK_TIMING
-  if(stats_wg && team_ctl == pk_cfg.abort_word - 1 + kTeamCtlWords && tid == 0)      // (team 0's leader)
-    for(int l = 0; l < 4; ++l) for(int k = 0; k < 7; ++k) (pk_cfg.abort_word - 1)[4 + l * 7 + k] += acc_t[l][k];      // words 4 .. 31 of the global line, summed over the team's pairs
-#endif
-  if(tid == 0) { pk_epoch_it_out = epoch_it; pk_arrivals = arrivals; }
-  // the pair is done: its state back to HBM (one copy; the others are identical)
-  if(stats_wg) {
-    uint32_t* g = reinterpret_cast<uint32_t*>(jobs_all[(size_t) level_hi * job_pitch + pair].st.get());
-    for(int i = tid; i < kStateWords; i += PK_THREADS) g[i] = pk_state[0][i];
-  }
+  const int level_lo = uni(pk_cfg.level_lo), scale_is_moot = uni(pk_cfg.scale_is_moot), join_mode = uni(pk_cfg.join_mode);
+  GrowingTeam team = {jobs_all, team_ctl, job_pitch, level_hi, pair, join_mode, uni(pk_nwg), uni(a.team_mode), stats_wg, (unsigned) uni((int) pk_arrivals)};
+  TeamTicks ticks;
+  if(!pk_team_levels<C, LOSS>(jobs_all, job_pitch, pair, uni(a.level), level_lo, uni(a.resume) != 0, scale_is_moot, fuse, stats_wg, pts_per_block, epoch_it, team, ticks)) return false;
+  if(stats_wg && team_ctl == pk_cfg.abort_word - 1 + kTeamCtlWords && tid == 0) ticks.add_to(pk_cfg.abort_word - 1);      // (team 0's leader)
+  if(tid == 0) { pk_epoch_it_out = epoch_it; pk_arrivals = team.arrivals; }
+  // the pair is done: its state back to HBM
+  if(stats_wg) pk_state_store(0, jobs_all[(size_t) level_hi * job_pitch + pair].st.get());
   __syncthreads();
   return true;
 }
 
 template <int C, int LOSS>
-__device__ __attribute__((noinline)) bool team_run_pair(const TeamPairArgs a) { return team_run_pair_body<C, LOSS, true>(a); }
-
-// JOIN = false: the launches in which nobody can join anybody (teams that start at the admission cap — batches of up to 16 pairs — or a
-// single team): the pair's loops inlined into the kernel as they were before teams could grow, without the admission turns (3 % at 8 pairs,
-// where an iteration lasts 12 us).
-template <int C, int LOSS, bool JOIN>
 __global__ __launch_bounds__(PK_THREADS) void gn_team_kernel(const PairJob* __restrict__ jobs_all /*[levels][job_pitch]*/, int job_pitch, int n_pairs,
                                                              int team_size, int n_teams, int level_hi, int level_lo, int pts_per_block,
                                                              int fuse_frozen, int scale_is_moot, unsigned* ctl, long long timeout, int local_ok,
                                                              int join_mode)
 {
-  constexpr bool kCanFuse = (C == 8);
   const int tid = threadIdx.x;
-  int team, member;
-  // SPARE workgroups: the grid may be larger than n_teams * team_size (the launcher fills the chip: 96 pairs as teams of 2 leave 64 CUs
-  // over) — what is beyond the teams starts as a helper and joins a team at its first admission
-  const bool spare = (int) blockIdx.x >= n_teams * team_size;
-  {
-    const int b = (int) blockIdx.x;
-    if(spare) {
-      team = b % n_teams;       // (where its search for a team starts)
-      member = -1;
-    } else if((n_teams & 7) == 0) {
-      const int xcd = b & 7, slot = b >> 3;            // slot-th workgroup of its XCD
-      team = xcd * (n_teams >> 3) + slot / team_size;
-      member = slot % team_size;
-    } else {
-      team = b / team_size;
-      member = b % team_size;
-    }
-  }
+  const TeamPlace place = team_geometry(n_teams, team_size);
+  const bool spare = place.spare;
+  int team = place.team;
+  const int member = place.member;
   // (the second launch of a split run behind a first one that gave up: its abort word was carried over, nothing to do here)
   if(__hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
   if(tid == 0) {
@@ -1019,13 +948,13 @@ __global__ __launch_bounds__(PK_THREADS) void gn_team_kernel(const PairJob* __re
   unsigned* const global_ctl = ctl;                                     // [1] abort, [2] next pair to hand out, [3] workgroups that joined another team
   unsigned* team_ctl = ctl + (size_t) (1 + team) * kTeamCtlWords;
   // which XCD this workgroup runs on (HW_REG_XCC_ID, bits 3:0), registered in the team's line [2] before the first barrier; behind it every
-  // member knows whether the team shares one L2 (team_mode 2: pk_team_barrier) — whatever the dispatcher did with the grid
+  // member knows whether the team shares one L2 (team_mode 2: pk_barrier) — whatever the dispatcher did with the grid
   if(tid == 0 && !spare) {
     (void) __hip_atomic_fetch_or(team_ctl + 2, pk_cfg.xcc_bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if(leader) __hip_atomic_store(team_ctl + 1, (unsigned) team_size, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   TeamPairArgs a;
-  a.jobs_all = jobs_all; a.job_pitch = job_pitch; a.level_hi = level_hi; a.pts_per_block = pts_per_block; a.fuse = (kCanFuse && fuse_frozen) ? 1 : 0;
+  a.jobs_all = jobs_all; a.job_pitch = job_pitch; a.level_hi = level_hi; a.pts_per_block = pts_per_block; a.fuse = (C == 8 && fuse_frozen) ? 1 : 0;
   a.epoch_it = 0;
   bool idle = spare;       // a workgroup without a team: looks for one before anything else
   for(;;) {
@@ -1057,7 +986,6 @@ __global__ __launch_bounds__(PK_THREADS) void gn_team_kernel(const PairJob* __re
     if(idle || a.pair >= n_pairs) {
       idle = false;
       // idle: join a team that still works (join_mode 0: leave; 1: teams on this workgroup's XCD only; 2: any)
-      if constexpr(!JOIN) return;
       if(!pk_take_seat(ctl, jobs_all, job_pitch, level_hi, team)) return;
       team = pk_seat.team;
       team_ctl = ctl + (size_t) (1 + team) * kTeamCtlWords;
@@ -1065,15 +993,12 @@ __global__ __launch_bounds__(PK_THREADS) void gn_team_kernel(const PairJob* __re
       a.pair = pk_seat.pair; a.level = pk_seat.level; a.epoch_it = pk_seat.epoch_it;
       a.resume = 1;
     } else {
-      // the pair's state: HBM -> this workgroup's LDS copy (set_pose_kernel has run: T_out, statistics defaults)
-      const uint32_t* g = reinterpret_cast<const uint32_t*>(jobs_all[(size_t) level_hi * job_pitch + a.pair].st.get());
-      for(int i = tid; i < kStateWords; i += PK_THREADS) pk_state[0][i] = g[i];
+      pk_state_load(0, jobs_all[(size_t) level_hi * job_pitch + a.pair].st.get());      // (set_pose_kernel has run: T_out, statistics defaults)
     }
     __syncthreads();
     a.team_ctl = team_ctl; a.leader = leader ? 1 : 0;
     a.team_mode = (local_ok && __popc(pk_team_xccs) == 1) ? 2 : 0;
-    if constexpr(JOIN) { if(!team_run_pair<C, LOSS>(a)) return; }
-    else { if(!team_run_pair_body<C, LOSS, false>(a)) return; }
+    if(!team_run_pair<C, LOSS>(a)) return;
     a.epoch_it = pk_epoch_it_out;
   }
 }
@@ -1088,34 +1013,44 @@ int gn_persistent_grid(const GNLaunch& g, int max_grid)
   const int chunks = (g.max_points + K6_BLOCK - 1) / K6_BLOCK;
   return std::max(1, std::min(max_grid, (chunks + PK_VB - 1) / PK_VB));
 }
+// Launch of one of the three kernels.  Once per KERNEL and device (the lanes' host threads may race here): the opt-in for the 123 KB of
+// median_block's LDS and the residency check — one workgroup per CU must fit; the persistent kernel's grid (<= 128) is far below the number
+// of CUs, the team kernels' is sized to them by the caller.
+template <auto Kern, class... Args>
+static hipError_t pk_launch(hipStream_t s, int grid, Args... args)
+{
+  static std::once_flag once[64];
+  static hipError_t status[64];
+  int dev = 0;
+  (void) hipGetDevice(&dev);
+  dev &= 63;
+  std::call_once(once[dev], [&] {
+    status[dev] = hipFuncSetAttribute((const void*) Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) kMedianLds);
+    int per_cu = 0;
+    if(status[dev] == hipSuccess) status[dev] = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kern, PK_THREADS, kMedianLds);
+    if(status[dev] == hipSuccess && per_cu < 1) status[dev] = hipErrorLaunchOutOfResources;
+  });
+  if(status[dev] != hipSuccess) return status[dev];
+  hipLaunchKernelGGL(Kern, dim3(grid), dim3(PK_THREADS), kMedianLds, s, args...);
+  return hipGetLastError();
+}
+// f(loss as a compile-time constant)
+template <class F>
+static hipError_t pk_with_loss(int loss, F&& f)
+{
+  switch(loss) {
+    case BPVO_LOSS_HUBER: return f(std::integral_constant<int, BPVO_LOSS_HUBER>());
+    case BPVO_LOSS_TUKEY: return f(std::integral_constant<int, BPVO_LOSS_TUKEY>());
+    default: return f(std::integral_constant<int, BPVO_LOSS_L2>());
+  }
+}
 template <int C>
 static hipError_t launch_gn_persistent_c(hipStream_t s, const GNLaunch& g, unsigned* ctl, int grid, long long timeout)
 {
-  const int ppb = gn_pts_per_block(C);
   const int fuse = (C == 8 && g.fuse_frozen) ? 1 : 0;
-  auto go = [&](auto kern) -> hipError_t {
-    // once per kernel and device (the lanes' host threads may race here): the opt-in for the 123 KB of median_block's LDS and the
-    // residency check — one workgroup per CU must fit, the grid itself (<= 128) is far below the number of CUs
-    static std::once_flag once[64];
-    static hipError_t status[64];
-    int dev = 0;
-    (void) hipGetDevice(&dev);
-    dev &= 63;
-    std::call_once(once[dev], [&] {
-      status[dev] = hipFuncSetAttribute((const void*) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) kMedianLds);
-      int per_cu = 0;
-      if(status[dev] == hipSuccess) status[dev] = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, PK_THREADS, kMedianLds);
-      if(status[dev] == hipSuccess && per_cu < 1) status[dev] = hipErrorLaunchOutOfResources;
-    });
-    if(status[dev] != hipSuccess) return status[dev];
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(PK_THREADS), kMedianLds, s, g.jobs, g.npairs, ppb, fuse, ctl, timeout, g.begin_level, g.begin_moot, g.next_jobs);
-    return hipGetLastError();
-  };
-  switch(g.loss) {
-    case BPVO_LOSS_HUBER: return go(gn_persistent_kernel<C, BPVO_LOSS_HUBER>);
-    case BPVO_LOSS_TUKEY: return go(gn_persistent_kernel<C, BPVO_LOSS_TUKEY>);
-    default: return go(gn_persistent_kernel<C, BPVO_LOSS_L2>);
-  }
+  return pk_with_loss(g.loss, [&](auto loss) {
+    return pk_launch<gn_persistent_kernel<C, loss()>>(s, grid, g.jobs, g.npairs, gn_pts_per_block(C), fuse, ctl, timeout, g.begin_level, g.begin_moot, g.next_jobs);
+  });
 }
 hipError_t launch_gn_persistent(hipStream_t s, const GNLaunch& g, unsigned* ctl, int grid, long long timeout_ticks)
 {
@@ -1143,54 +1078,14 @@ static hipError_t launch_gn_team_c(hipStream_t s, const GNTeamLaunch& t)
 {
   const int ppb = gn_pts_per_block(C);
   const int fuse = (C == 8 && t.fuse_frozen) ? 1 : 0;
-  constexpr size_t lds = kMedianLds;
-  constexpr int need_per_cu = 1;
-  auto go = [&](auto kern) -> hipError_t {
-    static std::once_flag once[64];
-    static hipError_t status[64];
-    int dev = 0;
-    (void) hipGetDevice(&dev);
-    dev &= 63;
-    std::call_once(once[dev], [&] {
-      status[dev] = hipFuncSetAttribute((const void*) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-      int per_cu = 0;
-      if(status[dev] == hipSuccess) status[dev] = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, PK_THREADS, lds);
-      if(status[dev] == hipSuccess && per_cu < need_per_cu) status[dev] = hipErrorLaunchOutOfResources;
-    });
-    if(status[dev] != hipSuccess) return status[dev];
-    hipLaunchKernelGGL(kern, dim3(t.team_size * t.n_teams + t.spare_workgroups), dim3(PK_THREADS), lds, s, t.jobs_all, t.job_pitch, t.n_pairs, t.team_size, t.n_teams, t.level_hi,
-                       t.level_lo, ppb, fuse, t.scale_is_moot, t.ctl, t.timeout_ticks, t.local_barriers, t.join_mode);
-    return hipGetLastError();
-  };
-  if(t.join_mode) {
-    switch(t.loss) {
-      case BPVO_LOSS_HUBER: return go(gn_team_kernel<C, BPVO_LOSS_HUBER, true>);
-      case BPVO_LOSS_TUKEY: return go(gn_team_kernel<C, BPVO_LOSS_TUKEY, true>);
-      default: return go(gn_team_kernel<C, BPVO_LOSS_L2, true>);
-    }
-  }
-  auto go_fixed = [&](auto kern) -> hipError_t {
-    static std::once_flag once[64];
-    static hipError_t status[64];
-    int dev = 0;
-    (void) hipGetDevice(&dev);
-    dev &= 63;
-    std::call_once(once[dev], [&] {
-      status[dev] = hipFuncSetAttribute((const void*) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-      int per_cu = 0;
-      if(status[dev] == hipSuccess) status[dev] = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, PK_THREADS, lds);
-      if(status[dev] == hipSuccess && per_cu < need_per_cu) status[dev] = hipErrorLaunchOutOfResources;
-    });
-    if(status[dev] != hipSuccess) return status[dev];
-    hipLaunchKernelGGL(kern, dim3(t.team_size * t.n_teams), dim3(PK_THREADS), lds, s, t.jobs_all, t.job_pitch, t.n_pairs, t.team_size, t.n_teams, t.level_hi,
-                       t.level_lo, ppb, fuse, t.scale_is_moot, t.ctl, t.timeout_ticks, t.local_barriers);
-    return hipGetLastError();
-  };
-  switch(t.loss) {
-    case BPVO_LOSS_HUBER: return go_fixed(gn_team_fixed_kernel<C, BPVO_LOSS_HUBER>);
-    case BPVO_LOSS_TUKEY: return go_fixed(gn_team_fixed_kernel<C, BPVO_LOSS_TUKEY>);
-    default: return go_fixed(gn_team_fixed_kernel<C, BPVO_LOSS_L2>);
-  }
+  const int grid = t.team_size * t.n_teams;
+  return pk_with_loss(t.loss, [&](auto loss) {
+    if(t.join_mode)
+      return pk_launch<gn_team_kernel<C, loss()>>(s, grid + t.spare_workgroups, t.jobs_all, t.job_pitch, t.n_pairs, t.team_size, t.n_teams, t.level_hi, t.level_lo, ppb,
+                                                  fuse, t.scale_is_moot, t.ctl, t.timeout_ticks, t.local_barriers, t.join_mode);
+    return pk_launch<gn_team_fixed_kernel<C, loss()>>(s, grid, t.jobs_all, t.job_pitch, t.n_pairs, t.team_size, t.n_teams, t.level_hi, t.level_lo, ppb, fuse,
+                                                      t.scale_is_moot, t.ctl, t.timeout_ticks, t.local_barriers);
+  });
 }
 hipError_t launch_gn_team(hipStream_t s, const GNTeamLaunch& t)
 {
