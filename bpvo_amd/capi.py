@@ -614,6 +614,82 @@ class Context:
             self.call("seq_get_trajectory", int(s), out.ctypes.data_as(C.c_void_p))
         return out
 
+    # -- rig mode: the cameras of a rigid rig estimated as one body pose (bpvo_hip_*_rig)
+    @staticmethod
+    def _rig_members(wss, refs, curs, X):
+        w = np.ascontiguousarray(wss, dtype=np.int32).reshape(-1)
+        r = np.ascontiguousarray(refs, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(curs, dtype=np.int32).reshape(-1)
+        Xf = _f32(X).reshape(-1, 16)
+        assert r.shape == w.shape and c.shape == w.shape and Xf.shape[0] == w.shape[0], "one template, current frame and extrinsic per member"
+        return w, r, c, Xf
+
+    def linearize_rig(self, wss, refs, curs, X, level, T_body, reset_scale=True):
+        """bpvo_hip_linearize_rig: the joint normal equations of the members (workspace wss[i], template refs[i], current curs[i], extrinsic
+        X[i] camera_from_body) at the body pose T_body; T_members: the member poses the kernels were run at."""
+        w, r, c, Xf = self._rig_members(wss, refs, curs, X)
+        n = w.shape[0]
+        T = _f32(T_body).reshape(16)
+        H, G, Tm = np.empty((6, 6), np.float32), np.empty(6, np.float32), np.empty((n, 4, 4), np.float32)
+        f, nv = C.c_float(), C.c_int()
+        self.call("linearize_rig", n, w.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p),
+                  Xf.ctypes.data_as(C.c_void_p), int(level), T.ctypes.data_as(C.c_void_p), int(bool(reset_scale)), H.ctypes.data_as(C.c_void_p),
+                  G.ctypes.data_as(C.c_void_p), C.byref(f), C.byref(nv), Tm.ctypes.data_as(C.c_void_p))
+        return dict(H=H, G=G, f_norm=f.value, num_valid=nv.value, T_members=Tm)
+
+    def estimate_pose_rig(self, wss, refs, curs, X, T_init=None):
+        """bpvo_hip_estimate_pose_rig: (body pose, per-level statistics of the joint system)."""
+        w, r, c, Xf = self._rig_members(wss, refs, curs, X)
+        T0 = _f32(np.eye(4) if T_init is None else T_init).reshape(16)
+        T = np.empty((4, 4), np.float32)
+        st = (Stats * self.L)()
+        self.call("estimate_pose_rig", w.shape[0], w.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p),
+                  Xf.ctypes.data_as(C.c_void_p), T0.ctypes.data_as(C.c_void_p), T.ctypes.data_as(C.c_void_p), st)
+        return T, [dict(numIterations=s.numIterations, finalError=s.finalError,
+                        firstOrderOptimality=s.firstOrderOptimality, status=s.status) for s in st]
+
+    def rig_set(self, X, seq=None):
+        """bpvo_hip_rig_set: the rig's members are sequences seq (None: 0 .. n-1) with extrinsics X [n, 4, 4] (camera_from_body)."""
+        Xf = _f32(X).reshape(-1, 16)
+        ids, p_ids = self._seq_ids(Xf.shape[0], seq)
+        self.call("rig_set", Xf.shape[0], p_ids, Xf.ctypes.data_as(C.c_void_p))
+
+    def rig_get(self):
+        """(sequence ids [n], extrinsics [n, 4, 4]) of the declared rig; n = 0: none."""
+        n = C.c_int()
+        self._ck(self.b.fn("rig_get")(self.h, C.byref(n), None, None))
+        ids, X = np.empty(n.value, np.int32), np.empty((n.value, 4, 4), np.float32)
+        if n.value:
+            self._ck(self.b.fn("rig_get")(self.h, C.byref(n), ids.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p)))
+        return ids, X
+
+    def add_frames_rig(self, images, disps):
+        """bpvo_hip_add_frames_rig: the next frame of every member (lists of 2-D arrays in member order, each of its camera's size, or stacks
+        [n, rows, cols]); returns the body's result in add_frame's format."""
+        ids, _ = self.rig_get()
+        assert len(images) == len(ids), f"the rig has {len(ids)} members"
+        for i, s in enumerate(ids):
+            cam = self.seq_get_camera(int(s))
+            assert np.shape(images[i]) == (cam.rows, cam.cols), f"frame {i}: member {i} (sequence {s}) takes {cam.rows}x{cam.cols} frames"
+        img, disp, _ = pack_frames(list(images), list(disps))
+        r = Result()
+        self.call("add_frames_rig", img.ctypes.data_as(C.c_void_p), disp.ctypes.data_as(C.c_void_p), 0, C.byref(r))
+        return self._result_dict(r)
+
+    def add_frames_rig_device(self, d_images_ptr, d_disps_ptr):
+        """add_frames_rig with the packed frames already in device memory."""
+        r = Result()
+        self.call("add_frames_rig", C.c_void_p(d_images_ptr), C.c_void_p(d_disps_ptr), 1, C.byref(r))
+        return self._result_dict(r)
+
+    def rig_trajectory(self):
+        n = C.c_int()
+        self.call("rig_trajectory_size", C.byref(n))
+        out = np.empty((n.value, 4, 4), np.float32)
+        if n.value:
+            self.call("rig_get_trajectory", out.ctypes.data_as(C.c_void_p))
+        return out
+
     # -- batches
     def _stats_array(self, st, n_pairs):
         a = np.ctypeslib.as_array(C.cast(st, C.POINTER(C.c_int32)), shape=(n_pairs, self.L, 4)).copy()

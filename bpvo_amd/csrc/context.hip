@@ -270,7 +270,7 @@ int ensure_lanes(bpvo_hip_ctx* c, int n)
       HIP_CK(c, hipHostMalloc((void**) &ln.h_team_ctl, sizeof(unsigned) * 64));      // (two launches' first lines: estimate.hip)
       std::memset(ln.h_team_ctl, 0, sizeof(unsigned) * 64);
     }
-    HIP_CK(c, hipHostMalloc((void**) &ln.h_states, sizeof(GNState) * n_pairs));
+    HIP_CK(c, hipHostMalloc((void**) &ln.h_states, sizeof(GNState) * (n_pairs + 1)));      // (+ 1: the body state of rig mode)
   }
   return BPVO_OK;
 }
@@ -636,8 +636,9 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
     // two buffers of tile partials (the persistent kernels double-buffer them by iteration parity, kernels_gn.hip pk_partials)
     CREATE_CK(hipMalloc((void**) &w.partials, sizeof(float) * (size_t) gn_partials_entries(cp->cap_max, cp->G > 1 ? cp->Cg : cp->C) * std::max(1, (cp->G + 1) / 2) * kPartialStride));
   }
-  CREATE_CK(hipMalloc((void**) &cp->d_states, sizeof(GNState) * n_pairs));
-  CREATE_CK(hipMemset(cp->d_states, 0, sizeof(GNState) * n_pairs));
+  // (entry n_pairs: the body state of rig mode, estimate.hip estimate_rig)
+  CREATE_CK(hipMalloc((void**) &cp->d_states, sizeof(GNState) * (n_pairs + 1)));
+  CREATE_CK(hipMemset(cp->d_states, 0, sizeof(GNState) * (n_pairs + 1)));
   CREATE_CK(hipMalloc((void**) &cp->d_fjobs, 2 * sizeof(FrameJob) * (size_t) cp->L * n_frames));
   CREATE_CK(hipMalloc((void**) &cp->d_job1, sizeof(PairJob) * (1 + kMaxGroups)));      // the whole job + its channel groups (wide descriptors)
   if(cp->params.descriptor == BPVO_DESC_LATCH) {
@@ -718,7 +719,7 @@ void bpvo_hip_destroy(bpvo_hip_ctx* c)
   for(auto& f : c->frames) { (void) hipFree(f.data_slab); (void) hipFree(f.tmpl_slab); }
   for(auto& w : c->ws) { (void) hipFree(w.r); (void) hipFree(w.valid); (void) hipFree(w.cand); (void) hipFree(w.med_blk); (void) hipFree(w.tapkey); (void) hipFree(w.tapcache); (void) hipFree(w.partials); }
   (void) hipFree(c->d_states); (void) hipFree(c->d_fjobs); (void) hipFree(c->d_job1); (void) hipFree(c->d_latch_off); (void) hipFree(c->d_cloud);
-  (void) hipFree(c->d_records); (void) hipFree(c->d_wtmp);
+  (void) hipFree(c->d_records); (void) hipFree(c->d_wtmp); (void) hipFree(c->d_rig_X);
   (void) hipFree(c->d_count); (void) hipFree(c->d_counters); (void) hipFree(c->d_tickets); (void) hipFree(c->d_trace);
   (void) hipFree(c->st_left); (void) hipFree(c->st_right); (void) hipFree(c->st_left_pre); (void) hipFree(c->st_right_pre); (void) hipFree(c->st_disp);
   (void) hipFree(c->st_sgm);

@@ -572,6 +572,204 @@ int get_weights_host(bpvo_hip_ctx* c, int ws, std::vector<float>& w_cm, int* n_o
   return BPVO_OK;
 }
 
+// ---- rig mode: the cameras of a rigid rig estimated as one body pose (rig_math.h, kernels_gn_rig.hip) -------------------------------------
+// (lane 0 on the API thread: the error goes to the context; nothing stays in flight that reads the lane's pinned staging)
+#define RIG_CK(ctx_, ln_, expr)                                                             \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if(e_ != hipSuccess) {                                                                  \
+      (ctx_)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                      \
+      (void) hipStreamSynchronize((ln_)->stream);                                           \
+      return BPVO_ERR_DEVICE;                                                               \
+    }                                                                                       \
+  } while(0)
+// Every check of a rig estimate over pyramid levels level_lo .. level_hi, before anything is queued
+static int rig_check(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, int level_lo, int level_hi)
+{
+  if(n < 1 || n > c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "rig: n must be within 1 .. the context's workspaces");
+  if(!wss || !refs || !curs || !X) return fail(c, BPVO_ERR_INVALID_ARG, "rig: nullptr members / extrinsics");
+  // (DisparitySpaceWarp's parameters are no rigid-body twist of the camera frame: Ad(X) does not carry them to the body)
+  if(c->dspace) return fail(c, BPVO_ERR_UNSUPPORTED, "rig mode does not serve BPVO_WARP_DISPARITY_SPACE_F32");
+  for(int i = 0; i < n; ++i) {
+    if(wss[i] < 0 || wss[i] >= c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "bad workspace");
+    for(int k = 0; k < i; ++k)
+      if(wss[k] == wss[i]) return fail(c, BPVO_ERR_INVALID_ARG, "rig: a workspace appears twice");
+    if(refs[i] < 0 || refs[i] >= c->n_frames || curs[i] < 0 || curs[i] >= c->n_frames) return fail(c, BPVO_ERR_INVALID_ARG, "bad frame slot");
+    if(!rig_extrinsic_ok(X + 16 * (size_t) i)) return fail(c, BPVO_ERR_INVALID_ARG, "rig: an extrinsic is not a rigid transform (finite, last row 0 0 0 1, R^T R = I within 1e-4)");
+  }
+  for(int i = 0; i < n; ++i) {
+    if(!c->frames[refs[i]].has_template) return fail(c, BPVO_ERR_NO_TEMPLATE, "reference frame has no template");
+    if(!c->frames[curs[i]].has_data) return fail(c, BPVO_ERR_NO_DATA, "no data in frame");
+    for(int l = level_lo; l <= level_hi; ++l)
+      if(c->frames[refs[i]].n_host[l] <= 0) return fail(c, BPVO_ERR_NO_TEMPLATE, "you should call setData before calling computeResiduals");
+  }
+  for(int i = 0; i < n; ++i)
+    if(int rc = ensure_dense_descriptor(c, curs[i])) return rc;
+  return BPVO_OK;
+}
+// the members' job tables (every level, as estimate_group lays them out) and extrinsics to the device, on lane 0; max_pts[l]: the most points of a member at level l
+static int rig_upload(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* refs, const int* curs, const float* X, std::vector<int>& max_pts)
+{
+  const int NP = c->n_pairs;
+  const size_t table = (size_t) c->L * NP;
+  max_pts.assign((size_t) c->L, 0);
+  for(int l = 0; l < c->L; ++l)
+    for(int i = 0; i < n; ++i) {
+      PairJob& pj = ln->h_pjobs[(size_t) l * NP + i];
+      pj = make_pair_job(c, wss[i], refs[i], curs[i], l);
+      for(int k = 0; k < c->G && c->G > 1; ++k) ln->h_pjobs[(size_t) (1 + k) * table + (size_t) l * NP + i] = group_pair_job(c, pj, k);
+      max_pts[l] = std::max(max_pts[l], pj.n);
+    }
+  RIG_CK(c, ln, hipMemcpyAsync(ln->d_pjobs, ln->h_pjobs, sizeof(PairJob) * table * (size_t) job_tables(c), hipMemcpyHostToDevice, ln->stream));
+  if(!c->d_rig_X) RIG_CK(c, ln, hipMalloc((void**) &c->d_rig_X, sizeof(float) * 16 * (size_t) NP));
+  // (from the caller's pageable memory: the copy has left it when the call returns)
+  RIG_CK(c, ln, hipMemcpyAsync(c->d_rig_X, X, sizeof(float) * 16 * (size_t) n, hipMemcpyHostToDevice, ln->stream));
+  return BPVO_OK;
+}
+static GNLaunch rig_level_launch(const bpvo_hip_ctx* c, const Lane* ln, int level, int n, int max_points)
+{
+  GNLaunch g;
+  g.jobs = ln->d_pjobs + (size_t) level * c->n_pairs;
+  g.npairs = n;
+  g.max_points = max_points;
+  g.C = c->C;
+  g.loss = c->params.lossFunction;
+  g.fast_warp = c->fast_warp;
+  g.interp = c->params.interp;
+  g.reference_reduction = c->reference_reduction ? 1 : 0;
+  g.dense_candidates = dense_candidates(c, max_points);
+  return g;      // (fuse_frozen and step_in_reduce stay 0: both assume a step per workspace)
+}
+// one linearisation of every member at its state's pose: the chain's own kernels, the step in its linearise-only mode (what bpvo_hip_linearize queues)
+static void rig_linearize_members(bpvo_hip_ctx* c, Lane* ln, const GNLaunch& g)
+{
+  const size_t table = (size_t) c->L * c->n_pairs;
+  { ScopedTimer t(c, KC_WARP_RESIDUAL, 0.0, ln, c->profile_all); for_each_group(c, g, table, [&](const GNLaunch& gg) { launch_warp_residual(ln->stream, gg); }); }
+  { ScopedTimer t(c, KC_MEDIAN, 0.0, ln, c->profile_all); launch_median(ln->stream, median_launch(c, g)); }
+  {
+    ScopedTimer t(c, KC_IRLS_REDUCE, 0.0, ln, c->profile_all);
+    if(g.reference_reduction) launch_irls_reduce(ln->stream, g);
+    else for_each_group(c, g, table, [&](const GNLaunch& gg) { launch_irls_reduce(ln->stream, gg); });
+  }
+  { ScopedTimer t(c, KC_GN_STEP, 0.0, ln, c->profile_all); launch_gn_step(ln->stream, g, 1); }
+}
+
+int estimate_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, const float* T_init, float* T_est, bpvo_hip_stats* stats)
+{
+  const bpvo_hip_params& p = c->params;
+  if(!T_init || !T_est) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr pose");
+  int rc = rig_check(c, n, wss, refs, curs, X, p.maxTestLevel, c->L - 1);
+  if(rc) return rc;
+  (void) hipSetDevice(c->device);
+  Lane* ln = &c->lanes[0];      // (the context's stream: the estimate queues behind the frame stages)
+  c->frac_valid = false;
+  RIG_CK(c, ln, join_pending_normalization(c, ln->stream));
+  // The loop iterates on the pose of the REFERENCE member (member 0) in its normalised twist (rig_math.h: the f32 solve wants a normalised
+  // system; a rig of one camera takes that camera's own steps): the extrinsics relative to it, its initial pose, and the body pose at the end
+  std::vector<float> X_rel((size_t) n * 16);
+  for(int i = 0; i < n; ++i) rig_relative_extrinsic(X + 16 * (size_t) i, X, &X_rel[16 * (size_t) i]);
+  std::vector<int> max_pts;
+  rc = rig_upload(c, ln, n, wss, refs, curs, X_rel.data(), max_pts);
+  if(rc) return rc;
+  const int NP = c->n_pairs;
+  GNState* body = c->d_states + NP;
+  rig_member_pose(X, T_init, ln->h_T);
+  RIG_CK(c, ln, hipMemcpyAsync(ln->d_Tinit, ln->h_T, 16 * sizeof(float), hipMemcpyHostToDevice, ln->stream));
+  launch_set_pose(ln->stream, ln->d_pjobs + (size_t) (c->L - 1) * NP, nullptr, n);
+  // the rounds of estimate_group: kItersPerSync iterations queued per round, round r + 1 queued while the flag of round r - 1 lands; the flag is the
+  // BODY's `active` (the rig step clears the members' with it)
+  const int max_lin = std::min(std::max(p.maxIterations, 0) + 2, kMaxFunEvals);
+  const int kItersPerSync = 4;
+  const int max_rounds = (max_lin + kItersPerSync - 1) / kItersPerSync + 2;
+  for(int l = c->L - 1; l >= p.maxTestLevel; --l) {
+    const GNLaunch g = rig_level_launch(c, ln, l, n, max_pts[l]);
+    launch_level_begin(ln->stream, g.jobs, n, g.max_points, l, 0);
+    RigStepArgs a{g.jobs, n, c->d_rig_X, body, 2, l, l == c->L - 1 ? ln->d_Tinit : nullptr, 1};
+    launch_rig_step(ln->stream, a);
+    a.mode = 0; a.T_init = nullptr;
+    for(int round = 0; round < max_rounds; ++round) {
+      for(int k = 0; k < kItersPerSync; ++k) {
+        rig_linearize_members(c, ln, g);
+        launch_rig_step(ln->stream, a);
+      }
+      const int slot = round % 3;
+      RIG_CK(c, ln, hipMemcpyAsync(ln->h_active + 2 * slot, &body->active, sizeof(int), hipMemcpyDeviceToHost, ln->stream));
+      RIG_CK(c, ln, hipEventRecord(ln->round_ev[slot], ln->stream));
+      if(round == 0) continue;
+      const int prev = (round - 1) % 3;
+      RIG_CK(c, ln, hipEventSynchronize(ln->round_ev[prev]));
+      if(ln->h_active[2 * prev] == 0) break;      // (the round just queued runs empty)
+    }
+  }
+  RIG_CK(c, ln, hipMemcpyAsync(ln->h_states + NP, body, sizeof(GNState), hipMemcpyDeviceToHost, ln->stream));
+  RIG_CK(c, ln, hipStreamSynchronize(ln->stream));
+  RIG_CK(c, ln, hipGetLastError());
+  resolve_events(c);
+  const GNState& st = ln->h_states[NP];
+  rig_body_pose(X, st.T_out, T_est);      // X_0^-1 T_0 X_0
+  if(stats)
+    for(int l = 0; l < c->L; ++l) stats[l] = st.stats[l];
+  for(int i = 0; i < n; ++i) {
+    Workspace& w = c->ws[wss[i]];
+    w.last_ref = refs[i]; w.last_cur = curs[i]; w.last_level = p.maxTestLevel;
+  }
+  return BPVO_OK;
+}
+
+}  // namespace bpvo_hip_host
+
+extern "C" {
+
+int bpvo_hip_linearize_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, int level, const float T_body[16],
+                           int reset_scale, float H[36], float G[6], float* f_norm, int* num_valid, float* T_members)
+{
+  CHECK_CTX(c); CHECK_LEVEL(c, level);
+  if(!T_body || !H || !G || !f_norm || !num_valid) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr pose / outputs");
+  int rc = rig_check(c, n, wss, refs, curs, X, level, level);
+  if(rc) return rc;
+  (void) hipSetDevice(c->device);
+  Lane* ln = &c->lanes[0];
+  c->frac_valid = false;
+  RIG_CK(c, ln, join_pending_normalization(c, ln->stream));
+  std::vector<int> max_pts;
+  rc = rig_upload(c, ln, n, wss, refs, curs, X, max_pts);
+  if(rc) return rc;
+  const int NP = c->n_pairs;
+  GNState* body = c->d_states + NP;
+  for(int i = 0; i < n; ++i) rig_member_pose(X + 16 * (size_t) i, T_body, ln->h_T + 16 * (size_t) i);      // the poses the members' kernels run at
+  if(T_members) std::memcpy(T_members, ln->h_T, sizeof(float) * 16 * (size_t) n);
+  RIG_CK(c, ln, hipMemcpyAsync(ln->d_Tinit, ln->h_T, sizeof(float) * 16 * (size_t) n, hipMemcpyHostToDevice, ln->stream));
+  const GNLaunch g = rig_level_launch(c, ln, level, n, max_pts[level]);
+  for(int i = 0; i < n; ++i) launch_prepare_linearize(ln->stream, g.jobs + i, ln->d_Tinit + 16 * (size_t) i, reset_scale ? 1 : 0, level);
+  launch_reset_tapkeys(ln->stream, g);
+  rig_linearize_members(c, ln, g);
+  launch_rig_step(ln->stream, RigStepArgs{g.jobs, n, c->d_rig_X, body, 1, level, nullptr, 0});
+  RIG_CK(c, ln, hipMemcpyAsync(ln->h_states + NP, body, sizeof(GNState), hipMemcpyDeviceToHost, ln->stream));
+  RIG_CK(c, ln, hipStreamSynchronize(ln->stream));
+  RIG_CK(c, ln, hipGetLastError());
+  resolve_events(c);
+  const GNState& st = ln->h_states[NP];
+  std::memcpy(H, st.H, sizeof(st.H));
+  std::memcpy(G, st.G, sizeof(st.G));
+  *f_norm = st.f_norm;
+  *num_valid = (int) st.n_valid;
+  for(int i = 0; i < n; ++i) {
+    Workspace& w = c->ws[wss[i]];
+    w.last_ref = refs[i]; w.last_cur = curs[i]; w.last_level = level;
+  }
+  return BPVO_OK;
+}
+int bpvo_hip_estimate_pose_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, const float T_init[16],
+                               float T_est[16], bpvo_hip_stats* stats)
+{
+  CHECK_CTX(c);
+  return estimate_rig(c, n, wss, refs, curs, X, T_init, T_est, stats);
+}
+
+}  // extern "C"
+
+namespace bpvo_hip_host {
+
 int check_template_not_empty(bpvo_hip_ctx* c, int ref_slot)
 {
   if(ref_slot < 0 || ref_slot >= c->n_frames || !c->frames[ref_slot].has_template) return BPVO_OK;   // reported elsewhere

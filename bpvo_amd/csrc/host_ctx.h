@@ -26,6 +26,7 @@
 
 #include "kernels.h"
 #include "latch_table.h"
+#include "rig_math.h"
 #include "vo_state.h"
 
 using namespace bpvo_hip;
@@ -197,6 +198,13 @@ struct bpvo_hip_ctx {
   unsigned* d_seq_cnt = nullptr;
   size_t* h_seq_off = nullptr;                     // pinned [seq_capacity]: pixel offsets of the frames of a mixed-size call in the packed device inputs
   size_t* d_seq_off = nullptr;
+  // Rig mode (bpvo_hip_rig_set ... bpvo_hip_add_frames_rig, vo.hip): the cameras of a rigid rig = sequences rig_seq[0 .. n) with extrinsics rig_X
+  // (camera_from_body, [n][16]) estimated as one body pose; rig_body keeps the body's T_kf and trajectory (its slot roles are unused: every member
+  // keeps its own).  A context with a rig (rig_seq not empty) serves bpvo_hip_add_frames_rig only.  d_rig_X: the extrinsics of the estimate under way.
+  std::vector<int> rig_seq;
+  std::vector<float> rig_X;
+  SeqState rig_body;
+  float* d_rig_X = nullptr;        // [n_pairs][16], allocated at its first use
   // measurement
   double points_fused = 0;     // points linearised through the fused path since the last counter reset
   int fast_warp = 0;           // bpvo_hip_set_warp_formulation
@@ -519,6 +527,9 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
                    bpvo_hip_stats* stats, float* d_records_out, bool allow_persistent, const bpvo_hip_params* const* prms = nullptr);
 int estimate_batch(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses, bpvo_hip_stats* stats,
                    const bpvo_hip_params* const* prms = nullptr);
+// Rig mode: members i = (workspace wss[i], template refs[i], current curs[i]) with extrinsics X [n][16] estimated as ONE body pose from T_init (the
+// coarse-to-fine loop of estimate_group on the four-kernel chain, kernels_gn_rig.hip's step in the place of gn_step); T_est and stats [L] are the body's
+int estimate_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, const float* T_init, float* T_est, bpvo_hip_stats* stats);
 void detile_to_channel_major(const float* src, int n, int C, int E, int V, float* out);
 size_t tiled_floats(int n, int floats_per_point);
 int refresh_counters(bpvo_hip_ctx* c);

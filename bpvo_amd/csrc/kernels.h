@@ -213,6 +213,22 @@ int  gn_team_ctl_words(int n_teams);
 void launch_team_ctl_reset_keep_abort(hipStream_t s, unsigned* ctl, int n_teams);   // between the launches of a split run: every control word to 0 but the abort word
 int  gn_team_max_size();       // teams stop admitting newcomers at this size
 hipError_t launch_gn_team(hipStream_t s, const GNTeamLaunch& t);
+// Rig mode (kernels_gn_rig.hip): the step of n members' jobs (one level's row of the job table, members 0 .. n-1) estimated as one body pose.
+// X: device [n][16] camera_from_body; body: the body's GNState (the entry behind the workspaces' states).  mode 0: the full step from the
+// members' linearisations (launch_gn_step mode 1 before it) and every member's next pose; 1: the joint linearisation only; 2: the start of
+// pyramid level `level` (the body's reset, the members' poses from the body's) — and, T_init (device [16]) non-null, of the estimate.
+struct RigStepArgs {
+  const PairJob* jobs;
+  int n;
+  const float* X;
+  GNState* body;
+  int mode, level;
+  const float* T_init;
+  // 1 (the estimate loops): the step is taken in the REFERENCE member's normalised twist — jobs[0]'s —, body's T is that member's pose, X the
+  // extrinsics relative to it (X[0] the identity) and T_init that member's initial pose; 0: the plain body twist of the body pose
+  int reference;
+};
+void launch_rig_step(hipStream_t s, const RigStepArgs& a);
 void launch_prepare_linearize(hipStream_t s, const PairJob* job, const float* T /*device [16]*/, int reset_scale, int level, float given_scale = 0.0f);
 int  gn_pts_per_block(int C);
 int  gn_partials_entries(int cap, int C);   // kPartialStride-float entries of a workspace's (double-buffered) tile partials

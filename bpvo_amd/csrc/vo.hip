@@ -328,6 +328,7 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
 {
   if(!ret) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
   if(c->n_frames < 3) return fail(c, BPVO_ERR_INVALID_ARG, "add_frame needs a ctx with n_frames >= 3");
+  if(!c->rig_seq.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares a rig (bpvo_hip_rig_set): it serves bpvo_hip_add_frames_rig only");
   if(c->vo_mode == 2) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frames: a context serves either add_frame or add_frames");
   c->vo_mode = 1;
   (void) hipSetDevice(c->device);
@@ -557,6 +558,7 @@ extern "C" {
 static int add_frames_check(bpvo_hip_ctx* c, int n, const int* seq, const void* images, const void* second, const char* what_null, bpvo_hip_result* results,
                             std::vector<int>& ids)
 {
+  if(!c->rig_seq.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares a rig (bpvo_hip_rig_set): it serves bpvo_hip_add_frames_rig only");
   if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a context serves either add_frame or add_frames");
   const int S = seq_capacity(c);
   if(S < 1) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames needs a ctx with n_frames >= 3 and n_pairs >= 1");
@@ -748,6 +750,185 @@ int bpvo_hip_add_frames(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* i
   const int rc = add_frames_check(c, n, seq, images, disparities, "nullptr image/disparity", results, ids);
   if(rc) return rc;
   return add_frames_run(c, n, ids, images, disparities, on_device != 0, results);
+}
+// ---- rig mode: the cameras of a rigid rig as ONE body (c_api.h; rig_math.h states the maps) ------------------------------------------------
+// Member p of the rig is sequence rig_seq[p] — its frame slots, its workspace, its camera — with extrinsic rig_X[p] (camera_from_body).  A call
+// runs the phases of add_frames_run once for the rig: one data stage over the members' frames, ONE estimate of the body pose from all members'
+// residuals (estimate_rig), one key-frame decision on the body pose with the fraction of good points pooled over the members, and every
+// member the same transition (vo_state.h: vo_rig_*).  The body keeps T_kf and the trajectory.
+int bpvo_hip_rig_set(bpvo_hip_ctx* c, int n, const int* seq, const float* X)
+{
+  CHECK_CTX(c);
+  if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a rig's members are sequences of bpvo_hip_add_frames' kind");
+  const int S = seq_capacity(c);
+  if(n < 1 || n > S) return fail(c, BPVO_ERR_INVALID_ARG, "rig_set: n must be within 1 .. the sequence capacity");
+  if(!X) return fail(c, BPVO_ERR_INVALID_ARG, "rig_set: nullptr extrinsics");
+  std::vector<int> ids((size_t) n);
+  std::vector<char> seen((size_t) S, 0);
+  for(int i = 0; i < n; ++i) {
+    ids[i] = seq ? seq[i] : i;
+    if(ids[i] < 0 || ids[i] >= S) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "no such sequence");
+    if(seen[ids[i]]) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "appears twice in the rig");
+    seen[ids[i]] = 1;
+  }
+  for(int i = 0; i < n; ++i)
+    if(!rig_extrinsic_ok(X + 16 * (size_t) i))
+      return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "extrinsic is not a rigid transform (finite, last row 0 0 0 1, R^T R = I within 1e-4)");
+  for(int i = 0; i < n; ++i)
+    if(int rc = seq_is_fresh(c, ids[i], "rig membership changes")) return rc;
+  for(int s : c->rig_seq)      // (a rig declared before: its members leave it only fresh, too)
+    if(int rc = seq_is_fresh(c, s, "rig membership changes")) return rc;
+  for(int i = 0; i < n && !c->seqs.empty(); ++i)
+    if(c->seqs[ids[i]].own_params) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "has parameters of its own: a rig runs the context's parameters");
+  seq_states(c);
+  c->rig_seq = ids;
+  c->rig_X.assign(X, X + 16 * (size_t) n);
+  vo_reset(c->rig_body, 0);
+  c->rig_body.params = c->params;
+  c->vo_mode = 2;
+  return BPVO_OK;
+}
+int bpvo_hip_rig_get(const bpvo_hip_ctx* c, int* n, int* seq, float* X)
+{
+  if(!c || !n) return BPVO_ERR_INVALID_ARG;
+  *n = (int) c->rig_seq.size();
+  if(seq) std::copy(c->rig_seq.begin(), c->rig_seq.end(), seq);
+  if(X) std::copy(c->rig_X.begin(), c->rig_X.end(), X);
+  return BPVO_OK;
+}
+int bpvo_hip_rig_trajectory_size(bpvo_hip_ctx* c, int* n)
+{
+  CHECK_CTX(c);
+  if(!n) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr count");
+  *n = c->rig_seq.empty() ? 0 : vo_trajectory_size(&c->rig_body);
+  return BPVO_OK;
+}
+int bpvo_hip_rig_get_trajectory(bpvo_hip_ctx* c, float* poses)
+{
+  CHECK_CTX(c);
+  if(c->rig_seq.empty()) return BPVO_OK;
+  if(!poses && vo_trajectory_size(&c->rig_body) > 0) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr poses");
+  vo_get_trajectory(&c->rig_body, poses);
+  return BPVO_OK;
+}
+int bpvo_hip_add_frames_rig(bpvo_hip_ctx* c, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* result)
+{
+  CHECK_CTX(c);
+  // 1. every check before any state changes
+  const int n = (int) c->rig_seq.size();
+  if(n < 1) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames_rig: the context declares no rig (bpvo_hip_rig_set)");
+  if(!images || !disparities) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image/disparity");   // bpvo/vo.cc:68-69
+  if(!result) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
+  const bpvo_hip_params& p = c->params;
+  const int L = c->L, lvl = p.maxTestLevel;
+  const std::vector<int>& ids = c->rig_seq;
+  const float* X = c->rig_X.data();
+  std::vector<SeqState*> members((size_t) n);
+  for(int i = 0; i < n; ++i) {
+    members[i] = &c->seqs[ids[i]];
+    if(members[i]->own_params) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "has parameters of its own: a rig runs the context's parameters");
+  }
+  const bool first = !c->frames[members[0]->ref].has_template;
+  if(c->dspace) return fail(c, BPVO_ERR_UNSUPPORTED, "rig mode does not serve BPVO_WARP_DISPARITY_SPACE_F32");
+  for(int i = 0; i < n && !first; ++i) {
+    const FrameSlot& ref = c->frames[members[i]->ref];
+    for(int l = lvl; l < L; ++l)      // template_data.cc:177 (check_template_not_empty)
+      if(!ref.has_template || ref.n_host[l] <= 0)
+        return seq_fail(c, BPVO_ERR_NO_TEMPLATE, ids[i], "the key frame's template is empty (you should call setData before calling computeResiduals)");
+  }
+  (void) hipSetDevice(c->device);
+  int rc = seq_storage(c);
+  if(rc) return rc;
+  SeqState& body = c->rig_body;
+  vo_begin_frame(body, L, result);
+  for(int i = 0; i < n; ++i) { bpvo_hip_result own; vo_begin_frame(*members[i], L, &own); }
+  auto drain = [&](int code) { (void) hipStreamSynchronize(c->stream); return code; };
+  auto template_stage = [&](const int* sl, int count, const size_t*, const FrameRun& fr) { return frames_set_template_slots(c, sl, count, fr); };
+
+  // 2. setData of every member: one data stage (frame i: its camera's pixels, the frames back to back in member order)
+  std::vector<int> slots((size_t) n);
+  std::vector<size_t> offsets((size_t) n);
+  size_t at = 0;
+  for(int i = 0; i < n; ++i) {
+    slots[i] = members[i]->cur;
+    offsets[i] = at;
+    at += slot_geom(c, c->frames[slots[i]], 0).npix;
+  }
+  rc = for_each_size(c, slots, &offsets, [&](const int* sl, int count, const size_t* off, const FrameRun& fr) {
+    return frames_set_data_slots(c, sl, count, images, disparities, on_device != 0, fr, 0, off);
+  });
+  if(rc) return drain(rc);
+
+  // 3. the first frame: every member's template
+  if(first) {
+    for(int i = 0; i < n; ++i) slots[i] = vo_first_frame(*members[i]);
+    rc = for_each_size(c, slots, nullptr, template_stage);
+    if(rc) return drain(rc);
+    vo_rig_first_frame_done(body, members.data(), n, result);
+    return BPVO_OK;
+  }
+
+  // 4. the body pose from every member's residuals, from the body's T_kf
+  std::vector<int> wss(ids), refs((size_t) n), curs((size_t) n);
+  for(int i = 0; i < n; ++i) { refs[i] = members[i]->ref; curs[i] = members[i]->cur; }
+  M44 T_est, T_again;
+  rc = estimate_rig(c, n, wss.data(), refs.data(), curs.data(), X, body.T_kf.m, T_est.m, result->optimizerStatistics);
+  if(rc) return drain(rc);
+
+  // 5. ONE key-frame decision: the body's motion, then the fraction of good points pooled over the members (one count launch)
+  int max_n = 0;
+  std::vector<int> n_points((size_t) n);
+  for(int i = 0; i < n; ++i) {
+    c->h_seq_jobs[i] = make_pair_job(c, wss[i], refs[i], curs[i], lvl);
+    n_points[i] = c->h_seq_jobs[i].n;
+    max_n = std::max(max_n, n_points[i]);
+  }
+  HIP_CK(c, hipMemcpyAsync(c->d_seq_jobs, c->h_seq_jobs, sizeof(PairJob) * (size_t) n, hipMemcpyHostToDevice, c->stream));
+  HIP_CK(c, hipMemsetAsync(c->d_seq_cnt, 0, sizeof(unsigned) * (size_t) n, c->stream));
+  launch_count_good_batch(c->stream, c->d_seq_jobs, n, max_n, c->C, p.lossFunction, p.goodPointThreshold, c->d_seq_cnt);
+  HIP_CK(c, hipMemcpyAsync(c->h_seq_cnt, c->d_seq_cnt, sizeof(unsigned) * (size_t) n, hipMemcpyDeviceToHost, c->stream));
+  HIP_CK(c, hipStreamSynchronize(c->stream));
+  HIP_CK(c, hipGetLastError());
+  bool again = false;
+  if(vo_decide(p, T_est, vo_rig_fraction_good(c->h_seq_cnt, n_points.data(), n, c->C), result)) {
+    // 6. the key frame: every member's point cloud from its old key frame and its last linearisation, the new templates, the estimate against them
+    const size_t cap = (size_t) c->geom[lvl].cap;
+    std::vector<size_t> cloud_points((size_t) n);
+    int max_c = 0;
+    for(int i = 0; i < n; ++i) {
+      if((size_t) n_points[i] > cap) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "size mismatch");
+      const FrameSlot& kfr = c->frames[refs[i]];
+      CloudJob& cj = c->h_cloud_jobs[i];
+      cj.job = c->d_seq_jobs + i; cj.img = kfr.img[0]; cj.out_offset = (size_t) ids[i] * cap;
+      std::memcpy(cj.K, slot_geom(c, kfr, lvl).K, sizeof(cj.K));
+      cj.rows = slot_geom(c, kfr, 0).rows; cj.cols = slot_geom(c, kfr, 0).cols;
+      cj.loss = p.lossFunction;
+      cloud_points[i] = (size_t) n_points[i];
+      max_c = std::max(max_c, n_points[i]);
+    }
+    HIP_CK(c, hipMemcpyAsync(c->d_cloud_jobs, c->h_cloud_jobs, sizeof(CloudJob) * (size_t) n, hipMemcpyHostToDevice, c->stream));
+    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, n, max_c, c->C, c->dspace, c->d_seq_cloud);
+    HIP_CK(c, hipGetLastError());
+    std::vector<KeyFrameSlots> ks((size_t) n);
+    vo_rig_keyframe(members.data(), n, c->frames[members[0]->prev].has_data, cloud_points.data(), ks.data(), result);
+    for(int i = 0; i < n; ++i) {
+      if(ks[i].clear_slot >= 0) slot_clear(c, ks[i].clear_slot);
+      slots[i] = ks[i].template_slot;
+    }
+    rc = for_each_size(c, slots, nullptr, template_stage);
+    if(rc) return drain(rc);
+    if(ks[0].reestimate) {
+      for(int i = 0; i < n; ++i) { refs[i] = members[i]->ref; curs[i] = members[i]->cur; }
+      const M44 I = m44_identity();
+      rc = estimate_rig(c, n, wss.data(), refs.data(), curs.data(), X, I.m, T_again.m, result->optimizerStatistics);
+      if(rc) return drain(rc);
+      again = true;
+    }
+  }
+
+  // 7. the pose, T_kf and the trajectory of the body; every member's slots, and its cloud's pose
+  vo_rig_finish(body, members.data(), X, n, T_est, again ? &T_again : nullptr, result);
+  return BPVO_OK;
 }
 // StereoAlgorithm::run + addFrame of every sequence of the call (apps/vo_app.cc per camera): the front-end once over all the pairs, each in
 // its sequence's camera geometry, into the context's own maps, which the frame stages then read where they lie — no host synchronisation

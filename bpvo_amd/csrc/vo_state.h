@@ -10,6 +10,7 @@
 
 #include "../../include/bpvo_hip/c_api.h"
 #include "device_math.h"
+#include "rig_math.h"
 
 namespace bpvo_hip_host {
 using namespace bpvo_hip;
@@ -147,6 +148,50 @@ inline void vo_finish(SeqState& q, const M44& T_est, const M44* T_again, bpvo_hi
   std::memcpy(ret->pose, pose.m, 64);
   trajectory_push(q.trajectory, pose);
   if(ret->hasPointCloud) q.cloud_pose = q.trajectory.back();
+}
+
+// ---- rig mode (bpvo_hip_add_frames_rig): the cameras of a rigid rig advance in lock step as ONE body.  The body's SeqState keeps T_kf and the
+// trajectory (its slot roles are unused); every member takes the same transition on its own slots.  X: the extrinsics [n][16], camera_from_body.
+// The fraction of good points of the rig's one decision: pooled over the members, sum good_p / sum n_p C (one member: vo_fraction_good)
+inline float vo_rig_fraction_good(const unsigned* good_counts, const int* n_points, int n, int C)
+{
+  size_t good = 0, total = 0;
+  for(int p = 0; p < n; ++p) { good += good_counts[p]; total += (size_t) n_points[p] * C; }
+  return good / static_cast<float>(total);
+}
+// the first frame of every member, then of the body (each member's template is queued between vo_first_frame and this)
+inline void vo_rig_first_frame_done(SeqState& body, SeqState* const* members, int n, bpvo_hip_result* ret)
+{
+  for(int p = 0; p < n; ++p) {
+    bpvo_hip_result own = *ret;
+    vo_first_frame_done(*members[p], &own);
+  }
+  vo_first_frame_done(body, ret);
+}
+// the rig's decision (vo_decide on the body pose with the pooled fraction) was "key frame": vo_keyframe of every member, slots[p] what its caller does
+inline void vo_rig_keyframe(SeqState* const* members, int n, bool prev_has_data, const size_t* cloud_points, KeyFrameSlots* slots, bpvo_hip_result* ret)
+{
+  for(int p = 0; p < n; ++p) {
+    bpvo_hip_result own = *ret;
+    slots[p] = vo_keyframe(*members[p], prev_has_data, cloud_points[p], &own);
+  }
+  ret->hasPointCloud = 1;
+}
+// vo_finish of the body with the body's estimates and of every member with its own, X_p T X_p^-1; a member's point cloud gets the pose
+// W_kf X_p^-1 (world_from_camera), W_kf the pose the body's trajectory gives the cloud (SeqState::cloud_pose of the body)
+inline void vo_rig_finish(SeqState& body, SeqState* const* members, const float* X, int n, const M44& T_est, const M44* T_again, bpvo_hip_result* ret)
+{
+  vo_finish(body, T_est, T_again, ret);
+  if(ret->hasPointCloud) body.cloud_n = 0;      // (the clouds are the members')
+  for(int p = 0; p < n; ++p) {
+    const float* Xp = X + 16 * (size_t) p;
+    M44 Tp, Tpa;
+    rig_member_pose(Xp, T_est.m, Tp.m);
+    if(T_again) rig_member_pose(Xp, T_again->m, Tpa.m);
+    bpvo_hip_result own = *ret;
+    vo_finish(*members[p], Tp, T_again ? &Tpa : nullptr, &own);
+    if(ret->hasPointCloud) rig_cloud_pose(body.cloud_pose.m, Xp, members[p]->cloud_pose.m);
+  }
 }
 
 }  // namespace bpvo_hip_host

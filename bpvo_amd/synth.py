@@ -353,6 +353,32 @@ def make_sequence(rows: int, cols: int, n_frames: int, index: int = 0, step_rot:
     return dict(K=K, b=b, frames=frames, poses=poses)
 
 
+def make_rig_sequence(rows: int, cols: int, n_frames: int, extrinsics, index: int = 0, step_rot: float = 0.004, step_trans: float = 0.03, cameras=None):
+    """make_sequence's plane seen by the cameras of a rigid rig: the body follows make_sequence's trajectory (poses[k] = T_k, body_k from
+    body_0), member p with extrinsic extrinsics[p] (4x4 camera_from_body) is rendered from extrinsics[p] @ T_k.  cameras: None (every member
+    calibration(rows, cols)) or per member (K 3x3, baseline, rows, cols).  Returns dict(K, b [per member], frames [k][p] = (img, disp),
+    poses [k], extrinsics)."""
+    seed = 1000 + int(index)
+    rng = np.random.default_rng(seed)
+    X = [np.asarray(x, dtype=np.float64).reshape(4, 4) for x in extrinsics]
+    cams = []
+    for p in range(len(X)):
+        if cameras is None:
+            K, b = calibration(rows, cols)
+            cams.append((K, b, rows, cols))
+        else:
+            K, b, r, c = cameras[p]
+            cams.append((np.asarray(K, dtype=np.float32).reshape(3, 3), float(b), int(r), int(c)))
+    T = np.eye(4)
+    frames, poses = [], []
+    for f in range(n_frames):
+        frames.append([_render(K, b, r, c, X[p] @ T, seed, 10.0, (0.1, -0.15)) for p, (K, b, r, c) in enumerate(cams)])
+        poses.append(T.copy())
+        tw = np.concatenate([rng.uniform(-step_rot, step_rot, 3), rng.uniform(-step_trans, step_trans, 3)])
+        T = twist_to_matrix(tw) @ T
+    return dict(K=[c[0] for c in cams], b=[c[1] for c in cams], frames=frames, poses=poses, extrinsics=X)
+
+
 def make_stereo_sequence(rows: int, cols: int, n_frames: int, index: int = 0, step_rot: float = 0.004, step_trans: float = 0.03, camera=None):
     """make_sequence with the right image of every frame (the rig's right camera sits the baseline along +x of the left one):
     list of (left, right) and the true left disparities — input of the stereo front-end + addFrame.  camera=(K 3x3, baseline): as

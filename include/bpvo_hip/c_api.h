@@ -397,6 +397,51 @@ int bpvo_hip_stereo_frames(bpvo_hip_ctx* ctx, int n, const bpvo_hip_camera* cams
 int bpvo_hip_add_frames_stereo(bpvo_hip_ctx* ctx, int n, const int* seq /*[n] distinct ids, NULL = 0..n-1*/, const uint8_t* left,
                                const uint8_t* right, int on_device, const bpvo_hip_stereo_params* sp, bpvo_hip_result* results /*[n]*/);
 
+/* ---- rig mode: the cameras of a rigid rig estimated as ONE 6-DoF body pose, from all cameras' residuals at once.
+ * Twists are ordered (omega, v).  The body pose T maps key-frame body coordinates to current body coordinates (the role T plays for one
+ * camera).  Member p has the extrinsic X_p, camera_from_body (x_cam = X_p x_body; rigid), and runs at the pose T_p = X_p T X_p^-1 (f64,
+ * narrowed to f32).  Its linearisation at T_p gives (H_p, G_p) in its Hartley-normalised twist xi — its update would be
+ * T_p <- T_p N_p^-1 exp(-xi) N_p with N_p = [sI, -s c; 0 1] —; with the body update T <- T exp(-zeta) that twist is xi = B_p zeta,
+ *     B_p = A_p^-1 Ad(X_p),   A_p^-1 = [[I, 0], [-s [c]x, sI]]  (A_p = [[I, 0], [[c]x, I/s]]; without normalisation A_p = I),   Ad(X) = [[R, 0], [[t]x R, R]],
+ * and the joint system is H = sum_p B_p^T H_p B_p, G = sum_p B_p^T G_p, f = sqrt(sum_p f_p^2), valid = sum_p valid_p (member order, f64,
+ * narrowed to f32 once).  H zeta = G is solved and T <- T twist_to_matrix(-zeta) applied per iteration, with the convergence tests, iteration
+ * limits and statistics of a single camera's run; every member keeps its own robust scale.  bpvo_hip_linearize_rig returns exactly this system.
+ * The ESTIMATE takes the same Gauss-Newton steps in a normalised parametrisation, because the f32 solve wants one (a camera's plain-twist H has
+ * a condition number of 2e4 where its normalised H has 30): it iterates on the pose T_0 of the reference member (member 0) in that member's
+ * normalised twist xi_0 = B_0 zeta, so that member p's map is B_p B_0^-1 = A_p^-1 Ad(X_p X_0^-1) A_0 (the identity for p = 0), the convergence
+ * tests read (xi_0, f, |G|_inf) of that system, and the body pose is X_0^-1 T_0 X_0 at the end.  A rig of ONE camera therefore takes that
+ * camera's own steps: its body pose is X^-1 T_p X of bpvo_hip_estimate_pose's T_p, to the rounding of the conjugation.  Per iteration the members
+ * run the four-kernel chain, then one wavefront takes the rig's step; the persistent and team kernels do not serve rig estimates.
+ * BPVO_WARP_DISPARITY_SPACE_F32: BPVO_ERR_UNSUPPORTED.  An extrinsic that is not finite, whose last row is not (0, 0, 0, 1) or with
+ * max |R^T R - I| > 1e-4, n < 1 or above the capacity, an id twice: BPVO_ERR_INVALID_ARG.  Every check comes before anything changes.
+ *
+ * Estimator level, stateless like bpvo_hip_estimate_pose: member i = workspace wss[i] (distinct), template refs[i], current frame curs[i],
+ * extrinsic X + 16 i.  bpvo_hip_linearize_rig: the joint system at the body pose T_body at one pyramid level (reset_scale as
+ * bpvo_hip_linearize's, for every member); T_members, if not NULL, receives the member poses the kernels were run at. */
+int bpvo_hip_linearize_rig(bpvo_hip_ctx* ctx, int n, const int* wss, const int* refs, const int* curs, const float* X /*[n][16]*/, int level,
+                           const float T_body[16], int reset_scale, float H[36], float G[6], float* f_norm, int* num_valid,
+                           float* T_members /*[n][16] or NULL*/);
+/* the coarse-to-fine estimate of the body pose from T_init; stats [numLevels] are the joint system's (finalError = f,
+ * firstOrderOptimality = |G|_inf).  A member whose template is empty at a level that runs: BPVO_ERR_NO_TEMPLATE. */
+int bpvo_hip_estimate_pose_rig(bpvo_hip_ctx* ctx, int n, const int* wss, const int* refs, const int* curs, const float* X /*[n][16]*/,
+                               const float T_init[16], float T_est[16], bpvo_hip_stats* stats /*[numLevels]*/);
+/* addFrame level.  bpvo_hip_rig_set declares the rig: member p is sequence seq[p] (NULL: 0 .. n-1) of bpvo_hip_add_frames' kind — its own
+ * camera (bpvo_hip_create_sequences, bpvo_hip_seq_set_camera) — with extrinsic X + 16 p; only while every named sequence holds no frame.
+ * A member with parameters of its own (bpvo_hip_seq_set_params): BPVO_ERR_INVALID_ARG, the rig runs the context's.  A context that
+ * declares a rig serves bpvo_hip_add_frames_rig only: bpvo_hip_add_frame, bpvo_hip_add_frames and bpvo_hip_add_frames_stereo return
+ * BPVO_ERR_INVALID_ARG. */
+int bpvo_hip_rig_set(bpvo_hip_ctx* ctx, int n, const int* seq /*[n] distinct ids, NULL = 0..n-1*/, const float* X /*[n][16]*/);
+int bpvo_hip_rig_get(const bpvo_hip_ctx* ctx, int* n, int* seq /*[n] or NULL*/, float* X /*[n][16] or NULL*/);
+/* VisualOdometry::addFrame of the rig: the members' frames packed as for bpvo_hip_add_frames, in member order, each in its camera's size.
+ * One estimate of the body pose (from the body's pose against the key frame; against a new key frame from the identity), ONE key-frame
+ * decision — the context's thresholds on the body pose, the fraction of good points pooled over the members, sum good_p / sum n_p C — and
+ * every member the same transition.  `result` is the body's (covariance: Identity).  At a key frame every member's point cloud and point
+ * counts come from the bpvo_hip_seq_* accessors; a cloud's pose is W_kf X_p^-1 (world_from_camera), W_kf the body trajectory's pose of the
+ * result that carries the cloud.  After an error the rig goes on as if the call had not been made. */
+int bpvo_hip_add_frames_rig(bpvo_hip_ctx* ctx, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* result);
+int bpvo_hip_rig_trajectory_size(bpvo_hip_ctx* ctx, int* n);
+int bpvo_hip_rig_get_trajectory(bpvo_hip_ctx* ctx, float* poses /*[n][16]: the body's trajectory*/);
+
 /* Pyramid levels that were run by the persistent single-launch Gauss-Newton kernel (groups of BPVO_HIP_PERSIST_MAX_WS or fewer
  * pairs) since the context was created, and whether such a launch ever gave up at a grid barrier (the
  * context then stays on the four-kernel chain; results are the same either way). */

@@ -140,6 +140,7 @@ class Trajectory {                                              // bpvo/trajecto
  private:
   friend class VisualOdometry;
   friend class VisualOdometrySequences;
+  friend class RigVisualOdometry;
   std::vector<Matrix44> _poses;
 };
 
@@ -527,6 +528,88 @@ class VisualOdometrySequences {
   }
   std::shared_ptr<detail::Device> _dev;
   std::vector<Trajectory> _trajectories;
+};
+
+/* The cameras of a rigid rig estimated as ONE body: addFrame takes the next frame of every camera and returns a single 6-DoF body pose, estimated
+ * from all cameras' residuals at once, with one key-frame decision for the rig (bpvo_hip_add_frames_rig; the mathematics: c_api.h).  Camera p
+ * sits at extrinsics[p], camera_from_body (x_cam = X_p x_body, rigid).  No counterpart in the reference, which is single-camera. */
+class RigVisualOdometry {
+ public:
+  typedef VisualOdometrySequences::Camera Camera;
+
+  RigVisualOdometry(const std::vector<Camera>& cameras, const std::vector<Matrix44>& extrinsics, const AlgorithmParameters& params = AlgorithmParameters(),
+                    int device = 0)
+      : _dev(std::make_shared<detail::Device>(toC(cameras), params, device)), _n((int) cameras.size())
+  {
+    if(extrinsics.size() != cameras.size()) throw Error("one extrinsic per camera");
+    std::vector<float> X;
+    for(const Matrix44& x : extrinsics) X.insert(X.end(), x.data(), x.data() + 16);
+    _dev->check(bpvo_hip_rig_set(_dev->ctx(), _n, nullptr, X.data()));
+  }
+
+  int numCameras() const { return _n; }
+
+  /* images / disparities: the cameras' frames back to back in camera order, each of its camera's size.  The Result is the body's: its pose maps the
+   * previous body frame to this one, its covariance is the Identity; at a key frame the cameras' point clouds are fetched with pointCloud(camera)
+   * (Result::pointCloud stays empty: there is one cloud per camera). */
+  Result addFrame(const uint8_t* images, const float* disparities)
+  {
+    if(images == nullptr || disparities == nullptr) throw Error("nullptr image/disparity");
+    bpvo_hip_result r;
+    _dev->check(bpvo_hip_add_frames_rig(_dev->ctx(), images, disparities, 0, &r));
+    Result ret;
+    std::memcpy(ret.pose.data(), r.pose, sizeof(r.pose));
+    std::memcpy(ret.covariance.data(), r.covariance, sizeof(r.covariance));
+    for(int i = 0; i < r.numLevels; ++i) ret.optimizerStatistics.push_back(OptimizerStatistics(r.optimizerStatistics[i]));
+    ret.isKeyFrame = r.isKeyFrame != 0;
+    ret.keyFramingReason = static_cast<KeyFramingReason>(r.keyFramingReason);
+    _hasPointClouds = r.hasPointCloud != 0;
+    int nt = 0;
+    _dev->check(bpvo_hip_rig_trajectory_size(_dev->ctx(), &nt));
+    _trajectory._poses.resize(nt);
+    if(nt) _dev->check(bpvo_hip_rig_get_trajectory(_dev->ctx(), _trajectory._poses[0].data()));
+    return ret;
+  }
+  /* did the last addFrame leave point clouds (a key frame after the first)? */
+  bool hasPointClouds() const { return _hasPointClouds; }
+  /* the point cloud of a camera from the last addFrame (empty unless hasPointClouds()); its pose is world_from_camera, W_kf X_p^-1 */
+  PointCloud pointCloud(int camera) const
+  {
+    PointCloud pc;
+    size_t n = 0;
+    _dev->check(bpvo_hip_seq_get_point_cloud(_dev->ctx(), camera, nullptr, &n, nullptr));
+    pc.points().resize(n);
+    _dev->check(bpvo_hip_seq_get_point_cloud(_dev->ctx(), camera, pc.points().data(), &n, pc.pose().data()));
+    return pc;
+  }
+  /* the body's trajectory */
+  const Trajectory& trajectory() const { return _trajectory; }
+  int numPointsAtLevel(int camera, int level = -1) const
+  {
+    int n = 0;
+    _dev->check(bpvo_hip_seq_num_points_at_level(_dev->ctx(), camera, level, &n));
+    return n;
+  }
+  void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  double getOption(const std::string& name) const { return _dev->getOption(name); }
+
+ private:
+  static std::vector<bpvo_hip_camera> toC(const std::vector<Camera>& cams)
+  {
+    std::vector<bpvo_hip_camera> v;
+    for(const Camera& cam : cams) {
+      bpvo_hip_camera c;
+      std::memcpy(c.K, cam.K.data(), sizeof(c.K));
+      c.baseline = cam.baseline;
+      c.rows = cam.size.rows; c.cols = cam.size.cols;
+      v.push_back(c);
+    }
+    return v;
+  }
+  std::shared_ptr<detail::Device> _dev;
+  int _n;
+  bool _hasPointClouds = false;
+  Trajectory _trajectory;
 };
 
 }  // namespace bpvo
