@@ -255,63 +255,26 @@ __device__ __forceinline__ void irls_tile_lat(const PairJob& j, const GNState* _
 #pragma unroll
   for(int k = 0; k < kNumAcc; ++k) acc[k] = 0.0f;
 
-  // one point: residuals (fused: warp_point's arithmetic on the preloaded taps), weights, rank-2 update — as in irls_tile
+  // one point: residuals (fused: warp_point's helpers on the preloaded taps), weights, rank-2 update — as in irls_tile
   auto point = [&](int i, const IrlsPointLat& d) {
     float rr[8], Ix[8], Iy[8];
     float v;
     if constexpr(FUSED) {
-      const double X0 = (double) d.Pt.x, X1 = (double) d.Pt.y, X2 = (double) d.Pt.z, X3 = (double) d.Pt.w;
-      double u[3];
-#pragma unroll
-      for(int r = 0; r < 3; ++r) {
-        double s = (double) P[r * 4 + 0] * X0;
-        s += (double) P[r * 4 + 1] * X1;
-        s += (double) P[r * 4 + 2] * X2;
-        s += (double) P[r * 4 + 3] * X3;
-        u[r] = s;
-      }
-      const double zi = 1.0 / u[2];
-      const double x = zi * u[0], y = zi * u[1];
-      const bool in_range = (x > -2147483648.0) && (x < 2147483648.0) && (y > -2147483648.0) && (y < 2147483648.0);
-      int xi = 0, yi = 0;
-      if(in_range) {
-        xi = (int) x; xi -= (xi > x);
-        yi = (int) y; yi -= (yi > y);
-      }
-      const bool valid = in_range && xi >= 0 && xi < W - 1 && yi >= 0 && yi < R - 1;
-      const double xf = x - (double) xi, yf = y - (double) yi;
+      const WarpFoot f = warp_foot(P, d.Pt.x, d.Pt.y, d.Pt.z, d.Pt.w, W, R);
+      const bool valid = f.valid;
       bool hit = false;
       if(valid) {
-        const double wx = 1.0 - xf, wy = 1.0 - yf;
-        const unsigned key = ((unsigned) yi << 16) | (unsigned) xi;
+        const unsigned key = tap_key(f.xi, f.yi);
         const bool cached = j.tapcache_on != 0;
         hit = cached && d.key == key;
         float4 t[8];
 #pragma unroll
         for(int k = 0; k < 8; ++k) t[k] = d.tc[k];
         if(!hit) {
-          const float4* q0 = reinterpret_cast<const float4*>(j.desc + ((size_t) yi * W + xi) * 8);
-          const float4* q1 = q0 + (size_t) W * 2;
-          t[0] = q0[0]; t[1] = q0[1]; t[2] = q0[2]; t[3] = q0[3];
-          t[4] = q1[0]; t[5] = q1[1]; t[6] = q1[2]; t[7] = q1[3];
-          if(cached) {
-            float4* tcw = reinterpret_cast<float4*>(j.tapcache.get());
-#pragma unroll
-            for(int k = 0; k < 8; ++k) store_v4<false>(tcw + tile_index<8>(i, k), t[k]);
-            j.tapkey[i] = key;
-          }
+          taps8_gather(j, f.xi, f.yi, W, t);
+          if(cached) taps8_cache_store<false>(j, i, key, t);
         }
-        // pieces 0, 1: I00 of channels 0-3 / 4-7; 2, 3: I01; 4, 5: I10; 6, 7: I11 (warp_point)
-        const float i00[8] = {t[0].x, t[0].y, t[0].z, t[0].w, t[1].x, t[1].y, t[1].z, t[1].w};
-        const float i01[8] = {t[2].x, t[2].y, t[2].z, t[2].w, t[3].x, t[3].y, t[3].z, t[3].w};
-        const float i10[8] = {t[4].x, t[4].y, t[4].z, t[4].w, t[5].x, t[5].y, t[5].z, t[5].w};
-        const float i11[8] = {t[6].x, t[6].y, t[6].z, t[6].w, t[7].x, t[7].y, t[7].z, t[7].w};
-        const float i0[8] = {d.px[0].x, d.px[0].y, d.px[0].z, d.px[0].w, d.px[1].x, d.px[1].y, d.px[1].z, d.px[1].w};
-#pragma unroll
-        for(int c = 0; c < 8; ++c) {
-          const double Iw = wy * ((double) i00[c] * wx + (double) i01[c] * xf) + yf * ((double) i10[c] * wx + (double) i11[c] * xf);
-          rr[c] = (float) (Iw - (double) i0[c]);
-        }
+        taps8_residuals(t, d.px[0], d.px[1], f.xf, f.yf, rr);
       } else {
 #pragma unroll
         for(int c = 0; c < 8; ++c) rr[c] = 0.0f;

@@ -1,21 +1,19 @@
 // K6 warp + residual, device side: projection, validity, (cached) bilinear taps, residuals of one template point / one 256-point chunk.
 #pragma once
 #include "gn_common.h"
+#include "warp_rule.h"
 
 namespace bpvo_hip {
 
 // ------------------------------------------------------------------------------------------------------------------
 // K6 warp_residual.  reference: TemplateData::computeResiduals (bpvo/template_data.cc:174-189) =
 //   RigidBodyWarp::setPose (bpvo/rigid_body_warp.h:111-114): P = K * T[0:3,:] in f32, index-order sums
-//   PhotoError::Impl::init (bpvo/photo_error.cc:344-363): x = normHomog(P.cast<double>() * X.cast<double>()),
-//       Floor (:255-265), valid = 0 <= xi < W-1 && 0 <= yi < R-1 (kLinear)
+//   PhotoError::Impl::init: projection, Floor and validity — warp_foot (warp_rule.h)
 //   PhotoError::Impl::run kLinear (bpvo/photo_error.cc:365-389,446-449): Iw in f64, r = float(Iw - I0); invalid -> 0
 // One thread per template point; all C channels of the point are handled by the same thread because the descriptor is
 // pixel-interleaved: the 4 taps are 2 x (2*C floats) contiguous, fetched as 16-byte loads.
-// FAST selects the reference's alternative all-f32 formulation (inactive there, PHOTO_ERROR_OPT = 0): projectPoints
-// (bpvo/project_points.cc:180-214: x = P*X in f32, w = 1.0f/x2, xi = (int) xf — truncation, not floor — valid =
-// 0 <= xi < W-1 && 0 <= yi < R-1, coefficients C = [xf*yf - yf - xf + 1, xf - xf*yf, yf - xf*yf, xf*yf]) followed by
-// PhotoError::Impl::operator() / run of that branch (bpvo/photo_error.cc:118-214; same arithmetic as BilinearInterp,
+// FAST selects the reference's alternative all-f32 formulation (inactive there, PHOTO_ERROR_OPT = 0): projectPoints (warp_foot_f32,
+// warp_rule.h: truncation, coefficients C) followed by PhotoError::Impl::operator() / run of that branch (bpvo/photo_error.cc:118-214; same arithmetic as BilinearInterp,
 // bpvo/interp_util.h:49-71,93-96,184-203): Iw = dp_ps(C, [I00, I01, I10, I11]) = (C0*I00 + C1*I01) + (C2*I10 + C3*I11),
 // r = Iw - I0, and for an invalid point Iw = 0, i.e. r = -I0.
 // P = K * T[0:3,:] in f32, index-order sums (RigidBodyWarp::setPose, bpvo/rigid_body_warp.h:111-114)
@@ -34,7 +32,7 @@ __device__ __forceinline__ void projection_matrix(const PairJob& j, const float*
 
 // DisparitySpaceWarp::setPose (bpvo/disparity_space_warp.h:36): H = G * T * G_inv in f32, the two fixed 4x4 products left
 // to right, G / G_inv as the constructor fills them (bpvo/disparity_space_warp.cc:26-47).  P <- rows 0, 1, 3 of H: with
-// them operator() (:66-71) is the projectPoints form below plus the principal point (x = pw0 * (1 / pw3) + cx).
+// them operator() (:66-71) is projectPoints' form plus the principal point (x = pw0 * (1 / pw3) + cx): warp_foot_f32 with `dspace`.
 __device__ __forceinline__ void dspace_matrix(const PairJob& j, const float* __restrict__ T, float (&P)[12])
 {
   const float fx = j.K[0], fy = j.K[4];
@@ -46,6 +44,53 @@ __device__ __forceinline__ void dspace_matrix(const PairJob& j, const float* __r
   const M44 H = m44_mul(m44_mul(G, Tm), Gi);
 #pragma unroll
   for(int c = 0; c < 4; ++c) { P[c] = H.m[c]; P[4 + c] = H.m[4 + c]; P[8 + c] = H.m[12 + c]; }
+}
+
+// PhotoError::Impl::run kLinear on one channel: Iw in f64 from the four taps, r = float(Iw - I0)
+__device__ __forceinline__ float bilinear_res(float i00, float i01, float i10, float i11, float i0, double xf, double yf, double wx, double wy)
+{
+  const double Iw = wy * ((double) i00 * wx + (double) i01 * xf) + yf * ((double) i10 * wx + (double) i11 * xf);
+  return (float) (Iw - (double) i0);
+}
+
+// The C = 8 bilinear footprint as eight 16-byte pieces, which is how it is gathered and how the tap cache keeps it.
+// pieces 0, 1: I00 of channels 0-3 / 4-7; 2, 3: I01; 4, 5: I10; 6, 7: I11
+__device__ __forceinline__ unsigned tap_key(int xi, int yi) { return ((unsigned) yi << 16) | (unsigned) xi; }
+__device__ __forceinline__ void taps8_gather(const PairJob& j, int xi, int yi, int W, float4 (&t)[8])
+{
+  const float4* q0 = reinterpret_cast<const float4*>(j.desc + ((size_t) yi * W + xi) * 8);
+  const float4* q1 = q0 + (size_t) W * 2;
+  t[0] = q0[0]; t[1] = q0[1]; t[2] = q0[2]; t[3] = q0[3];
+  t[4] = q1[0]; t[5] = q1[1]; t[6] = q1[2]; t[7] = q1[3];
+}
+template <bool NT>
+__device__ __forceinline__ void taps8_cache_store(const PairJob& j, int i, unsigned key, const float4 (&t)[8])
+{
+  float4* tc = reinterpret_cast<float4*>(j.tapcache.get());
+#pragma unroll
+  for(int k = 0; k < 8; ++k) store_v4<NT>(tc + tile_index<8>(i, k), t[k]);
+  j.tapkey[i] = key;
+}
+__device__ __forceinline__ void taps8_unpack(const float4 (&t)[8], const float4 px0, const float4 px1, float (&i00)[8], float (&i01)[8],
+                                             float (&i10)[8], float (&i11)[8], float (&i0)[8])
+{
+#pragma unroll
+  for(int h = 0; h < 2; ++h) {
+    i00[4 * h] = t[h].x; i00[4 * h + 1] = t[h].y; i00[4 * h + 2] = t[h].z; i00[4 * h + 3] = t[h].w;
+    i01[4 * h] = t[2 + h].x; i01[4 * h + 1] = t[2 + h].y; i01[4 * h + 2] = t[2 + h].z; i01[4 * h + 3] = t[2 + h].w;
+    i10[4 * h] = t[4 + h].x; i10[4 * h + 1] = t[4 + h].y; i10[4 * h + 2] = t[4 + h].z; i10[4 * h + 3] = t[4 + h].w;
+    i11[4 * h] = t[6 + h].x; i11[4 * h + 1] = t[6 + h].y; i11[4 * h + 2] = t[6 + h].z; i11[4 * h + 3] = t[6 + h].w;
+  }
+  i0[0] = px0.x; i0[1] = px0.y; i0[2] = px0.z; i0[3] = px0.w; i0[4] = px1.x; i0[5] = px1.y; i0[6] = px1.z; i0[7] = px1.w;
+}
+// residuals of the eight channels from the pieces and the template pixel's two halves
+__device__ __forceinline__ void taps8_residuals(const float4 (&t)[8], const float4 px0, const float4 px1, double xf, double yf, float (&res)[8])
+{
+  const double wx = 1.0 - xf, wy = 1.0 - yf;
+  float i00[8], i01[8], i10[8], i11[8], i0[8];
+  taps8_unpack(t, px0, px1, i00, i01, i10, i11, i0);
+#pragma unroll
+  for(int c = 0; c < 8; ++c) res[c] = bilinear_res(i00[c], i01[c], i10[c], i11[c], i0[c], xf, yf, wx, wy);
 }
 
 // One template point of warp_residual: projection, validity, (cached) bilinear taps, residuals of all C channels.
@@ -78,47 +123,13 @@ __device__ __forceinline__ bool warp_point(const PairJob& j, const float (&P)[12
   double xf = 0.0, yf = 0.0;       // fractional parts (standard formulation)
   float cf[4] = {0, 0, 0, 0};      // interpolation coefficients (FAST formulation)
   if constexpr(!FAST) {
-    const double X0 = (double) X.x, X1 = (double) X.y, X2 = (double) X.z, X3 = (double) X.w;
-    double u[3];
-#pragma unroll
-    for(int r = 0; r < 3; ++r) {
-      double s = (double) P[r * 4 + 0] * X0;
-      s += (double) P[r * 4 + 1] * X1;
-      s += (double) P[r * 4 + 2] * X2;
-      s += (double) P[r * 4 + 3] * X3;
-      u[r] = s;
-    }
-    const double zi = 1.0 / u[2];
-    const double x = zi * u[0], y = zi * u[1];
-    // Floor(): static_cast<int> then -(i > v).  x86 yields INT_MIN for NaN / out-of-range doubles, which can never be a
-    // valid pixel; the explicit range test gives the same verdict without relying on v_cvt_i32_f64 saturation.
-    const bool in_range = (x > -2147483648.0) && (x < 2147483648.0) && (y > -2147483648.0) && (y < 2147483648.0);
-    if(in_range) {
-      xi = (int) x; xi -= (xi > x);
-      yi = (int) y; yi -= (yi > y);
-    }
-    valid = in_range && xi >= 0 && xi < W - 1 && yi >= 0 && yi < R - 1;
-    xf = x - (double) xi; yf = y - (double) yi;
+    const WarpFoot f = warp_foot(P, X.x, X.y, X.z, X.w, W, R);
+    xi = f.xi; yi = f.yi; valid = f.valid; xf = f.xf; yf = f.yf;
   } else {
-    float u[3];
+    const WarpFootF32 f = warp_foot_f32(P, X.x, X.y, X.z, X.w, j.dspace != 0, j.K[2], j.K[5], W, R);
+    xi = f.xi; yi = f.yi; valid = f.valid;
 #pragma unroll
-    for(int r = 0; r < 3; ++r) {
-      float s = P[r * 4 + 0] * X.x;
-      s += P[r * 4 + 1] * X.y;
-      s += P[r * 4 + 2] * X.z;
-      s += P[r * 4 + 3] * X.w;
-      u[r] = s;
-    }
-    const float w_i = 1.0f / u[2];
-    float fx = w_i * u[0], fy = w_i * u[1];
-    if(j.dspace) { fx = fx + j.K[2]; fy = fy + j.K[5]; }   // DisparitySpaceWarp::operator() (disparity_space_warp.h:66-71)
-    // (int) xf: cvttss2si gives INT_MIN for NaN / out-of-range, never a valid pixel
-    const bool in_range = (fx > -2147483648.0f) && (fx < 2147483648.0f) && (fy > -2147483648.0f) && (fy < 2147483648.0f);
-    if(in_range) { xi = (int) fx; yi = (int) fy; }
-    valid = in_range && xi >= 0 && xi < W - 1 && yi >= 0 && yi < R - 1;
-    fx -= (float) xi; fy -= (float) yi;
-    const float xfyf = fx * fy;
-    cf[0] = xfyf - fy - fx + 1.0f; cf[1] = fx - xfyf; cf[2] = fy - xfyf; cf[3] = xfyf;
+    for(int k = 0; k < 4; ++k) cf[k] = f.cf[k];
   }
 
   if constexpr(HALF && C == 8 && !FAST) {
@@ -126,7 +137,7 @@ __device__ __forceinline__ bool warp_point(const PairJob& j, const float (&P)[12
       const double wx = 1.0 - xf, wy = 1.0 - yf;
       const float4* q0 = reinterpret_cast<const float4*>(j.desc + ((size_t) yi * W + xi) * 8);
       const float4* q1 = q0 + (size_t) W * 2;
-      const unsigned key = ((unsigned) yi << 16) | (unsigned) xi;
+      const unsigned key = tap_key(xi, yi);
       const bool cached = j.tapcache_on != 0;       // (uniform over the workspace) dense levels gather straight from the descriptor
       const bool hit = cached && j.tapkey[i] == key;
       cache_hit = hit;
@@ -149,10 +160,7 @@ __device__ __forceinline__ bool warp_point(const PairJob& j, const float (&P)[12
         const float i00[4] = {a.x, a.y, a.z, a.w}, i01[4] = {b.x, b.y, b.z, b.w}, i10[4] = {c.x, c.y, c.z, c.w},
                     i11[4] = {d.x, d.y, d.z, d.w}, i0[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
-        for(int k = 0; k < 4; ++k) {
-          const double Iw = wy * ((double) i00[k] * wx + (double) i01[k] * xf) + yf * ((double) i10[k] * wx + (double) i11[k] * xf);
-          res[4 * h + k] = (float) (Iw - (double) i0[k]);
-        }
+        for(int k = 0; k < 4; ++k) res[4 * h + k] = bilinear_res(i00[k], i01[k], i10[k], i11[k], i0[k], xf, yf, wx, wy);
         if(h == 0) __builtin_amdgcn_sched_barrier(0);   // keep the second group's loads behind the first group's arithmetic
       }
       if(!hit && in_block && cached) j.tapkey[i] = key;
@@ -175,41 +183,26 @@ __device__ __forceinline__ bool warp_point(const PairJob& j, const float (&P)[12
       // (sub-pixel pose updates), and then the four taps are the same 128 bytes.  They are kept per point in a tiled,
       // fully coalesced buffer keyed by (yi << 16 | xi): a hit replaces the gather — two 64-byte segments that cost
       // 2.3 128-byte HBM lines on average (profiles/r01_pmc_summary.txt) — by one coalesced 128-byte read.
-      const unsigned key = ((unsigned) yi << 16) | (unsigned) xi;
+      const unsigned key = tap_key(xi, yi);
       const bool cached = j.tapcache_on != 0;       // (uniform over the workspace) dense levels gather straight from the descriptor
       const bool hit = cached && j.tapkey[i] == key;
       cache_hit = hit;
-      float4 a0, a1, a2, a3, b0, b1, b2, b3;
-      float4* tc = reinterpret_cast<float4*>(j.tapcache.get());
+      float4 t[8];
       if(hit) {
-        a0 = load_v4<NT>(tc + tile_index<8>(i, 0)); a1 = load_v4<NT>(tc + tile_index<8>(i, 1));
-        a2 = load_v4<NT>(tc + tile_index<8>(i, 2)); a3 = load_v4<NT>(tc + tile_index<8>(i, 3));
-        b0 = load_v4<NT>(tc + tile_index<8>(i, 4)); b1 = load_v4<NT>(tc + tile_index<8>(i, 5));
-        b2 = load_v4<NT>(tc + tile_index<8>(i, 6)); b3 = load_v4<NT>(tc + tile_index<8>(i, 7));
+        const float4* tc = reinterpret_cast<const float4*>(j.tapcache.get());
+#pragma unroll
+        for(int k = 0; k < 8; ++k) t[k] = load_v4<NT>(tc + tile_index<8>(i, k));
       } else {
-        const float4* q0 = reinterpret_cast<const float4*>(d0);
-        const float4* q1 = reinterpret_cast<const float4*>(d1);
-        a0 = q0[0]; a1 = q0[1]; a2 = q0[2]; a3 = q0[3];
-        b0 = q1[0]; b1 = q1[1]; b2 = q1[2]; b3 = q1[3];
-        if(in_block && cached) {
-          store_v4<NT>(tc + tile_index<8>(i, 0), a0); store_v4<NT>(tc + tile_index<8>(i, 1), a1);
-          store_v4<NT>(tc + tile_index<8>(i, 2), a2); store_v4<NT>(tc + tile_index<8>(i, 3), a3);
-          store_v4<NT>(tc + tile_index<8>(i, 4), b0); store_v4<NT>(tc + tile_index<8>(i, 5), b1);
-          store_v4<NT>(tc + tile_index<8>(i, 6), b2); store_v4<NT>(tc + tile_index<8>(i, 7), b3);
-          j.tapkey[i] = key;
-        }
+        taps8_gather(j, xi, yi, W, t);
+        if(in_block && cached) taps8_cache_store<NT>(j, i, key, t);
       }
       const float4* p0 = reinterpret_cast<const float4*>(j.pix.get());
       const float4 t0 = load_v4<NT>(p0 + tile_index<2>(i, 0)), t1 = load_v4<NT>(p0 + tile_index<2>(i, 1));
-      I00[0] = a0.x; I00[1] = a0.y; I00[2] = a0.z; I00[3] = a0.w; I00[4] = a1.x; I00[5] = a1.y; I00[6] = a1.z; I00[7] = a1.w;
-      I01[0] = a2.x; I01[1] = a2.y; I01[2] = a2.z; I01[3] = a2.w; I01[4] = a3.x; I01[5] = a3.y; I01[6] = a3.z; I01[7] = a3.w;
-      I10[0] = b0.x; I10[1] = b0.y; I10[2] = b0.z; I10[3] = b0.w; I10[4] = b1.x; I10[5] = b1.y; I10[6] = b1.z; I10[7] = b1.w;
-      I11[0] = b2.x; I11[1] = b2.y; I11[2] = b2.z; I11[3] = b2.w; I11[4] = b3.x; I11[5] = b3.y; I11[6] = b3.z; I11[7] = b3.w;
-      I0[0] = t0.x; I0[1] = t0.y; I0[2] = t0.z; I0[3] = t0.w; I0[4] = t1.x; I0[5] = t1.y; I0[6] = t1.z; I0[7] = t1.w;
+      taps8_unpack(t, t0, t1, I00, I01, I10, I11, I0);
     } else if constexpr(C == 1) {
       // the same tap cache for single-channel descriptors: the four taps of a point are one 16-byte record.  The gather
       // costs two (mostly distinct) HBM lines per point at the sparse levels for 16 useful bytes; a hit is one coalesced load.
-      const unsigned key = ((unsigned) yi << 16) | (unsigned) xi;
+      const unsigned key = tap_key(xi, yi);
       float4* tc = reinterpret_cast<float4*>(j.tapcache.get());
       float4 t = spec_taps;
       const bool cached = j.tapcache_on != 0;
@@ -230,8 +223,7 @@ __device__ __forceinline__ bool warp_point(const PairJob& j, const float (&P)[12
 #pragma unroll
     for(int c = 0; c < C; ++c) {
       if constexpr(!FAST) {
-        const double Iw = wy * ((double) I00[c] * wx + (double) I01[c] * xf) + yf * ((double) I10[c] * wx + (double) I11[c] * xf);
-        res[c] = (float) (Iw - (double) I0[c]);
+        res[c] = bilinear_res(I00[c], I01[c], I10[c], I11[c], I0[c], xf, yf, wx, wy);
       } else {
         const float Iw = (cf[0] * I00[c] + cf[1] * I01[c]) + (cf[2] * I10[c] + cf[3] * I11[c]);
         res[c] = Iw - I0[c];

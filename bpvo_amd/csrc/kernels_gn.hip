@@ -124,26 +124,10 @@ __global__ __launch_bounds__(K6_BLOCK) void warp_residual_interp_kernel(const Pa
   const float4 X = load_point<false>(j, i);
   constexpr bool two_tap = interp == BPVO_INTERP_COSINE;
   constexpr int border_lo = two_tap ? 0 : 1, border_hi = two_tap ? 1 : 3;
-  int xi = 0, yi = 0;
-  const double X0 = (double) X.x, X1 = (double) X.y, X2 = (double) X.z, X3 = (double) X.w;
-  double u[3];
-#pragma unroll
-  for(int r = 0; r < 3; ++r) {
-    double s = (double) P[r * 4 + 0] * X0;
-    s += (double) P[r * 4 + 1] * X1;
-    s += (double) P[r * 4 + 2] * X2;
-    s += (double) P[r * 4 + 3] * X3;
-    u[r] = s;
-  }
-  const double zi = 1.0 / u[2];
-  const double x = zi * u[0], y = zi * u[1];
-  const bool in_range = (x > -2147483648.0) && (x < 2147483648.0) && (y > -2147483648.0) && (y < 2147483648.0);
-  if(in_range) {
-    xi = (int) x; xi -= (xi > x);
-    yi = (int) y; yi -= (yi > y);
-  }
-  const bool valid = in_range && xi >= border_lo && xi < W - border_hi && yi >= border_lo && yi < R - 1;
-  const float xf = (float) (x - (double) xi), yf = (float) (y - (double) yi);
+  const WarpFoot ft = warp_foot<border_lo, border_hi>(P, X.x, X.y, X.z, X.w, W, R);
+  const int xi = ft.xi, yi = ft.yi;
+  const bool valid = ft.valid;
+  const float xf = (float) ft.xf, yf = (float) ft.yf;
   if(in_block) j.valid[i] = valid ? 1 : 0;
 
   constexpr int G = InterpGroup<C>::G;
@@ -161,7 +145,7 @@ __global__ __launch_bounds__(K6_BLOCK) void warp_residual_interp_kernel(const Pa
   float4* const tc = kCache ? reinterpret_cast<float4*>(j.tapcache.get()) : nullptr;
   if constexpr(kCache) {
     cached = j.tapcache_on != 0 && j.tapkey;             // (uniform over the workspace)
-    key = ((unsigned) yi << 16) | (unsigned) xi;
+    key = tap_key(xi, yi);
     hit = cached && valid && j.tapkey[i] == key;
   }
   float res[C];

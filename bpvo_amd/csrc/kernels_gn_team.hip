@@ -115,13 +115,13 @@ __device__ __attribute__((noinline)) void pk_warp_phase(const PairJob* __restric
 // (profiles/r03_team_phases_under_load_before.txt).  Here a thread carries U points — one from each of U chunks — through the phase in
 // stages: everything whose address depends on the point index only (point, tap-cache key, the eight cached tap vectors, template pixels) is
 // requested for all U points at once, then the U projections, then the gathers of the misses (at dense levels, which run without the
-// cache: of all points) for all U at once.  Same expressions as warp_point, operation for operation: same bits.  The cached taps are loaded
+// cache: of all points) for all U at once.  The rule and the tap helpers are warp_point's own: same bits.  The cached taps are loaded
 // speculatively, as irls_tile_lat does (3 % of them are discarded at the sparse levels).
 struct WarpStage {
   float4 X, t[8], px[2];
   double xf, yf;
   unsigned key;
-  int i, xi, yi, chunk;
+  int i, chunk;
   bool has, in_block, valid, hit;
 };
 __shared__ BracketLds pk_br_u[PK_VB][4];
@@ -165,40 +165,16 @@ __device__ __attribute__((noinline)) void pk_warp_phase_staged(const PairJob* __
         s[u].key = 0xffffffffu;
       }
     }
-    // stage B: projection, validity (warp_point), and the gathers of the footprints the cache does not hold
+    // stage B: projection, validity (warp_foot), and the gathers of the footprints the cache does not hold
 #pragma unroll
     for(int u = 0; u < U; ++u) {
-      const float4 X = s[u].X;
-      const double X0 = (double) X.x, X1 = (double) X.y, X2 = (double) X.z, X3 = (double) X.w;
-      double uu[3];
-#pragma unroll
-      for(int r = 0; r < 3; ++r) {
-        double a = (double) P[r * 4 + 0] * X0;
-        a += (double) P[r * 4 + 1] * X1;
-        a += (double) P[r * 4 + 2] * X2;
-        a += (double) P[r * 4 + 3] * X3;
-        uu[r] = a;
-      }
-      const double zi = 1.0 / uu[2];
-      const double x = zi * uu[0], y = zi * uu[1];
-      const bool in_range = (x > -2147483648.0) && (x < 2147483648.0) && (y > -2147483648.0) && (y < 2147483648.0);
-      int xi = 0, yi = 0;
-      if(in_range) {
-        xi = (int) x; xi -= (xi > x);
-        yi = (int) y; yi -= (yi > y);
-      }
-      s[u].valid = in_range && xi >= 0 && xi < W - 1 && yi >= 0 && yi < R - 1;
-      s[u].xi = xi; s[u].yi = yi;
-      s[u].xf = x - (double) xi; s[u].yf = y - (double) yi;
-      const unsigned key = ((unsigned) yi << 16) | (unsigned) xi;
+      const WarpFoot f = warp_foot(P, s[u].X.x, s[u].X.y, s[u].X.z, s[u].X.w, W, R);
+      s[u].valid = f.valid;
+      s[u].xf = f.xf; s[u].yf = f.yf;
+      const unsigned key = tap_key(f.xi, f.yi);
       s[u].hit = s[u].valid && cached && s[u].key == key;
       s[u].key = key;
-      if(s[u].valid && !s[u].hit) {
-        const float4* q0 = reinterpret_cast<const float4*>(j.desc + ((size_t) yi * W + xi) * 8);
-        const float4* q1 = q0 + (size_t) W * 2;
-        s[u].t[0] = q0[0]; s[u].t[1] = q0[1]; s[u].t[2] = q0[2]; s[u].t[3] = q0[3];
-        s[u].t[4] = q1[0]; s[u].t[5] = q1[1]; s[u].t[6] = q1[2]; s[u].t[7] = q1[3];
-      }
+      if(s[u].valid && !s[u].hit) taps8_gather(j, f.xi, f.yi, W, s[u].t);
     }
     // stage C: residuals, stores, cache update, bracket step
 #pragma unroll
@@ -206,24 +182,8 @@ __device__ __attribute__((noinline)) void pk_warp_phase_staged(const PairJob* __
       const int i = s[u].i;
       float res[8];
       if(s[u].valid) {
-        const double xf = s[u].xf, yf = s[u].yf, wx = 1.0 - xf, wy = 1.0 - yf;
-        const float4* t = s[u].t;
-        // pieces 0, 1: I00 of channels 0-3 / 4-7; 2, 3: I01; 4, 5: I10; 6, 7: I11 (warp_point)
-        const float i00[8] = {t[0].x, t[0].y, t[0].z, t[0].w, t[1].x, t[1].y, t[1].z, t[1].w};
-        const float i01[8] = {t[2].x, t[2].y, t[2].z, t[2].w, t[3].x, t[3].y, t[3].z, t[3].w};
-        const float i10[8] = {t[4].x, t[4].y, t[4].z, t[4].w, t[5].x, t[5].y, t[5].z, t[5].w};
-        const float i11[8] = {t[6].x, t[6].y, t[6].z, t[6].w, t[7].x, t[7].y, t[7].z, t[7].w};
-        const float i0[8] = {s[u].px[0].x, s[u].px[0].y, s[u].px[0].z, s[u].px[0].w, s[u].px[1].x, s[u].px[1].y, s[u].px[1].z, s[u].px[1].w};
-#pragma unroll
-        for(int c = 0; c < 8; ++c) {
-          const double Iw = wy * ((double) i00[c] * wx + (double) i01[c] * xf) + yf * ((double) i10[c] * wx + (double) i11[c] * xf);
-          res[c] = (float) (Iw - (double) i0[c]);
-        }
-        if(!s[u].hit && s[u].in_block && cached) {
-#pragma unroll
-          for(int k = 0; k < 8; ++k) store_v4<NT>(tc + tile_index<8>(i, k), t[k]);
-          j.tapkey[i] = s[u].key;
-        }
+        taps8_residuals(s[u].t, s[u].px[0], s[u].px[1], s[u].xf, s[u].yf, res);
+        if(!s[u].hit && s[u].in_block && cached) taps8_cache_store<NT>(j, i, s[u].key, s[u].t);
       } else {
 #pragma unroll
         for(int c = 0; c < 8; ++c) res[c] = 0.0f;

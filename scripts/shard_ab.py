@@ -34,6 +34,8 @@ def child(a):
     p.descriptor = capi.DESC_BITPLANES if a.descriptor == "bitplanes" else capi.DESC_INTENSITY
     p.lossFunction = {"tukey": capi.LOSS_TUKEY, "huber": capi.LOSS_HUBER, "l2": capi.LOSS_L2}[a.loss]
     p.verbosity = capi.VERB_SILENT
+    if a.interp != "linear":      # warp_residual_interp_kernel; such batches take the four-kernel chain at every size
+        p.interp = {"cosine": capi.INTERP_COSINE, "cubic": capi.INTERP_CUBIC, "cubic_hermite": capi.INTERP_CUBIC_HERMITE}[a.interp]
     if a.tolerances == "timing":
         p.parameterTolerance, p.functionTolerance, p.gradientTolerance = 1e-6, 1e-4, 1e-6
     n = a.pairs
@@ -72,6 +74,7 @@ def main():
     ap.add_argument("--descriptor", default="bitplanes")
     ap.add_argument("--loss", default="tukey")
     ap.add_argument("--tolerances", default="default")
+    ap.add_argument("--interp", default="linear", choices=["linear", "cosine", "cubic", "cubic_hermite"])
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--child", default="")
     ap.add_argument("--host", action="store_true", help="hand the library HOST buffers (the upload pipeline) instead of device-resident inputs")
@@ -104,7 +107,7 @@ def main():
             for n in sizes:
                 steps = a.steps if n == a.pairs else max(2, a.steps // 4)
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", path, "--pairs", str(n), "--steps", str(steps), "--warmup", str(a.warmup),
-                       "--levels", str(a.levels), "--descriptor", a.descriptor, "--loss", a.loss, "--tolerances", a.tolerances] + (["--host"] if a.host else [])
+                       "--levels", str(a.levels), "--descriptor", a.descriptor, "--loss", a.loss, "--tolerances", a.tolerances, "--interp", a.interp] + (["--host"] if a.host else [])
                 r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
                 line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
                 out.append(json.loads(line[-1]) if line else dict(error=(r.stdout + r.stderr)[-400:]))

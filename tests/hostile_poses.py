@@ -3,13 +3,14 @@
 The rule is PhotoError::Impl::init (bpvo/photo_error.cc:344-363): x = normHomog(P.cast<double>() * X.cast<double>()) with the f32
 P = K * T[0:3], Floor, valid = lo <= xi < W - hi && lo <= yi < R - 1.  There is no z > 0 test: a point behind the camera that projects into
 the image is valid.  Floor is static_cast<int>, which on x86 (cvttsd2si) gives INT_MIN for NaN, infinities and everything beyond the int
-range — never a valid pixel; the device code carries an explicit range test in its place, in four hand-written copies (gn_warp.h,
-gn_irls.h, kernels_gn_team.hip, kernels_gn.hip).  projectPoints (bpvo/project_points.cc:180-214), the all-f32 form that also serves
+range — never a valid pixel; the device code carries an explicit range test in its place (warp_rule.h, called from gn_warp.h,
+gn_irls.h, kernels_gn_team.hip and kernels_gn.hip).  projectPoints (bpvo/project_points.cc:180-214), the all-f32 form that also serves
 DisparitySpaceWarp, truncates instead of flooring, so x in (-1, 0) is a valid pixel 0 with a negative fraction.
 
 poses(K, X, rows, cols) builds the named poses from a template's own points; PROPERTY names what each must exhibit there, and
 check_property fails loudly when a case no longer has it (a change of the synthetic scenes, say).  Used by tests/test_hostile_poses_cpu.py
-(the oracle against numpy) and tests/test_gpu_hostile_poses.py (every device copy against the oracle and numpy)."""
+(the oracle against numpy), tests/test_warp_rule_cpu.py (warp_rule.h on the host against numpy) and tests/test_gpu_hostile_poses.py (every
+device path against the oracle and numpy)."""
 import numpy as np
 
 # (rows, cols, pyramid levels): the size of the CPU re-derivations, and one at which xi and yi both pass 255 at level 0 (the tap-cache
