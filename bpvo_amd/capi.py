@@ -54,6 +54,21 @@ class Result(C.Structure):
                 ("numLevels", C.c_int), ("isKeyFrame", C.c_int), ("keyFramingReason", C.c_int), ("hasPointCloud", C.c_int)]
 
 
+COV_OK, COV_INDEFINITE, COV_DEGENERATE, COV_NONE = 0, 1, 2, 3
+COV_GROUP = 64
+
+
+class PoseCovariance(C.Structure):
+    """bpvo_hip_pose_covariance (c_api.h): the robust sandwich covariance of an estimated pose."""
+    _fields_ = [("T", C.c_float * 16), ("covariance", C.c_float * 36), ("sigma", C.c_float), ("num_valid", C.c_int), ("level", C.c_int),
+                ("status", C.c_int)]
+
+
+def _cov_dict(r: PoseCovariance):
+    return dict(T=np.array(r.T, np.float32).reshape(4, 4), covariance=np.array(r.covariance, np.float32).reshape(6, 6), sigma=float(np.float32(r.sigma)),
+                num_valid=int(r.num_valid), level=int(r.level), status=int(r.status))
+
+
 class Camera(C.Structure):
     """bpvo_hip_camera: one sequence's calibration and image size (bpvo_hip_create_sequences, bpvo_hip_seq_set_camera)."""
     _fields_ = [("K", C.c_float * 9), ("baseline", C.c_float), ("rows", C.c_int), ("cols", C.c_int)]
@@ -689,6 +704,51 @@ class Context:
         if n.value:
             self.call("rig_get_trajectory", out.ctypes.data_as(C.c_void_p))
         return out
+
+    # -- pose covariance (bpvo_hip_pose_covariances ...; HIP library only)
+    def pose_covariances(self, wss, refs, curs, level, T=None, sigma=None):
+        """One record (dict) per workspace: at the poses T [n, 4, 4] and scales sigma [n], or (both None) of each workspace's last estimate."""
+        w, r, c, _ = self._rig_members(wss, refs, curs, np.zeros((len(np.atleast_1d(wss)), 16)))
+        n = w.shape[0]
+        out = (PoseCovariance * n)()
+        Tf = None if T is None else _f32(T).reshape(n, 16)
+        sf = None if sigma is None else _f32(sigma).reshape(n)
+        self.call("pose_covariances", n, w.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), int(level),
+                  None if Tf is None else Tf.ctypes.data_as(C.c_void_p), None if sf is None else sf.ctypes.data_as(C.c_void_p), out)
+        return [_cov_dict(o) for o in out]
+
+    def pose_covariance_rig(self, wss, refs, curs, X, level, T_body=None, sigma=None):
+        """The body pose's record from the members (as linearize_rig takes them); sigma: every member's own scale."""
+        w, r, c, Xf = self._rig_members(wss, refs, curs, X)
+        n = w.shape[0]
+        out = PoseCovariance()
+        Tf = None if T_body is None else _f32(T_body).reshape(16)
+        sf = None if sigma is None else _f32(sigma).reshape(n)
+        self.call("pose_covariance_rig", n, w.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p),
+                  Xf.ctypes.data_as(C.c_void_p), int(level), None if Tf is None else Tf.ctypes.data_as(C.c_void_p),
+                  None if sf is None else sf.ctypes.data_as(C.c_void_p), C.byref(out))
+        return _cov_dict(out)
+
+    def vo_pose_covariance(self):
+        out = PoseCovariance()
+        self.call("vo_pose_covariance", C.byref(out))
+        return _cov_dict(out)
+
+    def seq_pose_covariance(self, s):
+        out = PoseCovariance()
+        self.call("seq_pose_covariance", int(s), C.byref(out))
+        return _cov_dict(out)
+
+    def rig_pose_covariance(self):
+        out = PoseCovariance()
+        self.call("rig_pose_covariance", C.byref(out))
+        return _cov_dict(out)
+
+    def debug_pose_covariance_sums(self, ws):
+        """(M, Q) of the last pose-covariance pass on workspace ws, in its normalised twist."""
+        M, Q = np.empty((6, 6), np.float32), np.empty((6, 6), np.float32)
+        self.call("debug_pose_covariance_sums", int(ws), M.ctypes.data_as(C.c_void_p), Q.ctypes.data_as(C.c_void_p))
+        return M, Q
 
     # -- batches
     def _stats_array(self, st, n_pairs):

@@ -241,6 +241,7 @@ int batch_run_staggered(bpvo_hip_ctx* c, int n_pairs, int nl, const uint8_t* ima
     w.last_ref = 2 * i;
     w.last_cur = 2 * i + 1;
     w.last_level = c->params.maxTestLevel;
+    w.has_estimate = true;
   }
   return BPVO_OK;
 }

@@ -332,6 +332,16 @@ const std::vector<OptionDef>& option_table()
     OPT_INT("stagger_min_pairs", stagger_min_pairs, 0, 1 << 20),
     OPT_INT("upload_workers", up_workers, 0, 32),
     OPT_INT("keep_current_disparity", keep_current_disparity, 0, 1),
+    // the addFrame entry points run the pose-covariance pass behind their estimates (pose_cov.hip); its scratch is allocated here
+    OptionDef{"pose_covariance", 0, 1, [](bpvo_hip_ctx* c) { return (double) c->pose_covariance; },
+              [](bpvo_hip_ctx* c, double v) -> int {
+                if((int) v) {
+                  const int rc = pose_cov_ensure_scratch(c);
+                  if(rc) return rc;
+                }
+                c->pose_covariance = (int) v;
+                return BPVO_OK;
+              }},
     OPT_INT("lazy_template_descriptor", lazy_template, 0, 1),
     OPT_INT("points_from_compact_stream", points_from_compact, 0, 1),
     OptionDef{"tapcache_max_density", 0.0, 1e9, [](bpvo_hip_ctx* c) { return c->tapcache_max_density; },
@@ -476,6 +486,8 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
     return BPVO_ERR_INVALID_ARG;
   }
   std::unique_ptr<bpvo_hip_ctx> c(new bpvo_hip_ctx);
+  pose_cov_none(&c->vo_cov);
+  pose_cov_none(&c->rig_cov);
   c->params = *p;
   std::memcpy(c->K, K, sizeof(c->K));
   c->baseline = baseline;
@@ -720,6 +732,7 @@ void bpvo_hip_destroy(bpvo_hip_ctx* c)
   for(auto& w : c->ws) { (void) hipFree(w.r); (void) hipFree(w.valid); (void) hipFree(w.cand); (void) hipFree(w.med_blk); (void) hipFree(w.tapkey); (void) hipFree(w.tapcache); (void) hipFree(w.partials); }
   (void) hipFree(c->d_states); (void) hipFree(c->d_fjobs); (void) hipFree(c->d_job1); (void) hipFree(c->d_latch_off); (void) hipFree(c->d_cloud);
   (void) hipFree(c->d_records); (void) hipFree(c->d_wtmp); (void) hipFree(c->d_rig_X);
+  pose_cov_free(c);
   (void) hipFree(c->d_count); (void) hipFree(c->d_counters); (void) hipFree(c->d_tickets); (void) hipFree(c->d_trace);
   (void) hipFree(c->st_left); (void) hipFree(c->st_right); (void) hipFree(c->st_left_pre); (void) hipFree(c->st_right_pre); (void) hipFree(c->st_disp);
   (void) hipFree(c->st_sgm);

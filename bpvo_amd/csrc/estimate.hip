@@ -458,6 +458,7 @@ static int estimate_one_loss(bpvo_hip_ctx* c, int n, const int* wss, const int* 
     w.last_ref = refs[i];
     w.last_cur = curs[i];
     w.last_level = p.maxTestLevel;
+    w.has_estimate = true;
   }
   return BPVO_OK;
 }
@@ -712,6 +713,7 @@ int estimate_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const 
   for(int i = 0; i < n; ++i) {
     Workspace& w = c->ws[wss[i]];
     w.last_ref = refs[i]; w.last_cur = curs[i]; w.last_level = p.maxTestLevel;
+    w.has_estimate = true;
   }
   return BPVO_OK;
 }
@@ -756,6 +758,7 @@ int bpvo_hip_linearize_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* re
   for(int i = 0; i < n; ++i) {
     Workspace& w = c->ws[wss[i]];
     w.last_ref = refs[i]; w.last_cur = curs[i]; w.last_level = level;
+    w.has_estimate = false;
   }
   return BPVO_OK;
 }
@@ -825,6 +828,7 @@ static int linearize_impl(bpvo_hip_ctx* c, int ws, int ref_slot, int cur_slot, i
   if(sigma) *sigma = st.scale;
   *num_valid = (int) st.n_valid;
   c->ws[ws].last_ref = ref_slot; c->ws[ws].last_cur = cur_slot; c->ws[ws].last_level = level;
+  c->ws[ws].has_estimate = false;
   return BPVO_OK;
 }
 int bpvo_hip_linearize(bpvo_hip_ctx* c, int ws, int ref_slot, int cur_slot, int level, const float T[16], int reset_scale,

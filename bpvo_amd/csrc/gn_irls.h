@@ -47,6 +47,79 @@ __device__ __forceinline__ float mest_weight(float r, float sigma_inv)
   return 1.0f;
 }
 
+// The per-point pieces of the reduction, shared by irls_tile below and by the pose-covariance reduction (gn_cov.h).
+// The non-fused loads of one point: its C residuals, then its 2 x C gradient floats (tiled C = 8, C = 1, point-major generic C).
+template <int C>
+__device__ __forceinline__ void irls_load_residuals(const PairJob& j, int i, float (&rr)[C])
+{
+  if constexpr(C == 8) {
+    const float4* qr = reinterpret_cast<const float4*>(j.r.get());
+    const float4 r0 = load_stream(qr + tile_index<2>(i, 0)), r1 = load_stream(qr + tile_index<2>(i, 1));
+    rr[0] = r0.x; rr[1] = r0.y; rr[2] = r0.z; rr[3] = r0.w; rr[4] = r1.x; rr[5] = r1.y; rr[6] = r1.z; rr[7] = r1.w;
+  } else if constexpr(C == 1) {
+    rr[0] = j.r[i];
+  } else {      // generic C: point-major r[N][pitch] (pitch = C, or the whole channel count for a channel group)
+    const size_t PT = (size_t) j.pitch;
+#pragma unroll
+    for(int c = 0; c < C; ++c) rr[c] = j.r[(size_t) i * PT + c];
+  }
+}
+template <int C>
+__device__ __forceinline__ void irls_load_gradients(const PairJob& j, int i, float (&Ix)[C], float (&Iy)[C])
+{
+  if constexpr(C == 8) {
+    const float4* qg = reinterpret_cast<const float4*>(j.grad.get());
+    const float4 gx0 = load_stream(qg + tile_index<4>(i, 0)), gx1 = load_stream(qg + tile_index<4>(i, 1)),
+                 gy0 = load_stream(qg + tile_index<4>(i, 2)), gy1 = load_stream(qg + tile_index<4>(i, 3));
+    Ix[0] = gx0.x; Ix[1] = gx0.y; Ix[2] = gx0.z; Ix[3] = gx0.w; Ix[4] = gx1.x; Ix[5] = gx1.y; Ix[6] = gx1.z; Ix[7] = gx1.w;
+    Iy[0] = gy0.x; Iy[1] = gy0.y; Iy[2] = gy0.z; Iy[3] = gy0.w; Iy[4] = gy1.x; Iy[5] = gy1.y; Iy[6] = gy1.z; Iy[7] = gy1.w;
+  } else if constexpr(C == 1) {
+    const float2 g2 = reinterpret_cast<const float2*>(j.grad.get())[i];
+    Ix[0] = g2.x; Iy[0] = g2.y;
+  } else {      // generic C: grad[N][2][pitch]
+    const size_t PT = (size_t) j.pitch;
+#pragma unroll
+    for(int c = 0; c < C; ++c) {
+      Ix[c] = j.grad[((size_t) i * 2 + 0) * PT + c];
+      Iy[c] = j.grad[((size_t) i * 2 + 1) * PT + c];
+    }
+  }
+}
+// Rank-2 structure: every channel's 1x6 Jacobian row at a point is J_c = Ix_c * A + Iy_c * B with A, B depending on the point only
+// (jac_row / dspace_jac_row in types.h expanded in Ix, Iy).  What of the job the two rows need, uniform over the launch, and the rows.
+struct IrlsRowGeom { float s_nrm[4]; bool dspace; float ds_fx, ds_fy, ds_fx_i, ds_fy_i, ds_b_i; };
+__device__ __forceinline__ IrlsRowGeom irls_row_geom(const PairJob& j)
+{
+  return IrlsRowGeom{{j.nrm[0], j.nrm[1], j.nrm[2], j.nrm[3]}, j.dspace != 0, j.K[0], j.K[4], 1.0f / j.K[0], 1.0f / j.K[4], 1.0f / j.b};
+}
+__device__ __forceinline__ void irls_point_rows(const IrlsRowGeom& g, const float4 Pt, float (&A)[6], float (&B)[6])
+{
+  if(!g.dspace) {
+    const JacPoint jp = jac_point(Pt.x, Pt.y, Pt.z, g.s_nrm);
+    const float t_xz2 = jp.x * jp.rz2, t_yz2 = jp.y * jp.rz2;
+    A[0] = -(t_xz2 * jp.yc2); A[1] = jp.zc3 * jp.rz + t_xz2 * jp.xc1; A[2] = -(jp.yc2 * jp.rz); A[3] = jp.rzs; A[4] = 0.0f; A[5] = -(jp.s_i * t_xz2);
+    B[0] = -(jp.zc3 * jp.rz) - t_yz2 * jp.yc2; B[1] = t_yz2 * jp.xc1; B[2] = jp.xc1 * jp.rz; B[3] = 0.0f; B[4] = jp.rzs; B[5] = -(jp.s_i * t_yz2);
+  } else {
+    // DisparitySpaceWarp::jacobian (types.h dspace_jac_row) expanded in the raw gradients Ix, Iy; point = (x, y, d, 1)
+    const float x = Pt.x, y = Pt.y, d = Pt.z;
+    const float xfi = x * g.ds_fx_i, yfi = y * g.ds_fy_i, dbi = d * g.ds_b_i;
+    A[0] = -(x * yfi); A[1] = g.ds_fx + x * xfi; A[2] = -(g.ds_fx * yfi); A[3] = dbi; A[4] = 0.0f; A[5] = -(dbi * xfi);
+    B[0] = -g.ds_fy - y * yfi; B[1] = y * xfi; B[2] = g.ds_fy * xfi; B[3] = 0.0f; B[4] = dbi * (g.ds_fy * g.ds_fx_i); B[5] = -(dbi * (y * g.ds_fx_i));
+  }
+}
+// acc[0 .. 20] += the upper triangle of Sxx A A^T + Sxy (A B^T + B A^T) + Syy B B^T
+__device__ __forceinline__ void irls_rank2_update(float Sxx, float Sxy, float Syy, const float (&A)[6], const float (&B)[6], float* acc)
+{
+  int idx = 0;
+#pragma unroll
+  for(int a = 0; a < 6; ++a) {
+    const float pa = irls_mad(Sxy, B[a], Sxx * A[a]);      // coefficient of A[b]
+    const float qa = irls_mad(Syy, B[a], Sxy * A[a]);      // coefficient of B[b]
+#pragma unroll
+    for(int b = a; b < 6; ++b) { acc[idx] = irls_mad(qa, B[b], irls_mad(pa, A[b], acc[idx])); ++idx; }
+  }
+}
+
 // the work of one workgroup of irls_reduce on workspace j
 // `tile` is the run of pts_per_block points (the blockIdx.x of irls_reduce), `vtid` the thread's index among the 256 that share the
 // tile, `s_part` their LDS scratch.  `has` = false: a tile past the end whose threads only keep in step (persistent kernel); all
@@ -73,9 +146,7 @@ __device__ __forceinline__ void irls_tile(const PairJob& j, const GNState* __res
   const int p_begin = tile * pts_per_block;
   const int p_end = has ? min(n, p_begin + pts_per_block) : p_begin;
   const float sigma_inv = 1.0f / st->scale;
-  const float s_nrm[4] = {j.nrm[0], j.nrm[1], j.nrm[2], j.nrm[3]};
-  const bool dspace = j.dspace != 0;      // uniform over the launch
-  const float ds_fx = j.K[0], ds_fy = j.K[4], ds_fx_i = 1.0f / j.K[0], ds_fy_i = 1.0f / j.K[4], ds_b_i = 1.0f / j.b;
+  const IrlsRowGeom geom = irls_row_geom(j);      // uniform over the launch
 
   float acc[kNumAcc];
 #pragma unroll
@@ -96,38 +167,17 @@ __device__ __forceinline__ void irls_tile(const PairJob& j, const GNState* __res
     // per point: the 8 B point record + 2*C gradient floats + C residuals (all tiled / coalesced), ALL issued before the first use
     // (7 independent 16-byte loads in flight per lane for C = 8).
     //
-    // Rank-2 structure: every channel's 1x6 Jacobian row at a point is J_c = Ix_c * A + Iy_c * B with A, B depending on
-    // the point only (jac_row in types.h expanded in Ix, Iy).  Hence
+    // Rank-2 structure (irls_point_rows): J_c = Ix_c * A + Iy_c * B with A, B depending on the point only.  Hence
     //    sum_c w_c J_c^T J_c = Sxx A A^T + Sxy (A B^T + B A^T) + Syy B B^T,   sum_c w_c r_c J_c^T = Gx A + Gy B
     // with the channel sums Sxx = sum w Ix^2, Sxy = sum w Ix Iy, Syy = sum w Iy^2, Gx = sum w r Ix, Gy = sum w r Iy.
     // Per (point, channel) that is 6 multiply-adds instead of the 27 of the reference's rankUpdatePoint; the 6x6 outer
     // products are formed once per point.  Algebraically identical, rounding differs at the 1e-7 level like any other
     // summation order (H, G are tolerance-compared).
-    if constexpr(!fused) Pt = load_point<true>(j, i);
-    if constexpr(C == 8) {
-      const float4* qr = reinterpret_cast<const float4*>(j.r.get());
-      const float4* qg = reinterpret_cast<const float4*>(j.grad.get());
-      if constexpr(!fused) {
-        const float4 r0 = load_stream(qr + tile_index<2>(i, 0)), r1 = load_stream(qr + tile_index<2>(i, 1));
-        rr[0] = r0.x; rr[1] = r0.y; rr[2] = r0.z; rr[3] = r0.w; rr[4] = r1.x; rr[5] = r1.y; rr[6] = r1.z; rr[7] = r1.w;
-      }
-      const float4 gx0 = load_stream(qg + tile_index<4>(i, 0)), gx1 = load_stream(qg + tile_index<4>(i, 1)),
-                   gy0 = load_stream(qg + tile_index<4>(i, 2)), gy1 = load_stream(qg + tile_index<4>(i, 3));
-      Ix[0] = gx0.x; Ix[1] = gx0.y; Ix[2] = gx0.z; Ix[3] = gx0.w; Ix[4] = gx1.x; Ix[5] = gx1.y; Ix[6] = gx1.z; Ix[7] = gx1.w;
-      Iy[0] = gy0.x; Iy[1] = gy0.y; Iy[2] = gy0.z; Iy[3] = gy0.w; Iy[4] = gy1.x; Iy[5] = gy1.y; Iy[6] = gy1.z; Iy[7] = gy1.w;
-    } else if constexpr(C == 1) {
-      rr[0] = j.r[i];
-      const float2 g2 = reinterpret_cast<const float2*>(j.grad.get())[i];
-      Ix[0] = g2.x; Iy[0] = g2.y;
-    } else {      // generic C: point-major r[N][pitch], grad[N][2][pitch] (pitch = C, or the whole channel count for a channel group)
-      const size_t PT = (size_t) j.pitch;
-#pragma unroll
-      for(int c = 0; c < C; ++c) {
-        rr[c] = j.r[(size_t) i * PT + c];
-        Ix[c] = j.grad[((size_t) i * 2 + 0) * PT + c];
-        Iy[c] = j.grad[((size_t) i * 2 + 1) * PT + c];
-      }
+    if constexpr(!fused) {
+      Pt = load_point<true>(j, i);
+      irls_load_residuals<C>(j, i, rr);
     }
+    irls_load_gradients<C>(j, i, Ix, Iy);
     float Sxx = 0.0f, Sxy = 0.0f, Syy = 0.0f, Gx = 0.0f, Gy = 0.0f;
 #pragma unroll
     for(int c = 0; c < C; ++c) {
@@ -142,30 +192,10 @@ __device__ __forceinline__ void irls_tile(const PairJob& j, const GNState* __res
       acc[27] = irls_mad(w * r, r, acc[27]);
     }
     float A[6], B[6];
-    if(!dspace) {
-      const JacPoint jp = jac_point(Pt.x, Pt.y, Pt.z, s_nrm);
-      const float t_xz2 = jp.x * jp.rz2, t_yz2 = jp.y * jp.rz2;
-      A[0] = -(t_xz2 * jp.yc2); A[1] = jp.zc3 * jp.rz + t_xz2 * jp.xc1; A[2] = -(jp.yc2 * jp.rz); A[3] = jp.rzs; A[4] = 0.0f; A[5] = -(jp.s_i * t_xz2);
-      B[0] = -(jp.zc3 * jp.rz) - t_yz2 * jp.yc2; B[1] = t_yz2 * jp.xc1; B[2] = jp.xc1 * jp.rz; B[3] = 0.0f; B[4] = jp.rzs; B[5] = -(jp.s_i * t_yz2);
-    } else {
-      // DisparitySpaceWarp::jacobian (types.h dspace_jac_row) expanded in the raw gradients Ix, Iy; point = (x, y, d, 1)
-      const float x = Pt.x, y = Pt.y, d = Pt.z;
-      const float xfi = x * ds_fx_i, yfi = y * ds_fy_i, dbi = d * ds_b_i;
-      A[0] = -(x * yfi); A[1] = ds_fx + x * xfi; A[2] = -(ds_fx * yfi); A[3] = dbi; A[4] = 0.0f; A[5] = -(dbi * xfi);
-      B[0] = -ds_fy - y * yfi; B[1] = y * xfi; B[2] = ds_fy * xfi; B[3] = 0.0f; B[4] = dbi * (ds_fy * ds_fx_i); B[5] = -(dbi * (y * ds_fx_i));
-    }
-    {
-      int idx = 0;
+    irls_point_rows(geom, Pt, A, B);
+    irls_rank2_update(Sxx, Sxy, Syy, A, B, acc);
 #pragma unroll
-      for(int a = 0; a < 6; ++a) {
-        const float pa = irls_mad(Sxy, B[a], Sxx * A[a]);      // coefficient of A[b]
-        const float qa = irls_mad(Syy, B[a], Sxy * A[a]);      // coefficient of B[b]
-#pragma unroll
-        for(int b = a; b < 6; ++b) { acc[idx] = irls_mad(qa, B[b], irls_mad(pa, A[b], acc[idx])); ++idx; }
-      }
-#pragma unroll
-      for(int a = 0; a < 6; ++a) acc[21 + a] = irls_mad(Gy, B[a], irls_mad(Gx, A[a], acc[21 + a]));
-    }
+    for(int a = 0; a < 6; ++a) acc[21 + a] = irls_mad(Gy, B[a], irls_mad(Gx, A[a], acc[21 + a]));
   }
 
   // wavefront tree (64 lanes, the pairing of a __shfl_down ladder without its LDS round trips: wave_tree_sums), then LDS across

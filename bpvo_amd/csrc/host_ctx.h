@@ -3,6 +3,7 @@
 //   estimate.hip  estimatePose: the Gauss-Newton drivers (chain, persistent, team)       batch.hip     pair batches, the upload pipeline
 //   vo.hip        the addFrame drivers (one frame, many sequences), point cloud,          measure.hip   profiling, counters, diagnostics
 //                 stereo front-end                                                       vo_state.h    addFrame's state machine (host only, no HIP)
+//   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)
 // The host keeps bpvo's object model (frames with a descriptor pyramid and a template pyramid, a pose estimator with per-level
 // Gauss-Newton runs, the VisualOdometry keyframe state machine) but every O(pixels) / O(points) array lives in HBM; per GN iteration the
 // host sees one 4-byte "pairs still active" counter.  See DESIGN.md.
@@ -96,6 +97,27 @@ struct Workspace {
   float* tapcache = nullptr;
   float* partials = nullptr;
   int last_ref = -1, last_cur = -1, last_level = -1;
+  bool has_estimate = false;   // the workspace's state is that of a finished estimate (pose, scale and level of its finest level): what
+                               // bpvo_hip_pose_covariances reads when no pose is given; a later linearize call on the workspace clears it
+};
+
+// Scratch of the pose-covariance pass (pose_cov.hip), allocated at its first use: `group` slots, each the residuals, valid flags, tile partials,
+// counters and Gauss-Newton state of one member, so that the pass writes nothing of a workspace; the tables of a group (jobs, members, poses,
+// scales, extrinsics) are staged in pinned memory and uploaded in one copy.
+struct CovScratch {
+  int group = 0;               // slots: min(BPVO_HIP_COV_GROUP, workspaces of the context)
+  void* d_slab = nullptr;
+  float* d_r = nullptr; size_t r_floats = 0;          // [group][r_floats]
+  uint8_t* d_valid = nullptr; size_t valid_bytes = 0; // [group][valid_bytes]
+  float* d_partials = nullptr; size_t partial_floats = 0;
+  unsigned long long* d_cnt = nullptr;                // [group][kWsCounters]
+  GNState* d_states = nullptr;                        // [group]
+  unsigned char* d_tables = nullptr;                  // the uploaded tables, laid out as h_tables
+  unsigned char* h_tables = nullptr;                  // pinned
+  size_t tables_bytes = 0, off_members = 0, off_T = 0, off_sigma = 0, off_X = 0;
+  bpvo_hip_pose_covariance* d_out = nullptr;          // [group]
+  bpvo_hip_pose_covariance* h_out = nullptr;          // pinned [group]
+  float* d_sums = nullptr;                            // [n_pairs][72]: M and Q of the last pass on each workspace
 };
 
 enum KernelClass { KC_PYRAMID = 0, KC_DESCRIPTOR, KC_SALIENCY_SELECT, KC_NORMALIZATION, KC_TEMPLATE, KC_WARP_RESIDUAL, KC_MEDIAN,
@@ -205,6 +227,12 @@ struct bpvo_hip_ctx {
   std::vector<float> rig_X;
   SeqState rig_body;
   float* d_rig_X = nullptr;        // [n_pairs][16], allocated at its first use
+  // Pose covariance (c_api.h bpvo_hip_pose_covariances, pose_cov.hip).  Option "pose_covariance": the addFrame entry points run the pass behind
+  // the estimate their result's pose comes from and keep the record — vo_cov for bpvo_hip_add_frame, seq_cov[s] per sequence, rig_cov for the rig.
+  int pose_covariance = 0;
+  CovScratch cov;
+  bpvo_hip_pose_covariance vo_cov, rig_cov;
+  std::vector<bpvo_hip_pose_covariance> seq_cov;
   // measurement
   double points_fused = 0;     // points linearised through the fused path since the last counter reset
   int fast_warp = 0;           // bpvo_hip_set_warp_formulation
@@ -541,6 +569,14 @@ int check_template_not_empty(bpvo_hip_ctx* c, int ref_slot);
 int ensure_lanes(bpvo_hip_ctx* c, int n);
 int lanes_for(bpvo_hip_ctx* c, int n, int cap);
 int ensure_dense_descriptor(bpvo_hip_ctx* c, int slot);      // a slot with lazy levels gets its full records (accessors, a template frame used as current)
+// Pose covariance (pose_cov.hip): n_records records of `members` members each — member p of record r is entry r * members + p of wss / refs / curs
+// (and of sigma; prms: each entry's own parameters or null) —, X null (cameras) or [members][16] (a rig: one record), T [n_records][16] and sigma
+// given, or both null: the workspaces' last estimates.  Runs on the context's stream and returns with the records in `out`.
+int pose_cov_pass(bpvo_hip_ctx* c, int n_records, int members, const int* wss, const int* refs, const int* curs, const float* X, int level,
+                  const float* T, const float* sigma, const bpvo_hip_params* const* prms, bpvo_hip_pose_covariance* out);
+int pose_cov_ensure_scratch(bpvo_hip_ctx* c);
+void pose_cov_none(bpvo_hip_pose_covariance* r);      // the record of "nothing was estimated": Identity pose and covariance, BPVO_COV_NONE
+void pose_cov_free(bpvo_hip_ctx* c);
 int set_option(bpvo_hip_ctx* c, const std::string& key, double v);
 int apply_options_string(bpvo_hip_ctx* c, const char* str);
 struct OptionDef { const char* key; double lo, hi; std::function<double(bpvo_hip_ctx*)> get; std::function<int(bpvo_hip_ctx*, double)> set; };

@@ -229,6 +229,29 @@ struct RigStepArgs {
   int reference;
 };
 void launch_rig_step(hipStream_t s, const RigStepArgs& a);
+// Pose covariance (kernels_gn_cov.hip; c_api.h bpvo_hip_pose_covariances).  A pass serves n_records records of `members` members each (a camera:
+// one member; a rig: one record of all its members); entry r * members + p of `jobs` / `members_tab` is member p of record r.  The jobs are COPIES
+// of the workspaces' jobs whose r, valid, partials, cnt and st point into the pass's own scratch (no tap cache, no median buffers: the scratch
+// state's scale is frozen), so the warp_residual launches of the pass write nothing a later call reads.
+struct CovMember {
+  const GNState* src;      // the workspace's own state: pose (T_out), scale and level of its last estimate, read when none is given
+  float* sums;             // [72] the member's M and Q (normalised twist, symmetric, narrowed to f32): bpvo_hip_debug_pose_covariance_sums
+};
+struct CovLaunch {
+  const PairJob* jobs;           // device
+  const CovMember* members_tab;  // device
+  int n_records, members;
+  const float* T;                // device [n_records][16] poses (a rig: body poses), or null: every member's src->T_out
+  const float* sigma;            // device [n_records * members], or null: src->scale
+  const float* X;                // device [members][16] camera_from_body, or null: one camera per record, X = I
+  int level;                     // the level of the jobs (echoed; T == null: the states' own level must equal it, else the record is BPVO_COV_NONE)
+  int max_points, C, loss;
+  bpvo_hip_pose_covariance* out; // device [n_records]
+};
+int  pose_cov_partials_floats(int cap, int C);          // floats of one member's tile partials
+void launch_pose_cov_prepare(hipStream_t s, const CovLaunch& g);   // the scratch states from (T, sigma) or from the workspaces' last estimates
+void launch_pose_cov_reduce(hipStream_t s, const CovLaunch& g);    // loss g.loss; members whose job carries another loss are left alone
+void launch_pose_cov_finish(hipStream_t s, const CovLaunch& g);
 void launch_prepare_linearize(hipStream_t s, const PairJob* job, const float* T /*device [16]*/, int reset_scale, int level, float given_scale = 0.0f);
 int  gn_pts_per_block(int C);
 int  gn_partials_entries(int cap, int C);   // kPartialStride-float entries of a workspace's (double-buffered) tile partials

@@ -334,6 +334,7 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
   (void) hipSetDevice(c->device);
   SeqState& q = c->vo;
   vo_begin_frame(q, c->L, ret);
+  pose_cov_none(&c->vo_cov);
 
   // _cur_frame->setData (vo.cc:131).  No host synchronisation behind it: the estimate queues behind the data stage on the same stream and ends
   // with one (every copy from the caller's buffers is complete when this function returns — its early returns synchronise themselves).  The
@@ -375,6 +376,12 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
     if(rc == BPVO_OK) rc = rcu;
   }
   if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
+  // option "pose_covariance": the pass behind the estimate, from the workspace's state on the device and before the key frame's stages rewrite any
+  // slot; at a key frame with re-estimation it runs again behind the re-estimate, whose pose the result carries
+  if(c->pose_covariance) {
+    rc = pose_cov_pass(c, 1, 1, &ws0, &q.ref, &q.cur, nullptr, c->params.maxTestLevel, nullptr, nullptr, nullptr, &c->vo_cov);
+    if(rc) return rc;
+  }
   // the key-frame decision (vo.cc:199-224).  The fraction of good points is fetched only where the motion leaves the decision to it: an estimate
   // that could not take the count along pays a launch and a round trip for it.
   float frac = 0.0f;
@@ -407,9 +414,14 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
       if(c->nrm_pending_finest) { (void) hipEventSynchronize(c->nrm_pending_finest); c->nrm_pending_finest = nullptr; }
       if(rc) return rc;
       again = true;
+      if(c->pose_covariance) {
+        rc = pose_cov_pass(c, 1, 1, &ws0, &q.ref, &q.cur, nullptr, c->params.maxTestLevel, nullptr, nullptr, nullptr, &c->vo_cov);
+        if(rc) return rc;
+      }
     }
   }
   vo_finish(q, T_est, again ? &T_again : nullptr, ret);
+  if(c->pose_covariance) std::memcpy(ret->covariance, c->vo_cov.covariance, sizeof(ret->covariance));
   return BPVO_OK;
 }
 
@@ -472,6 +484,8 @@ static void seq_reset_state(bpvo_hip_ctx* c, int s)
   for(int k = 0; k < 3; ++k) slot_clear(c, 3 * s + k);
   Workspace& w = c->ws[s];
   w.last_ref = w.last_cur = w.last_level = -1;
+  w.has_estimate = false;
+  if((size_t) s < c->seq_cov.size()) pose_cov_none(&c->seq_cov[(size_t) s]);
 }
 // the sequences' host state (no device storage: bpvo_hip_seq_set_params may come before the first frame); every sequence starts with the context's parameters
 static void seq_states(bpvo_hip_ctx* c)
@@ -594,6 +608,11 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
   c->vo_mode = 2;
   const M44 I = m44_identity();
   for(int i = 0; i < n; ++i) vo_begin_frame(c->seqs[ids[i]], c->L, results + i);
+  if(c->seq_cov.size() != c->seqs.size()) {
+    c->seq_cov.resize(c->seqs.size());
+    for(auto& r : c->seq_cov) pose_cov_none(&r);
+  }
+  for(int i = 0; i < n; ++i) pose_cov_none(&c->seq_cov[(size_t) ids[i]]);
   auto drain = [&](int code) { (void) hipStreamSynchronize(c->stream); return code; };
 
   // 2. _cur_frame->setData (vo.cc:131) of every sequence: one data stage over their current slots
@@ -650,6 +669,14 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
   rc = estimate_batch(c, m, wss.data(), refs.data(), curs.data(), T_init.data(), T_est.data(), stats.data(), own ? prms.data() : nullptr);
   if(rc) return drain(rc);
   for(int k = 0; k < m; ++k) std::memcpy(results[est[k]].optimizerStatistics, &stats[(size_t) k * L], sizeof(bpvo_hip_stats) * L);
+  // option "pose_covariance": every estimating sequence of the call in one launch set per group, from the workspaces' states on the device and
+  // before the key frames' stages rewrite any slot (the sequences that estimate again: once more behind that estimate)
+  std::vector<bpvo_hip_pose_covariance> cov;
+  if(c->pose_covariance) {
+    cov.resize((size_t) m);
+    rc = pose_cov_pass(c, m, 1, wss.data(), refs.data(), curs.data(), nullptr, lvl, nullptr, nullptr, own ? prms.data() : nullptr, cov.data());
+    if(rc) return rc;
+  }
 
   // 5. the key-frame decision (vo.cc:199-224): motion on the host, the fraction of good points of every estimated sequence in one count
   int max_n = 0;
@@ -728,6 +755,12 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
       rc = estimate_batch(c, mr, w2.data(), r2.data(), c2.data(), I2.data(), T_again_all.data(), st2.data(), own ? p2.data() : nullptr);
       if(rc) return drain(rc);
       for(int t = 0; t < mr; ++t) std::memcpy(results[est[kf[re[t]]]].optimizerStatistics, &st2[(size_t) t * L], sizeof(bpvo_hip_stats) * L);
+      if(c->pose_covariance) {
+        std::vector<bpvo_hip_pose_covariance> cov2((size_t) mr);
+        rc = pose_cov_pass(c, mr, 1, w2.data(), r2.data(), c2.data(), nullptr, lvl, nullptr, nullptr, own ? p2.data() : nullptr, cov2.data());
+        if(rc) return rc;
+        for(int t = 0; t < mr; ++t) cov[(size_t) kf[re[t]]] = cov2[(size_t) t];
+      }
     }
   }
 
@@ -739,6 +772,10 @@ static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, c
     std::memcpy(T.m, &T_est[(size_t) k * 16], 64);
     if(again_of[k] >= 0) std::memcpy(T_again.m, &T_again_all[(size_t) again_of[k] * 16], 64);
     vo_finish(c->seqs[wss[k]], T, again_of[k] >= 0 ? &T_again : nullptr, &results[est[k]]);
+    if(c->pose_covariance) {
+      c->seq_cov[(size_t) wss[k]] = cov[(size_t) k];
+      std::memcpy(results[est[k]].covariance, cov[(size_t) k].covariance, sizeof(results[est[k]].covariance));
+    }
   }
   return BPVO_OK;
 }
@@ -841,6 +878,7 @@ int bpvo_hip_add_frames_rig(bpvo_hip_ctx* c, const uint8_t* images, const float*
   if(rc) return rc;
   SeqState& body = c->rig_body;
   vo_begin_frame(body, L, result);
+  pose_cov_none(&c->rig_cov);
   for(int i = 0; i < n; ++i) { bpvo_hip_result own; vo_begin_frame(*members[i], L, &own); }
   auto drain = [&](int code) { (void) hipStreamSynchronize(c->stream); return code; };
   auto template_stage = [&](const int* sl, int count, const size_t*, const FrameRun& fr) { return frames_set_template_slots(c, sl, count, fr); };
@@ -874,6 +912,11 @@ int bpvo_hip_add_frames_rig(bpvo_hip_ctx* c, const uint8_t* images, const float*
   M44 T_est, T_again;
   rc = estimate_rig(c, n, wss.data(), refs.data(), curs.data(), X, body.T_kf.m, T_est.m, result->optimizerStatistics);
   if(rc) return drain(rc);
+  // option "pose_covariance": the body pose's, from the members' states on the device (again behind a re-estimate)
+  if(c->pose_covariance) {
+    rc = pose_cov_pass(c, 1, n, wss.data(), refs.data(), curs.data(), X, lvl, nullptr, nullptr, nullptr, &c->rig_cov);
+    if(rc) return rc;
+  }
 
   // 5. ONE key-frame decision: the body's motion, then the fraction of good points pooled over the members (one count launch)
   int max_n = 0;
@@ -923,11 +966,16 @@ int bpvo_hip_add_frames_rig(bpvo_hip_ctx* c, const uint8_t* images, const float*
       rc = estimate_rig(c, n, wss.data(), refs.data(), curs.data(), X, I.m, T_again.m, result->optimizerStatistics);
       if(rc) return drain(rc);
       again = true;
+      if(c->pose_covariance) {
+        rc = pose_cov_pass(c, 1, n, wss.data(), refs.data(), curs.data(), X, lvl, nullptr, nullptr, nullptr, &c->rig_cov);
+        if(rc) return rc;
+      }
     }
   }
 
   // 7. the pose, T_kf and the trajectory of the body; every member's slots, and its cloud's pose
   vo_rig_finish(body, members.data(), X, n, T_est, again ? &T_again : nullptr, result);
+  if(c->pose_covariance) std::memcpy(result->covariance, c->rig_cov.covariance, sizeof(result->covariance));
   return BPVO_OK;
 }
 // StereoAlgorithm::run + addFrame of every sequence of the call (apps/vo_app.cc per camera): the front-end once over all the pairs, each in

@@ -101,7 +101,8 @@ typedef struct bpvo_hip_stats {
  * fetched separately with bpvo_hip_get_point_cloud when isKeyFrame && hasPointCloud */
 typedef struct bpvo_hip_result {
   float pose[16];
-  float covariance[36];                   /* never written by the reference: Identity (Q16) */
+  float covariance[36];                   /* never written by the reference: Identity (Q16) — unless option "pose_covariance" is set: then the
+                                           * covariance of the estimate's pose, bpvo_hip_pose_covariance::covariance below */
   bpvo_hip_stats optimizerStatistics[BPVO_HIP_MAX_LEVELS];
   int   numLevels;
   int   isKeyFrame;
@@ -435,12 +436,71 @@ int bpvo_hip_rig_get(const bpvo_hip_ctx* ctx, int* n, int* seq /*[n] or NULL*/, 
 /* VisualOdometry::addFrame of the rig: the members' frames packed as for bpvo_hip_add_frames, in member order, each in its camera's size.
  * One estimate of the body pose (from the body's pose against the key frame; against a new key frame from the identity), ONE key-frame
  * decision — the context's thresholds on the body pose, the fraction of good points pooled over the members, sum good_p / sum n_p C — and
- * every member the same transition.  `result` is the body's (covariance: Identity).  At a key frame every member's point cloud and point
+ * every member the same transition.  `result` is the body's (covariance: Identity, or with option "pose_covariance" the body pose's).  At a key frame every member's point cloud and point
  * counts come from the bpvo_hip_seq_* accessors; a cloud's pose is W_kf X_p^-1 (world_from_camera), W_kf the body trajectory's pose of the
  * result that carries the cloud.  After an error the rig goes on as if the call had not been made. */
 int bpvo_hip_add_frames_rig(bpvo_hip_ctx* ctx, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* result);
 int bpvo_hip_rig_trajectory_size(bpvo_hip_ctx* ctx, int* n);
 int bpvo_hip_rig_get_trajectory(bpvo_hip_ctx* ctx, float* poses /*[n][16]: the body's trajectory*/);
+
+/* ---- pose covariance: a robust "sandwich" estimate of the uncertainty of an estimated pose (the reference has none: its Result::covariance is
+ * never written, Q16).
+ * Definition.  Take the pose T^ of a finished estimate at the finest pyramid level the estimate ran (maxTestLevel) and sigma, the robust scale
+ * that level ended with (kL2 ignores it).  With u = r / sigma, w(u) the library's M-estimator weight, v_p the valid flag of template point p — AND the
+ * point in front of the camera at T^ (z > 0, f32): the warp's own rule has no such test, a point behind the camera that projects into the image
+ * is valid for the estimate as it is in the reference, but it says nothing about the pose's uncertainty; num_valid counts the v_p of this rule — and
+ * J_pc the 1x6 Jacobian row of point p, channel c in the level's Hartley-normalised twist (the J of bpvo_hip_get_jacobians):
+ *   curvature         M = sum_p v_p sum_c d(u_pc) J_pc^T J_pc,  d = psi':  kL2 d = 1;  Huber d = 1 where |u| <= 1.345 (exactly where w = 1), else 0;
+ *                     Tukey, q = (u / 4.685)^2: d = (1 - q)(1 - 5 q) where |u| < 4.685, else 0
+ *   score covariance  Q = sum_p v_p g_p^T g_p,  g_p = sum_c w(u_pc) r_pc J_pc — the channels of a point are ONE cluster (they see the same pixel
+ *                     neighbourhood); sum_p g_p is the G of bpvo_hip_linearize_at_scale at the same pose and scale
+ *   Sigma_xi = M^-1 Q M^-1 — no sigma^2 factor, no finite-sample factor —, and in the plain twist Sigma = A Sigma_xi A^T with
+ *   A = [[I, 0], [[c]x, I/s]] for the level's normalisation (s, c): the identity without normalisation and for BPVO_WARP_DISPARITY_SPACE_F32.
+ * Sigma is the covariance of eps in T_true = T^ twist_to_matrix(eps), twist ordered (omega, v): the parametrisation of the library's own update.
+ * Rig: M_b = sum_p B_p^T M_p B_p, Q_b = sum_p B_p^T Q_p B_p with B_p = A_p^-1 Ad(X_p) (bpvo_hip_linearize_rig's map), members in order, and
+ * Sigma_b = M_b^-1 Q_b M_b^-1 is the covariance of the body pose in the plain body twist.  One camera is the rig of one member with X = I.
+ * The per-tile sums are f32 (the reduction's tiles and wave tree) and combined in tile order in f64 into each camera's M_p and Q_p, which are kept
+ * as f32 like H and G of a linearisation (bpvo_hip_debug_pose_covariance_sums returns exactly them); everything behind that is f64 — the maps, the
+ * congruences, an LDL^T of the curvature, two solves, the upper triangle mirrored — and the result is narrowed to f32 once.
+ * Limits.  The estimate treats the template points as independent clusters.  For the intensity descriptor it is calibrated: over 150 noise draws
+ * the empirical standard deviation of the pose is 1.07 - 1.13 times the reported one, under every loss.  For bit-planes it is OPTIMISTIC by a
+ * factor of 1.7 - 2.3 in standard deviation (census 3x3 and the 5x5 blur correlate neighbouring points, which no per-point form can see):
+ * INTEGRATION.md section 4, profiles/pose_covariance_calibration.json.  It is the uncertainty of the alignment given the template, not of the
+ * template's depth.
+ * status: BPVO_COV_OK; BPVO_COV_INDEFINITE — the LDL^T of the curvature met a pivot <= 0 (Tukey away from a minimum); BPVO_COV_DEGENERATE — fewer
+ * than 6 valid points in total, or a sum that is not finite; BPVO_COV_NONE — nothing was estimated (a first frame, a batch pair whose finest level
+ * was skipped).  Anything but OK leaves `covariance` at the Identity.  No status is an error return, and no pose raises. */
+enum { BPVO_COV_OK = 0, BPVO_COV_INDEFINITE = 1, BPVO_COV_DEGENERATE = 2, BPVO_COV_NONE = 3 };
+#define BPVO_HIP_COV_GROUP 64      /* workspaces that go through the pass together (its scratch holds this many finest-level templates) */
+typedef struct bpvo_hip_pose_covariance {
+  float T[16];              /* the pose the covariance belongs to (a rig: the body pose) */
+  float covariance[36];     /* row-major, exactly symmetric */
+  float sigma;              /* the robust scale the weights were taken with (a rig: member 0's) */
+  int   num_valid;          /* valid template points (a rig: over all members) */
+  int   level;
+  int   status;             /* BPVO_COV_* */
+} bpvo_hip_pose_covariance;
+/* Stateless, like bpvo_hip_linearize_at_scale: record i for workspace wss[i] (distinct), template refs[i], current frame curs[i] at pyramid
+ * level `level`.  T [n][16] and sigma [n] both given: at those poses and scales.  Both NULL: each workspace's LAST ESTIMATE — its final pose, the
+ * scale and the level it ended with, read on the device (`level` is ignored; BPVO_ERR_NO_DATA if a workspace holds no estimate, e.g. after a
+ * bpvo_hip_linearize on it) — which is how the covariances of a bpvo_hip_batch_run / bpvo_hip_batch_estimate are asked for.  The pass recomputes
+ * the residuals at the pose into scratch of its own (allocated at the first call, for BPVO_HIP_COV_GROUP workspaces; larger calls run in groups):
+ * the workspaces' residuals, weights, Gauss-Newton states and every measurement counter stay as they were.
+ * A context of more than 48 channels: BPVO_ERR_UNSUPPORTED. */
+int bpvo_hip_pose_covariances(bpvo_hip_ctx* ctx, int n, const int* wss, const int* refs, const int* curs, int level, const float* T /*[n][16] or NULL*/,
+                              const float* sigma /*[n] or NULL*/, bpvo_hip_pose_covariance* out /*[n]*/);
+/* The rig's: ONE record for the body pose from members (wss[i], refs[i], curs[i], X + 16 i) as in bpvo_hip_linearize_rig.  T_body and sigma [n]
+ * (every member's own scale) both given, or both NULL = the last bpvo_hip_estimate_pose_rig of exactly these members. */
+int bpvo_hip_pose_covariance_rig(bpvo_hip_ctx* ctx, int n, const int* wss, const int* refs, const int* curs, const float* X /*[n][16]*/, int level,
+                                 const float* T_body /*[16] or NULL*/, const float* sigma /*[n] or NULL*/, bpvo_hip_pose_covariance* out);
+/* The record of the last frame of bpvo_hip_add_frame / of sequence seq of bpvo_hip_add_frames / of bpvo_hip_add_frames_rig with option
+ * "pose_covariance" set (status BPVO_COV_NONE otherwise, and for a first frame).  T is the pose of the estimate the result's pose comes from
+ * AGAINST ITS KEY FRAME — at a key frame with re-estimation the re-estimate's —, not the frame-to-frame `pose` of the result. */
+int bpvo_hip_vo_pose_covariance(bpvo_hip_ctx* ctx, bpvo_hip_pose_covariance* out);
+int bpvo_hip_seq_pose_covariance(bpvo_hip_ctx* ctx, int seq, bpvo_hip_pose_covariance* out);
+int bpvo_hip_rig_pose_covariance(bpvo_hip_ctx* ctx, bpvo_hip_pose_covariance* out);
+/* diagnostics: the curvature M and the score covariance Q (row-major, symmetric) of the last pass on workspace ws, in its normalised twist */
+int bpvo_hip_debug_pose_covariance_sums(bpvo_hip_ctx* ctx, int ws, float M[36], float Q[36]);
 
 /* Pyramid levels that were run by the persistent single-launch Gauss-Newton kernel (groups of BPVO_HIP_PERSIST_MAX_WS or fewer
  * pairs) since the context was created, and whether such a launch ever gave up at a grid barrier (the
@@ -481,7 +541,8 @@ int bpvo_hip_fused_point_counts(bpvo_hip_ctx* ctx, uint64_t* fused, uint64_t* to
 int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* ctx, uint64_t out[4]);
 /* ---- per-context options: how the library schedules its work.  None of them changes a result (every setting is covered by a
  * bit-identity test) — with ONE exception, the validation mode "reference_reduction" at the end of the table, which changes the summation
- * order of the normal equations to the reference's own; they exist so that a caller — not the process environment — decides, per context.  Call between API calls, from the
+ * order of the normal equations to the reference's own, and a second one, "pose_covariance", which changes the covariance field of the
+ * results and nothing else; they exist so that a caller — not the process environment — decides, per context.  Call between API calls, from the
  * thread that drives the context.  Unknown key or value out of range: BPVO_ERR_INVALID_ARG (bpvo_hip_last_error names the key).
  *
  *   key                      default   meaning
@@ -567,6 +628,13 @@ int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* ctx, uint64_t out[4]);
  *                                      4e-6 of an f64 evaluation, poses within 1e-4 rad / 1e-3 m, iteration counts inside the reference's own
  *                                      spread between its serial and its TBB build.  In this mode every estimate takes the four-kernel chain
  *                                      (no persistent / team kernel, no fused path, no step inside the reduction).
+ *   "pose_covariance"        0         1: bpvo_hip_add_frame(_stereo), bpvo_hip_add_frames(_stereo) and bpvo_hip_add_frames_rig run the pose-covariance pass
+ *                                      (bpvo_hip_pose_covariances above) behind the estimate the result's pose comes from — all estimating sequences of
+ *                                      a call in one launch set per group of BPVO_HIP_COV_GROUP —, write it into result.covariance and keep the record
+ *                                      for bpvo_hip_vo / seq / rig_pose_covariance: about one more finest-level linearisation per estimate.  0: those
+ *                                      calls issue exactly the launches they issue without the feature and return the Identity.  Poses, statistics,
+ *                                      key-frame decisions, point clouds, residuals, weights and counters are the same either way.  More than 48
+ *                                      channels: BPVO_ERR_UNSUPPORTED.
  *   "keep_current_disparity" 0         bpvo_hip_batch_run stores the disparity of the CURRENT frame (B) of every pair too.  By default it is
  *                                      neither uploaded nor stored — nothing on the path reads it — and bpvo_hip_frame(s)_set_template on
  *                                      such a slot returns BPVO_ERR_NO_DATA; set 1 before batches whose B frames become templates later.

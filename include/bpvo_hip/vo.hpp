@@ -109,6 +109,23 @@ struct Result {                                                 // bpvo/types.h:
   Result& operator=(const Result&) = delete;
 };
 
+/* The covariance of an estimated pose (c_api.h bpvo_hip_pose_covariances states the definition and its limits): `covariance` is that of eps in
+ * T_true = pose * exp(eps), twist ordered (omega, v); `pose` is the estimate's pose against its key frame. */
+struct PoseCovarianceEstimate {
+  enum Status { kOk = BPVO_COV_OK, kIndefinite = BPVO_COV_INDEFINITE, kDegenerate = BPVO_COV_DEGENERATE, kNone = BPVO_COV_NONE };
+  Pose pose;
+  PoseCovariance covariance;
+  float sigma;
+  int numValid, level;
+  Status status;
+  PoseCovarianceEstimate() : sigma(0.0f), numValid(0), level(-1), status(kNone) {}
+  explicit PoseCovarianceEstimate(const bpvo_hip_pose_covariance& r) : sigma(r.sigma), numValid(r.num_valid), level(r.level), status((Status) r.status)
+  {
+    std::memcpy(pose.data(), r.T, sizeof(r.T));
+    std::memcpy(covariance.data(), r.covariance, sizeof(r.covariance));
+  }
+};
+
 class Trajectory {                                              // bpvo/trajectory.h
  public:
   size_t size() const { return _poses.size(); }
@@ -359,6 +376,14 @@ class VisualOdometry {
   /* scheduling options of the device context (c_api.h "Options"; the reference has none) */
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
+  /* Result::covariance carries the covariance of the estimated pose (option "pose_covariance"); poseCovariance(): the last frame's record */
+  void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
+  PoseCovarianceEstimate poseCovariance() const
+  {
+    bpvo_hip_pose_covariance r;
+    _dev->check(bpvo_hip_vo_pose_covariance(_dev->ctx(), &r));
+    return PoseCovarianceEstimate(r);
+  }
 
  private:
   Result makeResult(const bpvo_hip_result& r)
@@ -488,6 +513,14 @@ class VisualOdometrySequences {
   }
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
+  /* Result::covariance of every sequence carries the covariance of its estimated pose (option "pose_covariance"); poseCovariance(s): sequence s's last record */
+  void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
+  PoseCovarianceEstimate poseCovariance(int s) const
+  {
+    bpvo_hip_pose_covariance r;
+    _dev->check(bpvo_hip_seq_pose_covariance(_dev->ctx(), s, &r));
+    return PoseCovarianceEstimate(r);
+  }
 
  private:
   static bpvo_hip_camera toC(const Camera& cam)
@@ -550,7 +583,7 @@ class RigVisualOdometry {
   int numCameras() const { return _n; }
 
   /* images / disparities: the cameras' frames back to back in camera order, each of its camera's size.  The Result is the body's: its pose maps the
-   * previous body frame to this one, its covariance is the Identity; at a key frame the cameras' point clouds are fetched with pointCloud(camera)
+   * previous body frame to this one, its covariance is the Identity unless setPoseCovariance(true); at a key frame the cameras' point clouds are fetched with pointCloud(camera)
    * (Result::pointCloud stays empty: there is one cloud per camera). */
   Result addFrame(const uint8_t* images, const float* disparities)
   {
@@ -592,6 +625,14 @@ class RigVisualOdometry {
   }
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
+  /* Result::covariance carries the covariance of the BODY pose, in the plain body twist (option "pose_covariance"); poseCovariance(): the last frame's record */
+  void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
+  PoseCovarianceEstimate poseCovariance() const
+  {
+    bpvo_hip_pose_covariance r;
+    _dev->check(bpvo_hip_rig_pose_covariance(_dev->ctx(), &r));
+    return PoseCovarianceEstimate(r);
+  }
 
  private:
   static std::vector<bpvo_hip_camera> toC(const std::vector<Camera>& cams)
