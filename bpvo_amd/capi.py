@@ -705,6 +705,94 @@ class Context:
             self.call("rig_get_trajectory", out.ctypes.data_as(C.c_void_p))
         return out
 
+    # -- several rigs in one context (bpvo_hip_rigs_*; HIP library only)
+    def rigs_set(self, Xs, seqs=None):
+        """bpvo_hip_rigs_set: rig r has the extrinsics Xs[r] [n_r, 4, 4] and the member sequences seqs[r] (seqs None: 0, 1, 2, ... rig after rig)."""
+        counts = np.ascontiguousarray([len(X) for X in Xs], dtype=np.int32)
+        Xf = _f32(np.concatenate([_f32(X).reshape(-1, 16) for X in Xs], axis=0)) if len(Xs) else np.zeros((0, 16), np.float32)
+        ids, p_ids = (None, None) if seqs is None else self._seq_ids(int(counts.sum()), np.concatenate([np.asarray(q, np.int32).reshape(-1) for q in seqs]))
+        self.call("rigs_set", len(Xs), counts.ctypes.data_as(C.c_void_p), p_ids, Xf.ctypes.data_as(C.c_void_p))
+
+    def rigs_get(self):
+        """[(sequence ids [n_r], extrinsics [n_r, 4, 4])] of the declared rigs."""
+        R = C.c_int()
+        self._ck(self.b.fn("rigs_get")(self.h, C.byref(R), None, None, None))
+        if not R.value:
+            return []
+        counts = np.empty(R.value, np.int32)
+        self._ck(self.b.fn("rigs_get")(self.h, C.byref(R), counts.ctypes.data_as(C.c_void_p), None, None))
+        total = int(counts.sum())
+        ids, X = np.empty(total, np.int32), np.empty((total, 4, 4), np.float32)
+        self._ck(self.b.fn("rigs_get")(self.h, C.byref(R), counts.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), X.ctypes.data_as(C.c_void_p)))
+        at = np.concatenate([[0], np.cumsum(counts)])
+        return [(ids[at[r]:at[r + 1]].copy(), X[at[r]:at[r + 1]].copy()) for r in range(R.value)]
+
+    def rigs_set_params(self, rig, params: Params):
+        """bpvo_hip_rigs_set_params: rig `rig` runs with its own Params (the fields seq_set_params accepts); only while its members hold no frame."""
+        self.call("rigs_set_params", int(rig), C.byref(params))
+
+    def rigs_get_params(self, rig) -> Params:
+        p = Params()
+        self._ck(self.b.fn("rigs_get_params")(self.h, int(rig), C.byref(p)))
+        return p
+
+    def add_frames_rigs(self, images, disps, rigs=None):
+        """bpvo_hip_add_frames_rigs: images[i] / disps[i] are the next frames of the members of rig rigs[i] (None: 0 .. n-1), lists of 2-D arrays in
+        member order, each of its camera's size; returns the bodies' results, one dict per named rig."""
+        n = len(images)
+        ids, p_ids = self._seq_ids(n, rigs)
+        declared = self.rigs_get()
+        flat_i, flat_d = [], []
+        for i in range(n):
+            r = int(ids[i]) if ids is not None else i
+            if 0 <= r < len(declared):
+                assert len(images[i]) == len(declared[r][0]), f"rig {r} has {len(declared[r][0])} members"
+                for k, s in enumerate(declared[r][0]):
+                    cam = self.seq_get_camera(int(s))
+                    assert np.shape(images[i][k]) == (cam.rows, cam.cols), f"rig {r}: member {k} (sequence {s}) takes {cam.rows}x{cam.cols} frames"
+            flat_i += list(images[i])
+            flat_d += list(disps[i])
+        img, disp, _ = pack_frames(flat_i, flat_d)
+        res = (Result * n)()
+        self.call("add_frames_rigs", n, p_ids, img.ctypes.data_as(C.c_void_p), disp.ctypes.data_as(C.c_void_p), 0, res)
+        return [self._result_dict(r) for r in res]
+
+    def add_frames_rigs_device(self, n, d_images_ptr, d_disps_ptr, rigs=None):
+        """add_frames_rigs with the packed frames already in device memory."""
+        ids, p_ids = self._seq_ids(n, rigs)
+        res = (Result * n)()
+        self.call("add_frames_rigs", int(n), p_ids, C.c_void_p(d_images_ptr), C.c_void_p(d_disps_ptr), 1, res)
+        return [self._result_dict(r) for r in res]
+
+    def rigs_trajectory(self, rig):
+        n = C.c_int()
+        self.call("rigs_trajectory_size", int(rig), C.byref(n))
+        out = np.empty((n.value, 4, 4), np.float32)
+        if n.value:
+            self.call("rigs_get_trajectory", int(rig), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def rigs_pose_covariance(self, rig):
+        out = PoseCovariance()
+        self.call("rigs_pose_covariance", int(rig), C.byref(out))
+        return _cov_dict(out)
+
+    def estimate_pose_rigs(self, wss, refs, curs, X, T_init=None):
+        """bpvo_hip_estimate_pose_rigs: wss / refs / curs / X are lists with one entry per rig (as estimate_pose_rig takes them), T_init [n_rigs, 4, 4]
+        (None: identities); returns (body poses [n_rigs, 4, 4], [per-level statistics] per rig)."""
+        R = len(wss)
+        parts = [self._rig_members(wss[r], refs[r], curs[r], X[r]) for r in range(R)]
+        counts = np.ascontiguousarray([q[0].shape[0] for q in parts], dtype=np.int32)
+        w, r_, c_, Xf = (np.ascontiguousarray(np.concatenate([q[k] for q in parts], axis=0)) for k in range(4))
+        T0 = _f32(np.tile(np.eye(4), (R, 1, 1)) if T_init is None else T_init).reshape(R, 16)
+        T = np.empty((R, 4, 4), np.float32)
+        st = (Stats * (self.L * R))()
+        self.call("estimate_pose_rigs", R, counts.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), r_.ctypes.data_as(C.c_void_p),
+                  c_.ctypes.data_as(C.c_void_p), Xf.ctypes.data_as(C.c_void_p), T0.ctypes.data_as(C.c_void_p), T.ctypes.data_as(C.c_void_p), st)
+        stats = [[dict(numIterations=s.numIterations, finalError=s.finalError, firstOrderOptimality=s.firstOrderOptimality, status=s.status)
+                  for s in st[k * self.L:(k + 1) * self.L]] for k in range(R)]
+        return T, stats
+
     # -- pose covariance (bpvo_hip_pose_covariances ...; HIP library only)
     def pose_covariances(self, wss, refs, curs, level, T=None, sigma=None):
         """One record (dict) per workspace: at the poses T [n, 4, 4] and scales sigma [n], or (both None) of each workspace's last estimate."""

@@ -270,7 +270,7 @@ int ensure_lanes(bpvo_hip_ctx* c, int n)
       HIP_CK(c, hipHostMalloc((void**) &ln.h_team_ctl, sizeof(unsigned) * 64));      // (two launches' first lines: estimate.hip)
       std::memset(ln.h_team_ctl, 0, sizeof(unsigned) * 64);
     }
-    HIP_CK(c, hipHostMalloc((void**) &ln.h_states, sizeof(GNState) * (n_pairs + 1)));      // (+ 1: the body state of rig mode)
+    HIP_CK(c, hipHostMalloc((void**) &ln.h_states, sizeof(GNState) * (n_pairs + n_pairs)));      // (+ n_pairs: the body states of rig mode, a rig has at least one member)
   }
   return BPVO_OK;
 }
@@ -487,7 +487,6 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
   }
   std::unique_ptr<bpvo_hip_ctx> c(new bpvo_hip_ctx);
   pose_cov_none(&c->vo_cov);
-  pose_cov_none(&c->rig_cov);
   c->params = *p;
   std::memcpy(c->K, K, sizeof(c->K));
   c->baseline = baseline;
@@ -648,9 +647,9 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
     // two buffers of tile partials (the persistent kernels double-buffer them by iteration parity, kernels_gn.hip pk_partials)
     CREATE_CK(hipMalloc((void**) &w.partials, sizeof(float) * (size_t) gn_partials_entries(cp->cap_max, cp->G > 1 ? cp->Cg : cp->C) * std::max(1, (cp->G + 1) / 2) * kPartialStride));
   }
-  // (entry n_pairs: the body state of rig mode, estimate.hip estimate_rig)
-  CREATE_CK(hipMalloc((void**) &cp->d_states, sizeof(GNState) * (n_pairs + 1)));
-  CREATE_CK(hipMemset(cp->d_states, 0, sizeof(GNState) * (n_pairs + 1)));
+  // (entries n_pairs ..: the body states of rig mode, one per rig of a call — a rig has at least one member —, estimate.hip estimate_rigs)
+  CREATE_CK(hipMalloc((void**) &cp->d_states, sizeof(GNState) * (n_pairs + n_pairs)));
+  CREATE_CK(hipMemset(cp->d_states, 0, sizeof(GNState) * (n_pairs + n_pairs)));
   CREATE_CK(hipMalloc((void**) &cp->d_fjobs, 2 * sizeof(FrameJob) * (size_t) cp->L * n_frames));
   CREATE_CK(hipMalloc((void**) &cp->d_job1, sizeof(PairJob) * (1 + kMaxGroups)));      // the whole job + its channel groups (wide descriptors)
   if(cp->params.descriptor == BPVO_DESC_LATCH) {
@@ -731,7 +730,7 @@ void bpvo_hip_destroy(bpvo_hip_ctx* c)
   for(auto& f : c->frames) { (void) hipFree(f.data_slab); (void) hipFree(f.tmpl_slab); }
   for(auto& w : c->ws) { (void) hipFree(w.r); (void) hipFree(w.valid); (void) hipFree(w.cand); (void) hipFree(w.med_blk); (void) hipFree(w.tapkey); (void) hipFree(w.tapcache); (void) hipFree(w.partials); }
   (void) hipFree(c->d_states); (void) hipFree(c->d_fjobs); (void) hipFree(c->d_job1); (void) hipFree(c->d_latch_off); (void) hipFree(c->d_cloud);
-  (void) hipFree(c->d_records); (void) hipFree(c->d_wtmp); (void) hipFree(c->d_rig_X);
+  (void) hipFree(c->d_records); (void) hipFree(c->d_wtmp); (void) hipFree(c->d_rig_X); (void) hipFree(c->d_rig_stage); (void) hipFree(c->d_rig_active); (void) hipHostFree(c->h_rig_stage); (void) hipHostFree(c->h_rig_active);
   pose_cov_free(c);
   (void) hipFree(c->d_count); (void) hipFree(c->d_counters); (void) hipFree(c->d_tickets); (void) hipFree(c->d_trace);
   (void) hipFree(c->st_left); (void) hipFree(c->st_right); (void) hipFree(c->st_left_pre); (void) hipFree(c->st_right_pre); (void) hipFree(c->st_disp);

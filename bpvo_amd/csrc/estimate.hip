@@ -627,14 +627,14 @@ static int rig_upload(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const in
   RIG_CK(c, ln, hipMemcpyAsync(c->d_rig_X, X, sizeof(float) * 16 * (size_t) n, hipMemcpyHostToDevice, ln->stream));
   return BPVO_OK;
 }
-static GNLaunch rig_level_launch(const bpvo_hip_ctx* c, const Lane* ln, int level, int n, int max_points)
+static GNLaunch rig_level_launch(const bpvo_hip_ctx* c, const Lane* ln, int level, int n, int max_points, int loss)
 {
   GNLaunch g;
   g.jobs = ln->d_pjobs + (size_t) level * c->n_pairs;
   g.npairs = n;
   g.max_points = max_points;
   g.C = c->C;
-  g.loss = c->params.lossFunction;
+  g.loss = loss;
   g.fast_warp = c->fast_warp;
   g.interp = c->params.interp;
   g.reference_reduction = c->reference_reduction ? 1 : 0;
@@ -655,67 +655,147 @@ static void rig_linearize_members(bpvo_hip_ctx* c, Lane* ln, const GNLaunch& g)
   { ScopedTimer t(c, KC_GN_STEP, 0.0, ln, c->profile_all); launch_gn_step(ln->stream, g, 1); }
 }
 
-int estimate_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, const float* T_init, float* T_est, bpvo_hip_stats* stats)
+
+// the staging of estimate_rigs, allocated at its first use: the table of the call's rigs, their extrinsics and initial poses in ONE pinned block
+// (one upload per estimate), the bodies' `active` words of a round
+static int rig_storage(bpvo_hip_ctx* c, Lane* ln)
+{
+  if(c->h_rig_active) return BPVO_OK;      // (the last of the allocations below)
+  const size_t NP = (size_t) c->n_pairs;
+  if(!c->d_rig_stage) RIG_CK(c, ln, hipMalloc((void**) &c->d_rig_stage, rig_stage_bytes(c)));
+  if(!c->h_rig_stage) RIG_CK(c, ln, hipHostMalloc((void**) &c->h_rig_stage, rig_stage_bytes(c)));
+  if(!c->d_rig_active) RIG_CK(c, ln, hipMalloc((void**) &c->d_rig_active, sizeof(int) * NP));
+  RIG_CK(c, ln, hipHostMalloc((void**) &c->h_rig_active, 3 * sizeof(int) * NP));
+  return BPVO_OK;
+}
+
+// R rigs of ONE loss (the loss instantiates the chain's kernels: estimate_rigs).  The members of all rigs back to back in the job tables, rig
+// after rig; body r is state n_pairs + r; one level loop, every launch of the chain shared by all rigs, one launch of the batched rig step
+// per iteration.  A rig that has finished a level idles — its body and its members inactive, skipped by every kernel — until every rig has.
+static int estimate_rigs_one_loss(bpvo_hip_ctx* c, int R, const RigProblem* rigs, int loss)
 {
   const bpvo_hip_params& p = c->params;
-  if(!T_init || !T_est) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr pose");
-  int rc = rig_check(c, n, wss, refs, curs, X, p.maxTestLevel, c->L - 1);
-  if(rc) return rc;
   (void) hipSetDevice(c->device);
   Lane* ln = &c->lanes[0];      // (the context's stream: the estimate queues behind the frame stages)
   c->frac_valid = false;
   RIG_CK(c, ln, join_pending_normalization(c, ln->stream));
-  // The loop iterates on the pose of the REFERENCE member (member 0) in its normalised twist (rig_math.h: the f32 solve wants a normalised
-  // system; a rig of one camera takes that camera's own steps): the extrinsics relative to it, its initial pose, and the body pose at the end
-  std::vector<float> X_rel((size_t) n * 16);
-  for(int i = 0; i < n; ++i) rig_relative_extrinsic(X + 16 * (size_t) i, X, &X_rel[16 * (size_t) i]);
-  std::vector<int> max_pts;
-  rc = rig_upload(c, ln, n, wss, refs, curs, X_rel.data(), max_pts);
+  int rc = rig_storage(c, ln);
   if(rc) return rc;
-  const int NP = c->n_pairs;
-  GNState* body = c->d_states + NP;
-  rig_member_pose(X, T_init, ln->h_T);
-  RIG_CK(c, ln, hipMemcpyAsync(ln->d_Tinit, ln->h_T, 16 * sizeof(float), hipMemcpyHostToDevice, ln->stream));
-  launch_set_pose(ln->stream, ln->d_pjobs + (size_t) (c->L - 1) * NP, nullptr, n);
-  // the rounds of estimate_group: kItersPerSync iterations queued per round, round r + 1 queued while the flag of round r - 1 lands; the flag is the
-  // BODY's `active` (the rig step clears the members' with it)
-  const int max_lin = std::min(std::max(p.maxIterations, 0) + 2, kMaxFunEvals);
+  const int NP = c->n_pairs, L = c->L;
+  int N = 0, max_iterations = 0;
+  for(int r = 0; r < R; ++r) { N += rigs[r].n; max_iterations = std::max(max_iterations, (rigs[r].prm ? rigs[r].prm : &p)->maxIterations); }
+  // The loop iterates on the pose of each rig's REFERENCE member (its member 0) in that member's normalised twist (rig_math.h: the f32 solve wants
+  // a normalised system; a rig of one camera takes that camera's own steps): the extrinsics relative to it, its initial pose, and the body pose at the end
+  RigEntry* tab = reinterpret_cast<RigEntry*>(c->h_rig_stage);
+  float* hX = reinterpret_cast<float*>(c->h_rig_stage + rig_stage_X_at(c));
+  float* hT = hX + 16 * (size_t) NP;
+  char* const d_stage = c->d_rig_stage;
+  const float* dX = reinterpret_cast<const float*>(d_stage + rig_stage_X_at(c));
+  const float* dT = dX + 16 * (size_t) NP;
+  GNState* bodies = c->d_states + NP;
+  const size_t table = (size_t) L * NP;
+  std::vector<int> max_pts((size_t) L, 0);
+  for(int r = 0, first = 0; r < R; first += rigs[r].n, ++r) {
+    const RigProblem& q = rigs[r];
+    for(int i = 0; i < q.n; ++i) rig_relative_extrinsic(q.X + 16 * (size_t) i, q.X, hX + 16 * (size_t) (first + i));
+    rig_member_pose(q.X, q.T_init, hT + 16 * (size_t) r);
+    tab[r] = RigEntry{first, q.n, dX + 16 * (size_t) first, bodies + r, dT + 16 * (size_t) r};
+    for(int l = 0; l < L; ++l)
+      for(int i = 0; i < q.n; ++i) {
+        PairJob& pj = ln->h_pjobs[(size_t) l * NP + first + i];
+        pj = make_pair_job(c, q.wss[i], q.refs[i], q.curs[i], l);
+        if(q.prm) pair_job_set_params(pj, *q.prm);
+        for(int k = 0; k < c->G && c->G > 1; ++k) ln->h_pjobs[(size_t) (1 + k) * table + (size_t) l * NP + first + i] = group_pair_job(c, pj, k);
+        max_pts[l] = std::max(max_pts[l], pj.n);
+      }
+  }
+  RIG_CK(c, ln, hipMemcpyAsync(ln->d_pjobs, ln->h_pjobs, sizeof(PairJob) * table * (size_t) job_tables(c), hipMemcpyHostToDevice, ln->stream));
+  RIG_CK(c, ln, hipMemcpyAsync(d_stage, c->h_rig_stage, rig_stage_bytes(c), hipMemcpyHostToDevice, ln->stream));
+  launch_set_pose(ln->stream, ln->d_pjobs + (size_t) (L - 1) * NP, nullptr, N);
+  // the rounds of estimate_group: kItersPerSync iterations queued per round, round r + 1 queued while the flags of round r - 1 land; the flags are
+  // the BODIES' `active` words (the rig step clears the members' with them), R words in one copy
+  const int max_lin = std::min(std::max(max_iterations, 0) + 2, kMaxFunEvals);
   const int kItersPerSync = 4;
   const int max_rounds = (max_lin + kItersPerSync - 1) / kItersPerSync + 2;
-  for(int l = c->L - 1; l >= p.maxTestLevel; --l) {
-    const GNLaunch g = rig_level_launch(c, ln, l, n, max_pts[l]);
-    launch_level_begin(ln->stream, g.jobs, n, g.max_points, l, 0);
-    RigStepArgs a{g.jobs, n, c->d_rig_X, body, 2, l, l == c->L - 1 ? ln->d_Tinit : nullptr, 1};
-    launch_rig_step(ln->stream, a);
-    a.mode = 0; a.T_init = nullptr;
+  for(int l = L - 1; l >= p.maxTestLevel; --l) {
+    const GNLaunch g = rig_level_launch(c, ln, l, N, max_pts[l], loss);
+    launch_level_begin(ln->stream, g.jobs, N, g.max_points, l, 0);
+    RigStepsArgs a{g.jobs, reinterpret_cast<const RigEntry*>(d_stage), R, 2, l, l == L - 1 ? 1 : 0, 1, c->d_rig_active};
+    launch_rig_steps(ln->stream, a);
+    a.mode = 0; a.with_init = 0;
     for(int round = 0; round < max_rounds; ++round) {
       for(int k = 0; k < kItersPerSync; ++k) {
         rig_linearize_members(c, ln, g);
-        launch_rig_step(ln->stream, a);
+        launch_rig_steps(ln->stream, a);
       }
       const int slot = round % 3;
-      RIG_CK(c, ln, hipMemcpyAsync(ln->h_active + 2 * slot, &body->active, sizeof(int), hipMemcpyDeviceToHost, ln->stream));
+      RIG_CK(c, ln, hipMemcpyAsync(c->h_rig_active + (size_t) slot * NP, c->d_rig_active, sizeof(int) * (size_t) R, hipMemcpyDeviceToHost, ln->stream));
       RIG_CK(c, ln, hipEventRecord(ln->round_ev[slot], ln->stream));
       if(round == 0) continue;
       const int prev = (round - 1) % 3;
       RIG_CK(c, ln, hipEventSynchronize(ln->round_ev[prev]));
-      if(ln->h_active[2 * prev] == 0) break;      // (the round just queued runs empty)
+      bool any = false;
+      for(int r = 0; r < R; ++r) any = any || c->h_rig_active[(size_t) prev * NP + r] != 0;
+      if(!any) break;      // (the round just queued runs empty)
     }
   }
-  RIG_CK(c, ln, hipMemcpyAsync(ln->h_states + NP, body, sizeof(GNState), hipMemcpyDeviceToHost, ln->stream));
+  RIG_CK(c, ln, hipMemcpyAsync(ln->h_states + NP, bodies, sizeof(GNState) * (size_t) R, hipMemcpyDeviceToHost, ln->stream));
   RIG_CK(c, ln, hipStreamSynchronize(ln->stream));
   RIG_CK(c, ln, hipGetLastError());
   resolve_events(c);
-  const GNState& st = ln->h_states[NP];
-  rig_body_pose(X, st.T_out, T_est);      // X_0^-1 T_0 X_0
-  if(stats)
-    for(int l = 0; l < c->L; ++l) stats[l] = st.stats[l];
-  for(int i = 0; i < n; ++i) {
-    Workspace& w = c->ws[wss[i]];
-    w.last_ref = refs[i]; w.last_cur = curs[i]; w.last_level = p.maxTestLevel;
-    w.has_estimate = true;
+  for(int r = 0; r < R; ++r) {
+    const RigProblem& q = rigs[r];
+    const GNState& st = ln->h_states[NP + r];
+    rig_body_pose(q.X, st.T_out, q.T_est);      // X_0^-1 T_0 X_0
+    if(q.stats)
+      for(int l = 0; l < L; ++l) q.stats[l] = st.stats[l];
+    for(int i = 0; i < q.n; ++i) {
+      Workspace& w = c->ws[q.wss[i]];
+      w.last_ref = q.refs[i]; w.last_cur = q.curs[i]; w.last_level = p.maxTestLevel;
+      w.has_estimate = true;
+    }
   }
   return BPVO_OK;
+}
+
+// Rigs with different losses in one call: one estimate per loss present, the rigs of a loss in call order (what estimate_batch does for sequences
+// with parameters of their own; everything else a rig may own travels in its members' jobs and its body's state)
+int estimate_rigs(bpvo_hip_ctx* c, int R, const RigProblem* rigs)
+{
+  const bpvo_hip_params& p = c->params;
+  if(R < 1 || !rigs) return fail(c, BPVO_ERR_INVALID_ARG, "rigs: n_rigs must be at least 1");
+  int N = 0;
+  for(int r = 0; r < R; ++r) {
+    if(!rigs[r].T_init || !rigs[r].T_est) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr pose");
+    if(int rc = rig_check(c, rigs[r].n, rigs[r].wss, rigs[r].refs, rigs[r].curs, rigs[r].X, p.maxTestLevel, c->L - 1)) return rc;
+    N += rigs[r].n;
+    for(int q = 0; q < r; ++q)
+      for(int i = 0; i < rigs[r].n; ++i)
+        for(int k = 0; k < rigs[q].n; ++k)
+          if(rigs[r].wss[i] == rigs[q].wss[k]) return fail(c, BPVO_ERR_INVALID_ARG, "rigs: a workspace appears in two rigs");
+  }
+  if(N > c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "rigs: more members than the context's workspaces");
+  auto loss_of = [&](int r) { return (rigs[r].prm ? rigs[r].prm : &p)->lossFunction; };
+  bool one_loss = true;
+  for(int r = 1; r < R && one_loss; ++r) one_loss = loss_of(r) == loss_of(0);
+  if(one_loss) return estimate_rigs_one_loss(c, R, rigs, loss_of(0));
+  std::vector<char> done((size_t) R, 0);
+  for(int r = 0; r < R; ++r) {
+    if(done[r]) continue;
+    std::vector<RigProblem> part;
+    for(int k = r; k < R; ++k)
+      if(!done[k] && loss_of(k) == loss_of(r)) { done[k] = 1; part.push_back(rigs[k]); }
+    if(int rc = estimate_rigs_one_loss(c, (int) part.size(), part.data(), loss_of(r))) return rc;
+  }
+  return BPVO_OK;
+}
+
+// one rig: the R = 1 case
+int estimate_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, const float* T_init, float* T_est, bpvo_hip_stats* stats)
+{
+  if(!T_init || !T_est) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr pose");
+  const RigProblem q{n, wss, refs, curs, X, T_init, T_est, stats, nullptr};
+  return estimate_rigs(c, 1, &q);
 }
 
 }  // namespace bpvo_hip_host
@@ -741,7 +821,7 @@ int bpvo_hip_linearize_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* re
   for(int i = 0; i < n; ++i) rig_member_pose(X + 16 * (size_t) i, T_body, ln->h_T + 16 * (size_t) i);      // the poses the members' kernels run at
   if(T_members) std::memcpy(T_members, ln->h_T, sizeof(float) * 16 * (size_t) n);
   RIG_CK(c, ln, hipMemcpyAsync(ln->d_Tinit, ln->h_T, sizeof(float) * 16 * (size_t) n, hipMemcpyHostToDevice, ln->stream));
-  const GNLaunch g = rig_level_launch(c, ln, level, n, max_pts[level]);
+  const GNLaunch g = rig_level_launch(c, ln, level, n, max_pts[level], c->params.lossFunction);
   for(int i = 0; i < n; ++i) launch_prepare_linearize(ln->stream, g.jobs + i, ln->d_Tinit + 16 * (size_t) i, reset_scale ? 1 : 0, level);
   launch_reset_tapkeys(ln->stream, g);
   rig_linearize_members(c, ln, g);
@@ -767,6 +847,23 @@ int bpvo_hip_estimate_pose_rig(bpvo_hip_ctx* c, int n, const int* wss, const int
 {
   CHECK_CTX(c);
   return estimate_rig(c, n, wss, refs, curs, X, T_init, T_est, stats);
+}
+int bpvo_hip_estimate_pose_rigs(bpvo_hip_ctx* c, int n_rigs, const int* count, const int* wss, const int* refs, const int* curs, const float* X,
+                                const float* T_init, float* T_est, bpvo_hip_stats* stats)
+{
+  CHECK_CTX(c);
+  if(n_rigs < 1 || n_rigs > c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "rigs: n_rigs must be within 1 .. the context's workspaces");
+  if(!count || !wss || !refs || !curs || !X) return fail(c, BPVO_ERR_INVALID_ARG, "rigs: nullptr counts / members / extrinsics");
+  if(!T_init || !T_est) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr pose");
+  std::vector<RigProblem> rigs((size_t) n_rigs);
+  size_t at = 0;
+  for(int r = 0; r < n_rigs; ++r) {
+    if(count[r] < 1 || count[r] > c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "rigs: every rig has 1 .. the context's workspaces members");
+    rigs[r] = RigProblem{count[r], wss + at, refs + at, curs + at, X + 16 * at, T_init + 16 * (size_t) r, T_est + 16 * (size_t) r,
+                         stats ? stats + (size_t) r * c->L : nullptr, nullptr};
+    at += (size_t) count[r];
+  }
+  return estimate_rigs(c, n_rigs, rigs.data());
 }
 
 }  // extern "C"

@@ -147,7 +147,7 @@ struct Lane {
   unsigned* h_pk_ctl = nullptr;    // pinned copy
   unsigned* d_team_ctl = nullptr;  // gn_team_ctl_words(kMaxTeams) words of the team-persistent kernel (lane 0 only)
   unsigned* h_team_ctl = nullptr;  // pinned copy of its first line (abort word)
-  GNState* h_states = nullptr;     // pinned [n_pairs]
+  GNState* h_states = nullptr;     // pinned [n_pairs + n_pairs]: the workspaces' states, then the body states of rig mode (estimate_rigs)
   std::vector<EventPair> ev_pending;
   std::vector<hipEvent_t> ev_pool;
   unsigned k6_seq = 0;             // warp_residual launches of this lane since bpvo_hip_profiling (event sampling)
@@ -220,18 +220,19 @@ struct bpvo_hip_ctx {
   unsigned* d_seq_cnt = nullptr;
   size_t* h_seq_off = nullptr;                     // pinned [seq_capacity]: pixel offsets of the frames of a mixed-size call in the packed device inputs
   size_t* d_seq_off = nullptr;
-  // Rig mode (bpvo_hip_rig_set ... bpvo_hip_add_frames_rig, vo.hip): the cameras of a rigid rig = sequences rig_seq[0 .. n) with extrinsics rig_X
-  // (camera_from_body, [n][16]) estimated as one body pose; rig_body keeps the body's T_kf and trajectory (its slot roles are unused: every member
-  // keeps its own).  A context with a rig (rig_seq not empty) serves bpvo_hip_add_frames_rig only.  d_rig_X: the extrinsics of the estimate under way.
-  std::vector<int> rig_seq;
-  std::vector<float> rig_X;
-  SeqState rig_body;
-  float* d_rig_X = nullptr;        // [n_pairs][16], allocated at its first use
+  // Rig mode (bpvo_hip_rig_set / bpvo_hip_rigs_set ... bpvo_hip_add_frames_rig(s), vo.hip): rigs[r] (RigState below) = the cameras of one rigid rig,
+  // estimated as one body pose.  A context with a rig (rigs not empty) serves bpvo_hip_add_frames_rig(s) only.
+  std::vector<RigState> rigs;
+  float* d_rig_X = nullptr;        // [n_pairs][16], allocated at its first use (bpvo_hip_linearize_rig)
+  // estimate_rigs' staging (rig_stage_bytes: the rigs' table, extrinsics, initial poses — one upload per estimate) and the bodies' `active` words
+  // of a round (device [n_pairs]; pinned [3][n_pairs], a row per round in flight); allocated at their first use
+  char* d_rig_stage = nullptr; char* h_rig_stage = nullptr;
+  int* d_rig_active = nullptr; int* h_rig_active = nullptr;
   // Pose covariance (c_api.h bpvo_hip_pose_covariances, pose_cov.hip).  Option "pose_covariance": the addFrame entry points run the pass behind
-  // the estimate their result's pose comes from and keep the record — vo_cov for bpvo_hip_add_frame, seq_cov[s] per sequence, rig_cov for the rig.
+  // the estimate their result's pose comes from and keep the record — vo_cov for bpvo_hip_add_frame, seq_cov[s] per sequence, RigState::cov per rig.
   int pose_covariance = 0;
   CovScratch cov;
-  bpvo_hip_pose_covariance vo_cov, rig_cov;
+  bpvo_hip_pose_covariance vo_cov;
   std::vector<bpvo_hip_pose_covariance> seq_cov;
   // measurement
   double points_fused = 0;     // points linearised through the fused path since the last counter reset
@@ -558,6 +559,22 @@ int estimate_batch(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, cons
 // Rig mode: members i = (workspace wss[i], template refs[i], current curs[i]) with extrinsics X [n][16] estimated as ONE body pose from T_init (the
 // coarse-to-fine loop of estimate_group on the four-kernel chain, kernels_gn_rig.hip's step in the place of gn_step); T_est and stats [L] are the body's
 int estimate_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, const float* T_init, float* T_est, bpvo_hip_stats* stats);
+// Several rigs in one estimate (estimate_rig is its R = 1 case): rig r with members, extrinsics and poses as estimate_rig takes them and its own
+// parameters (prm: the Gauss-Newton limits, tolerances and loss of its jobs and its body; null: the context's).  No workspace in two rigs, at most
+// n_pairs members in all.  Every rig's result is what estimate_rig gives it alone, bit for bit.
+struct RigProblem {
+  int n;
+  const int* wss; const int* refs; const int* curs;
+  const float* X;            // [n][16]
+  const float* T_init;       // [16]
+  float* T_est;              // [16]
+  bpvo_hip_stats* stats;     // [L] or null
+  const bpvo_hip_params* prm;
+};
+int estimate_rigs(bpvo_hip_ctx* c, int R, const RigProblem* rigs);
+// the pinned / device staging block of estimate_rigs: [n_pairs] RigEntry, then [n_pairs][16] extrinsics, then [n_pairs][16] initial poses
+inline size_t rig_stage_X_at(const bpvo_hip_ctx* c) { return (sizeof(bpvo_hip::RigEntry) * (size_t) c->n_pairs + 63) / 64 * 64; }
+inline size_t rig_stage_bytes(const bpvo_hip_ctx* c) { return rig_stage_X_at(c) + 2 * sizeof(float) * 16 * (size_t) c->n_pairs; }
 void detile_to_channel_major(const float* src, int n, int C, int E, int V, float* out);
 size_t tiled_floats(int n, int floats_per_point);
 int refresh_counters(bpvo_hip_ctx* c);

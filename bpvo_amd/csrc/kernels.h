@@ -229,6 +229,24 @@ struct RigStepArgs {
   int reference;
 };
 void launch_rig_step(hipStream_t s, const RigStepArgs& a);
+// Several rigs in one launch (estimate_rigs): workgroup r takes the step of rig r of a device table — RigStepArgs' arithmetic per rig, a rig whose
+// body is no longer active left untouched.  The members of all rigs lie back to back in the level's job row, rig r at [first, first + n).
+struct RigEntry {
+  int first, n;            // the rig's members in the level's job row
+  const float* X;          // device [n][16]: the rig's extrinsics (RigStepArgs::X)
+  GNState* body;           // the rig's body state
+  const float* T_init;     // device [16]: the pose its estimate starts from (mode 2 with with_init)
+};
+struct RigStepsArgs {
+  const PairJob* jobs;     // the level's job row
+  const RigEntry* rigs;    // device [n_rigs]
+  int n_rigs;
+  int mode, level;         // RigStepArgs'
+  int with_init;           // mode 2: the start of the estimate as well (every rig's own T_init)
+  int reference;           // RigStepArgs'
+  int* active_out;         // device [n_rigs]: every body's `active` after the step (0 for a rig that was left alone)
+};
+void launch_rig_steps(hipStream_t s, const RigStepsArgs& b);
 // Pose covariance (kernels_gn_cov.hip; c_api.h bpvo_hip_pose_covariances).  A pass serves n_records records of `members` members each (a camera:
 // one member; a rig: one record of all its members); entry r * members + p of `jobs` / `members_tab` is member p of record r.  The jobs are COPIES
 // of the workspaces' jobs whose r, valid, partials, cnt and st point into the pass's own scratch (no tap cache, no median buffers: the scratch

@@ -41,14 +41,13 @@ __device__ __forceinline__ void rig_write_member_poses(const RigStepArgs& a, con
 
 // mode 0: the full step (solve, update, convergence: gn_logic); 1: linearise only (the joint H, G, f, valid count into the body's state);
 // 2: the start of a level (PoseEstimatorBase::reset of the body, the members' poses from the body's) — with T_init != null the start of the
-// estimate as well (set_pose of the body)
-__global__ __launch_bounds__(64) void rig_step_kernel(RigStepArgs a)
+// estimate as well (set_pose of the body).  One wavefront, one rig: a.jobs is the rig's first member.  The ONE step of both kernels below.
+__device__ __forceinline__ int rig_step_wave(RigStepLds& s, const RigStepArgs& a)      // returns the body's `active` after the step
 {
   constexpr int kWords = (int) (sizeof(GNState) / sizeof(uint32_t));
-  __shared__ RigStepLds s;
   const int lane = threadIdx.x;
   GNState* gst = a.body;
-  if(a.mode == 0 && !gst->active) return;      // (the level is over: the host's pipelined rounds run out empty)
+  if(a.mode == 0 && !gst->active) return 0;    // (the level is over: the host's pipelined rounds run out empty)
   for(int i = lane; i < kWords; i += 64) s.step.state[i] = reinterpret_cast<const uint32_t*>(gst)[i];
   // the twist the step is taken in: the plain body twist (the path nrm[4] != 0 selects in gn_update_pose), or — a.reference, the estimate
   // loops — the reference member's normalised twist, the state's T then being THAT member's pose and a.X the extrinsics relative to it
@@ -76,7 +75,7 @@ __global__ __launch_bounds__(64) void rig_step_kernel(RigStepArgs a)
     wave_lds_sync();
     rig_write_member_poses(a, st->T, st->T_out, true, lane);
     for(int i = lane; i < kWords; i += 64) reinterpret_cast<uint32_t*>(gst)[i] = s.step.state[i];
-    return;
+    return st->active;
   }
 
   // the joint system: lane a * 6 + b < 36 holds entry (a, b) of H, lanes 36 .. 41 the entries of G, lane 42 the squared norm, lane 43 the valid count
@@ -124,12 +123,37 @@ __global__ __launch_bounds__(64) void rig_step_kernel(RigStepArgs a)
     for(int p = 64 + lane; done && p < a.n; p += 64) a.jobs[p].st->active = 0;
   }
   for(int i = lane; i < kWords; i += 64) reinterpret_cast<uint32_t*>(gst)[i] = s.step.state[i];
+  return st->active;
+}
+
+__global__ __launch_bounds__(64) void rig_step_kernel(RigStepArgs a)
+{
+  __shared__ RigStepLds s;
+  (void) rig_step_wave(s, a);
+}
+
+// Several rigs in one launch: workgroup r (one wavefront) takes the step of rig r of the table — its members jobs[first .. first + n) of the
+// level's row, its extrinsics, its body state, its initial pose — with exactly rig_step_kernel's arithmetic.  A rig whose body is no longer
+// active leaves at once (rig_step_wave's first test): nothing of it is touched while the other rigs of the launch iterate.  active_out[r]: the
+// body's `active` after the step, the words the host reads once per round.
+__global__ __launch_bounds__(64) void rig_steps_kernel(RigStepsArgs b)
+{
+  __shared__ RigStepLds s;
+  const RigEntry e = b.rigs[blockIdx.x];
+  const RigStepArgs a{b.jobs + e.first, e.n, e.X, e.body, b.mode, b.level, (b.mode == 2 && b.with_init) ? e.T_init : nullptr, b.reference};
+  const int active = rig_step_wave(s, a);
+  if(threadIdx.x == 0) b.active_out[blockIdx.x] = active;
 }
 
 void launch_rig_step(hipStream_t s, const RigStepArgs& a)
 {
   if(a.n <= 0) return;
   hipLaunchKernelGGL(rig_step_kernel, dim3(1), dim3(64), 0, s, a);
+}
+void launch_rig_steps(hipStream_t s, const RigStepsArgs& b)
+{
+  if(b.n_rigs <= 0) return;
+  hipLaunchKernelGGL(rig_steps_kernel, dim3(b.n_rigs), dim3(64), 0, s, b);
 }
 
 }  // namespace bpvo_hip

@@ -229,7 +229,17 @@ int bpvo_hip_rig_pose_covariance(bpvo_hip_ctx* c, bpvo_hip_pose_covariance* out)
 {
   CHECK_CTX(c);
   if(!out) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr record");
-  *out = c->rig_cov;
+  if(c->rigs.size() > 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares several rigs (bpvo_hip_rigs_set): call bpvo_hip_rigs_pose_covariance");
+  if(c->rigs.empty()) pose_cov_none(out);
+  else *out = c->rigs[0].cov;
+  return BPVO_OK;
+}
+int bpvo_hip_rigs_pose_covariance(bpvo_hip_ctx* c, int rig, bpvo_hip_pose_covariance* out)
+{
+  CHECK_CTX(c);
+  if(!out) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr record");
+  if(rig < 0 || (size_t) rig >= c->rigs.size()) return fail(c, BPVO_ERR_INVALID_ARG, "no such rig (bpvo_hip_rigs_set declares rigs 0 .. n_rigs-1)");
+  *out = c->rigs[(size_t) rig].cov;
   return BPVO_OK;
 }
 

@@ -328,7 +328,7 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
 {
   if(!ret) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
   if(c->n_frames < 3) return fail(c, BPVO_ERR_INVALID_ARG, "add_frame needs a ctx with n_frames >= 3");
-  if(!c->rig_seq.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares a rig (bpvo_hip_rig_set): it serves bpvo_hip_add_frames_rig only");
+  if(!c->rigs.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares a rig (bpvo_hip_rig_set): it serves bpvo_hip_add_frames_rig only");
   if(c->vo_mode == 2) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frames: a context serves either add_frame or add_frames");
   c->vo_mode = 1;
   (void) hipSetDevice(c->device);
@@ -572,7 +572,7 @@ extern "C" {
 static int add_frames_check(bpvo_hip_ctx* c, int n, const int* seq, const void* images, const void* second, const char* what_null, bpvo_hip_result* results,
                             std::vector<int>& ids)
 {
-  if(!c->rig_seq.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares a rig (bpvo_hip_rig_set): it serves bpvo_hip_add_frames_rig only");
+  if(!c->rigs.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares a rig (bpvo_hip_rig_set): it serves bpvo_hip_add_frames_rig only");
   if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a context serves either add_frame or add_frames");
   const int S = seq_capacity(c);
   if(S < 1) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames needs a ctx with n_frames >= 3 and n_pairs >= 1");
@@ -789,23 +789,36 @@ int bpvo_hip_add_frames(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* i
   return add_frames_run(c, n, ids, images, disparities, on_device != 0, results);
 }
 // ---- rig mode: the cameras of a rigid rig as ONE body (c_api.h; rig_math.h states the maps) ------------------------------------------------
-// Member p of the rig is sequence rig_seq[p] — its frame slots, its workspace, its camera — with extrinsic rig_X[p] (camera_from_body).  A call
-// runs the phases of add_frames_run once for the rig: one data stage over the members' frames, ONE estimate of the body pose from all members'
-// residuals (estimate_rig), one key-frame decision on the body pose with the fraction of good points pooled over the members, and every
-// member the same transition (vo_state.h: vo_rig_*).  The body keeps T_kf and the trajectory.
-int bpvo_hip_rig_set(bpvo_hip_ctx* c, int n, const int* seq, const float* X)
+// A context declares one rig (bpvo_hip_rig_set) or several over disjoint sets of its sequences (bpvo_hip_rigs_set): bpvo_hip_ctx::rigs.  Member p
+// of a rig is sequence seq[p] — its frame slots, its workspace, its camera — with extrinsic X[p] (camera_from_body).  A call runs the phases of
+// add_frames_run once for ALL the rigs it names: one data stage over every member's frame, ONE estimate of the body poses from all members'
+// residuals (estimate_rigs), one count of good points, per rig one key-frame decision on its body pose with the fraction pooled over its members
+// and its own thresholds, every member of a rig the same transition (vo_state.h: vo_rig_*), one estimate against the new key frames.  A body
+// keeps T_kf, the trajectory and the rig's parameters.  The one-rig entry points are the calls of the plural ones on rig 0.
+static void rig_param_target(bpvo_hip_ctx* c, const RigState& g)      // the members' frame jobs read the rig's selection thresholds
 {
-  CHECK_CTX(c);
+  for(int s : g.seq)
+    for(int k = 0; k < 3; ++k) c->frames[3 * s + k].seq_params = g.body.own_params ? &g.body.params : nullptr;
+}
+static int rigs_set_impl(bpvo_hip_ctx* c, int n_rigs, const int* count, const int* seq, const float* X, const char* who)
+{
+  const std::string w(who);
   if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a rig's members are sequences of bpvo_hip_add_frames' kind");
   const int S = seq_capacity(c);
-  if(n < 1 || n > S) return fail(c, BPVO_ERR_INVALID_ARG, "rig_set: n must be within 1 .. the sequence capacity");
-  if(!X) return fail(c, BPVO_ERR_INVALID_ARG, "rig_set: nullptr extrinsics");
+  if(n_rigs < 1 || n_rigs > S) return fail(c, BPVO_ERR_INVALID_ARG, (w + ": n_rigs must be within 1 .. the sequence capacity").c_str());
+  if(!count) return fail(c, BPVO_ERR_INVALID_ARG, (w + ": nullptr member counts").c_str());
+  int n = 0;
+  for(int r = 0; r < n_rigs; ++r) {
+    if(count[r] < 1 || count[r] > S - n) return fail(c, BPVO_ERR_INVALID_ARG, (w + ": n must be within 1 .. the sequence capacity").c_str());
+    n += count[r];
+  }
+  if(!X) return fail(c, BPVO_ERR_INVALID_ARG, (w + ": nullptr extrinsics").c_str());
   std::vector<int> ids((size_t) n);
   std::vector<char> seen((size_t) S, 0);
   for(int i = 0; i < n; ++i) {
     ids[i] = seq ? seq[i] : i;
     if(ids[i] < 0 || ids[i] >= S) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "no such sequence");
-    if(seen[ids[i]]) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "appears twice in the rig");
+    if(seen[ids[i]]) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], n_rigs > 1 ? "appears twice in the rigs (a sequence belongs to one rig, once)" : "appears twice in the rig");
     seen[ids[i]] = 1;
   }
   for(int i = 0; i < n; ++i)
@@ -813,170 +826,342 @@ int bpvo_hip_rig_set(bpvo_hip_ctx* c, int n, const int* seq, const float* X)
       return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "extrinsic is not a rigid transform (finite, last row 0 0 0 1, R^T R = I within 1e-4)");
   for(int i = 0; i < n; ++i)
     if(int rc = seq_is_fresh(c, ids[i], "rig membership changes")) return rc;
-  for(int s : c->rig_seq)      // (a rig declared before: its members leave it only fresh, too)
-    if(int rc = seq_is_fresh(c, s, "rig membership changes")) return rc;
+  for(const RigState& g : c->rigs)      // (rigs declared before: their members leave them only fresh, too)
+    for(int s : g.seq)
+      if(int rc = seq_is_fresh(c, s, "rig membership changes")) return rc;
   for(int i = 0; i < n && !c->seqs.empty(); ++i)
-    if(c->seqs[ids[i]].own_params) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "has parameters of its own: a rig runs the context's parameters");
+    if(c->seqs[ids[i]].own_params) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "has parameters of its own: a rig runs its own (bpvo_hip_rigs_set_params) or the context's parameters");
   seq_states(c);
-  c->rig_seq = ids;
-  c->rig_X.assign(X, X + 16 * (size_t) n);
-  vo_reset(c->rig_body, 0);
-  c->rig_body.params = c->params;
+  for(RigState& g : c->rigs) { g.body.own_params = false; rig_param_target(c, g); }
+  c->rigs.assign((size_t) n_rigs, RigState());
+  for(int r = 0, at = 0; r < n_rigs; at += count[r], ++r) {
+    RigState& g = c->rigs[r];
+    g.seq.assign(ids.begin() + at, ids.begin() + at + count[r]);
+    g.X.assign(X + 16 * (size_t) at, X + 16 * (size_t) (at + count[r]));
+    vo_reset(g.body, 0);
+    g.body.params = c->params;
+    g.body.own_params = false;
+    pose_cov_none(&g.cov);
+  }
   c->vo_mode = 2;
   return BPVO_OK;
 }
-int bpvo_hip_rig_get(const bpvo_hip_ctx* c, int* n, int* seq, float* X)
+// the one-rig entry points on a context of several rigs
+static int rig_is_singular(bpvo_hip_ctx* c, const char* plural)
 {
-  if(!c || !n) return BPVO_ERR_INVALID_ARG;
-  *n = (int) c->rig_seq.size();
-  if(seq) std::copy(c->rig_seq.begin(), c->rig_seq.end(), seq);
-  if(X) std::copy(c->rig_X.begin(), c->rig_X.end(), X);
+  if(c->rigs.size() > 1) return fail(c, BPVO_ERR_INVALID_ARG, (std::string("this context declares several rigs (bpvo_hip_rigs_set): call ") + plural).c_str());
   return BPVO_OK;
 }
+int bpvo_hip_rig_set(bpvo_hip_ctx* c, int n, const int* seq, const float* X)
+{
+  CHECK_CTX(c);
+  return rigs_set_impl(c, 1, &n, seq, X, "rig_set");
+}
+int bpvo_hip_rigs_set(bpvo_hip_ctx* c, int n_rigs, const int* count, const int* seq, const float* X)
+{
+  CHECK_CTX(c);
+  return rigs_set_impl(c, n_rigs, count, seq, X, "rigs_set");
+}
+int bpvo_hip_rig_get(const bpvo_hip_ctx* c, int* n, int* seq, float* X)
+{
+  if(!c || !n || c->rigs.size() > 1) return BPVO_ERR_INVALID_ARG;
+  *n = c->rigs.empty() ? 0 : (int) c->rigs[0].seq.size();
+  if(seq && !c->rigs.empty()) std::copy(c->rigs[0].seq.begin(), c->rigs[0].seq.end(), seq);
+  if(X && !c->rigs.empty()) std::copy(c->rigs[0].X.begin(), c->rigs[0].X.end(), X);
+  return BPVO_OK;
+}
+int bpvo_hip_rigs_get(const bpvo_hip_ctx* c, int* n_rigs, int* count, int* seq, float* X)
+{
+  if(!c || !n_rigs) return BPVO_ERR_INVALID_ARG;
+  *n_rigs = (int) c->rigs.size();
+  size_t at = 0;
+  for(size_t r = 0; r < c->rigs.size(); ++r) {
+    const RigState& g = c->rigs[r];
+    if(count) count[r] = (int) g.seq.size();
+    if(seq) std::copy(g.seq.begin(), g.seq.end(), seq + at);
+    if(X) std::copy(g.X.begin(), g.X.end(), X + 16 * at);
+    at += g.seq.size();
+  }
+  return BPVO_OK;
+}
+#define CHECK_RIG(c, rig) do { if((rig) < 0 || (size_t) (rig) >= (c)->rigs.size()) return fail((c), BPVO_ERR_INVALID_ARG, ("rig " + std::to_string(rig) + ": no such rig (bpvo_hip_rigs_set declares rigs 0 .. n_rigs-1)").c_str()); } while(0)
 int bpvo_hip_rig_trajectory_size(bpvo_hip_ctx* c, int* n)
 {
   CHECK_CTX(c);
   if(!n) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr count");
-  *n = c->rig_seq.empty() ? 0 : vo_trajectory_size(&c->rig_body);
+  if(int rc = rig_is_singular(c, "bpvo_hip_rigs_trajectory_size")) return rc;
+  *n = c->rigs.empty() ? 0 : vo_trajectory_size(&c->rigs[0].body);
   return BPVO_OK;
 }
 int bpvo_hip_rig_get_trajectory(bpvo_hip_ctx* c, float* poses)
 {
   CHECK_CTX(c);
-  if(c->rig_seq.empty()) return BPVO_OK;
-  if(!poses && vo_trajectory_size(&c->rig_body) > 0) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr poses");
-  vo_get_trajectory(&c->rig_body, poses);
+  if(int rc = rig_is_singular(c, "bpvo_hip_rigs_get_trajectory")) return rc;
+  if(c->rigs.empty()) return BPVO_OK;
+  if(!poses && vo_trajectory_size(&c->rigs[0].body) > 0) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr poses");
+  vo_get_trajectory(&c->rigs[0].body, poses);
   return BPVO_OK;
 }
-int bpvo_hip_add_frames_rig(bpvo_hip_ctx* c, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* result)
+int bpvo_hip_rigs_trajectory_size(bpvo_hip_ctx* c, int rig, int* n)
 {
-  CHECK_CTX(c);
-  // 1. every check before any state changes
-  const int n = (int) c->rig_seq.size();
-  if(n < 1) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames_rig: the context declares no rig (bpvo_hip_rig_set)");
+  CHECK_CTX(c); CHECK_RIG(c, rig);
+  if(!n) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr count");
+  *n = vo_trajectory_size(&c->rigs[rig].body);
+  return BPVO_OK;
+}
+int bpvo_hip_rigs_get_trajectory(bpvo_hip_ctx* c, int rig, float* poses)
+{
+  CHECK_CTX(c); CHECK_RIG(c, rig);
+  if(!poses && vo_trajectory_size(&c->rigs[rig].body) > 0) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr poses");
+  vo_get_trajectory(&c->rigs[rig].body, poses);
+  return BPVO_OK;
+}
+
+// 1. every check of a call before any state changes; ids: the rigs it advances
+static int add_frames_rigs_check(bpvo_hip_ctx* c, int n, const int* rigs, const uint8_t* images, const float* disparities, bpvo_hip_result* results,
+                                 std::vector<int>& ids)
+{
+  const int R = (int) c->rigs.size();
+  if(n < 1 || n > R) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames_rigs: n must be within 1 .. the declared rigs");
   if(!images || !disparities) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image/disparity");   // bpvo/vo.cc:68-69
-  if(!result) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
+  if(!results) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
+  ids.assign((size_t) n, 0);
+  std::vector<char> seen((size_t) R, 0);
+  for(int i = 0; i < n; ++i) {
+    ids[i] = rigs ? rigs[i] : i;
+    CHECK_RIG(c, ids[i]);
+    if(seen[ids[i]]) return fail(c, BPVO_ERR_INVALID_ARG, ("rig " + std::to_string(ids[i]) + ": appears twice in one call").c_str());
+    seen[ids[i]] = 1;
+  }
+  const int L = c->L, lvl = c->params.maxTestLevel;
+  for(int i = 0; i < n; ++i)
+    for(int s : c->rigs[ids[i]].seq)
+      if(c->seqs[s].own_params) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "has parameters of its own: a rig runs its own (bpvo_hip_rigs_set_params) or the context's parameters");
+  if(c->dspace) return fail(c, BPVO_ERR_UNSUPPORTED, "rig mode does not serve BPVO_WARP_DISPARITY_SPACE_F32");
+  for(int i = 0; i < n; ++i) {
+    const RigState& g = c->rigs[ids[i]];
+    if(!c->frames[c->seqs[g.seq[0]].ref].has_template) continue;      // (its first frame)
+    for(int s : g.seq) {
+      const FrameSlot& ref = c->frames[c->seqs[s].ref];
+      for(int l = lvl; l < L; ++l)      // template_data.cc:177 (check_template_not_empty)
+        if(!ref.has_template || ref.n_host[l] <= 0)
+          return seq_fail(c, BPVO_ERR_NO_TEMPLATE, s, "the key frame's template is empty (you should call setData before calling computeResiduals)");
+    }
+  }
+  return BPVO_OK;
+}
+// entries of the call `which` (indices into ids) estimated in ONE estimate_rigs, each from T_init[k]; the poses to T_out[k], the statistics into the results
+static int rigs_estimate(bpvo_hip_ctx* c, const std::vector<int>& ids, const std::vector<int>& which, const std::vector<M44>& T_init, std::vector<M44>& T_out,
+                         bpvo_hip_result* results)
+{
+  const int m = (int) which.size();
+  std::vector<RigProblem> pr((size_t) m);
+  std::vector<std::vector<int>> refs((size_t) m), curs((size_t) m);
+  T_out.assign((size_t) m, m44_identity());
+  for(int k = 0; k < m; ++k) {
+    RigState& g = c->rigs[ids[which[k]]];
+    for(int s : g.seq) { refs[k].push_back(c->seqs[s].ref); curs[k].push_back(c->seqs[s].cur); }
+    pr[k] = RigProblem{(int) g.seq.size(), g.seq.data(), refs[k].data(), curs[k].data(), g.X.data(), T_init[k].m, T_out[k].m,
+                       results[which[k]].optimizerStatistics, g.body.own_params ? &g.body.params : nullptr};
+  }
+  return estimate_rigs(c, m, pr.data());
+}
+// option "pose_covariance": the body poses' records, from the members' states on the device — the existing one-record pass, rig by rig (its
+// launch takes ONE set of extrinsics for all its records: DESIGN.md section 5)
+static int rigs_covariance(bpvo_hip_ctx* c, const std::vector<int>& ids, const std::vector<int>& which)
+{
+  for(int e : which) {
+    RigState& g = c->rigs[ids[e]];
+    const int n = (int) g.seq.size();
+    std::vector<int> refs, curs;
+    for(int s : g.seq) { refs.push_back(c->seqs[s].ref); curs.push_back(c->seqs[s].cur); }
+    std::vector<const bpvo_hip_params*> prms((size_t) n, &g.body.params);
+    const int rc = pose_cov_pass(c, 1, n, g.seq.data(), refs.data(), curs.data(), g.X.data(), c->params.maxTestLevel, nullptr, nullptr,
+                                 g.body.own_params ? prms.data() : nullptr, &g.cov);
+    if(rc) return rc;
+  }
+  return BPVO_OK;
+}
+static int add_frames_rigs_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, const uint8_t* images, const float* disparities, bool on_device,
+                               bpvo_hip_result* results)
+{
   const bpvo_hip_params& p = c->params;
   const int L = c->L, lvl = p.maxTestLevel;
-  const std::vector<int>& ids = c->rig_seq;
-  const float* X = c->rig_X.data();
-  std::vector<SeqState*> members((size_t) n);
-  for(int i = 0; i < n; ++i) {
-    members[i] = &c->seqs[ids[i]];
-    if(members[i]->own_params) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "has parameters of its own: a rig runs the context's parameters");
-  }
-  const bool first = !c->frames[members[0]->ref].has_template;
-  if(c->dspace) return fail(c, BPVO_ERR_UNSUPPORTED, "rig mode does not serve BPVO_WARP_DISPARITY_SPACE_F32");
-  for(int i = 0; i < n && !first; ++i) {
-    const FrameSlot& ref = c->frames[members[i]->ref];
-    for(int l = lvl; l < L; ++l)      // template_data.cc:177 (check_template_not_empty)
-      if(!ref.has_template || ref.n_host[l] <= 0)
-        return seq_fail(c, BPVO_ERR_NO_TEMPLATE, ids[i], "the key frame's template is empty (you should call setData before calling computeResiduals)");
-  }
   (void) hipSetDevice(c->device);
   int rc = seq_storage(c);
   if(rc) return rc;
-  SeqState& body = c->rig_body;
-  vo_begin_frame(body, L, result);
-  pose_cov_none(&c->rig_cov);
-  for(int i = 0; i < n; ++i) { bpvo_hip_result own; vo_begin_frame(*members[i], L, &own); }
+  auto rig = [&](int i) -> RigState& { return c->rigs[ids[i]]; };
+  auto members_of = [&](int i) { std::vector<SeqState*> m; for(int s : rig(i).seq) m.push_back(&c->seqs[s]); return m; };
+  for(int i = 0; i < n; ++i) {
+    rig_param_target(c, rig(i));
+    vo_begin_frame(rig(i).body, L, results + i);
+    pose_cov_none(&rig(i).cov);
+    for(int s : rig(i).seq) { bpvo_hip_result own; vo_begin_frame(c->seqs[s], L, &own); }
+  }
   auto drain = [&](int code) { (void) hipStreamSynchronize(c->stream); return code; };
   auto template_stage = [&](const int* sl, int count, const size_t*, const FrameRun& fr) { return frames_set_template_slots(c, sl, count, fr); };
 
-  // 2. setData of every member: one data stage (frame i: its camera's pixels, the frames back to back in member order)
-  std::vector<int> slots((size_t) n);
-  std::vector<size_t> offsets((size_t) n);
+  // 2. setData of every member of every rig: one data stage (its camera's pixels each, the frames back to back rig after rig, in member order)
+  std::vector<int> slots;
+  std::vector<size_t> offsets;
   size_t at = 0;
-  for(int i = 0; i < n; ++i) {
-    slots[i] = members[i]->cur;
-    offsets[i] = at;
-    at += slot_geom(c, c->frames[slots[i]], 0).npix;
-  }
+  for(int i = 0; i < n; ++i)
+    for(int s : rig(i).seq) {
+      slots.push_back(c->seqs[s].cur);
+      offsets.push_back(at);
+      at += slot_geom(c, c->frames[slots.back()], 0).npix;
+    }
   rc = for_each_size(c, slots, &offsets, [&](const int* sl, int count, const size_t* off, const FrameRun& fr) {
-    return frames_set_data_slots(c, sl, count, images, disparities, on_device != 0, fr, 0, off);
+    return frames_set_data_slots(c, sl, count, images, disparities, on_device, fr, 0, off);
   });
   if(rc) return drain(rc);
 
-  // 3. the first frame: every member's template
-  if(first) {
-    for(int i = 0; i < n; ++i) slots[i] = vo_first_frame(*members[i]);
+  // 3. the rigs at their first frame: every member's template in one stage
+  std::vector<int> est;      // entries of the call that estimate
+  slots.clear();
+  for(int i = 0; i < n; ++i) {
+    if(c->frames[c->seqs[rig(i).seq[0]].ref].has_template) { est.push_back(i); continue; }
+    for(int s : rig(i).seq) slots.push_back(vo_first_frame(c->seqs[s]));
+  }
+  if(!slots.empty()) {
     rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
-    vo_rig_first_frame_done(body, members.data(), n, result);
-    return BPVO_OK;
+    for(int i = 0; i < n; ++i) {
+      if(std::find(est.begin(), est.end(), i) != est.end()) continue;
+      std::vector<SeqState*> mem = members_of(i);
+      vo_rig_first_frame_done(rig(i).body, mem.data(), (int) mem.size(), results + i);
+    }
   }
+  const int m = (int) est.size();
+  if(m == 0) return BPVO_OK;
 
-  // 4. the body pose from every member's residuals, from the body's T_kf
-  std::vector<int> wss(ids), refs((size_t) n), curs((size_t) n);
-  for(int i = 0; i < n; ++i) { refs[i] = members[i]->ref; curs[i] = members[i]->cur; }
-  M44 T_est, T_again;
-  rc = estimate_rig(c, n, wss.data(), refs.data(), curs.data(), X, body.T_kf.m, T_est.m, result->optimizerStatistics);
+  // 4. the body poses from every member's residuals, each from its body's T_kf: one estimate
+  std::vector<M44> T_init((size_t) m), T_est, T_again;
+  for(int k = 0; k < m; ++k) T_init[k] = rig(est[k]).body.T_kf;
+  rc = rigs_estimate(c, ids, est, T_init, T_est, results);
   if(rc) return drain(rc);
-  // option "pose_covariance": the body pose's, from the members' states on the device (again behind a re-estimate)
   if(c->pose_covariance) {
-    rc = pose_cov_pass(c, 1, n, wss.data(), refs.data(), curs.data(), X, lvl, nullptr, nullptr, nullptr, &c->rig_cov);
+    rc = rigs_covariance(c, ids, est);
     if(rc) return rc;
   }
 
-  // 5. ONE key-frame decision: the body's motion, then the fraction of good points pooled over the members (one count launch)
+  // 5. one key-frame decision per rig: the body's motion, then the fraction of good points pooled over its members (one count launch for all)
+  bool own = false;
+  std::vector<int> first((size_t) m + 1, 0), n_points;
   int max_n = 0;
-  std::vector<int> n_points((size_t) n);
-  for(int i = 0; i < n; ++i) {
-    c->h_seq_jobs[i] = make_pair_job(c, wss[i], refs[i], curs[i], lvl);
-    n_points[i] = c->h_seq_jobs[i].n;
-    max_n = std::max(max_n, n_points[i]);
+  for(int k = 0; k < m; ++k) {
+    const RigState& g = rig(est[k]);
+    own = own || g.body.own_params;
+    first[k + 1] = first[k] + (int) g.seq.size();
   }
-  HIP_CK(c, hipMemcpyAsync(c->d_seq_jobs, c->h_seq_jobs, sizeof(PairJob) * (size_t) n, hipMemcpyHostToDevice, c->stream));
-  HIP_CK(c, hipMemsetAsync(c->d_seq_cnt, 0, sizeof(unsigned) * (size_t) n, c->stream));
-  launch_count_good_batch(c->stream, c->d_seq_jobs, n, max_n, c->C, p.lossFunction, p.goodPointThreshold, c->d_seq_cnt);
-  HIP_CK(c, hipMemcpyAsync(c->h_seq_cnt, c->d_seq_cnt, sizeof(unsigned) * (size_t) n, hipMemcpyDeviceToHost, c->stream));
+  for(int k = 0; k < m; ++k) {
+    const RigState& g = rig(est[k]);
+    for(size_t i = 0; i < g.seq.size(); ++i) {
+      const SeqState& q = c->seqs[g.seq[i]];
+      PairJob& pj = c->h_seq_jobs[first[k] + (int) i];
+      pj = make_pair_job(c, g.seq[i], q.ref, q.cur, lvl);
+      if(own) pair_job_set_params(pj, g.body.params);
+      n_points.push_back(pj.n);
+      max_n = std::max(max_n, pj.n);
+    }
+  }
+  const int M = first[m];
+  HIP_CK(c, hipMemcpyAsync(c->d_seq_jobs, c->h_seq_jobs, sizeof(PairJob) * (size_t) M, hipMemcpyHostToDevice, c->stream));
+  HIP_CK(c, hipMemsetAsync(c->d_seq_cnt, 0, sizeof(unsigned) * (size_t) M, c->stream));
+  if(own) launch_count_good_jobs(c->stream, c->d_seq_jobs, M, max_n, c->C, c->d_seq_cnt);      // (each rig's loss and threshold, from its members' jobs)
+  else launch_count_good_batch(c->stream, c->d_seq_jobs, M, max_n, c->C, p.lossFunction, p.goodPointThreshold, c->d_seq_cnt);
+  HIP_CK(c, hipMemcpyAsync(c->h_seq_cnt, c->d_seq_cnt, sizeof(unsigned) * (size_t) M, hipMemcpyDeviceToHost, c->stream));
   HIP_CK(c, hipStreamSynchronize(c->stream));
   HIP_CK(c, hipGetLastError());
-  bool again = false;
-  if(vo_decide(p, T_est, vo_rig_fraction_good(c->h_seq_cnt, n_points.data(), n, c->C), result)) {
-    // 6. the key frame: every member's point cloud from its old key frame and its last linearisation, the new templates, the estimate against them
+  std::vector<int> kf;       // entries of est that key-frame
+  for(int k = 0; k < m; ++k) {
+    const RigState& g = rig(est[k]);
+    const float frac = vo_rig_fraction_good(c->h_seq_cnt + first[k], n_points.data() + first[k], (int) g.seq.size(), c->C);
+    if(vo_decide(g.body.params, T_est[k], frac, results + est[k])) kf.push_back(k);
+  }
+
+  // 6. the key frames: every member's point cloud from its old key frame and its last linearisation (one launch), the new templates (one stage),
+  // then ONE estimate against them of the rigs that had a previous frame
+  std::vector<int> re;       // entries of est that estimate again
+  if(!kf.empty()) {
     const size_t cap = (size_t) c->geom[lvl].cap;
-    std::vector<size_t> cloud_points((size_t) n);
-    int max_c = 0;
-    for(int i = 0; i < n; ++i) {
-      if((size_t) n_points[i] > cap) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "size mismatch");
-      const FrameSlot& kfr = c->frames[refs[i]];
-      CloudJob& cj = c->h_cloud_jobs[i];
-      cj.job = c->d_seq_jobs + i; cj.img = kfr.img[0]; cj.out_offset = (size_t) ids[i] * cap;
-      std::memcpy(cj.K, slot_geom(c, kfr, lvl).K, sizeof(cj.K));
-      cj.rows = slot_geom(c, kfr, 0).rows; cj.cols = slot_geom(c, kfr, 0).cols;
-      cj.loss = p.lossFunction;
-      cloud_points[i] = (size_t) n_points[i];
-      max_c = std::max(max_c, n_points[i]);
+    int max_c = 0, nj = 0;
+    for(int k : kf)
+      for(int j = first[k]; j < first[k + 1]; ++j)
+        if((size_t) n_points[j] > cap) return seq_fail(c, BPVO_ERR_INVALID_ARG, rig(est[k]).seq[j - first[k]], "size mismatch");
+    for(int k : kf) {
+      const RigState& g = rig(est[k]);
+      for(int j = first[k]; j < first[k + 1]; ++j, ++nj) {
+        const int s = g.seq[j - first[k]];
+        const FrameSlot& kfr = c->frames[c->seqs[s].ref];
+        CloudJob& cj = c->h_cloud_jobs[nj];
+        cj.job = c->d_seq_jobs + j; cj.img = kfr.img[0]; cj.out_offset = (size_t) s * cap;
+        std::memcpy(cj.K, slot_geom(c, kfr, lvl).K, sizeof(cj.K));
+        cj.rows = slot_geom(c, kfr, 0).rows; cj.cols = slot_geom(c, kfr, 0).cols;
+        cj.loss = g.body.params.lossFunction;
+        max_c = std::max(max_c, n_points[j]);
+      }
     }
-    HIP_CK(c, hipMemcpyAsync(c->d_cloud_jobs, c->h_cloud_jobs, sizeof(CloudJob) * (size_t) n, hipMemcpyHostToDevice, c->stream));
-    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, n, max_c, c->C, c->dspace, c->d_seq_cloud);
+    HIP_CK(c, hipMemcpyAsync(c->d_cloud_jobs, c->h_cloud_jobs, sizeof(CloudJob) * (size_t) nj, hipMemcpyHostToDevice, c->stream));
+    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, nj, max_c, c->C, c->dspace, c->d_seq_cloud);
     HIP_CK(c, hipGetLastError());
-    std::vector<KeyFrameSlots> ks((size_t) n);
-    vo_rig_keyframe(members.data(), n, c->frames[members[0]->prev].has_data, cloud_points.data(), ks.data(), result);
-    for(int i = 0; i < n; ++i) {
-      if(ks[i].clear_slot >= 0) slot_clear(c, ks[i].clear_slot);
-      slots[i] = ks[i].template_slot;
+    slots.clear();
+    for(int k : kf) {
+      std::vector<SeqState*> mem = members_of(est[k]);
+      const int nm = (int) mem.size();
+      std::vector<size_t> cloud_points((size_t) nm);
+      for(int i = 0; i < nm; ++i) cloud_points[i] = (size_t) n_points[first[k] + i];
+      std::vector<KeyFrameSlots> ks((size_t) nm);
+      vo_rig_keyframe(mem.data(), nm, c->frames[mem[0]->prev].has_data, cloud_points.data(), ks.data(), results + est[k]);
+      for(int i = 0; i < nm; ++i) {
+        if(ks[i].clear_slot >= 0) slot_clear(c, ks[i].clear_slot);
+        slots.push_back(ks[i].template_slot);
+      }
+      if(ks[0].reestimate) re.push_back(k);
     }
     rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
-    if(ks[0].reestimate) {
-      for(int i = 0; i < n; ++i) { refs[i] = members[i]->ref; curs[i] = members[i]->cur; }
-      const M44 I = m44_identity();
-      rc = estimate_rig(c, n, wss.data(), refs.data(), curs.data(), X, I.m, T_again.m, result->optimizerStatistics);
+    if(!re.empty()) {
+      std::vector<int> which;
+      for(int k : re) which.push_back(est[k]);
+      rc = rigs_estimate(c, ids, which, std::vector<M44>(re.size(), m44_identity()), T_again, results);
       if(rc) return drain(rc);
-      again = true;
       if(c->pose_covariance) {
-        rc = pose_cov_pass(c, 1, n, wss.data(), refs.data(), curs.data(), X, lvl, nullptr, nullptr, nullptr, &c->rig_cov);
+        rc = rigs_covariance(c, ids, which);
         if(rc) return rc;
       }
     }
   }
 
-  // 7. the pose, T_kf and the trajectory of the body; every member's slots, and its cloud's pose
-  vo_rig_finish(body, members.data(), X, n, T_est, again ? &T_again : nullptr, result);
-  if(c->pose_covariance) std::memcpy(result->covariance, c->rig_cov.covariance, sizeof(result->covariance));
+  // 7. per rig: the pose, T_kf and the trajectory of the body; every member's slots, and its cloud's pose
+  std::vector<int> again_of((size_t) m, -1);
+  for(size_t t = 0; t < re.size(); ++t) again_of[re[t]] = (int) t;
+  for(int k = 0; k < m; ++k) {
+    RigState& g = rig(est[k]);
+    std::vector<SeqState*> mem = members_of(est[k]);
+    vo_rig_finish(g.body, mem.data(), g.X.data(), (int) mem.size(), T_est[k], again_of[k] >= 0 ? &T_again[again_of[k]] : nullptr, results + est[k]);
+    if(c->pose_covariance) std::memcpy(results[est[k]].covariance, g.cov.covariance, sizeof(results[est[k]].covariance));
+  }
   return BPVO_OK;
+}
+int bpvo_hip_add_frames_rigs(bpvo_hip_ctx* c, int n, const int* rigs, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* results)
+{
+  CHECK_CTX(c);
+  if(c->rigs.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames_rigs: the context declares no rig (bpvo_hip_rigs_set)");
+  std::vector<int> ids;
+  const int rc = add_frames_rigs_check(c, n, rigs, images, disparities, results, ids);
+  if(rc) return rc;
+  return add_frames_rigs_run(c, n, ids, images, disparities, on_device != 0, results);
+}
+int bpvo_hip_add_frames_rig(bpvo_hip_ctx* c, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* result)
+{
+  CHECK_CTX(c);
+  if(c->rigs.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames_rig: the context declares no rig (bpvo_hip_rig_set)");
+  if(int rc = rig_is_singular(c, "bpvo_hip_add_frames_rigs")) return rc;
+  std::vector<int> ids;
+  const int rc = add_frames_rigs_check(c, 1, nullptr, images, disparities, result, ids);
+  if(rc) return rc;
+  return add_frames_rigs_run(c, 1, ids, images, disparities, on_device != 0, result);
 }
 // StereoAlgorithm::run + addFrame of every sequence of the call (apps/vo_app.cc per camera): the front-end once over all the pairs, each in
 // its sequence's camera geometry, into the context's own maps, which the frame stages then read where they lie — no host synchronisation
@@ -1209,6 +1394,15 @@ static bool structural_difference(const bpvo_hip_ctx* c, int seq, const bpvo_hip
 #undef SP_FLT
   return false;
 }
+// does anything the library reads per sequence (or per rig) differ between two parameter sets?
+static bool params_differ_where_read(const bpvo_hip_params& p, const bpvo_hip_params& o)
+{
+  return p.lossFunction != o.lossFunction || p.maxIterations != o.maxIterations || p.parameterTolerance != o.parameterTolerance ||
+         p.functionTolerance != o.functionTolerance || p.gradientTolerance != o.gradientTolerance ||
+         p.minTranslationMagToKeyFrame != o.minTranslationMagToKeyFrame || p.minRotationMagToKeyFrame != o.minRotationMagToKeyFrame ||
+         p.maxFractionOfGoodPointsToKeyFrame != o.maxFractionOfGoodPointsToKeyFrame || p.goodPointThreshold != o.goodPointThreshold ||
+         p.minSaliency != o.minSaliency || p.minValidDisparity != o.minValidDisparity || p.maxValidDisparity != o.maxValidDisparity;
+}
 int bpvo_hip_seq_set_params(bpvo_hip_ctx* c, int seq, const bpvo_hip_params* p)
 {
   CHECK_CTX(c); CHECK_SEQ(c, seq);
@@ -1225,11 +1419,7 @@ int bpvo_hip_seq_set_params(bpvo_hip_ctx* c, int seq, const bpvo_hip_params* p)
   const bpvo_hip_params& o = c->params;
   q.params = *p;
   // does anything the library reads differ from the context's?  (No: the sequence stays on the plain path, whatever the unread fields say)
-  q.own_params = p->lossFunction != o.lossFunction || p->maxIterations != o.maxIterations || p->parameterTolerance != o.parameterTolerance ||
-                 p->functionTolerance != o.functionTolerance || p->gradientTolerance != o.gradientTolerance ||
-                 p->minTranslationMagToKeyFrame != o.minTranslationMagToKeyFrame || p->minRotationMagToKeyFrame != o.minRotationMagToKeyFrame ||
-                 p->maxFractionOfGoodPointsToKeyFrame != o.maxFractionOfGoodPointsToKeyFrame || p->goodPointThreshold != o.goodPointThreshold ||
-                 p->minSaliency != o.minSaliency || p->minValidDisparity != o.minValidDisparity || p->maxValidDisparity != o.maxValidDisparity;
+  q.own_params = params_differ_where_read(*p, o);
   for(int k = 0; k < 3; ++k) c->frames[3 * seq + k].seq_params = q.own_params ? &q.params : nullptr;
   c->vo_mode = 2;      // a context with per-sequence parameters serves bpvo_hip_add_frames
   return BPVO_OK;
@@ -1240,6 +1430,31 @@ int bpvo_hip_seq_get_params(const bpvo_hip_ctx* c, int seq, bpvo_hip_params* p)
   *p = c->seqs.empty() ? c->params : c->seqs[seq].params;
   return BPVO_OK;
 }
+// A rig's parameters: the fields a sequence may own (bpvo_hip_seq_set_params), for all its members and its body — one rig, one parameter set
+int bpvo_hip_rigs_set_params(bpvo_hip_ctx* c, int rig, const bpvo_hip_params* p)
+{
+  CHECK_CTX(c); CHECK_RIG(c, rig);
+  if(!p) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr parameters");
+  RigState& g = c->rigs[rig];
+  for(int s : g.seq)
+    if(int rc = seq_is_fresh(c, s, "rig's parameters change")) return rc;
+  std::string why;
+  for(int s : g.seq)
+    if(structural_difference(c, s, *p, &why)) return fail(c, BPVO_ERR_UNSUPPORTED, ("rig " + std::to_string(rig) + ": " + why).c_str());
+  if(p->lossFunction != BPVO_LOSS_HUBER && p->lossFunction != BPVO_LOSS_TUKEY && p->lossFunction != BPVO_LOSS_L2)
+    return fail(c, BPVO_ERR_UNSUPPORTED, ("rig " + std::to_string(rig) + ": unknown lossFunction").c_str());
+  g.body.params = *p;
+  g.body.own_params = params_differ_where_read(*p, c->params);
+  rig_param_target(c, g);
+  return BPVO_OK;
+}
+int bpvo_hip_rigs_get_params(const bpvo_hip_ctx* c, int rig, bpvo_hip_params* p)
+{
+  if(!c || !p || rig < 0 || (size_t) rig >= c->rigs.size()) return BPVO_ERR_INVALID_ARG;
+  *p = c->rigs[rig].body.params;
+  return BPVO_OK;
+}
+#undef CHECK_RIG
 #undef CHECK_SEQ
 
 }  // extern "C"

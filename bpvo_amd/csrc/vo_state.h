@@ -152,6 +152,14 @@ inline void vo_finish(SeqState& q, const M44& T_est, const M44* T_again, bpvo_hi
 
 // ---- rig mode (bpvo_hip_add_frames_rig): the cameras of a rigid rig advance in lock step as ONE body.  The body's SeqState keeps T_kf and the
 // trajectory (its slot roles are unused); every member takes the same transition on its own slots.  X: the extrinsics [n][16], camera_from_body.
+// One declared rig (bpvo_hip_ctx::rigs): its members' sequence ids and extrinsics [n][16], the body — T_kf, the trajectory and the RIG's algorithm
+// parameters (SeqState::params / own_params: bpvo_hip_rigs_set_params; the context's until then) — and the pose-covariance record of its last frame
+struct RigState {
+  std::vector<int> seq;
+  std::vector<float> X;
+  SeqState body;
+  bpvo_hip_pose_covariance cov;
+};
 // The fraction of good points of the rig's one decision: pooled over the members, sum good_p / sum n_p C (one member: vo_fraction_good)
 inline float vo_rig_fraction_good(const unsigned* good_counts, const int* n_points, int n, int C)
 {

@@ -442,6 +442,43 @@ int bpvo_hip_rig_get(const bpvo_hip_ctx* ctx, int* n, int* seq /*[n] or NULL*/, 
 int bpvo_hip_add_frames_rig(bpvo_hip_ctx* ctx, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* result);
 int bpvo_hip_rig_trajectory_size(bpvo_hip_ctx* ctx, int* n);
 int bpvo_hip_rig_get_trajectory(bpvo_hip_ctx* ctx, float* poses /*[n][16]: the body's trajectory*/);
+/* ---- several rigs in one context, each with its own parameters.  bpvo_hip_rigs_set declares n_rigs rigs over DISJOINT sets of the context's
+ * sequences: rig r has count[r] members, the members of all rigs back to back in seq (NULL: 0, 1, 2, ...) and X, rig after rig; every matrix and
+ * rule is the rig section's above, per rig.  It replaces every rig declared before (only while all their members are fresh), and every rig
+ * starts with the context's parameters.  A sequence in two rigs or twice in one, a sequence with parameters of its own
+ * (bpvo_hip_seq_set_params), a membership change on a sequence that holds frames, an extrinsic that is not rigid, n_rigs or a count < 1 or
+ * above the sequence capacity: BPVO_ERR_INVALID_ARG, nothing changed.  bpvo_hip_rigs_set with n_rigs = 1 and bpvo_hip_rig_set declare the same
+ * rig: the one-rig calls (bpvo_hip_rig_get, bpvo_hip_add_frames_rig, bpvo_hip_rig_trajectory_*, bpvo_hip_rig_pose_covariance) are the plural
+ * calls on rig 0; on a context of SEVERAL rigs they return BPVO_ERR_INVALID_ARG and name the plural call. */
+int bpvo_hip_rigs_set(bpvo_hip_ctx* ctx, int n_rigs, const int* count /*[n_rigs]*/, const int* seq /*[sum count] distinct ids, NULL = 0..*/,
+                      const float* X /*[sum count][16]*/);
+int bpvo_hip_rigs_get(const bpvo_hip_ctx* ctx, int* n_rigs, int* count /*[n_rigs] or NULL*/, int* seq /*[sum count] or NULL*/,
+                      float* X /*[sum count][16] or NULL*/);
+/* One rig, one parameter set: the fields bpvo_hip_seq_set_params accepts — the Gauss-Newton limits and tolerances, the loss, the key-frame
+ * thresholds, goodPointThreshold, minSaliency and the disparity gate — for the rig's body and all its members; anything else must equal the
+ * context's (BPVO_ERR_UNSUPPORTED, the field named in the error string).  Only while the rig's members hold no frame.  Rigs of different losses
+ * in one call run one estimate per loss present. */
+int bpvo_hip_rigs_set_params(bpvo_hip_ctx* ctx, int rig, const bpvo_hip_params* p);
+int bpvo_hip_rigs_get_params(const bpvo_hip_ctx* ctx, int rig, bpvo_hip_params* p);
+/* bpvo_hip_add_frames_rig for n of the declared rigs in one call: rigs[i] (distinct; NULL: 0 .. n-1; any subset, any order) names the rig of
+ * results[i]; the frames of all their members back to back, rig after rig in call order, in member order inside a rig, each in its camera's
+ * size.  One data stage, ONE estimate of all body poses (the members of every rig share each launch of the four-kernel chain, one launch of the
+ * batched rig step per iteration takes every rig's step), one count of good points, per rig its own key-frame decision — its own thresholds on
+ * its own body pose, the fraction pooled over its own members —, one estimate for the rigs that estimate again.  Rigs at their first frame take
+ * part in the data and template stages only; rigs the call does not name are not touched.  Every rig's results, trajectory, point counts and
+ * clouds are bit for bit those of the same rig alone in a context of its own with the rig's parameters as the context's.  A rig named twice,
+ * a rig id out of range, BPVO_WARP_DISPARITY_SPACE_F32 (BPVO_ERR_UNSUPPORTED), a member with parameters of its own: refused before anything
+ * is queued; after an error the rigs go on as if the call had not been made. */
+int bpvo_hip_add_frames_rigs(bpvo_hip_ctx* ctx, int n, const int* rigs /*[n] distinct ids, NULL = 0..n-1*/, const uint8_t* images,
+                             const float* disparities, int on_device, bpvo_hip_result* results /*[n]*/);
+int bpvo_hip_rigs_trajectory_size(bpvo_hip_ctx* ctx, int rig, int* n);
+int bpvo_hip_rigs_get_trajectory(bpvo_hip_ctx* ctx, int rig, float* poses /*[n][16]: the body's trajectory*/);
+/* bpvo_hip_estimate_pose_rig for n_rigs rigs in one estimate (stateless): rig r has count[r] members, back to back in wss / refs / curs / X; no
+ * workspace in two rigs; T_init / T_est [n_rigs][16] the body poses, stats [n_rigs][numLevels] or NULL.  Every rig's result is bit for bit
+ * that of bpvo_hip_estimate_pose_rig on it alone. */
+int bpvo_hip_estimate_pose_rigs(bpvo_hip_ctx* ctx, int n_rigs, const int* count /*[n_rigs]*/, const int* wss, const int* refs, const int* curs,
+                                const float* X /*[sum count][16]*/, const float* T_init /*[n_rigs][16]*/, float* T_est /*[n_rigs][16]*/,
+                                bpvo_hip_stats* stats /*[n_rigs][numLevels] or NULL*/);
 
 /* ---- pose covariance: a robust "sandwich" estimate of the uncertainty of an estimated pose (the reference has none: its Result::covariance is
  * never written, Q16).
@@ -499,6 +536,7 @@ int bpvo_hip_pose_covariance_rig(bpvo_hip_ctx* ctx, int n, const int* wss, const
 int bpvo_hip_vo_pose_covariance(bpvo_hip_ctx* ctx, bpvo_hip_pose_covariance* out);
 int bpvo_hip_seq_pose_covariance(bpvo_hip_ctx* ctx, int seq, bpvo_hip_pose_covariance* out);
 int bpvo_hip_rig_pose_covariance(bpvo_hip_ctx* ctx, bpvo_hip_pose_covariance* out);
+int bpvo_hip_rigs_pose_covariance(bpvo_hip_ctx* ctx, int rig, bpvo_hip_pose_covariance* out);      /* rig `rig` of bpvo_hip_add_frames_rigs */
 /* diagnostics: the curvature M and the score covariance Q (row-major, symmetric) of the last pass on workspace ws, in its normalised twist */
 int bpvo_hip_debug_pose_covariance_sums(bpvo_hip_ctx* ctx, int ws, float M[36], float Q[36]);
 

@@ -158,6 +158,7 @@ class Trajectory {                                              // bpvo/trajecto
   friend class VisualOdometry;
   friend class VisualOdometrySequences;
   friend class RigVisualOdometry;
+  friend class RigsVisualOdometry;
   std::vector<Matrix44> _poses;
 };
 
@@ -651,6 +652,120 @@ class RigVisualOdometry {
   int _n;
   bool _hasPointClouds = false;
   Trajectory _trajectory;
+};
+
+/* Several rigid rigs in one context, advanced by one call (bpvo_hip_add_frames_rigs; c_api.h): a rig dataset's sequences, a fleet of identical
+ * vehicles, a parameter sweep over recorded rig data.  Rig r has the cameras cameras[r] at extrinsics[r] (camera_from_body, as
+ * RigVisualOdometry takes them) and, after setParameters(r, ...), its own algorithm parameters — the fields
+ * VisualOdometrySequences::setParameters accepts.  Every rig's results are those of a RigVisualOdometry of its own with those parameters. */
+class RigsVisualOdometry {
+ public:
+  typedef VisualOdometrySequences::Camera Camera;
+
+  RigsVisualOdometry(const std::vector<std::vector<Camera> >& cameras, const std::vector<std::vector<Matrix44> >& extrinsics,
+                     const AlgorithmParameters& params = AlgorithmParameters(), int device = 0)
+      : _dev(std::make_shared<detail::Device>(toC(cameras), params, device))
+  {
+    if(extrinsics.size() != cameras.size()) throw Error("one set of extrinsics per rig");
+    std::vector<float> X;
+    int first = 0;
+    for(size_t r = 0; r < cameras.size(); ++r) {
+      if(extrinsics[r].size() != cameras[r].size()) throw Error("one extrinsic per camera");
+      _count.push_back((int) cameras[r].size());
+      _first.push_back(first);
+      first += _count.back();
+      for(const Matrix44& x : extrinsics[r]) X.insert(X.end(), x.data(), x.data() + 16);
+    }
+    _dev->check(bpvo_hip_rigs_set(_dev->ctx(), (int) _count.size(), _count.data(), nullptr, X.data()));
+    _trajectories.resize(_count.size());
+    _hasPointClouds.assign(_count.size(), false);
+  }
+
+  int numRigs() const { return (int) _count.size(); }
+  int numCameras(int rig) const { return _count.at(rig); }
+  /* only before the rig's first frame; a field that fixes the context's storage or kernels must equal the context's (Error names it) */
+  void setParameters(int rig, const AlgorithmParameters& p) { _dev->check(bpvo_hip_rigs_set_params(_dev->ctx(), rig, &p)); }
+  AlgorithmParameters parameters(int rig) const
+  {
+    AlgorithmParameters p;
+    _dev->check(bpvo_hip_rigs_get_params(_dev->ctx(), rig, &p));
+    return p;
+  }
+
+  /* The next frame of the n rigs rigs[0 .. n) (nullptr: every rig, in order): the frames of all their cameras back to back, rig after rig in call
+   * order, camera order inside a rig, each of its camera's size.  Result i is the body's of rigs[i] (RigVisualOdometry::addFrame's). */
+  std::vector<Result> addFrames(const uint8_t* images, const float* disparities, const int* rigs = nullptr, int n = -1)
+  {
+    if(images == nullptr || disparities == nullptr) throw Error("nullptr image/disparity");
+    if(n < 0) n = numRigs();
+    std::vector<bpvo_hip_result> r((size_t) (n > 0 ? n : 0));
+    _dev->check(bpvo_hip_add_frames_rigs(_dev->ctx(), n, rigs, images, disparities, 0, r.data()));
+    std::vector<Result> ret((size_t) n);
+    for(int i = 0; i < n; ++i) {
+      const int g = rigs ? rigs[i] : i;
+      std::memcpy(ret[i].pose.data(), r[i].pose, sizeof(r[i].pose));
+      std::memcpy(ret[i].covariance.data(), r[i].covariance, sizeof(r[i].covariance));
+      for(int l = 0; l < r[i].numLevels; ++l) ret[i].optimizerStatistics.push_back(OptimizerStatistics(r[i].optimizerStatistics[l]));
+      ret[i].isKeyFrame = r[i].isKeyFrame != 0;
+      ret[i].keyFramingReason = static_cast<KeyFramingReason>(r[i].keyFramingReason);
+      _hasPointClouds[g] = r[i].hasPointCloud != 0;
+      int nt = 0;
+      _dev->check(bpvo_hip_rigs_trajectory_size(_dev->ctx(), g, &nt));
+      _trajectories[g]._poses.resize(nt);
+      if(nt) _dev->check(bpvo_hip_rigs_get_trajectory(_dev->ctx(), g, _trajectories[g]._poses[0].data()));
+    }
+    return ret;
+  }
+  /* did the rig's last frame leave point clouds (a key frame after the first)? */
+  bool hasPointClouds(int rig) const { return _hasPointClouds.at(rig); }
+  /* the point cloud of a rig's camera from its last frame; its pose is world_from_camera, W_kf X_p^-1 */
+  PointCloud pointCloud(int rig, int camera) const
+  {
+    PointCloud pc;
+    size_t n = 0;
+    const int s = _first.at(rig) + camera;
+    _dev->check(bpvo_hip_seq_get_point_cloud(_dev->ctx(), s, nullptr, &n, nullptr));
+    pc.points().resize(n);
+    _dev->check(bpvo_hip_seq_get_point_cloud(_dev->ctx(), s, pc.points().data(), &n, pc.pose().data()));
+    return pc;
+  }
+  /* the body's trajectory of a rig */
+  const Trajectory& trajectory(int rig) const { return _trajectories.at(rig); }
+  int numPointsAtLevel(int rig, int camera, int level = -1) const
+  {
+    int n = 0;
+    _dev->check(bpvo_hip_seq_num_points_at_level(_dev->ctx(), _first.at(rig) + camera, level, &n));
+    return n;
+  }
+  void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  double getOption(const std::string& name) const { return _dev->getOption(name); }
+  void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
+  /* the record of the rig's last frame: the covariance of its BODY pose, in the plain body twist */
+  PoseCovarianceEstimate poseCovariance(int rig) const
+  {
+    bpvo_hip_pose_covariance r;
+    _dev->check(bpvo_hip_rigs_pose_covariance(_dev->ctx(), rig, &r));
+    return PoseCovarianceEstimate(r);
+  }
+
+ private:
+  static std::vector<bpvo_hip_camera> toC(const std::vector<std::vector<Camera> >& rigs)
+  {
+    std::vector<bpvo_hip_camera> v;
+    for(const std::vector<Camera>& cams : rigs)
+      for(const Camera& cam : cams) {
+        bpvo_hip_camera c;
+        std::memcpy(c.K, cam.K.data(), sizeof(c.K));
+        c.baseline = cam.baseline;
+        c.rows = cam.size.rows; c.cols = cam.size.cols;
+        v.push_back(c);
+      }
+    return v;
+  }
+  std::shared_ptr<detail::Device> _dev;
+  std::vector<int> _count, _first;
+  std::vector<bool> _hasPointClouds;
+  std::vector<Trajectory> _trajectories;
 };
 
 }  // namespace bpvo
