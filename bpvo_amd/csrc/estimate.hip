@@ -62,6 +62,39 @@ static bool templates_suit_teams(const bpvo_hip_ctx* c, int n, const int* refs)
   return true;
 }
 
+// The job tables of a lane: rows [first, first + n) at every level — job i of workspace wss[i] on the pair (refs[i], curs[i]), with prm_of(i)'s
+// parameters where that is not null, the G channel-group rows of a wide descriptor behind table 0 — and into max_pts[l] the most points of a row
+// at level l (max_pts is the caller's: rigs fill their ranges one after the other).  Every estimate path lays its jobs out here.
+template <class PrmOf>
+static void fill_job_tables(bpvo_hip_ctx* c, Lane* ln, int first, int n, const int* wss, const int* refs, const int* curs, PrmOf&& prm_of, int* max_pts)
+{
+  const int NP = c->n_pairs;
+  const size_t table = (size_t) c->L * NP;      // jobs of one table [L][NP]; wide descriptors: table 0 the whole jobs, tables 1 .. G their channel groups
+  for(int l = 0; l < c->L; ++l)
+    for(int i = 0; i < n; ++i) {
+      PairJob& pj = ln->h_pjobs[(size_t) l * NP + first + i];
+      pj = make_pair_job(c, wss[i], refs[i], curs[i], l);
+      if(const bpvo_hip_params* prm = prm_of(i)) pair_job_set_params(pj, *prm);
+      for(int k = 0; k < c->G && c->G > 1; ++k) ln->h_pjobs[(size_t) (1 + k) * table + (size_t) l * NP + first + i] = group_pair_job(c, pj, k);
+      max_pts[l] = std::max(max_pts[l], pj.n);
+    }
+}
+// One estimate per loss present among n entries (the loss instantiates the kernels): run(at) for the entries `at` of one loss, the losses in the
+// order of their first occurrence, the entries of a loss in call order.  One loss: one run over all the entries.
+template <class LossOf, class Run>
+static int for_each_loss(int n, LossOf&& loss_of, Run&& run)
+{
+  std::vector<char> done((size_t) n, 0);
+  for(int i = 0; i < n; ++i) {
+    if(done[i]) continue;
+    std::vector<int> at;
+    for(int k = i; k < n; ++k)
+      if(!done[k] && loss_of(k) == loss_of(i)) { done[k] = 1; at.push_back(k); }
+    if(int rc = run(at)) return rc;
+  }
+  return BPVO_OK;
+}
+
 // allow_persistent: only a group that has the device to itself (a batch on ONE lane) may take the persistent kernel — two
 // hand-barrier grids of concurrent lanes must not be co-scheduled.
 int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* refs, const int* curs, const float* T_init,
@@ -81,23 +114,19 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
   const int NP = c->n_pairs;
   // (the pinned staging of a lane is free here: every call that uses it ends with a synchronisation of the lane's stream)
   std::vector<int> max_pts(c->L, 0);
-  const size_t table = (size_t) c->L * NP;      // jobs of one table [L][NP]; wide descriptors: table 0 the whole jobs, tables 1 .. G their channel groups
-  for(int l = 0; l < c->L; ++l)
-    for(int i = 0; i < n; ++i) {
-      PairJob& pj = ln->h_pjobs[(size_t) l * NP + i];
-      pj = make_pair_job(c, wss[i], refs[i], curs[i], l);
-      if(prms) pair_job_set_params(pj, *prms[i]);
-      for(int k = 0; k < c->G && c->G > 1; ++k) ln->h_pjobs[(size_t) (1 + k) * table + (size_t) l * NP + i] = group_pair_job(c, pj, k);
-      // Dense levels (no non-maximum suppression: most pixels are template points) gather their taps straight from the descriptor:
-      // neighbouring points share three quarters of their footprints, so the 32-byte records are fetched about once per pixel
-      // from HBM, where the per-point tap cache reads 128 bytes per point whatever the neighbours do.  The cache pays at the
-      // sparse levels (one point in ~25 pixels: every footprint its own two or three lines).  Batches only: the persistent
-      // single-pair kernel keeps its (L2-resident) cache.
-      if((c->C == 8 || c->C == 1) && n > c->persist_max_ws && (double) pj.n > c->tapcache_max_density * (double) slot_geom(c, c->frames[refs[i]], l).npix) {
-        pj.tapcache_on = 0;
+  const size_t table = (size_t) c->L * NP;
+  fill_job_tables(c, ln, 0, n, wss, refs, curs, [&](int i) { return prms ? prms[i] : nullptr; }, max_pts.data());
+  // Dense levels (no non-maximum suppression: most pixels are template points) gather their taps straight from the descriptor:
+  // neighbouring points share three quarters of their footprints, so the 32-byte records are fetched about once per pixel
+  // from HBM, where the per-point tap cache reads 128 bytes per point whatever the neighbours do.  The cache pays at the
+  // sparse levels (one point in ~25 pixels: every footprint its own two or three lines).  Batches only: the persistent
+  // single-pair kernel keeps its (L2-resident) cache.  (8 channels or 1: one table, no channel-group rows to copy the flag to.)
+  if((c->C == 8 || c->C == 1) && n > c->persist_max_ws)
+    for(int l = 0; l < c->L; ++l)
+      for(int i = 0; i < n; ++i) {
+        PairJob& pj = ln->h_pjobs[(size_t) l * NP + i];
+        if((double) pj.n > c->tapcache_max_density * (double) slot_geom(c, c->frames[refs[i]], l).npix) pj.tapcache_on = 0;
       }
-      max_pts[l] = std::max(max_pts[l], pj.n);
-    }
   // validation mode "reference_reduction": the four-kernel chain with the index-order reduction in irls_reduce's place — residuals always written
   // (no fused path), the step in its own launch, no persistent / team kernel
   const bool ref_mode = c->reference_reduction != 0;
@@ -383,25 +412,18 @@ static int estimate_one_loss(bpvo_hip_ctx* c, int n, const int* wss, const int* 
 int estimate_batch(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses, bpvo_hip_stats* stats,
                    const bpvo_hip_params* const* prms)
 {
-  bool one_loss = true;
-  for(int i = 1; i < n && prms && one_loss; ++i) one_loss = prms[i]->lossFunction == prms[0]->lossFunction;
-  if(!prms || one_loss) return estimate_one_loss(c, n, wss, refs, curs, T_init, poses, stats, prms);
-  std::vector<char> done((size_t) n, 0);
-  for(int i = 0; i < n; ++i) {
-    if(done[i]) continue;
-    std::vector<int> at, w, r, cu;
-    std::vector<const bpvo_hip_params*> pp;
-    for(int k = i; k < n; ++k)
-      if(!done[k] && prms[k]->lossFunction == prms[i]->lossFunction) {
-        done[k] = 1;
-        at.push_back(k); w.push_back(wss[k]); r.push_back(refs[k]); cu.push_back(curs[k]); pp.push_back(prms[k]);
-      }
+  if(!prms) return estimate_one_loss(c, n, wss, refs, curs, T_init, poses, stats, prms);
+  return for_each_loss(n, [&](int i) { return prms[i]->lossFunction; }, [&](const std::vector<int>& at) {
     const int m = (int) at.size();
+    if(m == n) return estimate_one_loss(c, n, wss, refs, curs, T_init, poses, stats, prms);      // (one loss: the call's own arrays)
+    std::vector<int> w(m), r(m), cu(m);
+    std::vector<const bpvo_hip_params*> pp(m);
     std::vector<float> Ti, To((size_t) m * 16);
     std::vector<bpvo_hip_stats> st((size_t) m * c->L);
-    if(T_init) {
-      Ti.resize((size_t) m * 16);
-      for(int k = 0; k < m; ++k) std::memcpy(&Ti[(size_t) k * 16], T_init + 16 * (size_t) at[k], 64);
+    if(T_init) Ti.resize((size_t) m * 16);
+    for(int k = 0; k < m; ++k) {
+      w[k] = wss[at[k]]; r[k] = refs[at[k]]; cu[k] = curs[at[k]]; pp[k] = prms[at[k]];
+      if(T_init) std::memcpy(&Ti[(size_t) k * 16], T_init + 16 * (size_t) at[k], 64);
     }
     const int rc = estimate_one_loss(c, m, w.data(), r.data(), cu.data(), T_init ? Ti.data() : nullptr, To.data(), st.data(), pp.data());
     if(rc) return rc;
@@ -409,8 +431,8 @@ int estimate_batch(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, cons
       if(poses) std::memcpy(poses + 16 * (size_t) at[k], &To[(size_t) k * 16], 64);
       if(stats) std::memcpy(stats + (size_t) at[k] * c->L, &st[(size_t) k * c->L], sizeof(bpvo_hip_stats) * (size_t) c->L);
     }
-  }
-  return BPVO_OK;
+    return (int) BPVO_OK;
+  });
 }
 static int estimate_one_loss(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses, bpvo_hip_stats* stats,
                              const bpvo_hip_params* const* prms)
@@ -614,13 +636,7 @@ static int rig_upload(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const in
   const int NP = c->n_pairs;
   const size_t table = (size_t) c->L * NP;
   max_pts.assign((size_t) c->L, 0);
-  for(int l = 0; l < c->L; ++l)
-    for(int i = 0; i < n; ++i) {
-      PairJob& pj = ln->h_pjobs[(size_t) l * NP + i];
-      pj = make_pair_job(c, wss[i], refs[i], curs[i], l);
-      for(int k = 0; k < c->G && c->G > 1; ++k) ln->h_pjobs[(size_t) (1 + k) * table + (size_t) l * NP + i] = group_pair_job(c, pj, k);
-      max_pts[l] = std::max(max_pts[l], pj.n);
-    }
+  fill_job_tables(c, ln, 0, n, wss, refs, curs, [](int) { return (const bpvo_hip_params*) nullptr; }, max_pts.data());
   RIG_CK(c, ln, hipMemcpyAsync(ln->d_pjobs, ln->h_pjobs, sizeof(PairJob) * table * (size_t) job_tables(c), hipMemcpyHostToDevice, ln->stream));
   if(!c->d_rig_X) RIG_CK(c, ln, hipMalloc((void**) &c->d_rig_X, sizeof(float) * 16 * (size_t) NP));
   // (from the caller's pageable memory: the copy has left it when the call returns)
@@ -700,14 +716,7 @@ static int estimate_rigs_one_loss(bpvo_hip_ctx* c, int R, const RigProblem* rigs
     for(int i = 0; i < q.n; ++i) rig_relative_extrinsic(q.X + 16 * (size_t) i, q.X, hX + 16 * (size_t) (first + i));
     rig_member_pose(q.X, q.T_init, hT + 16 * (size_t) r);
     tab[r] = RigEntry{first, q.n, dX + 16 * (size_t) first, bodies + r, dT + 16 * (size_t) r};
-    for(int l = 0; l < L; ++l)
-      for(int i = 0; i < q.n; ++i) {
-        PairJob& pj = ln->h_pjobs[(size_t) l * NP + first + i];
-        pj = make_pair_job(c, q.wss[i], q.refs[i], q.curs[i], l);
-        if(q.prm) pair_job_set_params(pj, *q.prm);
-        for(int k = 0; k < c->G && c->G > 1; ++k) ln->h_pjobs[(size_t) (1 + k) * table + (size_t) l * NP + first + i] = group_pair_job(c, pj, k);
-        max_pts[l] = std::max(max_pts[l], pj.n);
-      }
+    fill_job_tables(c, ln, first, q.n, q.wss, q.refs, q.curs, [&](int) { return q.prm; }, max_pts.data());
   }
   RIG_CK(c, ln, hipMemcpyAsync(ln->d_pjobs, ln->h_pjobs, sizeof(PairJob) * table * (size_t) job_tables(c), hipMemcpyHostToDevice, ln->stream));
   RIG_CK(c, ln, hipMemcpyAsync(d_stage, c->h_rig_stage, rig_stage_bytes(c), hipMemcpyHostToDevice, ln->stream));
@@ -776,18 +785,12 @@ int estimate_rigs(bpvo_hip_ctx* c, int R, const RigProblem* rigs)
   }
   if(N > c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "rigs: more members than the context's workspaces");
   auto loss_of = [&](int r) { return (rigs[r].prm ? rigs[r].prm : &p)->lossFunction; };
-  bool one_loss = true;
-  for(int r = 1; r < R && one_loss; ++r) one_loss = loss_of(r) == loss_of(0);
-  if(one_loss) return estimate_rigs_one_loss(c, R, rigs, loss_of(0));
-  std::vector<char> done((size_t) R, 0);
-  for(int r = 0; r < R; ++r) {
-    if(done[r]) continue;
+  return for_each_loss(R, loss_of, [&](const std::vector<int>& at) {
+    if((int) at.size() == R) return estimate_rigs_one_loss(c, R, rigs, loss_of(0));
     std::vector<RigProblem> part;
-    for(int k = r; k < R; ++k)
-      if(!done[k] && loss_of(k) == loss_of(r)) { done[k] = 1; part.push_back(rigs[k]); }
-    if(int rc = estimate_rigs_one_loss(c, (int) part.size(), part.data(), loss_of(r))) return rc;
-  }
-  return BPVO_OK;
+    for(int r : at) part.push_back(rigs[r]);
+    return estimate_rigs_one_loss(c, (int) part.size(), part.data(), loss_of(at[0]));
+  });
 }
 
 // one rig: the R = 1 case

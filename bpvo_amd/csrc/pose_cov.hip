@@ -230,9 +230,8 @@ int bpvo_hip_rig_pose_covariance(bpvo_hip_ctx* c, bpvo_hip_pose_covariance* out)
   CHECK_CTX(c);
   if(!out) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr record");
   if(c->rigs.size() > 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares several rigs (bpvo_hip_rigs_set): call bpvo_hip_rigs_pose_covariance");
-  if(c->rigs.empty()) pose_cov_none(out);
-  else *out = c->rigs[0].cov;
-  return BPVO_OK;
+  if(c->rigs.empty()) { pose_cov_none(out); return BPVO_OK; }
+  return bpvo_hip_rigs_pose_covariance(c, 0, out);
 }
 int bpvo_hip_rigs_pose_covariance(bpvo_hip_ctx* c, int rig, bpvo_hip_pose_covariance* out)
 {

@@ -7,7 +7,7 @@ using namespace bpvo_hip_host;
 
 extern "C" {
 
-// ---- VisualOdometry: one frame (the state machine both drivers run: vo_state.h) -----------------------------------------------------------
+// ---- VisualOdometry: one frame (the state machine both drivers run — add_frame_impl here, add_frames_run for sequences and rigs: vo_state.h) --------------------------------------------------
 // getPointCloudFromRefFrame + GetColor (reference: bpvo/vo.cc:250-281)
 static int build_point_cloud(bpvo_hip_ctx* c, size_t* cloud_points)
 {
@@ -471,12 +471,12 @@ int bpvo_hip_trajectory_size(bpvo_hip_ctx* c, int* n) { CHECK_CTX(c); *n = vo_tr
 int bpvo_hip_get_trajectory(bpvo_hip_ctx* c, float* poses) { CHECK_CTX(c); vo_get_trajectory(&c->vo, poses); return BPVO_OK; }
 
 // ---- many independent VisualOdometry sequences in one context (bpvo/vo.cc:125-224 per sequence) ---------------------------------------------
-// Sequence s owns frame slots 3s .. 3s+2 and workspace s.  One call runs every phase of addFrame once for all the sequences it advances: one data
-// stage over their current slots, one template stage for the first frames, one estimate, one count of good points, one point-cloud launch and
-// one template stage for the key frames, one estimate against the new key frames.  Each sequence sees the same kernels on the same inputs as
-// the single path's addFrame (the frame stages, the estimate and the counts do not depend on the batch a frame or pair is in), and the host
-// decides with the same float code — every decision and every change of a sequence's state is a call into vo_state.h, the calls add_frame_impl
-// makes —: the results are the single path's, bit for bit.
+// Sequence s owns frame slots 3s .. 3s+2 and workspace s.  One call runs every phase of addFrame once for all the sequences it advances
+// (add_frames_run below, the driver rigs share): one data stage over their current slots, one template stage for the first frames, one estimate,
+// one count of good points, one point-cloud launch and one template stage for the key frames, one estimate against the new key frames.  Each
+// sequence sees the same kernels on the same inputs as the single path's addFrame (the frame stages, the estimate and the counts do not depend
+// on the batch a frame or pair is in), and the host decides with the same float code — every decision and every change of a sequence's state
+// is a call into vo_state.h that performs the calls add_frame_impl makes —: the results are the single path's, bit for bit.
 static int seq_capacity(const bpvo_hip_ctx* c) { return std::max(0, std::min(c->n_frames / 3, c->n_pairs)); }
 static void seq_reset_state(bpvo_hip_ctx* c, int s)
 {
@@ -568,213 +568,316 @@ static int for_each_size(bpvo_hip_ctx* c, const std::vector<int>& slots, const s
 
 extern "C" {
 
-// 1. every check of a call before any state changes; ids: the sequences it advances
-static int add_frames_check(bpvo_hip_ctx* c, int n, const int* seq, const void* images, const void* second, const char* what_null, bpvo_hip_result* results,
-                            std::vector<int>& ids)
+// ---- the one batched driver: a call advances ENTRIES, bodies that move as one ------------------------------------------------------------------
+// An entry is a body (vo_state.h: vo_rig_*), its member sequences, its extrinsics, where its result goes and where its covariance record goes.
+// A sequence of bpvo_hip_add_frames is an entry of one member whose body IS the member (&c->seqs[s]), with null extrinsics; a rig of
+// bpvo_hip_add_frames_rig(s) is its RigState.  A call is homogeneous — a context serves one kind or the other — and the members of its entries
+// lie flattened, entry after entry in member order, wherever a phase runs over members (frame slots, count jobs, cloud jobs).  What the kinds do
+// differently is chosen by the kind in three places and nowhere else: the estimate (entries_estimate), the covariance pass (entries_covariance)
+// and launch_refresh_residuals before the count (sequences only).  Every phase both kinds share is thereby pinned, bit for bit, by the
+// sequences' comparison with add_frame_impl and the oracle (tests/test_gpu_multi_sequence.py).
+struct Entry {
+  SeqState* body;
+  const int* seq; int n;             // the members' sequence ids = their workspaces
+  std::vector<SeqState*> mem;        // &c->seqs[seq[p]]
+  const float* X;                    // [n][16] camera_from_body, or null: one member, the body is the member
+  bpvo_hip_result* ret;
+  bpvo_hip_pose_covariance* cov;     // seq_cov[s] / RigState::cov
+};
+static void rig_param_target(bpvo_hip_ctx* c, const RigState& g)      // the members' frame jobs read the rig's selection thresholds
 {
-  if(!c->rigs.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares a rig (bpvo_hip_rig_set): it serves bpvo_hip_add_frames_rig only");
-  if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a context serves either add_frame or add_frames");
-  const int S = seq_capacity(c);
-  if(S < 1) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames needs a ctx with n_frames >= 3 and n_pairs >= 1");
-  if(n < 1 || n > S) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames: n must be within 1 .. the sequence capacity");
+  for(int s : g.seq)
+    for(int k = 0; k < 3; ++k) c->frames[3 * s + k].seq_params = g.body.own_params ? &g.body.params : nullptr;
+}
+static int id_fail(bpvo_hip_ctx* c, bool rig, int id, const char* what)
+{
+  c->err = std::string(rig ? "rig " : "sequence ") + std::to_string(id) + ": " + what;
+  return BPVO_ERR_INVALID_ARG;
+}
+// 1. every check of a call before any state changes; ids: the sequences (given null: 0 .. n-1) or the rigs it advances
+static int add_frames_check(bpvo_hip_ctx* c, bool rig, int n, const int* given, const void* images, const void* second, const char* what_null,
+                            bpvo_hip_result* results, std::vector<int>& ids)
+{
+  const int limit = rig ? (int) c->rigs.size() : seq_capacity(c);
+  if(!rig) {
+    if(!c->rigs.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "this context declares a rig (bpvo_hip_rig_set): it serves bpvo_hip_add_frames_rig only");
+    if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a context serves either add_frame or add_frames");
+    if(limit < 1) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames needs a ctx with n_frames >= 3 and n_pairs >= 1");
+  }
+  if(n < 1 || n > limit)
+    return fail(c, BPVO_ERR_INVALID_ARG, rig ? "add_frames_rigs: n must be within 1 .. the declared rigs" : "add_frames: n must be within 1 .. the sequence capacity");
   if(!images || !second) return fail(c, BPVO_ERR_INVALID_ARG, what_null);   // bpvo/vo.cc:68-69
   if(!results) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
   ids.assign((size_t) n, 0);
-  std::vector<char> seen((size_t) S, 0);
+  std::vector<char> seen((size_t) limit, 0);
   for(int i = 0; i < n; ++i) {
-    ids[i] = seq ? seq[i] : i;
-    if(ids[i] < 0 || ids[i] >= S) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "no such sequence (n_frames >= 3 S and n_pairs >= S serve sequences 0 .. S-1)");
-    if(seen[ids[i]]) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "appears twice in one call");
+    ids[i] = given ? given[i] : i;
+    if(ids[i] < 0 || ids[i] >= limit)
+      return id_fail(c, rig, ids[i], rig ? "no such rig (bpvo_hip_rigs_set declares rigs 0 .. n_rigs-1)" : "no such sequence (n_frames >= 3 S and n_pairs >= S serve sequences 0 .. S-1)");
+    if(seen[ids[i]]) return id_fail(c, rig, ids[i], "appears twice in one call");
     seen[ids[i]] = 1;
   }
-  const bpvo_hip_params& p = c->params;
-  if(!c->seqs.empty())
-    for(int i = 0; i < n; ++i) {
-      const FrameSlot& ref = c->frames[c->seqs[ids[i]].ref];
-      if(!ref.has_template) continue;
-      for(int l = p.maxTestLevel; l < c->L; ++l)      // template_data.cc:177 (check_template_not_empty)
-        if(ref.n_host[l] <= 0) return seq_fail(c, BPVO_ERR_NO_TEMPLATE, ids[i], "the key frame's template is empty (you should call setData before calling computeResiduals)");
+  if(c->seqs.empty()) return BPVO_OK;      // (no sequence holds a frame yet; rigs_set_impl makes the states)
+  auto members = [&](int i) { return rig ? c->rigs[ids[i]].seq : std::vector<int>(1, ids[i]); };
+  // a member's own parameters are its body's: a sequence's its own, a rig's never
+  for(int i = 0; i < n && rig; ++i)
+    for(int s : members(i))
+      if(c->seqs[s].own_params) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "has parameters of its own: a rig runs its own (bpvo_hip_rigs_set_params) or the context's parameters");
+  if(rig && c->dspace) return fail(c, BPVO_ERR_UNSUPPORTED, "rig mode does not serve BPVO_WARP_DISPARITY_SPACE_F32");
+  for(int i = 0; i < n; ++i) {
+    const std::vector<int> mem = members(i);
+    if(!c->frames[c->seqs[mem[0]].ref].has_template) continue;      // (its first frame)
+    for(int s : mem) {
+      const FrameSlot& ref = c->frames[c->seqs[s].ref];
+      for(int l = c->params.maxTestLevel; l < c->L; ++l)      // template_data.cc:177 (check_template_not_empty)
+        if(!ref.has_template || ref.n_host[l] <= 0)
+          return seq_fail(c, BPVO_ERR_NO_TEMPLATE, s, "the key frame's template is empty (you should call setData before calling computeResiduals)");
     }
+  }
   return BPVO_OK;
 }
-static int add_frames_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, const uint8_t* images, const float* disparities, bool on_device,
+// the entries of a checked call (sequences: their states and covariance records are made at the first call)
+static std::vector<Entry> call_entries(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids, bpvo_hip_result* results)
+{
+  if(!rig) {
+    seq_states(c);
+    c->vo_mode = 2;
+    if(c->seq_cov.size() != c->seqs.size()) {
+      c->seq_cov.resize(c->seqs.size());
+      for(auto& r : c->seq_cov) pose_cov_none(&r);
+    }
+  }
+  std::vector<Entry> E(ids.size());
+  for(size_t i = 0; i < ids.size(); ++i) {
+    Entry& e = E[i];
+    if(rig) {
+      RigState& g = c->rigs[ids[i]];
+      rig_param_target(c, g);
+      e.body = &g.body; e.seq = g.seq.data(); e.n = (int) g.seq.size(); e.X = g.X.data(); e.cov = &g.cov;
+    } else {
+      e.body = &c->seqs[ids[i]]; e.seq = &ids[i]; e.n = 1; e.X = nullptr; e.cov = &c->seq_cov[(size_t) ids[i]];
+    }
+    for(int p = 0; p < e.n; ++p) e.mem.push_back(&c->seqs[e.seq[p]]);
+    e.ret = results + i;
+  }
+  return E;
+}
+// the members of some entries, flattened: member j is workspace wss[j] on the pair (refs[j], curs[j]); entry k's are [first[k], first[k + 1])
+struct Members { std::vector<int> wss, refs, curs, first; };
+static Members members_of(const std::vector<const Entry*>& which)
+{
+  Members M;
+  M.first.push_back(0);
+  for(const Entry* e : which) {
+    for(int p = 0; p < e->n; ++p) { M.wss.push_back(e->seq[p]); M.refs.push_back(e->mem[p]->ref); M.curs.push_back(e->mem[p]->cur); }
+    M.first.push_back((int) M.wss.size());
+  }
+  return M;
+}
+// each entry's parameters (its body's).  Whether the jobs take them is the kind's rule: sequences hand them on only when one of the call's estimating
+// sequences has its own — a call of uniform parameters runs exactly what it ran before there were any (null: the context's, from the launches'
+// one source); a rig hands on its own, or null, rig by rig
+static std::vector<const bpvo_hip_params*> entry_params(const std::vector<const Entry*>& which)
+{
+  std::vector<const bpvo_hip_params*> prms;
+  for(const Entry* e : which) prms.push_back(&e->body->params);
+  return prms;
+}
+// 4. ONE estimate of the entries `which`, entry k from T_init[k] to T_out[k], the statistics into the results.  Sequences: estimate_batch over the
+// pairs; rigs: estimate_rigs, each body pose from all its members' residuals.  own: one of the call's estimating entries has parameters of its own
+static int entries_estimate(bpvo_hip_ctx* c, const std::vector<const Entry*>& which, const Members& M, bool own, const std::vector<M44>& T_init,
+                            std::vector<M44>& T_out)
+{
+  const int m = (int) which.size(), L = c->L;
+  const std::vector<const bpvo_hip_params*> prms = entry_params(which);
+  T_out.assign((size_t) m, m44_identity());
+  if(which[0]->X) {
+    std::vector<RigProblem> pr((size_t) m);
+    for(int k = 0; k < m; ++k) {
+      const int at = M.first[k];
+      pr[k] = RigProblem{which[k]->n, &M.wss[at], &M.refs[at], &M.curs[at], which[k]->X, T_init[k].m, T_out[k].m, which[k]->ret->optimizerStatistics,
+                         which[k]->body->own_params ? prms[k] : nullptr};
+    }
+    return estimate_rigs(c, m, pr.data());
+  }
+  std::vector<bpvo_hip_stats> stats((size_t) m * L);
+  const int rc = estimate_batch(c, m, M.wss.data(), M.refs.data(), M.curs.data(), T_init[0].m, T_out[0].m, stats.data(), own ? prms.data() : nullptr);
+  if(rc) return rc;
+  for(int k = 0; k < m; ++k) std::memcpy(which[k]->ret->optimizerStatistics, &stats[(size_t) k * L], sizeof(bpvo_hip_stats) * L);
+  return BPVO_OK;
+}
+// option "pose_covariance": the records of the entries' last estimates, from the workspaces' states on the device, into cov[k].  Sequences: all in
+// ONE pass of one-member records; rigs: the one-record pass rig by rig (its launch takes ONE set of extrinsics for all its records: DESIGN.md §5)
+static int entries_covariance(bpvo_hip_ctx* c, const std::vector<const Entry*>& which, const Members& M, bool own, bpvo_hip_pose_covariance* cov)
+{
+  const int m = (int) which.size(), lvl = c->params.maxTestLevel;
+  const std::vector<const bpvo_hip_params*> prms = entry_params(which);
+  if(!which[0]->X)
+    return pose_cov_pass(c, m, 1, M.wss.data(), M.refs.data(), M.curs.data(), nullptr, lvl, nullptr, nullptr, own ? prms.data() : nullptr, cov);
+  for(int k = 0; k < m; ++k) {
+    const int at = M.first[k];
+    const std::vector<const bpvo_hip_params*> mine((size_t) which[k]->n, prms[k]);
+    const int rc = pose_cov_pass(c, 1, which[k]->n, &M.wss[at], &M.refs[at], &M.curs[at], which[k]->X, lvl, nullptr, nullptr,
+                                 which[k]->body->own_params ? mine.data() : nullptr, cov + k);
+    if(rc) return rc;
+  }
+  return BPVO_OK;
+}
+// The seven phases of addFrame, each ONCE for all the entries of the call (phase 1: add_frames_check)
+static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids, const uint8_t* images, const float* disparities, bool on_device,
                           bpvo_hip_result* results)
 {
   const bpvo_hip_params& p = c->params;
+  const int L = c->L, lvl = p.maxTestLevel;
   (void) hipSetDevice(c->device);
-  seq_states(c);
+  std::vector<Entry> E = call_entries(c, rig, ids, results);
   int rc = seq_storage(c);
   if(rc) return rc;
-  c->vo_mode = 2;
-  const M44 I = m44_identity();
-  for(int i = 0; i < n; ++i) vo_begin_frame(c->seqs[ids[i]], c->L, results + i);
-  if(c->seq_cov.size() != c->seqs.size()) {
-    c->seq_cov.resize(c->seqs.size());
-    for(auto& r : c->seq_cov) pose_cov_none(&r);
+  for(Entry& e : E) {
+    vo_rig_begin_frame(*e.body, e.mem.data(), e.n, L, e.ret);
+    pose_cov_none(e.cov);
   }
-  for(int i = 0; i < n; ++i) pose_cov_none(&c->seq_cov[(size_t) ids[i]]);
   auto drain = [&](int code) { (void) hipStreamSynchronize(c->stream); return code; };
-
-  // 2. _cur_frame->setData (vo.cc:131) of every sequence: one data stage over their current slots
-  // (frame i: slot_geom(cur, 0).npix pixels at the sum of the frames' before it)
-  std::vector<int> slots((size_t) n);
-  std::vector<size_t> offsets((size_t) n);
-  size_t at = 0;
-  for(int i = 0; i < n; ++i) {
-    slots[i] = c->seqs[ids[i]].cur;
-    offsets[i] = at;
-    at += slot_geom(c, c->frames[slots[i]], 0).npix;
-  }
   auto template_stage = [&](const int* sl, int count, const size_t*, const FrameRun& fr) { return frames_set_template_slots(c, sl, count, fr); };
+
+  // 2. _cur_frame->setData (vo.cc:131) of every member: one data stage over their current slots
+  // (member j: slot_geom(cur, 0).npix pixels — its camera's — at the sum of the members' before it)
+  std::vector<int> slots;
+  std::vector<size_t> offsets;
+  size_t at = 0;
+  for(const Entry& e : E)
+    for(const SeqState* q : e.mem) {
+      slots.push_back(q->cur);
+      offsets.push_back(at);
+      at += slot_geom(c, c->frames[q->cur], 0).npix;
+    }
   rc = for_each_size(c, slots, &offsets, [&](const int* sl, int count, const size_t* off, const FrameRun& fr) {
     return frames_set_data_slots(c, sl, count, images, disparities, on_device, fr, 0, off);
   });
   if(rc) return drain(rc);
 
-  // 3. first frames (vo.cc:133-139): their templates in one stage
-  std::vector<int> est;           // entries of the call that estimate
+  // 3. first frames (vo.cc:133-139): every member's template in one stage
+  std::vector<const Entry*> est, firsts;      // the entries that estimate / that are at their first frame
   slots.clear();
-  for(int i = 0; i < n; ++i) {
-    SeqState& q = c->seqs[ids[i]];
-    if(c->frames[q.ref].has_template) { est.push_back(i); continue; }
-    slots.push_back(vo_first_frame(q));
+  for(Entry& e : E) {
+    if(c->frames[e.mem[0]->ref].has_template) { est.push_back(&e); continue; }
+    firsts.push_back(&e);
+    for(SeqState* q : e.mem) slots.push_back(vo_first_frame(*q));
   }
-  if(!slots.empty()) {
+  if(!firsts.empty()) {
     rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
-    for(int i = 0; i < n; ++i) {
-      if(std::find(est.begin(), est.end(), i) != est.end()) continue;
-      vo_first_frame_done(c->seqs[ids[i]], &results[i]);
-    }
+    for(const Entry* e : firsts) vo_rig_first_frame_done(*e->body, e->mem.data(), e->n, e->ret);
   }
   const int m = (int) est.size();
   if(m == 0) return BPVO_OK;
 
-  // 4. estimatePose(ref, cur, T_kf) of the others in one estimate
-  const int L = c->L, lvl = p.maxTestLevel;
-  std::vector<int> wss(m), refs(m), curs(m);
-  std::vector<float> T_init((size_t) m * 16), T_est((size_t) m * 16);
-  std::vector<bpvo_hip_stats> stats((size_t) m * L);
-  // each estimating sequence's parameters — handed on only when one of them has its own: a call of uniform parameters runs exactly what it ran
-  // before there were any (null: the context's, from the launches' one source)
-  std::vector<const bpvo_hip_params*> prms((size_t) m);
+  // 4. estimatePose(ref, cur, T_kf) of the others, each from its body's T_kf: one estimate
   bool own = false;
-  for(int k = 0; k < m; ++k) {
-    const SeqState& q = c->seqs[ids[est[k]]];
-    wss[k] = ids[est[k]]; refs[k] = q.ref; curs[k] = q.cur;
-    std::memcpy(&T_init[(size_t) k * 16], q.T_kf.m, 64);
-    prms[k] = &q.params;
-    own = own || q.own_params;
-  }
-  rc = estimate_batch(c, m, wss.data(), refs.data(), curs.data(), T_init.data(), T_est.data(), stats.data(), own ? prms.data() : nullptr);
+  std::vector<M44> T_init((size_t) m), T_est, T_again;
+  for(int k = 0; k < m; ++k) { T_init[k] = est[k]->body->T_kf; own = own || est[k]->body->own_params; }
+  const Members M = members_of(est);
+  rc = entries_estimate(c, est, M, own, T_init, T_est);
   if(rc) return drain(rc);
-  for(int k = 0; k < m; ++k) std::memcpy(results[est[k]].optimizerStatistics, &stats[(size_t) k * L], sizeof(bpvo_hip_stats) * L);
-  // option "pose_covariance": every estimating sequence of the call in one launch set per group, from the workspaces' states on the device and
-  // before the key frames' stages rewrite any slot (the sequences that estimate again: once more behind that estimate)
-  std::vector<bpvo_hip_pose_covariance> cov;
+  // option "pose_covariance": behind the estimate and before the key frames' stages rewrite any slot (the entries that estimate again: once more
+  // behind that estimate)
+  std::vector<bpvo_hip_pose_covariance> cov((size_t) (c->pose_covariance ? m : 0));
   if(c->pose_covariance) {
-    cov.resize((size_t) m);
-    rc = pose_cov_pass(c, m, 1, wss.data(), refs.data(), curs.data(), nullptr, lvl, nullptr, nullptr, own ? prms.data() : nullptr, cov.data());
+    rc = entries_covariance(c, est, M, own, cov.data());
     if(rc) return rc;
   }
 
-  // 5. the key-frame decision (vo.cc:199-224): motion on the host, the fraction of good points of every estimated sequence in one count
+  // 5. the key-frame decision (vo.cc:199-224) per entry: the body's motion on the host, then the fraction of good points pooled over its members —
+  // every member's count from ONE launch over the workspaces' last linearisations (estimate: level maxTestLevel)
+  const int N = M.first[m];
+  std::vector<int> n_points((size_t) N);
   int max_n = 0;
-  for(int k = 0; k < m; ++k) {
-    c->h_seq_jobs[k] = make_pair_job(c, wss[k], refs[k], curs[k], lvl);      // the workspace's last linearisation (estimate_batch: level maxTestLevel)
-    if(own) pair_job_set_params(c->h_seq_jobs[k], *prms[k]);
-    max_n = std::max(max_n, c->h_seq_jobs[k].n);
-  }
-  HIP_CK(c, hipMemcpyAsync(c->d_seq_jobs, c->h_seq_jobs, sizeof(PairJob) * (size_t) m, hipMemcpyHostToDevice, c->stream));
-  {
-    GNLaunch gr;      // (fused path: the residual buffers may lag behind the last linearisation — ensure_residuals)
-    gr.jobs = c->d_seq_jobs; gr.npairs = m; gr.max_points = max_n; gr.C = c->C;
+  for(int k = 0; k < m; ++k)
+    for(int j = M.first[k]; j < M.first[k + 1]; ++j) {
+      PairJob& pj = c->h_seq_jobs[j];
+      pj = make_pair_job(c, M.wss[j], M.refs[j], M.curs[j], lvl);
+      if(own) pair_job_set_params(pj, est[k]->body->params);
+      n_points[j] = pj.n;
+      max_n = std::max(max_n, pj.n);
+    }
+  HIP_CK(c, hipMemcpyAsync(c->d_seq_jobs, c->h_seq_jobs, sizeof(PairJob) * (size_t) N, hipMemcpyHostToDevice, c->stream));
+  if(!rig) {
+    GNLaunch gr;      // (estimate_batch's fused path: the residual buffers may lag behind the last linearisation — ensure_residuals; estimate_rigs' chain writes them always)
+    gr.jobs = c->d_seq_jobs; gr.npairs = N; gr.max_points = max_n; gr.C = c->C;
     launch_refresh_residuals(c->stream, gr);
   }
-  HIP_CK(c, hipMemsetAsync(c->d_seq_cnt, 0, sizeof(unsigned) * (size_t) m, c->stream));
-  if(own) launch_count_good_jobs(c->stream, c->d_seq_jobs, m, max_n, c->C, c->d_seq_cnt);      // (each entry's loss and threshold, from its job)
-  else launch_count_good_batch(c->stream, c->d_seq_jobs, m, max_n, c->C, p.lossFunction, p.goodPointThreshold, c->d_seq_cnt);
-  HIP_CK(c, hipMemcpyAsync(c->h_seq_cnt, c->d_seq_cnt, sizeof(unsigned) * (size_t) m, hipMemcpyDeviceToHost, c->stream));
+  HIP_CK(c, hipMemsetAsync(c->d_seq_cnt, 0, sizeof(unsigned) * (size_t) N, c->stream));
+  if(own) launch_count_good_jobs(c->stream, c->d_seq_jobs, N, max_n, c->C, c->d_seq_cnt);      // (each entry's loss and threshold, from its members' jobs)
+  else launch_count_good_batch(c->stream, c->d_seq_jobs, N, max_n, c->C, p.lossFunction, p.goodPointThreshold, c->d_seq_cnt);
+  HIP_CK(c, hipMemcpyAsync(c->h_seq_cnt, c->d_seq_cnt, sizeof(unsigned) * (size_t) N, hipMemcpyDeviceToHost, c->stream));
   HIP_CK(c, hipStreamSynchronize(c->stream));
   HIP_CK(c, hipGetLastError());
   std::vector<int> kf;            // entries of est that key-frame
   for(int k = 0; k < m; ++k) {
-    M44 T;
-    std::memcpy(T.m, &T_est[(size_t) k * 16], 64);
-    // with the sequence's thresholds (the context's unless it was given its own)
-    if(vo_decide(*prms[k], T, vo_fraction_good(c->h_seq_cnt[k], c->h_seq_jobs[k].n, c->C), &results[est[k]])) kf.push_back(k);
+    const float frac = vo_rig_fraction_good(c->h_seq_cnt + M.first[k], n_points.data() + M.first[k], est[k]->n, c->C);
+    // with the entry's thresholds (the context's unless it was given its own)
+    if(vo_decide(est[k]->body->params, T_est[k], frac, est[k]->ret)) kf.push_back(k);
   }
 
-  // 6. key frames: the point clouds from the old key frames and the last linearisations (build_point_cloud), then the new templates, then the
-  // estimate against them of the sequences that had a previous frame (vo.cc:161-188)
-  const int nk = (int) kf.size();
+  // 6. key frames: every member's point cloud from its old key frame and its last linearisation (build_point_cloud; one launch), the slot
+  // rotation, the new templates (one stage), then ONE estimate against them of the entries that had a previous frame (vo.cc:161-188)
   std::vector<int> re;            // entries of est that estimate again
-  std::vector<float> T_again_all;
-  if(nk) {
+  if(!kf.empty()) {
     const size_t cap = (size_t) c->geom[lvl].cap;
-    int max_c = 0;
-    for(int j = 0; j < nk; ++j) {
-      const int k = kf[j];
-      const int npts = c->h_seq_jobs[k].n;
-      if((size_t) npts > cap) return seq_fail(c, BPVO_ERR_INVALID_ARG, wss[k], "size mismatch");
-      const FrameSlot& kfr = c->frames[refs[k]];
-      CloudJob& cj = c->h_cloud_jobs[j];
-      cj.job = c->d_seq_jobs + k; cj.img = kfr.img[0]; cj.out_offset = (size_t) wss[k] * cap;
-      std::memcpy(cj.K, slot_geom(c, kfr, lvl).K, sizeof(cj.K));      // (build_point_cloud: the context's size and level intrinsics; here the sequence's)
-      cj.rows = slot_geom(c, kfr, 0).rows; cj.cols = slot_geom(c, kfr, 0).cols;
-      cj.loss = prms[k]->lossFunction;
-      max_c = std::max(max_c, npts);
-    }
-    HIP_CK(c, hipMemcpyAsync(c->d_cloud_jobs, c->h_cloud_jobs, sizeof(CloudJob) * (size_t) nk, hipMemcpyHostToDevice, c->stream));
-    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, nk, max_c, c->C, c->dspace, c->d_seq_cloud);
+    int max_c = 0, nj = 0;
+    for(int k : kf)
+      for(int j = M.first[k]; j < M.first[k + 1]; ++j)
+        if((size_t) n_points[j] > cap) return seq_fail(c, BPVO_ERR_INVALID_ARG, M.wss[j], "size mismatch");
+    for(int k : kf)
+      for(int j = M.first[k]; j < M.first[k + 1]; ++j, ++nj) {
+        const FrameSlot& kfr = c->frames[M.refs[j]];
+        CloudJob& cj = c->h_cloud_jobs[nj];
+        cj.job = c->d_seq_jobs + j; cj.img = kfr.img[0]; cj.out_offset = (size_t) M.wss[j] * cap;
+        std::memcpy(cj.K, slot_geom(c, kfr, lvl).K, sizeof(cj.K));      // (build_point_cloud: the context's size and level intrinsics; here the member's)
+        cj.rows = slot_geom(c, kfr, 0).rows; cj.cols = slot_geom(c, kfr, 0).cols;
+        cj.loss = est[k]->body->params.lossFunction;
+        max_c = std::max(max_c, n_points[j]);
+      }
+    HIP_CK(c, hipMemcpyAsync(c->d_cloud_jobs, c->h_cloud_jobs, sizeof(CloudJob) * (size_t) nj, hipMemcpyHostToDevice, c->stream));
+    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, nj, max_c, c->C, c->dspace, c->d_seq_cloud);
     HIP_CK(c, hipGetLastError());
     slots.clear();
-    for(int j = 0; j < nk; ++j) {
-      const int k = kf[j];
-      SeqState& q = c->seqs[wss[k]];
-      const KeyFrameSlots ks = vo_keyframe(q, c->frames[q.prev].has_data, (size_t) c->h_seq_jobs[k].n, &results[est[k]]);
-      if(ks.clear_slot >= 0) slot_clear(c, ks.clear_slot);
-      if(ks.reestimate) re.push_back(j);
-      slots.push_back(ks.template_slot);
+    std::vector<const Entry*> again;
+    for(int k : kf) {
+      const Entry& e = *est[k];
+      std::vector<size_t> cloud_points(n_points.begin() + M.first[k], n_points.begin() + M.first[k + 1]);
+      std::vector<KeyFrameSlots> ks((size_t) e.n);
+      vo_rig_keyframe(e.mem.data(), e.n, c->frames[e.mem[0]->prev].has_data, cloud_points.data(), ks.data(), e.ret);
+      for(const KeyFrameSlots& s : ks) {
+        if(s.clear_slot >= 0) slot_clear(c, s.clear_slot);
+        slots.push_back(s.template_slot);
+      }
+      if(ks[0].reestimate) { re.push_back(k); again.push_back(&e); }
     }
     rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
     if(!re.empty()) {
-      const int mr = (int) re.size();
-      std::vector<int> w2(mr), r2(mr), c2(mr);
-      std::vector<float> I2((size_t) mr * 16);
-      std::vector<bpvo_hip_stats> st2((size_t) mr * L);
-      std::vector<const bpvo_hip_params*> p2((size_t) mr);
-      T_again_all.resize((size_t) mr * 16);
-      for(int t = 0; t < mr; ++t) {
-        const SeqState& q = c->seqs[wss[kf[re[t]]]];
-        w2[t] = wss[kf[re[t]]]; r2[t] = q.ref; c2[t] = q.cur;
-        std::memcpy(&I2[(size_t) t * 16], I.m, 64);
-        p2[t] = &q.params;
-      }
-      rc = estimate_batch(c, mr, w2.data(), r2.data(), c2.data(), I2.data(), T_again_all.data(), st2.data(), own ? p2.data() : nullptr);
+      const Members M2 = members_of(again);
+      rc = entries_estimate(c, again, M2, own, std::vector<M44>(re.size(), m44_identity()), T_again);
       if(rc) return drain(rc);
-      for(int t = 0; t < mr; ++t) std::memcpy(results[est[kf[re[t]]]].optimizerStatistics, &st2[(size_t) t * L], sizeof(bpvo_hip_stats) * L);
       if(c->pose_covariance) {
-        std::vector<bpvo_hip_pose_covariance> cov2((size_t) mr);
-        rc = pose_cov_pass(c, mr, 1, w2.data(), r2.data(), c2.data(), nullptr, lvl, nullptr, nullptr, own ? p2.data() : nullptr, cov2.data());
+        std::vector<bpvo_hip_pose_covariance> cov2(re.size());
+        rc = entries_covariance(c, again, M2, own, cov2.data());
         if(rc) return rc;
-        for(int t = 0; t < mr; ++t) cov[(size_t) kf[re[t]]] = cov2[(size_t) t];
+        for(size_t t = 0; t < re.size(); ++t) cov[(size_t) re[t]] = cov2[t];
       }
     }
   }
 
-  // 7. poses, T_kf and trajectories
+  // 7. per entry: the pose, T_kf and the trajectory of the body (a rig: every member's slots, and its cloud's pose), the covariance record
   std::vector<int> again_of((size_t) m, -1);
-  for(int t = 0; t < (int) re.size(); ++t) again_of[kf[re[t]]] = t;
+  for(size_t t = 0; t < re.size(); ++t) again_of[re[t]] = (int) t;
   for(int k = 0; k < m; ++k) {
-    M44 T, T_again;
-    std::memcpy(T.m, &T_est[(size_t) k * 16], 64);
-    if(again_of[k] >= 0) std::memcpy(T_again.m, &T_again_all[(size_t) again_of[k] * 16], 64);
-    vo_finish(c->seqs[wss[k]], T, again_of[k] >= 0 ? &T_again : nullptr, &results[est[k]]);
+    const Entry& e = *est[k];
+    vo_rig_finish(*e.body, e.mem.data(), e.X, e.n, T_est[k], again_of[k] >= 0 ? &T_again[again_of[k]] : nullptr, e.ret);
     if(c->pose_covariance) {
-      c->seq_cov[(size_t) wss[k]] = cov[(size_t) k];
-      std::memcpy(results[est[k]].covariance, cov[(size_t) k].covariance, sizeof(results[est[k]].covariance));
+      *e.cov = cov[(size_t) k];
+      std::memcpy(e.ret->covariance, e.cov->covariance, sizeof(e.ret->covariance));
     }
   }
   return BPVO_OK;
@@ -784,22 +887,17 @@ int bpvo_hip_add_frames(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* i
 {
   CHECK_CTX(c);
   std::vector<int> ids;
-  const int rc = add_frames_check(c, n, seq, images, disparities, "nullptr image/disparity", results, ids);
+  const int rc = add_frames_check(c, false, n, seq, images, disparities, "nullptr image/disparity", results, ids);
   if(rc) return rc;
-  return add_frames_run(c, n, ids, images, disparities, on_device != 0, results);
+  return add_frames_run(c, false, ids, images, disparities, on_device != 0, results);
 }
 // ---- rig mode: the cameras of a rigid rig as ONE body (c_api.h; rig_math.h states the maps) ------------------------------------------------
 // A context declares one rig (bpvo_hip_rig_set) or several over disjoint sets of its sequences (bpvo_hip_rigs_set): bpvo_hip_ctx::rigs.  Member p
-// of a rig is sequence seq[p] — its frame slots, its workspace, its camera — with extrinsic X[p] (camera_from_body).  A call runs the phases of
-// add_frames_run once for ALL the rigs it names: one data stage over every member's frame, ONE estimate of the body poses from all members'
-// residuals (estimate_rigs), one count of good points, per rig one key-frame decision on its body pose with the fraction pooled over its members
-// and its own thresholds, every member of a rig the same transition (vo_state.h: vo_rig_*), one estimate against the new key frames.  A body
-// keeps T_kf, the trajectory and the rig's parameters.  The one-rig entry points are the calls of the plural ones on rig 0.
-static void rig_param_target(bpvo_hip_ctx* c, const RigState& g)      // the members' frame jobs read the rig's selection thresholds
-{
-  for(int s : g.seq)
-    for(int k = 0; k < 3; ++k) c->frames[3 * s + k].seq_params = g.body.own_params ? &g.body.params : nullptr;
-}
+// of a rig is sequence seq[p] — its frame slots, its workspace, its camera — with extrinsic X[p] (camera_from_body).  A call IS add_frames_run
+// over the rigs it names as entries: one data stage over every member's frame, ONE estimate of the body poses from all members' residuals
+// (entries_estimate -> estimate_rigs), one count of good points, per rig one key-frame decision on its body pose with the fraction pooled over
+// its members and its own thresholds, every member of a rig the same transition (vo_state.h: vo_rig_*), one estimate against the new key
+// frames.  A body keeps T_kf, the trajectory and the rig's parameters.  The one-rig entry points are the calls of the plural ones on rig 0.
 static int rigs_set_impl(bpvo_hip_ctx* c, int n_rigs, const int* count, const int* seq, const float* X, const char* who)
 {
   const std::string w(who);
@@ -890,17 +988,15 @@ int bpvo_hip_rig_trajectory_size(bpvo_hip_ctx* c, int* n)
   CHECK_CTX(c);
   if(!n) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr count");
   if(int rc = rig_is_singular(c, "bpvo_hip_rigs_trajectory_size")) return rc;
-  *n = c->rigs.empty() ? 0 : vo_trajectory_size(&c->rigs[0].body);
-  return BPVO_OK;
+  if(c->rigs.empty()) { *n = 0; return BPVO_OK; }
+  return bpvo_hip_rigs_trajectory_size(c, 0, n);
 }
 int bpvo_hip_rig_get_trajectory(bpvo_hip_ctx* c, float* poses)
 {
   CHECK_CTX(c);
   if(int rc = rig_is_singular(c, "bpvo_hip_rigs_get_trajectory")) return rc;
   if(c->rigs.empty()) return BPVO_OK;
-  if(!poses && vo_trajectory_size(&c->rigs[0].body) > 0) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr poses");
-  vo_get_trajectory(&c->rigs[0].body, poses);
-  return BPVO_OK;
+  return bpvo_hip_rigs_get_trajectory(c, 0, poses);
 }
 int bpvo_hip_rigs_trajectory_size(bpvo_hip_ctx* c, int rig, int* n)
 {
@@ -917,251 +1013,21 @@ int bpvo_hip_rigs_get_trajectory(bpvo_hip_ctx* c, int rig, float* poses)
   return BPVO_OK;
 }
 
-// 1. every check of a call before any state changes; ids: the rigs it advances
-static int add_frames_rigs_check(bpvo_hip_ctx* c, int n, const int* rigs, const uint8_t* images, const float* disparities, bpvo_hip_result* results,
-                                 std::vector<int>& ids)
-{
-  const int R = (int) c->rigs.size();
-  if(n < 1 || n > R) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames_rigs: n must be within 1 .. the declared rigs");
-  if(!images || !disparities) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image/disparity");   // bpvo/vo.cc:68-69
-  if(!results) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
-  ids.assign((size_t) n, 0);
-  std::vector<char> seen((size_t) R, 0);
-  for(int i = 0; i < n; ++i) {
-    ids[i] = rigs ? rigs[i] : i;
-    CHECK_RIG(c, ids[i]);
-    if(seen[ids[i]]) return fail(c, BPVO_ERR_INVALID_ARG, ("rig " + std::to_string(ids[i]) + ": appears twice in one call").c_str());
-    seen[ids[i]] = 1;
-  }
-  const int L = c->L, lvl = c->params.maxTestLevel;
-  for(int i = 0; i < n; ++i)
-    for(int s : c->rigs[ids[i]].seq)
-      if(c->seqs[s].own_params) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "has parameters of its own: a rig runs its own (bpvo_hip_rigs_set_params) or the context's parameters");
-  if(c->dspace) return fail(c, BPVO_ERR_UNSUPPORTED, "rig mode does not serve BPVO_WARP_DISPARITY_SPACE_F32");
-  for(int i = 0; i < n; ++i) {
-    const RigState& g = c->rigs[ids[i]];
-    if(!c->frames[c->seqs[g.seq[0]].ref].has_template) continue;      // (its first frame)
-    for(int s : g.seq) {
-      const FrameSlot& ref = c->frames[c->seqs[s].ref];
-      for(int l = lvl; l < L; ++l)      // template_data.cc:177 (check_template_not_empty)
-        if(!ref.has_template || ref.n_host[l] <= 0)
-          return seq_fail(c, BPVO_ERR_NO_TEMPLATE, s, "the key frame's template is empty (you should call setData before calling computeResiduals)");
-    }
-  }
-  return BPVO_OK;
-}
-// entries of the call `which` (indices into ids) estimated in ONE estimate_rigs, each from T_init[k]; the poses to T_out[k], the statistics into the results
-static int rigs_estimate(bpvo_hip_ctx* c, const std::vector<int>& ids, const std::vector<int>& which, const std::vector<M44>& T_init, std::vector<M44>& T_out,
-                         bpvo_hip_result* results)
-{
-  const int m = (int) which.size();
-  std::vector<RigProblem> pr((size_t) m);
-  std::vector<std::vector<int>> refs((size_t) m), curs((size_t) m);
-  T_out.assign((size_t) m, m44_identity());
-  for(int k = 0; k < m; ++k) {
-    RigState& g = c->rigs[ids[which[k]]];
-    for(int s : g.seq) { refs[k].push_back(c->seqs[s].ref); curs[k].push_back(c->seqs[s].cur); }
-    pr[k] = RigProblem{(int) g.seq.size(), g.seq.data(), refs[k].data(), curs[k].data(), g.X.data(), T_init[k].m, T_out[k].m,
-                       results[which[k]].optimizerStatistics, g.body.own_params ? &g.body.params : nullptr};
-  }
-  return estimate_rigs(c, m, pr.data());
-}
-// option "pose_covariance": the body poses' records, from the members' states on the device — the existing one-record pass, rig by rig (its
-// launch takes ONE set of extrinsics for all its records: DESIGN.md section 5)
-static int rigs_covariance(bpvo_hip_ctx* c, const std::vector<int>& ids, const std::vector<int>& which)
-{
-  for(int e : which) {
-    RigState& g = c->rigs[ids[e]];
-    const int n = (int) g.seq.size();
-    std::vector<int> refs, curs;
-    for(int s : g.seq) { refs.push_back(c->seqs[s].ref); curs.push_back(c->seqs[s].cur); }
-    std::vector<const bpvo_hip_params*> prms((size_t) n, &g.body.params);
-    const int rc = pose_cov_pass(c, 1, n, g.seq.data(), refs.data(), curs.data(), g.X.data(), c->params.maxTestLevel, nullptr, nullptr,
-                                 g.body.own_params ? prms.data() : nullptr, &g.cov);
-    if(rc) return rc;
-  }
-  return BPVO_OK;
-}
-static int add_frames_rigs_run(bpvo_hip_ctx* c, int n, const std::vector<int>& ids, const uint8_t* images, const float* disparities, bool on_device,
-                               bpvo_hip_result* results)
-{
-  const bpvo_hip_params& p = c->params;
-  const int L = c->L, lvl = p.maxTestLevel;
-  (void) hipSetDevice(c->device);
-  int rc = seq_storage(c);
-  if(rc) return rc;
-  auto rig = [&](int i) -> RigState& { return c->rigs[ids[i]]; };
-  auto members_of = [&](int i) { std::vector<SeqState*> m; for(int s : rig(i).seq) m.push_back(&c->seqs[s]); return m; };
-  for(int i = 0; i < n; ++i) {
-    rig_param_target(c, rig(i));
-    vo_begin_frame(rig(i).body, L, results + i);
-    pose_cov_none(&rig(i).cov);
-    for(int s : rig(i).seq) { bpvo_hip_result own; vo_begin_frame(c->seqs[s], L, &own); }
-  }
-  auto drain = [&](int code) { (void) hipStreamSynchronize(c->stream); return code; };
-  auto template_stage = [&](const int* sl, int count, const size_t*, const FrameRun& fr) { return frames_set_template_slots(c, sl, count, fr); };
-
-  // 2. setData of every member of every rig: one data stage (its camera's pixels each, the frames back to back rig after rig, in member order)
-  std::vector<int> slots;
-  std::vector<size_t> offsets;
-  size_t at = 0;
-  for(int i = 0; i < n; ++i)
-    for(int s : rig(i).seq) {
-      slots.push_back(c->seqs[s].cur);
-      offsets.push_back(at);
-      at += slot_geom(c, c->frames[slots.back()], 0).npix;
-    }
-  rc = for_each_size(c, slots, &offsets, [&](const int* sl, int count, const size_t* off, const FrameRun& fr) {
-    return frames_set_data_slots(c, sl, count, images, disparities, on_device, fr, 0, off);
-  });
-  if(rc) return drain(rc);
-
-  // 3. the rigs at their first frame: every member's template in one stage
-  std::vector<int> est;      // entries of the call that estimate
-  slots.clear();
-  for(int i = 0; i < n; ++i) {
-    if(c->frames[c->seqs[rig(i).seq[0]].ref].has_template) { est.push_back(i); continue; }
-    for(int s : rig(i).seq) slots.push_back(vo_first_frame(c->seqs[s]));
-  }
-  if(!slots.empty()) {
-    rc = for_each_size(c, slots, nullptr, template_stage);
-    if(rc) return drain(rc);
-    for(int i = 0; i < n; ++i) {
-      if(std::find(est.begin(), est.end(), i) != est.end()) continue;
-      std::vector<SeqState*> mem = members_of(i);
-      vo_rig_first_frame_done(rig(i).body, mem.data(), (int) mem.size(), results + i);
-    }
-  }
-  const int m = (int) est.size();
-  if(m == 0) return BPVO_OK;
-
-  // 4. the body poses from every member's residuals, each from its body's T_kf: one estimate
-  std::vector<M44> T_init((size_t) m), T_est, T_again;
-  for(int k = 0; k < m; ++k) T_init[k] = rig(est[k]).body.T_kf;
-  rc = rigs_estimate(c, ids, est, T_init, T_est, results);
-  if(rc) return drain(rc);
-  if(c->pose_covariance) {
-    rc = rigs_covariance(c, ids, est);
-    if(rc) return rc;
-  }
-
-  // 5. one key-frame decision per rig: the body's motion, then the fraction of good points pooled over its members (one count launch for all)
-  bool own = false;
-  std::vector<int> first((size_t) m + 1, 0), n_points;
-  int max_n = 0;
-  for(int k = 0; k < m; ++k) {
-    const RigState& g = rig(est[k]);
-    own = own || g.body.own_params;
-    first[k + 1] = first[k] + (int) g.seq.size();
-  }
-  for(int k = 0; k < m; ++k) {
-    const RigState& g = rig(est[k]);
-    for(size_t i = 0; i < g.seq.size(); ++i) {
-      const SeqState& q = c->seqs[g.seq[i]];
-      PairJob& pj = c->h_seq_jobs[first[k] + (int) i];
-      pj = make_pair_job(c, g.seq[i], q.ref, q.cur, lvl);
-      if(own) pair_job_set_params(pj, g.body.params);
-      n_points.push_back(pj.n);
-      max_n = std::max(max_n, pj.n);
-    }
-  }
-  const int M = first[m];
-  HIP_CK(c, hipMemcpyAsync(c->d_seq_jobs, c->h_seq_jobs, sizeof(PairJob) * (size_t) M, hipMemcpyHostToDevice, c->stream));
-  HIP_CK(c, hipMemsetAsync(c->d_seq_cnt, 0, sizeof(unsigned) * (size_t) M, c->stream));
-  if(own) launch_count_good_jobs(c->stream, c->d_seq_jobs, M, max_n, c->C, c->d_seq_cnt);      // (each rig's loss and threshold, from its members' jobs)
-  else launch_count_good_batch(c->stream, c->d_seq_jobs, M, max_n, c->C, p.lossFunction, p.goodPointThreshold, c->d_seq_cnt);
-  HIP_CK(c, hipMemcpyAsync(c->h_seq_cnt, c->d_seq_cnt, sizeof(unsigned) * (size_t) M, hipMemcpyDeviceToHost, c->stream));
-  HIP_CK(c, hipStreamSynchronize(c->stream));
-  HIP_CK(c, hipGetLastError());
-  std::vector<int> kf;       // entries of est that key-frame
-  for(int k = 0; k < m; ++k) {
-    const RigState& g = rig(est[k]);
-    const float frac = vo_rig_fraction_good(c->h_seq_cnt + first[k], n_points.data() + first[k], (int) g.seq.size(), c->C);
-    if(vo_decide(g.body.params, T_est[k], frac, results + est[k])) kf.push_back(k);
-  }
-
-  // 6. the key frames: every member's point cloud from its old key frame and its last linearisation (one launch), the new templates (one stage),
-  // then ONE estimate against them of the rigs that had a previous frame
-  std::vector<int> re;       // entries of est that estimate again
-  if(!kf.empty()) {
-    const size_t cap = (size_t) c->geom[lvl].cap;
-    int max_c = 0, nj = 0;
-    for(int k : kf)
-      for(int j = first[k]; j < first[k + 1]; ++j)
-        if((size_t) n_points[j] > cap) return seq_fail(c, BPVO_ERR_INVALID_ARG, rig(est[k]).seq[j - first[k]], "size mismatch");
-    for(int k : kf) {
-      const RigState& g = rig(est[k]);
-      for(int j = first[k]; j < first[k + 1]; ++j, ++nj) {
-        const int s = g.seq[j - first[k]];
-        const FrameSlot& kfr = c->frames[c->seqs[s].ref];
-        CloudJob& cj = c->h_cloud_jobs[nj];
-        cj.job = c->d_seq_jobs + j; cj.img = kfr.img[0]; cj.out_offset = (size_t) s * cap;
-        std::memcpy(cj.K, slot_geom(c, kfr, lvl).K, sizeof(cj.K));
-        cj.rows = slot_geom(c, kfr, 0).rows; cj.cols = slot_geom(c, kfr, 0).cols;
-        cj.loss = g.body.params.lossFunction;
-        max_c = std::max(max_c, n_points[j]);
-      }
-    }
-    HIP_CK(c, hipMemcpyAsync(c->d_cloud_jobs, c->h_cloud_jobs, sizeof(CloudJob) * (size_t) nj, hipMemcpyHostToDevice, c->stream));
-    launch_point_cloud_batch(c->stream, c->d_cloud_jobs, nj, max_c, c->C, c->dspace, c->d_seq_cloud);
-    HIP_CK(c, hipGetLastError());
-    slots.clear();
-    for(int k : kf) {
-      std::vector<SeqState*> mem = members_of(est[k]);
-      const int nm = (int) mem.size();
-      std::vector<size_t> cloud_points((size_t) nm);
-      for(int i = 0; i < nm; ++i) cloud_points[i] = (size_t) n_points[first[k] + i];
-      std::vector<KeyFrameSlots> ks((size_t) nm);
-      vo_rig_keyframe(mem.data(), nm, c->frames[mem[0]->prev].has_data, cloud_points.data(), ks.data(), results + est[k]);
-      for(int i = 0; i < nm; ++i) {
-        if(ks[i].clear_slot >= 0) slot_clear(c, ks[i].clear_slot);
-        slots.push_back(ks[i].template_slot);
-      }
-      if(ks[0].reestimate) re.push_back(k);
-    }
-    rc = for_each_size(c, slots, nullptr, template_stage);
-    if(rc) return drain(rc);
-    if(!re.empty()) {
-      std::vector<int> which;
-      for(int k : re) which.push_back(est[k]);
-      rc = rigs_estimate(c, ids, which, std::vector<M44>(re.size(), m44_identity()), T_again, results);
-      if(rc) return drain(rc);
-      if(c->pose_covariance) {
-        rc = rigs_covariance(c, ids, which);
-        if(rc) return rc;
-      }
-    }
-  }
-
-  // 7. per rig: the pose, T_kf and the trajectory of the body; every member's slots, and its cloud's pose
-  std::vector<int> again_of((size_t) m, -1);
-  for(size_t t = 0; t < re.size(); ++t) again_of[re[t]] = (int) t;
-  for(int k = 0; k < m; ++k) {
-    RigState& g = rig(est[k]);
-    std::vector<SeqState*> mem = members_of(est[k]);
-    vo_rig_finish(g.body, mem.data(), g.X.data(), (int) mem.size(), T_est[k], again_of[k] >= 0 ? &T_again[again_of[k]] : nullptr, results + est[k]);
-    if(c->pose_covariance) std::memcpy(results[est[k]].covariance, g.cov.covariance, sizeof(results[est[k]].covariance));
-  }
-  return BPVO_OK;
-}
 int bpvo_hip_add_frames_rigs(bpvo_hip_ctx* c, int n, const int* rigs, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* results)
 {
   CHECK_CTX(c);
   if(c->rigs.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames_rigs: the context declares no rig (bpvo_hip_rigs_set)");
   std::vector<int> ids;
-  const int rc = add_frames_rigs_check(c, n, rigs, images, disparities, results, ids);
+  const int rc = add_frames_check(c, true, n, rigs, images, disparities, "nullptr image/disparity", results, ids);
   if(rc) return rc;
-  return add_frames_rigs_run(c, n, ids, images, disparities, on_device != 0, results);
+  return add_frames_run(c, true, ids, images, disparities, on_device != 0, results);
 }
 int bpvo_hip_add_frames_rig(bpvo_hip_ctx* c, const uint8_t* images, const float* disparities, int on_device, bpvo_hip_result* result)
 {
   CHECK_CTX(c);
   if(c->rigs.empty()) return fail(c, BPVO_ERR_INVALID_ARG, "add_frames_rig: the context declares no rig (bpvo_hip_rig_set)");
   if(int rc = rig_is_singular(c, "bpvo_hip_add_frames_rigs")) return rc;
-  std::vector<int> ids;
-  const int rc = add_frames_rigs_check(c, 1, nullptr, images, disparities, result, ids);
-  if(rc) return rc;
-  return add_frames_rigs_run(c, 1, ids, images, disparities, on_device != 0, result);
+  return bpvo_hip_add_frames_rigs(c, 1, nullptr, images, disparities, on_device, result);
 }
 // StereoAlgorithm::run + addFrame of every sequence of the call (apps/vo_app.cc per camera): the front-end once over all the pairs, each in
 // its sequence's camera geometry, into the context's own maps, which the frame stages then read where they lie — no host synchronisation
@@ -1171,7 +1037,7 @@ int bpvo_hip_add_frames_stereo(bpvo_hip_ctx* c, int n, const int* seq, const uin
 {
   CHECK_CTX(c);
   std::vector<int> ids;
-  int rc = add_frames_check(c, n, seq, left, right, "nullptr image", results, ids);
+  int rc = add_frames_check(c, false, n, seq, left, right, "nullptr image", results, ids);
   if(rc) return rc;
   std::vector<StereoSize> sz((size_t) n);
   for(int i = 0; i < n; ++i) {
@@ -1184,7 +1050,7 @@ int bpvo_hip_add_frames_stereo(bpvo_hip_ctx* c, int n, const int* seq, const uin
   const uint8_t* d_left = nullptr;
   rc = stereo_run_sizes(c, n, sz.data(), left, right, on_device != 0, sp, &d_left);
   if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
-  return add_frames_run(c, n, ids, d_left, c->st_disp, true, results);
+  return add_frames_run(c, false, ids, d_left, c->st_disp, true, results);
 }
 int bpvo_hip_stereo_frames(bpvo_hip_ctx* c, int n, const bpvo_hip_camera* cams, const uint8_t* left, const uint8_t* right, int on_device,
                            const bpvo_hip_stereo_params* sp, float* disparity, int disparity_on_device)

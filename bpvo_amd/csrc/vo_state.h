@@ -1,6 +1,8 @@
-// libbpvo_hip, host side: the state machine of VisualOdometry::addFrame (reference: bpvo/vo.cc:125-224) for bpvo_hip_add_frame and for every
-// sequence of bpvo_hip_add_frames.  No HIP header: the drivers (vo.hip) queue the GPU work and keep the frame slots' flags; every decision and
-// every change of a SeqState is made here, once, for both (tests/test_vo_state_cpu.py compiles this header with a plain C++ compiler).
+// libbpvo_hip, host side: the state machine of VisualOdometry::addFrame (reference: bpvo/vo.cc:125-224) for bpvo_hip_add_frame, for every
+// sequence of bpvo_hip_add_frames and for every rig of bpvo_hip_add_frames_rig(s).  No HIP header: the two drivers (vo.hip: add_frame_impl, the
+// single-sequence latency path, and add_frames_run, the one batched driver of sequences and rigs) queue the GPU work and keep the frame slots'
+// flags; every decision and every change of a SeqState is made here, once, for all (tests/test_vo_state_cpu.py and tests/test_rig_cpu.py
+// compile this header with a plain C++ compiler).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -150,19 +152,29 @@ inline void vo_finish(SeqState& q, const M44& T_est, const M44* T_again, bpvo_hi
   if(ret->hasPointCloud) q.cloud_pose = q.trajectory.back();
 }
 
-// ---- rig mode (bpvo_hip_add_frames_rig): the cameras of a rigid rig advance in lock step as ONE body.  The body's SeqState keeps T_kf and the
-// trajectory (its slot roles are unused); every member takes the same transition on its own slots.  X: the extrinsics [n][16], camera_from_body.
-// One declared rig (bpvo_hip_ctx::rigs): its members' sequence ids and extrinsics [n][16], the body — T_kf, the trajectory and the RIG's algorithm
-// parameters (SeqState::params / own_params: bpvo_hip_rigs_set_params; the context's until then) — and the pose-covariance record of its last frame
+// ---- a body that moves as one: what the batched driver (vo.hip: add_frames_run) advances.  A rig (bpvo_hip_add_frames_rig(s)) is a body of n
+// cameras that advance in lock step: the body's SeqState keeps T_kf, the trajectory and the RIG's parameters (its slot roles are unused), every
+// member takes the same transition on its own slots; X: the extrinsics [n][16], camera_from_body.  A sequence of bpvo_hip_add_frames is a body of
+// ONE member that IS the body (members[0] == &body) and has no extrinsics: X null.  A member that is the body is advanced by the body's own
+// call and by nothing else, so in that form every vo_rig_* below performs exactly the plain vo_* call above it on that one state — no second
+// state, no copy of the result, no float the plain call does not compute, X never read.
+// One declared rig (bpvo_hip_ctx::rigs): its members' sequence ids and extrinsics, the body, and the pose-covariance record of its last frame
 struct RigState {
   std::vector<int> seq;
   std::vector<float> X;
   SeqState body;
   bpvo_hip_pose_covariance cov;
 };
-// The fraction of good points of the rig's one decision: pooled over the members, sum good_p / sum n_p C (one member: vo_fraction_good)
+inline void vo_rig_begin_frame(SeqState& body, SeqState* const* members, int n, int numLevels, bpvo_hip_result* ret)
+{
+  vo_begin_frame(body, numLevels, ret);
+  for(int p = 0; p < n; ++p)
+    if(members[p] != &body) { bpvo_hip_result own; vo_begin_frame(*members[p], numLevels, &own); }
+}
+// The fraction of good points of the body's one decision: pooled over the members, sum good_p / sum n_p C (one member: vo_fraction_good itself)
 inline float vo_rig_fraction_good(const unsigned* good_counts, const int* n_points, int n, int C)
 {
+  if(n == 1) return vo_fraction_good(good_counts[0], n_points[0], C);
   size_t good = 0, total = 0;
   for(int p = 0; p < n; ++p) { good += good_counts[p]; total += (size_t) n_points[p] * C; }
   return good / static_cast<float>(total);
@@ -170,19 +182,16 @@ inline float vo_rig_fraction_good(const unsigned* good_counts, const int* n_poin
 // the first frame of every member, then of the body (each member's template is queued between vo_first_frame and this)
 inline void vo_rig_first_frame_done(SeqState& body, SeqState* const* members, int n, bpvo_hip_result* ret)
 {
-  for(int p = 0; p < n; ++p) {
-    bpvo_hip_result own = *ret;
-    vo_first_frame_done(*members[p], &own);
-  }
+  for(int p = 0; p < n; ++p)
+    if(members[p] != &body) { bpvo_hip_result own = *ret; vo_first_frame_done(*members[p], &own); }
   vo_first_frame_done(body, ret);
 }
-// the rig's decision (vo_decide on the body pose with the pooled fraction) was "key frame": vo_keyframe of every member, slots[p] what its caller does
+// the body's decision (vo_decide on the body pose with the pooled fraction) was "key frame": vo_keyframe of every member, slots[p] what its caller
+// does (one member: vo_keyframe itself, on the body's result — all it writes there is hasPointCloud)
 inline void vo_rig_keyframe(SeqState* const* members, int n, bool prev_has_data, const size_t* cloud_points, KeyFrameSlots* slots, bpvo_hip_result* ret)
 {
-  for(int p = 0; p < n; ++p) {
-    bpvo_hip_result own = *ret;
-    slots[p] = vo_keyframe(*members[p], prev_has_data, cloud_points[p], &own);
-  }
+  if(n == 1) { slots[0] = vo_keyframe(*members[0], prev_has_data, cloud_points[0], ret); return; }
+  for(int p = 0; p < n; ++p) { bpvo_hip_result own = *ret; slots[p] = vo_keyframe(*members[p], prev_has_data, cloud_points[p], &own); }
   ret->hasPointCloud = 1;
 }
 // vo_finish of the body with the body's estimates and of every member with its own, X_p T X_p^-1; a member's point cloud gets the pose
@@ -190,8 +199,9 @@ inline void vo_rig_keyframe(SeqState* const* members, int n, bool prev_has_data,
 inline void vo_rig_finish(SeqState& body, SeqState* const* members, const float* X, int n, const M44& T_est, const M44* T_again, bpvo_hip_result* ret)
 {
   vo_finish(body, T_est, T_again, ret);
-  if(ret->hasPointCloud) body.cloud_n = 0;      // (the clouds are the members')
   for(int p = 0; p < n; ++p) {
+    if(members[p] == &body) continue;
+    if(ret->hasPointCloud) body.cloud_n = 0;      // (the clouds are the members')
     const float* Xp = X + 16 * (size_t) p;
     M44 Tp, Tpa;
     rig_member_pose(Xp, T_est.m, Tp.m);

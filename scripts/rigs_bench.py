@@ -70,8 +70,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--frames", type=int, default=12)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rigs_bench.json"))
+    ap.add_argument("--lib", default="", help="another build of libbpvo_hip.so (A/B runs against an earlier commit's library)")
     a = ap.parse_args()
-    hip = bpvo_amd.load()
+    hip = capi.Binding(os.path.abspath(a.lib), "bpvo_hip_") if a.lib else bpvo_amd.load()
     seq = synth.make_rig_sequence(ROWS, COLS, a.frames, rig_extrinsics(CAMERAS), index=0)
     calls = packed(seq)
     rows = []

@@ -240,6 +240,35 @@ def test_one_sequence_equals_add_frame(hip):
     lockstep(hip, K, base, rows, cols, p, seqs)
 
 
+def test_every_branch_of_the_driver_in_one_call(hip):
+    """addframes_scenarios.py's one call: a first frame, no key frame, a key frame without and a key frame with re-estimation, two sequences
+    with parameters of their own and different losses (two estimates in the call), one camera of the other size, option "pose_covariance" on.
+    Every sequence, over all its frames, against bpvo_hip_add_frame in a context of its own camera and parameters, no tolerance: pose,
+    covariance and its record, every level's statistics, the key-frame flags, the point counts of every level, the point clouds' bytes and
+    poses, the trajectory."""
+    import addframes_scenarios as sc
+    from test_gpu_rigs import assert_same_frames
+    cams, frames, params, _, own = sc.one_call_setup(hip)
+    assert own[1].lossFunction != own[3].lossFunction and (cams[2][2], cams[2][3]) != (cams[0][2], cams[0][3])
+    recs, trajs = sc.run_one_call(hip)
+    last = [r[-1]["res"] for r in recs]
+    before = [r[-2]["res"] if len(r) > 1 else None for r in recs]
+    first, none, swap, again = (sc.ROLES.index(x) for x in sc.ROLES)
+    assert len(recs[first]) == 1 and last[first]["keyFramingReason"] == capi.KF_FIRST_FRAME, "no first frame in the call"
+    assert not last[none]["isKeyFrame"], "the sequence that should take no key frame took one"
+    assert last[swap]["isKeyFrame"] and before[swap]["isKeyFrame"] and last[swap]["hasPointCloud"], "no key frame without re-estimation in the call"
+    assert last[again]["isKeyFrame"] and not before[again]["isKeyFrame"] and last[again]["hasPointCloud"], "no key frame with re-estimation in the call"
+    assert all(len(recs[s]) == sc.ONE_CALL + 1 for s in (none, swap, again))
+    for s in range(4):
+        want, traj = sc.run_alone(hip, cams[s], frames[s][:len(recs[s])], params[s])
+        assert_same_frames(recs[s], want, f"sequence {s} ({sc.ROLES[s]})")
+        for k, (a, b) in enumerate(zip(recs[s], want)):
+            for (pa, _), (pb, _) in zip(a["clouds"] or [], b["clouds"] or []):
+                assert np.array_equal(pa.view(np.uint8), pb.view(np.uint8)), (s, k, "point cloud bytes")
+        assert bits_equal(trajs[s], traj), (s, "trajectory")
+        assert all(x["cov"]["status"] != capi.COV_NONE for x in recs[s][1:]), (s, "no covariance record")
+
+
 def test_errors_change_no_sequence(hip):
     rows, cols, levels = 120, 160, 3
     S = 4

@@ -1,8 +1,9 @@
 """Rig mode without a GPU: the maps of bpvo_amd/csrc/rig_math.h (Ad(X), A_p, A_p^-1, B_p = A_p^-1 Ad(X_p), the congruence B^T H B / B^T G, the
 member pose X T X^-1) against numpy float64, the two identities the maps rest on — X exp(zeta) X^-1 = exp(Ad(X) zeta) and
 N^-1 exp(xi) N = exp(A xi) — checked numerically with the project's own SE(3) exponential (independently of the code under test), and the rig
-additions to bpvo_amd/csrc/vo_state.h: the pooled fraction of good points, one key-frame decision applied to every member, cloud poses
-W_kf X_p^-1.  tests/cpp/rig_harness.cc includes only the two headers and is compiled by the host's C++ compiler."""
+additions to bpvo_amd/csrc/vo_state.h (the transitions of a body, vo_rig_*): the pooled fraction of good points, one key-frame decision applied to
+every member, cloud poses W_kf X_p^-1 — and, with null extrinsics, exactly the plain vo_* calls on one state, which is how the batched driver
+advances a sequence.  tests/cpp/rig_harness.cc includes only the two headers and is compiled by the host's C++ compiler."""
 import ctypes as C
 import os
 import subprocess
@@ -30,6 +31,10 @@ def harness(tmp_path_factory):
     lib.rg_fraction_good.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     lib.rg_fraction_good_one.restype = C.c_float
     lib.rg_fraction_good_one.argtypes = [C.c_uint, C.c_int, C.c_int]
+    lib.rg_fraction_good_null.restype = C.c_float
+    lib.rg_fraction_good_null.argtypes = [C.c_uint, C.c_int, C.c_int]
+    lib.rg_plain_add_frame.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.rg_state_bytes.argtypes = [C.c_int, C.c_void_p, C.c_int]
     lib.rg_add_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                  C.c_void_p, C.c_void_p]
     lib.rg_state.argtypes = [C.c_int] + [C.c_void_p] * 4
@@ -207,7 +212,7 @@ class Rig:
         good = (n_points * Cn * 9 // 10).astype(np.uint32) if good is None else np.asarray(good, np.uint32)
         cloud = np.asarray(n_points, np.uint64)
         T_again = pose() if T_again is None else T_again
-        self.lib.rg_add_frame(C.byref(self.p), L, self.n, _p(self.X), _p(f32(T_est)), _p(f32(T_again)), _p(good), _p(n_points), Cn, _p(cloud),
+        self.lib.rg_add_frame(C.byref(self.p), L, self.n, None if self.X is None else _p(self.X), _p(f32(T_est)), _p(f32(T_again)), _p(good), _p(n_points), Cn, _p(cloud),
                               C.byref(ret), _p(out))
         return ret, out
 
@@ -273,6 +278,39 @@ def test_a_rig_of_one_at_the_origin_is_the_single_state_machine(harness):
         b, m = rig.state(-1), rig.state(0)
         for k in ("T_kf", "back", "length", "cloud_pose"):
             assert np.array_equal(b[k], m[k]), k
+
+
+def test_null_extrinsics_are_the_plain_calls_on_one_state(harness):
+    """What the batched driver does to a sequence — the transitions of a body with null extrinsics, the body its own member — against the plain
+    vo_* calls in add_frame_impl's order, over every branch: first frame, no key frame, key frame with re-estimation (the previous slot holds
+    data), key frame without (that key frame cleared it), and the decision left to the fraction of good points.  After every frame the whole
+    SeqState (roles, T_kf, trajectory, cloud_n, cloud_pose) and the whole bpvo_hip_result are byte-identical."""
+    rig = Rig(harness, [np.eye(4)])
+    rig.X = None
+    small, far = pose(0.01, t=(0.01, 0, 0.02)), pose(0.0, t=(0.3, 0, 0))
+    Ta = pose(0.002, t=(0.002, 0.0, 0.005))
+    # (T_est, T_again, good, n_points, C)
+    series = [(pose(), Ta, 720, 100, 8), (small, Ta, 720, 100, 8), (far, Ta, 720, 100, 8), (far, Ta, 720, 100, 8), (small, Ta, 90, 100, 1),
+              (pose(0.02), Ta, 400, 100, 8), (pose(0.3), Ta, 0, 7, 1)]
+    branches = []
+    for T, T2, good, n_points, Cn in series:
+        ret, out = rig.add(T, T_again=T2, good=[good], n_points=[n_points], Cn=Cn)
+        want, wout = capi.Result(), np.full(6, -7, np.int32)
+        harness.rg_plain_add_frame(C.byref(rig.p), L, _p(f32(T)), _p(f32(T2)), good, n_points, Cn, n_points, C.byref(want), _p(wout))
+        assert bytes(ret) == bytes(want), (len(branches), "result")
+        assert out[0].tolist() == wout.tolist(), (len(branches), out, wout)
+        a, b = np.zeros(4096, np.uint8), np.zeros(4096, np.uint8)
+        na, nb = harness.rg_state_bytes(0, _p(a), a.size), harness.rg_state_bytes(1, _p(b), b.size)
+        assert na == nb > 0 and a[:na].tobytes() == b[:nb].tobytes(), (len(branches), "SeqState")
+        branches.append("first" if ret.keyFramingReason == capi.KF_FIRST_FRAME else "none" if not ret.isKeyFrame else "again" if out[0][5] else "swap")
+        assert bool(ret.hasPointCloud) == (branches[-1] in ("again", "swap"))
+    assert branches == ["first", "none", "again", "swap", "none", "again", "swap"], branches
+    # the fraction of good points: the single form's float for every count an unsigned holds
+    for good in (0, 1, 3, 2**24 - 1, 2**24 + 1, 2**31 - 1, 2**31, 2**31 + 129, 2**32 - 2, 2**32 - 1):
+        for n_points, Cn in ((1, 1), (100, 8), (2**29, 8), (2**31 - 1, 1), (2**31 - 1, 8)):
+            a = np.float32(harness.rg_fraction_good_null(good, n_points, Cn))
+            b = np.float32(harness.rg_fraction_good_one(good, n_points, Cn))
+            assert a.tobytes() == b.tobytes(), (good, n_points, Cn, a, b)
 
 
 def test_rig_visual_odometry_compiles_as_cpp11():
