@@ -109,10 +109,10 @@ FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l)
   std::memset(&j, 0, sizeof(j));
   j.img = f.img[l];
   j.cen = f.cen[l];
-  j.ch0 = f.ch0_valid ? f.ch0[l] : nullptr;
+  j.ch0 = (f.ch0_valid && f.lazy[l] != 2) ? f.ch0[l] : nullptr;      // (a census-only level has no channel-0 plane)
   j.scratch = f.scratch;
   j.desc = f.desc[l];
-  j.sal = f.sal[l];
+  j.sal = f.sal_state[l] == FrameSlot::SAL_STORED ? f.sal[l] : nullptr;      // (null: the selection does not store the map)
   j.flag = f.flag[l];
   j.words = reinterpret_cast<unsigned long long*>(f.flag[l]);
   j.blk_count = f.blk_count[l];
@@ -130,7 +130,7 @@ FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l)
   std::memcpy(j.K, g.K, sizeof(j.K));
   j.b = g.b;
   j.dspace = c->dspace;
-  j.lazy = f.lazy[l] ? 1 : 0;
+  j.lazy = f.lazy[l];
   // the selection thresholds: those of the slot's sequence (bpvo_hip_seq_set_params), or the context's
   const bpvo_hip_params& sp = f.seq_params ? *f.seq_params : c->params;
   j.min_saliency = sp.minSaliency; j.min_disp = sp.minValidDisparity; j.max_disp = sp.maxValidDisparity;
@@ -343,6 +343,7 @@ const std::vector<OptionDef>& option_table()
                 return BPVO_OK;
               }},
     OPT_INT("lazy_template_descriptor", lazy_template, 0, 1),
+    OPT_INT("lazy_template_saliency", lazy_saliency, 0, 1),
     OPT_INT("points_from_compact_stream", points_from_compact, 0, 1),
     OptionDef{"tapcache_max_density", 0.0, 1e9, [](bpvo_hip_ctx* c) { return c->tapcache_max_density; },
               [](bpvo_hip_ctx* c, double v) { c->tapcache_max_density = v; return BPVO_OK; }},

@@ -76,8 +76,20 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
   // fused into the blur kernel, CD3 gradients.  Every other frame, and every frame set through the frame API, is dense.
   const bool lazy_ok = skip_odd_disp != 0 && c->lazy_template && c->params.descriptor == BPVO_DESC_BITPLANES && c->C == 8 &&
                        !(c->params.sigmaPriorToCensusTransform > 0.0f) && c->params.sigmaBitPlanes > 0.0f && c->params.gradientEstimation == BPVO_GRAD_CD3;
-  for(int i = 0; i < count; ++i)
-    for(int l = 0; l < c->L; ++l) c->frames[slots[i]].lazy[l] = lazy_ok && !(i & 1) && geom[l].nms_radius > 0;
+  // ... and not even channel 0 where the tiled selection (NMS radius 1) forms it from the census bytes (option lazy_template_saliency):
+  // census_templates_kernel writes those, and the blur below runs over the dense tile columns of such a level only
+  const bool census_only_ok = lazy_ok && c->lazy_saliency;
+  bool census_only[kMaxLevels] = {};
+  bool any_census_only = false;
+  for(int l = c->params.maxTestLevel; l < c->L; ++l) any_census_only |= census_only[l] = census_only_ok && geom[l].nms_radius == 1;
+  for(int i = 0; i < count; ++i) {
+    FrameSlot& f = c->frames[slots[i]];
+    for(int l = 0; l < c->L; ++l) {
+      f.lazy[l] = (lazy_ok && !(i & 1) && geom[l].nms_radius > 0) ? (census_only[l] ? 2 : 1) : 0;
+      // a saliency map that would have been formed on demand from the data replaced here can no longer be (until the next template)
+      if(f.sal_state[l] == FrameSlot::SAL_ON_DEMAND) f.sal_state[l] = FrameSlot::SAL_GONE;
+    }
+  }
   const FrameJob* tab = nullptr;
   int rc = upload_frame_jobs_slots(c, slots, count, fr, 0, &tab);
   if(rc) return rc;
@@ -121,6 +133,7 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
     const bool plain_intensity = c->C == 1 && c->params.descriptor != BPVO_DESC_LAPLACIAN;
     const bool one_launch = (fused_bp || smoothed_bp || plain_intensity) && count <= c->merge_levels_max_frames && c->L - l_lo > 1;
     if(one_launch && fused_bp) {
+      if(any_census_only) launch_census_templates(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->L - l_lo, NF);
       launch_bitplanes(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->params.sigmaBitPlanes, c->gauss_k, 1, c->L - l_lo, NF);
     } else if(one_launch && smoothed_bp) {
       launch_census(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->census_taps, c->L - l_lo, NF);
@@ -146,6 +159,11 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
       } else {
         // census fused into the bit-planes kernel unless the census is taken of the smoothed image or the planes stay unsmoothed
         const bool fused_census = !(c->params.sigmaPriorToCensusTransform > 0.0f) && c->params.sigmaBitPlanes > 0.0f;
+        if(census_only[l]) {      // (implies the fused census)
+          launch_census_templates(s, jobs, g.cols, g.rows, count);
+          launch_bitplanes_pairs(s, jobs, g.cols, g.rows, count, c->gauss_k);
+          continue;
+        }
         if(!fused_census)
           launch_census(s, jobs, g.cols, g.rows, count, c->params.sigmaPriorToCensusTransform > 0.0f ? c->census_taps : nullptr);
         launch_bitplanes(s, jobs, g.cols, g.rows, count, c->params.sigmaBitPlanes, c->gauss_k, fused_census ? 1 : 0);
@@ -208,6 +226,11 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
     FR_CK(c, fr, hipMemsetAsync(f.tmpl_slab, 0, total, s));
     carve_frame_tmpl(c, f, (unsigned char*) f.tmpl_slab, nullptr);
   }
+  // the saliency map of a census-only level is not stored: whoever reads it has it formed first (ensure_saliency)
+  for(int i = 0; i < count; ++i) {
+    FrameSlot& f = c->frames[slots[i]];
+    for(int l = 0; l < c->L; ++l) f.sal_state[l] = f.lazy[l] == 2 ? FrameSlot::SAL_ON_DEMAND : FrameSlot::SAL_STORED;
+  }
   const FrameJob* tab = nullptr;
   int rc = upload_frame_jobs_slots(c, slots, count, fr, 1, &tab);
   if(rc) return rc;
@@ -246,14 +269,14 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
     for(int l = p.maxTestLevel; l < c->L; ++l) px += (double) geom[l].npix * count;
     ScopedTimer t(c, KC_SALIENCY_SELECT, px, fr.ln);
     const LevelGeom& g = geom[p.maxTestLevel];
-    launch_saliency_select(s, tab + (size_t) p.maxTestLevel * NF, c->C, g.cols, g.rows, count, 1, border,
+    launch_saliency_select(s, tab + (size_t) p.maxTestLevel * NF, c->C, g.cols, g.rows, count, 1, border, c->gauss_k,
                            c->L - p.maxTestLevel, NF);
   }
   for(int l = c->L - 1; l >= p.maxTestLevel && !one_launch; --l) {
     const FrameJob* jobs = tab + (size_t) l * NF;
     const LevelGeom& g = geom[l];
     ScopedTimer t(c, KC_SALIENCY_SELECT, (double) g.npix * count, fr.ln);
-    launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, border);
+    launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, border, c->gauss_k);
   }
   if(side) {
     FR_CK(c, fr, hipEventRecord(c->side_ev[0], s));
@@ -362,8 +385,8 @@ int ensure_dense_descriptor(bpvo_hip_ctx* c, int slot)
   if(!any) return BPVO_OK;
   // The job table is built from the flags, so they are cleared for it and put back if anything fails: the slot counts as dense
   // only once the kernels that fill its records have run.
-  bool was[kMaxLevels];
-  for(int l = 0; l < c->L; ++l) { was[l] = f.lazy[l]; f.lazy[l] = false; }
+  uint8_t was[kMaxLevels];
+  for(int l = 0; l < c->L; ++l) { was[l] = f.lazy[l]; f.lazy[l] = 0; }
   auto restore = [&]() { for(int l = 0; l < c->L; ++l) f.lazy[l] = was[l]; };
   const FrameRun fr = ctx_run(c);
   const FrameJob* tab = nullptr;
@@ -376,6 +399,29 @@ int ensure_dense_descriptor(bpvo_hip_ctx* c, int slot)
     return fail(c, BPVO_ERR_DEVICE, "ensure_dense_descriptor: descriptor kernels failed");
   }
   return BPVO_OK;
+}
+
+
+// The saliency map of a level whose selection did not store it (FrameSlot::sal_state; template frames of a pair batch): the slot's dense
+// records first, then the saliency kernel of the untiled selection — the closed form the tiles evaluate, value for value.
+int ensure_saliency(bpvo_hip_ctx* c, int slot, int level)
+{
+  FrameSlot& f = c->frames[slot];
+  if(f.sal_state[level] == FrameSlot::SAL_STORED) return BPVO_OK;
+  if(f.sal_state[level] == FrameSlot::SAL_GONE)
+    return fail(c, BPVO_ERR_NO_DATA, "the saliency map of a pair batch's template frame is formed on demand from the frame's data, which has been replaced");
+  if(int rc = ensure_dense_descriptor(c, slot)) return rc;
+  f.sal_state[level] = FrameSlot::SAL_STORED;      // (the job table is built from the state: the job carries the map's address)
+  const FrameRun fr = ctx_run(c);
+  const FrameJob* tab = nullptr;
+  int rc = upload_frame_jobs(c, slot, 1, 1, fr, 1, &tab);
+  if(rc == BPVO_OK) {
+    const LevelGeom& g = slot_geom(c, f, level);
+    launch_saliency(c->stream, tab + (size_t) level * c->n_frames, c->C, g.cols, g.rows, 1);
+    if(hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, BPVO_ERR_DEVICE, "ensure_saliency: saliency kernel failed");
+  }
+  if(rc) f.sal_state[level] = FrameSlot::SAL_ON_DEMAND;
+  return rc;
 }
 
 }  // namespace bpvo_hip_host
@@ -470,6 +516,7 @@ int bpvo_hip_get_saliency(bpvo_hip_ctx* c, int slot, int level, float* out)
   CHECK_CTX(c); CHECK_SLOT(c, slot); CHECK_LEVEL(c, level);
   if(!c->frames[slot].has_template) return fail(c, BPVO_ERR_NO_TEMPLATE, "no template");
   (void) hipSetDevice(c->device);
+  if(int rc = ensure_saliency(c, slot, level)) return rc;      // (a template frame of a pair batch: its selection stored no map)
   HIP_CK(c, hipMemcpyAsync(out, c->frames[slot].sal[level], c->geom[level].npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_CK(c, hipStreamSynchronize(c->stream));
   return BPVO_OK;

@@ -63,7 +63,11 @@ struct FrameSlot {
   uint8_t* img[kMaxLevels] = {};
   uint8_t* cen[kMaxLevels] = {};
   float* ch0[kMaxLevels] = {};
-  bool lazy[kMaxLevels] = {};     // levels whose descriptor records were not stored (FrameJob::lazy): census bytes + channel 0 only
+  uint8_t lazy[kMaxLevels] = {};  // levels whose descriptor records were not stored (FrameJob::lazy): 1 = census bytes + channel 0, 2 = census bytes only
+  // the saliency map of a level: kept by the selection (SAL_STORED), formed on demand from the slot's data (SAL_ON_DEMAND: template frames of a pair
+  // batch, option lazy_template_saliency; ensure_saliency), or gone because the data such a template was made of has been replaced (SAL_GONE)
+  enum : uint8_t { SAL_STORED = 0, SAL_ON_DEMAND = 1, SAL_GONE = 2 };
+  uint8_t sal_state[kMaxLevels] = {};
   bool ch0_valid = true;          // false: the descriptor of the slot's current data was computed without the compact channel-0 plane
   float* desc[kMaxLevels] = {};
   float* disp = nullptr;
@@ -347,6 +351,9 @@ struct bpvo_hip_ctx {
   int points_from_compact = 0;           // option "points_from_compact_stream" (debug): bpvo_hip_get_points returns load_point's rebuilt points
   int lazy_template = 1;                 // option "lazy_template_descriptor": the template frames (A) of a pair batch keep census bytes + channel 0 at the NMS
                                          // levels instead of 32-byte records nobody reads (bit-planes, CD3); template_build forms its stencils from the census
+  int lazy_saliency = 1;                 // option "lazy_template_saliency" (needs lazy_template_descriptor): such levels keep the census bytes ONLY — census_kernel
+                                         // writes them, the blur runs over the dense tile columns alone, the tiled selection forms channel 0 of its windows from
+                                         // the census bytes and does not store the saliency map (bpvo_hip_get_saliency forms it on demand)
   int keep_current_disparity = 0;        // option: pair batches store the disparity of the CURRENT frames (B) too, so that a B slot can be made
                                          // a template later (frames_set_template); off by default: 1.9 GB per 1024-pair step never read
   double up_last_seconds = 0.0;          // wall time the workers of the last call needed for all chunks (measurement)
@@ -585,6 +592,7 @@ int get_weights_host(bpvo_hip_ctx* c, int ws, std::vector<float>& w_cm, int* n_o
 int check_template_not_empty(bpvo_hip_ctx* c, int ref_slot);
 int ensure_lanes(bpvo_hip_ctx* c, int n);
 int lanes_for(bpvo_hip_ctx* c, int n, int cap);
+int ensure_saliency(bpvo_hip_ctx* c, int slot, int level);      // a level whose saliency map the selection did not store gets it (every reader of FrameSlot::sal)
 int ensure_dense_descriptor(bpvo_hip_ctx* c, int slot);      // a slot with lazy levels gets its full records (accessors, a template frame used as current)
 // Pose covariance (pose_cov.hip): n_records records of `members` members each — member p of record r is entry r * members + p of wss / refs / curs
 // (and of sigma; prms: each entry's own parameters or null) —, X null (cameras) or [members][16] (a rig: one record), T [n_records][16] and sigma

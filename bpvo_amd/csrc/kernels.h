@@ -71,13 +71,20 @@ void launch_latch(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes
                   const GaussTaps& after);   // C = 8 * bytes, bytes = 1 / 2 / 4
 void launch_laplacian(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int ksize /*1 or 3*/);
 void launch_census(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, const int* blur_taps /*null: no smoothing*/, int nlevels = 1, int job_pitch = 0);
+// one level of a pair batch (jobs A, B, A, B, ...) with census-only template frames: B over every tile, A over the dense tile columns only
+void launch_bitplanes_pairs(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, const float k[3]);
+// the census bytes of the census-only levels (FrameJob::lazy == 2) among jobs 0, 2, 4, ... — the template frames of a pair batch; other jobs are left alone
+void launch_census_templates(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int nlevels = 1, int job_pitch = 0);
 // from_image: the census transform is computed inside the bit-planes kernel (no launch_census, sigma_bp > 0 and sigma_ct <= 0)
 // nlevels > 1 (bit-planes, tiled selection, template build): `jobs` is the FINEST level's row of the table [level][job_pitch], W / R / max_points that level's — the
 // levels in one launch (kernels_frame.hip level_job)
 void launch_bitplanes(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, float sigma, const float k[3], int from_image, int nlevels = 1,
                       int job_pitch = 0);
 // (minSaliency and the disparity gate: each frame's own, FrameJob::min_saliency / min_disp / max_disp)
-void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, int nlevels = 1, int job_pitch = 0);
+// gauss_k: the bit-planes blur taps (census-only levels, FrameJob::lazy == 2: the tiles form channel 0 themselves)
+void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, const float gauss_k[3], int nlevels = 1,
+                            int job_pitch = 0);
+void launch_saliency(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes);      // the saliency map alone, from dense records
 void launch_copy_rows(hipStream_t s, void* dst, const void* src_host_pinned, size_t pitch_bytes, size_t width_bytes, int rows);   // multiples of 8 bytes
 void launch_gather_counts(hipStream_t s, const FrameJob* jobs /*[L][job_pitch]*/, int job_pitch, int nframes, int first_level, int num_levels,
                           int* out /*[nframes][kMaxLevels]*/);

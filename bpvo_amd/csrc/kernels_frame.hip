@@ -18,10 +18,11 @@ namespace bpvo_hip {
 // Levels in one launch (few frames: every per-level launch is a 5 - 20 us latency floor, four levels of them in a row): the grid is sized for
 // the FINEST level of the group, z = level x nframes + frame, and the workgroups that fall outside a coarser level's own grid leave at
 // once.  `jobs` is the finest level's row of the table [level][job_pitch]; a per-level launch has z < nframes: its own row.
-__device__ __forceinline__ const FrameJob& level_job(const FrameJob* jobs, unsigned z, int nframes, int job_pitch)
+// job_step = 2: every other job of a level's row — the template frames (A) or the current frames (B) of a pair batch (A, B, A, B, ...)
+__device__ __forceinline__ const FrameJob& level_job(const FrameJob* jobs, unsigned z, int nframes, int job_pitch, int job_step = 1)
 {
   const unsigned lvl = z / (unsigned) nframes;
-  return jobs[(size_t) lvl * job_pitch + (z - lvl * (unsigned) nframes)];
+  return jobs[(size_t) lvl * job_pitch + (size_t) (z - lvl * (unsigned) nframes) * job_step];
 }
 
 // AT: frame z's image and disparity begin at pixel offs[z] of the packed buffers (bpvo_hip_add_frames over cameras of different sizes: one
@@ -304,6 +305,62 @@ __global__ __launch_bounds__(256) void census_kernel(const FrameJob* jobs)
   }
 }
 
+// ---- K1a for the census-only levels (FrameJob::lazy == 2) of the template frames of a pair batch — jobs 0, 2, 4, ... of a level's row,
+// levels in one launch as in level_job; other jobs are left alone.  Same bits as census_kernel.  FOUR pixels of a row per thread: the six
+// window columns x-1 .. x+4 of a row arrive as one 4-byte and one 2-byte load (rows of a level are not 4-byte aligned: unaligned loads)
+// instead of twelve byte loads, the four census bytes leave as one store: the two lazy levels of 1024 frames of 1241x376 in 0.67 ms
+// against 1.05 ms through census_kernel (profiles/lazy_saliency.txt).
+typedef unsigned int u32_unaligned __attribute__((aligned(1)));
+typedef unsigned short u16_unaligned __attribute__((aligned(1)));
+constexpr int CT_ROWS = 8, CT_PX = 4;
+__global__ __launch_bounds__(256) void census_templates_kernel(const FrameJob* jobs, int nframes, int job_pitch)
+{
+  const FrameJob& j = level_job(jobs, blockIdx.z, nframes, job_pitch, 2);
+  if(j.lazy != 2) return;
+  const int W = j.cols, R = j.rows;
+  const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * CT_PX;
+  const int y0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * CT_ROWS;
+  if(x >= W || y0 >= R) return;
+  const uint8_t* __restrict__ img = j.img;
+  uint8_t* __restrict__ cen = j.cen;
+  const bool inner = x >= 1 && x + CT_PX < W;      // the six window columns lie inside the row
+  // byte q of w[k] = image(y0 - 1 + k, x - 1 + q), coordinates clamped (clamped positions only feed the border, which is 0)
+  unsigned long long w[CT_ROWS + 2];
+#pragma unroll
+  for(int k = 0; k < CT_ROWS + 2; ++k) {
+    const uint8_t* p = img + (size_t) min(max(y0 - 1 + k, 0), R - 1) * W;
+    if(inner) {
+      w[k] = (unsigned long long) *reinterpret_cast<const u32_unaligned*>(p + x - 1) |
+             ((unsigned long long) *reinterpret_cast<const u16_unaligned*>(p + x + 3) << 32);
+    } else {
+      unsigned long long v = 0;
+#pragma unroll
+      for(int q = 0; q < CT_PX + 2; ++q) v |= (unsigned long long) p[min(max(x - 1 + q, 0), W - 1)] << (8 * q);
+      w[k] = v;
+    }
+  }
+#pragma unroll
+  for(int k = 0; k < CT_ROWS; ++k) {
+    const int y = y0 + k;
+    if(y >= R) break;
+    const bool yin = y > 0 && y < R - 1;
+    unsigned out4 = 0;
+#pragma unroll
+    for(int q = 0; q < CT_PX; ++q) {
+      const unsigned a = (unsigned) (w[k] >> (8 * q)), b = (unsigned) (w[k + 1] >> (8 * q)), c = (unsigned) (w[k + 2] >> (8 * q));
+      const unsigned ctr = (b >> 8) & 0xffu;
+      unsigned out = (((a & 0xffu) >= ctr) << 0) | ((((a >> 8) & 0xffu) >= ctr) << 1) | ((((a >> 16) & 0xffu) >= ctr) << 2) | (((b & 0xffu) >= ctr) << 3) |
+                     ((((b >> 16) & 0xffu) >= ctr) << 4) | (((c & 0xffu) >= ctr) << 5) | ((((c >> 8) & 0xffu) >= ctr) << 6) | ((((c >> 16) & 0xffu) >= ctr) << 7);
+      if(!(yin && x + q > 0 && x + q < W - 1)) out = 0;
+      out4 |= out << (8 * q);
+    }
+    uint8_t* o = cen + (size_t) y * W + x;
+    if(x + CT_PX <= W) *reinterpret_cast<u32_unaligned*>(o) = out4;
+    else
+      for(int q = 0; q < W - x; ++q) o[q] = (uint8_t) (out4 >> (8 * q));
+  }
+}
+
 // ---- K1a': census of the 3x3-smoothed image, sigmaPriorToCensusTransform > 0 (reference: bpvo/census.cc:63-66 ->
 // cv::GaussianBlur(u8, Size(3,3), s, s) [ext: OpenCV 2.4 8-bit separable filter in fixed point: taps round(k * 256),
 // row pass u8 -> int, column pass (sum + 2^15) >> 16, saturated; BORDER_REFLECT_101]).  The smoothed image is never
@@ -387,16 +444,11 @@ constexpr int BP_PLANE = (BP_TH + 2 * BP_HALO) * BP_TW + 8;
 // planes 0-3, 4-7), the five positions of a row window are combined bytewise into the index a + 3 b + 9 S0 of all eight planes at
 // once, and the eighteen values — evaluated by the kernel itself with the very expression above — are looked up in LDS (different
 // entries lie in different banks, equal ones broadcast: no conflicts).  ~30 instead of ~136 VALU operations per position, same bits.
-__device__ __forceinline__ uint2 spread_planes(unsigned c)
-{
-  unsigned lo = c & 0xFu, hi = (c >> 4) & 0xFu;
-  lo = (lo | (lo << 14)) & 0x00030003u; lo = (lo | (lo << 7)) & 0x01010101u;
-  hi = (hi | (hi << 14)) & 0x00030003u; hi = (hi | (hi << 7)) & 0x01010101u;
-  return make_uint2(lo, hi);
-}
-
+// job_step / dense_columns (pair batches with census-only levels, launch_bitplanes_pairs): the launch serves every job_step-th job of the row, and
+// with dense_columns its grid spans only the tile columns of the level that stay dense — the first where it does, and the trailing ones.
 template <bool FROM_IMAGE>
-__global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* jobs, float k0, float k1, float k2, int stack, int nframes, int job_pitch)
+__global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* jobs, float k0, float k1, float k2, int stack, int nframes, int job_pitch, int job_step,
+                                                             int dense_columns)
 {
   constexpr int CR = BP_TH + 2 * BP_HALO, CC = BP_TW + 2 * BP_HALO;   // staged census rows / columns
   constexpr int CW = CC + 4;                                             // padded LDS row pitch of the census tile
@@ -407,9 +459,11 @@ __global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* job
   __shared__ uint8_t s_img[FROM_IMAGE ? IR * IW : 4];
   __shared__ float s_row[(BP_PLANE + CR * BP_TW) * 4];
   __shared__ float s_lut[18];
-  const FrameJob& j = level_job(jobs, blockIdx.z, nframes, job_pitch);
+  const FrameJob& j = level_job(jobs, blockIdx.z, nframes, job_pitch, job_step);
   const int W = j.cols, R = j.rows;
-  const int x0 = blockIdx.x * BP_TW;
+  int bx = blockIdx.x;
+  if(dense_columns && !(bx == 0 && !bp_tile_column_is_lazy(0, W))) bx += (W + BP_TW - 1) / BP_TW - (int) gridDim.x;
+  const int x0 = bx * BP_TW;
   if(x0 >= W || (int) blockIdx.y * BP_TH * stack >= R) return;      // (a coarser level inside a launch sized for the finest)
   const int tid = threadIdx.x;
   const uint8_t* __restrict__ cen = FROM_IMAGE ? j.img : j.cen;
@@ -421,16 +475,16 @@ __global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* job
   // stencil positions of one pixel in ~18 only — 72 % of them never — so the level keeps its census bytes and channel 0 (what the saliency
   // map needs) and template_build forms the stencils' records from the census bytes: the kernel then runs the census stage, one plane of
   // eight in the two passes, and stores 5 bytes per pixel instead of 36.
-  // The tile columns at the right edge stay dense: the saliency of the columns the reference's SIMD body treats apart — x < 4 (formed from
-  // columns n - 4 + x) and x >= n = W & ~3 (Q7) — reads whole records of columns n - 5 .. W - 1 (saliency_generic).  And when W is a
-  // multiple of 4, column x = 3 is formed at xs = W - 1, whose right neighbour is the reference's read past the end of the row: the
-  // record of column 0 of the NEXT row — so the first tile column stays dense too.
-  const bool lazy_level = FROM_IMAGE && j.lazy != 0;
-  const bool lazy = lazy_level && x0 + BP_TW + 8 <= (W & ~3) && !(x0 == 0 && (W & 3) == 0);
+  // The tile columns whose records the saliency of the columns the reference treats apart reads stay dense (bp_tile_column_is_lazy).
+  // A CENSUS-ONLY level (FrameJob::lazy == 2) keeps no channel-0 plane either: census_templates_kernel has written its census bytes, the tiled
+  // selection forms channel 0 of its window from them, and the lazy tile columns of such a level have nothing to do here.
+  static_assert(BP_TW == 64, "bp_tile_column_is_lazy speaks of 64-pixel tile columns");
+  const bool lazy = FROM_IMAGE && j.lazy != 0 && bp_tile_column_is_lazy(x0, W);
+  if(lazy && j.lazy == 2) return;
+  const bool lazy_level = FROM_IMAGE && j.lazy == 1;      // (the level's census bytes are this kernel's to store)
   uint8_t* __restrict__ const cen_out = j.cen;
   if(tid < 18) {      // entry a + 3 b + 9 S0 (visible after the first barrier below)
-    const float S0 = (float) (tid / 9), A = (float) (tid % 3), B = (float) ((tid / 3) % 3);
-    s_lut[tid] = S0 * k0 + A * k1 + B * k2;
+    s_lut[tid] = bp_row_entry(tid, k0, k1, k2);
   }
 
   uint8_t pre[NPRE];
@@ -448,7 +502,7 @@ __global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* job
         pre[k] = cen[(size_t) gy * W + gx];
       } else {
         const int ly = i / CC, lx = i - ly * CC;
-        const int gy = reflect101(min(y0 + ly - BP_HALO, R + 1), R), gx = reflect101(min(x0 + lx - BP_HALO, W + 1), W);
+        const int gy = bp_census_coord(y0 + ly - BP_HALO, R), gx = bp_census_coord(x0 + lx - BP_HALO, W);
         pre[k] = cen[(size_t) gy * W + gx];
       }
     }
@@ -480,7 +534,7 @@ __global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* job
       // census of the staged positions: (gy, gx) = REFLECT_101 of the census coordinate, read from the image window
       for(int i = tid; i < CR * CC; i += 256) {
         const int ly = i / CC, lx = i - ly * CC;
-        const int gy = reflect101(min(y0 + ly - BP_HALO, R + 1), R), gx = reflect101(min(x0 + lx - BP_HALO, W + 1), W);
+        const int gy = bp_census_coord(y0 + ly - BP_HALO, R), gx = bp_census_coord(x0 + lx - BP_HALO, W);
         uint8_t out = 0;
         if(gx > 0 && gx < W - 1 && gy > 0 && gy < R - 1) {
           // window origin: image row y0 - 3, column x0 - 3 (the reflected position lies inside the window: |reflection| <= 2 px)
@@ -504,7 +558,7 @@ __global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* job
       for(int i = tid; i < CR * BP_TW; i += 256) {
         const int ly = i / BP_TW, lx = i - ly * BP_TW;
         const uint2* c = s_cen + ly * CW + lx;
-        const unsigned ilo = (c[1].x + c[3].x) + 3u * (c[0].x + c[4].x) + 9u * c[2].x;
+        const unsigned ilo = bp_row_index(c[0].x, c[1].x, c[2].x, c[3].x, c[4].x);
         s_row[i] = s_lut[ilo & 0xffu];
       }
       __syncthreads();
@@ -515,8 +569,7 @@ __global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* job
         if(gx >= W || gy >= R) continue;
         const float* Th = s_row + ly * BP_TW + lx;
         constexpr int pitch = BP_TW;
-        float o = k0 * Th[2 * pitch]; o += k1 * (Th[3 * pitch] + Th[pitch]); o += k2 * (Th[4 * pitch] + Th[0]);
-        ch0[(size_t) gy * W + gx] = o;
+        ch0[(size_t) gy * W + gx] = bp_col(Th[0], Th[pitch], Th[2 * pitch], Th[3 * pitch], Th[4 * pitch], k0, k1, k2);
       }
       __syncthreads();
       continue;
@@ -526,8 +579,8 @@ __global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* job
       const int ly = i / BP_TW, lx = i - ly * BP_TW;
       const uint2* c = s_cen + ly * CW + lx;   // c[0..4] = columns x-2..x+2
       const uint2 cm2 = c[0], cm1 = c[1], c0 = c[2], cp1 = c[3], cp2 = c[4];
-      const unsigned ilo = (cm1.x + cp1.x) + 3u * (cm2.x + cp2.x) + 9u * c0.x;     // bytewise, <= 17: no carries
-      const unsigned ihi = (cm1.y + cp1.y) + 3u * (cm2.y + cp2.y) + 9u * c0.y;
+      const unsigned ilo = bp_row_index(cm2.x, cm1.x, c0.x, cp1.x, cp2.x);     // bytewise, <= 17: no carries
+      const unsigned ihi = bp_row_index(cm2.y, cm1.y, c0.y, cp1.y, cp2.y);
       float tt[8];
 #pragma unroll
       for(int b = 0; b < 4; ++b) {
@@ -555,10 +608,10 @@ __global__ __launch_bounds__(256) void bitplanes_blur_kernel(const FrameJob* job
       constexpr int pitch = BP_TW;
       const float4 Tm2 = Th[0], Tm1 = Th[pitch], T0 = Th[2 * pitch], Tp1 = Th[3 * pitch], Tp2 = Th[4 * pitch];
       float4 o4;
-      o4.x = k0 * T0.x; o4.x += k1 * (Tp1.x + Tm1.x); o4.x += k2 * (Tp2.x + Tm2.x);
-      o4.y = k0 * T0.y; o4.y += k1 * (Tp1.y + Tm1.y); o4.y += k2 * (Tp2.y + Tm2.y);
-      o4.z = k0 * T0.z; o4.z += k1 * (Tp1.z + Tm1.z); o4.z += k2 * (Tp2.z + Tm2.z);
-      o4.w = k0 * T0.w; o4.w += k1 * (Tp1.w + Tm1.w); o4.w += k2 * (Tp2.w + Tm2.w);
+      o4.x = bp_col(Tm2.x, Tm1.x, T0.x, Tp1.x, Tp2.x, k0, k1, k2);
+      o4.y = bp_col(Tm2.y, Tm1.y, T0.y, Tp1.y, Tp2.y, k0, k1, k2);
+      o4.z = bp_col(Tm2.z, Tm1.z, T0.z, Tp1.z, Tp2.z, k0, k1, k2);
+      o4.w = bp_col(Tm2.w, Tm1.w, T0.w, Tp1.w, Tp2.w, k0, k1, k2);
       store_stream(reinterpret_cast<float4*>(desc + ((size_t) gy * W + gx) * 8) + h, o4);
       if(h == 0 && ch0) ch0[(size_t) gy * W + gx] = o4.x;      // (not for frames that only ever serve as the current frame of a pair batch)
     }
@@ -849,13 +902,23 @@ constexpr int ST_W = 64, ST_H = 32, ST_ROWS_PER_WAVE = ST_H / 4;
 constexpr int ST_CH_ROWS = ST_H + 4, ST_CH_COLS = ST_W + 5, ST_CH_PITCH = 72;     // channel 0: rows y0-2 .. y0+H+1, columns x0-2 .. x0+W+2
 constexpr int ST_S_ROWS = ST_H + 2, ST_S_COLS = ST_W + 3, ST_S_PITCH = 68;        // saliency:  rows y0-1 .. y0+H,   columns x0-1 .. x0+W+1
 
+// census-only levels: census positions of a tile — rows y0-4 .. y0+H+3, columns x0-4 .. x0+W+4: the channel-0 window + the blur's 2-px halo —
+// as bit 0 of the census byte, the row pass' table index (bp_row_index) per position of the window's columns, the row-pass table
+constexpr int ST_CEN_ROWS = ST_CH_ROWS + 4, ST_CEN_PITCH = 76;      // (ST_CH_COLS + 4 = 73 columns, padded)
+static_assert(ST_CEN_PITCH >= ST_CH_COLS + 4, "a staged census row holds the window's columns and the halo");
+struct CensusStage {
+  uint8_t bit[ST_CEN_ROWS * ST_CEN_PITCH];
+  uint8_t idx[ST_CEN_ROWS * ST_CH_PITCH];
+  float lut[18];
+};
+static_assert(sizeof(CensusStage) <= sizeof(float) * ST_S_ROWS * ST_S_PITCH, "the census staging fits the saliency tile's storage");
+
 template <int C>
-__device__ __forceinline__ float saliency_generic(const FrameJob& j, int x, int y)
+__device__ __forceinline__ float saliency_generic(const float* __restrict__ I /* the level's records */, int W, int R, int x, int y)
 {
   // the per-pixel closed form (see saliency_kernel), for the columns the tile does not cover
-  const int W = j.cols, R = j.rows, n = W & ~3;
+  const int n = W & ~3;
   if(!(y >= 1 && y <= R - 2 && x != W - 1)) return 0.0f;
-  const float* __restrict__ I = j.desc;
   const size_t row = (size_t) y * W;
   if(x >= n) {
     float S = grad_tail<C>(I, row + x, W, 0);
@@ -869,10 +932,12 @@ __device__ __forceinline__ float saliency_generic(const FrameJob& j, int x, int 
 }
 
 template <int C>
-__global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJob* jobs, int border, int nframes, int job_pitch)
+__global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJob* jobs, int border, int nframes, int job_pitch, float k0, float k1, float k2)
 {
   __shared__ float s_ch[ST_CH_ROWS][ST_CH_PITCH];
-  __shared__ float s_sal[ST_S_ROWS][ST_S_PITCH];
+  // (the census staging of a census-only level lives in the saliency tile's storage, which is written only behind the barrier that completes s_ch)
+  __shared__ union { float sal[ST_S_ROWS][ST_S_PITCH]; CensusStage cs; } s_u;
+  float (&s_sal)[ST_S_ROWS][ST_S_PITCH] = s_u.sal;
   const FrameJob& j = level_job(jobs, blockIdx.z, nframes, job_pitch);
   const int W = j.cols, R = j.rows, n = W & ~3;
   const int x0 = blockIdx.x * ST_W, y0 = blockIdx.y * ST_H;
@@ -884,12 +949,61 @@ __global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJo
   const bool compact = C == 8 && j.ch0;
   const float* __restrict__ ch = compact ? j.ch0.get() : j.desc.get();
   const int CS = compact ? 1 : C;
-  // (flat index over rows x pitch: every pass of the 256 threads is 3.5 full rows instead of one row plus a 5-lane remainder)
-  for(int i = threadIdx.x; i < ST_CH_ROWS * ST_CH_PITCH; i += 256) {
-    const int r = i / ST_CH_PITCH, cc = i - r * ST_CH_PITCH;
-    if(cc < ST_CH_COLS) {
-      const int y = min(max(y0 - 2 + r, 0), R - 1), xx = min(max(x0 - 2 + cc, 0), W - 1);
-      s_ch[r][cc] = ch[((size_t) y * W + xx) * CS];
+  // what the passes behind the staging read of the job, in registers (scalar loads, issued here: behind the staging's stores the compiler
+  // no longer takes the job table for unchanged and re-reads every field per use, with vector loads)
+  const float* __restrict__ const recs = j.desc;
+  const float* __restrict__ const disp = j.disp;
+  const int radius = j.nms_radius, dstep = 1 << j.level, disp_cols = j.disp_cols;
+  const float min_saliency = j.min_saliency, min_disp = j.min_disp, max_disp = j.max_disp;      // the frame's own thresholds (one frame per workgroup: uniform)
+  unsigned long long* __restrict__ const words_out = j.words;
+  float* __restrict__ const sal_out = j.sal;
+  if(C == 8 && j.lazy == 2) {      // (uniform over the workgroup: a frame's level is census-only or it is not)
+    // A CENSUS-ONLY level (template frames of a pair batch at the NMS levels, option lazy_template_saliency): no channel-0 plane exists.
+    // The window's channel 0 — plane 0 of the blurred bit-planes: bit 0 of the census byte — is formed here as bitplanes_blur_kernel
+    // forms it, value for value: the census bits of the window + the blur's 2-px halo (REFLECT_101 on the census coordinates) are staged,
+    // the row pass leaves its table INDEX per position (a byte; the table entry is the row-pass value), the column pass looks the five
+    // values up.
+    // (window positions outside the image hold values of reflected positions instead of the dense form's clamped ones: they only feed
+    // saliencies that are defined as 0 or replaced, see below)
+    constexpr int NR = ST_CEN_ROWS, NP = ST_CEN_PITCH;
+    CensusStage& cs = s_u.cs;
+    if(threadIdx.x < 18) cs.lut[threadIdx.x] = bp_row_entry(threadIdx.x, k0, k1, k2);
+    const uint8_t* __restrict__ cen = j.cen;
+    // (all loads of a thread issued before the first is used; the lanes past the end load a byte they do not stage)
+    constexpr int NPRE = (NR * NP + 255) / 256;
+    uint8_t pre[NPRE];
+#pragma unroll
+    for(int q = 0; q < NPRE; ++q) {
+      const int i = min((int) threadIdx.x + q * 256, NR * NP - 1);
+      const int r = i / NP, k = i - r * NP;
+      pre[q] = cen[(size_t) bp_census_coord(y0 - 4 + r, R) * W + bp_census_coord(x0 - 4 + k, W)];
+    }
+#pragma unroll
+    for(int q = 0; q < NPRE; ++q) {
+      const int i = threadIdx.x + q * 256;
+      if(i < NR * NP) cs.bit[i] = pre[q] & 1u;
+    }
+    __syncthreads();
+    for(int i = threadIdx.x; i < NR * ST_CH_PITCH; i += 256) {
+      const int r = i / ST_CH_PITCH, cc = i - r * ST_CH_PITCH;
+      const uint8_t* b = cs.bit + r * NP + cc;      // b[0..4] = columns x-2 .. x+2 of window column cc
+      if(cc < ST_CH_COLS) cs.idx[i] = (uint8_t) bp_row_index(b[0], b[1], b[2], b[3], b[4]);
+    }
+    __syncthreads();
+    for(int i = threadIdx.x; i < ST_CH_ROWS * ST_CH_PITCH; i += 256) {
+      const int r = i / ST_CH_PITCH, cc = i - r * ST_CH_PITCH;
+      const uint8_t* t = cs.idx + i;                // rows y-2 .. y+2 of window row r
+      if(cc < ST_CH_COLS)
+        s_ch[r][cc] = bp_col(cs.lut[t[0]], cs.lut[t[ST_CH_PITCH]], cs.lut[t[2 * ST_CH_PITCH]], cs.lut[t[3 * ST_CH_PITCH]], cs.lut[t[4 * ST_CH_PITCH]], k0, k1, k2);
+    }
+  } else {
+    // (flat index over rows x pitch: every pass of the 256 threads is 3.5 full rows instead of one row plus a 5-lane remainder)
+    for(int i = threadIdx.x; i < ST_CH_ROWS * ST_CH_PITCH; i += 256) {
+      const int r = i / ST_CH_PITCH, cc = i - r * ST_CH_PITCH;
+      if(cc < ST_CH_COLS) {
+        const int y = min(max(y0 - 2 + r, 0), R - 1), xx = min(max(x0 - 2 + cc, 0), W - 1);
+        s_ch[r][cc] = ch[((size_t) y * W + xx) * CS];
+      }
     }
   }
   __syncthreads();
@@ -900,13 +1014,12 @@ __global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJo
     // the SIMD body's form from the tile, unconditionally; the exceptions (image border, the columns the reference treats apart) after it
     float S = fabsf(s_ch[r + 1][cc] - s_ch[r + 1][cc + 2]) + fabsf(s_ch[r][cc + 1] - s_ch[r + 2][cc + 1]);
     const bool inside = xx >= 0 && xx < W && y >= 0 && y < R;
-    if(!(xx >= 4 && xx < n && xx != W - 1 && y >= 1 && y <= R - 2)) S = (inside && (xx < 4 || xx >= n)) ? saliency_generic<C>(j, xx, y) : 0.0f;
+    if(!(xx >= 4 && xx < n && xx != W - 1 && y >= 1 && y <= R - 2)) S = (inside && (xx < 4 || xx >= n)) ? saliency_generic<C>(recs, W, R, xx, y) : 0.0f;
     s_sal[r][cc] = S;
   }
   __syncthreads();
   // candidates: one column per lane, ST_ROWS_PER_WAVE rows per wave, the 3 x 4 window slides down the column
   const int x = x0 + lane, c = lane + 1;
-  const int radius = j.nms_radius;
   const bool col_ok = x >= border && x < W - border - 1;
   const int ry0 = wave * ST_ROWS_PER_WAVE;        // first row of this wave inside the tile
   // strict > against the 11 neighbours (Q8: 3 rows, columns x-1 .. x+2) = v > their maximum (saliencies are finite sums of |.|);
@@ -920,7 +1033,6 @@ __global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJo
     full[q] = fmaxf(side[q], t[1]);
   }
   bool ok[ST_ROWS_PER_WAVE];
-  const float min_saliency = j.min_saliency;      // the frame's own thresholds (one frame per workgroup: uniform)
 #pragma unroll
   for(int q = 0; q < ST_ROWS_PER_WAVE; ++q) {
     const int y = y0 + ry0 + q;
@@ -933,20 +1045,19 @@ __global__ __launch_bounds__(256) void saliency_select_tile_kernel(const FrameJo
   float dv[ST_ROWS_PER_WAVE];
 #pragma unroll
   for(int q = 0; q < ST_ROWS_PER_WAVE; ++q)
-    dv[q] = ok[q] ? j.disp[(size_t) (1 << j.level) * ((size_t) (y0 + ry0 + q) * j.disp_cols + x)] : 0.0f;
+    dv[q] = ok[q] ? disp[(size_t) dstep * ((size_t) (y0 + ry0 + q) * disp_cols + x)] : 0.0f;
   unsigned long long words = 0;      // lane q keeps the word of row q
-  const float min_disp = j.min_disp, max_disp = j.max_disp;
 #pragma unroll
   for(int q = 0; q < ST_ROWS_PER_WAVE; ++q) {
     const unsigned long long m = __ballot(ok[q] && dv[q] >= min_disp && dv[q] <= max_disp);
     if(lane == q) words = m;
   }
   const int y = y0 + ry0 + lane;
-  if(lane < ST_ROWS_PER_WAVE && y < R) j.words[(size_t) y * ((W + 63) / 64) + blockIdx.x] = words;
+  if(lane < ST_ROWS_PER_WAVE && y < R) words_out[(size_t) y * ((W + 63) / 64) + blockIdx.x] = words;
   // the saliency map itself (bpvo_hip_get_saliency), LAST: stores issued before the gate's loads would be waited for with them (one in-order
   // counter for loads and stores), a memory round trip per tile
-  if(x < W) {
-    float* __restrict__ sal_out = j.sal;
+  // (not for the template frames of a pair batch whose map is formed on demand — FrameSlot::sal_state: their jobs carry no `sal`)
+  if(x < W && sal_out) {
 #pragma unroll
     for(int q = 0; q < ST_ROWS_PER_WAVE; ++q) {
       const int yy = y0 + ry0 + q;
@@ -1369,8 +1480,8 @@ __device__ __forceinline__ void bp_row_from_census(const uint8_t* __restrict__ c
   const uint8_t* row = cen + (size_t) reflect101(r, R) * W;
   const uint2 cm2 = spread_planes(row[reflect101(px - 2, W)]), cm1 = spread_planes(row[reflect101(px - 1, W)]), c0 = spread_planes(row[reflect101(px, W)]),
               cp1 = spread_planes(row[reflect101(px + 1, W)]), cp2 = spread_planes(row[reflect101(px + 2, W)]);
-  const unsigned ilo = (cm1.x + cp1.x) + 3u * (cm2.x + cp2.x) + 9u * c0.x;
-  const unsigned ihi = (cm1.y + cp1.y) + 3u * (cm2.y + cp2.y) + 9u * c0.y;
+  const unsigned ilo = bp_row_index(cm2.x, cm1.x, c0.x, cp1.x, cp2.x);
+  const unsigned ihi = bp_row_index(cm2.y, cm1.y, c0.y, cp1.y, cp2.y);
 #pragma unroll
   for(int b = 0; b < 4; ++b) {
     T[b] = lut[(ilo >> (8 * b)) & 0xffu];
@@ -1382,12 +1493,7 @@ __device__ __forceinline__ void bp_col_pass(const float (&Tm2)[8], const float (
                                             float k0, float k1, float k2, float (&out)[8])
 {
 #pragma unroll
-  for(int c = 0; c < 8; ++c) {
-    float o = k0 * T0[c];
-    o += k1 * (Tp1[c] + Tm1[c]);
-    o += k2 * (Tp2[c] + Tm2[c]);
-    out[c] = o;
-  }
+  for(int c = 0; c < 8; ++c) out[c] = bp_col(Tm2[c], Tm1[c], T0[c], Tp1[c], Tp2[c], k0, k1, k2);
 }
 
 template <int C>
@@ -1396,10 +1502,7 @@ __global__ __launch_bounds__(256) void template_build_kernel(const FrameJob* job
   const FrameJob& j = level_job(jobs, blockIdx.z, nframes, job_pitch);
   __shared__ float s_lut[18];
   if(C == 8 && j.lazy) {      // (uniform over the workgroup: a frame's level is lazy or it is not)
-    if(threadIdx.x < 18) {    // the row-pass table of bitplanes_blur_kernel: entry a + 3 b + 9 S0
-      const float S0 = (float) (threadIdx.x / 9), A = (float) (threadIdx.x % 3), B = (float) ((threadIdx.x / 3) % 3);
-      s_lut[threadIdx.x] = S0 * k0 + A * k1 + B * k2;
-    }
+    if(threadIdx.x < 18) s_lut[threadIdx.x] = bp_row_entry(threadIdx.x, k0, k1, k2);    // the row-pass table of bitplanes_blur_kernel
     __syncthreads();
   }
   const int N = *j.n_out;
@@ -1620,6 +1723,13 @@ void launch_census(hipStream_t s, const FrameJob* jobs, int W, int R, int nframe
   else
     hipLaunchKernelGGL(census_kernel, dim3((W + 63) / 64, (R + 4 * CENSUS_ROWS - 1) / (4 * CENSUS_ROWS), nframes), dim3(256), 0, s, jobs);
 }
+// the census bytes of the census-only levels of a pair batch's template frames: jobs 0, 2, 4, ... of `nframes` (A, B, A, B, ...)
+void launch_census_templates(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int nlevels, int job_pitch)
+{
+  const int na = (nframes + 1) / 2;
+  hipLaunchKernelGGL(census_templates_kernel, dim3((W + 64 * CT_PX - 1) / (64 * CT_PX), (R + 4 * CT_ROWS - 1) / (4 * CT_ROWS), na * nlevels), dim3(256), 0, s, jobs, na,
+                     job_pitch);
+}
 void launch_bitplanes(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, float sigma, const float k[3], int from_image, int nlevels,
                       int job_pitch)
 {
@@ -1627,20 +1737,40 @@ void launch_bitplanes(hipStream_t s, const FrameJob* jobs, int W, int R, int nfr
   const int stack = nframes >= 16 ? 8 : (nframes > 4 ? 4 : 1);
   const dim3 grid((W + BP_TW - 1) / BP_TW, (R + BP_TH * stack - 1) / (BP_TH * stack), nframes * nlevels);
   if(sigma > 0.0f && from_image)
-    hipLaunchKernelGGL(bitplanes_blur_kernel<true>, grid, dim3(256), 0, s, jobs, k[0], k[1], k[2], stack, nframes, job_pitch);
+    hipLaunchKernelGGL(bitplanes_blur_kernel<true>, grid, dim3(256), 0, s, jobs, k[0], k[1], k[2], stack, nframes, job_pitch, 1, 0);
   else if(sigma > 0.0f)
-    hipLaunchKernelGGL(bitplanes_blur_kernel<false>, grid, dim3(256), 0, s, jobs, k[0], k[1], k[2], stack, nframes, job_pitch);
+    hipLaunchKernelGGL(bitplanes_blur_kernel<false>, grid, dim3(256), 0, s, jobs, k[0], k[1], k[2], stack, nframes, job_pitch, 1, 0);
   else
     hipLaunchKernelGGL(bitplanes_noblur_kernel, dim3((W * R + 255) / 256, 1, nframes), dim3(256), 0, s, jobs);
 }
-void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, int nlevels, int job_pitch)
+// the saliency map alone, from dense records (and the channel-0 plane where the job has one)
+// One level of a pair batch (jobs A, B, A, B, ...) whose template frames are census-only there (FrameJob::lazy == 2; census fused, sigma > 0):
+// the current frames in one launch over every tile, the template frames in one over the tile columns that stay dense — no workgroup is
+// started for a lazy tile (144 k of them per 1024-pair step, each waiting for its 32 KB of LDS only to leave).
+void launch_bitplanes_pairs(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, const float k[3])
+{
+  const int stack = nframes >= 16 ? 8 : (nframes > 4 ? 4 : 1);      // (as launch_bitplanes: by the frames of the stage)
+  const int ncols = (W + BP_TW - 1) / BP_TW, nrows = (R + BP_TH * stack - 1) / (BP_TH * stack);
+  int dense = 0;
+  for(int cx = 0; cx < ncols; ++cx) dense += bp_tile_column_is_lazy(cx * BP_TW, W) ? 0 : 1;
+  const int na = (nframes + 1) / 2, nb = nframes / 2;
+  if(nb > 0) hipLaunchKernelGGL(bitplanes_blur_kernel<true>, dim3(ncols, nrows, nb), dim3(256), 0, s, jobs + 1, k[0], k[1], k[2], stack, nb, 0, 2, 0);
+  if(dense > 0) hipLaunchKernelGGL(bitplanes_blur_kernel<true>, dim3(dense, nrows, na), dim3(256), 0, s, jobs, k[0], k[1], k[2], stack, na, 0, 2, 1);
+}
+void launch_saliency(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes)
+{
+  auto plain = [&](auto c) { hipLaunchKernelGGL(saliency_kernel<decltype(c)::value>, grid2d_rows(W, R, nframes), dim3(256), 0, s, jobs); };
+  if(C <= 48 || !dispatch_wide_channels(C, plain)) dispatch_channels(C, plain);
+}
+void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, const float gauss_k[3], int nlevels,
+                            int job_pitch)
 {
   if(nms_radius <= 1) {
     // tiles: saliency + NMS + gate in one pass, candidate bits, word scan, lane-per-pixel compaction
     const int WPR = (W + 63) / 64, nw = R * WPR;
     auto tile = [&](auto c) {
       hipLaunchKernelGGL(saliency_select_tile_kernel<decltype(c)::value>, dim3(WPR, (R + ST_H - 1) / ST_H, nframes * nlevels), dim3(256), 0, s, jobs,
-                         border, nframes, job_pitch);
+                         border, nframes, job_pitch, gauss_k[0], gauss_k[1], gauss_k[2]);
     };
     if(C <= 48 || !dispatch_wide_channels(C, tile)) dispatch_channels(C, tile);
     hipLaunchKernelGGL(select_words_scan_kernel, dim3(nframes * nlevels), dim3(1024), 0, s, jobs, nframes, job_pitch);
@@ -1649,8 +1779,7 @@ void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, i
     return;
   }
   // larger NMS windows: the saliency map first, then flag bytes / chunk scan / compaction straight from it
-  auto plain = [&](auto c) { hipLaunchKernelGGL(saliency_kernel<decltype(c)::value>, grid2d_rows(W, R, nframes), dim3(256), 0, s, jobs); };
-  if(C <= 48 || !dispatch_wide_channels(C, plain)) dispatch_channels(C, plain);
+  launch_saliency(s, jobs, C, W, R, nframes);
   const int nblk = (W * R + SEL_BLOCK_PX - 1) / SEL_BLOCK_PX;
   hipLaunchKernelGGL(select_flag_kernel, dim3(nblk, 1, nframes), dim3(256), 0, s, jobs, border);
   hipLaunchKernelGGL(select_scan_kernel, dim3(nframes), dim3(1024), 0, s, jobs);

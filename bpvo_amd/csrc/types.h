@@ -264,6 +264,8 @@ struct FrameJob {
   int            lazy;      // 1 (C = 8 bit-planes, template frames of a pair batch at the NMS levels): the level's 32-byte records are NOT
                             // stored — `cen` holds the census bytes and `ch0` channel 0 (all the selection needs); template_build
                             // forms the records of its stencils from the census bytes (kernels_frame.hip)
+                            // 2 (option lazy_template_saliency, NMS radius 1): census-only — `ch0` is null too, census_templates_kernel writes
+                            // `cen`, the tiled selection forms channel 0 of its windows from it; `sal` is null where the map is formed on demand
 };
 
 }  // namespace bpvo_hip

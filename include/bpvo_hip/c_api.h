@@ -653,6 +653,12 @@ int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* ctx, uint64_t out[4]);
  *                                      one pixel in ~18 is a template point there, template_build forms the records of its stencils from the census
  *                                      bytes (same operations, same bits).  The accessors and a later estimate with such a slot as the CURRENT frame
  *                                      rebuild the records on demand.
+ *   "lazy_template_saliency" 1         needs lazy_template_descriptor = 1 (without it the option does nothing).  1: at those levels (NMS radius 1) the
+ *                                      template frames of bpvo_hip_batch_run keep the census bytes ONLY: a census launch writes them, the bit-planes
+ *                                      kernel runs over the few tile columns that stay dense, the tiled selection forms channel 0 of its windows from
+ *                                      the census bytes (same operations, same bits) and does not store the saliency map.  bpvo_hip_get_saliency
+ *                                      forms the map on demand from the slot's data — the same bytes — and fails with BPVO_ERR_NO_DATA once that data
+ *                                      has been replaced (frame_set_data on the slot, the next batch) before a new template was made of it.
  *   "points_from_compact_stream" 0     debug: bpvo_hip_get_points returns the points as the Gauss-Newton kernels rebuild them from the 8-byte records
  *                                      they stream ({Z or d, x | y << 16}: DESIGN.md 3) instead of the stored (X, Y, Z, 1) — the same bits
  *   "reference_reduction"    0         VALIDATION MODE (the one option that changes numbers).  1: H, G and the squared residual norm of every
