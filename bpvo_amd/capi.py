@@ -603,6 +603,40 @@ class Context:
         self._ck(self.b.fn("seq_get_params")(self.h, int(s), C.byref(p)))
         return p
 
+    # -- point budget (an extension: no reference member)
+    @staticmethod
+    def _budget_arg(max_points):
+        mp = [int(k) for k in (max_points if max_points is not None else [])]
+        return ((C.c_int * len(mp))(*mp) if mp else None), len(mp)
+
+    def set_point_budget(self, max_points):
+        """bpvo_hip_set_point_budget: at most max_points[l] template points at level l, the most salient first (0 / levels beyond the list: no
+        budget); from the next set_template on."""
+        arr, n = self._budget_arg(max_points)
+        self.call("set_point_budget", arr, n)
+
+    def get_point_budget(self):
+        out = (C.c_int * MAX_LEVELS)()
+        self._ck(self.b.fn("get_point_budget")(self.h, out))
+        return [int(v) for v in out][:self.L]
+
+    def seq_set_point_budget(self, s, max_points):
+        """bpvo_hip_seq_set_point_budget: sequence s's own budget in the place of the context's; an empty list returns it to the context's."""
+        arr, n = self._budget_arg(max_points)
+        self.call("seq_set_point_budget", int(s), arr, n)
+
+    def seq_get_point_budget(self, s):
+        """(budget per level, True if it is the sequence's own)"""
+        out, own = (C.c_int * MAX_LEVELS)(), C.c_int()
+        self._ck(self.b.fn("seq_get_point_budget")(self.h, int(s), out, C.byref(own)))
+        return [int(v) for v in out][:self.L], bool(own.value)
+
+    def selection_info(self, slot, level):
+        """bpvo_hip_get_selection_info: dict(n_candidates, threshold, n_ties_kept) of the slot's template at `level`."""
+        n, t, k = C.c_int(), C.c_float(), C.c_int()
+        self.call("get_selection_info", int(slot), int(level), C.byref(n), C.byref(t), C.byref(k))
+        return dict(n_candidates=n.value, threshold=np.float32(t.value), n_ties_kept=k.value)
+
     def seq_get_camera(self, s) -> Camera:
         cam = Camera()
         self._ck(self.b.fn("seq_get_camera")(self.h, int(s), C.byref(cam)))

@@ -87,6 +87,7 @@ void carve_frame_tmpl(bpvo_hip_ctx* c, FrameSlot& f, unsigned char* base, size_t
   }
   f.nrm = cv.take<float>(4 * kMaxLevels);
   f.n_dev = cv.take<int>(kMaxLevels);
+  f.sel_info = cv.take<int>(4 * kMaxLevels);
   if(total) *total = cv.off;
 }
 
@@ -134,6 +135,8 @@ FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l)
   // the selection thresholds: those of the slot's sequence (bpvo_hip_seq_set_params), or the context's
   const bpvo_hip_params& sp = f.seq_params ? *f.seq_params : c->params;
   j.min_saliency = sp.minSaliency; j.min_disp = sp.minValidDisparity; j.max_disp = sp.maxValidDisparity;
+  j.max_points = slot_budget(c, f, l);
+  j.sel_info = f.sel_info ? f.sel_info + 4 * l : nullptr;
   return j;
 }
 

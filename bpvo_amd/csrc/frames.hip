@@ -229,7 +229,18 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
   // the saliency map of a census-only level is not stored: whoever reads it has it formed first (ensure_saliency)
   for(int i = 0; i < count; ++i) {
     FrameSlot& f = c->frames[slots[i]];
-    for(int l = 0; l < c->L; ++l) f.sal_state[l] = f.lazy[l] == 2 ? FrameSlot::SAL_ON_DEMAND : FrameSlot::SAL_STORED;
+    // (... but it is stored for a level with a point budget: the budget's threshold is read from the map)
+    for(int l = 0; l < c->L; ++l) f.sal_state[l] = (f.lazy[l] == 2 && slot_budget(c, f, l) <= 0) ? FrameSlot::SAL_ON_DEMAND : FrameSlot::SAL_STORED;
+  }
+  // the point budgets of the stage: what each slot's levels run with (bpvo_hip_get_selection_info), and whether any level of any slot has one
+  bool budget_at[kMaxLevels] = {}, any_budget = false;
+  for(int i = 0; i < count; ++i) {
+    FrameSlot& f = c->frames[slots[i]];
+    f.min_saliency_used = (f.seq_params ? f.seq_params : &c->params)->minSaliency;
+    for(int l = 0; l < c->L; ++l) {
+      f.budget_used[l] = l >= c->params.maxTestLevel ? slot_budget(c, f, l) : 0;
+      if(f.budget_used[l] > 0) budget_at[l] = any_budget = true;
+    }
   }
   const FrameJob* tab = nullptr;
   int rc = upload_frame_jobs_slots(c, slots, count, fr, 1, &tab);
@@ -270,13 +281,35 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
     ScopedTimer t(c, KC_SALIENCY_SELECT, px, fr.ln);
     const LevelGeom& g = geom[p.maxTestLevel];
     launch_saliency_select(s, tab + (size_t) p.maxTestLevel * NF, c->C, g.cols, g.rows, count, 1, border, c->gauss_k,
-                           c->L - p.maxTestLevel, NF);
+                           c->L - p.maxTestLevel, NF, any_budget ? SELECT_CANDIDATES : SELECT_ALL);
+  }
+  if(one_launch && any_budget) {
+    // a stage with a point budget: the budget's kernel between the candidates and their scan (units: the pixels it may visit)
+    const LevelGeom& g = geom[p.maxTestLevel];
+    {
+      double px = 0;
+      for(int l = p.maxTestLevel; l < c->L; ++l) px += budget_at[l] ? (double) geom[l].npix * count : 0.0;
+      ScopedTimer t(c, KC_POINT_BUDGET, px, fr.ln);
+      launch_point_budget(s, tab + (size_t) p.maxTestLevel * NF, count, 1, c->L - p.maxTestLevel, NF);
+    }
+    ScopedTimer t(c, KC_SALIENCY_SELECT, 0.0, fr.ln);
+    launch_saliency_select(s, tab + (size_t) p.maxTestLevel * NF, c->C, g.cols, g.rows, count, 1, border, c->gauss_k,
+                           c->L - p.maxTestLevel, NF, SELECT_COMPACT);
   }
   for(int l = c->L - 1; l >= p.maxTestLevel && !one_launch; --l) {
     const FrameJob* jobs = tab + (size_t) l * NF;
     const LevelGeom& g = geom[l];
-    ScopedTimer t(c, KC_SALIENCY_SELECT, (double) g.npix * count, fr.ln);
-    launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, border, c->gauss_k);
+    {
+      ScopedTimer t(c, KC_SALIENCY_SELECT, (double) g.npix * count, fr.ln);
+      launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, border, c->gauss_k, 1, 0, budget_at[l] ? SELECT_CANDIDATES : SELECT_ALL);
+    }
+    if(!budget_at[l]) continue;
+    {
+      ScopedTimer t(c, KC_POINT_BUDGET, (double) g.npix * count, fr.ln);
+      launch_point_budget(s, jobs, count, g.nms_radius);
+    }
+    ScopedTimer t(c, KC_SALIENCY_SELECT, 0.0, fr.ln);
+    launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, border, c->gauss_k, 1, 0, SELECT_COMPACT);
   }
   if(side) {
     FR_CK(c, fr, hipEventRecord(c->side_ev[0], s));
@@ -424,9 +457,69 @@ int ensure_saliency(bpvo_hip_ctx* c, int slot, int level)
   return rc;
 }
 
+int check_point_budget(bpvo_hip_ctx* c, const int* max_points, int n_levels)
+{
+  if(n_levels < 0 || n_levels > c->L) return fail(c, BPVO_ERR_INVALID_ARG, "point budget: more levels than the context has");
+  if(n_levels > 0 && !max_points) return fail(c, BPVO_ERR_INVALID_ARG, "point budget: nullptr");
+  for(int l = 0; l < n_levels; ++l) {
+    if(max_points[l] < 0) return fail(c, BPVO_ERR_INVALID_ARG, "point budget: negative");
+    if(max_points[l] > 0 && max_points[l] < 16) return fail(c, BPVO_ERR_INVALID_ARG, "point budget: 1 .. 15 points would always give an empty template (templates are cut to a multiple of 16)");
+  }
+  return BPVO_OK;
+}
+
 }  // namespace bpvo_hip_host
 
 extern "C" {
+
+// ---- point budget (an extension: no reference member) -----------------------------------------------------------------
+int bpvo_hip_set_point_budget(bpvo_hip_ctx* c, const int* max_points, int n_levels)
+{
+  CHECK_CTX(c);
+  if(int rc = check_point_budget(c, max_points, n_levels)) return rc;
+  for(int l = 0; l < kMaxLevels; ++l) c->point_budget[l] = l < n_levels ? max_points[l] : 0;
+  return BPVO_OK;
+}
+int bpvo_hip_get_point_budget(const bpvo_hip_ctx* c, int* max_points)
+{
+  if(!c || !max_points) return BPVO_ERR_INVALID_ARG;
+  for(int l = 0; l < kMaxLevels; ++l) max_points[l] = c->point_budget[l];
+  return BPVO_OK;
+}
+int bpvo_hip_get_selection_info(bpvo_hip_ctx* c, int slot, int level, int* n_candidates, float* threshold, int* n_ties_kept)
+{
+  CHECK_CTX(c); CHECK_SLOT(c, slot); CHECK_LEVEL(c, level);
+  FrameSlot& f = c->frames[slot];
+  if(!f.has_template) return fail(c, BPVO_ERR_NO_TEMPLATE, "no template");
+  (void) hipSetDevice(c->device);
+  int info[4] = {0, 0, 0, 0};
+  float thr = f.min_saliency_used;
+  if(f.budget_used[level] > 0) {
+    // the record the budget's kernel left: {candidates, bits of the threshold, ties kept, 1 if the budget bound}
+    HIP_CK(c, hipMemcpyAsync(info, f.sel_info + 4 * level, sizeof(info), hipMemcpyDeviceToHost, c->stream));
+    HIP_CK(c, hipStreamSynchronize(c->stream));
+    if(info[3]) std::memcpy(&thr, &info[1], sizeof(float));
+    else info[2] = 0;
+  } else {
+    // no budget ran: the candidates are still all there, as bits (tiled selection) or flag bytes
+    const LevelGeom& g = slot_geom(c, f, level);
+    if(g.nms_radius <= 1) {
+      std::vector<unsigned long long> w((size_t) g.rows * ((g.cols + 63) / 64));
+      HIP_CK(c, hipMemcpyAsync(w.data(), f.flag[level], w.size() * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_CK(c, hipStreamSynchronize(c->stream));
+      for(unsigned long long v : w) info[0] += __builtin_popcountll(v);
+    } else {
+      std::vector<uint8_t> fl(g.npix);
+      HIP_CK(c, hipMemcpyAsync(fl.data(), f.flag[level], fl.size(), hipMemcpyDeviceToHost, c->stream));
+      HIP_CK(c, hipStreamSynchronize(c->stream));
+      for(uint8_t v : fl) info[0] += v ? 1 : 0;
+    }
+  }
+  if(n_candidates) *n_candidates = info[0];
+  if(threshold) *threshold = thr;
+  if(n_ties_kept) *n_ties_kept = info[2];
+  return BPVO_OK;
+}
 
 int bpvo_hip_frame_set_data(bpvo_hip_ctx* c, int slot, const uint8_t* image, const float* disparity)
 {

@@ -90,6 +90,13 @@ struct FrameSlot {
   // the algorithm parameters of the slot's sequence when they are not the context's own (bpvo_hip_seq_set_params: SeqState::params), else null;
   // the frame stages take the selection thresholds from them (make_frame_job)
   const bpvo_hip_params* seq_params = nullptr;
+  // the point budget (bpvo_hip_set_point_budget): the slot's sequence's own (bpvo_hip_seq_set_point_budget) in the place of the context's; what the last
+  // template stage applied per level, with the minSaliency it ran with (bpvo_hip_get_selection_info); the device record point_budget_kernel leaves
+  bool own_budget = false;
+  int budget[kMaxLevels] = {};
+  int budget_used[kMaxLevels] = {};
+  float min_saliency_used = 0.0f;
+  int* sel_info = nullptr;  // [L][4]
 };
 
 struct Workspace {
@@ -125,9 +132,9 @@ struct CovScratch {
 };
 
 enum KernelClass { KC_PYRAMID = 0, KC_DESCRIPTOR, KC_SALIENCY_SELECT, KC_NORMALIZATION, KC_TEMPLATE, KC_WARP_RESIDUAL, KC_MEDIAN,
-                   KC_IRLS_REDUCE, KC_GN_STEP, KC_COUNT };
+                   KC_IRLS_REDUCE, KC_GN_STEP, KC_POINT_BUDGET, KC_COUNT };
 static const char* const kKernelNames[KC_COUNT] = {"pyramid", "descriptor", "saliency_select", "normalization", "template_build", "warp_residual",
-                                      "median", "irls_reduce", "gn_step"};
+                                      "median", "irls_reduce", "gn_step", "point_budget"};
 
 struct EventPair { hipEvent_t a, b; int kc; double units; };
 
@@ -177,6 +184,7 @@ using namespace bpvo_hip_host;
 struct bpvo_hip_ctx {
 
   bpvo_hip_params params;
+  int point_budget[kMaxLevels] = {};   // bpvo_hip_set_point_budget: template points a level keeps at most, the most salient first (0: no budget)
   float K[9];
   float baseline;
   int rows, cols, L, C, device;
@@ -480,6 +488,10 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
                 const int* min_caps);
 // a frame slot's geometry at level l: its camera's, or the context's
 inline const LevelGeom& slot_geom(const bpvo_hip_ctx* c, const FrameSlot& f, int l) { return f.own_geom ? f.geom[l] : c->geom[l]; }
+// a frame slot's point budget at level l: its sequence's, or the context's
+inline int slot_budget(const bpvo_hip_ctx* c, const FrameSlot& f, int l) { return f.own_budget ? f.budget[l] : c->point_budget[l]; }
+// BPVO_OK, or why max_points [n_levels] is no budget of this context (0 or at least 16 per level: fewer would always give an empty template)
+int check_point_budget(bpvo_hip_ctx* c, const int* max_points, int n_levels);
 
 // ---- shared between the translation units (definitions: see the table at the top)
 int fail(bpvo_hip_ctx* c, int code, const char* msg);

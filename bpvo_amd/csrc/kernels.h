@@ -82,8 +82,12 @@ void launch_bitplanes(hipStream_t s, const FrameJob* jobs, int W, int R, int nfr
                       int job_pitch = 0);
 // (minSaliency and the disparity gate: each frame's own, FrameJob::min_saliency / min_disp / max_disp)
 // gauss_k: the bit-planes blur taps (census-only levels, FrameJob::lazy == 2: the tiles form channel 0 themselves)
+// part: everything, or — a stage with a point budget, which launch_point_budget serves in between — the candidates alone, then the scan and the compaction
+enum { SELECT_ALL = 0, SELECT_CANDIDATES = 1, SELECT_COMPACT = 2 };
 void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, const float gauss_k[3], int nlevels = 1,
-                            int job_pitch = 0);
+                            int job_pitch = 0, int part = SELECT_ALL);
+// of the candidates of every job with FrameJob::max_points > 0 the max_points most salient stay (kernels_frame.hip point_budget_kernel)
+void launch_point_budget(hipStream_t s, const FrameJob* jobs, int nframes, int nms_radius, int nlevels = 1, int job_pitch = 0);
 void launch_saliency(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes);      // the saliency map alone, from dense records
 void launch_copy_rows(hipStream_t s, void* dst, const void* src_host_pinned, size_t pitch_bytes, size_t width_bytes, int rows);   // multiples of 8 bytes
 void launch_gather_counts(hipStream_t s, const FrameJob* jobs /*[L][job_pitch]*/, int job_pitch, int nframes, int first_level, int num_levels,

@@ -1174,6 +1174,332 @@ __global__ __launch_bounds__(256) void select_words_write_kernel(const FrameJob*
   }
 }
 
+// ---- Point budget (an extension, no reference member): of the candidates of a (frame, level) keep the FrameJob::max_points most salient.
+// Between candidate formation and the scan, on both selection paths: WORDS — the candidate bits of the tiled path; otherwise the flag bytes and
+// chunk counts of the three-pass path.  One workgroup per (frame, level), the grid of the scan kernels; a frame without a budget, or whose
+// candidates fit it, leaves at once.
+// The threshold t is the K-th largest saliency, EXACT: saliencies are finite and non-negative, so their f32 bits order like unsigned integers, and
+// a radix select walks them from the top — bits [30:20], [19:10], [9:0].  Pass 1 is the only one that reads the map: at the candidates (a
+// wavefront per 64-pixel unit — a word, or 64 flags —, a lane per pixel: a unit's loads are one 256-byte run; every wavefront owns a contiguous
+// run of units), it counts the top digit and leaves the keys COMPACT IN RASTER ORDER in the level's index array (which the compaction behind the
+// scan overwrites): key i is candidate i.  Passes 2 and 3 read the keys.  Then who stays is decided on the keys, a bit per key: S > t, and of the
+// S == t ties the first K - #{S > t} in key order — every wavefront owns a contiguous run of keys, counts its ties, and ranks them behind the sum
+// of the runs in front of it (skipped when every tie stays).  Last, the losers' bits are cleared: a lane per word puts the bits of its
+// candidates back at the places of its set bits (flag path: a lane per pixel looks its bit up; the chunk counts are rewritten).
+// Per (frame, level) with n candidates: 4 n bytes of saliency in runs of 256 read once, 4 n bytes of keys written once and read three times
+// (four when ties are cut), n / 8 bytes of bits written and read, the words (or flags and chunk counts) read three times and rewritten.
+constexpr int PB_THREADS = 1024, PB_WAVES = PB_THREADS / 64;
+constexpr int PB_SPARSE_MAX = 512;      // 64 words with at most this many candidates (an eighth of their pixels) are walked a lane per word
+#ifndef PB_UB_WORDS
+#define PB_UB_WORDS 32
+#endif
+#ifndef PB_UB_FLAGS
+#define PB_UB_FLAGS 8
+#endif
+// histogram of `digit` over the lanes with `act`: one add for a wavefront whose digits agree (ties are massive on binary descriptors, and
+// 64 adds to one LDS address are 64 serial ones)
+__device__ __forceinline__ void pb_hist_add(int* hist, bool act, unsigned digit)
+{
+  const unsigned long long am = __ballot(act);
+  if(am == 0ull) return;
+  const unsigned d0 = (unsigned) __shfl((int) digit, __ffsll((long long) am) - 1);
+  const unsigned long long same = __ballot(act && digit == d0);
+  if(same == am) {
+    if((threadIdx.x & 63) == 0) atomicAdd(&hist[d0], __popcll(am));
+  } else if(act) {
+    atomicAdd(&hist[digit], 1);
+  }
+}
+// the bin that holds the k-th largest entry (1 <= k <= entries): s_res = {bin, k - entries above the bin, entries of the bin}; clears the histogram
+template <int BPT>
+__device__ __forceinline__ void pb_find_bin(int* hist, int* s_wave, int* s_res, int k)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int h[BPT], local = 0;
+#pragma unroll
+  for(int b = 0; b < BPT; ++b) { h[b] = hist[threadIdx.x * BPT + b]; local += h[b]; }
+  int incl = local;
+#pragma unroll
+  for(int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(incl, o);
+    if(lane >= o) incl += t;
+  }
+  if(lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int total = 0;
+#pragma unroll
+  for(int w = 0; w < PB_WAVES; ++w) { if(w < wave) incl += s_wave[w]; total += s_wave[w]; }
+  int above = total - incl;      // entries of the bins above this thread's
+#pragma unroll
+  for(int b = BPT - 1; b >= 0; --b) {
+    if(above < k && k <= above + h[b]) { s_res[0] = threadIdx.x * BPT + b; s_res[1] = k - above; s_res[2] = h[b]; }
+    above += h[b];
+  }
+#pragma unroll
+  for(int b = 0; b < BPT; ++b) hist[threadIdx.x * BPT + b] = 0;
+  __syncthreads();
+}
+// The 64-pixel units [u0, u1) (uniform over the wavefront) in order, PB_UB of them with their loads in flight together — a wavefront that waits for
+// one memory round trip per unit spends the whole stage waiting —: f(unit, candidate mask, this lane is a candidate, the bits of its saliency, its
+// pixel).  WORDS: unit u is word u — row u / WPR, columns 64 (u % WPR) ... —, 64 words per load, the next 64 fetched under the work on these;
+// otherwise pixels 64 u ... of the row-major scan, their flag bytes first.  LOAD = false: the masks alone, no saliency.
+template <bool WORDS, bool LOAD, class F>
+__device__ __forceinline__ void pb_walk(const FrameJob& j, const float* __restrict__ sal, int u0, int u1, F&& f)
+{
+  const int lane = threadIdx.x & 63;
+  const int W = j.cols, WPR = (W + 63) / 64, npix = W * j.rows;
+  const unsigned long long* const words = j.words;      // (not __restrict__: the last walk rewrites the units behind it)
+  const uint8_t* const flag = j.flag;
+  constexpr int PB_UB = WORDS ? PB_UB_WORDS : PB_UB_FLAGS;      // units in flight (the flag path holds their bytes as well)
+  unsigned long long wv_next = (WORDS && u0 + lane < u1) ? words[u0 + lane] : 0ull;
+  for(int ub = u0; ub < u1; ub += 64) {
+    const unsigned long long wv = wv_next;
+    if(WORDS && ub + 64 + lane < u1) wv_next = words[ub + 64 + lane];
+    const int wlo = (int) (unsigned) wv, whi = (int) (unsigned) (wv >> 32);
+    for(int b = 0; b < 64 && ub + b < u1; b += PB_UB) {
+      const int y0 = (ub + b) / WPR, xw0 = (ub + b) - y0 * WPR;      // (scalar: once per PB_UB units; then word by word along the rows)
+      unsigned key[PB_UB];
+      unsigned actbits = 0u;      // bit k: this lane is a candidate of unit ub + b + k
+      uint8_t fl[PB_UB];
+      if(!WORDS) {
+#pragma unroll
+        for(int k = 0; k < PB_UB; ++k) {
+          const int q = (ub + b + k) * 64 + lane;
+          fl[k] = (ub + b + k < u1 && q < npix) ? flag[q] : (uint8_t) 0;
+        }
+      }
+      int y = y0, xw = xw0;
+#pragma unroll
+      for(int k = 0; k < PB_UB; ++k) {
+        const int u = ub + b + k;
+        bool act;
+        int p;
+        if(WORDS) {
+          const unsigned long long mk = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(wlo, (b + k) & 63)) |
+                                        ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(whi, (b + k) & 63) << 32);
+          act = u < u1 && ((mk >> lane) & 1ull) != 0ull;
+          p = min(y * W + xw * 64 + lane, npix - 1);      // (the tiles set no bit past the image's columns; whatever a word holds, the load stays inside)
+          if(++xw == WPR) { xw = 0; ++y; }
+        } else {
+          p = u * 64 + lane;
+          act = fl[k] != 0;
+        }
+        key[k] = (LOAD && act) ? __float_as_uint(sal[p]) : 0u;
+        actbits |= (act ? 1u : 0u) << k;
+      }
+      y = y0; xw = xw0;
+#pragma unroll
+      for(int k = 0; k < PB_UB; ++k) {
+        const bool act = ((actbits >> k) & 1u) != 0u;
+        int p;
+        if(WORDS) {
+          p = y * W + xw * 64 + lane;
+          if(++xw == WPR) { xw = 0; ++y; }
+        } else {
+          p = (ub + b + k) * 64 + lane;
+        }
+        f(ub + b + k, __ballot(act), act, key[k], p);
+      }
+    }
+  }
+}
+template <bool WORDS>
+__global__ __launch_bounds__(PB_THREADS) void point_budget_kernel(const FrameJob* jobs, int nframes, int job_pitch)
+{
+  const FrameJob& j = level_job(jobs, blockIdx.x, nframes, job_pitch);
+  const int K = j.max_points;
+  if(K <= 0) return;                                 // no budget
+  __shared__ int s_hist[2048];
+  __shared__ int s_wave[PB_WAVES];
+  __shared__ int s_cnt[PB_WAVES];
+  __shared__ int s_res[3];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (a scalar for the compiler: the unit arithmetic below runs on the scalar unit)
+  const int W = j.cols, npix = W * j.rows;
+  const int nunits = WORDS ? j.rows * ((W + 63) / 64) : (npix + 63) / 64;
+  int* const info = j.sel_info;
+  // every wavefront a contiguous run of units (whole 256-pixel chunks: the flag path's counts are per chunk)
+  const int per = ((nunits + PB_WAVES - 1) / PB_WAVES + 63) & ~63;
+  const int u0 = min(wave * per, nunits), u1 = min(u0 + per, nunits);
+  // the candidates of the runs: set bits, or the chunk counts select_flag_kernel left
+  int cnt = 0;
+  if(WORDS) for(int i = u0 + lane; i < u1; i += 64) cnt += __popcll(j.words[i]);
+  else for(int i = (u0 >> 2) + lane; i < ((u1 + 3) >> 2); i += 64) cnt += j.blk_count[i];
+#pragma unroll
+  for(int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if(lane == 0) s_cnt[wave] = cnt;
+  for(int i = tid; i < 2048; i += PB_THREADS) s_hist[i] = 0;
+  __syncthreads();
+  int n_cand = 0, key_base = 0;                      // all candidates; those of the runs in front of this wavefront's
+#pragma unroll
+  for(int w = 0; w < PB_WAVES; ++w) { if(w < wave) key_base += s_cnt[w]; n_cand += s_cnt[w]; }
+  if(n_cand <= K) {                                  // within the budget: nothing changes
+    if(tid == 0) { info[0] = n_cand; info[1] = (int) __float_as_uint(j.min_saliency); info[2] = 0; info[3] = 0; }
+    return;
+  }
+  const float* __restrict__ const sal = j.sal;
+  unsigned* const keys = reinterpret_cast<unsigned*>(j.inds.get());
+  const int cap = j.cap;      // (the capacity bounds the candidates a level can have — context.hip level_geometry —: every key has its place)
+  // pass 1: the top digit's histogram; the keys compact, behind those of the runs in front
+  int fill = key_base;
+  auto per_pixel = [&](int, unsigned long long m, bool act, unsigned key, int) {
+    const int r = fill + __popcll(m & ((1ull << lane) - 1ull));
+    if(act && r < cap) keys[r] = key;
+    fill += __popcll(m);
+    pb_hist_add(s_hist, act, key >> 20);
+  };
+  if constexpr(WORDS) {
+    // 64 words at a time.  Where they hold few candidates — a level with non-maximum suppression: three or four per word — a lane per pixel is 60
+    // lanes idle for every one at work, and the stage is bound by the issue of ONE compute unit: there a lane takes a word and walks its set bits,
+    // four loads in flight.  Dense words go a lane per pixel.
+    const int WPR = (W + 63) / 64;
+    for(int ub = u0; ub < u1; ub += 64) {
+      const int u = ub + lane;
+      const unsigned long long word = u < u1 ? j.words[u] : 0ull;
+      const int c = __popcll(word);
+      int incl = c;
+#pragma unroll
+      for(int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if(lane >= o) incl += v;
+      }
+      const int total = __builtin_amdgcn_readlane(incl, 63);
+      if(total == 0) continue;
+      if(total > PB_SPARSE_MAX) { pb_walk<WORDS, true>(j, sal, ub, min(ub + 64, u1), per_pixel); continue; }
+      const int off = fill + incl - c;
+      const int y = u / WPR, pbase = y * W + (u - y * WPR) * 64;
+      unsigned long long rest = word;
+      for(int n = 0; __ballot(rest != 0ull) != 0ull; n += 4) {
+        unsigned key[4];
+        bool v[4];
+#pragma unroll
+        for(int q = 0; q < 4; ++q) {
+          v[q] = rest != 0ull;
+          const int bit = v[q] ? __ffsll((long long) rest) - 1 : 0;
+          rest &= rest - 1ull;
+          key[q] = v[q] ? __float_as_uint(sal[min(pbase + bit, npix - 1)]) : 0u;
+        }
+#pragma unroll
+        for(int q = 0; q < 4; ++q) {
+          if(v[q] && off + n + q < cap) keys[off + n + q] = key[q];
+          pb_hist_add(s_hist, v[q], key[q] >> 20);
+        }
+      }
+      fill += total;
+    }
+  } else {
+    pb_walk<WORDS, true>(j, sal, u0, u1, per_pixel);
+  }
+  __syncthreads();
+  const int nkeys = min(n_cand, cap);
+  pb_find_bin<2>(s_hist, s_wave, s_res, K);
+  unsigned prefix = (unsigned) s_res[0];
+  int k_rem = s_res[1], n_eq = 0;
+  __syncthreads();
+  // passes 2 and 3 over the compact keys: the digits below, among the keys that share the digits above
+#pragma unroll
+  for(int pass = 0; pass < 2; ++pass) {
+    const int shift = pass == 0 ? 10 : 0;
+    for(int i0 = 0; i0 < nkeys; i0 += 4 * PB_THREADS) {
+      unsigned kk[4];
+#pragma unroll
+      for(int q = 0; q < 4; ++q) { const int i = i0 + q * PB_THREADS + tid; kk[q] = i < nkeys ? keys[i] : 0xffffffffu; }
+#pragma unroll
+      for(int q = 0; q < 4; ++q) pb_hist_add(s_hist, (kk[q] >> (shift + 10)) == prefix, (kk[q] >> shift) & 1023u);      // (no key has bit 31: the filler never matches)
+    }
+    __syncthreads();
+    pb_find_bin<1>(s_hist, s_wave, s_res, k_rem);
+    prefix = (prefix << 10) | (unsigned) s_res[0];
+    k_rem = s_res[1];
+    n_eq = s_res[2];
+    __syncthreads();
+  }
+  const unsigned t = prefix;
+  const int quota = k_rem;                           // ties to keep (>= 1) of the n_eq there are
+  if(tid == 0) { info[0] = n_cand; info[1] = (int) t; info[2] = quota; info[3] = 1; }
+  // Who stays, a bit per key in key order = raster order (in the level's compact point records, which the compaction behind the scan overwrites:
+  // 8 bytes per capacity point).  Every wavefront a contiguous run of keys, whole 64-key words; where ties are cut the wavefronts count the
+  // ties of their runs first, and a tie's rank is the ties in front of its run + those in front of it inside.
+  unsigned long long* const keepw = reinterpret_cast<unsigned long long*>(j.ptc.get());
+  const int kper = ((nkeys + PB_WAVES - 1) / PB_WAVES + 63) & ~63;
+  const int k0 = min(wave * kper, nkeys), k1 = min(k0 + kper, nkeys);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int running = 0;
+  if(quota < n_eq) {
+    int mine = 0;
+    for(int i0 = k0; i0 < k1; i0 += 8 * 64) {
+      unsigned kk[8];
+#pragma unroll
+      for(int q = 0; q < 8; ++q) { const int i = i0 + q * 64 + lane; kk[q] = i < k1 ? keys[i] : 0xffffffffu; }
+#pragma unroll
+      for(int q = 0; q < 8; ++q) mine += __popcll(__ballot(kk[q] == t));
+    }
+    if(lane == 0) s_wave[wave] = mine;
+    __syncthreads();
+    for(int w = 0; w < wave; ++w) running += s_wave[w];
+  }
+  for(int i0 = k0; i0 < k1; i0 += 8 * 64) {
+    unsigned kk[8];
+#pragma unroll
+    for(int q = 0; q < 8; ++q) { const int i = i0 + q * 64 + lane; kk[q] = i < k1 ? keys[i] : 0xffffffffu; }
+#pragma unroll
+    for(int q = 0; q < 8; ++q) {
+      const bool in = i0 + q * 64 + lane < k1, eq = kk[q] == t;      // (the filler has bit 31, no key has: it never ties)
+      const unsigned long long m_eq = __ballot(eq);
+      const bool keep = in && (kk[q] > t || (eq && (quota >= n_eq || running + __popcll(m_eq & below) < quota)));
+      const unsigned long long kw = __ballot(keep);
+      if(lane == 0 && i0 + q * 64 < k1) keepw[(i0 + q * 64) >> 6] = kw;
+      running += __popcll(m_eq);
+    }
+  }
+  __syncthreads();
+  // the losers leave: candidate i of the raster order is key i
+  if(WORDS) {
+    // a lane per word: the word's candidates are keys [off, off + popcount), their bits go back to the places of the word's set bits
+    const int nkw = (nkeys + 63) >> 6;
+    int base = key_base;
+    for(int ub = u0; ub < u1; ub += 64) {
+      const int u = ub + lane;
+      const unsigned long long word = u < u1 ? j.words[u] : 0ull;
+      const int c = __popcll(word);
+      int incl = c;
+#pragma unroll
+      for(int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if(lane >= o) incl += v;
+      }
+      const int off = base + incl - c;
+      base += __shfl(incl, 63);
+      if(c == 0 || off + c > nkeys) continue;
+      const int w0 = off >> 6, sh = off & 63;
+      unsigned long long kb = keepw[w0] >> sh;
+      if(sh + c > 64 && w0 + 1 < nkw) kb |= keepw[w0 + 1] << (64 - sh);
+      unsigned long long keep = 0ull, rest = word;
+      while(rest) {
+        const unsigned long long lowest = rest & (0ull - rest);
+        if(kb & 1ull) keep |= lowest;
+        kb >>= 1;
+        rest ^= lowest;
+      }
+      if(keep != word) j.words[u] = keep;
+    }
+  } else {
+    // a lane per pixel: the flag bytes, and the chunk counts the scan reads
+    int at = key_base, chunk_cnt = 0;
+    pb_walk<false, false>(j, nullptr, u0, u1, [&](int u, unsigned long long m, bool act, unsigned, int p) {
+      const int i = at + __popcll(m & below);
+      const bool kept = act && i < nkeys && ((keepw[i >> 6] >> (i & 63)) & 1ull) != 0ull;
+      if(act && !kept) j.flag[p] = 0;
+      at += __popcll(m);
+      chunk_cnt += __popcll(__ballot(kept));
+      if(u < u1 && ((u & 3) == 3 || u == u1 - 1)) {
+        if(lane == 0) j.blk_count[u >> 2] = chunk_cnt;
+        chunk_cnt = 0;
+      }
+    });
+  }
+}
+
 // ---- Hartley normalisation (reference: bpvo/warps.cc:27-48, bpvo/rigid_body_warp.h:62-71).
 // The reference sums N points sequentially in f32; to reproduce its rounding the sums here are sequential too: chunks staged in LDS, one
 // wave adding in point order.  It runs once per keyframe and level, all levels and frames side by side.  The dependent adds are the whole
@@ -1763,8 +2089,9 @@ void launch_saliency(hipStream_t s, const FrameJob* jobs, int C, int W, int R, i
   if(C <= 48 || !dispatch_wide_channels(C, plain)) dispatch_channels(C, plain);
 }
 void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, const float gauss_k[3], int nlevels,
-                            int job_pitch)
+                            int job_pitch, int part)
 {
+  const bool form = part != SELECT_COMPACT, compact = part != SELECT_CANDIDATES;
   if(nms_radius <= 1) {
     // tiles: saliency + NMS + gate in one pass, candidate bits, word scan, lane-per-pixel compaction
     const int WPR = (W + 63) / 64, nw = R * WPR;
@@ -1772,18 +2099,28 @@ void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, i
       hipLaunchKernelGGL(saliency_select_tile_kernel<decltype(c)::value>, dim3(WPR, (R + ST_H - 1) / ST_H, nframes * nlevels), dim3(256), 0, s, jobs,
                          border, nframes, job_pitch, gauss_k[0], gauss_k[1], gauss_k[2]);
     };
-    if(C <= 48 || !dispatch_wide_channels(C, tile)) dispatch_channels(C, tile);
+    if(form && (C <= 48 || !dispatch_wide_channels(C, tile))) dispatch_channels(C, tile);
+    if(!compact) return;
     hipLaunchKernelGGL(select_words_scan_kernel, dim3(nframes * nlevels), dim3(1024), 0, s, jobs, nframes, job_pitch);
     hipLaunchKernelGGL(select_words_write_kernel, dim3((nw + 4 * SW_WORDS - 1) / (4 * SW_WORDS), 1, nframes * nlevels), dim3(256), 0, s, jobs, nframes,
                        job_pitch);
     return;
   }
   // larger NMS windows: the saliency map first, then flag bytes / chunk scan / compaction straight from it
-  launch_saliency(s, jobs, C, W, R, nframes);
   const int nblk = (W * R + SEL_BLOCK_PX - 1) / SEL_BLOCK_PX;
-  hipLaunchKernelGGL(select_flag_kernel, dim3(nblk, 1, nframes), dim3(256), 0, s, jobs, border);
+  if(form) {
+    launch_saliency(s, jobs, C, W, R, nframes);
+    hipLaunchKernelGGL(select_flag_kernel, dim3(nblk, 1, nframes), dim3(256), 0, s, jobs, border);
+  }
+  if(!compact) return;
   hipLaunchKernelGGL(select_scan_kernel, dim3(nframes), dim3(1024), 0, s, jobs);
   hipLaunchKernelGGL(select_write_kernel, dim3(nblk, 1, nframes), dim3(256), 0, s, jobs);
+}
+// the point budget between the two parts of launch_saliency_select (SELECT_CANDIDATES, SELECT_COMPACT), with the jobs and the grid of its scan
+void launch_point_budget(hipStream_t s, const FrameJob* jobs, int nframes, int nms_radius, int nlevels, int job_pitch)
+{
+  if(nms_radius <= 1) hipLaunchKernelGGL(point_budget_kernel<true>, dim3(nframes * nlevels), dim3(PB_THREADS), 0, s, jobs, nframes, job_pitch);
+  else hipLaunchKernelGGL(point_budget_kernel<false>, dim3(nframes), dim3(PB_THREADS), 0, s, jobs, nframes, 0);
 }
 // Small control tables (job rows, initial poses) copied by a KERNEL that reads the pinned host rows directly: while the upload pipeline
 // keeps the DMA engines busy with 45 MB chunks a hipMemcpyAsync of a few KB on a lane's stream waits its turn behind them

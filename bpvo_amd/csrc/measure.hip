@@ -33,7 +33,7 @@ int bpvo_hip_get_kernel_stats(bpvo_hip_ctx* c, bpvo_hip_kernel_stat* out, int ma
   // algorithmic bytes per unit: unit = template point for the GN kernels, pixel otherwise
   const double C = c->C;
   const double bpu[KC_COUNT] = {2.0, 1.0 + 4.0 * C, 4.0 * C + 4.0 + 4.0, 32.0, 16.0 + 4.0 + 5.0 * 4.0 * C + 28.0 * C, 18.0 + 24.0 * C,
-                                4.0 * C, 2.0 + 28.0 * C, 0.0};
+                                4.0 * C, 2.0 + 28.0 * C, 0.0, 0.0};      // (the step and the point budget: a workgroup per pair / per frame level, no stream to rate)
   int n = 0;
   for(int k = 0; k < KC_COUNT && n < max_out; ++k, ++n) {
     std::memset(&out[n], 0, sizeof(out[n]));

@@ -261,7 +261,11 @@ struct FrameJob {
   // the selection thresholds of the frame's sequence (bpvo_hip_seq_set_params; the context's everywhere else): minSaliency and the disparity gate
   // [minValidDisparity, maxValidDisparity] — read from here by the selection kernels, so that one launch serves frames of several parameter sets
   float          min_saliency, min_disp, max_disp;
-  int            lazy;      // 1 (C = 8 bit-planes, template frames of a pair batch at the NMS levels): the level's 32-byte records are NOT
+  // the point budget of the frame at this level (bpvo_hip_set_point_budget / bpvo_hip_seq_set_point_budget; 0: none): at most this many candidates, the
+  // most salient first, survive point_budget_kernel; sel_info: the {candidates, bits of the threshold, ties kept, 1 if the budget bound} it leaves
+  int            max_points;
+  GPtr<int> sel_info;
+  int            lazy;     // 1 (C = 8 bit-planes, template frames of a pair batch at the NMS levels): the level's 32-byte records are NOT
                             // stored — `cen` holds the census bytes and `ch0` channel 0 (all the selection needs); template_build
                             // forms the records of its stencils from the census bytes (kernels_frame.hip)
                             // 2 (option lazy_template_saliency, NMS radius 1): census-only — `ch0` is null too, census_templates_kernel writes

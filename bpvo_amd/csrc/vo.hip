@@ -1093,6 +1093,27 @@ int bpvo_hip_seq_reset(bpvo_hip_ctx* c, int seq)
   if(!c->seqs.empty()) seq_reset_state(c, seq);
   return BPVO_OK;
 }
+// A sequence's own point budget (an extension: no reference member), kept on its three frame slots: it outlives bpvo_hip_seq_reset like the
+// sequence's parameters; n_levels = 0 returns the sequence to the context's budget
+int bpvo_hip_seq_set_point_budget(bpvo_hip_ctx* c, int seq, const int* max_points, int n_levels)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  if(int rc = check_point_budget(c, max_points, n_levels)) return rc;
+  for(int k = 0; k < 3; ++k) {
+    FrameSlot& f = c->frames[3 * seq + k];
+    f.own_budget = n_levels > 0;
+    for(int l = 0; l < kMaxLevels; ++l) f.budget[l] = l < n_levels ? max_points[l] : 0;
+  }
+  return BPVO_OK;
+}
+int bpvo_hip_seq_get_point_budget(const bpvo_hip_ctx* c, int seq, int* max_points, int* own)
+{
+  if(!c || !max_points || seq < 0 || seq >= seq_capacity(c)) return BPVO_ERR_INVALID_ARG;
+  const FrameSlot& f = c->frames[3 * seq];
+  for(int l = 0; l < kMaxLevels; ++l) max_points[l] = slot_budget(c, f, l);
+  if(own) *own = f.own_budget ? 1 : 0;
+  return BPVO_OK;
+}
 static const SeqState* seq_state(const bpvo_hip_ctx* c, int seq) { return c->seqs.empty() ? nullptr : &c->seqs[seq]; }
 int bpvo_hip_seq_num_points_at_level(bpvo_hip_ctx* c, int seq, int level, int* n)
 {

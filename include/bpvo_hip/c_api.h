@@ -290,6 +290,33 @@ int bpvo_hip_seq_get_camera(const bpvo_hip_ctx* ctx, int seq, bpvo_hip_camera* c
 int bpvo_hip_seq_set_params(bpvo_hip_ctx* ctx, int seq, const bpvo_hip_params* p);
 int bpvo_hip_seq_get_params(const bpvo_hip_ctx* ctx, int seq, bpvo_hip_params* p);
 
+/* ---- Point budget: at most max_points[l] template points at level l, the most salient first.  AN EXTENSION: the reference has no such
+ * member (its template size follows from minSaliency, the non-maximum suppression and the scene alone).  Off by default; nothing changes while
+ * it is off or while a level's candidates fit its budget.
+ * The rule, per frame and level with budget K > 0: cand = the pixels today's selection keeps (border, saliency >= minSaliency, the NMS test where
+ * the level has one, the disparity gate), before the cut to a multiple of 16.  |cand| <= K: nothing changes.  Otherwise t = the K-th largest
+ * saliency of cand (exact); every candidate with S > t stays, and of those with S == t the first K - #{S > t} in raster order.  The kept set
+ * stays in raster order and is cut to a multiple of 16 as ever: N = min(K, capacity) & ~15.  When #{S >= t} == K the template is, bit for bit,
+ * the one minSaliency = max(minSaliency, t) gives without a budget.
+ * bpvo_hip_set_point_budget (an extension, no reference member): the context's budget — single frames, bpvo_hip_add_frame,
+ *   bpvo_hip_frames_set_template, pair batches, and every sequence without a budget of its own.  max_points [n_levels], level 0 first; the levels
+ *   beyond n_levels have none; 0 = no budget at that level.  Takes effect at the next template; existing templates are untouched.  A value of
+ *   1 .. 15 (always an empty template) or below 0, or n_levels above the context's levels: BPVO_ERR_INVALID_ARG, the setting stays as it was.
+ * bpvo_hip_get_point_budget (an extension, no reference member): the setting, max_points [BPVO_HIP_MAX_LEVELS]. */
+int bpvo_hip_set_point_budget(bpvo_hip_ctx* ctx, const int* max_points /*[n_levels]*/, int n_levels);
+int bpvo_hip_get_point_budget(const bpvo_hip_ctx* ctx, int* max_points /*[BPVO_HIP_MAX_LEVELS]*/);
+/* bpvo_hip_seq_set_point_budget (an extension, no reference member): sequence seq's own budget in the place of the context's, for
+ *   bpvo_hip_add_frames, bpvo_hip_add_frames_stereo and the members of rigs; n_levels = 0 returns the sequence to the context's budget.  It
+ *   outlives bpvo_hip_seq_reset, as the sequence's parameters do.  Refusals as above, and for a sequence the context does not have.
+ * bpvo_hip_seq_get_point_budget (an extension, no reference member): the budget the sequence's next template runs with, max_points
+ *   [BPVO_HIP_MAX_LEVELS]; own (may be null): 1 if it is the sequence's own. */
+int bpvo_hip_seq_set_point_budget(bpvo_hip_ctx* ctx, int seq, const int* max_points /*[n_levels]*/, int n_levels);
+int bpvo_hip_seq_get_point_budget(const bpvo_hip_ctx* ctx, int seq, int* max_points /*[BPVO_HIP_MAX_LEVELS]*/, int* own);
+/* bpvo_hip_get_selection_info (an extension, no reference member; a diagnostic, valid after set_template, synchronises): what the selection
+ *   of the slot's template did at `level` — n_candidates = |cand|; threshold = t, or the frame's minSaliency when no budget was set or it did
+ *   not bind; n_ties_kept = K - #{S > t}, the candidates with S == t that stayed (0 when the budget did not bind).  Outputs may be null. */
+int bpvo_hip_get_selection_info(bpvo_hip_ctx* ctx, int slot, int level, int* n_candidates, float* threshold, int* n_ties_kept);
+
 /* ---- batches of independent frame pairs (BASELINE.json config 5).
  * Pair p uses frame slots 2p (reference/template frame A) and 2p+1 (current frame B) and workspace p.
  * For each pair: A.setData, A.setTemplate, B.setData, estimatePose(A, B, Identity) -> poses[p].

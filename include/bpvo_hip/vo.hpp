@@ -188,6 +188,16 @@ class Device {
   /* how the device schedules its work (c_api.h "Options"); no counterpart in the reference */
   void setOption(const std::string& name, double value) { check(bpvo_hip_set_option(_ctx, name.c_str(), value)); }
   double getOption(const std::string& name) const { double v = 0.0; check(bpvo_hip_get_option(_ctx, name.c_str(), &v)); return v; }
+  /* the point budget (c_api.h bpvo_hip_set_point_budget; an extension, no counterpart in the reference): the context's, or sequence seq's own */
+  void setPointBudget(const std::vector<int>& maxPoints) { check(bpvo_hip_set_point_budget(_ctx, maxPoints.data(), (int) maxPoints.size())); }
+  void setPointBudget(int seq, const std::vector<int>& maxPoints) { check(bpvo_hip_seq_set_point_budget(_ctx, seq, maxPoints.data(), (int) maxPoints.size())); }
+  /* finestLevel points at level 0 and a quarter of the level below at every level above it, rounded down to a multiple of 16, never below 256 */
+  std::vector<int> quarteredPointBudget(int finestLevel) const
+  {
+    std::vector<int> b((size_t) bpvo_hip_num_levels(_ctx));
+    for(size_t l = 0; l < b.size(); ++l) b[l] = std::max(256, (int) ((long long) finestLevel >> (2 * l)) & ~15);
+    return b;
+  }
  private:
   bpvo_hip_ctx* _ctx;
   ImageSize _size;
@@ -376,6 +386,10 @@ class VisualOdometry {
   const Trajectory& trajectory() const { return _trajectory; }   // bpvo/vo.h:98
   /* scheduling options of the device context (c_api.h "Options"; the reference has none) */
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  /* at most maxPoints[l] template points at level l, the most salient first (an extension; c_api.h bpvo_hip_set_point_budget); from the next key frame on */
+  void setPointBudget(const std::vector<int>& maxPoints) { _dev->setPointBudget(maxPoints); }
+  /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
+  void setPointBudget(int finestLevelPoints) { _dev->setPointBudget(_dev->quarteredPointBudget(finestLevelPoints)); }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   /* Result::covariance carries the covariance of the estimated pose (option "pose_covariance"); poseCovariance(): the last frame's record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
@@ -513,6 +527,11 @@ class VisualOdometrySequences {
     _trajectories.at((size_t) s)._poses.clear();
   }
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  /* at most maxPoints[l] template points at level l of sequence s, the most salient first (an extension; c_api.h bpvo_hip_seq_set_point_budget); an
+   * empty list returns the sequence to the context's budget */
+  void setPointBudget(int s, const std::vector<int>& maxPoints) { _dev->setPointBudget(s, maxPoints); }
+  /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
+  void setPointBudget(int s, int finestLevelPoints) { _dev->setPointBudget(s, _dev->quarteredPointBudget(finestLevelPoints)); }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   /* Result::covariance of every sequence carries the covariance of its estimated pose (option "pose_covariance"); poseCovariance(s): sequence s's last record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
@@ -625,6 +644,10 @@ class RigVisualOdometry {
     return n;
   }
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  /* at most maxPoints[l] template points at level l, the most salient first (an extension; c_api.h bpvo_hip_set_point_budget); from the next key frame on */
+  void setPointBudget(const std::vector<int>& maxPoints) { _dev->setPointBudget(maxPoints); }
+  /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
+  void setPointBudget(int finestLevelPoints) { _dev->setPointBudget(_dev->quarteredPointBudget(finestLevelPoints)); }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   /* Result::covariance carries the covariance of the BODY pose, in the plain body twist (option "pose_covariance"); poseCovariance(): the last frame's record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
@@ -738,6 +761,10 @@ class RigsVisualOdometry {
     return n;
   }
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  /* at most maxPoints[l] template points at level l, the most salient first (an extension; c_api.h bpvo_hip_set_point_budget); from the next key frame on */
+  void setPointBudget(const std::vector<int>& maxPoints) { _dev->setPointBudget(maxPoints); }
+  /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
+  void setPointBudget(int finestLevelPoints) { _dev->setPointBudget(_dev->quarteredPointBudget(finestLevelPoints)); }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
   /* the record of the rig's last frame: the covariance of its BODY pose, in the plain body twist */
