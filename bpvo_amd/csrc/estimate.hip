@@ -1,5 +1,13 @@
-// libbpvo_hip, host side: VisualOdometryPoseEstimator::estimatePose — the host drivers of the Gauss-Newton kernels (four-kernel chain with pipelined
-// rounds, persistent single-pair kernel, team kernel), the operator-level seam (linearize, residuals, weights) and bpvo_hip_batch_estimate.
+// libbpvo_hip, host side: VisualOdometryPoseEstimator::estimatePose.  estimate_group, the driver of every estimate of cameras, is
+//   1. group_upload         the group's job tables and initial poses
+//   2. run_team             small batches: every level of every pair in ONE launch of the team kernel (or two: the split form)
+//   3. run_levels           otherwise level by level, coarse to fine: run_level_persistent (the level in one launch) or run_level_chain (the four-kernel
+//                           chain in pipelined rounds: gn_rounds.h run_rounds queues linearize_launches)
+//   4. queue_fraction_good  the result records, and addFrame's count of good points behind the estimate
+//   5. group_collect        states and control words back, the one synchronisation; a persistent form gave up: 1 .. 5 once more without
+//   6. group_outputs        poses and statistics
+// The rig estimates (estimate_rigs) run on the same rounds and the same launches.  Also here: the operator-level seam (linearize, residuals, weights)
+// and bpvo_hip_batch_estimate.
 #include "host_ctx.h"
 
 using namespace bpvo_hip;
@@ -9,11 +17,7 @@ namespace bpvo_hip_host {
 
 // ---- estimatePose ---------------------------------------------------------------------------------------------------
 
-// VisualOdometryPoseEstimator::estimatePose (reference: bpvo/vo_pose_estimator.cc:63-93) for a group of `n` workspaces on one
-// lane.  wss[i]: workspace, refs[i] / curs[i]: frame slots.  T_init host [n][16] or null (Identity).
-// Does a group of n pairs take the team-persistent kernel?  (kLinear, the f64 formulation, C = 8 or 1 like gn_persistent_kernel; not
-// while per-kernel timings are being collected: there are no kernels to time)
-// The shape of the team launch for a group of n pairs — ONE place decides it, for the launcher below and for team_serves: one workgroup per CU,
+// The shape of the team launch for a group of n pairs — ONE place decides it, for run_team below and for team_serves: one workgroup per CU,
 // teams of CUs / pairs workgroups (at most an eighth of the device's CUs, 32 of 256: teams of 64 were 8 - 12 % slower at 2 - 5 pairs, 4 % at 6 - 7; a
 // team's workgroups stay dealt over ALL XCDs — pinned to one XCD each, 2 - 4 teams were 3 - 8 % slower), as many teams as fit; whether idle
 // workgroups may join other teams (the growing form), and how many spare workgroups the division leaves for that.
@@ -34,6 +38,8 @@ static TeamPlan team_plan(const bpvo_hip_ctx* c, int n)
   return t;
 }
 
+// Does a group of n pairs take the team-persistent kernel?  (kLinear, the f64 formulation, C = 8 or 1 like gn_persistent_kernel; not
+// while per-kernel timings are being collected: there are no kernels to time)
 bool team_serves(const bpvo_hip_ctx* c, int n)
 {
   bool size_ok = n >= 2 && n > c->persist_max_ws && n <= c->team_max_pairs;
@@ -95,27 +101,99 @@ static int for_each_loss(int n, LossOf&& loss_of, Run&& run)
   return BPVO_OK;
 }
 
-// allow_persistent: only a group that has the device to itself (a batch on ONE lane) may take the persistent kernel — two
-// hand-barrier grids of concurrent lanes must not be co-scheduled.
-int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* refs, const int* curs, const float* T_init,
-                   float* poses, bpvo_hip_stats* stats, float* d_records_out, bool allow_persistent, const bpvo_hip_params* const* prms)
+// One linearisation of the jobs of g at their states' poses: warp_residual (K6) per channel group, the median (K7), the reduction (K8) per channel
+// group — or once, in reference order —, and the step unless the reduction takes it.  The ONE place that queues these four kernels: the estimate
+// loops of cameras and rigs, the operator-level seam and the pose-covariance pass (its residuals: the warp alone) all come here.
+void linearize_launches(bpvo_hip_ctx* c, Lane* ln, const GNLaunch& g, size_t stride, const LinearizeFlags& f)
 {
-  if(n <= 0) return BPVO_OK;
-  (void) hipSetDevice(c->device);
-  const bpvo_hip_params& p = c->params;
+  constexpr unsigned kProfileEvery = 5;   // co-prime with kItersPerSync: no phase lock with the host round trips
+  const bool all = f.timers == TIMERS_ALWAYS || (f.timers != TIMERS_OFF && c->profile_all);
+  if(f.warp) {
+    // TIMERS_ESTIMATE, level 1, brackets every kProfileEvery-th warp_residual launch of the lane with events (a running counter, so the
+    // sampled launches rotate through all iterations and levels): an event pair costs a few µs of dispatch gap
+    const bool sampled = all || (f.timers == TIMERS_ESTIMATE && (c->profile_k6_all || (ln->k6_seq++ % kProfileEvery) == 0));
+    ScopedTimer t(c, KC_WARP_RESIDUAL, 0.0, ln, sampled);
+    for_each_group(c, g, stride, [&](const GNLaunch& gg) { launch_warp_residual(ln->stream, gg); });
+  }
+  // level 2 times every kernel; level 3 (bench.py's single-lane roofline pass) every warp_residual AND every irls_reduce launch
+  { ScopedTimer t(c, KC_MEDIAN, 0.0, ln, all && f.median); if(f.median) launch_median(ln->stream, median_launch(c, g)); }
+  if(f.reduce) {
+    ScopedTimer t(c, KC_IRLS_REDUCE, 0.0, ln, all || (f.timers == TIMERS_ESTIMATE && c->profile_k6_all));
+    if(g.reference_reduction) launch_irls_reduce(ln->stream, g);      // (reference order: one wave per pair walks every channel of the whole job)
+    else for_each_group(c, g, stride, [&](const GNLaunch& gg) { launch_irls_reduce(ln->stream, gg); });
+  }
+  if(f.step && !g.step_in_reduce) {
+    ScopedTimer t(c, KC_GN_STEP, 0.0, ln, all);
+    launch_gn_step(ln->stream, g, f.step_mode);
+  }
+}
+
+// run_rounds (gn_rounds.h) on a lane: a round's flags are marked by the lane's event of the slot ("the flags of round r have landed"), which the
+// host waits for a round later.  queue_flags(slot): the copy of the flags into the slot's pinned words.
+template <class QueueIterations, class QueueFlags, class Read>
+static int lane_rounds(Lane* ln, int max_iterations, QueueIterations&& queue_iterations, QueueFlags&& queue_flags, Read&& read)
+{
+  return run_rounds(max_iterations, queue_iterations,
+                    [&](int slot) -> int {
+                      if(int rc = queue_flags(slot)) return rc;
+                      LANE_CK(ln, hipEventRecord(ln->round_ev[slot], ln->stream));
+                      return BPVO_OK;
+                    },
+                    [&](int slot) -> int {
+                      LANE_CK(ln, hipEventSynchronize(ln->round_ev[slot]));
+                      return BPVO_OK;
+                    },
+                    read);
+}
+
+// One estimate_group call: what its steps share.  The modes are set per attempt (group_modes).
+struct GroupRun {
+  bpvo_hip_ctx* c;
+  Lane* ln;
+  int n;
+  const int* wss; const int* refs; const int* curs;      // [n] workspace, template slot, current slot
+  const float* T_init;                                   // host [n][16] or null (Identity)
+  const bpvo_hip_params* const* prms;                    // [n] or null
+  float* d_records_out;
   // the group's loss (one per group: estimate_batch) and the largest iteration limit among its entries: the host sizes its rounds by it, the
   // device enforces each workspace's own (PairJob::prm)
-  const int loss = prms ? prms[0]->lossFunction : p.lossFunction;
-  int max_iterations = p.maxIterations;
-  if(prms) {
-    max_iterations = prms[0]->maxIterations;
-    for(int i = 1; i < n; ++i) max_iterations = std::max(max_iterations, prms[i]->maxIterations);
-  }
-  const int NP = c->n_pairs;
+  int loss, max_iterations;
+  std::vector<int> max_pts;      // [L] the most points of a job at the level
+  // validation mode "reference_reduction": the four-kernel chain with the index-order reduction in irls_reduce's place — residuals always written
+  // (no fused path), the step in its own launch, no persistent / team kernel
+  bool ref_mode;
+  int fuse_frozen;
+  bool allow_persistent;         // this attempt may take the persistent forms
+  bool pk_group;                 // ... and is a group for the persistent single-pair kernel
+  bool small_ctx;                // a context of a few pairs (one pair per call): table, poses and control words in one launch, the states copied out by the last one
+  bool l2_moot;                  // kL2: the weights are 1 whatever the robust scale — with the fused path every linearisation is irls_reduce + gn_step only
+  bool team_ran, team_split, frac_queued;
+};
+static void group_modes(GroupRun& r, bool allow_persistent)
+{
+  const bpvo_hip_ctx* c = r.c;
+  r.ref_mode = c->reference_reduction != 0;
+  r.fuse_frozen = r.ref_mode ? 0 : c->fuse_frozen;
+  r.allow_persistent = allow_persistent;
+  r.pk_group = allow_persistent && c->persistent && !c->persistent_failed.load() && r.n <= c->persist_max_ws && !c->profile_all && !r.ref_mode;
+  r.small_ctx = (size_t) c->L * c->n_pairs <= 64 && r.n <= 8 && c->small_batch_fused && c->G == 1;
+  r.l2_moot = r.loss == BPVO_LOSS_L2 && c->C == 8 && r.fuse_frozen && !c->fast_warp && c->params.interp == BPVO_INTERP_LINEAR;
+  r.team_ran = r.team_split = r.frac_queued = false;
+}
+
+// 1. the job tables of the group (dense levels without the tap cache), and the initial poses into the states of the coarsest level's jobs
+static int group_upload(GroupRun& r)
+{
+  bpvo_hip_ctx* c = r.c;
+  Lane* ln = r.ln;
+  const int n = r.n, NP = c->n_pairs;
+  const int* refs = r.refs;
+  const float* T_init = r.T_init;
+  const bool persistent = r.pk_group;
   // (the pinned staging of a lane is free here: every call that uses it ends with a synchronisation of the lane's stream)
-  std::vector<int> max_pts(c->L, 0);
+  std::fill(r.max_pts.begin(), r.max_pts.end(), 0);
   const size_t table = (size_t) c->L * NP;
-  fill_job_tables(c, ln, 0, n, wss, refs, curs, [&](int i) { return prms ? prms[i] : nullptr; }, max_pts.data());
+  fill_job_tables(c, ln, 0, n, r.wss, refs, r.curs, [&](int i) { return r.prms ? r.prms[i] : nullptr; }, r.max_pts.data());
   // Dense levels (no non-maximum suppression: most pixels are template points) gather their taps straight from the descriptor:
   // neighbouring points share three quarters of their footprints, so the 32-byte records are fetched about once per pixel
   // from HBM, where the per-point tap cache reads 128 bytes per point whatever the neighbours do.  The cache pays at the
@@ -127,15 +205,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
         PairJob& pj = ln->h_pjobs[(size_t) l * NP + i];
         if((double) pj.n > c->tapcache_max_density * (double) slot_geom(c, c->frames[refs[i]], l).npix) pj.tapcache_on = 0;
       }
-  // validation mode "reference_reduction": the four-kernel chain with the index-order reduction in irls_reduce's place — residuals always written
-  // (no fused path), the step in its own launch, no persistent / team kernel
-  const bool ref_mode = c->reference_reduction != 0;
-  const int fuse_frozen = ref_mode ? 0 : c->fuse_frozen;
-  const bool pk_group = allow_persistent && c->persistent && !c->persistent_failed.load() && n <= c->persist_max_ws && !c->profile_all && !ref_mode;
-  bool persistent = pk_group;
-  // a context of a few pairs (one pair per call): table, poses and control words in one launch, the states copied out by the last one
-  const bool small_ctx = (size_t) c->L * NP <= 64 && n <= 8 && c->small_batch_fused && c->G == 1;
-  if(small_ctx) {
+  if(r.small_ctx) {
     if(T_init) std::memcpy(ln->h_T, T_init, sizeof(float) * 16 * n);
     launch_set_pose_upload(ln->stream, ln->d_pjobs, ln->h_pjobs, (size_t) c->L * NP, ln->h_pjobs + (size_t) (c->L - 1) * NP, T_init ? ln->h_T : nullptr, n,
                            persistent ? ln->d_pk_ctl : nullptr, persistent ? kPkCtlWords * kMaxLevels : 0);
@@ -152,211 +222,202 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
     }
     launch_set_pose(ln->stream, ln->d_pjobs + (size_t) (c->L - 1) * NP, dT, n, persistent ? ln->d_pk_ctl : nullptr, persistent ? kPkCtlWords * kMaxLevels : 0);
   }
+  return BPVO_OK;
+}
 
-  // Small batches: the whole level loop in ONE launch, a team of workgroups per pair (gn_team_kernel)
-  bool team_ran = false;
-  // the normalisation of the levels below the coarsest, of the template stage queued just before (frames.hip, ctx->nrm_pending), may still be
-  // running on the context's side stream: this lane waits for it where the second level starts — the team kernel, every level in one launch, at once
-  // (level: the pyramid level about to start — the finest level's own event is joined only there; < 0: everything)
-  auto join_normalization = [&](int level) -> int {
-    if(c->nrm_pending) {
-      LANE_CK(ln, hipStreamWaitEvent(ln->stream, c->nrm_pending, 0));
-      c->nrm_pending = nullptr;
-    }
-    if(c->nrm_pending_finest && (level < 0 || level <= p.maxTestLevel)) {
-      LANE_CK(ln, hipStreamWaitEvent(ln->stream, c->nrm_pending_finest, 0));
-      c->nrm_pending_finest = nullptr;
-    }
-    return BPVO_OK;
-  };
-  bool team_split = false;
-  if(allow_persistent && ln == &c->lanes[0] && team_serves(c, n) && templates_suit_teams(c, n, refs)) {
-    // Small batches whose template stage left the normalisation of the levels below the coarsest on the side stream (frames.hip): the
-    // team kernel in TWO launches — the coarsest level of every pair, then (behind that normalisation) the others.  The sums (0.17 - 0.19 ms
-    // for a 1241x376 frame, whatever the batch) then run under the coarsest level's iterations instead of in front of the first one;
-    // larger batches join them here, at once: a launch boundary makes every pair wait for the slowest (measured: 2 / 4 pairs + 1.2 / + 1.5 %,
-    // 8 / 16 / 32 / 64 pairs - 5 / - 7 / - 4 / - 6 %: option "team_split_max_pairs", 4).
-    team_split = (c->nrm_pending != nullptr || c->nrm_pending_finest != nullptr) && n <= c->team_split_max_pairs && c->L - 1 > p.maxTestLevel;
-    if(!team_split)
-      if(int rcj = join_normalization(-1)) return rcj;
-    GNTeamLaunch t;
-    t.jobs_all = ln->d_pjobs; t.job_pitch = NP; t.n_pairs = n; t.level_hi = c->L - 1; t.level_lo = p.maxTestLevel;
-    t.C = c->C; t.loss = loss; t.fuse_frozen = c->fuse_frozen;
-    t.scale_is_moot = (loss == BPVO_LOSS_L2 && c->C == 8 && c->fuse_frozen) ? 1 : 0;
-    const TeamPlan plan = team_plan(c, n);      // (the same plan team_serves judged)
-    t.team_size = plan.team_size;
-    t.n_teams = plan.n_teams;
-    t.ctl = ln->d_team_ctl;
-    t.timeout_ticks = c->persist_timeout;
-    t.local_barriers = c->team_local_barriers;
-    t.join_mode = plan.join_mode;
-    t.spare_workgroups = plan.spare_workgroups;
-    LANE_CK(ln, hipMemsetAsync(ln->d_team_ctl, 0, sizeof(unsigned) * (size_t) gn_team_ctl_words(t.n_teams), ln->stream));
-    hipError_t te;
-    if(team_split) {
-      t.level_lo = c->L - 1;
-      te = launch_gn_team(ln->stream, t);
-      if(te == hipSuccess) {
-        // (the first launch's control words: its abort word and join count are looked at with the second's)
-        LANE_CK(ln, hipMemcpyAsync(ln->h_team_ctl + 32, ln->d_team_ctl, sizeof(unsigned) * 32, hipMemcpyDeviceToHost, ln->stream));
-        launch_team_ctl_reset_keep_abort(ln->stream, ln->d_team_ctl, t.n_teams);      // (a first launch that gave up: the second leaves at once)
-      }
-      if(int rcj = join_normalization(-1)) return rcj;
-      t.level_hi = c->L - 2; t.level_lo = p.maxTestLevel;
-      if(te == hipSuccess) te = launch_gn_team(ln->stream, t);
-    } else {
-      te = launch_gn_team(ln->stream, t);
-    }
+// 2. Small batches: the whole level loop in ONE launch, a team of workgroups per pair (gn_team_kernel).  r.team_ran: the launch went out — a
+// launch the device refuses degrades the context to the chain, now and for later calls.
+static int run_team(GroupRun& r)
+{
+  bpvo_hip_ctx* c = r.c;
+  Lane* ln = r.ln;
+  const bpvo_hip_params& p = c->params;
+  const int n = r.n;
+  // Small batches whose template stage left the normalisation of the levels below the coarsest on the side stream (frames.hip): the
+  // team kernel in TWO launches — the coarsest level of every pair, then (behind that normalisation) the others.  The sums (0.17 - 0.19 ms
+  // for a 1241x376 frame, whatever the batch) then run under the coarsest level's iterations instead of in front of the first one;
+  // larger batches join them here, at once: a launch boundary makes every pair wait for the slowest (measured: 2 / 4 pairs + 1.2 / + 1.5 %,
+  // 8 / 16 / 32 / 64 pairs - 5 / - 7 / - 4 / - 6 %: option "team_split_max_pairs", 4).
+  r.team_split = (c->nrm_pending != nullptr || c->nrm_pending_finest != nullptr) && n <= c->team_split_max_pairs && c->L - 1 > p.maxTestLevel;
+  if(!r.team_split) LANE_CK(ln, join_pending_normalization(c, ln->stream));
+  GNTeamLaunch t;
+  t.jobs_all = ln->d_pjobs; t.job_pitch = c->n_pairs; t.n_pairs = n; t.level_hi = c->L - 1; t.level_lo = p.maxTestLevel;
+  t.C = c->C; t.loss = r.loss; t.fuse_frozen = c->fuse_frozen;
+  t.scale_is_moot = (r.loss == BPVO_LOSS_L2 && c->C == 8 && c->fuse_frozen) ? 1 : 0;
+  const TeamPlan plan = team_plan(c, n);      // (the same plan team_serves judged)
+  t.team_size = plan.team_size;
+  t.n_teams = plan.n_teams;
+  t.ctl = ln->d_team_ctl;
+  t.timeout_ticks = c->persist_timeout;
+  t.local_barriers = c->team_local_barriers;
+  t.join_mode = plan.join_mode;
+  t.spare_workgroups = plan.spare_workgroups;
+  LANE_CK(ln, hipMemsetAsync(ln->d_team_ctl, 0, sizeof(unsigned) * (size_t) gn_team_ctl_words(t.n_teams), ln->stream));
+  hipError_t te;
+  if(r.team_split) {
+    t.level_lo = c->L - 1;
+    te = launch_gn_team(ln->stream, t);
     if(te == hipSuccess) {
-      team_ran = true;
-      c->team_launches.fetch_add(1);
-      LANE_CK(ln, hipMemcpyAsync(ln->h_team_ctl, ln->d_team_ctl, sizeof(unsigned) * 32, hipMemcpyDeviceToHost, ln->stream));
-    } else {
-      (void) hipGetLastError();
-      c->persistent_failed.store(true);      // degrade to the chain, now and for later calls
+      // (the first launch's control words: its abort word and join count are looked at with the second's)
+      LANE_CK(ln, hipMemcpyAsync(ln->h_team_ctl + 32, ln->d_team_ctl, sizeof(unsigned) * 32, hipMemcpyDeviceToHost, ln->stream));
+      launch_team_ctl_reset_keep_abort(ln->stream, ln->d_team_ctl, t.n_teams);      // (a first launch that gave up: the second leaves at once)
     }
+    LANE_CK(ln, join_pending_normalization(c, ln->stream));
+    t.level_hi = c->L - 2; t.level_lo = p.maxTestLevel;
+    if(te == hipSuccess) te = launch_gn_team(ln->stream, t);
+  } else {
+    te = launch_gn_team(ln->stream, t);
   }
-  auto level_launch = [&](int l) {
-    GNLaunch g;
-    g.jobs = ln->d_pjobs + (size_t) l * NP;
-    g.npairs = n;
-    g.max_points = max_pts[l];
-    g.C = c->C;
-    g.loss = loss;
-    g.fast_warp = c->fast_warp;
-    g.interp = p.interp;
-    g.fuse_frozen = fuse_frozen;
-    g.step_in_reduce = (n <= c->step_in_reduce_max && !ref_mode && c->G == 1) ? 1 : 0;
-    g.reference_reduction = ref_mode ? 1 : 0;
-    g.dense_candidates = dense_candidates(c, g.max_points);
-    return g;
-  };
-  // kL2: the weights are 1 whatever the robust scale — with the fused path every linearisation is irls_reduce + gn_step only
-  const bool l2_moot = loss == BPVO_LOSS_L2 && c->C == 8 && fuse_frozen && !c->fast_warp && p.interp == BPVO_INTERP_LINEAR;
+  if(te == hipSuccess) {
+    r.team_ran = true;
+    c->team_launches.fetch_add(1);
+    LANE_CK(ln, hipMemcpyAsync(ln->h_team_ctl, ln->d_team_ctl, sizeof(unsigned) * 32, hipMemcpyDeviceToHost, ln->stream));
+  } else {
+    (void) hipGetLastError();
+    c->persistent_failed.store(true);      // degrade to the chain, now and for later calls
+  }
+  return BPVO_OK;
+}
+
+// the launch of level l's kernels over the whole group
+static GNLaunch group_level_launch(const GroupRun& r, int l)
+{
+  const bpvo_hip_ctx* c = r.c;
+  GNLaunch g = level_launch(c, r.ln->d_pjobs + (size_t) l * c->n_pairs, r.n, r.max_pts[l], r.loss);
+  g.fuse_frozen = r.fuse_frozen;
+  g.step_in_reduce = (r.n <= c->step_in_reduce_max && !r.ref_mode && c->G == 1) ? 1 : 0;
+  return g;
+}
+static bool persistent_serves_level(const GroupRun& r, int l)
+{
+  return r.max_pts[l] > 0 && gn_persistent_serves(group_level_launch(r, l)) && r.max_pts[l] <= r.c->persist_max_points;
+}
+
+// 3a. The whole level l in one launch of the persistent kernel — and the start of the next level with it, when that one takes the kernel too.
+// was_begun: this level's start was left to this launch by the one before.
+struct PersistentLevel { bool served, began_next; };
+static PersistentLevel run_level_persistent(GroupRun& r, GNLaunch g, int l, bool was_begun)
+{
+  bpvo_hip_ctx* c = r.c;
+  Lane* ln = r.ln;
+  const bool next_too = l - 1 >= c->params.maxTestLevel && persistent_serves_level(r, l - 1);
+  g.begin_level = was_begun ? l : -1;
+  g.begin_moot = r.l2_moot ? 1 : 0;
+  g.next_jobs = next_too ? ln->d_pjobs + (size_t) (l - 1) * c->n_pairs : nullptr;
+  const hipError_t pe = launch_gn_persistent(ln->stream, g, ln->d_pk_ctl + (size_t) l * kPkCtlWords, gn_persistent_grid(g, c->persist_grid), c->persist_timeout);
+  if(pe == hipSuccess) {
+    c->persistent_levels.fetch_add(1);
+    return {true, next_too};
+  }
+  // the device cannot grant the kernel its LDS / residency (or the launch failed): degrade to the four-kernel chain — this level,
+  // the rest of the pyramid and every later call of the context — instead of failing the estimate
+  (void) hipGetLastError();
+  c->persistent_failed.store(true);
+  if(was_begun) launch_level_begin(ln->stream, g.jobs, r.n, g.max_points, l, r.l2_moot ? 1 : 0);
+  return {false, false};
+}
+
+// 3b. The level on the four-kernel chain, in pipelined rounds (gn_rounds.h): a round's flags are the compacted list of the still-active
+// workspaces, its count and how many of them still estimate their scale; round r + 1 runs over the list that came out of round r - 1.
+static int run_level_chain(GroupRun& r, GNLaunch g)
+{
+  bpvo_hip_ctx* c = r.c;
+  Lane* ln = r.ln;
+  const int NP = c->n_pairs;
+  const size_t table = (size_t) c->L * NP;
+  int* const lists[3] = {ln->d_list, ln->d_list + NP, ln->d_list + 2 * (size_t) NP};
+  int n_cur = r.n;
+  g.active.list = nullptr;                // first rounds: every workspace of the group, in order
+  // Once NO active workspace of the list estimates its robust scale any more (a frozen scale stays frozen for the level, and the
+  // list only shrinks), the median has nothing to do and — with the fused path, where irls_reduce recomputes the residuals of
+  // frozen workspaces itself — neither has warp_residual: their launches are dropped for the rest of the level.  (Each would
+  // still cost its floor of ~5 us per iteration in the tail of a level.)  l2_moot: true from the first linearisation.
+  const bool fused_path = c->C == 8 && r.fuse_frozen && !c->fast_warp && c->params.interp == BPVO_INTERP_LINEAR;
+  bool none_moving = r.l2_moot;
+  LinearizeFlags f;
+  f.timers = TIMERS_ESTIMATE;
+  return lane_rounds(ln, r.max_iterations,
+                     [&](int) -> int {
+                       g.npairs = n_cur;
+                       f.median = !none_moving;
+                       f.warp = !(none_moving && fused_path);
+                       for(int k = 0; k < kItersPerSync; ++k) linearize_launches(c, ln, g, table, f);
+                       return BPVO_OK;
+                     },
+                     [&](int slot) -> int {
+                       launch_compact_active(ln->stream, g.jobs, g.active, n_cur, lists[slot], ln->d_active + 2 * slot);
+                       LANE_CK(ln, hipMemcpyAsync(ln->h_active + 2 * slot, ln->d_active + 2 * slot, 2 * sizeof(int), hipMemcpyDeviceToHost, ln->stream));
+                       return BPVO_OK;
+                     },
+                     [&](int slot) {
+                       const int n_left = ln->h_active[2 * slot];
+                       if(n_left <= 0) return false;
+                       n_cur = n_left;
+                       none_moving = none_moving || ln->h_active[2 * slot + 1] == 0;
+                       g.active.list = lists[slot];
+                       return true;
+                     });
+}
+
+// 3. Level by level, coarse to fine.  A level the persistent kernel does not serve takes the chain, and the rest of the pyramid with it.
+static int run_levels(GroupRun& r)
+{
+  bpvo_hip_ctx* c = r.c;
+  Lane* ln = r.ln;
+  bool persistent = r.pk_group;
   bool begun = false;      // this level's start was left to its persistent kernel (its tap-cache keys invalidated by the kernel of the level before)
-  for(int l = c->L - 1; l >= p.maxTestLevel && !team_ran; --l) {
-    GNLaunch g = level_launch(l);
-    if(l < c->L - 1)
-      if(int rcj = join_normalization(l)) return rcj;
+  for(int l = c->L - 1; l >= c->params.maxTestLevel; --l) {
+    const GNLaunch g = group_level_launch(r, l);
+    // (the deferred normalisation: this lane waits for it where the second level starts)
+    if(l < c->L - 1) LANE_CK(ln, join_pending_normalization(c, ln->stream, l));
     const bool was_begun = begun;
     begun = false;
-    if(!was_begun) launch_level_begin(ln->stream, g.jobs, n, g.max_points, l, l2_moot ? 1 : 0);    // (and the tap-cache keys of the level)
+    if(!was_begun) launch_level_begin(ln->stream, g.jobs, r.n, g.max_points, l, r.l2_moot ? 1 : 0);    // (and the tap-cache keys of the level)
     if(g.max_points <= 0) continue;
-    if(persistent && gn_persistent_serves(g) && g.max_points <= c->persist_max_points) {
-      // the whole level in one launch — and the start of the next level with it, when that one takes the kernel too
-      const bool next_too = l - 1 >= p.maxTestLevel && max_pts[l - 1] > 0 && gn_persistent_serves(level_launch(l - 1)) && max_pts[l - 1] <= c->persist_max_points;
-      g.begin_level = was_begun ? l : -1;
-      g.begin_moot = l2_moot ? 1 : 0;
-      g.next_jobs = next_too ? ln->d_pjobs + (size_t) (l - 1) * NP : nullptr;
-      const hipError_t pe = launch_gn_persistent(ln->stream, g, ln->d_pk_ctl + (size_t) l * kPkCtlWords, gn_persistent_grid(g, c->persist_grid), c->persist_timeout);
-      if(pe == hipSuccess) {
-        c->persistent_levels.fetch_add(1);
-        begun = next_too;
-        continue;
-      }
-      // the device cannot grant the kernel its LDS / residency (or the launch failed): degrade to the four-kernel chain — this level,
-      // the rest of the pyramid and every later call of the context — instead of failing the estimate
-      (void) hipGetLastError();
-      c->persistent_failed.store(true);
-      if(was_begun) launch_level_begin(ln->stream, g.jobs, n, g.max_points, l, l2_moot ? 1 : 0);
+    if(persistent && persistent_serves_level(r, l)) {
+      const PersistentLevel pk = run_level_persistent(r, g, l, was_begun);
+      begun = pk.began_next;
+      if(pk.served) continue;
     }
-    persistent = false;     // (a level the kernel does not serve: the rest of the pyramid takes the chain as well)
-    // At most maxIterations + 2 linearisations per level (pose_estimator_base.h:373-393); the state machine on the device
-    // enforces the limits, the host queues rounds of kItersPerSync iterations until the device reports no active workspace.
-    // Every round ends with a compaction of the list of still-active workspaces (ActiveSet, kernels.h) and the copy of its
-    // count.  The rounds are PIPELINED: round r + 1 is queued with the list and count that came out of round r - 1, as soon
-    // as those have landed — the device never waits for the host (a synchronisation per round was a ~30 us bubble: 7 % of a
-    // round at 128 pairs, 11 % for a single pair).  Workspaces that finished in between are still dispatched for one more
-    // round (their workgroups exit on the first load), and the level ends with one round of empty launches.
-    const int max_lin = std::min(std::max(max_iterations, 0) + 2, kMaxFunEvals);
-    const int kItersPerSync = 4;
-    const int max_rounds = (max_lin + kItersPerSync - 1) / kItersPerSync + 2;
-    constexpr unsigned kProfileEvery = 5;   // co-prime with kItersPerSync: no phase lock with the host round trips
-    int* const lists[3] = {ln->d_list, ln->d_list + NP, ln->d_list + 2 * (size_t) NP};
-    int n_cur = n;
-    g.active.list = nullptr;                // first rounds: every workspace of the group, in order
-    // Once NO active workspace of the list estimates its robust scale any more (a frozen scale stays frozen for the level, and the
-    // list only shrinks), the median has nothing to do and — with the fused path, where irls_reduce recomputes the residuals of
-    // frozen workspaces itself — neither has warp_residual: their launches are dropped for the rest of the level.  (Each would
-    // still cost its floor of ~5 us per iteration in the tail of a level.)  l2_moot: true from the first linearisation.
-    const bool fused_path = c->C == 8 && fuse_frozen && !c->fast_warp && p.interp == BPVO_INTERP_LINEAR;
-    bool none_moving = l2_moot;
-    for(int round = 0; round < max_rounds; ++round) {
-      g.npairs = n_cur;
-      const bool launch_median_k = !none_moving, launch_warp_k = !(none_moving && fused_path);
-      for(int k = 0; k < kItersPerSync; ++k) {
-        // level 1 brackets every kProfileEvery-th warp_residual launch of the lane with events (a running counter, so the
-        // sampled launches rotate through all iterations and levels): an event pair costs a few µs of dispatch gap
-        if(launch_warp_k) {
-          const bool sampled = c->profile_all || c->profile_k6_all || (ln->k6_seq++ % kProfileEvery) == 0;
-          ScopedTimer t(c, KC_WARP_RESIDUAL, 0.0, ln, sampled);
-          for_each_group(c, g, table, [&](const GNLaunch& gg) { launch_warp_residual(ln->stream, gg); });
-        }
-        // level 2 times every kernel; level 3 (bench.py's single-lane roofline pass) every warp_residual AND every irls_reduce launch
-        { ScopedTimer t(c, KC_MEDIAN, 0.0, ln, c->profile_all && launch_median_k); if(launch_median_k) launch_median(ln->stream, median_launch(c, g)); }
-        {
-          ScopedTimer t(c, KC_IRLS_REDUCE, 0.0, ln, c->profile_all || c->profile_k6_all);
-          if(ref_mode) launch_irls_reduce(ln->stream, g);      // (reference order: one wave per pair walks every channel of the whole job)
-          else for_each_group(c, g, table, [&](const GNLaunch& gg) { launch_irls_reduce(ln->stream, gg); });
-        }
-        if(!g.step_in_reduce) {
-          ScopedTimer t(c, KC_GN_STEP, 0.0, ln, c->profile_all);
-          launch_gn_step(ln->stream, g, 0);
-        }
-      }
-      const int slot = round % 3;
-      launch_compact_active(ln->stream, g.jobs, g.active, n_cur, lists[slot], ln->d_active + 2 * slot);
-      LANE_CK(ln, hipMemcpyAsync(ln->h_active + 2 * slot, ln->d_active + 2 * slot, 2 * sizeof(int), hipMemcpyDeviceToHost, ln->stream));
-      LANE_CK(ln, hipEventRecord(ln->round_ev[slot], ln->stream));
-      if(round == 0) continue;              // nothing to learn yet: queue the second round behind the first
-      const int prev = (round - 1) % 3;
-      LANE_CK(ln, hipEventSynchronize(ln->round_ev[prev]));
-      const int n_prev = ln->h_active[2 * prev];
-      if(n_prev <= 0) break;                // (the round just queued runs empty)
-      n_cur = n_prev;
-      none_moving = none_moving || ln->h_active[2 * prev + 1] == 0;
-      g.active.list = lists[prev];
-    }
+    persistent = false;
+    if(int rc = run_level_chain(r, g)) return rc;
   }
-  const bool want_frac = n == 1 && c->prefetch_frac_thr >= 0.0f && ln == &c->lanes[0];
-  if(small_ctx) launch_pack_records(ln->stream, ln->d_pjobs + (size_t) (c->L - 1) * NP, n, c->L, d_records_out, c->d_states, ln->h_states, pk_group ? ln->d_pk_ctl : nullptr,
-                                    pk_group ? ln->h_pk_ctl : nullptr, kPkCtlWords * kMaxLevels, want_frac ? c->d_count : nullptr);
-  else launch_pack_records(ln->stream, ln->d_pjobs + (size_t) (c->L - 1) * NP, n, c->L, d_records_out);
-  bool frac_queued = false;
-  if(want_frac) {
-    // fraction_good of this workspace at the level the estimate ended on, from the job already on the device
-    const PairJob* job = ln->d_pjobs + (size_t) p.maxTestLevel * NP;
-    const int npts = ln->h_pjobs[(size_t) p.maxTestLevel * NP].n;
-    if(npts > 0) {
-      GNLaunch gr;
-      gr.jobs = job; gr.npairs = 1; gr.max_points = npts; gr.C = c->C;
-      launch_refresh_residuals(ln->stream, gr);
-      if(!small_ctx) LANE_CK(ln, hipMemsetAsync(c->d_count, 0, sizeof(unsigned int), ln->stream));      // (small contexts: cleared by pack_records)
-      launch_count_good(ln->stream, job, npts, c->C, p.lossFunction, c->prefetch_frac_thr, c->d_count);
-      LANE_CK(ln, hipMemcpyAsync(c->h_ints, c->d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, ln->stream));
-      frac_queued = true;
-      c->frac_n = npts;
-    }
-  }
-  // only this group's states: other lanes may still be writing theirs
-  int ws_lo = wss[0], ws_hi = wss[0];
-  for(int i = 1; i < n; ++i) { ws_lo = std::min(ws_lo, wss[i]); ws_hi = std::max(ws_hi, wss[i]); }
-  if(!small_ctx) {
-    LANE_CK(ln, hipMemcpyAsync(ln->h_states + ws_lo, c->d_states + ws_lo, sizeof(GNState) * (size_t) (ws_hi - ws_lo + 1), hipMemcpyDeviceToHost, ln->stream));
-    if(pk_group)
-      LANE_CK(ln, hipMemcpyAsync(ln->h_pk_ctl, ln->d_pk_ctl, sizeof(unsigned) * kPkCtlWords * kMaxLevels, hipMemcpyDeviceToHost, ln->stream));
-  }
-  if(c->before_final_sync && ln == &c->lanes[0]) {      // (every kernel of the estimate is queued: the host is free for a moment)
-    const std::function<int()> f = std::move(c->before_final_sync);
-    c->before_final_sync = nullptr;
-    if(const int rcf = f()) return rcf;
-  }
-  LANE_CK(ln, hipStreamSynchronize(ln->stream));
-  LANE_CK(ln, hipGetLastError());
-  if(frac_queued) { c->frac_valid = true; c->frac_ws = wss[0]; c->frac_thr = c->prefetch_frac_thr; c->frac_cnt = (unsigned) c->h_ints[0]; }
+  return BPVO_OK;
+}
+
+// 4. The result records; and for addFrame (one pair, lane 0) the fraction of good points of the workspace at the level the estimate ended on,
+// from the job already on the device, queued behind the estimate
+static int queue_fraction_good(GroupRun& r)
+{
+  bpvo_hip_ctx* c = r.c;
+  Lane* ln = r.ln;
+  const bpvo_hip_params& p = c->params;
+  const int NP = c->n_pairs;
+  const PairJob* coarsest = ln->d_pjobs + (size_t) (c->L - 1) * NP;
+  const bool want_frac = r.n == 1 && c->prefetch_frac_thr >= 0.0f && ln == &c->lanes[0];
+  if(r.small_ctx) launch_pack_records(ln->stream, coarsest, r.n, c->L, r.d_records_out, c->d_states, ln->h_states, r.pk_group ? ln->d_pk_ctl : nullptr,
+                                      r.pk_group ? ln->h_pk_ctl : nullptr, kPkCtlWords * kMaxLevels, want_frac ? c->d_count : nullptr);
+  else launch_pack_records(ln->stream, coarsest, r.n, c->L, r.d_records_out);
+  const int npts = ln->h_pjobs[(size_t) p.maxTestLevel * NP].n;
+  if(!want_frac || npts <= 0) return BPVO_OK;
+  const PairJob* job = ln->d_pjobs + (size_t) p.maxTestLevel * NP;
+  launch_refresh_residuals(ln->stream, level_launch(c, job, 1, npts, p.lossFunction));
+  if(!r.small_ctx) LANE_CK(ln, hipMemsetAsync(c->d_count, 0, sizeof(unsigned int), ln->stream));      // (small contexts: cleared by pack_records)
+  launch_count_good(ln->stream, job, npts, c->C, p.lossFunction, c->prefetch_frac_thr, c->d_count);
+  LANE_CK(ln, hipMemcpyAsync(c->h_ints, c->d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, ln->stream));
+  r.frac_queued = true;
+  c->frac_n = npts;
+  return BPVO_OK;
+}
+
 #ifdef BPVO_PK_TIMING
-  if(pk_group) {     // library built with -DBPVO_PK_TIMING: per-phase ticks (10 ns) of workgroup 0
-    static const char* names[6] = {"warp", "barrier1", "median", "irls", "barrier2", "step"};
+// library built with -DBPVO_PK_TIMING: per-phase ticks (10 ns) of workgroup 0 of the persistent kernel / of team 0's first workgroup
+static void print_pk_timing(const GroupRun& r)
+{
+  const bpvo_hip_ctx* c = r.c;
+  const Lane* ln = r.ln;
+  static const char* names[6] = {"warp", "barrier1", "median", "irls", "barrier2", "step"};
+  if(r.pk_group) {
     for(int l = c->L - 1; l >= 0; --l) {
       const unsigned* t = ln->h_pk_ctl + (size_t) l * kPkCtlWords;
       if(!t[15]) continue;
@@ -367,8 +428,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
       std::fprintf(stderr, " us per iteration\n");
     }
   }
-  if(team_ran) {       // phases of team 0's first workgroup
-    static const char* names[6] = {"warp", "barrier1", "median", "irls", "barrier2", "step"};
+  if(r.team_ran) {
     for(int l = c->L - 1; l >= 0 && l < 4; --l) {
       const unsigned* t = ln->h_team_ctl + 4 + 7 * l;
       if(!t[6]) continue;
@@ -377,29 +437,104 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
       std::fprintf(stderr, " us per iteration\n");
     }
   }
+}
 #endif
-  if(team_ran) c->team_joins.fetch_add(ln->h_team_ctl[3] + (team_split ? ln->h_team_ctl[32 + 3] : 0u));      // workgroups that joined another team (measurement)
-  if(team_ran && (ln->h_team_ctl[1] != 0 || (team_split && ln->h_team_ctl[32 + 1] != 0))) {
-    // a team barrier timed out (teams not co-resident): rerun the group through the four-kernel chain and stay on it
-    c->persistent_failed.store(true);
-    return estimate_group(c, ln, n, wss, refs, curs, T_init, poses, stats, d_records_out, false, prms);
+
+// 5. The group's states and the control words of the persistent forms back, addFrame's work under the queued estimate, the synchronisation.
+// gave_up: a barrier of the persistent or of the team kernel timed out (workgroups not co-resident) — the states of that level were not written back.
+static int group_collect(GroupRun& r, bool* gave_up)
+{
+  bpvo_hip_ctx* c = r.c;
+  Lane* ln = r.ln;
+  // only this group's states: other lanes may still be writing theirs
+  int ws_lo = r.wss[0], ws_hi = r.wss[0];
+  for(int i = 1; i < r.n; ++i) { ws_lo = std::min(ws_lo, r.wss[i]); ws_hi = std::max(ws_hi, r.wss[i]); }
+  if(!r.small_ctx) {
+    LANE_CK(ln, hipMemcpyAsync(ln->h_states + ws_lo, c->d_states + ws_lo, sizeof(GNState) * (size_t) (ws_hi - ws_lo + 1), hipMemcpyDeviceToHost, ln->stream));
+    if(r.pk_group)
+      LANE_CK(ln, hipMemcpyAsync(ln->h_pk_ctl, ln->d_pk_ctl, sizeof(unsigned) * kPkCtlWords * kMaxLevels, hipMemcpyDeviceToHost, ln->stream));
   }
-  if(pk_group) {
-    bool gave_up = false;
-    for(int l = 0; l < c->L; ++l) gave_up = gave_up || ln->h_pk_ctl[(size_t) l * kPkCtlWords + 1] != 0;
-    if(gave_up) {
-      // a barrier timed out: the states of that level were not written back.  Rerun the group through the four-kernel chain
-      // (same results) and keep this context on it.
-      c->persistent_failed.store(true);
-      return estimate_group(c, ln, n, wss, refs, curs, T_init, poses, stats, d_records_out, false, prms);
-    }
+  if(c->before_final_sync && ln == &c->lanes[0]) {      // (every kernel of the estimate is queued: the host is free for a moment)
+    const std::function<int()> f = std::move(c->before_final_sync);
+    c->before_final_sync = nullptr;
+    if(const int rcf = f()) return rcf;
   }
-  for(int i = 0; i < n; ++i) {
-    const GNState& st = ln->h_states[wss[i]];
+  LANE_CK(ln, hipStreamSynchronize(ln->stream));
+  LANE_CK(ln, hipGetLastError());
+  if(r.frac_queued) { c->frac_valid = true; c->frac_ws = r.wss[0]; c->frac_thr = c->prefetch_frac_thr; c->frac_cnt = (unsigned) c->h_ints[0]; }
+#ifdef BPVO_PK_TIMING
+  print_pk_timing(r);
+#endif
+  if(r.team_ran) {
+    c->team_joins.fetch_add(ln->h_team_ctl[3] + (r.team_split ? ln->h_team_ctl[32 + 3] : 0u));      // workgroups that joined another team (measurement)
+    *gave_up = ln->h_team_ctl[1] != 0 || (r.team_split && ln->h_team_ctl[32 + 1] != 0);
+  }
+  if(r.pk_group)
+    for(int l = 0; l < c->L; ++l) *gave_up = *gave_up || ln->h_pk_ctl[(size_t) l * kPkCtlWords + 1] != 0;
+  return BPVO_OK;
+}
+
+// 6. poses [n][16] and statistics [n][L] from the states, where asked for
+static void group_outputs(const GroupRun& r, float* poses, bpvo_hip_stats* stats)
+{
+  const int L = r.c->L;
+  for(int i = 0; i < r.n; ++i) {
+    const GNState& st = r.ln->h_states[r.wss[i]];
     if(poses) std::memcpy(poses + 16 * (size_t) i, st.T_out, 16 * sizeof(float));
     if(stats)
-      for(int l = 0; l < c->L; ++l) stats[(size_t) i * c->L + l] = st.stats[l];
+      for(int l = 0; l < L; ++l) stats[(size_t) i * L + l] = st.stats[l];
   }
+}
+
+// VisualOdometryPoseEstimator::estimatePose (reference: bpvo/vo_pose_estimator.cc:63-93) for a group of `n` workspaces on one lane.
+// wss[i]: workspace, refs[i] / curs[i]: frame slots.  T_init host [n][16] or null (Identity).
+// allow_persistent: only a group that has the device to itself (a batch on ONE lane) may take the persistent kernel — two
+// hand-barrier grids of concurrent lanes must not be co-scheduled.
+int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* refs, const int* curs, const float* T_init,
+                   float* poses, bpvo_hip_stats* stats, float* d_records_out, bool allow_persistent, const bpvo_hip_params* const* prms)
+{
+  if(n <= 0) return BPVO_OK;
+  (void) hipSetDevice(c->device);
+  GroupRun r{c, ln, n, wss, refs, curs, T_init, prms, d_records_out};
+  r.loss = prms ? prms[0]->lossFunction : c->params.lossFunction;
+  r.max_iterations = c->params.maxIterations;
+  if(prms) {
+    r.max_iterations = prms[0]->maxIterations;
+    for(int i = 1; i < n; ++i) r.max_iterations = std::max(r.max_iterations, prms[i]->maxIterations);
+  }
+  r.max_pts.assign((size_t) c->L, 0);
+  // with the persistent forms where the group may take them; one of them gave up at a barrier: the group once more through the four-kernel
+  // chain (same results), and the context stays on it
+  for(const bool persistent_forms : {allow_persistent, false}) {
+    group_modes(r, persistent_forms);
+    if(int rc = group_upload(r)) return rc;
+    if(persistent_forms && ln == &c->lanes[0] && team_serves(c, n) && templates_suit_teams(c, n, refs))
+      if(int rc = run_team(r)) return rc;
+    if(!r.team_ran)
+      if(int rc = run_levels(r)) return rc;
+    if(int rc = queue_fraction_good(r)) return rc;
+    bool gave_up = false;
+    if(int rc = group_collect(r, &gave_up)) return rc;
+    if(!gave_up) break;
+    c->persistent_failed.store(true);
+  }
+  group_outputs(r, poses, stats);
+  return BPVO_OK;
+}
+
+int check_pairs(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, int level_lo, int level_hi)
+{
+  for(int i = 0; i < n; ++i) {
+    CHECK_WS(c, wss[i]); CHECK_SLOT(c, refs[i]); CHECK_SLOT(c, curs[i]);
+  }
+  for(int i = 0; i < n; ++i) {
+    if(!c->frames[refs[i]].has_template) return fail(c, BPVO_ERR_NO_TEMPLATE, "reference frame has no template");
+    if(!c->frames[curs[i]].has_data) return fail(c, BPVO_ERR_NO_DATA, "no data in frame");
+    for(int l = level_lo; l <= level_hi; ++l)
+      if(c->frames[refs[i]].n_host[l] <= 0) return fail(c, BPVO_ERR_NO_TEMPLATE, "you should call setData before calling computeResiduals");
+  }
+  for(int i = 0; i < n; ++i)
+    if(int rc = ensure_dense_descriptor(c, curs[i])) return rc;
   return BPVO_OK;
 }
 
@@ -440,13 +575,8 @@ static int estimate_one_loss(bpvo_hip_ctx* c, int n, const int* wss, const int* 
   if(n <= 0) return BPVO_OK;
   if(n > c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "more pairs than workspaces");
   const bpvo_hip_params& p = c->params;
-  for(int i = 0; i < n; ++i) {
-    if(wss[i] < 0 || wss[i] >= c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "bad workspace");
-    if(refs[i] < 0 || refs[i] >= c->n_frames || curs[i] < 0 || curs[i] >= c->n_frames) return fail(c, BPVO_ERR_INVALID_ARG, "bad frame slot");
-    if(!c->frames[refs[i]].has_template) return fail(c, BPVO_ERR_NO_TEMPLATE, "reference frame has no template");
-    if(!c->frames[curs[i]].has_data) return fail(c, BPVO_ERR_NO_DATA, "no data in frame");
-    if(int rc = ensure_dense_descriptor(c, curs[i])) return rc;      // (a batch's template frame as the current frame of this estimate)
-  }
+  // (no level check: the batch entry points skip the empty levels of a pair, the single-pair ones have refused them — check_template_not_empty)
+  if(int rc = check_pairs(c, n, wss, refs, curs, 0, -1)) return rc;
   int nl = lanes_for(c, n, 8);
   if(nl < 0) return nl;
   if(team_serves(c, n) && templates_suit_teams(c, n, refs)) nl = 1;      // the team-persistent kernel takes the whole chip
@@ -545,9 +675,7 @@ int ensure_residuals(bpvo_hip_ctx* c, int ws)
   if(w.last_ref < 0 || c->C != 8) return BPVO_OK;
   int rc = upload_single_job(c, ws, w.last_ref, w.last_cur, w.last_level);
   if(rc) return rc;
-  GNLaunch g;
-  g.jobs = c->d_job1; g.npairs = 1; g.max_points = c->frames[w.last_ref].n_host[w.last_level]; g.C = c->C;
-  launch_refresh_residuals(c->stream, g);
+  launch_refresh_residuals(c->stream, level_launch(c, c->d_job1, 1, c->frames[w.last_ref].n_host[w.last_level], c->params.lossFunction));
   return BPVO_OK;
 }
 
@@ -596,16 +724,13 @@ int get_weights_host(bpvo_hip_ctx* c, int ws, std::vector<float>& w_cm, int* n_o
 }
 
 // ---- rig mode: the cameras of a rigid rig estimated as one body pose (rig_math.h, kernels_gn_rig.hip) -------------------------------------
-// (lane 0 on the API thread: the error goes to the context; nothing stays in flight that reads the lane's pinned staging)
-#define RIG_CK(ctx_, ln_, expr)                                                             \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if(e_ != hipSuccess) {                                                                  \
-      (ctx_)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                      \
-      (void) hipStreamSynchronize((ln_)->stream);                                           \
-      return BPVO_ERR_DEVICE;                                                               \
-    }                                                                                       \
-  } while(0)
+// (Lane 0 on the API thread.  The functions that queue work check with LANE_CK — nothing stays in flight that reads the lane's pinned staging —
+// and their callers hand the lane's error to the context: lane_error.)
+static int lane_error(bpvo_hip_ctx* c, const Lane* ln, int rc)
+{
+  if(rc) c->err = ln->err;
+  return rc;
+}
 // Every check of a rig estimate over pyramid levels level_lo .. level_hi, before anything is queued
 static int rig_check(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, int level_lo, int level_hi)
 {
@@ -614,21 +739,11 @@ static int rig_check(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, co
   // (DisparitySpaceWarp's parameters are no rigid-body twist of the camera frame: Ad(X) does not carry them to the body)
   if(c->dspace) return fail(c, BPVO_ERR_UNSUPPORTED, "rig mode does not serve BPVO_WARP_DISPARITY_SPACE_F32");
   for(int i = 0; i < n; ++i) {
-    if(wss[i] < 0 || wss[i] >= c->n_pairs) return fail(c, BPVO_ERR_INVALID_ARG, "bad workspace");
     for(int k = 0; k < i; ++k)
       if(wss[k] == wss[i]) return fail(c, BPVO_ERR_INVALID_ARG, "rig: a workspace appears twice");
-    if(refs[i] < 0 || refs[i] >= c->n_frames || curs[i] < 0 || curs[i] >= c->n_frames) return fail(c, BPVO_ERR_INVALID_ARG, "bad frame slot");
     if(!rig_extrinsic_ok(X + 16 * (size_t) i)) return fail(c, BPVO_ERR_INVALID_ARG, "rig: an extrinsic is not a rigid transform (finite, last row 0 0 0 1, R^T R = I within 1e-4)");
   }
-  for(int i = 0; i < n; ++i) {
-    if(!c->frames[refs[i]].has_template) return fail(c, BPVO_ERR_NO_TEMPLATE, "reference frame has no template");
-    if(!c->frames[curs[i]].has_data) return fail(c, BPVO_ERR_NO_DATA, "no data in frame");
-    for(int l = level_lo; l <= level_hi; ++l)
-      if(c->frames[refs[i]].n_host[l] <= 0) return fail(c, BPVO_ERR_NO_TEMPLATE, "you should call setData before calling computeResiduals");
-  }
-  for(int i = 0; i < n; ++i)
-    if(int rc = ensure_dense_descriptor(c, curs[i])) return rc;
-  return BPVO_OK;
+  return check_pairs(c, n, wss, refs, curs, level_lo, level_hi);
 }
 // the members' job tables (every level, as estimate_group lays them out) and extrinsics to the device, on lane 0; max_pts[l]: the most points of a member at level l
 static int rig_upload(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* refs, const int* curs, const float* X, std::vector<int>& max_pts)
@@ -637,40 +752,25 @@ static int rig_upload(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const in
   const size_t table = (size_t) c->L * NP;
   max_pts.assign((size_t) c->L, 0);
   fill_job_tables(c, ln, 0, n, wss, refs, curs, [](int) { return (const bpvo_hip_params*) nullptr; }, max_pts.data());
-  RIG_CK(c, ln, hipMemcpyAsync(ln->d_pjobs, ln->h_pjobs, sizeof(PairJob) * table * (size_t) job_tables(c), hipMemcpyHostToDevice, ln->stream));
-  if(!c->d_rig_X) RIG_CK(c, ln, hipMalloc((void**) &c->d_rig_X, sizeof(float) * 16 * (size_t) NP));
+  LANE_CK(ln, hipMemcpyAsync(ln->d_pjobs, ln->h_pjobs, sizeof(PairJob) * table * (size_t) job_tables(c), hipMemcpyHostToDevice, ln->stream));
+  if(!c->d_rig_X) LANE_CK(ln, hipMalloc((void**) &c->d_rig_X, sizeof(float) * 16 * (size_t) NP));
   // (from the caller's pageable memory: the copy has left it when the call returns)
-  RIG_CK(c, ln, hipMemcpyAsync(c->d_rig_X, X, sizeof(float) * 16 * (size_t) n, hipMemcpyHostToDevice, ln->stream));
+  LANE_CK(ln, hipMemcpyAsync(c->d_rig_X, X, sizeof(float) * 16 * (size_t) n, hipMemcpyHostToDevice, ln->stream));
   return BPVO_OK;
 }
+// The launch of the members' kernels at a level (fuse_frozen and step_in_reduce stay 0: both assume a step per workspace), and one linearisation
+// of every member at its state's pose: the chain's own kernels, the step in its linearise-only mode (what bpvo_hip_linearize queues)
 static GNLaunch rig_level_launch(const bpvo_hip_ctx* c, const Lane* ln, int level, int n, int max_points, int loss)
 {
-  GNLaunch g;
-  g.jobs = ln->d_pjobs + (size_t) level * c->n_pairs;
-  g.npairs = n;
-  g.max_points = max_points;
-  g.C = c->C;
-  g.loss = loss;
-  g.fast_warp = c->fast_warp;
-  g.interp = c->params.interp;
-  g.reference_reduction = c->reference_reduction ? 1 : 0;
-  g.dense_candidates = dense_candidates(c, max_points);
-  return g;      // (fuse_frozen and step_in_reduce stay 0: both assume a step per workspace)
+  return level_launch(c, ln->d_pjobs + (size_t) level * c->n_pairs, n, max_points, loss);
 }
-// one linearisation of every member at its state's pose: the chain's own kernels, the step in its linearise-only mode (what bpvo_hip_linearize queues)
-static void rig_linearize_members(bpvo_hip_ctx* c, Lane* ln, const GNLaunch& g)
+static LinearizeFlags rig_linearize_flags()
 {
-  const size_t table = (size_t) c->L * c->n_pairs;
-  { ScopedTimer t(c, KC_WARP_RESIDUAL, 0.0, ln, c->profile_all); for_each_group(c, g, table, [&](const GNLaunch& gg) { launch_warp_residual(ln->stream, gg); }); }
-  { ScopedTimer t(c, KC_MEDIAN, 0.0, ln, c->profile_all); launch_median(ln->stream, median_launch(c, g)); }
-  {
-    ScopedTimer t(c, KC_IRLS_REDUCE, 0.0, ln, c->profile_all);
-    if(g.reference_reduction) launch_irls_reduce(ln->stream, g);
-    else for_each_group(c, g, table, [&](const GNLaunch& gg) { launch_irls_reduce(ln->stream, gg); });
-  }
-  { ScopedTimer t(c, KC_GN_STEP, 0.0, ln, c->profile_all); launch_gn_step(ln->stream, g, 1); }
+  LinearizeFlags f;
+  f.step_mode = 1;
+  f.timers = TIMERS_LEVEL2;
+  return f;
 }
-
 
 // the staging of estimate_rigs, allocated at its first use: the table of the call's rigs, their extrinsics and initial poses in ONE pinned block
 // (one upload per estimate), the bodies' `active` words of a round
@@ -678,23 +778,21 @@ static int rig_storage(bpvo_hip_ctx* c, Lane* ln)
 {
   if(c->h_rig_active) return BPVO_OK;      // (the last of the allocations below)
   const size_t NP = (size_t) c->n_pairs;
-  if(!c->d_rig_stage) RIG_CK(c, ln, hipMalloc((void**) &c->d_rig_stage, rig_stage_bytes(c)));
-  if(!c->h_rig_stage) RIG_CK(c, ln, hipHostMalloc((void**) &c->h_rig_stage, rig_stage_bytes(c)));
-  if(!c->d_rig_active) RIG_CK(c, ln, hipMalloc((void**) &c->d_rig_active, sizeof(int) * NP));
-  RIG_CK(c, ln, hipHostMalloc((void**) &c->h_rig_active, 3 * sizeof(int) * NP));
+  if(!c->d_rig_stage) LANE_CK(ln, hipMalloc((void**) &c->d_rig_stage, rig_stage_bytes(c)));
+  if(!c->h_rig_stage) LANE_CK(ln, hipHostMalloc((void**) &c->h_rig_stage, rig_stage_bytes(c)));
+  if(!c->d_rig_active) LANE_CK(ln, hipMalloc((void**) &c->d_rig_active, sizeof(int) * NP));
+  LANE_CK(ln, hipHostMalloc((void**) &c->h_rig_active, 3 * sizeof(int) * NP));
   return BPVO_OK;
 }
 
 // R rigs of ONE loss (the loss instantiates the chain's kernels: estimate_rigs).  The members of all rigs back to back in the job tables, rig
 // after rig; body r is state n_pairs + r; one level loop, every launch of the chain shared by all rigs, one launch of the batched rig step
 // per iteration.  A rig that has finished a level idles — its body and its members inactive, skipped by every kernel — until every rig has.
-static int estimate_rigs_one_loss(bpvo_hip_ctx* c, int R, const RigProblem* rigs, int loss)
+static int estimate_rigs_on_lane(bpvo_hip_ctx* c, Lane* ln, int R, const RigProblem* rigs, int loss)
 {
   const bpvo_hip_params& p = c->params;
-  (void) hipSetDevice(c->device);
-  Lane* ln = &c->lanes[0];      // (the context's stream: the estimate queues behind the frame stages)
   c->frac_valid = false;
-  RIG_CK(c, ln, join_pending_normalization(c, ln->stream));
+  LANE_CK(ln, join_pending_normalization(c, ln->stream));
   int rc = rig_storage(c, ln);
   if(rc) return rc;
   const int NP = c->n_pairs, L = c->L;
@@ -718,39 +816,40 @@ static int estimate_rigs_one_loss(bpvo_hip_ctx* c, int R, const RigProblem* rigs
     tab[r] = RigEntry{first, q.n, dX + 16 * (size_t) first, bodies + r, dT + 16 * (size_t) r};
     fill_job_tables(c, ln, first, q.n, q.wss, q.refs, q.curs, [&](int) { return q.prm; }, max_pts.data());
   }
-  RIG_CK(c, ln, hipMemcpyAsync(ln->d_pjobs, ln->h_pjobs, sizeof(PairJob) * table * (size_t) job_tables(c), hipMemcpyHostToDevice, ln->stream));
-  RIG_CK(c, ln, hipMemcpyAsync(d_stage, c->h_rig_stage, rig_stage_bytes(c), hipMemcpyHostToDevice, ln->stream));
+  LANE_CK(ln, hipMemcpyAsync(ln->d_pjobs, ln->h_pjobs, sizeof(PairJob) * table * (size_t) job_tables(c), hipMemcpyHostToDevice, ln->stream));
+  LANE_CK(ln, hipMemcpyAsync(d_stage, c->h_rig_stage, rig_stage_bytes(c), hipMemcpyHostToDevice, ln->stream));
   launch_set_pose(ln->stream, ln->d_pjobs + (size_t) (L - 1) * NP, nullptr, N);
-  // the rounds of estimate_group: kItersPerSync iterations queued per round, round r + 1 queued while the flags of round r - 1 land; the flags are
-  // the BODIES' `active` words (the rig step clears the members' with them), R words in one copy
-  const int max_lin = std::min(std::max(max_iterations, 0) + 2, kMaxFunEvals);
-  const int kItersPerSync = 4;
-  const int max_rounds = (max_lin + kItersPerSync - 1) / kItersPerSync + 2;
+  const LinearizeFlags members = rig_linearize_flags();
   for(int l = L - 1; l >= p.maxTestLevel; --l) {
     const GNLaunch g = rig_level_launch(c, ln, l, N, max_pts[l], loss);
     launch_level_begin(ln->stream, g.jobs, N, g.max_points, l, 0);
     RigStepsArgs a{g.jobs, reinterpret_cast<const RigEntry*>(d_stage), R, 2, l, l == L - 1 ? 1 : 0, 1, c->d_rig_active};
     launch_rig_steps(ln->stream, a);
     a.mode = 0; a.with_init = 0;
-    for(int round = 0; round < max_rounds; ++round) {
-      for(int k = 0; k < kItersPerSync; ++k) {
-        rig_linearize_members(c, ln, g);
-        launch_rig_steps(ln->stream, a);
-      }
-      const int slot = round % 3;
-      RIG_CK(c, ln, hipMemcpyAsync(c->h_rig_active + (size_t) slot * NP, c->d_rig_active, sizeof(int) * (size_t) R, hipMemcpyDeviceToHost, ln->stream));
-      RIG_CK(c, ln, hipEventRecord(ln->round_ev[slot], ln->stream));
-      if(round == 0) continue;
-      const int prev = (round - 1) % 3;
-      RIG_CK(c, ln, hipEventSynchronize(ln->round_ev[prev]));
-      bool any = false;
-      for(int r = 0; r < R; ++r) any = any || c->h_rig_active[(size_t) prev * NP + r] != 0;
-      if(!any) break;      // (the round just queued runs empty)
-    }
+    // the pipelined rounds of the chain (gn_rounds.h): the flags are the BODIES' `active` words (the rig step clears the members' with them), R
+    // words in one copy; every rig goes on — a finished one idling — while any body is active
+    rc = lane_rounds(ln, max_iterations,
+                     [&](int) -> int {
+                       for(int k = 0; k < kItersPerSync; ++k) {
+                         linearize_launches(c, ln, g, table, members);
+                         launch_rig_steps(ln->stream, a);
+                       }
+                       return BPVO_OK;
+                     },
+                     [&](int slot) -> int {
+                       LANE_CK(ln, hipMemcpyAsync(c->h_rig_active + (size_t) slot * NP, c->d_rig_active, sizeof(int) * (size_t) R, hipMemcpyDeviceToHost, ln->stream));
+                       return BPVO_OK;
+                     },
+                     [&](int slot) {
+                       bool any = false;
+                       for(int r = 0; r < R; ++r) any = any || c->h_rig_active[(size_t) slot * NP + r] != 0;
+                       return any;
+                     });
+    if(rc) return rc;
   }
-  RIG_CK(c, ln, hipMemcpyAsync(ln->h_states + NP, bodies, sizeof(GNState) * (size_t) R, hipMemcpyDeviceToHost, ln->stream));
-  RIG_CK(c, ln, hipStreamSynchronize(ln->stream));
-  RIG_CK(c, ln, hipGetLastError());
+  LANE_CK(ln, hipMemcpyAsync(ln->h_states + NP, bodies, sizeof(GNState) * (size_t) R, hipMemcpyDeviceToHost, ln->stream));
+  LANE_CK(ln, hipStreamSynchronize(ln->stream));
+  LANE_CK(ln, hipGetLastError());
   resolve_events(c);
   for(int r = 0; r < R; ++r) {
     const RigProblem& q = rigs[r];
@@ -765,6 +864,12 @@ static int estimate_rigs_one_loss(bpvo_hip_ctx* c, int R, const RigProblem* rigs
     }
   }
   return BPVO_OK;
+}
+static int estimate_rigs_one_loss(bpvo_hip_ctx* c, int R, const RigProblem* rigs, int loss)
+{
+  (void) hipSetDevice(c->device);
+  Lane* ln = &c->lanes[0];      // (the context's stream: the estimate queues behind the frame stages)
+  return lane_error(c, ln, estimate_rigs_on_lane(c, ln, R, rigs, loss));
 }
 
 // Rigs with different losses in one call: one estimate per loss present, the rigs of a loss in call order (what estimate_batch does for sequences
@@ -805,6 +910,28 @@ int estimate_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const 
 
 extern "C" {
 
+// the members' linearisations at the body pose and the joint one, queued on lane 0 and waited for: the body's state in ln->h_states[n_pairs]
+static int linearize_rig_on_lane(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* refs, const int* curs, const float* X, int level,
+                                 const float T_body[16], int reset_scale, float* T_members)
+{
+  LANE_CK(ln, join_pending_normalization(c, ln->stream));
+  std::vector<int> max_pts;
+  if(int rc = rig_upload(c, ln, n, wss, refs, curs, X, max_pts)) return rc;
+  const int NP = c->n_pairs;
+  GNState* body = c->d_states + NP;
+  for(int i = 0; i < n; ++i) rig_member_pose(X + 16 * (size_t) i, T_body, ln->h_T + 16 * (size_t) i);      // the poses the members' kernels run at
+  if(T_members) std::memcpy(T_members, ln->h_T, sizeof(float) * 16 * (size_t) n);
+  LANE_CK(ln, hipMemcpyAsync(ln->d_Tinit, ln->h_T, sizeof(float) * 16 * (size_t) n, hipMemcpyHostToDevice, ln->stream));
+  const GNLaunch g = rig_level_launch(c, ln, level, n, max_pts[level], c->params.lossFunction);
+  for(int i = 0; i < n; ++i) launch_prepare_linearize(ln->stream, g.jobs + i, ln->d_Tinit + 16 * (size_t) i, reset_scale ? 1 : 0, level);
+  launch_reset_tapkeys(ln->stream, g);
+  linearize_launches(c, ln, g, (size_t) c->L * NP, rig_linearize_flags());
+  launch_rig_step(ln->stream, RigStepArgs{g.jobs, n, c->d_rig_X, body, 1, level, nullptr, 0});
+  LANE_CK(ln, hipMemcpyAsync(ln->h_states + NP, body, sizeof(GNState), hipMemcpyDeviceToHost, ln->stream));
+  LANE_CK(ln, hipStreamSynchronize(ln->stream));
+  LANE_CK(ln, hipGetLastError());
+  return BPVO_OK;
+}
 int bpvo_hip_linearize_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* X, int level, const float T_body[16],
                            int reset_scale, float H[36], float G[6], float* f_norm, int* num_valid, float* T_members)
 {
@@ -815,25 +942,10 @@ int bpvo_hip_linearize_rig(bpvo_hip_ctx* c, int n, const int* wss, const int* re
   (void) hipSetDevice(c->device);
   Lane* ln = &c->lanes[0];
   c->frac_valid = false;
-  RIG_CK(c, ln, join_pending_normalization(c, ln->stream));
-  std::vector<int> max_pts;
-  rc = rig_upload(c, ln, n, wss, refs, curs, X, max_pts);
+  rc = lane_error(c, ln, linearize_rig_on_lane(c, ln, n, wss, refs, curs, X, level, T_body, reset_scale, T_members));
   if(rc) return rc;
-  const int NP = c->n_pairs;
-  GNState* body = c->d_states + NP;
-  for(int i = 0; i < n; ++i) rig_member_pose(X + 16 * (size_t) i, T_body, ln->h_T + 16 * (size_t) i);      // the poses the members' kernels run at
-  if(T_members) std::memcpy(T_members, ln->h_T, sizeof(float) * 16 * (size_t) n);
-  RIG_CK(c, ln, hipMemcpyAsync(ln->d_Tinit, ln->h_T, sizeof(float) * 16 * (size_t) n, hipMemcpyHostToDevice, ln->stream));
-  const GNLaunch g = rig_level_launch(c, ln, level, n, max_pts[level], c->params.lossFunction);
-  for(int i = 0; i < n; ++i) launch_prepare_linearize(ln->stream, g.jobs + i, ln->d_Tinit + 16 * (size_t) i, reset_scale ? 1 : 0, level);
-  launch_reset_tapkeys(ln->stream, g);
-  rig_linearize_members(c, ln, g);
-  launch_rig_step(ln->stream, RigStepArgs{g.jobs, n, c->d_rig_X, body, 1, level, nullptr, 0});
-  RIG_CK(c, ln, hipMemcpyAsync(ln->h_states + NP, body, sizeof(GNState), hipMemcpyDeviceToHost, ln->stream));
-  RIG_CK(c, ln, hipStreamSynchronize(ln->stream));
-  RIG_CK(c, ln, hipGetLastError());
   resolve_events(c);
-  const GNState& st = ln->h_states[NP];
+  const GNState& st = ln->h_states[c->n_pairs];
   std::memcpy(H, st.H, sizeof(st.H));
   std::memcpy(G, st.G, sizeof(st.G));
   *f_norm = st.f_norm;
@@ -889,11 +1001,8 @@ extern "C" {
 static int linearize_impl(bpvo_hip_ctx* c, int ws, int ref_slot, int cur_slot, int level, const float T[16], int reset_scale, float given_scale,
                           float H[36], float G[6], float* f_norm, float* sigma, int* num_valid)
 {
-  CHECK_CTX(c); CHECK_WS(c, ws); CHECK_SLOT(c, ref_slot); CHECK_SLOT(c, cur_slot); CHECK_LEVEL(c, level);
-  if(!c->frames[ref_slot].has_template) return fail(c, BPVO_ERR_NO_TEMPLATE, "reference frame has no template");
-  if(!c->frames[cur_slot].has_data) return fail(c, BPVO_ERR_NO_DATA, "no data in frame");
-  if(int rc0 = ensure_dense_descriptor(c, cur_slot)) return rc0;
-  if(c->frames[ref_slot].n_host[level] <= 0) return fail(c, BPVO_ERR_NO_TEMPLATE, "you should call setData before calling computeResiduals");
+  CHECK_CTX(c); CHECK_LEVEL(c, level);
+  if(int rc0 = check_pairs(c, 1, &ws, &ref_slot, &cur_slot, level, level)) return rc0;
   c->frac_valid = false;
   (void) hipSetDevice(c->device);
   int rc = upload_single_job(c, ws, ref_slot, cur_slot, level);
@@ -902,21 +1011,12 @@ static int linearize_impl(bpvo_hip_ctx* c, int ws, int ref_slot, int cur_slot, i
   std::memcpy(l0.h_T, T, 16 * sizeof(float));
   HIP_CK(c, hipMemcpyAsync(l0.d_Tinit, l0.h_T, 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
   launch_prepare_linearize(c->stream, c->d_job1, l0.d_Tinit, reset_scale, level, given_scale);
-  GNLaunch g;
-  g.jobs = c->d_job1; g.npairs = 1; g.max_points = c->frames[ref_slot].n_host[level]; g.C = c->C; g.loss = c->params.lossFunction;
-  g.fast_warp = c->fast_warp;
-  g.interp = c->params.interp;
-  g.reference_reduction = c->reference_reduction ? 1 : 0;
-  g.dense_candidates = dense_candidates(c, g.max_points);
+  const GNLaunch g = level_launch(c, c->d_job1, 1, c->frames[ref_slot].n_host[level], c->params.lossFunction);
   launch_reset_tapkeys(c->stream, g);
-  { ScopedTimer t(c, KC_WARP_RESIDUAL, 0.0); for_each_group(c, g, 1, [&](const GNLaunch& gg) { launch_warp_residual(c->stream, gg); }); }
-  { ScopedTimer t(c, KC_MEDIAN, 0.0); launch_median(c->stream, median_launch(c, g)); }
-  {
-    ScopedTimer t(c, KC_IRLS_REDUCE, 0.0);
-    if(g.reference_reduction) launch_irls_reduce(c->stream, g);
-    else for_each_group(c, g, 1, [&](const GNLaunch& gg) { launch_irls_reduce(c->stream, gg); });
-  }
-  { ScopedTimer t(c, KC_GN_STEP, 0.0); launch_gn_step(c->stream, g, 1); }
+  LinearizeFlags f;      // (lane 0 is the context's stream; every launch timed, the step in its linearise-only mode; d_job1[1 + k]: channel group k)
+  f.step_mode = 1;
+  f.timers = TIMERS_ALWAYS;
+  linearize_launches(c, &l0, g, 1, f);
   HIP_CK(c, hipMemcpyAsync(l0.h_states, c->d_states + ws, sizeof(GNState), hipMemcpyDeviceToHost, c->stream));
   HIP_CK(c, hipStreamSynchronize(c->stream));
   HIP_CK(c, hipGetLastError());
@@ -1035,8 +1135,7 @@ int bpvo_hip_estimate_pose_trace(bpvo_hip_ctx* c, int ws, int ref_slot, int cur_
   if(!T_init || !T_est || !n_records || max_records < 0 || (max_records > 0 && !records)) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr pose / records");
   if(int rc = check_template_not_empty(c, ref_slot)) return rc;
   (void) hipSetDevice(c->device);
-  // at most min(maxIterations + 2, maxFuncEvals) linearisations per level (pose_estimator_base.h:373-393)
-  const int cap = c->L * (std::min(std::max(c->params.maxIterations, 0) + 2, kMaxFunEvals) + 1);
+  const int cap = c->L * (max_linearizations(c->params.maxIterations) + 1);
   if(cap > c->trace_cap) {
     HIP_CK(c, hipStreamSynchronize(c->stream));
     (void) hipFree(c->d_trace);

@@ -3,6 +3,7 @@
 //   estimate.hip  estimatePose: the Gauss-Newton drivers (chain, persistent, team)       batch.hip     pair batches, the upload pipeline
 //   vo.hip        the addFrame drivers (one frame, many sequences), point cloud,          measure.hip   profiling, counters, diagnostics
 //                 stereo front-end                                                       vo_state.h    addFrame's state machine (host only, no HIP)
+//                                                                                        gn_rounds.h   the chain's pipelined rounds (host only, no HIP)
 //   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)
 // The host keeps bpvo's object model (frames with a descriptor pyramid and a template pyramid, a pose estimator with per-level
 // Gauss-Newton runs, the VisualOdometry keyframe state machine) but every O(pixels) / O(points) array lives in HBM; per GN iteration the
@@ -25,6 +26,7 @@
 #include <thread>
 #include <vector>
 
+#include "gn_rounds.h"
 #include "kernels.h"
 #include "latch_table.h"
 #include "rig_math.h"
@@ -174,7 +176,6 @@ constexpr int kDefaultLanesNarrow = 2;
 constexpr int kMinPairsPerLane = 8;
 constexpr int kPkCtlWords = 32;    // one 128-byte line per level
 constexpr int kMaxTeams = 1024;
-constexpr int kMaxFunEvals = 6 * 200;   // PoseEstimatorParameters::maxFuncEvals, which AlgorithmParameters does not reach (Q4)
 
 }  // namespace bpvo_hip_host
 
@@ -542,12 +543,18 @@ inline void for_each_group(const bpvo_hip_ctx* c, const bpvo_hip::GNLaunch& g, s
 // (the size of a segment)
 // entry of Workspace::med_blk (uint4 units, a multiple of 8 = one 128-byte line) where the dense form's totals begin
 inline size_t med_totals_at(const bpvo_hip_ctx* c) { return (((size_t) ((c->cap_max + bpvo_hip::kChunkPoints - 1) / bpvo_hip::kChunkPoints) * (size_t) c->G) + 7) / 8 * 8; }
-// every deferred normalisation joins `s` (errors aside, the estimation has done that level by level: estimate.hip)
-inline hipError_t join_pending_normalization(bpvo_hip_ctx* c, hipStream_t s)
+// The normalisation of the levels below the coarsest, of the template stage queued just before (frames.hip, ctx->nrm_pending), may still be
+// running on the context's side streams: whoever reads those levels' (scale, centroid) next makes its stream `s` wait for it.  level: the
+// pyramid level about to start — the finest level's own event is joined only there; < 0: everything.
+inline hipError_t join_pending_normalization(bpvo_hip_ctx* c, hipStream_t s, int level = -1)
 {
   hipError_t e = hipSuccess;
   if(c->nrm_pending) { e = hipStreamWaitEvent(s, c->nrm_pending, 0); c->nrm_pending = nullptr; }
-  if(c->nrm_pending_finest) { const hipError_t e2 = hipStreamWaitEvent(s, c->nrm_pending_finest, 0); c->nrm_pending_finest = nullptr; if(e == hipSuccess) e = e2; }
+  if(c->nrm_pending_finest && (level < 0 || level <= c->params.maxTestLevel)) {
+    const hipError_t e2 = hipStreamWaitEvent(s, c->nrm_pending_finest, 0);
+    c->nrm_pending_finest = nullptr;
+    if(e == hipSuccess) e = e2;
+  }
   return e;
 }
 // can a template of this context have a level of more points than the persistent kernels are given (persist_max_points)?  Only a level without
@@ -568,6 +575,35 @@ inline bool single_pair_is_queued_at_once(const bpvo_hip_ctx* c)
 }
 inline int dense_candidates(const bpvo_hip_ctx* c, int max_points) { return (c->G == 1 && max_points >= c->dense_candidates_from) ? 1 : 0; }
 inline bpvo_hip::GNLaunch median_launch(const bpvo_hip_ctx* c, bpvo_hip::GNLaunch g) { if(c->G > 1) g.C = c->Cg; return g; }
+// The launch of the chain's kernels over `npairs` jobs of one level: everything the context decides — channels, warp formulation, interpolation,
+// reference order, the form of the median's candidates — in ONE place, so that the launches of an iteration agree.  A call site sets only what
+// is its own: fuse_frozen and step_in_reduce (the estimate loops of cameras), the persistent kernel's hand-over fields.
+inline bpvo_hip::GNLaunch level_launch(const bpvo_hip_ctx* c, const bpvo_hip::PairJob* jobs, int npairs, int max_points, int loss)
+{
+  bpvo_hip::GNLaunch g;
+  g.jobs = jobs; g.npairs = npairs; g.max_points = max_points; g.C = c->C; g.loss = loss;
+  g.fast_warp = c->fast_warp; g.interp = c->params.interp;
+  g.reference_reduction = c->reference_reduction ? 1 : 0;
+  g.dense_candidates = dense_candidates(c, max_points);
+  return g;
+}
+// One linearisation's launches (estimate.hip linearize_launches): which of them run, the step's mode (launch_gn_step), and which timers are armed
+//   TIMERS_ESTIMATE  the estimate loops of cameras: a 1-in-kProfileEvery sample of the warp_residual launches of the lane at profiling level 1, every
+//                    kernel at level 2, every warp_residual and reduction at level 3 (bench.py's roofline pass)
+//   TIMERS_LEVEL2    every kernel at profiling level 2, none below (rigs)
+//   TIMERS_ALWAYS    every kernel whenever profiling is on (the operator-level seam)
+enum LinearizeTimers { TIMERS_OFF, TIMERS_ESTIMATE, TIMERS_LEVEL2, TIMERS_ALWAYS };
+struct LinearizeFlags {
+  bool warp = true, median = true, reduce = true, step = true;      // (the step runs in its own launch unless GNLaunch::step_in_reduce folds it into the reduction)
+  int step_mode = 0;
+  LinearizeTimers timers = TIMERS_OFF;
+};
+// g: the level's launch; stride: jobs between the channel-group tables of a wide descriptor (for_each_group).  Launches go to the lane's stream.
+void linearize_launches(bpvo_hip_ctx* c, Lane* ln, const bpvo_hip::GNLaunch& g, size_t stride, const LinearizeFlags& f);
+// The checks every estimate path makes of its pairs, before anything is queued: workspaces and frame slots in range; then templates and data
+// in place and, for level_lo <= level_hi, no empty template level among level_lo .. level_hi; then the current frames' full descriptor records
+// (ensure_dense_descriptor: a batch's template frame as the current frame of an estimate).
+int check_pairs(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, int level_lo, int level_hi);
 // prms: null (every entry runs with the context's parameters: the batch entry points, the single-sequence path), or each entry's own parameters
 // (bpvo_hip_add_frames).  estimate_batch runs one estimate per loss among them — the loss instantiates the kernels —, so every entry of an
 // estimate_group call has the same loss; limits and tolerances travel in the entries' jobs.

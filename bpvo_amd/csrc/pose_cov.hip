@@ -140,10 +140,12 @@ int pose_cov_pass(bpvo_hip_ctx* c, int n_records, int members, const int* wss, c
     g.max_points = max_points; g.C = c->C; g.loss = c->params.lossFunction;
     g.out = k.d_out;
     launch_pose_cov_prepare(s, g);
-    GNLaunch w;      // the residuals at the pose: the chain's warp_residual on the copies (every descriptor, interpolation and warp formulation)
-    w.jobs = g.jobs; w.npairs = nm; w.max_points = max_points; w.C = c->C; w.loss = g.loss;
-    w.fast_warp = c->fast_warp; w.interp = c->params.interp;
-    launch_warp_residual(s, w);
+    // the residuals at the pose: the chain's warp_residual on the copies (every descriptor, interpolation and warp formulation)
+    GNLaunch w = level_launch(c, g.jobs, nm, max_points, g.loss);
+    w.dense_candidates = 0;      // (the copies hold no candidate buffers: warp_residual reads this field, and no median follows)
+    LinearizeFlags warp_only;
+    warp_only.median = warp_only.reduce = warp_only.step = false;
+    linearize_launches(c, &c->lanes[0], w, 0, warp_only);      // (lane 0 is the context's stream)
     for(int b = 0; b < 3; ++b)
       if(losses & (1u << b)) {
         g.loss = b == 0 ? BPVO_LOSS_HUBER : b == 1 ? BPVO_LOSS_TUKEY : BPVO_LOSS_L2;
@@ -166,16 +168,12 @@ static int pose_cov_check(bpvo_hip_ctx* c, int n, const int* wss, const int* ref
   if(!given) *level_io = c->params.maxTestLevel;
   const int level = *level_io;
   CHECK_LEVEL(c, level);
+  if(int rc = check_pairs(c, n, wss, refs, curs, 0, -1)) return rc;      // (an empty template level is answered by its record: no level check)
   for(int i = 0; i < n; ++i) {
-    CHECK_WS(c, wss[i]); CHECK_SLOT(c, refs[i]); CHECK_SLOT(c, curs[i]);
-    if(!c->frames[refs[i]].has_template) return fail(c, BPVO_ERR_NO_TEMPLATE, "reference frame has no template");
-    if(!c->frames[curs[i]].has_data) return fail(c, BPVO_ERR_NO_DATA, "no data in frame");
     const Workspace& w = c->ws[wss[i]];
     if(!given && !(w.has_estimate && w.last_ref == refs[i] && w.last_cur == curs[i] && w.last_level == level))
       return fail(c, BPVO_ERR_NO_DATA, "pose covariance: the workspace holds no estimate of this pair (give T and sigma)");
   }
-  for(int i = 0; i < n; ++i)
-    if(int rc = ensure_dense_descriptor(c, curs[i])) return rc;
   return BPVO_OK;
 }
 

@@ -802,9 +802,8 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
     }
   HIP_CK(c, hipMemcpyAsync(c->d_seq_jobs, c->h_seq_jobs, sizeof(PairJob) * (size_t) N, hipMemcpyHostToDevice, c->stream));
   if(!rig) {
-    GNLaunch gr;      // (estimate_batch's fused path: the residual buffers may lag behind the last linearisation — ensure_residuals; estimate_rigs' chain writes them always)
-    gr.jobs = c->d_seq_jobs; gr.npairs = N; gr.max_points = max_n; gr.C = c->C;
-    launch_refresh_residuals(c->stream, gr);
+    // (estimate_batch's fused path: the residual buffers may lag behind the last linearisation — ensure_residuals; estimate_rigs' chain writes them always)
+    launch_refresh_residuals(c->stream, level_launch(c, c->d_seq_jobs, N, max_n, p.lossFunction));
   }
   HIP_CK(c, hipMemsetAsync(c->d_seq_cnt, 0, sizeof(unsigned) * (size_t) N, c->stream));
   if(own) launch_count_good_jobs(c->stream, c->d_seq_jobs, N, max_n, c->C, c->d_seq_cnt);      // (each entry's loss and threshold, from its members' jobs)
