@@ -69,6 +69,16 @@ def _cov_dict(r: PoseCovariance):
                 num_valid=int(r.num_valid), level=int(r.level), status=int(r.status))
 
 
+class PoseScore(C.Structure):
+    """bpvo_hip_pose_score (c_api.h): the truncated-L1 score of one candidate pose."""
+    _fields_ = [("cost_sum", C.c_double), ("score", C.c_double), ("n_valid", C.c_int), ("n_below", C.c_int)]
+
+
+# ... and the same 24 bytes as a numpy record, which is how Context.score_poses returns them
+POSE_SCORE = np.dtype([("cost_sum", np.float64), ("score", np.float64), ("n_valid", np.int32), ("n_below", np.int32)])
+assert POSE_SCORE.itemsize == C.sizeof(PoseScore) == 24
+
+
 class Camera(C.Structure):
     """bpvo_hip_camera: one sequence's calibration and image size (bpvo_hip_create_sequences, bpvo_hip_seq_set_camera)."""
     _fields_ = [("K", C.c_float * 9), ("baseline", C.c_float), ("rows", C.c_int), ("cols", C.c_int)]
@@ -871,6 +881,41 @@ class Context:
         M, Q = np.empty((6, 6), np.float32), np.empty((6, 6), np.float32)
         self.call("debug_pose_covariance_sums", int(ws), M.ctypes.data_as(C.c_void_p), Q.ctypes.data_as(C.c_void_p))
         return M, Q
+
+    # -- pose scoring (bpvo_hip_score_poses ...; HIP library only)
+    def score_poses(self, ref, cur, level, poses, tau):
+        """The truncated-L1 score of every pose [P, 4, 4] of the pair (ref, cur) at `level` in one launch: a POSE_SCORE record array [P]."""
+        Tf = _f32(poses).reshape(-1, 16)
+        out = np.zeros(Tf.shape[0], POSE_SCORE)
+        self.call("score_poses", int(ref), int(cur), int(level), int(Tf.shape[0]), Tf.ctypes.data_as(C.c_void_p), C.c_float(tau),
+                  out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def score_poses_pairs(self, refs, curs, level, poses, tau):
+        """... of n pairs in one launch, poses [n, P, 4, 4]: a POSE_SCORE record array [n, P]."""
+        r = np.ascontiguousarray(refs, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(curs, dtype=np.int32).reshape(-1)
+        n = r.shape[0]
+        assert c.shape[0] == n, "one current frame per template"
+        Tf = _f32(poses).reshape(n, -1, 16)
+        out = np.zeros((n, Tf.shape[1]), POSE_SCORE)
+        self.call("score_poses_pairs", n, r.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), int(level), int(Tf.shape[1]),
+                  Tf.ctypes.data_as(C.c_void_p), C.c_float(tau), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def estimate_pose_best_start(self, ws, ref, cur, candidates, tau, score_level=-1):
+        """estimate_pose from the best-scoring of the candidate starts [n, 4, 4] (score_level < 0: the coarsest level):
+        (T, stats, chosen index, POSE_SCORE records [n])."""
+        Tf = _f32(candidates).reshape(-1, 16)
+        n = Tf.shape[0]
+        T = np.empty((4, 4), np.float32)
+        st = (Stats * self.L)()
+        chosen = C.c_int(-1)
+        scores = np.zeros(n, POSE_SCORE)
+        self.call("estimate_pose_best_start", int(ws), int(ref), int(cur), n, Tf.ctypes.data_as(C.c_void_p), int(score_level), C.c_float(tau),
+                  T.ctypes.data_as(C.c_void_p), st, C.byref(chosen), scores.ctypes.data_as(C.c_void_p))
+        stats = [dict(numIterations=s.numIterations, finalError=s.finalError, firstOrderOptimality=s.firstOrderOptimality, status=s.status) for s in st]
+        return T, stats, chosen.value, scores
 
     # -- batches
     def _stats_array(self, st, n_pairs):

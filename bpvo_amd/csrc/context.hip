@@ -736,6 +736,7 @@ void bpvo_hip_destroy(bpvo_hip_ctx* c)
   (void) hipFree(c->d_states); (void) hipFree(c->d_fjobs); (void) hipFree(c->d_job1); (void) hipFree(c->d_latch_off); (void) hipFree(c->d_cloud);
   (void) hipFree(c->d_records); (void) hipFree(c->d_wtmp); (void) hipFree(c->d_rig_X); (void) hipFree(c->d_rig_stage); (void) hipFree(c->d_rig_active); (void) hipHostFree(c->h_rig_stage); (void) hipHostFree(c->h_rig_active);
   pose_cov_free(c);
+  pose_score_free(c);
   (void) hipFree(c->d_count); (void) hipFree(c->d_counters); (void) hipFree(c->d_tickets); (void) hipFree(c->d_trace);
   (void) hipFree(c->st_left); (void) hipFree(c->st_right); (void) hipFree(c->st_left_pre); (void) hipFree(c->st_right_pre); (void) hipFree(c->st_disp);
   (void) hipFree(c->st_sgm);

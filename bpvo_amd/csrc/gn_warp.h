@@ -52,6 +52,12 @@ __device__ __forceinline__ float bilinear_res(float i00, float i01, float i10, f
   const double Iw = wy * ((double) i00 * wx + (double) i01 * xf) + yf * ((double) i10 * wx + (double) i11 * xf);
   return (float) (Iw - (double) i0);
 }
+// ... and of the all-f32 formulation (FAST): Iw = dp_ps(cf, [I00, I01, I10, I11]), r = Iw - I0
+__device__ __forceinline__ float bilinear_res_f32(float i00, float i01, float i10, float i11, float i0, const float (&cf)[4])
+{
+  const float Iw = (cf[0] * i00 + cf[1] * i01) + (cf[2] * i10 + cf[3] * i11);
+  return Iw - i0;
+}
 
 // The C = 8 bilinear footprint as eight 16-byte pieces, which is how it is gathered and how the tap cache keeps it.
 // pieces 0, 1: I00 of channels 0-3 / 4-7; 2, 3: I01; 4, 5: I10; 6, 7: I11
@@ -225,8 +231,7 @@ __device__ __forceinline__ bool warp_point(const PairJob& j, const float (&P)[12
       if constexpr(!FAST) {
         res[c] = bilinear_res(I00[c], I01[c], I10[c], I11[c], I0[c], xf, yf, wx, wy);
       } else {
-        const float Iw = (cf[0] * I00[c] + cf[1] * I01[c]) + (cf[2] * I10[c] + cf[3] * I11[c]);
-        res[c] = Iw - I0[c];
+        res[c] = bilinear_res_f32(I00[c], I01[c], I10[c], I11[c], I0[c], cf);
       }
     }
   } else {

@@ -133,6 +133,15 @@ struct CovScratch {
   float* d_sums = nullptr;                            // [n_pairs][72]: M and Q of the last pass on each workspace
 };
 
+// Device buffers of the pose-scoring calls (score.hip), the context's own, grown on demand: the jobs of a call's pairs, its poses, the
+// per-(pair, chunk, pose) partials and the records.  Capacities in elements.
+struct ScoreScratch {
+  PairJob* d_jobs = nullptr; size_t jobs_cap = 0;
+  float* d_T = nullptr; size_t T_cap = 0;
+  ScorePartial* d_partials = nullptr; size_t partials_cap = 0;
+  bpvo_hip_pose_score* d_out = nullptr; size_t out_cap = 0;
+};
+
 enum KernelClass { KC_PYRAMID = 0, KC_DESCRIPTOR, KC_SALIENCY_SELECT, KC_NORMALIZATION, KC_TEMPLATE, KC_WARP_RESIDUAL, KC_MEDIAN,
                    KC_IRLS_REDUCE, KC_GN_STEP, KC_POINT_BUDGET, KC_COUNT };
 static const char* const kKernelNames[KC_COUNT] = {"pyramid", "descriptor", "saliency_select", "normalization", "template_build", "warp_residual",
@@ -247,6 +256,7 @@ struct bpvo_hip_ctx {
   CovScratch cov;
   bpvo_hip_pose_covariance vo_cov;
   std::vector<bpvo_hip_pose_covariance> seq_cov;
+  ScoreScratch score;              // pose scoring (c_api.h bpvo_hip_score_poses, score.hip)
   // measurement
   double points_fused = 0;     // points linearised through the fused path since the last counter reset
   int fast_warp = 0;           // bpvo_hip_set_warp_formulation
@@ -650,6 +660,7 @@ int pose_cov_pass(bpvo_hip_ctx* c, int n_records, int members, const int* wss, c
 int pose_cov_ensure_scratch(bpvo_hip_ctx* c);
 void pose_cov_none(bpvo_hip_pose_covariance* r);      // the record of "nothing was estimated": Identity pose and covariance, BPVO_COV_NONE
 void pose_cov_free(bpvo_hip_ctx* c);
+void pose_score_free(bpvo_hip_ctx* c);      // score.hip: the scoring calls' device buffers
 int set_option(bpvo_hip_ctx* c, const std::string& key, double v);
 int apply_options_string(bpvo_hip_ctx* c, const char* str);
 struct OptionDef { const char* key; double lo, hi; std::function<double(bpvo_hip_ctx*)> get; std::function<int(bpvo_hip_ctx*, double)> set; };

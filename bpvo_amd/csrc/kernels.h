@@ -281,6 +281,24 @@ int  pose_cov_partials_floats(int cap, int C);          // floats of one member'
 void launch_pose_cov_prepare(hipStream_t s, const CovLaunch& g);   // the scratch states from (T, sigma) or from the workspaces' last estimates
 void launch_pose_cov_reduce(hipStream_t s, const CovLaunch& g);    // loss g.loss; members whose job carries another loss are left alone
 void launch_pose_cov_finish(hipStream_t s, const CovLaunch& g);
+// Pose scoring (kernels_score.hip; c_api.h bpvo_hip_score_poses): the truncated-L1 cost of n_poses poses of each of n_pairs jobs in one launch,
+// one partial per (pair, chunk, pose), then the finish — the partials in chunk order, the score.  The jobs are read for their template, descriptor
+// and geometry only (the host clears their workspace pointers).  `tile`: poses a workgroup walks (1 .. kScoreTile; the host sizes it so that the
+// launch fills the chip) — no result depends on it.
+constexpr int kScoreTile = 16;
+struct ScorePartial { double cost; int n_valid, n_below; };
+struct ScoreLaunch {
+  const PairJob* jobs;           // device [n_pairs]
+  int n_pairs, n_poses;
+  int max_points;                // the most points of a job (0: every template is empty — the finish alone runs)
+  int C, fast_warp, tile;
+  float tau;
+  const float* T;                // device [n_pairs][n_poses][16]
+  ScorePartial* partials;        // device [n_pairs][score_chunks(max_points)][n_poses]
+  bpvo_hip_pose_score* out;      // device [n_pairs][n_poses]
+};
+int  score_chunks(int max_points);      // 256-point chunks of the largest template, at least 1
+void launch_score_poses(hipStream_t s, const ScoreLaunch& g);
 void launch_prepare_linearize(hipStream_t s, const PairJob* job, const float* T /*device [16]*/, int reset_scale, int level, float given_scale = 0.0f);
 int  gn_pts_per_block(int C);
 int  gn_partials_entries(int cap, int C);   // kPartialStride-float entries of a workspace's (double-buffered) tile partials

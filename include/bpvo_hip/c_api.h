@@ -567,6 +567,49 @@ int bpvo_hip_rigs_pose_covariance(bpvo_hip_ctx* ctx, int rig, bpvo_hip_pose_cova
 /* diagnostics: the curvature M and the score covariance Q (row-major, symmetric) of the last pass on workspace ws, in its normalised twist */
 int bpvo_hip_debug_pose_covariance_sums(bpvo_hip_ctx* ctx, int ws, float M[36], float Q[36]);
 
+/* ---- pose scoring: the robust cost of MANY candidate poses of a pair in one launch (the reference has none).  Gauss-Newton converges only
+ * inside the basin of its start; a caller with a handful of plausible starts — a constant-velocity prediction, an IMU guess, Identity, a grid
+ * for relocalisation — scores them here and starts at the best (bpvo_hip_estimate_pose_best_start).
+ * Definition.  Template (ref_slot, level) of N points and C channels, the current frame's descriptor at that level, a pose T meant as in
+ * bpvo_hip_linearize, a truncation tau (finite, > 0).  valid_i and r[i][c] are exactly what bpvo_hip_linearize at T leaves in
+ * bpvo_hip_get_valid / bpvo_hip_get_residuals (the context's warp formulation, the same f32 bits).  Then
+ *   n_valid  = #{i : valid_i}
+ *   n_below  = #{(i, c) : valid_i and |r[i][c]| < tau}
+ *   cost_sum = sum over valid i and all c of min(|r[i][c]|, tau), every term converted to f64 and summed in f64
+ *   score    = (cost_sum + tau C (N - n_valid)) / (C N): an invalid point is charged tau per channel, so a pose that throws the scene out of
+ *              view cannot win by having nothing to explain.  N = 0: cost_sum 0, both counts 0, score = tau.
+ * Residuals of invalid points never enter (the f32 formulations' -I0 is ignored).  A pose that is NaN, Inf or beyond the int range makes every
+ * point invalid (the warp's rule); no pose raises.  cost_sum is the same bits from call to call and does not depend on how many poses or pairs
+ * share the launch nor on a pose's place in the list: no floating-point atomics, one partial per (pose, 256-point chunk), combined in chunk order.
+ * tau is in DESCRIPTOR units: about 0.5 for bit-planes (channels in [0, 1]), about 30 grey levels for intensity.
+ * Known limit.  The charge for invalid points favours poses that keep the scene in view: when the true motion moves a third of the template out of
+ * the image (measured: |t| = 2.5 m on the 240x320 plane scene, 2 626 of 3 856 points still in view), Identity can outscore a start next to the
+ * truth.  The score ranks starts; it is no estimate.
+ * Served: kLinear interpolation, the three warp formulations, descriptors of at most 48 channels.  Another interpolation, or a descriptor of more
+ * than 48 channels (LATCH of 8+ bytes, CentralDifference radius 4+): BPVO_ERR_UNSUPPORTED, the message says which.
+ * The calls read the template, the descriptor and the geometry; they touch no workspace: residuals, weights, tap cache, robust scale, Gauss-Newton
+ * state and every measurement counter stay as they were.  Device buffers for poses, partials and results belong to the context and grow on demand.
+ * ref_slot without a template: BPVO_ERR_NO_TEMPLATE; cur_slot without data: BPVO_ERR_NO_DATA; level outside [maxTestLevel, numLevels), n_poses < 1
+ * (or above 1 048 576), n_pairs < 1 (or above 65 535), tau not finite or <= 0, a NULL pointer: BPVO_ERR_INVALID_ARG. */
+typedef struct bpvo_hip_pose_score {
+  double cost_sum;
+  double score;
+  int    n_valid;
+  int    n_below;
+} bpvo_hip_pose_score;      /* 24 bytes */
+int bpvo_hip_score_poses(bpvo_hip_ctx* ctx, int ref_slot, int cur_slot, int level, int n_poses, const float* T /*[n_poses][16]*/, float tau,
+                         bpvo_hip_pose_score* out /*[n_poses]*/);
+/* ... of n_pairs pairs (refs[i], curs[i]) in ONE launch, n_poses poses each; the pairs may have cameras and sizes of their own
+ * (bpvo_hip_create_sequences).  Pair i's records are bit for bit those of bpvo_hip_score_poses on it alone. */
+int bpvo_hip_score_poses_pairs(bpvo_hip_ctx* ctx, int n_pairs, const int* refs, const int* curs, int level, int n_poses,
+                               const float* T /*[n_pairs][n_poses][16]*/, float tau, bpvo_hip_pose_score* out /*[n_pairs][n_poses]*/);
+/* Scores the n_cands candidate starts at score_level (< 0: the coarsest level), takes the lowest score (ties: the lowest index; a NaN score never
+ * wins) and runs bpvo_hip_estimate_pose on workspace ws with that candidate as T_init: T_est and stats are bit for bit those of
+ * bpvo_hip_estimate_pose(T_init = T_cands + 16 * chosen).  chosen and scores [n_cands] may be NULL. */
+int bpvo_hip_estimate_pose_best_start(bpvo_hip_ctx* ctx, int ws, int ref_slot, int cur_slot, int n_cands, const float* T_cands /*[n_cands][16]*/,
+                                      int score_level, float tau, float T_est[16], bpvo_hip_stats* stats /*[numLevels] or NULL*/, int* chosen,
+                                      bpvo_hip_pose_score* scores);
+
 /* Pyramid levels that were run by the persistent single-launch Gauss-Newton kernel (groups of BPVO_HIP_PERSIST_MAX_WS or fewer
  * pairs) since the context was created, and whether such a launch ever gave up at a grid barrier (the
  * context then stays on the four-kernel chain; results are the same either way). */

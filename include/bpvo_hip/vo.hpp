@@ -111,6 +111,9 @@ struct Result {                                                 // bpvo/types.h:
 
 /* The covariance of an estimated pose (c_api.h bpvo_hip_pose_covariances states the definition and its limits): `covariance` is that of eps in
  * T_true = pose * exp(eps), twist ordered (omega, v); `pose` is the estimate's pose against its key frame. */
+/* the score of one candidate pose (c_api.h bpvo_hip_pose_score: cost_sum, score, n_valid, n_below) */
+typedef bpvo_hip_pose_score PoseScore;
+
 struct PoseCovarianceEstimate {
   enum Status { kOk = BPVO_COV_OK, kIndefinite = BPVO_COV_INDEFINITE, kDegenerate = BPVO_COV_DEGENERATE, kNone = BPVO_COV_NONE };
   Pose pose;
@@ -271,6 +274,34 @@ class VisualOdometryPoseEstimator {
   {
     std::vector<bpvo_hip_stats> st(bpvo_hip_num_levels(_dev->ctx()));
     _dev->check(bpvo_hip_estimate_pose(_dev->ctx(), _ws, ref_frame->slot(), cur_frame->slot(), T_init.data(), T_est.data(), st.data()));
+    std::vector<OptimizerStatistics> ret;
+    for(const auto& s : st) ret.push_back(OptimizerStatistics(s));
+    return ret;
+  }
+  /* Pose scoring (c_api.h bpvo_hip_score_poses; no counterpart in the reference): the truncated-L1 score of every pose of `poses` at pyramid
+   * level `level`, one launch for all of them; tau in descriptor units (about 0.5 for bit-planes, about 30 grey levels for intensity).  Touches
+   * nothing of the estimator's state. */
+  std::vector<PoseScore> scorePoses(const VisualOdometryFrame* ref_frame, const VisualOdometryFrame* cur_frame, int level,
+                                    const std::vector<Matrix44>& poses, float tau) const
+  {
+    std::vector<float> T(poses.size() * 16);
+    for(size_t i = 0; i < poses.size(); ++i) std::memcpy(&T[16 * i], poses[i].data(), 16 * sizeof(float));
+    std::vector<PoseScore> out(poses.size());
+    _dev->check(bpvo_hip_score_poses(_dev->ctx(), ref_frame->slot(), cur_frame->slot(), level, (int) poses.size(), T.data(), tau, out.data()));
+    return out;
+  }
+  /* estimatePose from the best-scoring of the candidate starts (ties: the first; scoreLevel < 0: the coarsest level): exactly
+   * estimatePose(T_init = candidates[chosen]).  chosen / scores: which start it was and every candidate's score, where asked for. */
+  std::vector<OptimizerStatistics> estimatePoseFromBest(const VisualOdometryFrame* ref_frame, const VisualOdometryFrame* cur_frame,
+                                                        const std::vector<Matrix44>& candidates, float tau, Matrix44& T_est, int* chosen = nullptr,
+                                                        std::vector<PoseScore>* scores = nullptr, int scoreLevel = -1)
+  {
+    std::vector<float> T(candidates.size() * 16);
+    for(size_t i = 0; i < candidates.size(); ++i) std::memcpy(&T[16 * i], candidates[i].data(), 16 * sizeof(float));
+    std::vector<bpvo_hip_stats> st(bpvo_hip_num_levels(_dev->ctx()));
+    if(scores) scores->resize(candidates.size());
+    _dev->check(bpvo_hip_estimate_pose_best_start(_dev->ctx(), _ws, ref_frame->slot(), cur_frame->slot(), (int) candidates.size(), T.data(), scoreLevel, tau,
+                                                  T_est.data(), st.data(), chosen, scores ? scores->data() : nullptr));
     std::vector<OptimizerStatistics> ret;
     for(const auto& s : st) ret.push_back(OptimizerStatistics(s));
     return ret;
