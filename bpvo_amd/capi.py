@@ -78,6 +78,36 @@ class PoseScore(C.Structure):
 POSE_SCORE = np.dtype([("cost_sum", np.float64), ("score", np.float64), ("n_valid", np.int32), ("n_below", np.int32)])
 assert POSE_SCORE.itemsize == C.sizeof(PoseScore) == 24
 
+# the start policy (c_api.h: an extension, no reference member): where the addFrame drivers start Gauss-Newton
+START_KEYFRAME_POSE, START_CONSTANT_VELOCITY, START_SCORED = 0, 1, 2
+MAX_START_CANDIDATES, MAX_START_HINTS = 16, 13
+START_KIND_IDENTITY, START_KIND_LAST_MOTION, START_KIND_LAST_MOTION_TWICE, START_KIND_HINT = 0, 1, 2, 3
+
+
+class StartPolicy(C.Structure):
+    """bpvo_hip_start_policy: mode (START_*), score_level (-1: the coarsest), tau (descriptor units; mode START_SCORED only)."""
+    _fields_ = [("mode", C.c_int), ("score_level", C.c_int), ("tau", C.c_float)]
+
+
+class StartInfo(C.Structure):
+    """bpvo_hip_start_info: what an estimate of the last call started from."""
+    _fields_ = [("n_candidates", C.c_int), ("chosen", C.c_int), ("kind", C.c_int * MAX_START_CANDIDATES), ("T_start", C.c_float * 16),
+                ("scores", PoseScore * MAX_START_CANDIDATES)]
+
+
+assert C.sizeof(StartPolicy) == 12 and C.sizeof(StartInfo) == 520
+
+
+def start_policy(mode=START_KEYFRAME_POSE, score_level=-1, tau=0.0) -> StartPolicy:
+    return StartPolicy(int(mode), int(score_level), float(tau))
+
+
+def _start_info_dict(r: StartInfo):
+    n = int(r.n_candidates)
+    scores = np.frombuffer(bytes(r.scores), POSE_SCORE)[:n].copy()
+    return dict(n_candidates=n, chosen=int(r.chosen), kind=[int(k) for k in r.kind[:n]], T_start=np.array(r.T_start, np.float32).reshape(4, 4),
+                scores=scores)
+
 
 class Camera(C.Structure):
     """bpvo_hip_camera: one sequence's calibration and image size (bpvo_hip_create_sequences, bpvo_hip_seq_set_camera)."""
@@ -916,6 +946,83 @@ class Context:
                   T.ctypes.data_as(C.c_void_p), st, C.byref(chosen), scores.ctypes.data_as(C.c_void_p))
         stats = [dict(numIterations=s.numIterations, finalError=s.finalError, firstOrderOptimality=s.firstOrderOptimality, status=s.status) for s in st]
         return T, stats, chosen.value, scores
+
+    # -- start policy (bpvo_hip_set_start_policy ...; an extension: no reference member; HIP library only)
+    @staticmethod
+    def _policy_arg(policy):
+        if policy is None or isinstance(policy, StartPolicy):
+            return policy
+        if isinstance(policy, dict):
+            return start_policy(**policy)
+        return start_policy(*policy)
+
+    @staticmethod
+    def _policy_dict(p: StartPolicy):
+        return dict(mode=int(p.mode), score_level=int(p.score_level), tau=float(np.float32(p.tau)))
+
+    @staticmethod
+    def _hints_arg(hints):
+        M = _f32(hints if hints is not None and len(hints) else np.zeros((0, 4, 4))).reshape(-1, 16)
+        return M.shape[0], (M.ctypes.data_as(C.c_void_p) if M.shape[0] else None), M
+
+    def set_start_policy(self, policy):
+        """bpvo_hip_set_start_policy: the context's policy — a StartPolicy, a dict(mode, score_level, tau) or a (mode, score_level, tau) tuple."""
+        p = self._policy_arg(policy)
+        self.call("set_start_policy", C.byref(p))
+
+    def get_start_policy(self):
+        p = StartPolicy()
+        self._ck(self.b.fn("get_start_policy")(self.h, C.byref(p)))
+        return self._policy_dict(p)
+
+    def seq_set_start_policy(self, s, policy):
+        """bpvo_hip_seq_set_start_policy: sequence s's own policy; None returns it to the context's."""
+        p = self._policy_arg(policy)
+        self.call("seq_set_start_policy", int(s), None if p is None else C.byref(p))
+
+    def seq_get_start_policy(self, s):
+        """(policy dict, True if it is the sequence's own)"""
+        p, own = StartPolicy(), C.c_int()
+        self._ck(self.b.fn("seq_get_start_policy")(self.h, int(s), C.byref(p), C.byref(own)))
+        return self._policy_dict(p), bool(own.value)
+
+    def rigs_set_start_policy(self, rig, policy):
+        p = self._policy_arg(policy)
+        self.call("rigs_set_start_policy", int(rig), None if p is None else C.byref(p))
+
+    def rigs_get_start_policy(self, rig):
+        p, own = StartPolicy(), C.c_int()
+        self._ck(self.b.fn("rigs_get_start_policy")(self.h, int(rig), C.byref(p), C.byref(own)))
+        return self._policy_dict(p), bool(own.value)
+
+    def vo_set_start_hints(self, hints):
+        """bpvo_hip_vo_set_start_hints: the pending hints [n, 4, 4] (frame-to-frame guesses in Result.pose's convention) of add_frame's next estimate."""
+        n, ptr, _keep = self._hints_arg(hints)
+        self.call("vo_set_start_hints", n, ptr)
+
+    def seq_set_start_hints(self, s, hints):
+        n, ptr, _keep = self._hints_arg(hints)
+        self.call("seq_set_start_hints", int(s), n, ptr)
+
+    def rigs_set_start_hints(self, rig, hints):
+        n, ptr, _keep = self._hints_arg(hints)
+        self.call("rigs_set_start_hints", int(rig), n, ptr)
+
+    def vo_start_info(self, which=0):
+        """bpvo_hip_vo_start_info: dict(n_candidates, chosen, kind [n], T_start [4, 4], scores POSE_SCORE [n]) of estimate `which` of the last add_frame."""
+        out = StartInfo()
+        self.call("vo_start_info", int(which), C.byref(out))
+        return _start_info_dict(out)
+
+    def seq_start_info(self, s, which=0):
+        out = StartInfo()
+        self.call("seq_start_info", int(s), int(which), C.byref(out))
+        return _start_info_dict(out)
+
+    def rigs_start_info(self, rig, which=0):
+        out = StartInfo()
+        self.call("rigs_start_info", int(rig), int(which), C.byref(out))
+        return _start_info_dict(out)
 
     # -- batches
     def _stats_array(self, st, n_pairs):

@@ -195,6 +195,7 @@ struct bpvo_hip_ctx {
 
   bpvo_hip_params params;
   int point_budget[kMaxLevels] = {};   // bpvo_hip_set_point_budget: template points a level keeps at most, the most salient first (0: no budget)
+  bpvo_hip_start_policy start_policy = {BPVO_START_KEYFRAME_POSE, -1, 0.0f};   // bpvo_hip_set_start_policy: where the addFrame drivers start (vo_state.h); bodies without their own run it
   float K[9];
   float baseline;
   int rows, cols, L, C, device;
@@ -661,6 +662,12 @@ int pose_cov_ensure_scratch(bpvo_hip_ctx* c);
 void pose_cov_none(bpvo_hip_pose_covariance* r);      // the record of "nothing was estimated": Identity pose and covariance, BPVO_COV_NONE
 void pose_cov_free(bpvo_hip_ctx* c);
 void pose_score_free(bpvo_hip_ctx* c);      // score.hip: the scoring calls' device buffers
+// ... does the context serve pose scoring (kLinear, at most 48 channels)?  BPVO_OK, or BPVO_ERR_UNSUPPORTED with the message
+int pose_score_served(bpvo_hip_ctx* c);
+// ... and the call behind bpvo_hip_score_poses(_pairs): the records of n_poses poses T [n_pairs][n_poses][16] for each of the pairs, one launch,
+// no workspace touched; the addFrame drivers score their start candidates with it (vo.hip)
+int score_pairs(bpvo_hip_ctx* c, int n_pairs, const int* refs, const int* curs, int level, int n_poses, const float* T, float tau,
+                bpvo_hip_pose_score* out);
 int set_option(bpvo_hip_ctx* c, const std::string& key, double v);
 int apply_options_string(bpvo_hip_ctx* c, const char* str);
 struct OptionDef { const char* key; double lo, hi; std::function<double(bpvo_hip_ctx*)> get; std::function<int(bpvo_hip_ctx*, double)> set; };

@@ -28,8 +28,19 @@ static int score_grow(bpvo_hip_ctx* c, T** p, size_t* cap, size_t need)
   return BPVO_OK;
 }
 
-static int score_pairs(bpvo_hip_ctx* c, int n_pairs, const int* refs, const int* curs, int level, int n_poses, const float* T, float tau,
-                       bpvo_hip_pose_score* out)
+int pose_score_served(bpvo_hip_ctx* c)
+{
+  if(c->params.interp != BPVO_INTERP_LINEAR) {
+    const char* kind = c->params.interp == BPVO_INTERP_COSINE ? "kCosine" : c->params.interp == BPVO_INTERP_CUBIC ? "kCubic" : "kCubicHermite";
+    return fail(c, BPVO_ERR_UNSUPPORTED, (std::string("pose score: kLinear interpolation only, this context runs ") + kind).c_str());
+  }
+  if(c->G > 1 || c->C > 48)
+    return fail(c, BPVO_ERR_UNSUPPORTED, ("pose score: descriptors of at most 48 channels only, this context's has " + std::to_string(c->C)).c_str());
+  return BPVO_OK;
+}
+
+int score_pairs(bpvo_hip_ctx* c, int n_pairs, const int* refs, const int* curs, int level, int n_poses, const float* T, float tau,
+                bpvo_hip_pose_score* out)
 {
   if(!refs || !curs || !T || !out) return fail(c, BPVO_ERR_INVALID_ARG, "pose score: nullptr slots / poses / records");
   if(n_pairs < 1 || n_pairs > 65535) return fail(c, BPVO_ERR_INVALID_ARG, "pose score: n_pairs must be within 1 .. 65535");
@@ -37,12 +48,7 @@ static int score_pairs(bpvo_hip_ctx* c, int n_pairs, const int* refs, const int*
   if(!(tau > 0.0f) || !std::isfinite(tau)) return fail(c, BPVO_ERR_INVALID_ARG, "pose score: tau must be finite and positive");
   CHECK_LEVEL(c, level);
   for(int i = 0; i < n_pairs; ++i) { CHECK_SLOT(c, refs[i]); CHECK_SLOT(c, curs[i]); }
-  if(c->params.interp != BPVO_INTERP_LINEAR) {
-    const char* kind = c->params.interp == BPVO_INTERP_COSINE ? "kCosine" : c->params.interp == BPVO_INTERP_CUBIC ? "kCubic" : "kCubicHermite";
-    return fail(c, BPVO_ERR_UNSUPPORTED, (std::string("pose score: kLinear interpolation only, this context runs ") + kind).c_str());
-  }
-  if(c->G > 1 || c->C > 48)
-    return fail(c, BPVO_ERR_UNSUPPORTED, ("pose score: descriptors of at most 48 channels only, this context's has " + std::to_string(c->C)).c_str());
+  if(int rc = pose_score_served(c)) return rc;
   for(int i = 0; i < n_pairs; ++i) {
     if(!c->frames[refs[i]].has_template) return fail(c, BPVO_ERR_NO_TEMPLATE, "pose score: reference frame has no template");
     if(!c->frames[curs[i]].has_data) return fail(c, BPVO_ERR_NO_DATA, "pose score: no data in frame");

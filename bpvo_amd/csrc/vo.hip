@@ -324,6 +324,72 @@ int bpvo_hip_add_frame_stereo(bpvo_hip_ctx* c, const uint8_t* left, const uint8_
   return add_frame_impl(c, d_left, c->st_disp, true, ret);
 }
 static void slot_clear(bpvo_hip_ctx* c, int slot) { c->frames[slot].has_data = false; c->frames[slot].has_template = false; }
+
+// ---- the start policy in the drivers (vo_state.h states the rule: "where an estimate starts") ----------------------------------------------
+// the policy a body runs: its own, or the context's
+static const bpvo_hip_start_policy& body_policy(const bpvo_hip_ctx* c, const SeqState& q) { return q.own_policy ? q.policy : c->start_policy; }
+// A body about to estimate: its n member pairs (refs[p], curs[p]) and their extrinsics X [n][16] (null: one member that is the body)
+struct StartBody { SeqState* body; int n; const int* refs; const int* curs; const float* X; };
+// Where estimate `which` of each of the m bodies starts: T_start[k], and the body's SeqState::start[which].  Modes 0 and 1 are host work only.  The
+// bodies in mode 2 are scored by score_pairs — which touches no workspace and gives a pair the same records whatever shares its launch —, all
+// their member pairs in ONE call per distinct (score level, tau) among them, in order of first appearance; a shorter candidate list is padded
+// with its candidate 0, whose repeats are not read back.  The choice is vo_start_choose's, on the host, from the returned records.
+static int choose_starts(bpvo_hip_ctx* c, int which, int m, const StartBody* b, M44* T_start)
+{
+  std::vector<StartCandidates> sc((size_t) m);
+  std::vector<int> scored;      // the bodies in mode 2
+  for(int k = 0; k < m; ++k) {
+    const bpvo_hip_start_policy& pol = body_policy(c, *b[k].body);
+    sc[k] = vo_start_candidates(*b[k].body, pol, which);
+    if(pol.mode == BPVO_START_SCORED) scored.push_back(k);
+    else T_start[k] = vo_start_choose(*b[k].body, which, sc[k], nullptr);
+  }
+  std::vector<char> done((size_t) m, 0);
+  for(int k0 : scored) {
+    if(done[k0]) continue;
+    const bpvo_hip_start_policy& pol0 = body_policy(c, *b[k0].body);
+    const int level = pol0.score_level < 0 ? c->L - 1 : pol0.score_level;
+    std::vector<int> group, refs, curs;
+    int n_poses = 0;
+    for(int k : scored) {
+      const bpvo_hip_start_policy& pol = body_policy(c, *b[k].body);
+      if(done[k] || (pol.score_level < 0 ? c->L - 1 : pol.score_level) != level || pol.tau != pol0.tau) continue;
+      done[k] = 1;
+      group.push_back(k);
+      n_poses = std::max(n_poses, sc[k].n);
+      refs.insert(refs.end(), b[k].refs, b[k].refs + b[k].n);
+      curs.insert(curs.end(), b[k].curs, b[k].curs + b[k].n);
+    }
+    const size_t n_pairs = refs.size();
+    std::vector<float> T(n_pairs * (size_t) n_poses * 16);
+    size_t pair = 0;
+    for(int k : group)
+      for(int p = 0; p < b[k].n; ++p, ++pair)
+        for(int j = 0; j < n_poses; ++j) {
+          const M44& cand = sc[k].T[j < sc[k].n ? j : 0];
+          float* dst = &T[(pair * (size_t) n_poses + (size_t) j) * 16];
+          if(b[k].X) rig_member_pose(b[k].X + 16 * (size_t) p, cand.m, dst);      // (what estimate_rigs starts its members with)
+          else std::memcpy(dst, cand.m, 64);
+        }
+    std::vector<bpvo_hip_pose_score> rec(n_pairs * (size_t) n_poses);
+    if(int rc = score_pairs(c, (int) n_pairs, refs.data(), curs.data(), level, n_poses, T.data(), pol0.tau, rec.data())) return rc;
+    pair = 0;
+    for(int k : group) {
+      bpvo_hip_pose_score body_rec[BPVO_HIP_MAX_START_CANDIDATES];
+      std::vector<bpvo_hip_pose_score> mine((size_t) b[k].n);
+      std::vector<int> n_points((size_t) b[k].n);
+      for(int p = 0; p < b[k].n; ++p) n_points[(size_t) p] = c->frames[b[k].refs[p]].n_host[level];
+      for(int j = 0; j < sc[k].n; ++j) {
+        for(int p = 0; p < b[k].n; ++p) mine[(size_t) p] = rec[(pair + (size_t) p) * (size_t) n_poses + (size_t) j];
+        body_rec[j] = vo_rig_start_score(mine.data(), n_points.data(), b[k].n, c->C, pol0.tau);
+      }
+      T_start[k] = vo_start_choose(*b[k].body, which, sc[k], body_rec);
+      pair += (size_t) b[k].n;
+    }
+  }
+  return BPVO_OK;
+}
+
 static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* disparity, bool on_device, bpvo_hip_result* ret)
 {
   if(!ret) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr result");
@@ -367,9 +433,16 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
   const int ws0 = 0;
   rc = check_template_not_empty(c, q.ref);
   if(rc) { (void) upload_now(); (void) hipStreamSynchronize(c->stream); return rc; }
+  // the start (vo_state.h; the default policy: T_kf itself and no launch).  The scored mode's round trip lies here, in front of the estimate
+  M44 T_start;
+  {
+    const StartBody sb{&q, 1, &q.ref, &q.cur, nullptr};
+    rc = choose_starts(c, 0, 1, &sb, &T_start);
+    if(rc) { (void) upload_now(); (void) hipStreamSynchronize(c->stream); return rc; }
+  }
   c->prefetch_frac_thr = c->params.goodPointThreshold;      // the decision's fraction of good points rides behind the estimate
   if(disparity_pending) c->before_final_sync = [&]() { return upload_now(); };
-  rc = estimate_batch(c, 1, &ws0, &q.ref, &q.cur, q.T_kf.m, T_est.m, ret->optimizerStatistics);
+  rc = estimate_batch(c, 1, &ws0, &q.ref, &q.cur, T_start.m, T_est.m, ret->optimizerStatistics);
   c->prefetch_frac_thr = -1.0f;
   {      // (an estimate that did not come by its final synchronisation — an error on the way, another path — : now)
     const int rcu = upload_now();
@@ -407,8 +480,12 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
       fr.no_final_sync = !c->profiling;
       fr.defer_finest_nrm = true;
       rc = frames_set_template(c, kf.template_slot, 1, 1, fr);
-      const M44 I = m44_identity();
-      if(rc == BPVO_OK) rc = estimate_batch(c, 1, &ws0, &q.ref, &q.cur, I.m, T_again.m, ret->optimizerStatistics);
+      M44 T_start2 = m44_identity();      // (the default policy: the Identity)
+      if(rc == BPVO_OK) {
+        const StartBody sb{&q, 1, &q.ref, &q.cur, nullptr};
+        rc = choose_starts(c, 1, 1, &sb, &T_start2);
+      }
+      if(rc == BPVO_OK) rc = estimate_batch(c, 1, &ws0, &q.ref, &q.cur, T_start2.m, T_again.m, ret->optimizerStatistics);
       // (an error on the way: nothing of this call stays in flight)
       if(c->nrm_pending) { (void) hipEventSynchronize(c->nrm_pending); c->nrm_pending = nullptr; }
       if(c->nrm_pending_finest) { (void) hipEventSynchronize(c->nrm_pending_finest); c->nrm_pending_finest = nullptr; }
@@ -775,8 +852,18 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
   // 4. estimatePose(ref, cur, T_kf) of the others, each from its body's T_kf: one estimate
   bool own = false;
   std::vector<M44> T_init((size_t) m), T_est, T_again;
-  for(int k = 0; k < m; ++k) { T_init[k] = est[k]->body->T_kf; own = own || est[k]->body->own_params; }
+  for(int k = 0; k < m; ++k) own = own || est[k]->body->own_params;
   const Members M = members_of(est);
+  // (their starts: vo_state.h's rule — the default policy gives T_kf itself and adds no launch; the scored mode one score_pairs call per
+  // distinct (level, tau) among them)
+  auto starts = [&](int which, const std::vector<const Entry*>& ents, const Members& Mm, std::vector<M44>& T) {
+    std::vector<StartBody> sb(ents.size());
+    for(size_t k = 0; k < ents.size(); ++k) sb[k] = StartBody{ents[k]->body, ents[k]->n, &Mm.refs[Mm.first[k]], &Mm.curs[Mm.first[k]], ents[k]->X};
+    T.assign(ents.size(), m44_identity());
+    return choose_starts(c, which, (int) ents.size(), sb.data(), T.data());
+  };
+  rc = starts(0, est, M, T_init);
+  if(rc) return drain(rc);
   rc = entries_estimate(c, est, M, own, T_init, T_est);
   if(rc) return drain(rc);
   // option "pose_covariance": behind the estimate and before the key frames' stages rewrite any slot (the entries that estimate again: once more
@@ -857,7 +944,10 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
     if(rc) return drain(rc);
     if(!re.empty()) {
       const Members M2 = members_of(again);
-      rc = entries_estimate(c, again, M2, own, std::vector<M44>(re.size(), m44_identity()), T_again);
+      std::vector<M44> T_init2;
+      rc = starts(1, again, M2, T_init2);
+      if(rc) return drain(rc);
+      rc = entries_estimate(c, again, M2, own, T_init2, T_again);
       if(rc) return drain(rc);
       if(c->pose_covariance) {
         std::vector<bpvo_hip_pose_covariance> cov2(re.size());
@@ -928,6 +1018,9 @@ static int rigs_set_impl(bpvo_hip_ctx* c, int n_rigs, const int* count, const in
       if(int rc = seq_is_fresh(c, s, "rig membership changes")) return rc;
   for(int i = 0; i < n && !c->seqs.empty(); ++i)
     if(c->seqs[ids[i]].own_params) return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "has parameters of its own: a rig runs its own (bpvo_hip_rigs_set_params) or the context's parameters");
+  for(int i = 0; i < n && !c->seqs.empty(); ++i)
+    if(c->seqs[ids[i]].own_policy || !c->seqs[ids[i]].hints.empty())
+      return seq_fail(c, BPVO_ERR_INVALID_ARG, ids[i], "has a start policy or hints of its own: a rig runs its body's (bpvo_hip_rigs_set_start_policy) or the context's");
   seq_states(c);
   for(RigState& g : c->rigs) { g.body.own_params = false; rig_param_target(c, g); }
   c->rigs.assign((size_t) n_rigs, RigState());
@@ -1339,6 +1432,111 @@ int bpvo_hip_rigs_get_params(const bpvo_hip_ctx* c, int rig, bpvo_hip_params* p)
   if(!c || !p || rig < 0 || (size_t) rig >= c->rigs.size()) return BPVO_ERR_INVALID_ARG;
   *p = c->rigs[rig].body.params;
   return BPVO_OK;
+}
+
+// ---- the start policy's setters and records (extensions; the rule and its refusals: vo_state.h) ---------------------------------------------
+// BPVO_OK, or why the context refuses the policy (nothing is changed)
+static int start_policy_check(bpvo_hip_ctx* c, const bpvo_hip_start_policy* pol)
+{
+  if(!pol) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr start policy");
+  if(const char* why = vo_start_policy_refusal(*pol, c->L, c->params.maxTestLevel)) return fail(c, BPVO_ERR_INVALID_ARG, why);
+  if(pol->mode == BPVO_START_SCORED) return pose_score_served(c);
+  return BPVO_OK;
+}
+static int start_hints_set(bpvo_hip_ctx* c, SeqState& q, int n, const float* M)
+{
+  if(const char* why = vo_start_hints_refusal(body_policy(c, q), n, M)) return fail(c, BPVO_ERR_INVALID_ARG, why);
+  vo_set_start_hints(q, n, M);
+  return BPVO_OK;
+}
+static int start_info_get(bpvo_hip_ctx* c, const SeqState* q, int which, bpvo_hip_start_info* out)
+{
+  if(!out) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr start info");
+  if(which < 0 || which > 1) return fail(c, BPVO_ERR_INVALID_ARG, "start info: which must be 0 (against the key frame the call began with) or 1 (the re-estimate)");
+  if(q) *out = q->start[which];
+  else std::memset(out, 0, sizeof(*out));
+  return BPVO_OK;
+}
+static int seq_not_in_a_rig(bpvo_hip_ctx* c, int seq, const char* what)
+{
+  for(const RigState& g : c->rigs)
+    for(int s : g.seq)
+      if(s == seq) return seq_fail(c, BPVO_ERR_INVALID_ARG, seq, (std::string("is a member of a rig: ") + what + " belong to the rig's body (bpvo_hip_rigs_set_start_policy / _hints)").c_str());
+  return BPVO_OK;
+}
+int bpvo_hip_set_start_policy(bpvo_hip_ctx* c, const bpvo_hip_start_policy* policy)
+{
+  CHECK_CTX(c);
+  if(int rc = start_policy_check(c, policy)) return rc;
+  c->start_policy = *policy;
+  return BPVO_OK;
+}
+int bpvo_hip_get_start_policy(const bpvo_hip_ctx* c, bpvo_hip_start_policy* policy)
+{
+  if(!c || !policy) return BPVO_ERR_INVALID_ARG;
+  *policy = c->start_policy;
+  return BPVO_OK;
+}
+int bpvo_hip_seq_set_start_policy(bpvo_hip_ctx* c, int seq, const bpvo_hip_start_policy* policy)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  if(int rc = seq_not_in_a_rig(c, seq, "a start policy and hints")) return rc;
+  if(policy)
+    if(int rc = start_policy_check(c, policy)) return rc;
+  seq_states(c);
+  SeqState& q = c->seqs[seq];
+  q.own_policy = policy != nullptr;
+  if(policy) q.policy = *policy;
+  return BPVO_OK;
+}
+int bpvo_hip_seq_get_start_policy(const bpvo_hip_ctx* c, int seq, bpvo_hip_start_policy* policy, int* own)
+{
+  if(!c || !policy || seq < 0 || seq >= seq_capacity(c)) return BPVO_ERR_INVALID_ARG;
+  const SeqState* q = seq_state(c, seq);
+  *policy = q ? body_policy(c, *q) : c->start_policy;
+  if(own) *own = q && q->own_policy ? 1 : 0;
+  return BPVO_OK;
+}
+int bpvo_hip_rigs_set_start_policy(bpvo_hip_ctx* c, int rig, const bpvo_hip_start_policy* policy)
+{
+  CHECK_CTX(c); CHECK_RIG(c, rig);
+  if(policy)
+    if(int rc = start_policy_check(c, policy)) return rc;
+  SeqState& q = c->rigs[rig].body;
+  q.own_policy = policy != nullptr;
+  if(policy) q.policy = *policy;
+  return BPVO_OK;
+}
+int bpvo_hip_rigs_get_start_policy(const bpvo_hip_ctx* c, int rig, bpvo_hip_start_policy* policy, int* own)
+{
+  if(!c || !policy || rig < 0 || (size_t) rig >= c->rigs.size()) return BPVO_ERR_INVALID_ARG;
+  *policy = body_policy(c, c->rigs[rig].body);
+  if(own) *own = c->rigs[rig].body.own_policy ? 1 : 0;
+  return BPVO_OK;
+}
+int bpvo_hip_vo_set_start_hints(bpvo_hip_ctx* c, int n, const float* M) { CHECK_CTX(c); return start_hints_set(c, c->vo, n, M); }
+int bpvo_hip_seq_set_start_hints(bpvo_hip_ctx* c, int seq, int n, const float* M)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  if(int rc = seq_not_in_a_rig(c, seq, "a start policy and hints")) return rc;
+  seq_states(c);
+  return start_hints_set(c, c->seqs[seq], n, M);
+}
+int bpvo_hip_rigs_set_start_hints(bpvo_hip_ctx* c, int rig, int n, const float* M)
+{
+  CHECK_CTX(c); CHECK_RIG(c, rig);
+  return start_hints_set(c, c->rigs[rig].body, n, M);
+}
+int bpvo_hip_vo_start_info(bpvo_hip_ctx* c, int which, bpvo_hip_start_info* out) { CHECK_CTX(c); return start_info_get(c, &c->vo, which, out); }
+int bpvo_hip_seq_start_info(bpvo_hip_ctx* c, int seq, int which, bpvo_hip_start_info* out)
+{
+  CHECK_CTX(c); CHECK_SEQ(c, seq);
+  return start_info_get(c, seq_state(c, seq), which, out);
+}
+int bpvo_hip_rigs_start_info(bpvo_hip_ctx* c, int rig, int which, bpvo_hip_start_info* out)
+{
+  CHECK_CTX(c); CHECK_RIG(c, rig);
+  return start_info_get(c, &c->rigs[rig].body, which, out);
 }
 #undef CHECK_RIG
 #undef CHECK_SEQ

@@ -1,8 +1,8 @@
 // libbpvo_hip, host side: the state machine of VisualOdometry::addFrame (reference: bpvo/vo.cc:125-224) for bpvo_hip_add_frame, for every
 // sequence of bpvo_hip_add_frames and for every rig of bpvo_hip_add_frames_rig(s).  No HIP header: the two drivers (vo.hip: add_frame_impl, the
 // single-sequence latency path, and add_frames_run, the one batched driver of sequences and rigs) queue the GPU work and keep the frame slots'
-// flags; every decision and every change of a SeqState is made here, once, for all (tests/test_vo_state_cpu.py and tests/test_rig_cpu.py
-// compile this header with a plain C++ compiler).
+// flags; every decision and every change of a SeqState — where an estimate starts among them — is made here, once, for all
+// (tests/test_vo_state_cpu.py, tests/test_rig_cpu.py and tests/test_start_policy_cpu.py compile this header with a plain C++ compiler).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -12,6 +12,7 @@
 
 #include "../../include/bpvo_hip/c_api.h"
 #include "device_math.h"
+#include "pose_score_math.h"
 #include "rig_math.h"
 
 namespace bpvo_hip_host {
@@ -29,6 +30,15 @@ struct SeqState {
   // own_params: they differ from the context's in a field the library reads (only then do the sequence's jobs and decisions take them from here)
   bpvo_hip_params params;
   bool own_params = false;
+  // the start policy (below: "where an estimate starts").  M: the pose the body's last Result carried, as vo_finish wrote it — Identity after
+  // vo_reset and after a first frame; policy / own_policy: the body's own policy (bpvo_hip_seq / rigs_set_start_policy; the context's until
+  // then) — it outlives vo_reset, like the parameters; hints: the pending hints, used by the next call that estimates and dropped by
+  // vo_finish and by vo_reset; start[which]: what estimate `which` of the last call started from
+  M44 M = m44_identity();
+  bpvo_hip_start_policy policy = {BPVO_START_KEYFRAME_POSE, -1, 0.0f};
+  bool own_policy = false;
+  std::vector<M44> hints;
+  bpvo_hip_start_info start[2] = {};
 };
 // a fresh VisualOdometry on slots first_slot .. first_slot + 2 (the slots' flags are the caller's)
 inline void vo_reset(SeqState& q, int first_slot)
@@ -38,6 +48,9 @@ inline void vo_reset(SeqState& q, int first_slot)
   q.trajectory.clear();
   q.cloud_n = 0;
   q.cloud_pose = m44_identity();
+  q.M = m44_identity();
+  q.hints.clear();
+  std::memset(q.start, 0, sizeof(q.start));
 }
 
 // what addFrame hands back before it knows anything
@@ -58,6 +71,7 @@ inline void vo_begin_frame(SeqState& q, int numLevels, bpvo_hip_result* ret)    
   vo_init_result(numLevels, ret);
   q.cloud_n = 0;
   q.cloud_pose = m44_identity();
+  std::memset(q.start, 0, sizeof(q.start));      // (no estimate of this call has run yet)
 }
 inline void trajectory_push(std::vector<M44>& trajectory, const M44& T)   // Trajectory::push_back + InvertPose (bpvo/trajectory.cc:30-50)
 {
@@ -150,6 +164,109 @@ inline void vo_finish(SeqState& q, const M44& T_est, const M44* T_again, bpvo_hi
   std::memcpy(ret->pose, pose.m, 64);
   trajectory_push(q.trajectory, pose);
   if(ret->hasPointCloud) q.cloud_pose = q.trajectory.back();
+  q.M = pose;
+  q.hints.clear();      // (both estimates of the call have used them)
+}
+
+// ---- where an estimate starts (an extension: the reference knows mode 0 only, bpvo/vo.cc:144-145,184-186).  A call makes up to two estimates: which = 0
+// against the key frame it began with, base B = T_kf; which = 1 against the new key frame, base B = Identity.  A candidate c — a frame-to-frame
+// motion in Result::pose's convention — starts the estimate at m44_mul(c, B); for which = 1 that is c itself, and the candidate Identity is B
+// itself: neither takes a product.
+//   mode 0  Identity                                                      today's start, bit for bit; no hints
+//   mode 1  hints[0] if one is pending, else M                            that one; nothing is scored
+//   mode 2  Identity (kind 0), M (kind 1), m44_mul(M, M) (kind 2),        the lowest score by pose_score_argmin: ties go to the first — the
+//           then the pending hints (kind 3)                               reference's start —, a NaN never wins
+// (A sequence's second frame has M = Identity: mode 2 then starts where mode 0 does.)
+enum { START_KIND_IDENTITY = 0, START_KIND_LAST_MOTION = 1, START_KIND_LAST_MOTION_TWICE = 2, START_KIND_HINT = 3 };
+struct StartCandidates {
+  int n = 0;
+  int kind[BPVO_HIP_MAX_START_CANDIDATES] = {};
+  M44 T[BPVO_HIP_MAX_START_CANDIDATES];
+};
+// null, or why the policy is refused before the context is asked whether it serves the scoring (numLevels, maxTestLevel: the context's)
+inline const char* vo_start_policy_refusal(const bpvo_hip_start_policy& pol, int numLevels, int maxTestLevel)
+{
+  if(pol.mode < BPVO_START_KEYFRAME_POSE || pol.mode > BPVO_START_SCORED) return "start policy: mode must be 0 (key-frame pose), 1 (constant velocity) or 2 (scored)";
+  if(pol.mode != BPVO_START_SCORED) return nullptr;
+  if(!(pol.tau > 0.0f) || !(pol.tau - pol.tau == 0.0f)) return "start policy: the scored mode needs a tau that is finite and positive (descriptor units; no default is guessed)";
+  if(pol.score_level != -1 && (pol.score_level < maxTestLevel || pol.score_level >= numLevels))
+    return "start policy: score_level must be -1 (the coarsest) or within [maxTestLevel, numLevels)";
+  return nullptr;
+}
+// the hints a body may hold under a policy: null, or why n of them are refused (a hint: rigid and finite, rig_extrinsic_ok's rule)
+inline const char* vo_start_hints_refusal(const bpvo_hip_start_policy& pol, int n, const float* M)
+{
+  if(n < 0 || (n > 0 && !M)) return "start hints: n >= 0 poses";
+  if(n > 0 && pol.mode == BPVO_START_KEYFRAME_POSE) return "start hints: the body's start policy is mode 0 (key-frame pose), which takes none";
+  if(n > 1 && pol.mode == BPVO_START_CONSTANT_VELOCITY) return "start hints: mode 1 (constant velocity) takes at most one";
+  if(n > BPVO_HIP_MAX_START_HINTS) return "start hints: at most 13";
+  for(int i = 0; i < n; ++i)
+    if(!rig_extrinsic_ok(M + 16 * (size_t) i)) return "start hints: a hint is not a rigid transform (finite, last row 0 0 0 1, R^T R = I within 1e-4)";
+  return nullptr;
+}
+inline void vo_set_start_hints(SeqState& q, int n, const float* M)
+{
+  q.hints.resize((size_t) n);
+  for(int i = 0; i < n; ++i) std::memcpy(q.hints[(size_t) i].m, M + 16 * (size_t) i, 64);
+}
+// the candidates of estimate `which` of body q under the policy it runs with (hints beyond what the mode takes — the policy changed after they
+// were set — are not listed)
+inline StartCandidates vo_start_candidates(const SeqState& q, const bpvo_hip_start_policy& pol, int which)
+{
+  StartCandidates sc;
+  const M44 B = which == 0 ? q.T_kf : m44_identity();
+  auto add = [&](int kind, const M44& c) {
+    sc.kind[sc.n] = kind;
+    sc.T[sc.n] = kind == START_KIND_IDENTITY ? B : which == 0 ? m44_mul(c, B) : c;
+    ++sc.n;
+  };
+  if(pol.mode == BPVO_START_CONSTANT_VELOCITY) {
+    if(!q.hints.empty()) add(START_KIND_HINT, q.hints[0]);
+    else add(START_KIND_LAST_MOTION, q.M);
+  } else if(pol.mode == BPVO_START_SCORED) {
+    add(START_KIND_IDENTITY, B);
+    add(START_KIND_LAST_MOTION, q.M);
+    add(START_KIND_LAST_MOTION_TWICE, m44_mul(q.M, q.M));
+    for(size_t i = 0; i < q.hints.size() && sc.n < BPVO_HIP_MAX_START_CANDIDATES; ++i) add(START_KIND_HINT, q.hints[i]);
+  } else {
+    add(START_KIND_IDENTITY, B);
+  }
+  return sc;
+}
+// The choice: records null (modes 0 and 1: the one candidate, zeroed records) or the candidates' records [sc.n] (mode 2).  Writes q.start[which]
+// and returns the pose the estimate starts at.
+inline M44 vo_start_choose(SeqState& q, int which, const StartCandidates& sc, const bpvo_hip_pose_score* records)
+{
+  bpvo_hip_start_info& info = q.start[which];
+  std::memset(&info, 0, sizeof(info));
+  info.n_candidates = sc.n;
+  double score[BPVO_HIP_MAX_START_CANDIDATES];
+  for(int k = 0; k < sc.n; ++k) {
+    info.kind[k] = sc.kind[k];
+    if(records) info.scores[k] = records[k];
+    score[k] = info.scores[k].score;
+  }
+  info.chosen = records ? pose_score_argmin(score, sc.n) : 0;
+  std::memcpy(info.T_start, sc.T[info.chosen].m, 64);
+  return sc.T[info.chosen];
+}
+// A rig's record of one body candidate from its members' records of it (rec[p], template of n_points[p] points): the sums are the members' sums,
+// the score is pooled like the fraction of good points — (sum cost_sum_p + tau sum C (N_p - n_valid_p)) / sum C N_p, f64, member order; nothing
+// to score (sum N_p = 0): tau.  One member: its own record.
+inline bpvo_hip_pose_score vo_rig_start_score(const bpvo_hip_pose_score* rec, const int* n_points, int n, int C, float tau)
+{
+  if(n == 1) return rec[0];
+  bpvo_hip_pose_score out = {};
+  double charged = 0.0, terms = 0.0;
+  for(int p = 0; p < n; ++p) {
+    out.cost_sum += rec[p].cost_sum;
+    out.n_valid += rec[p].n_valid;
+    out.n_below += rec[p].n_below;
+    charged += (double) ((long long) C * (long long) (n_points[p] - rec[p].n_valid));
+    terms += (double) ((long long) C * (long long) n_points[p]);
+  }
+  out.score = terms > 0.0 ? (out.cost_sum + (double) tau * charged) / terms : (double) tau;
+  return out;
 }
 
 // ---- a body that moves as one: what the batched driver (vo.hip: add_frames_run) advances.  A rig (bpvo_hip_add_frames_rig(s)) is a body of n

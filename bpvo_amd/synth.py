@@ -353,6 +353,31 @@ def make_sequence(rows: int, cols: int, n_frames: int, index: int = 0, step_rot:
     return dict(K=K, b=b, frames=frames, poses=poses)
 
 
+def make_sequence_steps(rows: int, cols: int, steps, direction, rot, index: int = 0, extrinsics=None):
+    """The plane scene along a trajectory of GIVEN steps (start-policy tests: an accelerating camera): len(steps) + 1 frames, frame k + 1 at
+    twist_to_matrix((rot, steps[k] * direction)) @ T_k — a constant rotation step `rot` (3) and translation steps of steps[k] metres along
+    `direction` (3, used as given).  Returns make_sequence's dict.  extrinsics: a list of 4x4 camera_from_body — the body follows that
+    trajectory and the dict is make_rig_sequence's (frames [k][p], K and b per member, extrinsics)."""
+    seed = 1000 + int(index)
+    K, b = calibration(rows, cols)
+    direction = np.asarray(direction, dtype=np.float64).reshape(3)
+    rot = np.asarray(rot, dtype=np.float64).reshape(3)
+    X = None if extrinsics is None else [np.asarray(x, dtype=np.float64).reshape(4, 4) for x in extrinsics]
+    T = np.eye(4)
+    frames, poses = [], []
+    for f in range(len(steps) + 1):
+        if X is None:
+            frames.append(_render(K, b, rows, cols, T, seed, 10.0, (0.1, -0.15)))
+        else:
+            frames.append([_render(K, b, rows, cols, Xp @ T, seed, 10.0, (0.1, -0.15)) for Xp in X])
+        poses.append(T.copy())
+        if f < len(steps):
+            T = twist_to_matrix(np.concatenate([rot, float(steps[f]) * direction])) @ T
+    if X is None:
+        return dict(K=K, b=b, frames=frames, poses=poses)
+    return dict(K=[K] * len(X), b=[b] * len(X), frames=frames, poses=poses, extrinsics=X)
+
+
 def make_rig_sequence(rows: int, cols: int, n_frames: int, extrinsics, index: int = 0, step_rot: float = 0.004, step_trans: float = 0.03, cameras=None):
     """make_sequence's plane seen by the cameras of a rigid rig: the body follows make_sequence's trajectory (poses[k] = T_k, body_k from
     body_0), member p with extrinsic extrinsics[p] (4x4 camera_from_body) is rendered from extrinsics[p] @ T_k.  cameras: None (every member

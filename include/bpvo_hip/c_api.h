@@ -610,6 +610,63 @@ int bpvo_hip_estimate_pose_best_start(bpvo_hip_ctx* ctx, int ws, int ref_slot, i
                                       int score_level, float tau, float T_est[16], bpvo_hip_stats* stats /*[numLevels] or NULL*/, int* chosen,
                                       bpvo_hip_pose_score* scores);
 
+/* ---- start policy: where the addFrame drivers begin Gauss-Newton (an extension, off by default: it replaces no reference member).  The reference
+ * starts every estimate at T_kf, the pose accumulated since the key frame, and a key frame's re-estimate at the Identity (bpvo/vo.cc:144-145,184-186): a
+ * start that is wrong by one whole inter-frame motion.  A policy lets bpvo_hip_add_frame(_stereo), bpvo_hip_add_frames(_stereo) and
+ * bpvo_hip_add_frames_rig(s) start at the body's own last motion, at a caller's hint, or at the best-scoring of them (bpvo_hip_score_poses).
+ * The rule (stated once, bpvo_amd/csrc/vo_state.h).  A call makes up to two estimates: which = 0 against the key frame the call began with, base
+ * B = T_kf; which = 1 against the new key frame, base B = Identity.  M is the `pose` of the body's last Result (f32; Identity after creation,
+ * after bpvo_hip_seq_reset and after a first frame).  A candidate c starts the estimate at c B (the host's f32 4x4 product, index-order sums);
+ * for which = 1 it is c itself, and the candidate Identity is B itself, no product.
+ *   mode BPVO_START_KEYFRAME_POSE (0, the default, the reference): the one candidate Identity — today's start, bit for bit, no launch added
+ *   mode BPVO_START_CONSTANT_VELOCITY (1): the pending hint if there is one, else M; nothing is scored, no launch is added
+ *   mode BPVO_START_SCORED (2): Identity (kind 0), M (kind 1), M M (kind 2), then the pending hints (kind 3), scored at score_level (-1: the
+ *     coarsest) with truncation tau (descriptor units, finite and > 0: no default is guessed); the lowest score starts the estimate, ties go to
+ *     the first — the reference's start —, a NaN never wins.  One more launch pair and one host round trip per estimate; in the batched
+ *     drivers one per distinct (score_level, tau) among the entries that estimate.  A rig scores member p at its member pose of the body
+ *     candidate and pools like its fraction of good points: (sum_p cost_sum_p + tau sum_p C (N_p - n_valid_p)) / sum_p C N_p, in f64, member order.
+ * Hints: at most BPVO_HIP_MAX_START_HINTS rigid 4x4 frame-to-frame guesses in Result::pose's convention (an IMU or odometry prediction), stored
+ * by the setter, used by both estimates of the body's next call that estimates, then dropped (bpvo_hip_seq_reset drops them too).
+ * A policy outlives bpvo_hip_seq_reset, like parameters and budgets; it may change while the body holds frames and takes effect at the next call.
+ * Refusals, each leaving the earlier setting in place: mode outside 0 .. 2, a mode-2 tau that is not finite and positive, score_level other than
+ * -1 or within [maxTestLevel, numLevels), a hint that is not rigid and finite, more than 13 hints (mode 1: more than one; mode 0: any), a policy or
+ * hints for a sequence that is a member of a rig: BPVO_ERR_INVALID_ARG; mode 2 on a context pose scoring does not serve: BPVO_ERR_UNSUPPORTED. */
+#define BPVO_HIP_MAX_START_CANDIDATES 16
+#define BPVO_HIP_MAX_START_HINTS 13
+enum { BPVO_START_KEYFRAME_POSE = 0, BPVO_START_CONSTANT_VELOCITY = 1, BPVO_START_SCORED = 2 };
+typedef struct bpvo_hip_start_policy { int mode; int score_level; float tau; } bpvo_hip_start_policy;
+/* What estimate `which` of the body's last call started from: n_candidates = 0 when that estimate did not run; kind[k] as above; chosen: the
+ * candidate it started at, T_start its pose (a rig: the body's); scores[k]: the candidates' records — zeroed in modes 0 and 1, which list their
+ * one candidate; for a rig score is the pooled score and cost_sum, n_valid, n_below are the members' sums. */
+typedef struct bpvo_hip_start_info {
+  int   n_candidates;
+  int   chosen;
+  int   kind[BPVO_HIP_MAX_START_CANDIDATES];
+  float T_start[16];
+  bpvo_hip_pose_score scores[BPVO_HIP_MAX_START_CANDIDATES];
+} bpvo_hip_start_info;      /* 520 bytes */
+/* bpvo_hip_set_start_policy / bpvo_hip_get_start_policy (an extension, no reference member): the context's policy — bpvo_hip_add_frame, and every
+ * sequence and rig without one of its own. */
+int bpvo_hip_set_start_policy(bpvo_hip_ctx* ctx, const bpvo_hip_start_policy* policy);
+int bpvo_hip_get_start_policy(const bpvo_hip_ctx* ctx, bpvo_hip_start_policy* policy);
+/* bpvo_hip_seq_set_start_policy / bpvo_hip_seq_get_start_policy (an extension, no reference member): sequence seq's own policy in the place of the
+ * context's (policy NULL: back to the context's); the getter returns the policy its next call runs with, own (may be NULL): 1 if it is its own. */
+int bpvo_hip_seq_set_start_policy(bpvo_hip_ctx* ctx, int seq, const bpvo_hip_start_policy* policy);
+int bpvo_hip_seq_get_start_policy(const bpvo_hip_ctx* ctx, int seq, bpvo_hip_start_policy* policy, int* own);
+/* bpvo_hip_rigs_set_start_policy / bpvo_hip_rigs_get_start_policy (an extension, no reference member): the same for the body of rig `rig`. */
+int bpvo_hip_rigs_set_start_policy(bpvo_hip_ctx* ctx, int rig, const bpvo_hip_start_policy* policy);
+int bpvo_hip_rigs_get_start_policy(const bpvo_hip_ctx* ctx, int rig, bpvo_hip_start_policy* policy, int* own);
+/* bpvo_hip_vo_set_start_hints / bpvo_hip_seq_set_start_hints / bpvo_hip_rigs_set_start_hints (extensions, no reference member): the pending hints
+ * of bpvo_hip_add_frame's state / of sequence seq / of rig `rig` (body poses); n = 0 drops them; a new call replaces the earlier hints. */
+int bpvo_hip_vo_set_start_hints(bpvo_hip_ctx* ctx, int n, const float* M /*[n][16]*/);
+int bpvo_hip_seq_set_start_hints(bpvo_hip_ctx* ctx, int seq, int n, const float* M /*[n][16]*/);
+int bpvo_hip_rigs_set_start_hints(bpvo_hip_ctx* ctx, int rig, int n, const float* M /*[n][16]*/);
+/* bpvo_hip_vo_start_info / bpvo_hip_seq_start_info / bpvo_hip_rigs_start_info (extensions, no reference member): the record of estimate which
+ * (0 or 1) of the last bpvo_hip_add_frame / of sequence seq's / of rig `rig`'s last call. */
+int bpvo_hip_vo_start_info(bpvo_hip_ctx* ctx, int which, bpvo_hip_start_info* out);
+int bpvo_hip_seq_start_info(bpvo_hip_ctx* ctx, int seq, int which, bpvo_hip_start_info* out);
+int bpvo_hip_rigs_start_info(bpvo_hip_ctx* ctx, int rig, int which, bpvo_hip_start_info* out);
+
 /* Pyramid levels that were run by the persistent single-launch Gauss-Newton kernel (groups of BPVO_HIP_PERSIST_MAX_WS or fewer
  * pairs) since the context was created, and whether such a launch ever gave up at a grid barrier (the
  * context then stays on the four-kernel chain; results are the same either way). */

@@ -114,6 +114,22 @@ struct Result {                                                 // bpvo/types.h:
 /* the score of one candidate pose (c_api.h bpvo_hip_pose_score: cost_sum, score, n_valid, n_below) */
 typedef bpvo_hip_pose_score PoseScore;
 
+/* where the addFrame drivers start Gauss-Newton (c_api.h "start policy", an extension with no reference member): at the reference's start
+ * (kKeyFramePose, the default), at the body's last motion or a hint (kConstantVelocity), or at the best-scoring of Identity, the last motion, the
+ * last motion twice and the hints (kScored; tau in descriptor units, scoreLevel -1: the coarsest) */
+struct StartPolicy : public bpvo_hip_start_policy {
+  enum Mode { kKeyFramePose = BPVO_START_KEYFRAME_POSE, kConstantVelocity = BPVO_START_CONSTANT_VELOCITY, kScored = BPVO_START_SCORED };
+  explicit StartPolicy(int mode_ = kKeyFramePose, float tau_ = 0.0f, int scoreLevel = -1) { mode = mode_; score_level = scoreLevel; tau = tau_; }
+};
+/* what an estimate of the last call started from (c_api.h bpvo_hip_start_info: n_candidates, chosen, kind, T_start, scores) */
+typedef bpvo_hip_start_info StartInfo;
+inline std::vector<float> packPoses(const std::vector<Matrix44>& poses)
+{
+  std::vector<float> M(16 * poses.size());
+  for(size_t i = 0; i < poses.size(); ++i) std::memcpy(&M[16 * i], poses[i].data(), 16 * sizeof(float));
+  return M;
+}
+
 struct PoseCovarianceEstimate {
   enum Status { kOk = BPVO_COV_OK, kIndefinite = BPVO_COV_INDEFINITE, kDegenerate = BPVO_COV_DEGENERATE, kNone = BPVO_COV_NONE };
   Pose pose;
@@ -422,6 +438,11 @@ class VisualOdometry {
   /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
   void setPointBudget(int finestLevelPoints) { _dev->setPointBudget(_dev->quarteredPointBudget(finestLevelPoints)); }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
+  /* where addFrame starts Gauss-Newton (an extension; c_api.h bpvo_hip_set_start_policy), the hints of the next estimate (frame-to-frame guesses in
+   * Result::pose's convention), and what estimate `which` of the last addFrame started from (0: against the key frame, 1: the re-estimate) */
+  void setStartPolicy(const StartPolicy& policy) { _dev->check(bpvo_hip_set_start_policy(_dev->ctx(), &policy)); }
+  void setStartHints(const std::vector<Matrix44>& hints) { const std::vector<float> M = packPoses(hints); _dev->check(bpvo_hip_vo_set_start_hints(_dev->ctx(), (int) hints.size(), M.data())); }
+  StartInfo startInfo(int which = 0) const { StartInfo r; _dev->check(bpvo_hip_vo_start_info(_dev->ctx(), which, &r)); return r; }
   /* Result::covariance carries the covariance of the estimated pose (option "pose_covariance"); poseCovariance(): the last frame's record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
   PoseCovarianceEstimate poseCovariance() const
@@ -563,6 +584,12 @@ class VisualOdometrySequences {
   void setPointBudget(int s, const std::vector<int>& maxPoints) { _dev->setPointBudget(s, maxPoints); }
   /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
   void setPointBudget(int s, int finestLevelPoints) { _dev->setPointBudget(s, _dev->quarteredPointBudget(finestLevelPoints)); }
+  /* where the sequences start Gauss-Newton (an extension; c_api.h bpvo_hip_set_start_policy): every sequence's, or sequence s's own; the hints of
+   * sequence s's next estimate; what estimate `which` of its last frame started from */
+  void setStartPolicy(const StartPolicy& policy) { _dev->check(bpvo_hip_set_start_policy(_dev->ctx(), &policy)); }
+  void setStartPolicy(int s, const StartPolicy& policy) { _dev->check(bpvo_hip_seq_set_start_policy(_dev->ctx(), s, &policy)); }
+  void setStartHints(int s, const std::vector<Matrix44>& hints) { const std::vector<float> M = packPoses(hints); _dev->check(bpvo_hip_seq_set_start_hints(_dev->ctx(), s, (int) hints.size(), M.data())); }
+  StartInfo startInfo(int s, int which = 0) const { StartInfo r; _dev->check(bpvo_hip_seq_start_info(_dev->ctx(), s, which, &r)); return r; }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   /* Result::covariance of every sequence carries the covariance of its estimated pose (option "pose_covariance"); poseCovariance(s): sequence s's last record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
@@ -679,6 +706,11 @@ class RigVisualOdometry {
   void setPointBudget(const std::vector<int>& maxPoints) { _dev->setPointBudget(maxPoints); }
   /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
   void setPointBudget(int finestLevelPoints) { _dev->setPointBudget(_dev->quarteredPointBudget(finestLevelPoints)); }
+  /* where the body starts Gauss-Newton (an extension; c_api.h bpvo_hip_rigs_set_start_policy on rig 0), the hints of its next estimate (body
+   * motions), what estimate `which` of its last frame started from */
+  void setStartPolicy(const StartPolicy& policy) { _dev->check(bpvo_hip_rigs_set_start_policy(_dev->ctx(), 0, &policy)); }
+  void setStartHints(const std::vector<Matrix44>& hints) { const std::vector<float> M = packPoses(hints); _dev->check(bpvo_hip_rigs_set_start_hints(_dev->ctx(), 0, (int) hints.size(), M.data())); }
+  StartInfo startInfo(int which = 0) const { StartInfo r; _dev->check(bpvo_hip_rigs_start_info(_dev->ctx(), 0, which, &r)); return r; }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   /* Result::covariance carries the covariance of the BODY pose, in the plain body twist (option "pose_covariance"); poseCovariance(): the last frame's record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
@@ -796,6 +828,12 @@ class RigsVisualOdometry {
   void setPointBudget(const std::vector<int>& maxPoints) { _dev->setPointBudget(maxPoints); }
   /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
   void setPointBudget(int finestLevelPoints) { _dev->setPointBudget(_dev->quarteredPointBudget(finestLevelPoints)); }
+  /* where the bodies start Gauss-Newton (an extension; c_api.h bpvo_hip_set_start_policy): every rig's, or rig `rig`'s own; the hints of its next
+   * estimate (body motions); what estimate `which` of its last frame started from */
+  void setStartPolicy(const StartPolicy& policy) { _dev->check(bpvo_hip_set_start_policy(_dev->ctx(), &policy)); }
+  void setStartPolicy(int rig, const StartPolicy& policy) { _dev->check(bpvo_hip_rigs_set_start_policy(_dev->ctx(), rig, &policy)); }
+  void setStartHints(int rig, const std::vector<Matrix44>& hints) { const std::vector<float> M = packPoses(hints); _dev->check(bpvo_hip_rigs_set_start_hints(_dev->ctx(), rig, (int) hints.size(), M.data())); }
+  StartInfo startInfo(int rig, int which = 0) const { StartInfo r; _dev->check(bpvo_hip_rigs_start_info(_dev->ctx(), rig, which, &r)); return r; }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
   /* the record of the rig's last frame: the covariance of its BODY pose, in the plain body twist */
