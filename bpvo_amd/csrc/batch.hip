@@ -169,7 +169,7 @@ int upload_consume(bpvo_hip_ctx* c, UploadRun& u, int lo, int hi, const FrameRun
     fr.tab = 2 * p0;
     fr.selected_ev = nullptr; fr.on_selected = nullptr;
     // skip_odd_disp = 2: the staging area holds the A frames' disparities only, packed
-    int rc = frames_set_data(c, 2 * p0, 1, 2 * np, c->up_d_img + (size_t) 2 * p0 * npix, c->up_d_disp + (size_t) p0 * npix, true, fr, 2);
+    int rc = frames_set_data_slots(c, strided_slots(2 * p0, 1, 2 * np).data(), 2 * np, c->up_d_img + (size_t) 2 * p0 * npix, c->up_d_disp + (size_t) p0 * npix, true, fr, 2);
     if(rc) return rc;
     i += take;
   }
@@ -212,13 +212,14 @@ int batch_run_staggered(bpvo_hip_ctx* c, int n_pairs, int nl, const uint8_t* ima
       if(n <= 0) continue;
       FrameRun fr{ln->stream, ln, 2 * lo, true, nullptr, nullptr};
       int rc = pipe ? upload_consume(c, *pipe, lo, hi, fr)
-                    : frames_set_data(c, 2 * lo, 1, 2 * n, images + (size_t) 2 * lo * npix, disparities + (size_t) 2 * lo * npix, on_device, fr, c->keep_current_disparity ? 0 : 1);
+                    : frames_set_data_slots(c, strided_slots(2 * lo, 1, 2 * n).data(), 2 * n, images + (size_t) 2 * lo * npix, disparities + (size_t) 2 * lo * npix, on_device, fr,
+                                            c->keep_current_disparity ? 0 : 1);
       if(rc) { rcs[k] = rc; return; }
       if(sub == 0) {
         fr.selected_ev = ln->selected_ev;     // recorded, and the next lane released, before the template stage waits for its point counts
         fr.on_selected = release_next;
       }
-      rc = frames_set_template(c, 2 * lo, 2, n, fr);
+      rc = frames_set_template_slots(c, strided_slots(2 * lo, 2, n).data(), n, fr);
       if(rc) { rcs[k] = rc; return; }
       std::vector<int> wss(n), refs(n), curs(n);
       for(int i = 0; i < n; ++i) { wss[i] = lo + i; refs[i] = 2 * (lo + i); curs[i] = 2 * (lo + i) + 1; }
@@ -303,7 +304,7 @@ int bpvo_hip_batch_run(bpvo_hip_ctx* c, int n_pairs, const uint8_t* images, cons
   // chain — so parameters that allow a dense level defer as the chain does: 8 dense pairs lost 11 - 43 % to the sums in front of their first
   // iteration; sparse team batches of 8 - 16 pairs lose 2 - 4 % to the deferral's three launches: scripts/path_sweep.py)
   fr.defer_finest_nrm = !team_serves(c, n_pairs) || n_pairs <= c->team_split_max_pairs || templates_may_be_dense(c);
-  rc = frames_set_template(c, 0, 2, n_pairs, fr);
+  rc = frames_set_template_slots(c, strided_slots(0, 2, n_pairs).data(), n_pairs, fr);
   if(rc == BPVO_OK) rc = bpvo_hip_batch_estimate(c, n_pairs, nullptr, poses, stats);
   // (an error on the way: nothing of this call stays in flight)
   if(c->nrm_pending) { (void) hipEventSynchronize(c->nrm_pending); c->nrm_pending = nullptr; }

@@ -11,7 +11,7 @@ FrameRun ctx_run(bpvo_hip_ctx* c) { return FrameRun{c->stream, &c->lanes[0], 0, 
 
 // which: 0 = table of the setData stage, 1 = table of the setTemplate stage (two tables, so that queueing the template stage does not
 // have to wait for the descriptor kernels that still read the first).  Returns the device table through *tab (row fr.tab of level 0).
-int upload_frame_jobs_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr, int which, const FrameJob** tab)
+int upload_frame_jobs(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr, int which, const FrameJob** tab)
 {
   const size_t table = (size_t) which * c->L * c->n_frames;
   FR_CK(c, fr, hipEventSynchronize(fr.ln->staging_ev[which]));   // the pinned rows may still feed the copy of an earlier call
@@ -38,10 +38,16 @@ std::vector<int> strided_slots(int first, int stride, int count)
   for(int i = 0; i < count; ++i) v[i] = first + i * stride;
   return v;
 }
-int upload_frame_jobs(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr, int which, const FrameJob** tab)
+// the launch-wide sizes of a stage: those of its slots (the context's, or one camera size of bpvo_hip_add_frames), which must all agree
+static const LevelGeom* stage_geom(bpvo_hip_ctx* c, const int* slots, int count)
 {
-  const std::vector<int> slots = strided_slots(first, stride, count);
-  return upload_frame_jobs_slots(c, slots.data(), count, fr, which, tab);
+  const LevelGeom* geom = c->frames[slots[0]].own_geom ? c->frames[slots[0]].geom : c->geom;
+  for(int i = 1; i < count; ++i)
+    if(slot_geom(c, c->frames[slots[i]], 0).rows != geom[0].rows || slot_geom(c, c->frames[slots[i]], 0).cols != geom[0].cols) {
+      fail(c, BPVO_ERR_INVALID_ARG, "frame stage over slots of different sizes");
+      return nullptr;
+    }
+  return geom;
 }
 
 // VisualOdometryFrame::setData (reference: bpvo/vo_frame.cc:48-55) for `count` frames at once
@@ -53,12 +59,11 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
                           const FrameRun& fr, int skip_odd_disp, const size_t* offsets)
 {
   if(count <= 0) return BPVO_OK;
-  // the launch-wide sizes: those of the stage's slots (the context's, or one camera size of bpvo_hip_add_frames)
-  const LevelGeom* geom = c->frames[slots[0]].own_geom ? c->frames[slots[0]].geom : c->geom;
-  for(int i = 1; i < count; ++i)
-    if(slot_geom(c, c->frames[slots[i]], 0).rows != geom[0].rows || slot_geom(c, c->frames[slots[i]], 0).cols != geom[0].cols)
-      return fail(c, BPVO_ERR_INVALID_ARG, "frame stage over slots of different sizes");
+  const LevelGeom* geom = stage_geom(c, slots, count);
+  if(!geom) return BPVO_ERR_INVALID_ARG;
   const size_t npix = geom[0].npix;
+  const bpvo_hip_params& p = c->params;
+  const DescriptorForm form = descriptor_form(p, c->C);
   hipStream_t s = fr.stream;
   if(!on_device) {
     for(int i = 0; i < count; ++i) {
@@ -71,19 +76,19 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
   }
   // pair batches: the compact channel-0 plane serves the saliency map of TEMPLATE frames only; the current frames' descriptor kernel
   // skips its store (the selection reads channel 0 from the records should such a frame be made a template later)
-  for(int i = 0; i < count; ++i) c->frames[slots[i]].ch0_valid = !(skip_odd_disp && (i & 1));
+  // (FrameSlot::ch0_valid, set with the lazy flags below)
   // ... and the TEMPLATE frames (A, even) of a pair batch keep no records at the NMS levels (FrameSlot::lazy): bit-planes with the census
   // fused into the blur kernel, CD3 gradients.  Every other frame, and every frame set through the frame API, is dense.
-  const bool lazy_ok = skip_odd_disp != 0 && c->lazy_template && c->params.descriptor == BPVO_DESC_BITPLANES && c->C == 8 &&
-                       !(c->params.sigmaPriorToCensusTransform > 0.0f) && c->params.sigmaBitPlanes > 0.0f && c->params.gradientEstimation == BPVO_GRAD_CD3;
+  const bool lazy_ok = skip_odd_disp != 0 && c->lazy_template && form == DF_BITPLANES_FUSED && p.gradientEstimation == BPVO_GRAD_CD3;
   // ... and not even channel 0 where the tiled selection (NMS radius 1) forms it from the census bytes (option lazy_template_saliency):
   // census_templates_kernel writes those, and the blur below runs over the dense tile columns of such a level only
   const bool census_only_ok = lazy_ok && c->lazy_saliency;
   bool census_only[kMaxLevels] = {};
   bool any_census_only = false;
-  for(int l = c->params.maxTestLevel; l < c->L; ++l) any_census_only |= census_only[l] = census_only_ok && geom[l].nms_radius == 1;
+  for(int l = p.maxTestLevel; l < c->L; ++l) any_census_only |= census_only[l] = census_only_ok && geom[l].nms_radius == 1;
   for(int i = 0; i < count; ++i) {
     FrameSlot& f = c->frames[slots[i]];
+    f.ch0_valid = !(skip_odd_disp && (i & 1));
     for(int l = 0; l < c->L; ++l) {
       f.lazy[l] = (lazy_ok && !(i & 1) && geom[l].nms_radius > 0) ? (census_only[l] ? 2 : 1) : 0;
       // a saliency map that would have been formed on demand from the data replaced here can no longer be (until the next template)
@@ -91,7 +96,7 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
     }
   }
   const FrameJob* tab = nullptr;
-  int rc = upload_frame_jobs_slots(c, slots, count, fr, 0, &tab);
+  int rc = upload_frame_jobs(c, slots, count, fr, 0, &tab);
   if(rc) return rc;
   const int NF = c->n_frames;
   if(on_device && offsets) {
@@ -122,51 +127,35 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
     }
   }
   {
+    const int tested = c->L - p.maxTestLevel;
     double px = 0;
-    for(int l = c->L - 1; l >= c->params.maxTestLevel; --l) px += (double) geom[l].npix * count;
+    for(int l = p.maxTestLevel; l < c->L; ++l) px += (double) geom[l].npix * count;
     ScopedTimer t(c, KC_DESCRIPTOR, px, fr.ln);
-    // few frames, bit-planes with the census fused: every level in ONE launch (kernels_frame.hip level_job)
-    const bool fused_bp = c->C == 8 && c->params.descriptor == BPVO_DESC_BITPLANES && !(c->params.sigmaPriorToCensusTransform > 0.0f) && c->params.sigmaBitPlanes > 0.0f;
-    const int l_lo = c->params.maxTestLevel;
-    // ... and the same for the census of the smoothed image + the bit-planes blur (conf/perf_bitplanes.cfg: two launches) and the intensity descriptor
-    const bool smoothed_bp = c->C == 8 && c->params.descriptor == BPVO_DESC_BITPLANES && c->params.sigmaPriorToCensusTransform > 0.0f && c->params.sigmaBitPlanes > 0.0f;
-    const bool plain_intensity = c->C == 1 && c->params.descriptor != BPVO_DESC_LAPLACIAN;
-    const bool one_launch = (fused_bp || smoothed_bp || plain_intensity) && count <= c->merge_levels_max_frames && c->L - l_lo > 1;
-    if(one_launch && fused_bp) {
-      if(any_census_only) launch_census_templates(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->L - l_lo, NF);
-      launch_bitplanes(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->params.sigmaBitPlanes, c->gauss_k, 1, c->L - l_lo, NF);
-    } else if(one_launch && smoothed_bp) {
-      launch_census(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->census_taps, c->L - l_lo, NF);
-      launch_bitplanes(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->params.sigmaBitPlanes, c->gauss_k, 0, c->L - l_lo, NF);
-    } else if(one_launch) {
-      launch_intensity(s, tab + (size_t) l_lo * NF, geom[l_lo].cols, geom[l_lo].rows, count, c->L - l_lo, NF);
-    }
-    for(int l = c->L - 1; l >= c->params.maxTestLevel && !one_launch; --l) {   // DenseDescriptorPyramid::init (dense_descriptor_pyramid.cc:67-71)
-      const FrameJob* jobs = tab + (size_t) l * NF;
-      const LevelGeom& g = geom[l];
-      if(c->params.descriptor == BPVO_DESC_CENTRAL_DIFFERENCE) {
-        launch_central_difference(s, jobs, g.cols, g.rows, count, c->params.centralDifferenceRadius, c->cd_before, c->cd_after);
-      } else if(c->params.descriptor == BPVO_DESC_LATCH) {
-        launch_latch(s, jobs, g.cols, g.rows, count, c->params.latchNumBytes, c->params.latchHalfSsdSize, c->d_latch_off, c->latch_taps[0], c->latch_taps[1],
-                     c->latch_after);
-      } else if(c->C == 5 || c->C == 10) {
-        launch_descriptor_fields(s, jobs, g.cols, g.rows, count, c->C == 10, c->df_g1, c->df_g2);
-      } else if(c->C == 3) {
-        launch_gradient_descriptor(s, jobs, g.cols, g.rows, count, c->grad_pre);
-      } else if(c->C == 1) {
-        if(c->params.descriptor == BPVO_DESC_LAPLACIAN) launch_laplacian(s, jobs, g.cols, g.rows, count, c->params.laplacianKernelSize);
-        else launch_intensity(s, jobs, g.cols, g.rows, count);
-      } else {
-        // census fused into the bit-planes kernel unless the census is taken of the smoothed image or the planes stay unsmoothed
-        const bool fused_census = !(c->params.sigmaPriorToCensusTransform > 0.0f) && c->params.sigmaBitPlanes > 0.0f;
-        if(census_only[l]) {      // (implies the fused census)
-          launch_census_templates(s, jobs, g.cols, g.rows, count);
-          launch_bitplanes_pairs(s, jobs, g.cols, g.rows, count, c->gauss_k);
-          continue;
-        }
-        if(!fused_census)
-          launch_census(s, jobs, g.cols, g.rows, count, c->params.sigmaPriorToCensusTransform > 0.0f ? c->census_taps : nullptr);
-        launch_bitplanes(s, jobs, g.cols, g.rows, count, c->params.sigmaBitPlanes, c->gauss_k, fused_census ? 1 : 0);
+    // DenseDescriptorPyramid::init (dense_descriptor_pyramid.cc:67-71): the levels in one launch (frame_plan.h) or level by level
+    for(const LevelSpan& sp : level_spans(c->L, p.maxTestLevel, merge_descriptor_levels(count, c->merge_levels_max_frames, tested, form))) {
+      const FrameLaunch f = frame_launch(c, tab, geom, sp, count);
+      switch(form) {
+        case DF_BITPLANES_FUSED:
+          // census-only levels of a pair batch's template frames: their census bytes, then — level by level — the current frames over every tile and
+          // the template frames over the dense tile columns only; in one launch the blur kernel runs over all frames and leaves the lazy tiles itself
+          if(sp.count > 1 ? any_census_only : census_only[sp.first]) launch_census_templates(s, f);
+          if(sp.count == 1 && census_only[sp.first]) launch_bitplanes_pairs(s, f, c->gauss_k);
+          else launch_bitplanes(s, f, p.sigmaBitPlanes, c->gauss_k, 1);
+          break;
+        case DF_BITPLANES_SMOOTHED_CENSUS:      // (conf/perf_bitplanes.cfg: two launches)
+        case DF_BITPLANES_UNSMOOTHED:
+          launch_census(s, f, p.sigmaPriorToCensusTransform > 0.0f ? c->census_taps : nullptr);
+          launch_bitplanes(s, f, p.sigmaBitPlanes, c->gauss_k, 0);
+          break;
+        case DF_INTENSITY: launch_intensity(s, f); break;
+        case DF_LAPLACIAN: launch_laplacian(s, f.jobs, f.W, f.R, count, p.laplacianKernelSize); break;
+        case DF_GRADIENT: launch_gradient_descriptor(s, f.jobs, f.W, f.R, count, c->grad_pre); break;
+        case DF_FIELDS_1ST:
+        case DF_FIELDS_2ND: launch_descriptor_fields(s, f.jobs, f.W, f.R, count, form == DF_FIELDS_2ND, c->df_g1, c->df_g2); break;
+        case DF_CENTRAL_DIFFERENCE: launch_central_difference(s, f.jobs, f.W, f.R, count, p.centralDifferenceRadius, c->cd_before, c->cd_after); break;
+        case DF_LATCH:
+          launch_latch(s, f.jobs, f.W, f.R, count, p.latchNumBytes, p.latchHalfSsdSize, c->d_latch_off, c->latch_taps[0], c->latch_taps[1], c->latch_after);
+          break;
       }
     }
   }
@@ -177,12 +166,6 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
     f.has_disp = !(skip_odd_disp && (i & 1));
   }
   return BPVO_OK;
-}
-int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uint8_t* images, const float* disps, bool on_device,
-                    const FrameRun& fr, int skip_odd_disp)
-{
-  const std::vector<int> slots = strided_slots(first, stride, count);
-  return frames_set_data_slots(c, slots.data(), count, images, disps, on_device, fr, skip_odd_disp);
 }
 // the disparity of a slot whose data stage ran with FrameRun::skip_disparity_upload, from the caller's host buffer, on the context's copy stream; the
 // context's stream waits for it (whatever is queued there later sees the disparity).  A copy from pageable memory holds the host until it is done
@@ -203,18 +186,15 @@ int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uin
   if(count <= 0) return BPVO_OK;
   if(first < 0 || stride < 1 || first + (count - 1) * stride >= c->n_frames) return fail(c, BPVO_ERR_INVALID_ARG, "bad frame slot range");
   if(!images || !disps) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image/disparity");
-  return frames_set_data(c, first, stride, count, images, disps, on_device, ctx_run(c), skip_odd_disp);
+  return frames_set_data_slots(c, strided_slots(first, stride, count).data(), count, images, disps, on_device, ctx_run(c), skip_odd_disp);
 }
 
 // VisualOdometryFrame::setTemplate (reference: bpvo/vo_frame.cc:61-93 -> bpvo/template_data.cc:37-142) for `count` frames
 int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr)
 {
   if(count <= 0) return BPVO_OK;
-  // the launch-wide sizes: those of the stage's slots (the context's, or one camera size of bpvo_hip_add_frames); storage: the context's
-  const LevelGeom* geom = c->frames[slots[0]].own_geom ? c->frames[slots[0]].geom : c->geom;
-  for(int i = 1; i < count; ++i)
-    if(slot_geom(c, c->frames[slots[i]], 0).rows != geom[0].rows || slot_geom(c, c->frames[slots[i]], 0).cols != geom[0].cols)
-      return fail(c, BPVO_ERR_INVALID_ARG, "frame stage over slots of different sizes");
+  const LevelGeom* geom = stage_geom(c, slots, count);      // (storage: the context's)
+  if(!geom) return BPVO_ERR_INVALID_ARG;
   hipStream_t s = fr.stream;
   for(int i = 0; i < count; ++i) {
     FrameSlot& f = c->frames[slots[i]];
@@ -226,122 +206,88 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
     FR_CK(c, fr, hipMemsetAsync(f.tmpl_slab, 0, total, s));
     carve_frame_tmpl(c, f, (unsigned char*) f.tmpl_slab, nullptr);
   }
-  // the saliency map of a census-only level is not stored: whoever reads it has it formed first (ensure_saliency)
-  for(int i = 0; i < count; ++i) {
-    FrameSlot& f = c->frames[slots[i]];
-    // (... but it is stored for a level with a point budget: the budget's threshold is read from the map)
-    for(int l = 0; l < c->L; ++l) f.sal_state[l] = (f.lazy[l] == 2 && slot_budget(c, f, l) <= 0) ? FrameSlot::SAL_ON_DEMAND : FrameSlot::SAL_STORED;
-  }
-  // the point budgets of the stage: what each slot's levels run with (bpvo_hip_get_selection_info), and whether any level of any slot has one
-  bool budget_at[kMaxLevels] = {}, any_budget = false;
+  // the point budgets of the stage: what each slot's levels run with (bpvo_hip_get_selection_info), and which levels have one in any slot
+  bool budget_at[kMaxLevels] = {};
   for(int i = 0; i < count; ++i) {
     FrameSlot& f = c->frames[slots[i]];
     f.min_saliency_used = (f.seq_params ? f.seq_params : &c->params)->minSaliency;
     for(int l = 0; l < c->L; ++l) {
       f.budget_used[l] = l >= c->params.maxTestLevel ? slot_budget(c, f, l) : 0;
-      if(f.budget_used[l] > 0) budget_at[l] = any_budget = true;
+      if(f.budget_used[l] > 0) budget_at[l] = true;
+      // the saliency map of a census-only level is not stored: whoever reads it has it formed first (ensure_saliency)
+      // (... but it is stored for a level with a point budget: the budget's threshold is read from the map)
+      f.sal_state[l] = (f.lazy[l] == 2 && slot_budget(c, f, l) <= 0) ? FrameSlot::SAL_ON_DEMAND : FrameSlot::SAL_STORED;
     }
   }
   const FrameJob* tab = nullptr;
-  int rc = upload_frame_jobs_slots(c, slots, count, fr, 1, &tab);
+  int rc = upload_frame_jobs(c, slots, count, fr, 1, &tab);
   if(rc) return rc;
   const int NF = c->n_frames;
   int* const h_ints = c->h_ints + (size_t) fr.tab * kMaxLevels;
   int* const d_ints = c->d_ints + (size_t) fr.tab * kMaxLevels;
   const bpvo_hip_params& p = c->params;
   const int border = std::max(p.nonMaxSuppRadius, 3);   // template_data.cc:51
-  // few frames, every level on the tiled path (NMS radius <= 1): the levels in ONE launch of each of its three kernels (kernels_frame.hip level_job)
+  const int tested = c->L - p.maxTestLevel;
   bool tiled = true;
   for(int l = p.maxTestLevel; l < c->L; ++l) tiled = tiled && geom[l].nms_radius <= 1;
-  const bool one_launch = tiled && count <= c->merge_levels_max_frames && c->L - p.maxTestLevel > 1;
   hipEvent_t counts_ev = fr.ln ? fr.ln->round_ev[0] : nullptr;      // (the lane's round events are idle outside its estimation)
   // The normalisation — sequential sums in the reference's order, a latency chain of one workgroup per (frame, level): 0.2 ms whatever the
   // batch — is read by the Gauss-Newton kernels only (the Jacobian rows are rebuilt there; template_build stores pixels and gradients).
   // A stage that runs alone on the context's stream (single frames, batches on one lane) puts it on a stream of its own — forked right
   // behind the selection, next to the read-back of the point counts, the host's round trip for them and template_build — and joins
   // the two before it returns; lanes of a fanned-out batch keep it in line.
-  hipStream_t side = nullptr;
-  if(c->nrm_side_stream && !fr.own_thread && fr.ln == &c->lanes[0] && counts_ev) {
-    if(!c->side_stream) {
-      FR_CK(c, fr, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-      FR_CK(c, fr, hipStreamCreateWithFlags(&c->side_stream2, hipStreamNonBlocking));
-      for(auto& e : c->side_ev) FR_CK(c, fr, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    side = c->side_stream;
+  const bool side = c->nrm_side_stream && !fr.own_thread && fr.ln == &c->lanes[0] && counts_ev;
+  if(side && !c->side_stream) {
+    FR_CK(c, fr, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+    FR_CK(c, fr, hipStreamCreateWithFlags(&c->side_stream2, hipStreamNonBlocking));
+    for(auto& e : c->side_ev) FR_CK(c, fr, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   // ... and when the estimation follows on this stream within the same call (fr.defer_finest_nrm: a batch on one lane), only the COARSEST
   // level's sums are joined here: the others — the longest is the first level without non-maximum suppression, 100 k points of a
   // 1241x376 frame, 0.17 ms — are needed when the Gauss-Newton iterations leave the coarsest level: ctx->nrm_pending, waited for by the
-  // estimation just before its second level (estimate.hip).
+  // estimation just before its second level (estimate.hip).  Which launches, streams and events that makes: normalization_plan (frame_plan.h)
   const int with_nrm = c->dspace ? 0 : p.withNormalization;      // DisparitySpaceWarp::setNormalization is a no-op (bpvo/disparity_space_warp.h:87-90)
-  const bool defer = side && fr.defer_finest_nrm && c->nrm_defer && c->L - p.maxTestLevel > 1 && !c->nrm_pending && !c->nrm_pending_finest;
-  if(one_launch) {
-    double px = 0;
-    for(int l = p.maxTestLevel; l < c->L; ++l) px += (double) geom[l].npix * count;
-    ScopedTimer t(c, KC_SALIENCY_SELECT, px, fr.ln);
-    const LevelGeom& g = geom[p.maxTestLevel];
-    launch_saliency_select(s, tab + (size_t) p.maxTestLevel * NF, c->C, g.cols, g.rows, count, 1, border, c->gauss_k,
-                           c->L - p.maxTestLevel, NF, any_budget ? SELECT_CANDIDATES : SELECT_ALL);
-  }
-  if(one_launch && any_budget) {
-    // a stage with a point budget: the budget's kernel between the candidates and their scan (units: the pixels it may visit)
-    const LevelGeom& g = geom[p.maxTestLevel];
+  const bool defer = fr.defer_finest_nrm && c->nrm_defer && !c->nrm_pending && !c->nrm_pending_finest;
+  const NrmPlan nrm = normalization_plan(c->L, p.maxTestLevel, side, defer, templates_may_be_dense(c));
+  // (on a side stream it is timed like the in-line form, with events there: they are resolved once this stream — which the side stream joins — is synchronised)
+  auto run_normalization = [&]() -> int {
+    if(side) FR_CK(c, fr, hipEventRecord(c->side_ev[0], s));
+    for(int k = 0; k < nrm.n; ++k) {
+      const NrmPart& q = nrm.part[k];
+      hipStream_t on = q.stream == NRM_INLINE ? s : (q.stream == NRM_SIDE ? c->side_stream : c->side_stream2);
+      if(on != s && (k == 0 || q.stream != nrm.part[k - 1].stream)) FR_CK(c, fr, hipStreamWaitEvent(on, c->side_ev[0], 0));
+      { ScopedTimer t(c, KC_NORMALIZATION, 0.0, fr.ln, true, on == s ? nullptr : on); launch_normalization(on, tab, NF, count, q.first_level, q.end_level, with_nrm, c->nrm_dpp_asm); }
+      if(q.event >= 0) FR_CK(c, fr, hipEventRecord(c->side_ev[q.event], on));
+    }
+    if(nrm.pending_finest_event >= 0) c->nrm_pending_finest = c->side_ev[nrm.pending_finest_event];
+    if(nrm.pending_event >= 0) c->nrm_pending = c->side_ev[nrm.pending_event];
+    return BPVO_OK;
+  };
+  // the selection: the levels in one launch of each of its kernels, or level by level.  A span with a point budget: the budget's kernel between
+  // the candidates and their scan (units: the pixels it may visit)
+  for(const LevelSpan& sp : level_spans(c->L, p.maxTestLevel, merge_selection_levels(count, c->merge_levels_max_frames, tested, tiled))) {
+    const FrameLaunch f = frame_launch(c, tab, geom, sp, count);
+    const int radius = geom[sp.first].nms_radius;      // (several levels: every one of them tiled)
+    double px = 0, budget_px = 0;
+    for(int l = sp.first; l < sp.first + sp.count; ++l) {
+      px += (double) geom[l].npix * count;
+      if(budget_at[l]) budget_px += (double) geom[l].npix * count;
+    }
+    const bool budget = budget_px > 0;
     {
-      double px = 0;
-      for(int l = p.maxTestLevel; l < c->L; ++l) px += budget_at[l] ? (double) geom[l].npix * count : 0.0;
-      ScopedTimer t(c, KC_POINT_BUDGET, px, fr.ln);
-      launch_point_budget(s, tab + (size_t) p.maxTestLevel * NF, count, 1, c->L - p.maxTestLevel, NF);
+      ScopedTimer t(c, KC_SALIENCY_SELECT, px, fr.ln);
+      launch_saliency_select(s, f, c->C, radius, border, c->gauss_k, budget ? SELECT_CANDIDATES : SELECT_ALL);
+    }
+    if(!budget) continue;
+    {
+      ScopedTimer t(c, KC_POINT_BUDGET, budget_px, fr.ln);
+      launch_point_budget(s, f, radius);
     }
     ScopedTimer t(c, KC_SALIENCY_SELECT, 0.0, fr.ln);
-    launch_saliency_select(s, tab + (size_t) p.maxTestLevel * NF, c->C, g.cols, g.rows, count, 1, border, c->gauss_k,
-                           c->L - p.maxTestLevel, NF, SELECT_COMPACT);
+    launch_saliency_select(s, f, c->C, radius, border, c->gauss_k, SELECT_COMPACT);
   }
-  for(int l = c->L - 1; l >= p.maxTestLevel && !one_launch; --l) {
-    const FrameJob* jobs = tab + (size_t) l * NF;
-    const LevelGeom& g = geom[l];
-    {
-      ScopedTimer t(c, KC_SALIENCY_SELECT, (double) g.npix * count, fr.ln);
-      launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, border, c->gauss_k, 1, 0, budget_at[l] ? SELECT_CANDIDATES : SELECT_ALL);
-    }
-    if(!budget_at[l]) continue;
-    {
-      ScopedTimer t(c, KC_POINT_BUDGET, (double) g.npix * count, fr.ln);
-      launch_point_budget(s, jobs, count, g.nms_radius);
-    }
-    ScopedTimer t(c, KC_SALIENCY_SELECT, 0.0, fr.ln);
-    launch_saliency_select(s, jobs, c->C, g.cols, g.rows, count, g.nms_radius, border, c->gauss_k, 1, 0, SELECT_COMPACT);
-  }
-  if(side) {
-    FR_CK(c, fr, hipEventRecord(c->side_ev[0], s));
-    FR_CK(c, fr, hipStreamWaitEvent(side, c->side_ev[0], 0));
-    // (timed like the in-line form, with events on the side stream: they are resolved once this stream — which the side stream joins — is synchronised)
-    if(defer && templates_may_be_dense(c)) {
-      // parameters that allow a dense level (NMS off on a large one): the finest level first, on its own stream (the longest chain of adds — 2 ms for
-      // 300 k points — starts at once and runs on under the iterations of ALL the levels above it); the coarsest, then the levels between, on the other
-      hipStream_t side2 = c->side_stream2;
-      FR_CK(c, fr, hipStreamWaitEvent(side2, c->side_ev[0], 0));
-      { ScopedTimer t(c, KC_NORMALIZATION, 0.0, fr.ln, true, side2); launch_normalization(side2, tab, NF, count, p.maxTestLevel, p.maxTestLevel + 1, with_nrm, c->nrm_dpp_asm); }
-      FR_CK(c, fr, hipEventRecord(c->side_ev[3], side2));
-      c->nrm_pending_finest = c->side_ev[3];
-      { ScopedTimer t(c, KC_NORMALIZATION, 0.0, fr.ln, true, side); launch_normalization(side, tab, NF, count, c->L - 1, c->L, with_nrm, c->nrm_dpp_asm); }
-      FR_CK(c, fr, hipEventRecord(c->side_ev[1], side));
-      if(c->L - 1 > p.maxTestLevel + 1) {
-        { ScopedTimer t(c, KC_NORMALIZATION, 0.0, fr.ln, true, side); launch_normalization(side, tab, NF, count, p.maxTestLevel + 1, c->L - 1, with_nrm, c->nrm_dpp_asm); }
-        FR_CK(c, fr, hipEventRecord(c->side_ev[2], side));
-        c->nrm_pending = c->side_ev[2];
-      }
-    } else if(defer) {
-      // (sparse templates: two launches on one stream — the third launch, the second stream and their events cost a single pair 1 % of its step)
-      { ScopedTimer t(c, KC_NORMALIZATION, 0.0, fr.ln, true, side); launch_normalization(side, tab, NF, count, c->L - 1, c->L, with_nrm, c->nrm_dpp_asm); }
-      FR_CK(c, fr, hipEventRecord(c->side_ev[1], side));
-      { ScopedTimer t(c, KC_NORMALIZATION, 0.0, fr.ln, true, side); launch_normalization(side, tab, NF, count, p.maxTestLevel, c->L - 1, with_nrm, c->nrm_dpp_asm); }
-      FR_CK(c, fr, hipEventRecord(c->side_ev[2], side));
-      c->nrm_pending = c->side_ev[2];
-    } else {
-      { ScopedTimer t(c, KC_NORMALIZATION, 0.0, fr.ln, true, side); launch_normalization(side, tab, NF, count, p.maxTestLevel, c->L, with_nrm, c->nrm_dpp_asm); }
-      FR_CK(c, fr, hipEventRecord(c->side_ev[1], side));
-    }
-  }
+  if(!nrm.behind_readback)
+    if(int rcn = run_normalization()) return rcn;
   // one read-back of the point counts: the host needs them to size the template-build and GN grids.  Queued AHEAD of an in-line normalisation
   // and waited for through an event of its own: the host's round trip (~30 us) then runs under the normalisation's sequential sums
   // instead of behind them.
@@ -350,14 +296,11 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
   if(counts_ev) FR_CK(c, fr, hipEventRecord(counts_ev, s));
   if(fr.selected_ev) FR_CK(c, fr, hipEventRecord(fr.selected_ev, s));
   if(fr.on_selected) fr.on_selected();
-  if(!side) {
-    // the sequential (reference-order) normalisation sums of all levels and frames run side by side in one launch
-    ScopedTimer t(c, KC_NORMALIZATION, 0.0, fr.ln);
-    launch_normalization(s, tab, NF, count, p.maxTestLevel, c->L, with_nrm, c->nrm_dpp_asm);
-  }
+  if(nrm.behind_readback)
+    if(int rcn = run_normalization()) return rcn;
   if(counts_ev) FR_CK(c, fr, hipEventSynchronize(counts_ev));
   else FR_CK(c, fr, hipStreamSynchronize(s));
-  std::vector<int> max_n(c->L, 0);
+  int max_n[kMaxLevels] = {};
   double pts = 0;
   for(int i = 0; i < count; ++i) {
     FrameSlot& f = c->frames[slots[i]];
@@ -372,18 +315,12 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
     c->kc_units[KC_TEMPLATE] += pts;
     c->kc_units[KC_NORMALIZATION] += pts;
   }
-  if(count <= c->merge_levels_max_frames && c->L - p.maxTestLevel > 1) {
+  for(const LevelSpan& sp : level_spans(c->L, p.maxTestLevel, merge_template_levels(count, c->merge_levels_max_frames, tested))) {
     ScopedTimer t(c, KC_TEMPLATE, 0.0, fr.ln);
-    int most = 0;
-    for(int l = p.maxTestLevel; l < c->L; ++l) most = std::max(most, max_n[l]);
-    launch_template_build(s, tab + (size_t) p.maxTestLevel * NF, c->C, most, count, p.gradientEstimation == BPVO_GRAD_CD5, c->gauss_k, c->L - p.maxTestLevel, NF);
-  } else {
-    for(int l = c->L - 1; l >= p.maxTestLevel; --l) {
-      ScopedTimer t(c, KC_TEMPLATE, 0.0, fr.ln);
-      launch_template_build(s, tab + (size_t) l * NF, c->C, max_n[l], count, p.gradientEstimation == BPVO_GRAD_CD5, c->gauss_k);
-    }
+    const int most = *std::max_element(max_n + sp.first, max_n + sp.first + sp.count);
+    launch_template_build(s, frame_launch(c, tab, geom, sp, count), c->C, most, p.gradientEstimation == BPVO_GRAD_CD5, c->gauss_k);
   }
-  if(side) FR_CK(c, fr, hipStreamWaitEvent(s, c->side_ev[1], 0));      // the normalisation joins here: whatever follows on this stream sees it
+  if(nrm.join_event >= 0) FR_CK(c, fr, hipStreamWaitEvent(s, c->side_ev[nrm.join_event], 0));      // the normalisation joins here: whatever follows on this stream sees it
   if(!fr.own_thread && !fr.no_final_sync) {      // (a lane thread goes straight on to its estimation on the same stream)
     FR_CK(c, fr, hipStreamSynchronize(s));
     FR_CK(c, fr, hipGetLastError());
@@ -391,11 +328,6 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
   }
   for(int i = 0; i < count; ++i) c->frames[slots[i]].has_template = true;
   return BPVO_OK;
-}
-int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr)
-{
-  const std::vector<int> slots = strided_slots(first, stride, count);
-  return frames_set_template_slots(c, slots.data(), count, fr);
 }
 int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count)
 {
@@ -405,7 +337,7 @@ int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count)
     if(!c->frames[first + i * stride].has_data) return fail(c, BPVO_ERR_NO_DATA, "no data in frame");   // vo_frame.cc:63
     if(!c->frames[first + i * stride].has_disp) return fail(c, BPVO_ERR_NO_DATA, "no disparity in frame (the current frame of a pair batch)");
   }
-  return frames_set_template(c, first, stride, count, ctx_run(c));
+  return frames_set_template_slots(c, strided_slots(first, stride, count).data(), count, ctx_run(c));
 }
 
 // The full records of a slot's lazy levels, from the image the slot still holds: the descriptor kernel again, for this frame alone,
@@ -423,10 +355,10 @@ int ensure_dense_descriptor(bpvo_hip_ctx* c, int slot)
   auto restore = [&]() { for(int l = 0; l < c->L; ++l) f.lazy[l] = was[l]; };
   const FrameRun fr = ctx_run(c);
   const FrameJob* tab = nullptr;
-  const int rc = upload_frame_jobs(c, slot, 1, 1, fr, 0, &tab);
+  const int rc = upload_frame_jobs(c, &slot, 1, fr, 0, &tab);
   if(rc) { restore(); return rc; }
-  for(int l = c->L - 1; l >= c->params.maxTestLevel; --l)
-    launch_bitplanes(c->stream, tab + (size_t) l * c->n_frames, c->geom[l].cols, c->geom[l].rows, 1, c->params.sigmaBitPlanes, c->gauss_k, 1);
+  for(const LevelSpan& sp : level_spans(c->L, c->params.maxTestLevel, false))      // (lazy levels: DF_BITPLANES_FUSED only, frames_set_data_slots)
+    launch_bitplanes(c->stream, frame_launch(c, tab, c->geom, sp, 1), c->params.sigmaBitPlanes, c->gauss_k, 1);
   if(hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
     restore();
     return fail(c, BPVO_ERR_DEVICE, "ensure_dense_descriptor: descriptor kernels failed");
@@ -447,10 +379,9 @@ int ensure_saliency(bpvo_hip_ctx* c, int slot, int level)
   f.sal_state[level] = FrameSlot::SAL_STORED;      // (the job table is built from the state: the job carries the map's address)
   const FrameRun fr = ctx_run(c);
   const FrameJob* tab = nullptr;
-  int rc = upload_frame_jobs(c, slot, 1, 1, fr, 1, &tab);
+  int rc = upload_frame_jobs(c, &slot, 1, fr, 1, &tab);
   if(rc == BPVO_OK) {
-    const LevelGeom& g = slot_geom(c, f, level);
-    launch_saliency(c->stream, tab + (size_t) level * c->n_frames, c->C, g.cols, g.rows, 1);
+    launch_saliency(c->stream, frame_launch(c, tab, &slot_geom(c, f, 0), LevelSpan{level, 1}, 1), c->C);
     if(hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, BPVO_ERR_DEVICE, "ensure_saliency: saliency kernel failed");
   }
   if(rc) f.sal_state[level] = FrameSlot::SAL_ON_DEMAND;
@@ -521,26 +452,6 @@ int bpvo_hip_get_selection_info(bpvo_hip_ctx* c, int slot, int level, int* n_can
   return BPVO_OK;
 }
 
-int bpvo_hip_frame_set_data(bpvo_hip_ctx* c, int slot, const uint8_t* image, const float* disparity)
-{
-  CHECK_CTX(c); CHECK_SLOT(c, slot);
-  (void) hipSetDevice(c->device);
-  int rc = frames_set_data(c, slot, 1, 1, image, disparity, false);
-  if(rc) return rc;
-  HIP_CK(c, hipStreamSynchronize(c->stream));   // the caller may reuse its buffers on return (vo_frame.cc:50-51)
-  resolve_events(c);
-  return BPVO_OK;
-}
-int bpvo_hip_frame_set_data_device(bpvo_hip_ctx* c, int slot, const uint8_t* d_image, const float* d_disparity)
-{
-  CHECK_CTX(c); CHECK_SLOT(c, slot);
-  (void) hipSetDevice(c->device);
-  int rc = frames_set_data(c, slot, 1, 1, d_image, d_disparity, true);
-  if(rc) return rc;
-  HIP_CK(c, hipStreamSynchronize(c->stream));
-  resolve_events(c);
-  return BPVO_OK;
-}
 int bpvo_hip_frames_set_data(bpvo_hip_ctx* c, int first_slot, int slot_stride, int count, const uint8_t* images,
                              const float* disparities, int on_device)
 {
@@ -548,9 +459,19 @@ int bpvo_hip_frames_set_data(bpvo_hip_ctx* c, int first_slot, int slot_stride, i
   (void) hipSetDevice(c->device);
   int rc = frames_set_data(c, first_slot, slot_stride, count, images, disparities, on_device != 0);
   if(rc) return rc;
-  HIP_CK(c, hipStreamSynchronize(c->stream));
+  HIP_CK(c, hipStreamSynchronize(c->stream));   // the caller may reuse its buffers on return (vo_frame.cc:50-51)
   resolve_events(c);
   return BPVO_OK;
+}
+int bpvo_hip_frame_set_data(bpvo_hip_ctx* c, int slot, const uint8_t* image, const float* disparity)
+{
+  CHECK_CTX(c); CHECK_SLOT(c, slot);
+  return bpvo_hip_frames_set_data(c, slot, 1, 1, image, disparity, 0);
+}
+int bpvo_hip_frame_set_data_device(bpvo_hip_ctx* c, int slot, const uint8_t* d_image, const float* d_disparity)
+{
+  CHECK_CTX(c); CHECK_SLOT(c, slot);
+  return bpvo_hip_frames_set_data(c, slot, 1, 1, d_image, d_disparity, 1);
 }
 int bpvo_hip_frame_set_template(bpvo_hip_ctx* c, int slot)
 {

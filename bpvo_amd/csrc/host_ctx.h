@@ -4,7 +4,7 @@
 //   vo.hip        the addFrame drivers (one frame, many sequences), point cloud,          measure.hip   profiling, counters, diagnostics
 //                 stereo front-end                                                       vo_state.h    addFrame's state machine (host only, no HIP)
 //                                                                                        gn_rounds.h   the chain's pipelined rounds (host only, no HIP)
-//   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)
+//   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)      frame_plan.h  the frame stage's decisions (host only, no HIP)
 // The host keeps bpvo's object model (frames with a descriptor pyramid and a template pyramid, a pose estimator with per-level
 // Gauss-Newton runs, the VisualOdometry keyframe state machine) but every O(pixels) / O(points) array lives in HBM; per GN iteration the
 // host sees one 4-byte "pairs still active" counter.  See DESIGN.md.
@@ -26,6 +26,7 @@
 #include <thread>
 #include <vector>
 
+#include "frame_plan.h"
 #include "gn_rounds.h"
 #include "kernels.h"
 #include "latch_table.h"
@@ -465,7 +466,6 @@ struct ScopedTimer {
 };
 
 // ---- frame stages ---------------------------------------------------------------------------------------------------
-// slots: first, first+stride, ...; uploads the FrameJob table [L][count] and returns its device base
 // A frame stage runs either on the ctx stream (single frames, batches on one lane) or, for staggered batches, on a lane's own stream
 // with its own rows [tab, tab + count) of the job tables and count staging (FrameRun); errors of a lane go to the lane's string.
 struct FrameRun {
@@ -519,21 +519,24 @@ PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l);      //
 void pair_job_set_params(PairJob& j, const bpvo_hip_params& p);              // ... and a sequence's own in their place
 void resolve_events(bpvo_hip_ctx* c);
 FrameRun ctx_run(bpvo_hip_ctx* c);
-int upload_frame_jobs(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr, int which, const FrameJob** tab);
-// the frame stages over any list of slots (the strided forms above and below build the list first, slots[i] = first + i * stride)
+// the frame stages over any list of slots (strided_slots: slots[i] = first + i * stride)
 std::vector<int> strided_slots(int first, int stride, int count);
-int upload_frame_jobs_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr, int which, const FrameJob** tab);
+int upload_frame_jobs(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr, int which, const FrameJob** tab);
+// the launch of a stage's kernels over the levels of `span` (frame_plan.h) of `count` frames, from the stage's table and level sizes: the jobs and
+// the size of the span's FINEST level, which the grid of a launch over several levels is made for
+inline bpvo_hip::FrameLaunch frame_launch(const bpvo_hip_ctx* c, const FrameJob* tab, const LevelGeom* geom, LevelSpan span, int count)
+{
+  return bpvo_hip::FrameLaunch{tab + (size_t) span.first * c->n_frames, geom[span.first].cols, geom[span.first].rows, count, span.count, c->n_frames};
+}
 // offsets: null, or the pixel offset of each entry's image / disparity in `images` / `disps` (otherwise entry i is at i x its level-0 pixels).  Every
 // slot of one stage has the same sizes (slot_geom); mixed sizes run a stage per size
 int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const uint8_t* images, const float* disps, bool on_device, const FrameRun& fr,
                           int skip_odd_disp = 0, const size_t* offsets = nullptr);
 int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, const FrameRun& fr);
-int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uint8_t* images, const float* disps, bool on_device, const FrameRun& fr,
-                    int skip_odd_disp = 0);
+// ... and over first, first + stride, ... on the context's stream, with the checks of the C entry points (slot range, null buffers, data and disparity in a frame made a template)
 int frames_set_data(bpvo_hip_ctx* c, int first, int stride, int count, const uint8_t* images, const float* disps, bool on_device, int skip_odd_disp = 0);
-int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count, const FrameRun& fr);
-int upload_disparity(bpvo_hip_ctx* c, int slot, const float* disparity);
 int frames_set_template(bpvo_hip_ctx* c, int first, int stride, int count);
+int upload_disparity(bpvo_hip_ctx* c, int slot, const float* disparity);
 bool team_serves(const bpvo_hip_ctx* c, int n);
 PairJob group_pair_job(const bpvo_hip_ctx* c, const PairJob& whole, int k);
 inline int job_tables(const bpvo_hip_ctx* c) { return c->G > 1 ? 1 + c->G : 1; }      // job tables of a lane: the whole jobs, then one table per channel group

@@ -61,7 +61,10 @@ void launch_ingest_at(hipStream_t s, const FrameJob* jobs_level0, const uint8_t*
 void launch_pyrdown(hipStream_t s, const FrameJob* src, const FrameJob* dst, int dW, int dR, int nframes);
 // few frames: `steps` (1..3) pyrDown steps in one launch — src_row is the source level's row of the table [level][job_pitch], dW x dR the COARSEST level of the group
 void launch_pyramid_levels(hipStream_t s, const FrameJob* src_row, int job_pitch, int steps, int dW, int dR, int nframes);
-void launch_intensity(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int nlevels = 1, int job_pitch = 0);
+// A frame-stage launch over `nlevels` consecutive levels of `nframes` frames each (kernels_frame.hip level_job): `jobs` is the FINEST of these
+// levels' row of the table [level][job_pitch] and W x R that level's size — the grid is sized for it.  Built in one place: host_ctx.h frame_launch
+struct FrameLaunch { const FrameJob* jobs; int W, R, nframes, nlevels, job_pitch; };
+void launch_intensity(hipStream_t s, const FrameLaunch& f);
 void launch_gradient_descriptor(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, const GaussTaps& pre);   // (I, Ix, Iy), C = 3
 void launch_descriptor_fields(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int second_order, const GaussTaps& g1,
                               const GaussTaps& g2);   // C = 5 / 10
@@ -70,33 +73,30 @@ void launch_central_difference(hipStream_t s, const FrameJob* jobs, int W, int R
 void launch_latch(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int bytes, int half_ssd, const signed char* d_offsets, int kc, int ks,
                   const GaussTaps& after);   // C = 8 * bytes, bytes = 1 / 2 / 4
 void launch_laplacian(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int ksize /*1 or 3*/);
-void launch_census(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, const int* blur_taps /*null: no smoothing*/, int nlevels = 1, int job_pitch = 0);
+void launch_census(hipStream_t s, const FrameLaunch& f, const int* blur_taps /*null: no smoothing, one level*/);
 // one level of a pair batch (jobs A, B, A, B, ...) with census-only template frames: B over every tile, A over the dense tile columns only
-void launch_bitplanes_pairs(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, const float k[3]);
+void launch_bitplanes_pairs(hipStream_t s, const FrameLaunch& f, const float k[3]);
 // the census bytes of the census-only levels (FrameJob::lazy == 2) among jobs 0, 2, 4, ... — the template frames of a pair batch; other jobs are left alone
-void launch_census_templates(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int nlevels = 1, int job_pitch = 0);
-// from_image: the census transform is computed inside the bit-planes kernel (no launch_census, sigma_bp > 0 and sigma_ct <= 0)
-// nlevels > 1 (bit-planes, tiled selection, template build): `jobs` is the FINEST level's row of the table [level][job_pitch], W / R / max_points that level's — the
-// levels in one launch (kernels_frame.hip level_job)
-void launch_bitplanes(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, float sigma, const float k[3], int from_image, int nlevels = 1,
-                      int job_pitch = 0);
+void launch_census_templates(hipStream_t s, const FrameLaunch& f);
+// from_image: the census transform is computed inside the bit-planes kernel (no launch_census, sigma_bp > 0 and sigma_ct <= 0); sigma <= 0: one level
+void launch_bitplanes(hipStream_t s, const FrameLaunch& f, float sigma, const float k[3], int from_image);
 // (minSaliency and the disparity gate: each frame's own, FrameJob::min_saliency / min_disp / max_disp)
 // gauss_k: the bit-planes blur taps (census-only levels, FrameJob::lazy == 2: the tiles form channel 0 themselves)
 // part: everything, or — a stage with a point budget, which launch_point_budget serves in between — the candidates alone, then the scan and the compaction
 enum { SELECT_ALL = 0, SELECT_CANDIDATES = 1, SELECT_COMPACT = 2 };
-void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, const float gauss_k[3], int nlevels = 1,
-                            int job_pitch = 0, int part = SELECT_ALL);
+// nms_radius > 1 (flag bytes): one level
+void launch_saliency_select(hipStream_t s, const FrameLaunch& f, int C, int nms_radius, int border, const float gauss_k[3], int part);
 // of the candidates of every job with FrameJob::max_points > 0 the max_points most salient stay (kernels_frame.hip point_budget_kernel)
-void launch_point_budget(hipStream_t s, const FrameJob* jobs, int nframes, int nms_radius, int nlevels = 1, int job_pitch = 0);
-void launch_saliency(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes);      // the saliency map alone, from dense records
+void launch_point_budget(hipStream_t s, const FrameLaunch& f, int nms_radius);
+void launch_saliency(hipStream_t s, const FrameLaunch& f, int C);      // the saliency map alone, from dense records (one level)
 void launch_copy_rows(hipStream_t s, void* dst, const void* src_host_pinned, size_t pitch_bytes, size_t width_bytes, int rows);   // multiples of 8 bytes
 void launch_gather_counts(hipStream_t s, const FrameJob* jobs /*[L][job_pitch]*/, int job_pitch, int nframes, int first_level, int num_levels,
                           int* out /*[nframes][kMaxLevels]*/);
 void launch_normalization(hipStream_t s, const FrameJob* jobs /*[L][job_pitch]*/, int job_pitch, int nframes, int first_level,
                           int num_levels, int with_normalization, int form = 1);   // form of the sequential sums (same sums): 1 hand-scheduled DPP add chains, 0 the compiler's DPP form, 2 broadcast LDS reads + plain adds
 void launch_export_jacobians(hipStream_t s, const FrameJob* job /*device, one job*/, int C, int n, float* out /*[C*n][6]*/);
-void launch_template_build(hipStream_t s, const FrameJob* jobs, int C, int max_points, int nframes, int grad_cd5, const float gauss_k[3], int nlevels = 1,
-                           int job_pitch = 0);   // gauss_k: the bit-planes blur taps (lazy levels)
+// max_points: the most points of a job of the launch; gauss_k: the bit-planes blur taps (lazy levels)
+void launch_template_build(hipStream_t s, const FrameLaunch& f, int C, int max_points, int grad_cd5, const float gauss_k[3]);
 
 // stereo front-end (kernels_stereo.hip): OpenCV 2.4 block matching with the reference's parameters, batched over frames
 // A frame of a call whose frames differ in size: its size and where its pixels start in the packed images and maps (device table, a row per frame)

@@ -2036,91 +2036,89 @@ void launch_pyrdown(hipStream_t s, const FrameJob* src, const FrameJob* dst, int
 {
   hipLaunchKernelGGL(pyrdown_u8_lds_kernel, dim3((dW + PDT_W - 1) / PDT_W, (dR + PDT_H * PD_STACK - 1) / (PDT_H * PD_STACK), nframes), dim3(256), 0, s, src, dst);
 }
-void launch_intensity(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int nlevels, int job_pitch)
+void launch_intensity(hipStream_t s, const FrameLaunch& f)
 {
-  hipLaunchKernelGGL(intensity_kernel, dim3((W * R + 1023) / 1024, 1, nframes * nlevels), dim3(256), 0, s, jobs, nframes, job_pitch);
+  hipLaunchKernelGGL(intensity_kernel, dim3((f.W * f.R + 1023) / 1024, 1, f.nframes * f.nlevels), dim3(256), 0, s, f.jobs, f.nframes, f.job_pitch);
 }
 // (nlevels > 1: the smoothed-census form only)
-void launch_census(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, const int* blur_taps, int nlevels, int job_pitch)
+void launch_census(hipStream_t s, const FrameLaunch& f, const int* blur_taps)
 {
   if(blur_taps)
-    hipLaunchKernelGGL(census_blur_kernel, dim3((W + CB_TW - 1) / CB_TW, (R + CB_TH - 1) / CB_TH, nframes * nlevels), dim3(256), 0, s,
-                       jobs, blur_taps[0], blur_taps[1], nframes, job_pitch);
+    hipLaunchKernelGGL(census_blur_kernel, dim3((f.W + CB_TW - 1) / CB_TW, (f.R + CB_TH - 1) / CB_TH, f.nframes * f.nlevels), dim3(256), 0, s,
+                       f.jobs, blur_taps[0], blur_taps[1], f.nframes, f.job_pitch);
   else
-    hipLaunchKernelGGL(census_kernel, dim3((W + 63) / 64, (R + 4 * CENSUS_ROWS - 1) / (4 * CENSUS_ROWS), nframes), dim3(256), 0, s, jobs);
+    hipLaunchKernelGGL(census_kernel, dim3((f.W + 63) / 64, (f.R + 4 * CENSUS_ROWS - 1) / (4 * CENSUS_ROWS), f.nframes), dim3(256), 0, s, f.jobs);
 }
 // the census bytes of the census-only levels of a pair batch's template frames: jobs 0, 2, 4, ... of `nframes` (A, B, A, B, ...)
-void launch_census_templates(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int nlevels, int job_pitch)
+void launch_census_templates(hipStream_t s, const FrameLaunch& f)
 {
-  const int na = (nframes + 1) / 2;
-  hipLaunchKernelGGL(census_templates_kernel, dim3((W + 64 * CT_PX - 1) / (64 * CT_PX), (R + 4 * CT_ROWS - 1) / (4 * CT_ROWS), na * nlevels), dim3(256), 0, s, jobs, na,
-                     job_pitch);
+  const int na = (f.nframes + 1) / 2;
+  hipLaunchKernelGGL(census_templates_kernel, dim3((f.W + 64 * CT_PX - 1) / (64 * CT_PX), (f.R + 4 * CT_ROWS - 1) / (4 * CT_ROWS), na * f.nlevels), dim3(256), 0, s,
+                     f.jobs, na, f.job_pitch);
 }
-void launch_bitplanes(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, float sigma, const float k[3], int from_image, int nlevels,
-                      int job_pitch)
+void launch_bitplanes(hipStream_t s, const FrameLaunch& f, float sigma, const float k[3], int from_image)
 {
   // tiles a workgroup walks: few frames do not fill the chip with stacks of four (1241x376 x 2 frames: 480 workgroups of 32 rows)
-  const int stack = nframes >= 16 ? 8 : (nframes > 4 ? 4 : 1);
-  const dim3 grid((W + BP_TW - 1) / BP_TW, (R + BP_TH * stack - 1) / (BP_TH * stack), nframes * nlevels);
+  const int stack = f.nframes >= 16 ? 8 : (f.nframes > 4 ? 4 : 1);
+  const dim3 grid((f.W + BP_TW - 1) / BP_TW, (f.R + BP_TH * stack - 1) / (BP_TH * stack), f.nframes * f.nlevels);
   if(sigma > 0.0f && from_image)
-    hipLaunchKernelGGL(bitplanes_blur_kernel<true>, grid, dim3(256), 0, s, jobs, k[0], k[1], k[2], stack, nframes, job_pitch, 1, 0);
+    hipLaunchKernelGGL(bitplanes_blur_kernel<true>, grid, dim3(256), 0, s, f.jobs, k[0], k[1], k[2], stack, f.nframes, f.job_pitch, 1, 0);
   else if(sigma > 0.0f)
-    hipLaunchKernelGGL(bitplanes_blur_kernel<false>, grid, dim3(256), 0, s, jobs, k[0], k[1], k[2], stack, nframes, job_pitch, 1, 0);
+    hipLaunchKernelGGL(bitplanes_blur_kernel<false>, grid, dim3(256), 0, s, f.jobs, k[0], k[1], k[2], stack, f.nframes, f.job_pitch, 1, 0);
   else
-    hipLaunchKernelGGL(bitplanes_noblur_kernel, dim3((W * R + 255) / 256, 1, nframes), dim3(256), 0, s, jobs);
+    hipLaunchKernelGGL(bitplanes_noblur_kernel, dim3((f.W * f.R + 255) / 256, 1, f.nframes), dim3(256), 0, s, f.jobs);
 }
 // the saliency map alone, from dense records (and the channel-0 plane where the job has one)
 // One level of a pair batch (jobs A, B, A, B, ...) whose template frames are census-only there (FrameJob::lazy == 2; census fused, sigma > 0):
 // the current frames in one launch over every tile, the template frames in one over the tile columns that stay dense — no workgroup is
 // started for a lazy tile (144 k of them per 1024-pair step, each waiting for its 32 KB of LDS only to leave).
-void launch_bitplanes_pairs(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, const float k[3])
+void launch_bitplanes_pairs(hipStream_t s, const FrameLaunch& f, const float k[3])
 {
-  const int stack = nframes >= 16 ? 8 : (nframes > 4 ? 4 : 1);      // (as launch_bitplanes: by the frames of the stage)
-  const int ncols = (W + BP_TW - 1) / BP_TW, nrows = (R + BP_TH * stack - 1) / (BP_TH * stack);
+  const int stack = f.nframes >= 16 ? 8 : (f.nframes > 4 ? 4 : 1);      // (as launch_bitplanes: by the frames of the stage)
+  const int ncols = (f.W + BP_TW - 1) / BP_TW, nrows = (f.R + BP_TH * stack - 1) / (BP_TH * stack);
   int dense = 0;
-  for(int cx = 0; cx < ncols; ++cx) dense += bp_tile_column_is_lazy(cx * BP_TW, W) ? 0 : 1;
-  const int na = (nframes + 1) / 2, nb = nframes / 2;
-  if(nb > 0) hipLaunchKernelGGL(bitplanes_blur_kernel<true>, dim3(ncols, nrows, nb), dim3(256), 0, s, jobs + 1, k[0], k[1], k[2], stack, nb, 0, 2, 0);
-  if(dense > 0) hipLaunchKernelGGL(bitplanes_blur_kernel<true>, dim3(dense, nrows, na), dim3(256), 0, s, jobs, k[0], k[1], k[2], stack, na, 0, 2, 1);
+  for(int cx = 0; cx < ncols; ++cx) dense += bp_tile_column_is_lazy(cx * BP_TW, f.W) ? 0 : 1;
+  const int na = (f.nframes + 1) / 2, nb = f.nframes / 2;
+  if(nb > 0) hipLaunchKernelGGL(bitplanes_blur_kernel<true>, dim3(ncols, nrows, nb), dim3(256), 0, s, f.jobs + 1, k[0], k[1], k[2], stack, nb, 0, 2, 0);
+  if(dense > 0) hipLaunchKernelGGL(bitplanes_blur_kernel<true>, dim3(dense, nrows, na), dim3(256), 0, s, f.jobs, k[0], k[1], k[2], stack, na, 0, 2, 1);
 }
-void launch_saliency(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes)
+void launch_saliency(hipStream_t s, const FrameLaunch& f, int C)
 {
-  auto plain = [&](auto c) { hipLaunchKernelGGL(saliency_kernel<decltype(c)::value>, grid2d_rows(W, R, nframes), dim3(256), 0, s, jobs); };
+  auto plain = [&](auto c) { hipLaunchKernelGGL(saliency_kernel<decltype(c)::value>, grid2d_rows(f.W, f.R, f.nframes), dim3(256), 0, s, f.jobs); };
   if(C <= 48 || !dispatch_wide_channels(C, plain)) dispatch_channels(C, plain);
 }
-void launch_saliency_select(hipStream_t s, const FrameJob* jobs, int C, int W, int R, int nframes, int nms_radius, int border, const float gauss_k[3], int nlevels,
-                            int job_pitch, int part)
+void launch_saliency_select(hipStream_t s, const FrameLaunch& f, int C, int nms_radius, int border, const float gauss_k[3], int part)
 {
   const bool form = part != SELECT_COMPACT, compact = part != SELECT_CANDIDATES;
   if(nms_radius <= 1) {
     // tiles: saliency + NMS + gate in one pass, candidate bits, word scan, lane-per-pixel compaction
-    const int WPR = (W + 63) / 64, nw = R * WPR;
+    const int WPR = (f.W + 63) / 64, nw = f.R * WPR;
     auto tile = [&](auto c) {
-      hipLaunchKernelGGL(saliency_select_tile_kernel<decltype(c)::value>, dim3(WPR, (R + ST_H - 1) / ST_H, nframes * nlevels), dim3(256), 0, s, jobs,
-                         border, nframes, job_pitch, gauss_k[0], gauss_k[1], gauss_k[2]);
+      hipLaunchKernelGGL(saliency_select_tile_kernel<decltype(c)::value>, dim3(WPR, (f.R + ST_H - 1) / ST_H, f.nframes * f.nlevels), dim3(256), 0, s, f.jobs,
+                         border, f.nframes, f.job_pitch, gauss_k[0], gauss_k[1], gauss_k[2]);
     };
     if(form && (C <= 48 || !dispatch_wide_channels(C, tile))) dispatch_channels(C, tile);
     if(!compact) return;
-    hipLaunchKernelGGL(select_words_scan_kernel, dim3(nframes * nlevels), dim3(1024), 0, s, jobs, nframes, job_pitch);
-    hipLaunchKernelGGL(select_words_write_kernel, dim3((nw + 4 * SW_WORDS - 1) / (4 * SW_WORDS), 1, nframes * nlevels), dim3(256), 0, s, jobs, nframes,
-                       job_pitch);
+    hipLaunchKernelGGL(select_words_scan_kernel, dim3(f.nframes * f.nlevels), dim3(1024), 0, s, f.jobs, f.nframes, f.job_pitch);
+    hipLaunchKernelGGL(select_words_write_kernel, dim3((nw + 4 * SW_WORDS - 1) / (4 * SW_WORDS), 1, f.nframes * f.nlevels), dim3(256), 0, s, f.jobs, f.nframes,
+                       f.job_pitch);
     return;
   }
   // larger NMS windows: the saliency map first, then flag bytes / chunk scan / compaction straight from it
-  const int nblk = (W * R + SEL_BLOCK_PX - 1) / SEL_BLOCK_PX;
+  const int nblk = (f.W * f.R + SEL_BLOCK_PX - 1) / SEL_BLOCK_PX;
   if(form) {
-    launch_saliency(s, jobs, C, W, R, nframes);
-    hipLaunchKernelGGL(select_flag_kernel, dim3(nblk, 1, nframes), dim3(256), 0, s, jobs, border);
+    launch_saliency(s, f, C);
+    hipLaunchKernelGGL(select_flag_kernel, dim3(nblk, 1, f.nframes), dim3(256), 0, s, f.jobs, border);
   }
   if(!compact) return;
-  hipLaunchKernelGGL(select_scan_kernel, dim3(nframes), dim3(1024), 0, s, jobs);
-  hipLaunchKernelGGL(select_write_kernel, dim3(nblk, 1, nframes), dim3(256), 0, s, jobs);
+  hipLaunchKernelGGL(select_scan_kernel, dim3(f.nframes), dim3(1024), 0, s, f.jobs);
+  hipLaunchKernelGGL(select_write_kernel, dim3(nblk, 1, f.nframes), dim3(256), 0, s, f.jobs);
 }
 // the point budget between the two parts of launch_saliency_select (SELECT_CANDIDATES, SELECT_COMPACT), with the jobs and the grid of its scan
-void launch_point_budget(hipStream_t s, const FrameJob* jobs, int nframes, int nms_radius, int nlevels, int job_pitch)
+void launch_point_budget(hipStream_t s, const FrameLaunch& f, int nms_radius)
 {
-  if(nms_radius <= 1) hipLaunchKernelGGL(point_budget_kernel<true>, dim3(nframes * nlevels), dim3(PB_THREADS), 0, s, jobs, nframes, job_pitch);
-  else hipLaunchKernelGGL(point_budget_kernel<false>, dim3(nframes), dim3(PB_THREADS), 0, s, jobs, nframes, 0);
+  if(nms_radius <= 1) hipLaunchKernelGGL(point_budget_kernel<true>, dim3(f.nframes * f.nlevels), dim3(PB_THREADS), 0, s, f.jobs, f.nframes, f.job_pitch);
+  else hipLaunchKernelGGL(point_budget_kernel<false>, dim3(f.nframes), dim3(PB_THREADS), 0, s, f.jobs, f.nframes, 0);
 }
 // Small control tables (job rows, initial poses) copied by a KERNEL that reads the pinned host rows directly: while the upload pipeline
 // keeps the DMA engines busy with 45 MB chunks a hipMemcpyAsync of a few KB on a lane's stream waits its turn behind them
@@ -2157,14 +2155,13 @@ void launch_gather_counts(hipStream_t s, const FrameJob* jobs, int job_pitch, in
   hipLaunchKernelGGL(gather_counts_kernel, dim3((nframes * kMaxLevels + 255) / 256), dim3(256), 0, s, jobs, job_pitch, nframes, first_level,
                      num_levels, out);
 }
-void launch_template_build(hipStream_t s, const FrameJob* jobs, int C, int max_points, int nframes, int grad_cd5, const float gauss_k[3], int nlevels,
-                           int job_pitch)
+void launch_template_build(hipStream_t s, const FrameLaunch& f, int C, int max_points, int grad_cd5, const float gauss_k[3])
 {
   if(max_points <= 0) return;
-  const dim3 g((max_points + 255) / 256, 1, nframes * nlevels);
-  if(C > 48) { hipLaunchKernelGGL(template_build_wide_kernel, g, dim3(256), 0, s, jobs, C, grad_cd5, nframes, job_pitch); return; }
+  const dim3 g((max_points + 255) / 256, 1, f.nframes * f.nlevels);
+  if(C > 48) { hipLaunchKernelGGL(template_build_wide_kernel, g, dim3(256), 0, s, f.jobs, C, grad_cd5, f.nframes, f.job_pitch); return; }
   dispatch_channels(C, [&](auto c) {
-    hipLaunchKernelGGL(template_build_kernel<decltype(c)::value>, g, dim3(256), 0, s, jobs, grad_cd5, gauss_k[0], gauss_k[1], gauss_k[2], nframes, job_pitch);
+    hipLaunchKernelGGL(template_build_kernel<decltype(c)::value>, g, dim3(256), 0, s, f.jobs, grad_cd5, gauss_k[0], gauss_k[1], gauss_k[2], f.nframes, f.job_pitch);
   });
 }
 

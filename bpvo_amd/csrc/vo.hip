@@ -409,7 +409,7 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
   if(q.cur < 0 || q.cur >= c->n_frames) return fail(c, BPVO_ERR_INVALID_ARG, "bad frame slot range");
   FrameRun data_run = ctx_run(c);
   data_run.skip_disparity_upload = !on_device && c->vo_disparity_late && single_pair_is_queued_at_once(c);
-  int rc = frames_set_data(c, q.cur, 1, 1, image, disparity, on_device, data_run, 0);
+  int rc = frames_set_data_slots(c, &q.cur, 1, image, disparity, on_device, data_run);
   if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
   const int data_slot = q.cur;
   bool disparity_pending = data_run.skip_disparity_upload;
@@ -479,7 +479,7 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
       FrameRun fr = ctx_run(c);
       fr.no_final_sync = !c->profiling;
       fr.defer_finest_nrm = true;
-      rc = frames_set_template(c, kf.template_slot, 1, 1, fr);
+      rc = frames_set_template_slots(c, &kf.template_slot, 1, fr);
       M44 T_start2 = m44_identity();      // (the default policy: the Identity)
       if(rc == BPVO_OK) {
         const StartBody sb{&q, 1, &q.ref, &q.cur, nullptr};
