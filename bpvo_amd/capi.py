@@ -216,6 +216,14 @@ class Binding:
     def has(self, name):
         return hasattr(self.lib, self.prefix + name)
 
+    def debug_live_resources(self):
+        """bpvo_hip_debug_live_resources: (device buffers, pinned buffers, streams, events) the library's contexts hold, process-wide."""
+        counts = (C.c_int * 4)()
+        rc = self.fn("debug_live_resources")(counts)
+        if rc != 0:
+            raise BpvoError(f"status {rc}")
+        return tuple(counts)
+
     def default_params(self) -> Params:
         p = Params()
         self.fn("default_params", None)(C.byref(p))

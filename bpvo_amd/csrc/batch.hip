@@ -29,36 +29,28 @@ struct UploadRun {
 int upload_prepare(bpvo_hip_ctx* c, int n_pairs)
 {
   const size_t npix = c->geom[0].npix;
-  // one worker = one pinned block of two slots + the events that free them (the copy stream is shared: up_streams[0]).  A worker's
+  // one worker = one pinned block of two slots + the events that free them (the copy stream is shared: up_stream).  A worker's
   // resources are taken into the context only when all of them exist: a failed pinned allocation leaves the vectors in step
   c->up_slot_bytes = (size_t) kUploadChunkPairs * npix * (2 + 4);
-  if(c->up_streams.empty()) {
-    hipStream_t st = nullptr;
-    HIP_CK(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    c->up_streams.push_back(st);
-  }
+  if(!c->up_stream) HIP_CK(c, c->up_stream.create());
   while((int) c->up_pinned.size() < c->up_workers) {
-    uint8_t* pin = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    hipError_t e = hipHostMalloc((void**) &pin, 2 * c->up_slot_bytes);
-    for(int sl = 0; sl < 2 && e == hipSuccess; ++sl) e = hipEventCreateWithFlags(&ev[sl], hipEventDisableTiming);
+    PinnedBuf<uint8_t> pin;
+    Event ev[2];
+    hipError_t e = pin.alloc(2 * c->up_slot_bytes);
+    for(int sl = 0; sl < 2 && e == hipSuccess; ++sl) e = ev[sl].create(hipEventDisableTiming);
     if(e != hipSuccess) {
-      if(pin) (void) hipHostFree(pin);
-      for(auto x : ev) if(x) (void) hipEventDestroy(x);
       c->err = std::string("upload pipeline: ") + hipGetErrorString(e);
       return BPVO_ERR_DEVICE;
     }
-    c->up_pinned.push_back(pin);
-    c->up_slot_free.push_back(ev[0]);
-    c->up_slot_free.push_back(ev[1]);
+    c->up_pinned.push_back(std::move(pin));
+    c->up_slot_free.push_back(std::move(ev[0]));
+    c->up_slot_free.push_back(std::move(ev[1]));
   }
-  if(n_pairs > c->up_cap_pairs) {
+  if((size_t) n_pairs * npix > c->up_d_disp.size()) {
     HIP_CK(c, hipDeviceSynchronize());
-    (void) hipFree(c->up_d_img); (void) hipFree(c->up_d_disp);
-    c->up_d_img = nullptr; c->up_d_disp = nullptr; c->up_cap_pairs = 0;
-    HIP_CK(c, hipMalloc((void**) &c->up_d_img, (size_t) 2 * n_pairs * npix));
-    HIP_CK(c, hipMalloc((void**) &c->up_d_disp, (size_t) n_pairs * npix * sizeof(float)));
-    c->up_cap_pairs = n_pairs;
+    c->up_d_img.reset(); c->up_d_disp.reset();
+    HIP_CK(c, c->up_d_img.alloc((size_t) 2 * n_pairs * npix));
+    HIP_CK(c, c->up_d_disp.alloc((size_t) n_pairs * npix));
   }
   return BPVO_OK;
 }
@@ -102,9 +94,9 @@ int upload_start(bpvo_hip_ctx* c, UploadRun& u, int n_pairs, const std::vector<s
     for(int p0 = g.first; p0 < g.second; p0 += kUploadChunkPairs) u.chunks.emplace_back(p0, std::min(kUploadChunkPairs, g.second - p0));
   const int nchunks = (int) u.chunks.size();
   while((int) c->up_chunk_done.size() < nchunks) {
-    hipEvent_t e = nullptr;
-    HIP_CK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->up_chunk_done.push_back(e);
+    Event e;
+    HIP_CK(c, e.create(hipEventDisableTiming));
+    c->up_chunk_done.push_back(std::move(e));
   }
   u.recorded.assign(nchunks, 0);
   const size_t npix = c->geom[0].npix;
@@ -115,7 +107,7 @@ int upload_start(bpvo_hip_ctx* c, UploadRun& u, int n_pairs, const std::vector<s
   for(int w = 0; w < T; ++w) {
     u.workers.emplace_back([c, &u, w, T, nchunks, npix, images, disparities, t_start, done_count] {
       (void) hipSetDevice(c->device);
-      hipStream_t st = c->up_streams[0];      // one copy stream for all workers (see bpvo_hip_ctx::up_workers)
+      hipStream_t st = c->up_stream;      // one copy stream for all workers (see bpvo_hip_ctx::up_workers)
       int turn = 0;
       for(int k = w; k < nchunks; k += T, ++turn) {
         const int p0 = u.chunks[k].first, np = u.chunks[k].second, sl = turn & 1;

@@ -91,16 +91,16 @@ void carve_frame_tmpl(bpvo_hip_ctx* c, FrameSlot& f, unsigned char* base, size_t
   if(total) *total = cv.off;
 }
 
-int ensure_template_storage(bpvo_hip_ctx* c, FrameSlot& f)
+hipError_t ensure_template_storage(bpvo_hip_ctx* c, FrameSlot& f, hipStream_t stream)
 {
-  if(f.tmpl_slab) return BPVO_OK;
+  if(f.tmpl_slab) return hipSuccess;
   size_t total = 0;
   FrameSlot tmp;
   carve_frame_tmpl(c, tmp, nullptr, &total);
-  HIP_CK(c, hipMalloc(&f.tmpl_slab, total));
-  HIP_CK(c, hipMemsetAsync(f.tmpl_slab, 0, total, c->stream));
-  carve_frame_tmpl(c, f, (unsigned char*) f.tmpl_slab, nullptr);
-  return BPVO_OK;
+  if(hipError_t e = f.tmpl_slab.alloc(total)) return e;
+  if(hipError_t e = hipMemsetAsync(f.tmpl_slab, 0, total, stream)) return e;
+  carve_frame_tmpl(c, f, f.tmpl_slab, nullptr);
+  return hipSuccess;
 }
 
 FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l)
@@ -170,7 +170,7 @@ PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l)
   j.st = c->d_states + ws;
   j.cnt = c->d_counters + kWsCounters * (size_t) ws;
   j.ticket = c->d_tickets + ws;
-  if(ws == c->trace_ws) { j.trace = c->d_trace; j.trace_cap = c->trace_cap; }
+  if(ws == c->trace_ws) { j.trace = c->d_trace; j.trace_cap = (int) (c->d_trace.size() / kTraceFloats); }
   j.pitch = c->C;
   j.n_groups = c->G;
   j.med_tot = (int) med_totals_at(c);
@@ -206,15 +206,14 @@ PairJob group_pair_job(const bpvo_hip_ctx* c, const PairJob& whole, int k)
 }
 
 // ---- measurement: HIP events on the ctx stream around kernel classes ------------------------------------------------
-hipEvent_t take_event(Lane* ln)
+Event take_event(Lane* ln)
 {
+  Event e;
   if(!ln->ev_pool.empty()) {
-    hipEvent_t e = ln->ev_pool.back();
+    e = std::move(ln->ev_pool.back());
     ln->ev_pool.pop_back();
-    return e;
   }
-  hipEvent_t e;
-  (void) hipEventCreate(&e);
+  else (void) e.create(0);
   return e;
 }
 void resolve_events(bpvo_hip_ctx* c)   // call from the API thread after the lanes' streams are synchronised
@@ -227,8 +226,8 @@ void resolve_events(bpvo_hip_ctx* c)   // call from the API thread after the lan
         c->kc_units[ep.kc] += ep.units;
         c->kc_launches[ep.kc] += 1;
       }
-      ln.ev_pool.push_back(ep.a);
-      ln.ev_pool.push_back(ep.b);
+      ln.ev_pool.push_back(std::move(ep.a));
+      ln.ev_pool.push_back(std::move(ep.b));
     }
     ln.ev_pending.clear();
   }
@@ -253,27 +252,27 @@ int ensure_lanes(bpvo_hip_ctx* c, int n)
     c->lanes.emplace_back();
     Lane& ln = c->lanes.back();
     const bool first = c->lanes.size() == 1;
-    if(first) { ln.stream = c->stream; ln.owns_stream = false; }
-    else { HIP_CK(c, hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking)); ln.owns_stream = true; }
+    if(first) ln.stream = c->stream;
+    else { HIP_CK(c, ln.own_stream.create()); ln.stream = ln.own_stream; }
     // (wide descriptors: the table of the whole jobs, then one table per channel group)
-    HIP_CK(c, hipMalloc((void**) &ln.d_pjobs, sizeof(PairJob) * (size_t) c->L * n_pairs * job_tables(c)));
-    HIP_CK(c, hipMalloc((void**) &ln.d_Tinit, sizeof(float) * 16 * n_pairs));
-    HIP_CK(c, hipMalloc((void**) &ln.d_active, 8 * sizeof(int)));
-    HIP_CK(c, hipMalloc((void**) &ln.d_list, 3 * sizeof(int) * (size_t) n_pairs));
-    for(auto& e : ln.round_ev) HIP_CK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_CK(c, hipEventCreateWithFlags(&ln.selected_ev, hipEventDisableTiming));
-    for(auto& e : ln.staging_ev) HIP_CK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_CK(c, hipHostMalloc((void**) &ln.h_pjobs, sizeof(PairJob) * std::max((size_t) c->L * n_pairs * job_tables(c), (size_t) (1 + kMaxGroups))));
-    HIP_CK(c, hipHostMalloc((void**) &ln.h_T, sizeof(float) * 16 * n_pairs));
-    HIP_CK(c, hipHostMalloc((void**) &ln.h_active, 8 * sizeof(int)));
-    HIP_CK(c, hipMalloc((void**) &ln.d_pk_ctl, sizeof(unsigned) * kPkCtlWords * kMaxLevels));
-    HIP_CK(c, hipHostMalloc((void**) &ln.h_pk_ctl, sizeof(unsigned) * kPkCtlWords * kMaxLevels));
+    HIP_CK(c, ln.d_pjobs.alloc((size_t) c->L * n_pairs * job_tables(c)));
+    HIP_CK(c, ln.d_Tinit.alloc((size_t) 16 * n_pairs));
+    HIP_CK(c, ln.d_active.alloc(8));
+    HIP_CK(c, ln.d_list.alloc(3 * (size_t) n_pairs));
+    for(auto& e : ln.round_ev) HIP_CK(c, e.create(hipEventDisableTiming));
+    HIP_CK(c, ln.selected_ev.create(hipEventDisableTiming));
+    for(auto& e : ln.staging_ev) HIP_CK(c, e.create(hipEventDisableTiming));
+    HIP_CK(c, ln.h_pjobs.alloc(std::max((size_t) c->L * n_pairs * job_tables(c), (size_t) (1 + kMaxGroups))));
+    HIP_CK(c, ln.h_T.alloc((size_t) 16 * n_pairs));
+    HIP_CK(c, ln.h_active.alloc(8));
+    HIP_CK(c, ln.d_pk_ctl.alloc(kPkCtlWords * kMaxLevels));
+    HIP_CK(c, ln.h_pk_ctl.alloc(kPkCtlWords * kMaxLevels));
     if(first) {
-      HIP_CK(c, hipMalloc((void**) &ln.d_team_ctl, sizeof(unsigned) * (size_t) gn_team_ctl_words(kMaxTeams)));
-      HIP_CK(c, hipHostMalloc((void**) &ln.h_team_ctl, sizeof(unsigned) * 64));      // (two launches' first lines: estimate.hip)
+      HIP_CK(c, ln.d_team_ctl.alloc((size_t) gn_team_ctl_words(kMaxTeams)));
+      HIP_CK(c, ln.h_team_ctl.alloc(64));      // (two launches' first lines: estimate.hip)
       std::memset(ln.h_team_ctl, 0, sizeof(unsigned) * 64);
     }
-    HIP_CK(c, hipHostMalloc((void**) &ln.h_states, sizeof(GNState) * (n_pairs + n_pairs)));      // (+ n_pairs: the body states of rig mode, a rig has at least one member)
+    HIP_CK(c, ln.h_states.alloc((size_t) n_pairs + n_pairs));      // (+ n_pairs: the body states of rig mode, a rig has at least one member)
   }
   return BPVO_OK;
 }
@@ -600,27 +599,27 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
     c->cap_max = std::max(c->cap_max, c->geom[l].cap);
   }
 
+  // (a return from here on deletes the context and, with it, whatever it owns so far)
   bpvo_hip_ctx* cp = c.get();
   auto dev_fail = [&](hipError_t e, const char* what) {
     g_create_error = std::string(what) + ": " + hipGetErrorString(e);
-    bpvo_hip_destroy(c.release());   // frees whatever was allocated so far (a failed create must not leak device memory)
     return BPVO_ERR_DEVICE;
   };
 #define CREATE_CK(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) return dev_fail(e_, #expr); } while(0)
   CREATE_CK(hipSetDevice(device));
-  CREATE_CK(hipStreamCreateWithFlags(&cp->stream, hipStreamNonBlocking));
+  CREATE_CK(cp->stream.create());
   cp->frames.resize(n_frames);
   size_t data_total = 0;
   { FrameSlot tmp; carve_frame_data(cp, tmp, nullptr, &data_total); }
   for(auto& f : cp->frames) {
-    CREATE_CK(hipMalloc(&f.data_slab, data_total));
-    carve_frame_data(cp, f, (unsigned char*) f.data_slab, nullptr);
+    CREATE_CK(f.data_slab.alloc(data_total));
+    carve_frame_data(cp, f, f.data_slab, nullptr);
   }
   // sequential-VO contexts (up to 3 slots) get their template storage now: allocated on first use it is a ~10 ms hiccup on
   // the frame that switches keyframes; batch contexts keep it lazy (only every other slot of a pair batch is a template)
   if(n_frames <= 3)
     for(auto& f : cp->frames)
-      if(ensure_template_storage(cp, f) != BPVO_OK) return dev_fail(hipErrorOutOfMemory, "template storage");
+      if(hipError_t e = ensure_template_storage(cp, f, cp->stream)) return dev_fail(e, "template storage");
   cp->ws.resize(n_pairs);
   const size_t nblk_max = (size_t) gn_num_blocks(cp->cap_max);
   // the 4 x 4 tap cache of kCubic / kCubicHermite (512 B per point for eight channels) is an optimisation, not a requirement: a context whose
@@ -635,27 +634,27 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
     }
   }
   for(auto& w : cp->ws) {
-    CREATE_CK(hipMalloc((void**) &w.r, sizeof(float) * (size_t) cp->cap_max * cp->C));
-    CREATE_CK(hipMalloc((void**) &w.valid, (size_t) cp->cap_max));
+    CREATE_CK(w.r.alloc((size_t) cp->cap_max * cp->C));
+    CREATE_CK(w.valid.alloc((size_t) cp->cap_max));
     // (channel groups: a group's candidate segments and bracket counters follow those of the group before it, whole 256-point chunks each)
     // (+ kDenseRuns chunks: the dense form's runs are whole multiples of a chunk; + kDenseRuns lines of totals behind the chunks' counters)
-    CREATE_CK(hipMalloc((void**) &w.cand, sizeof(uint32_t) * (nblk_max + bpvo_hip::kDenseRuns) * kChunkPoints * (size_t) cp->C));
-    CREATE_CK(hipMalloc((void**) &w.med_blk, sizeof(uint32_t) * 4 * (med_totals_at(cp) + 8 * (size_t) bpvo_hip::kDenseRuns)));
+    CREATE_CK(w.cand.alloc((nblk_max + bpvo_hip::kDenseRuns) * kChunkPoints * (size_t) cp->C));
+    CREATE_CK(w.med_blk.alloc(4 * (med_totals_at(cp) + 8 * (size_t) bpvo_hip::kDenseRuns)));
     CREATE_CK(hipMemset(w.med_blk + 4 * med_totals_at(cp), 0, sizeof(uint32_t) * 4 * 8 * bpvo_hip::kDenseRuns));      // (every finish leaves the totals at zero again)
     if(tap_cache) {      // tap cache of warp_residual: the footprint's taps x C floats per point (2 x 2; kCubic / kCubicHermite: 4 x 4), whole tiles
       const bool wide_taps = cp->params.interp == BPVO_INTERP_CUBIC || cp->params.interp == BPVO_INTERP_CUBIC_HERMITE;
       const size_t cap_tiles = ((size_t) cp->cap_max + kTile - 1) / kTile * kTile;
-      CREATE_CK(hipMalloc((void**) &w.tapkey, sizeof(uint32_t) * (size_t) cp->cap_max));
-      CREATE_CK(hipMalloc((void**) &w.tapcache, sizeof(float) * (wide_taps ? 16 : 4) * cp->C * cap_tiles));
+      CREATE_CK(w.tapkey.alloc((size_t) cp->cap_max));
+      CREATE_CK(w.tapcache.alloc((size_t) (wide_taps ? 16 : 4) * cp->C * cap_tiles));
     }
     // two buffers of tile partials (the persistent kernels double-buffer them by iteration parity, kernels_gn.hip pk_partials)
-    CREATE_CK(hipMalloc((void**) &w.partials, sizeof(float) * (size_t) gn_partials_entries(cp->cap_max, cp->G > 1 ? cp->Cg : cp->C) * std::max(1, (cp->G + 1) / 2) * kPartialStride));
+    CREATE_CK(w.partials.alloc((size_t) gn_partials_entries(cp->cap_max, cp->G > 1 ? cp->Cg : cp->C) * std::max(1, (cp->G + 1) / 2) * kPartialStride));
   }
   // (entries n_pairs ..: the body states of rig mode, one per rig of a call — a rig has at least one member —, estimate.hip estimate_rigs)
-  CREATE_CK(hipMalloc((void**) &cp->d_states, sizeof(GNState) * (n_pairs + n_pairs)));
+  CREATE_CK(cp->d_states.alloc((size_t) n_pairs + n_pairs));
   CREATE_CK(hipMemset(cp->d_states, 0, sizeof(GNState) * (n_pairs + n_pairs)));
-  CREATE_CK(hipMalloc((void**) &cp->d_fjobs, 2 * sizeof(FrameJob) * (size_t) cp->L * n_frames));
-  CREATE_CK(hipMalloc((void**) &cp->d_job1, sizeof(PairJob) * (1 + kMaxGroups)));      // the whole job + its channel groups (wide descriptors)
+  CREATE_CK(cp->d_fjobs.alloc(2 * (size_t) cp->L * n_frames));
+  CREATE_CK(cp->d_job1.alloc(1 + kMaxGroups));      // the whole job + its channel groups (wide descriptors)
   if(cp->params.descriptor == BPVO_DESC_LATCH) {
     // The triplet coordinates as CalcuateSums uses them (bpvo/latch_descriptor.cc:170-236): the table's, or — latchRotationInvariance —
     // rotated by the key point's angle and clamped to the patch.  The dense evaluation builds its key points with cv::KeyPoint() (:135-141),
@@ -674,7 +673,7 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
       }
       off[t] = (signed char) x; off[t + 1] = (signed char) y;
     }
-    CREATE_CK(hipMalloc((void**) &cp->d_latch_off, (size_t) n_ints));
+    CREATE_CK(cp->d_latch_off.alloc((size_t) n_ints));
     CREATE_CK(hipMemcpy(cp->d_latch_off, off.data(), (size_t) n_ints, hipMemcpyHostToDevice));
   }
   {
@@ -696,16 +695,16 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
     const int rc = ensure_lanes(cp, std::max(1, std::min(std::min(cp->max_lanes_now, 2), n_pairs / kMinPairsPerLane)));
     if(rc) { g_create_error = cp->err; return rc; }
   }
-  CREATE_CK(hipMalloc((void**) &cp->d_records, sizeof(float) * kRecordFloats * n_pairs));
-  CREATE_CK(hipMalloc((void**) &cp->d_wtmp, sizeof(float) * (size_t) cp->cap_max * cp->C));
-  CREATE_CK(hipMalloc((void**) &cp->d_count, sizeof(unsigned int)));
-  CREATE_CK(hipMalloc((void**) &cp->d_tickets, sizeof(unsigned) * n_pairs));
+  CREATE_CK(cp->d_records.alloc((size_t) kRecordFloats * n_pairs));
+  CREATE_CK(cp->d_wtmp.alloc((size_t) cp->cap_max * cp->C));
+  CREATE_CK(cp->d_count.alloc(1));
+  CREATE_CK(cp->d_tickets.alloc((size_t) n_pairs));
   CREATE_CK(hipMemset(cp->d_tickets, 0, sizeof(unsigned) * n_pairs));
-  CREATE_CK(hipMalloc((void**) &cp->d_counters, kWsCounters * sizeof(unsigned long long) * n_pairs));
+  CREATE_CK(cp->d_counters.alloc((size_t) kWsCounters * n_pairs));
   CREATE_CK(hipMemset(cp->d_counters, 0, kWsCounters * sizeof(unsigned long long) * n_pairs));
-  CREATE_CK(hipHostMalloc((void**) &cp->h_fjobs, 2 * sizeof(FrameJob) * (size_t) cp->L * n_frames));
-  CREATE_CK(hipHostMalloc((void**) &cp->h_ints, sizeof(int) * std::max((size_t) n_frames * kMaxLevels, (size_t) 16)));
-  CREATE_CK(hipMalloc((void**) &cp->d_ints, sizeof(int) * std::max((size_t) n_frames * kMaxLevels, (size_t) 16)));
+  CREATE_CK(cp->h_fjobs.alloc(2 * (size_t) cp->L * n_frames));
+  CREATE_CK(cp->h_ints.alloc(std::max((size_t) n_frames * kMaxLevels, (size_t) 16)));
+  CREATE_CK(cp->d_ints.alloc(std::max((size_t) n_frames * kMaxLevels, (size_t) 16)));
 #undef CREATE_CK
   cp->vo.params = cp->params;
   vo_reset(cp->vo, 0);
@@ -730,45 +729,11 @@ void bpvo_hip_destroy(bpvo_hip_ctx* c)
   if(!c) return;
   if(c->counted_live) g_live_ctx[c->device & 63].fetch_sub(1);
   (void) hipSetDevice(c->device);
+  // everything the context owns goes with the delete below; nothing of it may still be in use then: every stream it owns is drained first
   if(c->stream) (void) hipStreamSynchronize(c->stream);
-  for(auto& f : c->frames) { (void) hipFree(f.data_slab); (void) hipFree(f.tmpl_slab); }
-  for(auto& w : c->ws) { (void) hipFree(w.r); (void) hipFree(w.valid); (void) hipFree(w.cand); (void) hipFree(w.med_blk); (void) hipFree(w.tapkey); (void) hipFree(w.tapcache); (void) hipFree(w.partials); }
-  (void) hipFree(c->d_states); (void) hipFree(c->d_fjobs); (void) hipFree(c->d_job1); (void) hipFree(c->d_latch_off); (void) hipFree(c->d_cloud);
-  (void) hipFree(c->d_records); (void) hipFree(c->d_wtmp); (void) hipFree(c->d_rig_X); (void) hipFree(c->d_rig_stage); (void) hipFree(c->d_rig_active); (void) hipHostFree(c->h_rig_stage); (void) hipHostFree(c->h_rig_active);
-  pose_cov_free(c);
-  pose_score_free(c);
-  (void) hipFree(c->d_count); (void) hipFree(c->d_counters); (void) hipFree(c->d_tickets); (void) hipFree(c->d_trace);
-  (void) hipFree(c->st_left); (void) hipFree(c->st_right); (void) hipFree(c->st_left_pre); (void) hipFree(c->st_right_pre); (void) hipFree(c->st_disp);
-  (void) hipFree(c->st_sgm);
-  (void) hipFree(c->d_st_frames); (void) hipHostFree(c->h_st_frames);
-  if(c->st_tab_ev) (void) hipEventDestroy(c->st_tab_ev);
-  (void) hipFree(c->d_seq_cloud); (void) hipFree(c->d_seq_jobs); (void) hipFree(c->d_cloud_jobs); (void) hipFree(c->d_seq_cnt);
-  (void) hipHostFree(c->h_seq_jobs); (void) hipHostFree(c->h_cloud_jobs); (void) hipHostFree(c->h_seq_cnt);
-  for(auto st : c->up_streams) if(st) { (void) hipStreamSynchronize(st); (void) hipStreamDestroy(st); }
-  for(auto p : c->up_pinned) (void) hipHostFree(p);
-  for(auto e : c->up_slot_free) if(e) (void) hipEventDestroy(e);
-  for(auto e : c->up_chunk_done) if(e) (void) hipEventDestroy(e);
-  (void) hipFree(c->up_d_img); (void) hipFree(c->up_d_disp);
-  (void) hipHostFree(c->h_fjobs); (void) hipHostFree(c->h_ints); (void) hipFree(c->d_ints);
-  for(auto& ln : c->lanes) {
-    if(ln.stream) (void) hipStreamSynchronize(ln.stream);
-    (void) hipFree(ln.d_pjobs); (void) hipFree(ln.d_Tinit); (void) hipFree(ln.d_active); (void) hipFree(ln.d_list);
-    (void) hipHostFree(ln.h_pjobs); (void) hipHostFree(ln.h_T); (void) hipHostFree(ln.h_active); (void) hipHostFree(ln.h_states);
-    (void) hipFree(ln.d_pk_ctl); (void) hipHostFree(ln.h_pk_ctl);
-    (void) hipFree(ln.d_team_ctl); (void) hipHostFree(ln.h_team_ctl);
-    for(auto& ep : ln.ev_pending) { (void) hipEventDestroy(ep.a); (void) hipEventDestroy(ep.b); }
-    for(auto e : ln.ev_pool) (void) hipEventDestroy(e);
-    for(auto e : ln.round_ev) if(e) (void) hipEventDestroy(e);
-    if(ln.selected_ev) (void) hipEventDestroy(ln.selected_ev);
-    for(auto e : ln.staging_ev) if(e) (void) hipEventDestroy(e);
-    if(ln.owns_stream && ln.stream) (void) hipStreamDestroy(ln.stream);
-  }
-  if(c->side_stream) { (void) hipStreamSynchronize(c->side_stream); (void) hipStreamDestroy(c->side_stream); }
-  if(c->side_stream2) { (void) hipStreamSynchronize(c->side_stream2); (void) hipStreamDestroy(c->side_stream2); }
-  if(c->copy_stream) { (void) hipStreamSynchronize(c->copy_stream); (void) hipStreamDestroy(c->copy_stream); }
-  if(c->copy_ev) (void) hipEventDestroy(c->copy_ev);
-  for(auto e : c->side_ev) if(e) (void) hipEventDestroy(e);
-  if(c->stream) (void) hipStreamDestroy(c->stream);
+  if(c->up_stream) (void) hipStreamSynchronize(c->up_stream);
+  for(auto& ln : c->lanes) if(ln.stream) (void) hipStreamSynchronize(ln.stream);
+  for(hipStream_t st : {c->side_stream.get(), c->side_stream2.get(), c->copy_stream.get()}) if(st) (void) hipStreamSynchronize(st);
   delete c;
 }
 

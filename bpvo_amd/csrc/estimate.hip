@@ -753,7 +753,7 @@ static int rig_upload(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const in
   max_pts.assign((size_t) c->L, 0);
   fill_job_tables(c, ln, 0, n, wss, refs, curs, [](int) { return (const bpvo_hip_params*) nullptr; }, max_pts.data());
   LANE_CK(ln, hipMemcpyAsync(ln->d_pjobs, ln->h_pjobs, sizeof(PairJob) * table * (size_t) job_tables(c), hipMemcpyHostToDevice, ln->stream));
-  if(!c->d_rig_X) LANE_CK(ln, hipMalloc((void**) &c->d_rig_X, sizeof(float) * 16 * (size_t) NP));
+  if(!c->d_rig_X) LANE_CK(ln, c->d_rig_X.alloc(16 * (size_t) NP));
   // (from the caller's pageable memory: the copy has left it when the call returns)
   LANE_CK(ln, hipMemcpyAsync(c->d_rig_X, X, sizeof(float) * 16 * (size_t) n, hipMemcpyHostToDevice, ln->stream));
   return BPVO_OK;
@@ -776,12 +776,11 @@ static LinearizeFlags rig_linearize_flags()
 // (one upload per estimate), the bodies' `active` words of a round
 static int rig_storage(bpvo_hip_ctx* c, Lane* ln)
 {
-  if(c->h_rig_active) return BPVO_OK;      // (the last of the allocations below)
   const size_t NP = (size_t) c->n_pairs;
-  if(!c->d_rig_stage) LANE_CK(ln, hipMalloc((void**) &c->d_rig_stage, rig_stage_bytes(c)));
-  if(!c->h_rig_stage) LANE_CK(ln, hipHostMalloc((void**) &c->h_rig_stage, rig_stage_bytes(c)));
-  if(!c->d_rig_active) LANE_CK(ln, hipMalloc((void**) &c->d_rig_active, sizeof(int) * NP));
-  LANE_CK(ln, hipHostMalloc((void**) &c->h_rig_active, 3 * sizeof(int) * NP));
+  if(!c->d_rig_stage) LANE_CK(ln, c->d_rig_stage.alloc(rig_stage_bytes(c)));
+  if(!c->h_rig_stage) LANE_CK(ln, c->h_rig_stage.alloc(rig_stage_bytes(c)));
+  if(!c->d_rig_active) LANE_CK(ln, c->d_rig_active.alloc(NP));
+  if(!c->h_rig_active) LANE_CK(ln, c->h_rig_active.alloc(3 * NP));
   return BPVO_OK;
 }
 
@@ -800,7 +799,7 @@ static int estimate_rigs_on_lane(bpvo_hip_ctx* c, Lane* ln, int R, const RigProb
   for(int r = 0; r < R; ++r) { N += rigs[r].n; max_iterations = std::max(max_iterations, (rigs[r].prm ? rigs[r].prm : &p)->maxIterations); }
   // The loop iterates on the pose of each rig's REFERENCE member (its member 0) in that member's normalised twist (rig_math.h: the f32 solve wants
   // a normalised system; a rig of one camera takes that camera's own steps): the extrinsics relative to it, its initial pose, and the body pose at the end
-  RigEntry* tab = reinterpret_cast<RigEntry*>(c->h_rig_stage);
+  RigEntry* tab = reinterpret_cast<RigEntry*>(c->h_rig_stage.get());
   float* hX = reinterpret_cast<float*>(c->h_rig_stage + rig_stage_X_at(c));
   float* hT = hX + 16 * (size_t) NP;
   char* const d_stage = c->d_rig_stage;
@@ -1135,13 +1134,10 @@ int bpvo_hip_estimate_pose_trace(bpvo_hip_ctx* c, int ws, int ref_slot, int cur_
   if(!T_init || !T_est || !n_records || max_records < 0 || (max_records > 0 && !records)) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr pose / records");
   if(int rc = check_template_not_empty(c, ref_slot)) return rc;
   (void) hipSetDevice(c->device);
-  const int cap = c->L * (max_linearizations(c->params.maxIterations) + 1);
-  if(cap > c->trace_cap) {
+  const size_t cap = (size_t) kTraceFloats * c->L * (max_linearizations(c->params.maxIterations) + 1);
+  if(cap > c->d_trace.size()) {
     HIP_CK(c, hipStreamSynchronize(c->stream));
-    (void) hipFree(c->d_trace);
-    c->d_trace = nullptr; c->trace_cap = 0;
-    HIP_CK(c, hipMalloc((void**) &c->d_trace, sizeof(float) * kTraceFloats * (size_t) cap));
-    c->trace_cap = cap;
+    HIP_CK(c, c->d_trace.reserve(cap));
   }
   c->trace_ws = ws;
   const int rc = estimate_batch(c, 1, &ws, &ref_slot, &cur_slot, T_init, T_est, stats);
@@ -1149,7 +1145,7 @@ int bpvo_hip_estimate_pose_trace(bpvo_hip_ctx* c, int ws, int ref_slot, int cur_
   if(rc) return rc;
   const int n = c->lanes[0].h_states[ws].trace_n;
   *n_records = n;
-  const int ncopy = std::min(std::min(n, max_records), c->trace_cap);
+  const int ncopy = std::min(std::min(n, max_records), (int) (c->d_trace.size() / kTraceFloats));
   if(ncopy > 0) HIP_CK(c, hipMemcpy(records, c->d_trace, sizeof(float) * kTraceFloats * (size_t) ncopy, hipMemcpyDeviceToHost));
   return BPVO_OK;
 }

@@ -173,8 +173,8 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
 int upload_disparity(bpvo_hip_ctx* c, int slot, const float* disparity)
 {
   if(!c->copy_stream) {
-    HIP_CK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    HIP_CK(c, hipEventCreateWithFlags(&c->copy_ev, hipEventDisableTiming));
+    HIP_CK(c, c->copy_stream.create());
+    HIP_CK(c, c->copy_ev.create(hipEventDisableTiming));
   }
   HIP_CK(c, hipMemcpyAsync(c->frames[slot].disp, disparity, slot_geom(c, c->frames[slot], 0).npix * sizeof(float), hipMemcpyHostToDevice, c->copy_stream));
   HIP_CK(c, hipEventRecord(c->copy_ev, c->copy_stream));
@@ -196,16 +196,7 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
   const LevelGeom* geom = stage_geom(c, slots, count);      // (storage: the context's)
   if(!geom) return BPVO_ERR_INVALID_ARG;
   hipStream_t s = fr.stream;
-  for(int i = 0; i < count; ++i) {
-    FrameSlot& f = c->frames[slots[i]];
-    if(f.tmpl_slab) continue;
-    size_t total = 0;
-    FrameSlot tmp;
-    carve_frame_tmpl(c, tmp, nullptr, &total);
-    FR_CK(c, fr, hipMalloc(&f.tmpl_slab, total));
-    FR_CK(c, fr, hipMemsetAsync(f.tmpl_slab, 0, total, s));
-    carve_frame_tmpl(c, f, (unsigned char*) f.tmpl_slab, nullptr);
-  }
+  for(int i = 0; i < count; ++i) FR_CK(c, fr, ensure_template_storage(c, c->frames[slots[i]], s));
   // the point budgets of the stage: what each slot's levels run with (bpvo_hip_get_selection_info), and which levels have one in any slot
   bool budget_at[kMaxLevels] = {};
   for(int i = 0; i < count; ++i) {
@@ -238,9 +229,9 @@ int frames_set_template_slots(bpvo_hip_ctx* c, const int* slots, int count, cons
   // the two before it returns; lanes of a fanned-out batch keep it in line.
   const bool side = c->nrm_side_stream && !fr.own_thread && fr.ln == &c->lanes[0] && counts_ev;
   if(side && !c->side_stream) {
-    FR_CK(c, fr, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-    FR_CK(c, fr, hipStreamCreateWithFlags(&c->side_stream2, hipStreamNonBlocking));
-    for(auto& e : c->side_ev) FR_CK(c, fr, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    FR_CK(c, fr, c->side_stream.create());
+    FR_CK(c, fr, c->side_stream2.create());
+    for(auto& e : c->side_ev) FR_CK(c, fr, e.create(hipEventDisableTiming));
   }
   // ... and when the estimation follows on this stream within the same call (fr.defer_finest_nrm: a batch on one lane), only the COARSEST
   // level's sums are joined here: the others — the longest is the first level without non-maximum suppression, 100 k points of a
@@ -547,13 +538,11 @@ int bpvo_hip_get_points(bpvo_hip_ctx* c, int slot, int level, float* xyzw)
 {
   TMPL(c, slot, level);
   if(n && c->points_from_compact) {      // debug: the points as the Gauss-Newton kernels rebuild them from the 8-byte records (load_point)
-    float4* d_out = nullptr;
-    HIP_CK(c, hipMalloc((void**) &d_out, sizeof(float4) * n));
+    DeviceBuf<float4> d_out;
+    HIP_CK(c, d_out.alloc((size_t) n));
     launch_rebuild_points(c->stream, make_pair_job(c, 0, slot, slot, level), d_out);
-    hipError_t e = hipMemcpyAsync(xyzw, d_out, sizeof(float4) * n, hipMemcpyDeviceToHost, c->stream);
-    if(e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void) hipFree(d_out);
-    HIP_CK(c, e);
+    HIP_CK(c, hipMemcpyAsync(xyzw, d_out, sizeof(float4) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_CK(c, hipStreamSynchronize(c->stream));
     return BPVO_OK;
   }
   if(n) HIP_CK(c, hipMemcpyAsync(xyzw, f.pts[level], sizeof(float4) * n, hipMemcpyDeviceToHost, c->stream));
@@ -582,19 +571,15 @@ int bpvo_hip_get_jacobians(bpvo_hip_ctx* c, int slot, int level, float* J)
   TMPL(c, slot, level);
   if(n == 0) return BPVO_OK;
   // the rows are not stored: evaluate them on the device from (point, Ix, Iy) exactly like irls_reduce does
-  const size_t bytes = sizeof(float) * 6 * (size_t) n * c->C;
-  float* d_out = nullptr;
-  HIP_CK(c, hipMalloc((void**) &d_out, bytes));
+  const size_t floats = 6 * (size_t) n * c->C;
+  DeviceBuf<float> d_out;
+  HIP_CK(c, d_out.alloc(floats));
   HIP_CK(c, hipStreamSynchronize(c->stream));
   c->h_fjobs[0] = make_frame_job(c, f, level);
-  hipError_t e = hipMemcpyAsync(c->d_fjobs, c->h_fjobs, sizeof(FrameJob), hipMemcpyHostToDevice, c->stream);
-  if(e == hipSuccess) {
-    launch_export_jacobians(c->stream, c->d_fjobs, c->C, n, d_out);
-    e = hipMemcpyAsync(J, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  if(e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void) hipFree(d_out);
-  HIP_CK(c, e);
+  HIP_CK(c, hipMemcpyAsync(c->d_fjobs, c->h_fjobs, sizeof(FrameJob), hipMemcpyHostToDevice, c->stream));
+  launch_export_jacobians(c->stream, c->d_fjobs, c->C, n, d_out);
+  HIP_CK(c, hipMemcpyAsync(J, d_out, sizeof(float) * floats, hipMemcpyDeviceToHost, c->stream));
+  HIP_CK(c, hipStreamSynchronize(c->stream));
   return BPVO_OK;
 }
 int bpvo_hip_get_normalization(bpvo_hip_ctx* c, int slot, int level, float T[16], float T_inv[16])

@@ -5,6 +5,7 @@
 //                 stereo front-end                                                       vo_state.h    addFrame's state machine (host only, no HIP)
 //                                                                                        gn_rounds.h   the chain's pipelined rounds (host only, no HIP)
 //   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)      frame_plan.h  the frame stage's decisions (host only, no HIP)
+//   device_owned.h  the owners of every device buffer, pinned buffer, stream and event below (the only place that acquires or releases one)
 // The host keeps bpvo's object model (frames with a descriptor pyramid and a template pyramid, a pose estimator with per-level
 // Gauss-Newton runs, the VisualOdometry keyframe state machine) but every O(pixels) / O(points) array lives in HBM; per GN iteration the
 // host sees one 4-byte "pairs still active" counter.  See DESIGN.md.
@@ -26,6 +27,7 @@
 #include <thread>
 #include <vector>
 
+#include "device_owned.h"
 #include "frame_plan.h"
 #include "gn_rounds.h"
 #include "kernels.h"
@@ -61,8 +63,7 @@ struct LevelGeom {
 struct FrameSlot {
   bool has_data = false, has_template = false;
   bool has_disp = false;     // the slot holds the disparity of its image (false for the current frames B of a pair batch: never uploaded)
-  void* data_slab = nullptr;
-  void* tmpl_slab = nullptr;
+  DeviceBuf<unsigned char> data_slab, tmpl_slab;   // the slot's storage: the pointers below are views carved from them (carve_frame_data / carve_frame_tmpl)
   uint8_t* img[kMaxLevels] = {};
   uint8_t* cen[kMaxLevels] = {};
   float* ch0[kMaxLevels] = {};
@@ -103,13 +104,10 @@ struct FrameSlot {
 };
 
 struct Workspace {
-  float* r = nullptr;
-  uint8_t* valid = nullptr;
-  uint32_t* cand = nullptr;
-  uint32_t* med_blk = nullptr;
-  uint32_t* tapkey = nullptr;
-  float* tapcache = nullptr;
-  float* partials = nullptr;
+  DeviceBuf<float> r;
+  DeviceBuf<uint8_t> valid;
+  DeviceBuf<uint32_t> cand, med_blk, tapkey;
+  DeviceBuf<float> tapcache, partials;
   int last_ref = -1, last_cur = -1, last_level = -1;
   bool has_estimate = false;   // the workspace's state is that of a finished estimate (pose, scale and level of its finest level): what
                                // bpvo_hip_pose_covariances reads when no pose is given; a later linearize call on the workspace clears it
@@ -120,27 +118,27 @@ struct Workspace {
 // scales, extrinsics) are staged in pinned memory and uploaded in one copy.
 struct CovScratch {
   int group = 0;               // slots: min(BPVO_HIP_COV_GROUP, workspaces of the context)
-  void* d_slab = nullptr;
+  DeviceBuf<unsigned char> d_slab;                    // the d_ pointers below are views carved from it
   float* d_r = nullptr; size_t r_floats = 0;          // [group][r_floats]
   uint8_t* d_valid = nullptr; size_t valid_bytes = 0; // [group][valid_bytes]
   float* d_partials = nullptr; size_t partial_floats = 0;
   unsigned long long* d_cnt = nullptr;                // [group][kWsCounters]
   GNState* d_states = nullptr;                        // [group]
   unsigned char* d_tables = nullptr;                  // the uploaded tables, laid out as h_tables
-  unsigned char* h_tables = nullptr;                  // pinned
+  PinnedBuf<unsigned char> h_tables;
   size_t tables_bytes = 0, off_members = 0, off_T = 0, off_sigma = 0, off_X = 0;
   bpvo_hip_pose_covariance* d_out = nullptr;          // [group]
-  bpvo_hip_pose_covariance* h_out = nullptr;          // pinned [group]
+  PinnedBuf<bpvo_hip_pose_covariance> h_out;          // [group]
   float* d_sums = nullptr;                            // [n_pairs][72]: M and Q of the last pass on each workspace
 };
 
 // Device buffers of the pose-scoring calls (score.hip), the context's own, grown on demand: the jobs of a call's pairs, its poses, the
-// per-(pair, chunk, pose) partials and the records.  Capacities in elements.
+// per-(pair, chunk, pose) partials and the records.
 struct ScoreScratch {
-  PairJob* d_jobs = nullptr; size_t jobs_cap = 0;
-  float* d_T = nullptr; size_t T_cap = 0;
-  ScorePartial* d_partials = nullptr; size_t partials_cap = 0;
-  bpvo_hip_pose_score* d_out = nullptr; size_t out_cap = 0;
+  DeviceBuf<PairJob> d_jobs;
+  DeviceBuf<float> d_T;
+  DeviceBuf<ScorePartial> d_partials;
+  DeviceBuf<bpvo_hip_pose_score> d_out;
 };
 
 enum KernelClass { KC_PYRAMID = 0, KC_DESCRIPTOR, KC_SALIENCY_SELECT, KC_NORMALIZATION, KC_TEMPLATE, KC_WARP_RESIDUAL, KC_MEDIAN,
@@ -148,31 +146,31 @@ enum KernelClass { KC_PYRAMID = 0, KC_DESCRIPTOR, KC_SALIENCY_SELECT, KC_NORMALI
 static const char* const kKernelNames[KC_COUNT] = {"pyramid", "descriptor", "saliency_select", "normalization", "template_build", "warp_residual",
                                       "median", "irls_reduce", "gn_step", "point_budget"};
 
-struct EventPair { hipEvent_t a, b; int kc; double units; };
+struct EventPair { Event a, b; int kc; double units; };
 
 // An estimation lane: one HIP stream plus the host staging it needs.  Batches of independent pairs are split over
 // several lanes driven by their own host threads, so that the narrow per-pair kernels of one group (median select,
 // gn_step: one workgroup per pair) overlap with the chip-filling kernels (warp_residual, irls_reduce) of another.
 struct Lane {
-  hipStream_t stream = nullptr;
-  bool owns_stream = false;
-  PairJob* h_pjobs = nullptr;      // pinned [L][n_pairs]
-  PairJob* d_pjobs = nullptr;      // [L][n_pairs]
-  float* h_T = nullptr;            // pinned [n_pairs][16]
-  float* d_Tinit = nullptr;
-  int* d_active = nullptr;         // [3][2] per round in flight: entries of the active list, and how many of them still estimate their scale
-  int* d_list = nullptr;           // [3][n_pairs] active-workspace lists of the host rounds in flight (ActiveSet)
-  int* h_active = nullptr;         // pinned [3][2]
-  hipEvent_t round_ev[3] = {};     // "compaction of round r and its count have landed"
-  hipEvent_t staging_ev[2] = {};   // "the upload of this lane's rows of FrameJob table 0 / 1 has left the pinned staging"
-  hipEvent_t selected_ev = nullptr; // staggered batches: "the selection of this lane's templates has been queued" (FrameRun)
-  unsigned* d_pk_ctl = nullptr;    // [kMaxLevels][kPkCtlWords] {arrivals, abort} of the persistent kernel, one slot per level
-  unsigned* h_pk_ctl = nullptr;    // pinned copy
-  unsigned* d_team_ctl = nullptr;  // gn_team_ctl_words(kMaxTeams) words of the team-persistent kernel (lane 0 only)
-  unsigned* h_team_ctl = nullptr;  // pinned copy of its first line (abort word)
-  GNState* h_states = nullptr;     // pinned [n_pairs + n_pairs]: the workspaces' states, then the body states of rig mode (estimate_rigs)
+  hipStream_t stream = nullptr;    // the context's stream (lane 0) or own_stream
+  Stream own_stream;
+  PinnedBuf<PairJob> h_pjobs;      // [L][n_pairs]
+  DeviceBuf<PairJob> d_pjobs;      // [L][n_pairs]
+  PinnedBuf<float> h_T;            // [n_pairs][16]
+  DeviceBuf<float> d_Tinit;
+  DeviceBuf<int> d_active;         // [3][2] per round in flight: entries of the active list, and how many of them still estimate their scale
+  DeviceBuf<int> d_list;           // [3][n_pairs] active-workspace lists of the host rounds in flight (ActiveSet)
+  PinnedBuf<int> h_active;         // [3][2]
+  Event round_ev[3];               // "compaction of round r and its count have landed"
+  Event staging_ev[2];             // "the upload of this lane's rows of FrameJob table 0 / 1 has left the pinned staging"
+  Event selected_ev;               // staggered batches: "the selection of this lane's templates has been queued" (FrameRun)
+  DeviceBuf<unsigned> d_pk_ctl;    // [kMaxLevels][kPkCtlWords] {arrivals, abort} of the persistent kernel, one slot per level
+  PinnedBuf<unsigned> h_pk_ctl;    // its host copy
+  DeviceBuf<unsigned> d_team_ctl;  // gn_team_ctl_words(kMaxTeams) words of the team-persistent kernel (lane 0 only)
+  PinnedBuf<unsigned> h_team_ctl;  // host copy of its first line (abort word)
+  PinnedBuf<GNState> h_states;     // [n_pairs + n_pairs]: the workspaces' states, then the body states of rig mode (estimate_rigs)
   std::vector<EventPair> ev_pending;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
   unsigned k6_seq = 0;             // warp_residual launches of this lane since bpvo_hip_profiling (event sampling)
   std::string err;
 };
@@ -209,49 +207,48 @@ struct bpvo_hip_ctx {
   GaussTaps grad_pre;           // cv::GaussianBlur(Size(), sigma) of GradientDescriptor (sigmaPriorToCensusTransform > 0)
   GaussTaps latch_after;        // imsmooth(1.75) of every LATCH channel (bpvo/latch_descriptor.cc:1082)
   int latch_taps[2] = {0, 0};   // fixed-point {centre, side} taps of LATCH's cv::GaussianBlur(Size(3,3), 2, 2) (:147)
-  signed char* d_latch_off = nullptr;   // [48 * latchNumBytes] triplet coordinates as CalcuateSums uses them (:170-236)
+  DeviceBuf<signed char> d_latch_off;   // [48 * latchNumBytes] triplet coordinates as CalcuateSums uses them (:170-236)
   int scratch_planes = kDfPlanes;   // work planes of FrameSlot::scratch
   bool plane_scratch = false; // descriptor built from plane operations (descriptor fields, central difference, smoothed gradient)
-  hipStream_t stream = nullptr;
+  Stream stream;
   std::vector<FrameSlot> frames;
   std::vector<Workspace> ws;
-  GNState* d_states = nullptr;
-  FrameJob* d_fjobs = nullptr;     // [2][L][n_frames]: the table of the setData stage, then the one of the setTemplate stage
+  DeviceBuf<GNState> d_states;
+  DeviceBuf<FrameJob> d_fjobs;     // [2][L][n_frames]: the table of the setData stage, then the one of the setTemplate stage
   std::vector<Lane> lanes;         // lanes[0] shares the ctx stream
-  PairJob* d_job1 = nullptr;       // scratch single job (linearize / weights)
-  float* d_records = nullptr;      // [n_pairs][kRecordFloats]
-  float* d_wtmp = nullptr;         // [cap_max * C] weights scratch
-  unsigned int* d_count = nullptr;
-  unsigned* d_tickets = nullptr;             // [n_pairs] PairJob::ticket
-  unsigned long long* d_counters = nullptr;   // [4] points, linearisations, bracketed / full median selections
+  DeviceBuf<PairJob> d_job1;       // scratch single job (linearize / weights)
+  DeviceBuf<float> d_records;      // [n_pairs][kRecordFloats]
+  DeviceBuf<float> d_wtmp;         // [cap_max * C] weights scratch
+  DeviceBuf<unsigned int> d_count;
+  DeviceBuf<unsigned> d_tickets;             // [n_pairs] PairJob::ticket
+  DeviceBuf<unsigned long long> d_counters;   // [4] points, linearisations, bracketed / full median selections
   // pinned staging
-  FrameJob* h_fjobs = nullptr;
-  int* h_ints = nullptr;           // [max(n_frames*kMaxLevels, 16)] pinned
-  int* d_ints = nullptr;           // same size, device
+  PinnedBuf<FrameJob> h_fjobs;
+  PinnedBuf<int> h_ints;           // [max(n_frames*kMaxLevels, 16)]
+  DeviceBuf<int> d_ints;           // same size, device
   int cap_max = 0;
   SeqState vo;                     // bpvo_hip_add_frame's VisualOdometry state (vo_state.h) on frame slots 0 .. 2 and workspace 0
-  bpvo_hip_point_with_info* d_cloud = nullptr;   // the last key frame's point cloud: built on the device (vo.hip build_point_cloud), copied out when asked for
-  size_t d_cloud_cap = 0;
+  DeviceBuf<bpvo_hip_point_with_info> d_cloud;   // the last key frame's point cloud: built on the device (vo.hip build_point_cloud), copied out when asked for
   // many independent VisualOdometry sequences (bpvo_hip_add_frames, vo.hip): vo_mode 0 = not yet decided, 1 = bpvo_hip_add_frame, 2 = bpvo_hip_add_frames
   int vo_mode = 0;
   std::vector<SeqState> seqs;                      // [seq_capacity], created by the first bpvo_hip_add_frames
-  bpvo_hip_point_with_info* d_seq_cloud = nullptr; // [seq_capacity][geom[maxTestLevel].cap] point clouds
-  PairJob* h_seq_jobs = nullptr;                   // pinned [seq_capacity]: the jobs of the fraction-of-good-points count and the point clouds
-  PairJob* d_seq_jobs = nullptr;
-  CloudJob* h_cloud_jobs = nullptr;                // pinned [seq_capacity]
-  CloudJob* d_cloud_jobs = nullptr;
-  unsigned* h_seq_cnt = nullptr;                   // pinned [seq_capacity]: good-point counters
-  unsigned* d_seq_cnt = nullptr;
-  size_t* h_seq_off = nullptr;                     // pinned [seq_capacity]: pixel offsets of the frames of a mixed-size call in the packed device inputs
-  size_t* d_seq_off = nullptr;
+  DeviceBuf<bpvo_hip_point_with_info> d_seq_cloud; // [seq_capacity][geom[maxTestLevel].cap] point clouds
+  PinnedBuf<PairJob> h_seq_jobs;                   // [seq_capacity]: the jobs of the fraction-of-good-points count and the point clouds
+  DeviceBuf<PairJob> d_seq_jobs;
+  PinnedBuf<CloudJob> h_cloud_jobs;                // [seq_capacity]
+  DeviceBuf<CloudJob> d_cloud_jobs;
+  PinnedBuf<unsigned> h_seq_cnt;                   // [seq_capacity]: good-point counters
+  DeviceBuf<unsigned> d_seq_cnt;
+  PinnedBuf<size_t> h_seq_off;                     // [seq_capacity]: pixel offsets of the frames of a mixed-size call in the packed device inputs
+  DeviceBuf<size_t> d_seq_off;
   // Rig mode (bpvo_hip_rig_set / bpvo_hip_rigs_set ... bpvo_hip_add_frames_rig(s), vo.hip): rigs[r] (RigState below) = the cameras of one rigid rig,
   // estimated as one body pose.  A context with a rig (rigs not empty) serves bpvo_hip_add_frames_rig(s) only.
   std::vector<RigState> rigs;
-  float* d_rig_X = nullptr;        // [n_pairs][16], allocated at its first use (bpvo_hip_linearize_rig)
+  DeviceBuf<float> d_rig_X;        // [n_pairs][16], allocated at its first use (bpvo_hip_linearize_rig)
   // estimate_rigs' staging (rig_stage_bytes: the rigs' table, extrinsics, initial poses — one upload per estimate) and the bodies' `active` words
   // of a round (device [n_pairs]; pinned [3][n_pairs], a row per round in flight); allocated at their first use
-  char* d_rig_stage = nullptr; char* h_rig_stage = nullptr;
-  int* d_rig_active = nullptr; int* h_rig_active = nullptr;
+  DeviceBuf<char> d_rig_stage; PinnedBuf<char> h_rig_stage;
+  DeviceBuf<int> d_rig_active; PinnedBuf<int> h_rig_active;
   // Pose covariance (c_api.h bpvo_hip_pose_covariances, pose_cov.hip).  Option "pose_covariance": the addFrame entry points run the pass behind
   // the estimate their result's pose comes from and keep the record — vo_cov for bpvo_hip_add_frame, seq_cov[s] per sequence, RigState::cov per rig.
   int pose_covariance = 0;
@@ -310,14 +307,14 @@ struct bpvo_hip_ctx {
   // the normalisation's streams (created at their first use) and their events: [0] fork, [1] coarsest level done (or all), [2] the levels between the
   // coarsest and the finest done, [3] the finest level done.  Deferred form: the finest level — the long one: 2.3 ms of dependent adds for a dense
   // 640x480 template — has a stream of its own, so that the levels above it are ready, and their Gauss-Newton iterations run, while it is still adding.
-  hipStream_t side_stream = nullptr, side_stream2 = nullptr;
-  hipStream_t copy_stream = nullptr;      // addFrame's disparity upload (frames.hip upload_disparity); created at its first use, with its event
-  hipEvent_t copy_ev = nullptr;
+  Stream side_stream, side_stream2;
+  Stream copy_stream;      // addFrame's disparity upload (frames.hip upload_disparity); created at its first use, with its event
+  Event copy_ev;
   // run once by the estimation of a group on the context's stream right before its final synchronisation, i.e. with every kernel of the estimate
   // queued (estimate.hip): addFrame's disparity upload
   std::function<int()> before_final_sync;
   int vo_disparity_late = 1;      // option "vo_disparity_late": addFrame uploads a host frame's disparity under the queued estimate (1) or in its data stage (0)
-  hipEvent_t side_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event side_ev[4];
   hipEvent_t nrm_pending = nullptr;   // non-null: recorded behind the normalisation of the levels between the coarsest and the finest of the template stage just
                                  // queued; whoever reads those levels' (scale, centroid) next makes its stream wait for it (estimate.hip) and clears it
   hipEvent_t nrm_pending_finest = nullptr;   // ... and behind the finest level's
@@ -329,20 +326,18 @@ struct bpvo_hip_ctx {
   std::atomic<bool> persistent_failed{false};      // (atomics: estimate_group runs on the lane threads)
   std::atomic<uint64_t> persistent_levels{0};      // levels run by the persistent kernel (measurement)
   // bpvo_hip_estimate_pose_trace: while trace_ws >= 0 the jobs of that workspace carry the device trace buffer
-  float* d_trace = nullptr;
-  int trace_cap = 0, trace_ws = -1;
+  DeviceBuf<float> d_trace;    // [records][kTraceFloats]
+  int trace_ws = -1;
   int max_lanes_now = 1 << 30; // bpvo_hip_set_max_lanes: measurement runs that need per-launch timings without overlap
-  // stereo front-end scratch (lazily sized for the most pixels a call has held, the sum over its frames): raw and pre-filtered u8 pairs, f32 disparities
-  uint8_t* st_left = nullptr; uint8_t* st_right = nullptr; uint8_t* st_left_pre = nullptr; uint8_t* st_right_pre = nullptr;
-  float* st_disp = nullptr;
+  // stereo front-end scratch (st_pixels each: the most pixels a call has held, the sum over its frames): raw and pre-filtered u8 pairs, f32 disparities
+  DeviceBuf<uint8_t> st_left, st_right, st_left_pre, st_right_pre;
+  DeviceBuf<float> st_disp;
   size_t st_pixels = 0;
-  void* st_sgm = nullptr;      // scratch of the semi-global matchers (cost volumes: the largest frame x disparity range x frames per launch seen)
-  size_t st_sgm_bytes = 0;
+  DeviceBuf<unsigned char> st_sgm;      // scratch of the semi-global matchers (cost volumes: the largest frame x disparity range x frames per launch seen)
   // calls whose frames differ in size: the block matcher's frame table (kernels.h StereoFrame), filled in pinned memory and copied on the
   // stream; st_tab_ev: behind the last copy (the pinned rows are rewritten only once it has passed)
-  StereoFrame* h_st_frames = nullptr; StereoFrame* d_st_frames = nullptr;
-  int st_tab_cap = 0;
-  hipEvent_t st_tab_ev = nullptr;
+  PinnedBuf<StereoFrame> h_st_frames; DeviceBuf<StereoFrame> d_st_frames;
+  Event st_tab_ev;
   // option "stereo_frames_per_launch": SGM frames of one size that go through each kernel together; 0: as many as fit a third of the device
   // memory that was free when the SGM scratch was first needed (st_sgm_budget, read once per context), 1: one after the other, k: at most k
   int stereo_frames_per_launch = 0;
@@ -358,14 +353,13 @@ struct bpvo_hip_ctx {
   // a kernel from their pinned rows (a hipMemcpyAsync waits its turn behind 45 MB chunk copies in the DMA engines).
   int up_workers = 6;
   std::atomic<bool> ctl_by_kernel{false};
-  std::vector<hipStream_t> up_streams;
-  std::vector<uint8_t*> up_pinned;       // [worker]: 2 slots of up_slot_bytes
-  std::vector<hipEvent_t> up_slot_free;  // [worker * 2 + slot]
-  std::vector<hipEvent_t> up_chunk_done; // pool, one per chunk of a call
+  Stream up_stream;                      // the workers' one copy stream
+  std::vector<PinnedBuf<uint8_t>> up_pinned;   // [worker]: 2 slots of up_slot_bytes
+  std::vector<Event> up_slot_free;       // [worker * 2 + slot]
+  std::vector<Event> up_chunk_done;      // pool, one per chunk of a call
   size_t up_slot_bytes = 0;
-  uint8_t* up_d_img = nullptr;           // device staging: images [2 n][npix]
-  float* up_d_disp = nullptr;            //                 disparities of the A frames [n][npix]
-  int up_cap_pairs = 0;
+  DeviceBuf<uint8_t> up_d_img;           // device staging: images [2 n][npix]
+  DeviceBuf<float> up_d_disp;            //                 disparities of the A frames [n][npix]
   // host batches on two lanes: the pairs are cut into a SMALL first group (lane 0 starts its Gauss-Newton stage while most of the batch
   // is still crossing the bus), a large second one for lane 1, and the rest for lane 0 again (host_groups_plan); fractions of the batch
   double up_plan[2] = {0.19, 0.50};      // options "upload_plan_first" / "upload_plan_second"; first = 0: two equal groups.  Measured: profiles/r03_host_buffers_plan.txt
@@ -443,7 +437,7 @@ struct Carver {
 };
 
 // HIP events around a kernel class on a lane's stream (measurement; resolved by resolve_events)
-hipEvent_t take_event(Lane* ln);
+Event take_event(Lane* ln);
 struct ScopedTimer {
   Lane* ln;
   EventPair ep;
@@ -461,7 +455,7 @@ struct ScopedTimer {
   {
     if(!on) return;
     (void) hipEventRecord(ep.b, st);
-    ln->ev_pending.push_back(ep);
+    ln->ev_pending.push_back(std::move(ep));
   }
 };
 
@@ -513,7 +507,7 @@ int imsmooth_taps(float sigma);
 int auto_gauss_taps_f32(float sigma);
 void carve_frame_data(bpvo_hip_ctx* c, FrameSlot& f, unsigned char* base, size_t* total);
 void carve_frame_tmpl(bpvo_hip_ctx* c, FrameSlot& f, unsigned char* base, size_t* total);
-int ensure_template_storage(bpvo_hip_ctx* c, FrameSlot& f);
+hipError_t ensure_template_storage(bpvo_hip_ctx* c, FrameSlot& f, hipStream_t stream);      // a slot without template storage gets it, zeroed on `stream`
 FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l);
 PairJob make_pair_job(bpvo_hip_ctx* c, int ws, int ref, int cur, int l);      // (with the context's parameters)
 void pair_job_set_params(PairJob& j, const bpvo_hip_params& p);              // ... and a sequence's own in their place
@@ -663,8 +657,6 @@ int pose_cov_pass(bpvo_hip_ctx* c, int n_records, int members, const int* wss, c
                   const float* T, const float* sigma, const bpvo_hip_params* const* prms, bpvo_hip_pose_covariance* out);
 int pose_cov_ensure_scratch(bpvo_hip_ctx* c);
 void pose_cov_none(bpvo_hip_pose_covariance* r);      // the record of "nothing was estimated": Identity pose and covariance, BPVO_COV_NONE
-void pose_cov_free(bpvo_hip_ctx* c);
-void pose_score_free(bpvo_hip_ctx* c);      // score.hip: the scoring calls' device buffers
 // ... does the context serve pose scoring (kLinear, at most 48 channels)?  BPVO_OK, or BPVO_ERR_UNSUPPORTED with the message
 int pose_score_served(bpvo_hip_ctx* c);
 // ... and the call behind bpvo_hip_score_poses(_pairs): the records of n_poses poses T [n_pairs][n_poses][16] for each of the pairs, one launch,

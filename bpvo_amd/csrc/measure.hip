@@ -104,6 +104,12 @@ int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* c, uint64_t out[4])
 }
 // diagnostics: the Gauss-Newton state of a workspace after its last call — out[0..15] T, [16..51] H, [52..57] G, [58..63] dp,
 // [64] f_norm, [65] scale, [66] delta_scale, [67] g_norm, [68..83] T_lin (pose of the last linearisation)
+int bpvo_hip_debug_live_resources(int counts[4])
+{
+  if(!counts) return BPVO_ERR_INVALID_ARG;
+  for(int k = 0; k < RES_KINDS; ++k) counts[k] = g_live_resources[k].load();
+  return BPVO_OK;
+}
 int bpvo_hip_debug_gn_state(bpvo_hip_ctx* c, int ws, float out[84])
 {
   CHECK_CTX(c); CHECK_WS(c, ws);

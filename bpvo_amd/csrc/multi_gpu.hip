@@ -109,11 +109,11 @@ int bpvo_hip_node_create(bpvo_hip_node** out, int n_devices, const int* devices,
     const int rc = bpvo_hip_create(&k.ctx, K, baseline, rows, cols, p, k.device, 2 * max_pairs_per_device, max_pairs_per_device);
     if(rc) return bail(rc, std::string("bpvo_hip_create on device ") + std::to_string(k.device) + ": " + bpvo_hip_last_error(nullptr));
     if(hipSetDevice(k.device) != hipSuccess || hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking) != hipSuccess ||
-       hipMalloc((void**) &k.d_send, sizeof(float) * kRecordFloats * (size_t) max_pairs_per_device) != hipSuccess)
+       hipMalloc(&k.d_send, sizeof(float) * kRecordFloats * (size_t) max_pairs_per_device) != hipSuccess)
       return bail(BPVO_ERR_DEVICE, "stream / staging allocation failed on device " + std::to_string(k.device));
   }
   if(hipSetDevice(n->ranks[0].device) != hipSuccess ||
-     hipMalloc((void**) &n->d_recv, sizeof(float) * kRecordFloats * (size_t) max_pairs_per_device * n_devices) != hipSuccess)
+     hipMalloc(&n->d_recv, sizeof(float) * kRecordFloats * (size_t) max_pairs_per_device * n_devices) != hipSuccess)
     return bail(BPVO_ERR_DEVICE, "gather buffer allocation failed");
   n->h_recv.resize((size_t) kRecordFloats * max_pairs_per_device * n_devices);
   std::vector<ncclComm_t> comms(n_devices);

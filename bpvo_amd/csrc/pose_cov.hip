@@ -18,15 +18,6 @@ void pose_cov_none(bpvo_hip_pose_covariance* r)
   r->status = BPVO_COV_NONE;
 }
 
-void pose_cov_free(bpvo_hip_ctx* c)
-{
-  CovScratch& k = c->cov;
-  (void) hipFree(k.d_slab);
-  (void) hipHostFree(k.h_tables);
-  (void) hipHostFree(k.h_out);
-  k = CovScratch();
-}
-
 static int pose_cov_supported(bpvo_hip_ctx* c)
 {
   if(c->G > 1 || c->C > 48) return fail(c, BPVO_ERR_UNSUPPORTED, "pose covariance: descriptors of more than 48 channels are not served (the channels of a point are one cluster)");
@@ -66,23 +57,18 @@ int pose_cov_ensure_scratch(bpvo_hip_ctx* c)
     return cv.off;
   };
   const size_t total = carve(nullptr, nullptr);
-  void* slab = nullptr;
-  HIP_CK(c, hipMalloc(&slab, total));
-  hipError_t e = hipMemset(slab, 0, total);
-  unsigned char* h_tables = nullptr;
-  bpvo_hip_pose_covariance* h_out = nullptr;
-  if(e == hipSuccess) e = hipHostMalloc((void**) &h_tables, tables_bytes);
-  if(e == hipSuccess) e = hipHostMalloc((void**) &h_out, sizeof(bpvo_hip_pose_covariance) * (size_t) group);
-  if(e != hipSuccess) {
-    (void) hipFree(slab); (void) hipHostFree(h_tables); (void) hipHostFree(h_out);
-    c->err = std::string("pose covariance scratch: ") + hipGetErrorString(e);
-    return BPVO_ERR_DEVICE;
-  }
+  // (local owners: the scratch is the context's only once all of it exists)
+  DeviceBuf<unsigned char> slab;
+  PinnedBuf<unsigned char> h_tables;
+  PinnedBuf<bpvo_hip_pose_covariance> h_out;
+  HIP_CK(c, slab.alloc(total));
+  HIP_CK(c, hipMemset(slab, 0, total));
+  HIP_CK(c, h_tables.alloc(tables_bytes));
+  HIP_CK(c, h_out.alloc((size_t) group));
   k.group = group;
-  k.d_slab = slab;
   k.r_floats = r_floats; k.valid_bytes = valid_bytes; k.partial_floats = partial_floats;
-  carve((unsigned char*) slab, &k);
-  k.h_tables = h_tables; k.h_out = h_out;
+  carve(slab, &k);
+  k.d_slab = std::move(slab); k.h_tables = std::move(h_tables); k.h_out = std::move(h_out);
   k.tables_bytes = tables_bytes; k.off_members = off_members; k.off_T = off_T; k.off_sigma = off_sigma; k.off_X = off_X;
   return BPVO_OK;
 }
@@ -98,7 +84,7 @@ int pose_cov_pass(bpvo_hip_ctx* c, int n_records, int members, const int* wss, c
   hipStream_t s = c->stream;
   HIP_CK(c, join_pending_normalization(c, s));
   const int per_group = k.group / members;      // records of one launch set
-  PairJob* h_jobs = reinterpret_cast<PairJob*>(k.h_tables);
+  PairJob* h_jobs = reinterpret_cast<PairJob*>(k.h_tables.get());
   CovMember* h_members = reinterpret_cast<CovMember*>(k.h_tables + k.off_members);
   float* h_T = reinterpret_cast<float*>(k.h_tables + k.off_T);
   float* h_sigma = reinterpret_cast<float*>(k.h_tables + k.off_sigma);

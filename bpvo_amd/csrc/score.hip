@@ -9,25 +9,6 @@ using namespace bpvo_hip_host;
 
 namespace bpvo_hip_host {
 
-void pose_score_free(bpvo_hip_ctx* c)
-{
-  ScoreScratch& k = c->score;
-  (void) hipFree(k.d_jobs); (void) hipFree(k.d_T); (void) hipFree(k.d_partials); (void) hipFree(k.d_out);
-  k = ScoreScratch();
-}
-
-// a buffer of the scratch at `need` elements at least (nothing of an earlier call is in flight: every call ends with a synchronisation)
-template <class T>
-static int score_grow(bpvo_hip_ctx* c, T** p, size_t* cap, size_t need)
-{
-  if(need <= *cap) return BPVO_OK;
-  (void) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  HIP_CK(c, hipMalloc((void**) p, sizeof(T) * need));
-  *cap = need;
-  return BPVO_OK;
-}
-
 int pose_score_served(bpvo_hip_ctx* c)
 {
   if(c->params.interp != BPVO_INTERP_LINEAR) {
@@ -71,10 +52,11 @@ int score_pairs(bpvo_hip_ctx* c, int n_pairs, const int* refs, const int* curs, 
   const size_t records = (size_t) n_pairs * (size_t) n_poses;
   const int chunks = score_chunks(max_points);
   ScoreScratch& k = c->score;
-  if(int rc = score_grow(c, &k.d_jobs, &k.jobs_cap, (size_t) n_pairs)) return rc;
-  if(int rc = score_grow(c, &k.d_T, &k.T_cap, records * 16)) return rc;
-  if(int rc = score_grow(c, &k.d_partials, &k.partials_cap, records * (size_t) chunks)) return rc;
-  if(int rc = score_grow(c, &k.d_out, &k.out_cap, records)) return rc;
+  // (nothing of an earlier call is in flight when the scratch grows: every call ends with a synchronisation)
+  HIP_CK(c, k.d_jobs.reserve((size_t) n_pairs));
+  HIP_CK(c, k.d_T.reserve(records * 16));
+  HIP_CK(c, k.d_partials.reserve(records * (size_t) chunks));
+  HIP_CK(c, k.d_out.reserve(records));
 
   HIP_CK(c, hipMemcpyAsync(k.d_jobs, h_jobs.data(), sizeof(PairJob) * (size_t) n_pairs, hipMemcpyHostToDevice, s));
   HIP_CK(c, hipMemcpyAsync(k.d_T, T, sizeof(float) * 16 * records, hipMemcpyHostToDevice, s));

@@ -25,13 +25,9 @@ static int build_point_cloud(bpvo_hip_ctx* c, size_t* cloud_points)
   if(rc) return rc;
   rc = upload_single_job(c, 0, w.last_ref, w.last_cur, w.last_level);
   if(rc) return rc;
-  if((size_t) n > c->d_cloud_cap) {
+  if((size_t) n > c->d_cloud.size()) {
     HIP_CK(c, hipStreamSynchronize(c->stream));
-    (void) hipFree(c->d_cloud);
-    c->d_cloud = nullptr; c->d_cloud_cap = 0;
-    const size_t cap = std::max<size_t>((size_t) c->geom[lvl].cap, (size_t) n);
-    HIP_CK(c, hipMalloc((void**) &c->d_cloud, cap * sizeof(bpvo_hip_point_with_info)));
-    c->d_cloud_cap = cap;
+    HIP_CK(c, c->d_cloud.reserve(std::max<size_t>((size_t) c->geom[lvl].cap, (size_t) n)));
   }
   launch_point_cloud(c->stream, c->d_job1, n, c->C, c->params.lossFunction, ref.img[0], c->rows, c->cols, c->geom[lvl].K, c->dspace, c->d_cloud);
   HIP_CK(c, hipGetLastError());
@@ -102,22 +98,20 @@ static int stereo_reserve(bpvo_hip_ctx* c, size_t npix)      // npix: the pixels
 {
   if(npix <= c->st_pixels) return BPVO_OK;
   HIP_CK(c, hipStreamSynchronize(c->stream));
-  (void) hipFree(c->st_left); (void) hipFree(c->st_right); (void) hipFree(c->st_left_pre); (void) hipFree(c->st_right_pre); (void) hipFree(c->st_disp);
-  c->st_left = c->st_right = c->st_left_pre = c->st_right_pre = nullptr; c->st_disp = nullptr; c->st_pixels = 0;
-  HIP_CK(c, hipMalloc((void**) &c->st_left, npix)); HIP_CK(c, hipMalloc((void**) &c->st_right, npix));
-  HIP_CK(c, hipMalloc((void**) &c->st_left_pre, npix)); HIP_CK(c, hipMalloc((void**) &c->st_right_pre, npix));
-  HIP_CK(c, hipMalloc((void**) &c->st_disp, npix * sizeof(float)));
+  DeviceBuf<uint8_t>* const u8[4] = {&c->st_left, &c->st_right, &c->st_left_pre, &c->st_right_pre};
+  c->st_pixels = 0;
+  for(auto* b : u8) b->reset();      // (all five go before the first comes back: the peak is one set)
+  c->st_disp.reset();
+  for(auto* b : u8) HIP_CK(c, b->alloc(npix));
+  HIP_CK(c, c->st_disp.alloc(npix));
   c->st_pixels = npix;
   return BPVO_OK;
 }
 static int stereo_scratch(bpvo_hip_ctx* c, size_t need)      // the semi-global matchers' scratch, at least `need` bytes
 {
-  if(need <= c->st_sgm_bytes) return BPVO_OK;
+  if(need <= c->st_sgm.size()) return BPVO_OK;
   HIP_CK(c, hipStreamSynchronize(c->stream));
-  (void) hipFree(c->st_sgm);
-  c->st_sgm = nullptr; c->st_sgm_bytes = 0;
-  HIP_CK(c, hipMalloc(&c->st_sgm, need));
-  c->st_sgm_bytes = need;
+  HIP_CK(c, c->st_sgm.reserve(need));
   return BPVO_OK;
 }
 static int seq_capacity(const bpvo_hip_ctx* c);
@@ -147,7 +141,7 @@ static int sgm_frames_per_launch(bpvo_hip_ctx* c, size_t per_frame, int count)
   if(c->st_sgm_budget == 0) {
     size_t free_b = 0, total_b = 0;
     if(hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void) hipGetLastError(); free_b = 0; }
-    c->st_free_seen = free_b + c->st_sgm_bytes;      // (a scratch this context already holds is given back before a larger one is taken)
+    c->st_free_seen = free_b + c->st_sgm.size();      // (a scratch this context already holds is given back before a larger one is taken)
     c->st_sgm_budget = std::max<size_t>(1, c->st_free_seen / 3);
   }
   int F = (int) std::min<size_t>((size_t) count, std::max<size_t>(1, c->st_sgm_budget / per_frame));
@@ -227,16 +221,14 @@ static int stereo_run_sizes(bpvo_hip_ctx* c, int n, const StereoSize* sz, const 
     launch_stereo_prefilter(c->stream, dl, c->st_left_pre, max_rows, max_cols, sp->preFilterCap, n);
     launch_stereo_prefilter(c->stream, dr, c->st_right_pre, max_rows, max_cols, sp->preFilterCap, n);
   } else {
-    if(n > c->st_tab_cap) {
+    if((size_t) n > c->h_st_frames.size()) {      // (the pinned table comes last: its size says that both are there)
       HIP_CK(c, hipStreamSynchronize(c->stream));
-      (void) hipFree(c->d_st_frames); (void) hipHostFree(c->h_st_frames);
-      c->d_st_frames = c->h_st_frames = nullptr; c->st_tab_cap = 0;
-      const int cap = std::max(n, seq_capacity(c));
-      HIP_CK(c, hipMalloc((void**) &c->d_st_frames, (size_t) cap * sizeof(StereoFrame)));
-      HIP_CK(c, hipHostMalloc((void**) &c->h_st_frames, (size_t) cap * sizeof(StereoFrame)));
-      c->st_tab_cap = cap;
+      c->d_st_frames.reset(); c->h_st_frames.reset();
+      const size_t cap = (size_t) std::max(n, seq_capacity(c));
+      HIP_CK(c, c->d_st_frames.alloc(cap));
+      HIP_CK(c, c->h_st_frames.alloc(cap));
     }
-    if(!c->st_tab_ev) HIP_CK(c, hipEventCreateWithFlags(&c->st_tab_ev, hipEventDisableTiming));
+    if(!c->st_tab_ev) HIP_CK(c, c->st_tab_ev.create(hipEventDisableTiming));
     else HIP_CK(c, hipEventSynchronize(c->st_tab_ev));      // (the last call's copy has read the pinned rows)
     size_t at = 0;
     for(int i = 0; i < n; ++i) {
@@ -577,17 +569,16 @@ static void seq_states(bpvo_hip_ctx* c)
 }
 static int seq_storage(bpvo_hip_ctx* c)
 {
-  if(c->h_seq_off) return BPVO_OK;      // (the last of the allocations below)
   const size_t S = (size_t) seq_capacity(c), cap = (size_t) c->geom[c->params.maxTestLevel].cap;
-  if(!c->d_seq_cloud) HIP_CK(c, hipMalloc((void**) &c->d_seq_cloud, S * cap * sizeof(bpvo_hip_point_with_info)));
-  if(!c->d_seq_jobs) HIP_CK(c, hipMalloc((void**) &c->d_seq_jobs, S * sizeof(PairJob)));
-  if(!c->h_seq_jobs) HIP_CK(c, hipHostMalloc((void**) &c->h_seq_jobs, S * sizeof(PairJob)));
-  if(!c->d_cloud_jobs) HIP_CK(c, hipMalloc((void**) &c->d_cloud_jobs, S * sizeof(CloudJob)));
-  if(!c->h_cloud_jobs) HIP_CK(c, hipHostMalloc((void**) &c->h_cloud_jobs, S * sizeof(CloudJob)));
-  if(!c->d_seq_cnt) HIP_CK(c, hipMalloc((void**) &c->d_seq_cnt, S * sizeof(unsigned)));
-  if(!c->h_seq_cnt) HIP_CK(c, hipHostMalloc((void**) &c->h_seq_cnt, S * sizeof(unsigned)));
-  if(!c->d_seq_off) HIP_CK(c, hipMalloc((void**) &c->d_seq_off, S * sizeof(size_t)));
-  if(!c->h_seq_off) HIP_CK(c, hipHostMalloc((void**) &c->h_seq_off, S * sizeof(size_t)));
+  if(!c->d_seq_cloud) HIP_CK(c, c->d_seq_cloud.alloc(S * cap));
+  if(!c->d_seq_jobs) HIP_CK(c, c->d_seq_jobs.alloc(S));
+  if(!c->h_seq_jobs) HIP_CK(c, c->h_seq_jobs.alloc(S));
+  if(!c->d_cloud_jobs) HIP_CK(c, c->d_cloud_jobs.alloc(S));
+  if(!c->h_cloud_jobs) HIP_CK(c, c->h_cloud_jobs.alloc(S));
+  if(!c->d_seq_cnt) HIP_CK(c, c->d_seq_cnt.alloc(S));
+  if(!c->h_seq_cnt) HIP_CK(c, c->h_seq_cnt.alloc(S));
+  if(!c->d_seq_off) HIP_CK(c, c->d_seq_off.alloc(S));
+  if(!c->h_seq_off) HIP_CK(c, c->h_seq_off.alloc(S));
   return BPVO_OK;
 }
 static int seq_fail(bpvo_hip_ctx* c, int code, int seq, const char* what)

@@ -819,6 +819,9 @@ int bpvo_hip_set_max_lanes(bpvo_hip_ctx* ctx, int n);
 /* diagnostics: Gauss-Newton state of a workspace after its last call: T (16), H (36), G (6), dp (6), f_norm, scale, delta_scale,
  * g_norm, pose of the last linearisation (16) */
 int bpvo_hip_debug_gn_state(bpvo_hip_ctx* ctx, int ws, float out[84]);
+/* diagnostics: what the library's contexts hold right now, process-wide: device buffers, pinned host buffers, streams, events (a
+ * context that has been destroyed, or whose creation failed, has given back all it took) */
+int bpvo_hip_debug_live_resources(int counts[4]);
 
 #ifdef __cplusplus
 }
