@@ -12,6 +12,7 @@ import os
 import numpy as np
 
 LOSS_HUBER, LOSS_TUKEY, LOSS_L2 = 0x10, 0x11, 0x12
+LOSS_STUDENT_T = 0x13      # an extension (c_api.h): t-distribution weights, nu = 5, the scale fitted on the device; libbpvo_hip only
 VERB_ITERATION, VERB_FINAL, VERB_SILENT, VERB_DEBUG = 0x20, 0x21, 0x22, 0x23
 DESC_INTENSITY, DESC_GRADIENT, DESC_LAPLACIAN, DESC_BITPLANES = 0x30, 0x31, 0x36, 0x37
 DESC_FIELDS1, DESC_FIELDS2, DESC_LATCH, DESC_CENTRAL_DIFFERENCE = 0x32, 0x33, 0x34, 0x35
@@ -1092,6 +1093,12 @@ class Context:
     def median_path_counts(self):
         a, b = C.c_uint64(), C.c_uint64()
         self.call("median_path_counts", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def tscale_counts(self):
+        """(runs of the Student-t scale stage, passes of its iteration) since the last counter reset (HIP library only)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self.call("tscale_counts", C.byref(a), C.byref(b))
         return a.value, b.value
 
     def fused_point_counts(self):

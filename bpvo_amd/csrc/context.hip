@@ -541,7 +541,8 @@ int create_impl(bpvo_hip_ctx** out, const float K[9], float baseline, int rows, 
      c->params.laplacianKernelSize != 5 && c->params.laplacianKernelSize != 7)
     return unsupported("laplacianKernelSize: 1, 3, 5 and 7 are on the device path (from 11 on OpenCV's f32 sums are no longer exact integers)");
   if(c->params.interp < BPVO_INTERP_LINEAR || c->params.interp > BPVO_INTERP_CUBIC_HERMITE) return unsupported("unknown interp");
-  if(c->params.lossFunction != BPVO_LOSS_HUBER && c->params.lossFunction != BPVO_LOSS_TUKEY && c->params.lossFunction != BPVO_LOSS_L2)
+  if(c->params.lossFunction != BPVO_LOSS_HUBER && c->params.lossFunction != BPVO_LOSS_TUKEY && c->params.lossFunction != BPVO_LOSS_L2 &&
+     c->params.lossFunction != BPVO_LOSS_STUDENT_T)
     return unsupported("unknown lossFunction");
   if(c->params.gradientEstimation != BPVO_GRAD_CD3 && c->params.gradientEstimation != BPVO_GRAD_CD5) return unsupported("unknown gradientEstimation");
   switch(c->params.descriptor) {

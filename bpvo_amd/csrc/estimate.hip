@@ -51,7 +51,7 @@ bool team_serves(const bpvo_hip_ctx* c, int n)
     const int busy = t.team_size * t.n_teams + t.spare_workgroups;
     size_ok = 20 * busy >= 19 * c->num_cus;
   }
-  return c->team_mode && c->persistent && !c->persistent_failed.load() && size_ok && !c->reference_reduction &&
+  return c->team_mode && c->persistent && !c->persistent_failed.load() && size_ok && !c->reference_reduction && !loss_is_chain_only(c->params.lossFunction) &&
          (c->C == 8 || c->C == 1) && c->params.interp == BPVO_INTERP_LINEAR && !c->fast_warp && !c->profile_all && !c->profile_k6_all &&
          c->num_cus >= 2 && g_live_ctx[c->device & 63].load() <= 1;
 }
@@ -175,7 +175,8 @@ static void group_modes(GroupRun& r, bool allow_persistent)
   r.ref_mode = c->reference_reduction != 0;
   r.fuse_frozen = r.ref_mode ? 0 : c->fuse_frozen;
   r.allow_persistent = allow_persistent;
-  r.pk_group = allow_persistent && c->persistent && !c->persistent_failed.load() && r.n <= c->persist_max_ws && !c->profile_all && !r.ref_mode;
+  r.pk_group = allow_persistent && c->persistent && !c->persistent_failed.load() && r.n <= c->persist_max_ws && !c->profile_all && !r.ref_mode &&
+               !loss_is_chain_only(r.loss);
   r.small_ctx = (size_t) c->L * c->n_pairs <= 64 && r.n <= 8 && c->small_batch_fused && c->G == 1;
   r.l2_moot = r.loss == BPVO_LOSS_L2 && c->C == 8 && r.fuse_frozen && !c->fast_warp && c->params.interp == BPVO_INTERP_LINEAR;
   r.team_ran = r.team_split = r.frac_queued = false;
@@ -508,7 +509,7 @@ int estimate_group(bpvo_hip_ctx* c, Lane* ln, int n, const int* wss, const int* 
   for(const bool persistent_forms : {allow_persistent, false}) {
     group_modes(r, persistent_forms);
     if(int rc = group_upload(r)) return rc;
-    if(persistent_forms && ln == &c->lanes[0] && team_serves(c, n) && templates_suit_teams(c, n, refs))
+    if(persistent_forms && ln == &c->lanes[0] && !loss_is_chain_only(r.loss) && team_serves(c, n) && templates_suit_teams(c, n, refs))
       if(int rc = run_team(r)) return rc;
     if(!r.team_ran)
       if(int rc = run_levels(r)) return rc;
@@ -539,7 +540,7 @@ int check_pairs(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const i
 }
 
 // Entries with parameters of their own (bpvo_hip_add_frames): the loss is a template parameter of the reduction, persistent and team kernels, so
-// the entries of a call are PARTITIONED by loss — at most three estimates, one per loss present and never one per sequence, each over the
+// the entries of a call are PARTITIONED by loss — at most four estimates, one per loss present and never one per sequence, each over the
 // entries of that loss in call order; everything else a sequence may own travels in its jobs.  One loss (every call without per-sequence
 // parameters): the one estimate there has always been.  (The alternative, a loss read per workspace inside the kernels: DESIGN.md §5.)
 static int estimate_one_loss(bpvo_hip_ctx* c, int n, const int* wss, const int* refs, const int* curs, const float* T_init, float* poses, bpvo_hip_stats* stats,
@@ -579,7 +580,8 @@ static int estimate_one_loss(bpvo_hip_ctx* c, int n, const int* wss, const int* 
   if(int rc = check_pairs(c, n, wss, refs, curs, 0, -1)) return rc;
   int nl = lanes_for(c, n, 8);
   if(nl < 0) return nl;
-  if(team_serves(c, n) && templates_suit_teams(c, n, refs)) nl = 1;      // the team-persistent kernel takes the whole chip
+  const int loss = prms ? prms[0]->lossFunction : p.lossFunction;      // (one loss per call of this function: estimate_batch)
+  if(!loss_is_chain_only(loss) && team_serves(c, n) && templates_suit_teams(c, n, refs)) nl = 1;      // the team-persistent kernel takes the whole chip
   // frame stages run on the ctx stream: the other lanes' streams start from a quiet device.  A single lane IS the ctx stream — its
   // launches simply queue behind the frame stage (sequential addFrame: ~30 us of idle device per frame otherwise).
   if(nl > 1) {
@@ -640,6 +642,7 @@ int refresh_counters(bpvo_hip_ctx* c)
     for(int k = 0; k < kWsCounters; ++k) h[k] += all[kWsCounters * (size_t) w + k];
   c->median_bracketed = h[2];
   c->median_full = h[3];
+  c->tscale_passes = h[9]; c->tscale_stages = h[11];
   for(int k = 0; k < 4; ++k) c->tap_counts[k] = h[5 + k];
   c->total_lin = h[1];
   // units of the GN kernels = points linearised (device-side count: only the pairs still active in a launch count)

@@ -22,6 +22,11 @@ __device__ __forceinline__ float mest_curvature(float r, float sigma_inv)
     float q = x * t_i;
     q = q * q;
     return (fabsf(x) < t) ? (1.0f - q) * (1.0f - 5.0f * q) : 0.0f;
+  } else if(LOSS == BPVO_LOSS_STUDENT_T) {      // psi(u) = 6 u / (5 + u^2): psi'(u) = 6 (5 - u^2) / (5 + u^2)^2, negative beyond |u| = sqrt(5)
+    const float x = r * sigma_inv;
+    const float x2 = x * x;
+    const float den = 5.0f + x2;
+    return (6.0f * (5.0f - x2)) / (den * den);
   }
   return 1.0f;
 }

@@ -43,6 +43,9 @@ __device__ __forceinline__ float mest_weight(float r, float sigma_inv)
     q = 1.0f - q * q;
     q = q * q;
     return (fabsf(x) < t) ? q : 0.0f;
+  } else if(LOSS == BPVO_LOSS_STUDENT_T) {      // (nu + 1) / (nu + x^2), nu = 5 (c_api.h): in (0, 1.2]
+    const float x = r * sigma_inv;
+    return 6.0f / (5.0f + x * x);
   }
   return 1.0f;
 }

@@ -390,6 +390,7 @@ struct bpvo_hip_ctx {
   double kc_units[KC_COUNT] = {};
   uint64_t kc_launches[KC_COUNT] = {};
   uint64_t total_lin = 0, median_bracketed = 0, median_full = 0;
+  uint64_t tscale_stages = 0, tscale_passes = 0;      // runs of the Student-t scale stage and the passes of its iteration (PairJob::cnt[11], [9])
   uint64_t tap_counts[4] = {};
   std::mutex units_mu;         // kc_units updates of concurrent frame stages
   std::string err;
@@ -573,13 +574,16 @@ inline bool templates_may_be_dense(const bpvo_hip_ctx* c)
     if(c->geom[l].nms_radius <= 0 && c->geom[l].npix > (size_t) std::max(0, c->persist_max_points)) return true;
   return false;
 }
+// The Student-t loss (c_api.h) runs on the four-kernel chain only: its scale stage (tscale_kernel) stands in the chain's median launch, and neither the
+// persistent nor the team kernels are built for it — what reference_reduction is to the context, this is to a group's loss.
+inline bool loss_is_chain_only(int loss) { return loss == BPVO_LOSS_STUDENT_T; }
 // will the estimate of ONE pair be a handful of launches — the persistent kernel, a launch per pyramid level — queued in one go?  (Then the host is free
 // while the GPU works, and addFrame uploads its frame's disparity in that time: vo.hip.  On the chain the host paces the rounds, and the upload's hold on
 // it costs more behind the last round than in front of the first: conf/tsukuba.cfg's parameters 2.9 -> 3.2 ms per frame.)
 inline bool single_pair_is_queued_at_once(const bpvo_hip_ctx* c)
 {
-  return c->persistent && !c->persistent_failed.load() && !c->profile_all && !c->reference_reduction && (c->C == 8 || c->C == 1) &&
-         c->params.interp == BPVO_INTERP_LINEAR && !c->fast_warp && !templates_may_be_dense(c);
+  return c->persistent && !c->persistent_failed.load() && !c->profile_all && !c->reference_reduction && !loss_is_chain_only(c->params.lossFunction) &&
+         (c->C == 8 || c->C == 1) && c->params.interp == BPVO_INTERP_LINEAR && !c->fast_warp && !templates_may_be_dense(c);
 }
 inline int dense_candidates(const bpvo_hip_ctx* c, int max_points) { return (c->G == 1 && max_points >= c->dense_candidates_from) ? 1 : 0; }
 inline bpvo_hip::GNLaunch median_launch(const bpvo_hip_ctx* c, bpvo_hip::GNLaunch g) { if(c->G > 1) g.C = c->Cg; return g; }

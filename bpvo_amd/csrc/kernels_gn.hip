@@ -21,6 +21,7 @@
 #include "gn_common.h"
 #include "gn_warp.h"
 #include "gn_median.h"
+#include "gn_tscale.h"
 #include "gn_irls.h"
 #include "gn_step.h"
 
@@ -301,6 +302,19 @@ __global__ __launch_bounds__(NT) void median_finish_kernel(const PairJob* __rest
   median_block<C, NT, COPIES, CACHE>(j, st, smem_raw, true, dense != 0);
 }
 
+// K7t: the scale of the Student-t loss in the median's place (gn_tscale.h) — one workgroup per workspace, the same gate, the same two shapes (the
+// bits do not depend on which one ran).  16 KB of LDS: the residuals are re-read from L2 pass by pass, not staged.
+template <int C, int NT>
+__global__ __launch_bounds__(NT) void tscale_kernel(const PairJob* __restrict__ jobs, ActiveSet act)
+{
+  const PairJob& j = jobs[active_workspace(act, blockIdx.x)];
+  GNState* st = j.st;
+  if(!st->active) return;
+  if(!(st->delta_scale > 1e-6f)) return;   // frozen for the rest of the level, as the median's scale is
+  __shared__ TScaleLds s;
+  tscale_block<C, NT>(j, st, s);
+}
+
 // Two instantiations share the work of a launch slot: FUSED = false handles the workspaces whose scale still moves, FUSED =
 // true (136 VGPRs instead of 103: kept out of the plain kernel's register budget) the frozen ones.
 // step.on (only without fuse_frozen, where one launch serves every workspace): the last tile of a workspace takes the Gauss-Newton
@@ -504,7 +518,8 @@ __global__ __launch_bounds__(256) void weights_kernel(const PairJob* job, float*
 // ... and for descriptors of more than 48 channels (point-major records of C floats, run-time channel loop)
 __device__ __forceinline__ float mest_weight_rt(int loss, float r, float sigma_inv)
 {
-  return loss == BPVO_LOSS_HUBER ? mest_weight<BPVO_LOSS_HUBER>(r, sigma_inv) : loss == BPVO_LOSS_TUKEY ? mest_weight<BPVO_LOSS_TUKEY>(r, sigma_inv) : 1.0f;
+  return loss == BPVO_LOSS_HUBER ? mest_weight<BPVO_LOSS_HUBER>(r, sigma_inv) : loss == BPVO_LOSS_TUKEY ? mest_weight<BPVO_LOSS_TUKEY>(r, sigma_inv) :
+         loss == BPVO_LOSS_STUDENT_T ? mest_weight<BPVO_LOSS_STUDENT_T>(r, sigma_inv) : 1.0f;
 }
 __global__ __launch_bounds__(256) void weights_wide_kernel(const PairJob* job, int C, int loss, float* w_out /*[n][C] point-major*/)
 {
@@ -732,6 +747,15 @@ void launch_refresh_residuals(hipStream_t s, const GNLaunch& g)
 void launch_median(hipStream_t s, const GNLaunch& g)
 {
   if(g.max_points <= 0) return;
+  constexpr int wide_from = 257;      // launches of more workgroups than CUs take the 512-thread shape (profiles/r02_median_shapes.txt, r03_shard_ab_lanes_median.txt)
+  if(g.loss == BPVO_LOSS_STUDENT_T) {      // the t-distribution's scale is fitted, not selected
+    dispatch_channels(g.C, [&](auto c) {
+      constexpr int CC = decltype(c)::value;
+      if(g.npairs >= wide_from) hipLaunchKernelGGL((tscale_kernel<CC, MED_THREADS_B>), dim3(g.npairs), dim3(MED_THREADS_B), 0, s, g.jobs, g.active);
+      else hipLaunchKernelGGL((tscale_kernel<CC, MED_THREADS>), dim3(g.npairs), dim3(MED_THREADS), 0, s, g.jobs, g.active);
+    });
+    return;
+  }
   // the attribute is per device (a process may hold contexts on several) and the lanes' host threads race here
   static std::once_flag attr_once[64];
   int dev = 0;
@@ -744,7 +768,6 @@ void launch_median(hipStream_t s, const GNLaunch& g)
         (void) hipFuncSetAttribute((const void*) median_finish_kernel<CC, MED_THREADS_B, MED_COPIES_B, MED_CACHE_B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) kMedianLdsB);
       });
   });
-  constexpr int wide_from = 257;      // launches of more workgroups than CUs take the 512-thread shape (profiles/r02_median_shapes.txt, r03_shard_ab_lanes_median.txt)
   dispatch_channels(g.C, [&](auto c) {
     constexpr int CC = decltype(c)::value;
     if(g.npairs >= wide_from)
@@ -766,6 +789,7 @@ static void launch_irls_c(hipStream_t s, const GNLaunch& g, int ppb)
       switch(g.loss) {
         case BPVO_LOSS_HUBER: hipLaunchKernelGGL((irls_reduce_both_kernel<BPVO_LOSS_HUBER>), grid, dim3(GN_BLOCK), 0, s, g.jobs, g.active, ppb, step); break;
         case BPVO_LOSS_TUKEY: hipLaunchKernelGGL((irls_reduce_both_kernel<BPVO_LOSS_TUKEY>), grid, dim3(GN_BLOCK), 0, s, g.jobs, g.active, ppb, step); break;
+        case BPVO_LOSS_STUDENT_T: hipLaunchKernelGGL((irls_reduce_both_kernel<BPVO_LOSS_STUDENT_T>), grid, dim3(GN_BLOCK), 0, s, g.jobs, g.active, ppb, step); break;
         default: hipLaunchKernelGGL((irls_reduce_both_kernel<BPVO_LOSS_L2>), grid, dim3(GN_BLOCK), 0, s, g.jobs, g.active, ppb, step); break;
       }
       return;
@@ -774,6 +798,7 @@ static void launch_irls_c(hipStream_t s, const GNLaunch& g, int ppb)
   switch(g.loss) {
     case BPVO_LOSS_HUBER: hipLaunchKernelGGL((irls_reduce_kernel<C, BPVO_LOSS_HUBER, false>), grid, dim3(GN_BLOCK), 0, s, g.jobs, g.active, ppb, fuse, step); break;
     case BPVO_LOSS_TUKEY: hipLaunchKernelGGL((irls_reduce_kernel<C, BPVO_LOSS_TUKEY, false>), grid, dim3(GN_BLOCK), 0, s, g.jobs, g.active, ppb, fuse, step); break;
+    case BPVO_LOSS_STUDENT_T: hipLaunchKernelGGL((irls_reduce_kernel<C, BPVO_LOSS_STUDENT_T, false>), grid, dim3(GN_BLOCK), 0, s, g.jobs, g.active, ppb, fuse, step); break;
     default: hipLaunchKernelGGL((irls_reduce_kernel<C, BPVO_LOSS_L2, false>), grid, dim3(GN_BLOCK), 0, s, g.jobs, g.active, ppb, fuse, step); break;
   }
 }
@@ -806,6 +831,7 @@ static void launch_weights_c(hipStream_t s, const PairJob* job, int n, int loss,
   switch(loss) {
     case BPVO_LOSS_HUBER: hipLaunchKernelGGL((weights_kernel<C, BPVO_LOSS_HUBER>), grid, dim3(256), 0, s, job, w_out); break;
     case BPVO_LOSS_TUKEY: hipLaunchKernelGGL((weights_kernel<C, BPVO_LOSS_TUKEY>), grid, dim3(256), 0, s, job, w_out); break;
+    case BPVO_LOSS_STUDENT_T: hipLaunchKernelGGL((weights_kernel<C, BPVO_LOSS_STUDENT_T>), grid, dim3(256), 0, s, job, w_out); break;
     default: hipLaunchKernelGGL((weights_kernel<C, BPVO_LOSS_L2>), grid, dim3(256), 0, s, job, w_out); break;
   }
 }
@@ -821,6 +847,7 @@ static void launch_count_good_c(hipStream_t s, const PairJob* jobs, dim3 grid, i
   switch(loss) {
     case BPVO_LOSS_HUBER: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_HUBER>), grid, dim3(256), 0, s, jobs, thr, counts); break;
     case BPVO_LOSS_TUKEY: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_TUKEY>), grid, dim3(256), 0, s, jobs, thr, counts); break;
+    case BPVO_LOSS_STUDENT_T: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_STUDENT_T>), grid, dim3(256), 0, s, jobs, thr, counts); break;
     default: hipLaunchKernelGGL((count_good_kernel<C, BPVO_LOSS_L2>), grid, dim3(256), 0, s, jobs, thr, counts); break;
   }
 }

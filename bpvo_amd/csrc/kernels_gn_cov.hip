@@ -159,6 +159,7 @@ static void launch_pose_cov_reduce_c(hipStream_t s, const CovLaunch& g, int ppb)
   switch(g.loss) {
     case BPVO_LOSS_HUBER: hipLaunchKernelGGL((pose_cov_reduce_kernel<C, BPVO_LOSS_HUBER>), grid, dim3(GN_BLOCK), 0, s, g.jobs, ppb); break;
     case BPVO_LOSS_TUKEY: hipLaunchKernelGGL((pose_cov_reduce_kernel<C, BPVO_LOSS_TUKEY>), grid, dim3(GN_BLOCK), 0, s, g.jobs, ppb); break;
+    case BPVO_LOSS_STUDENT_T: hipLaunchKernelGGL((pose_cov_reduce_kernel<C, BPVO_LOSS_STUDENT_T>), grid, dim3(GN_BLOCK), 0, s, g.jobs, ppb); break;
     default: hipLaunchKernelGGL((pose_cov_reduce_kernel<C, BPVO_LOSS_L2>), grid, dim3(GN_BLOCK), 0, s, g.jobs, ppb); break;
   }
 }

@@ -26,6 +26,7 @@ __device__ __forceinline__ float ref_weight(int loss, float r, float sigma_inv)
   switch(loss) {
     case BPVO_LOSS_HUBER: return mest_weight<BPVO_LOSS_HUBER>(r, sigma_inv);
     case BPVO_LOSS_TUKEY: return mest_weight<BPVO_LOSS_TUKEY>(r, sigma_inv);
+    case BPVO_LOSS_STUDENT_T: return mest_weight<BPVO_LOSS_STUDENT_T>(r, sigma_inv);
     default: return 1.0f;
   }
 }

@@ -966,7 +966,8 @@ __global__ __launch_bounds__(PK_THREADS) void gn_team_kernel(const PairJob* __re
 // ---- persistent kernel for small groups
 bool gn_persistent_serves(const GNLaunch& g)
 {
-  return (g.C == 8 || g.C == 1) && g.interp == BPVO_INTERP_LINEAR && !g.fast_warp && g.npairs >= 1 && g.npairs <= kPersistMaxWs && !g.active.list;
+  return (g.C == 8 || g.C == 1) && g.interp == BPVO_INTERP_LINEAR && !g.fast_warp && g.npairs >= 1 && g.npairs <= kPersistMaxWs && !g.active.list &&
+         g.loss != BPVO_LOSS_STUDENT_T;      // (the t-scale stage exists on the chain only)
 }
 int gn_persistent_grid(const GNLaunch& g, int max_grid)
 {
@@ -1001,6 +1002,7 @@ static hipError_t pk_with_loss(int loss, F&& f)
   switch(loss) {
     case BPVO_LOSS_HUBER: return f(std::integral_constant<int, BPVO_LOSS_HUBER>());
     case BPVO_LOSS_TUKEY: return f(std::integral_constant<int, BPVO_LOSS_TUKEY>());
+    case BPVO_LOSS_STUDENT_T: return hipErrorInvalidValue;      // never reached: the Student-t loss stays on the chain (gn_persistent_serves, loss_is_chain_only) and no persistent kernel is built for it
     default: return f(std::integral_constant<int, BPVO_LOSS_L2>());
   }
 }

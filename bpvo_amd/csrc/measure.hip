@@ -92,6 +92,18 @@ int bpvo_hip_median_path_counts(bpvo_hip_ctx* c, uint64_t* bracketed, uint64_t* 
   *full = c->median_full;
   return BPVO_OK;
 }
+int bpvo_hip_tscale_counts(bpvo_hip_ctx* c, uint64_t* stages, uint64_t* passes)
+{
+  CHECK_CTX(c);
+  if(!stages || !passes) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr counts");
+  (void) hipSetDevice(c->device);
+  HIP_CK(c, hipStreamSynchronize(c->stream));
+  int rc = refresh_counters(c);
+  if(rc) return rc;
+  *stages = c->tscale_stages;
+  *passes = c->tscale_passes;
+  return BPVO_OK;
+}
 int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* c, uint64_t out[4])
 {
   CHECK_CTX(c);

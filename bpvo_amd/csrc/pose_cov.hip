@@ -92,7 +92,7 @@ int pose_cov_pass(bpvo_hip_ctx* c, int n_records, int members, const int* wss, c
   for(int first = 0; first < n_records; first += per_group) {
     const int nr = std::min(per_group, n_records - first), nm = nr * members;
     int max_points = 0;
-    unsigned losses = 0;      // bit 0 Huber, 1 Tukey, 2 L2: the losses present in the group (one launch of the reduction each)
+    unsigned losses = 0;      // bit 0 Huber, 1 Tukey, 2 L2, 3 Student-t: the losses present in the group (one launch of the reduction each)
     for(int m = 0; m < nm; ++m) {
       const int e = first * members + m;
       PairJob& pj = h_jobs[m];
@@ -109,7 +109,7 @@ int pose_cov_pass(bpvo_hip_ctx* c, int n_records, int members, const int* wss, c
       pj.tapkey = nullptr; pj.tapcache = nullptr; pj.cand = nullptr; pj.med_blk = nullptr; pj.ticket = nullptr;
       pj.trace = nullptr; pj.trace_cap = 0;
       max_points = std::max(max_points, pj.n);
-      losses |= pj.loss == BPVO_LOSS_HUBER ? 1u : pj.loss == BPVO_LOSS_TUKEY ? 2u : 4u;
+      losses |= pj.loss == BPVO_LOSS_HUBER ? 1u : pj.loss == BPVO_LOSS_TUKEY ? 2u : pj.loss == BPVO_LOSS_STUDENT_T ? 8u : 4u;
       if(sigma) h_sigma[m] = sigma[e];
     }
     if(T) std::memcpy(h_T, T + 16 * (size_t) first, sizeof(float) * 16 * (size_t) nr);
@@ -132,9 +132,9 @@ int pose_cov_pass(bpvo_hip_ctx* c, int n_records, int members, const int* wss, c
     LinearizeFlags warp_only;
     warp_only.median = warp_only.reduce = warp_only.step = false;
     linearize_launches(c, &c->lanes[0], w, 0, warp_only);      // (lane 0 is the context's stream)
-    for(int b = 0; b < 3; ++b)
+    for(int b = 0; b < 4; ++b)
       if(losses & (1u << b)) {
-        g.loss = b == 0 ? BPVO_LOSS_HUBER : b == 1 ? BPVO_LOSS_TUKEY : BPVO_LOSS_L2;
+        g.loss = b == 0 ? BPVO_LOSS_HUBER : b == 1 ? BPVO_LOSS_TUKEY : b == 2 ? BPVO_LOSS_L2 : BPVO_LOSS_STUDENT_T;
         launch_pose_cov_reduce(s, g);
       }
     launch_pose_cov_finish(s, g);

@@ -207,7 +207,7 @@ struct PairJob {
                            // [2] bracketed / [3] full median selections, [4] points processed by warp_residual (the rest
                            // went through the fused path of irls_reduce), [5] tap-cache hits / [6] lookups (= valid points),
                            // [7] / [8] the same over the first 8 linearisations of a level, [10] points linearised through the
-                           // fused path; written by one thread each: no atomics
+                           // fused path, [9] passes / [11] runs of the Student-t scale stage (gn_tscale.h); written by one thread each: no atomics
   GPtr<GNState> st;
   GPtr<unsigned> ticket;   // tiles of the running irls_reduce launch that have stored their partial (the last one takes the step; back to 0 by then)
   // per-linearisation trace of the Gauss-Newton run (bpvo_hip_estimate_pose_trace; null otherwise): trace_cap records of

@@ -1382,7 +1382,7 @@ int bpvo_hip_seq_set_params(bpvo_hip_ctx* c, int seq, const bpvo_hip_params* p)
   if(rc) return rc;
   std::string why;
   if(structural_difference(c, seq, *p, &why)) return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, why.c_str());
-  if(p->lossFunction != BPVO_LOSS_HUBER && p->lossFunction != BPVO_LOSS_TUKEY && p->lossFunction != BPVO_LOSS_L2)
+  if(p->lossFunction != BPVO_LOSS_HUBER && p->lossFunction != BPVO_LOSS_TUKEY && p->lossFunction != BPVO_LOSS_L2 && p->lossFunction != BPVO_LOSS_STUDENT_T)
     return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, "unknown lossFunction");      // (bpvo_hip_create's answer)
   seq_states(c);
   SeqState& q = c->seqs[seq];
@@ -1411,7 +1411,7 @@ int bpvo_hip_rigs_set_params(bpvo_hip_ctx* c, int rig, const bpvo_hip_params* p)
   std::string why;
   for(int s : g.seq)
     if(structural_difference(c, s, *p, &why)) return fail(c, BPVO_ERR_UNSUPPORTED, ("rig " + std::to_string(rig) + ": " + why).c_str());
-  if(p->lossFunction != BPVO_LOSS_HUBER && p->lossFunction != BPVO_LOSS_TUKEY && p->lossFunction != BPVO_LOSS_L2)
+  if(p->lossFunction != BPVO_LOSS_HUBER && p->lossFunction != BPVO_LOSS_TUKEY && p->lossFunction != BPVO_LOSS_L2 && p->lossFunction != BPVO_LOSS_STUDENT_T)
     return fail(c, BPVO_ERR_UNSUPPORTED, ("rig " + std::to_string(rig) + ": unknown lossFunction").c_str());
   g.body.params = *p;
   g.body.own_params = params_differ_where_read(*p, c->params);

@@ -32,7 +32,33 @@ extern "C" {
 #endif
 
 /* ---- enums: numeric values equal to the reference's (bpvo/types.h:127-169,418-441) */
-enum { BPVO_LOSS_HUBER = 0x10, BPVO_LOSS_TUKEY = 0x11, BPVO_LOSS_L2 = 0x12 };
+enum { BPVO_LOSS_HUBER = 0x10, BPVO_LOSS_TUKEY = 0x11, BPVO_LOSS_L2 = 0x12,
+       BPVO_LOSS_STUDENT_T = 0x13      /* an extension, no reference member: defined below */ };
+/* ---- BPVO_LOSS_STUDENT_T = 0x13 (an extension, no reference member): the t-distribution weights of Kerl, Sturm and Cremers (ICRA 2013) with nu = 5
+ * fixed, and a scale that is fitted to the residuals in the place of the MAD.  There is no new parameter, and bpvo_hip_params keeps its layout.
+ * Let R be the multiset of residuals r[i][c] of the valid points of a workspace.  Valid flags and residuals are exactly those of bpvo_hip_get_valid /
+ * bpvo_hip_get_residuals.  Let n = C * #valid and m = #{r in R : r != 0}.
+ * Map.  T(s) = ((nu + 1) / n) * sum_R r^2 * s / (nu * s + r^2) for s > 0.  This form has no division by zero at r = 0.  T is increasing and concave;
+ *   its slope at a fixed point is (nu + 1) * mean(a^2) < 1, with a = r^2 / (nu * s + r^2) and mean(a) = 1 / (nu + 1); so a positive fixed point s* is
+ *   unique, and plain iteration converges to it monotonically from any s > 0.  It exists if and only if (nu + 1) * m > n, because
+ *   T(s) / s -> (nu + 1) m / n as s -> 0.
+ * Scale.  If n == 0, or (nu + 1) * m <= n, or the result is below 1e-6, then sigma = 1 (the reference's own answer to a vanishing scale,
+ *   mestimator.cc:452-490); the delta stored with it is |1 - sigma_prev|, as the median stage stores it.  Otherwise sigma_k = sqrt(s_k) with
+ *   s_{k+1} = T(s_k).  Start: s_0 = sigma_prev^2 when this level already holds an estimated scale; on the first linearisation of a level, or after
+ *   reset_scale, s_0 = mean r^2.  Stop: the first k with |sigma_{k+1} - sigma_k| <= 1e-4 * sigma_k, or k + 1 = 64 (a termination guard).  The result
+ *   is sigma_{k+1}.
+ * Freeze.  If the first pass from sigma_prev already satisfies the stop rule, the scale is frozen for the rest of the level: it keeps sigma_prev bit
+ *   for bit.  Otherwise the scale is sigma_{k+1} and the level goes on estimating it.  (The state machine is the one of the other losses: a frozen
+ *   scale is what lets the fused frozen-scale reduction serve the late iterations.)
+ * Arithmetic.  Terms are f32; the residuals are summed in tiles of a fixed number of points (a function of the point index alone, never of the launch
+ *   shape, the batch or the place in the active set), each point's channels in channel order, in f64, and the tiles are combined in a fixed order in
+ *   f64; the iteration and the stop rule are f64.  Consequently sigma is the same bits wherever the same workspace history is replayed.
+ * Weight.  x = r * sigma_inv; w = 6.0f / (5.0f + x * x), in f32, the operations in that order; w in (0, 1.2].  goodPointThreshold keeps its meaning
+ *   (w > thr): at the default 0.75 that is |x| < 1.73, where Tukey's is |x| < 1.71.
+ * Covariance.  d(u) = psi'(u) = 6 * (5 - u^2) / (5 + u^2)^2 — negative beyond |u| = sqrt(5), as Tukey's is beyond its own bend; BPVO_COV_INDEFINITE
+ *   covers that.
+ * Paths.  Estimates with this loss run on the four-kernel chain (the persistent and team kernels are not built for it): single contexts, sequences,
+ *   stereo sequences and rigs. */
 enum { BPVO_VERB_ITERATION = 0x20, BPVO_VERB_FINAL = 0x21, BPVO_VERB_SILENT = 0x22, BPVO_VERB_DEBUG = 0x23 };
 enum { BPVO_DESC_INTENSITY = 0x30, BPVO_DESC_INTENSITY_AND_GRADIENT = 0x31, BPVO_DESC_FIELDS_FIRST_ORDER = 0x32,
        BPVO_DESC_FIELDS_SECOND_ORDER = 0x33, BPVO_DESC_LATCH = 0x34, BPVO_DESC_CENTRAL_DIFFERENCE = 0x35, BPVO_DESC_LAPLACIAN = 0x36, BPVO_DESC_BITPLANES = 0x37 };
@@ -515,7 +541,8 @@ int bpvo_hip_estimate_pose_rigs(bpvo_hip_ctx* ctx, int n_rigs, const int* count 
  * is valid for the estimate as it is in the reference, but it says nothing about the pose's uncertainty; num_valid counts the v_p of this rule — and
  * J_pc the 1x6 Jacobian row of point p, channel c in the level's Hartley-normalised twist (the J of bpvo_hip_get_jacobians):
  *   curvature         M = sum_p v_p sum_c d(u_pc) J_pc^T J_pc,  d = psi':  kL2 d = 1;  Huber d = 1 where |u| <= 1.345 (exactly where w = 1), else 0;
- *                     Tukey, q = (u / 4.685)^2: d = (1 - q)(1 - 5 q) where |u| < 4.685, else 0
+ *                     Tukey, q = (u / 4.685)^2: d = (1 - q)(1 - 5 q) where |u| < 4.685, else 0;
+ *                     Student-t (BPVO_LOSS_STUDENT_T): d = 6 (5 - u^2) / (5 + u^2)^2
  *   score covariance  Q = sum_p v_p g_p^T g_p,  g_p = sum_c w(u_pc) r_pc J_pc — the channels of a point are ONE cluster (they see the same pixel
  *                     neighbourhood); sum_p g_p is the G of bpvo_hip_linearize_at_scale at the same pose and scale
  *   Sigma_xi = M^-1 Q M^-1 — no sigma^2 factor, no finite-sample factor —, and in the plain twist Sigma = A Sigma_xi A^T with
@@ -531,7 +558,7 @@ int bpvo_hip_estimate_pose_rigs(bpvo_hip_ctx* ctx, int n_rigs, const int* count 
  * factor of 1.7 - 2.3 in standard deviation (census 3x3 and the 5x5 blur correlate neighbouring points, which no per-point form can see):
  * INTEGRATION.md section 4, profiles/pose_covariance_calibration.json.  It is the uncertainty of the alignment given the template, not of the
  * template's depth.
- * status: BPVO_COV_OK; BPVO_COV_INDEFINITE — the LDL^T of the curvature met a pivot <= 0 (Tukey away from a minimum); BPVO_COV_DEGENERATE — fewer
+ * status: BPVO_COV_OK; BPVO_COV_INDEFINITE — the LDL^T of the curvature met a pivot <= 0 (Tukey or Student-t away from a minimum); BPVO_COV_DEGENERATE — fewer
  * than 6 valid points in total, or a sum that is not finite; BPVO_COV_NONE — nothing was estimated (a first frame, a batch pair whose finest level
  * was skipped).  Anything but OK leaves `covariance` at the Identity.  No status is an error return, and no pose raises. */
 enum { BPVO_COV_OK = 0, BPVO_COV_INDEFINITE = 1, BPVO_COV_DEGENERATE = 2, BPVO_COV_NONE = 3 };
@@ -698,6 +725,10 @@ int bpvo_hip_get_kernel_stats(bpvo_hip_ctx* ctx, bpvo_hip_kernel_stat* out, int 
 int bpvo_hip_total_linearizations(bpvo_hip_ctx* ctx, uint64_t* n);  /* GN iterations done since create/reset */
 /* exact median selections served by the bracketed path / by the full 3-pass path since the last counter reset */
 int bpvo_hip_median_path_counts(bpvo_hip_ctx* ctx, uint64_t* bracketed, uint64_t* full);
+/* BPVO_LOSS_STUDENT_T since the last counter reset: runs of the scale stage (linearisations whose scale was not frozen) and the passes of the
+ * iteration over them.  The median-path counts above do not move for such workspaces, and the tap-cache counts (which the median stage folds in
+ * from its bracket counters) are not kept for them. */
+int bpvo_hip_tscale_counts(bpvo_hip_ctx* ctx, uint64_t* stages, uint64_t* passes);
 /* points linearised since the last counter reset: `fused` of `total` went through the fused residual + reduction path that
  * irls_reduce takes once a workspace's robust scale is frozen for the level (warp_residual skips those workspaces) */
 int bpvo_hip_fused_point_counts(bpvo_hip_ctx* ctx, uint64_t* fused, uint64_t* total);

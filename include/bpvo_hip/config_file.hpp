@@ -99,6 +99,7 @@ inline LossFunctionType LossFunctionTypeFromString(const std::string& s)
   if(icompare("Huber", s)) return kHuber;
   if(icompare("Tukey", s)) return kTukey;
   if(icompare("L2", s)) return kL2;
+  if(icompare("StudentT", s)) return kStudentT;      // (an extension: c_api.h BPVO_LOSS_STUDENT_T)
   throw Error("unknown LossFunctionType");
 }
 inline InterpolationType InterpolationTypeFromString(const std::string& s)
@@ -182,7 +183,7 @@ inline AlgorithmParameters AlgorithmParametersFromFile(const std::string& filena
 /* ToString (reference: bpvo/types.cc:109-264) — the strings the apps print, spelling included ("CenteralDifference") */
 inline std::string ToString(LossFunctionType t)
 {
-  switch(t) { case kHuber: return "Huber"; case kTukey: return "Tukey"; case kL2: return "L2"; }
+  switch(t) { case kHuber: return "Huber"; case kTukey: return "Tukey"; case kL2: return "L2"; case kStudentT: return "StudentT"; }
   return "Unknown";
 }
 inline std::string ToString(VerbosityType v)

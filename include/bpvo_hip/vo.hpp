@@ -43,7 +43,8 @@ typedef std::array<float, 4> Point;                             // (X, Y, Z, 1) 
 typedef std::vector<Point> PointVector;
 typedef std::vector<float> WeightsVector;
 
-enum LossFunctionType { kHuber = BPVO_LOSS_HUBER, kTukey = BPVO_LOSS_TUKEY, kL2 = BPVO_LOSS_L2 };
+enum LossFunctionType { kHuber = BPVO_LOSS_HUBER, kTukey = BPVO_LOSS_TUKEY, kL2 = BPVO_LOSS_L2,
+                        kStudentT = BPVO_LOSS_STUDENT_T /* an extension: c_api.h */ };
 enum VerbosityType { kIteration = BPVO_VERB_ITERATION, kFinal, kSilent, kDebug };
 /* all eight values of the reference (bpvo/types.h:142-152), all on the device path */
 enum DescriptorType { kIntensity = BPVO_DESC_INTENSITY, kIntensityAndGradient, kDescriptorFieldsFirstOrder, kDescriptorFieldsSecondOrder,
