@@ -127,6 +127,25 @@ def _as_camera(c) -> Camera:
     return c if isinstance(c, Camera) else camera(*c)
 
 
+class Lens(C.Structure):
+    """bpvo_hip_lens: the raw camera of one side (intrinsics, Brown-Conrady k1 k2 p1 p2 k3 k4 k5 k6, the rotation raw -> rectified, the raw size)."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 8), ("R", C.c_double * 9),
+                ("raw_rows", C.c_int), ("raw_cols", C.c_int)]
+
+
+assert C.sizeof(Lens) == 21 * 8 + 2 * 4
+
+
+def lens(K4, dist, R, raw_rows, raw_cols) -> Lens:
+    """A Lens from (fx, fy, cx, cy), eight distortion coefficients, a 3x3 rotation and the raw image size."""
+    q = Lens()
+    q.fx, q.fy, q.cx, q.cy = [float(v) for v in K4]
+    q.dist[:] = [float(v) for v in np.asarray(dist, dtype=np.float64).reshape(8)]
+    q.R[:] = [float(v) for v in np.asarray(R, dtype=np.float64).reshape(9)]
+    q.raw_rows, q.raw_cols = int(raw_rows), int(raw_cols)
+    return q
+
+
 def pack_frames(images, disps):
     """Frames of possibly different sizes back to back, as bpvo_hip_add_frames takes them: (u8 [sum of pixels], f32 [sum of pixels],
     [(rows, cols)] per frame)."""
@@ -628,6 +647,97 @@ class Context:
         res = (Result * n)()
         self.call("add_frames_stereo", int(n), p_ids, C.c_void_p(d_left_ptr), C.c_void_p(d_right_ptr), 1, C.byref(sp), res)
         return [self._result_dict(r) for r in res]
+
+    # -- rectification on the device (c_api.h): seq None = the context's own camera
+    def set_rectification(self, side, lens_, seq=None):
+        """bpvo_hip_(seq_)set_rectification: the map of a side (0 left, 1 right) from a Lens."""
+        if seq is None:
+            self.call("set_rectification", int(side), C.byref(lens_))
+        else:
+            self.call("seq_set_rectification", int(seq), int(side), C.byref(lens_))
+
+    def set_rectification_maps(self, side, raw_rows, raw_cols, mapx, mapy, seq=None):
+        """bpvo_hip_(seq_)set_rectification_maps: the map of a side from the caller's f32 maps of the camera's size."""
+        mapx, mapy = _f32(mapx), _f32(mapy)
+        assert mapx.shape == mapy.shape
+        args = (int(side), int(raw_rows), int(raw_cols), mapx.ctypes.data_as(C.c_void_p), mapy.ctypes.data_as(C.c_void_p))
+        if seq is None:
+            self.call("set_rectification_maps", *args)
+        else:
+            self.call("seq_set_rectification_maps", int(seq), *args)
+
+    def clear_rectification(self, seq=None):
+        if seq is None:
+            self.call("clear_rectification")
+        else:
+            self.call("seq_clear_rectification", int(seq))
+
+    def rectification_info(self, side, seq=None):
+        """(raw_rows, raw_cols, outside_pixels) of a side's rectification."""
+        r, w, o = C.c_int(), C.c_int(), C.c_uint64()
+        if seq is None:
+            self.call("rectification_info", int(side), C.byref(r), C.byref(w), C.byref(o))
+        else:
+            self.call("seq_rectification_info", int(seq), int(side), C.byref(r), C.byref(w), C.byref(o))
+        return r.value, w.value, o.value
+
+    def rectify_counts(self):
+        """bpvo_hip_rectify_counts: (launches, destination pixels) so far."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self.call("rectify_counts", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def _rect_out_shapes(self, n, seq):
+        if seq is None:
+            return [(self.rows, self.cols)] * n
+        return [(cam.rows, cam.cols) for cam in (self.seq_get_camera(int(s)) for s in seq)]
+
+    def rectify_frames(self, raws, side, seq=None):
+        """bpvo_hip_rectify_frames, host to host: raws[i] (2-D u8, the raw size of seq[i]'s side; seq None: the context's own camera) -> the list of
+        rectified images, each of its camera's size."""
+        n = len(raws)
+        ids, p_ids = self._seq_ids(n, seq)
+        raw, _ = pack_images(raws)
+        shapes = self._rect_out_shapes(n, ids)
+        out = np.empty(sum(r * w for r, w in shapes), np.uint8)
+        self.call("rectify_frames", n, p_ids, int(side), raw.ctypes.data_as(C.c_void_p), 0, out.ctypes.data_as(C.c_void_p), 0)
+        imgs, at = [], 0
+        for r, w in shapes:
+            imgs.append(out[at:at + r * w].reshape(r, w))
+            at += r * w
+        return imgs
+
+    def rectify_frames_ptr(self, n, side, raw_ptr, raw_on_device, out_ptr, out_on_device, seq=None):
+        """bpvo_hip_rectify_frames on packed buffers given by address, each in host or device memory."""
+        ids, p_ids = self._seq_ids(n, seq)
+        self.call("rectify_frames", int(n), p_ids, int(side), C.c_void_p(raw_ptr), int(bool(raw_on_device)), C.c_void_p(out_ptr), int(bool(out_on_device)))
+
+    def add_frames_stereo_raw(self, lefts, rights, sp, seq=None):
+        """bpvo_hip_add_frames_stereo_raw: raw pair i (2-D u8 arrays of the raw sizes of sequence seq[i]'s sides; None: 0 .. n-1) is rectified on the
+        device and becomes the next frame of its sequence.  Returns n dicts in add_frame's format."""
+        n = len(lefts)
+        assert len(rights) == n, "one right image per left image"
+        ids, p_ids = self._seq_ids(n, seq)
+        left, _ = pack_images(lefts)
+        right, _ = pack_images(rights)
+        res = (Result * n)()
+        self.call("add_frames_stereo_raw", n, p_ids, left.ctypes.data_as(C.c_void_p), right.ctypes.data_as(C.c_void_p), 0, C.byref(sp), res)
+        return [self._result_dict(r) for r in res]
+
+    def add_frames_stereo_raw_device(self, n, d_left_ptr, d_right_ptr, sp, seq=None):
+        """add_frames_stereo_raw with the n packed raw pairs already in device memory."""
+        ids, p_ids = self._seq_ids(n, seq)
+        res = (Result * n)()
+        self.call("add_frames_stereo_raw", int(n), p_ids, C.c_void_p(d_left_ptr), C.c_void_p(d_right_ptr), 1, C.byref(sp), res)
+        return [self._result_dict(r) for r in res]
+
+    def add_frame_stereo_raw(self, left, right, sp):
+        """bpvo_hip_add_frame_stereo_raw: the context's own camera, a raw pair from host memory."""
+        left = np.ascontiguousarray(left, dtype=np.uint8)
+        right = np.ascontiguousarray(right, dtype=np.uint8)
+        r = Result()
+        self.call("add_frame_stereo_raw", left.ctypes.data_as(C.c_void_p), right.ctypes.data_as(C.c_void_p), C.byref(sp), C.byref(r))
+        return self._result_dict(r)
 
     def seq_capacity(self):
         n = C.c_int()

@@ -321,6 +321,12 @@ const std::vector<OptionDef>& option_table()
     // read-only (bpvo_hip_get_option): the frames per launch of the last SGM call and the free device memory (MiB) its rule saw
     OptionDef{"stereo_frames_per_launch_seen", 0, 0, [](bpvo_hip_ctx* c) { return (double) c->st_frames_per_launch_seen; }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
     OptionDef{"stereo_free_mib_seen", 0, 0, [](bpvo_hip_ctx* c) { return (double) (c->st_free_seen >> 20); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
+    // read-only: the duration of the last rectification launch between two events on the stream, ms; -1 unless bpvo_hip_profiling was on for it
+    OptionDef{"rectify_last_kernel_ms", 0, 0, [](bpvo_hip_ctx* c) {
+                float ms = -1.0f;
+                if(!c->rect.timed || hipEventSynchronize(c->rect.t1) != hipSuccess || hipEventElapsedTime(&ms, c->rect.t0, c->rect.t1) != hipSuccess) return -1.0;
+                return (double) ms;
+              }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
     OPT_INT("normalization_side_stream", nrm_side_stream, 0, 1),
     OPT_INT("normalization_form", nrm_dpp_asm, 0, 4),
     OPT_INT("small_batch_fused", small_batch_fused, 0, 1),

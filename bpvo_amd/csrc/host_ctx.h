@@ -5,6 +5,7 @@
 //                 stereo front-end                                                       vo_state.h    addFrame's state machine (host only, no HIP)
 //                                                                                        gn_rounds.h   the chain's pipelined rounds (host only, no HIP)
 //   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)      frame_plan.h  the frame stage's decisions (host only, no HIP)
+//   rectify.hip   rectification on the device: the maps of the camera sides, the launch in front of the stereo front-end (kernels_rectify.hip, rectify_math.h)
 //   device_owned.h  the owners of every device buffer, pinned buffer, stream and event below (the only place that acquires or releases one)
 // The host keeps bpvo's object model (frames with a descriptor pyramid and a template pyramid, a pose estimator with per-level
 // Gauss-Newton runs, the VisualOdometry keyframe state machine) but every O(pixels) / O(points) array lives in HBM; per GN iteration the
@@ -139,6 +140,27 @@ struct ScoreScratch {
   DeviceBuf<float> d_T;
   DeviceBuf<ScorePartial> d_partials;
   DeviceBuf<bpvo_hip_pose_score> d_out;
+};
+
+// Rectification (c_api.h "rectification on the device", rectify.hip): the map of one camera side — the entries of its destination pixels
+// (rectify_math.h RectEntry), built on the host by a set call and uploaded once — and what the context holds for the calls: everything is
+// acquired at its first use, so a context that never rectifies holds nothing.
+struct RectMap {
+  DeviceBuf<int2> d_map;             // [rows][cols]; empty: the side has no rectification
+  int rows = 0, cols = 0;            // the destination: the camera's size when the map was set
+  int raw_rows = 0, raw_cols = 0;
+  uint64_t outside = 0;              // destination pixels without a full source (rectify_outside)
+};
+struct RectState {
+  RectMap own[2];                    // the context's own camera (bpvo_hip_set_rectification): left, right
+  std::vector<RectMap> seq;          // [2 * sequence capacity], made by the first bpvo_hip_seq_set_rectification: sequence s side k at 2 s + k
+  DeviceBuf<uint8_t> raw[2];         // raw images of a call that came from host memory, per side of the call
+  DeviceBuf<uint8_t> out;            // rectified images on their way to host memory (bpvo_hip_rectify_frames)
+  // the frame table of a call (kernels.h RectifyFrame), filled in pinned memory and copied on the stream; tab_ev: behind the last copy
+  PinnedBuf<RectifyFrame> h_tab; DeviceBuf<RectifyFrame> d_tab;
+  Event tab_ev;
+  uint64_t launches = 0, pixels = 0; // bpvo_hip_rectify_counts
+  Event t0, t1; bool timed = false;   // while bpvo_hip_profiling is on: events around the last launch (option "rectify_last_kernel_ms")
 };
 
 enum KernelClass { KC_PYRAMID = 0, KC_DESCRIPTOR, KC_SALIENCY_SELECT, KC_NORMALIZATION, KC_TEMPLATE, KC_WARP_RESIDUAL, KC_MEDIAN,
@@ -343,6 +365,7 @@ struct bpvo_hip_ctx {
   int stereo_frames_per_launch = 0;
   size_t st_sgm_budget = 0, st_free_seen = 0;
   int st_frames_per_launch_seen = 0;      // what the last SGM launch used (measurement: option "stereo_frames_per_launch_seen")
+  RectState rect;                         // rectification on the device (rectify.hip)
   // Upload pipeline of pair batches handed over in HOST buffers (bpvo_hip_batch_run, on_device = 0): worker threads stage chunks of
   // kUploadChunkPairs pairs in pinned memory and copy them on a stream of their own into a device staging area, chunk after chunk in lane
   // order, while the lanes already work on the chunks that have landed (upload_pipeline below).  Option "upload_workers" (0 = off).
@@ -667,6 +690,17 @@ int pose_score_served(bpvo_hip_ctx* c);
 // no workspace touched; the addFrame drivers score their start candidates with it (vo.hip)
 int score_pairs(bpvo_hip_ctx* c, int n_pairs, const int* refs, const int* curs, int level, int n_poses, const float* T, float tau,
                 bpvo_hip_pose_score* out);
+// the sequences a context serves (bpvo_hip_add_frames: three frame slots and one workspace each)
+inline int seq_capacity(const bpvo_hip_ctx* c) { return std::max(0, std::min(c->n_frames / 3, c->n_pairs)); }
+// Rectification (rectify.hip).  rect_map_of: the map of sequence seq's side (seq < 0: the context's own camera), or null where none is set.
+// rectify_queue: ONE launch for the n frames of each of n_sides sides — frame i of side k is a raw image of its map's raw size, the frames of a
+// side back to back at sides[k].raw (host memory: uploaded once into the context's staging), the rectified frames back to back at sides[k].dst
+// (device), each of its map's destination size; the caller has seen to it that every map exists.  Nothing is synchronised.
+// rect_clear: the maps of a sequence (seq < 0: the context's own) go, after the stream has finished with them.
+const RectMap* rect_map_of(const bpvo_hip_ctx* c, int seq, int side);
+struct RectSide { int side; const uint8_t* raw; uint8_t* dst; };
+int rectify_queue(bpvo_hip_ctx* c, int n, const int* seq /*null: the context's own camera*/, int n_sides, const RectSide* sides, bool on_device);
+int rect_clear(bpvo_hip_ctx* c, int seq);
 int set_option(bpvo_hip_ctx* c, const std::string& key, double v);
 int apply_options_string(bpvo_hip_ctx* c, const char* str);
 struct OptionDef { const char* key; double lo, hi; std::function<double(bpvo_hip_ctx*)> get; std::function<int(bpvo_hip_ctx*, double)> set; };

@@ -114,6 +114,10 @@ void launch_stereo_prefilter(hipStream_t s, const uint8_t* src, uint8_t* dst, in
 void launch_stereo_prefilter_frames(hipStream_t s, const uint8_t* src, uint8_t* dst, const StereoFrame* frames /*device*/, int max_rows, int max_cols,
                                     int cap, int nframes);
 bool launch_stereo_bm(hipStream_t s, const StereoLaunch& g);   // false: window size / disparity range outside what the kernel serves
+// Rectification (kernels_rectify.hip; the rule: rectify_math.h): one frame of a call — a raw image of raw_rows x raw_cols bytes at src, the map
+// of the rows x cols destination pixels (RectEntry per pixel), the rectified image at dst (any byte address).  One launch serves the table.
+struct RectifyFrame { int rows, cols, raw_rows, raw_cols; const int2* map; const uint8_t* src; uint8_t* dst; };
+void launch_rectify_frames(hipStream_t s, const RectifyFrame* frames /*device*/, int nframes, int max_rows, int max_cols);
 
 // semi-global matching (kernels_sgm.hip): the reference's in-tree SgmStereo (utils/sgm.cc)
 struct SgmLaunch {

@@ -114,7 +114,6 @@ static int stereo_scratch(bpvo_hip_ctx* c, size_t need)      // the semi-global 
   HIP_CK(c, c->st_sgm.reserve(need));
   return BPVO_OK;
 }
-static int seq_capacity(const bpvo_hip_ctx* c);
 struct StereoSize { int rows, cols; };
 static bool operator==(const StereoSize& a, const StereoSize& b) { return a.rows == b.rows && a.cols == b.cols; }
 // The checks of a call's stereo stage, once per size among its frames; nothing is touched.  ids: null (the context's own size: stereo_run), or the
@@ -313,6 +312,33 @@ int bpvo_hip_add_frame_stereo(bpvo_hip_ctx* c, const uint8_t* left, const uint8_
   const uint8_t* d_left = nullptr;
   int rc = stereo_run(c, 1, left, right, false, sp, &d_left);
   if(rc) return rc;
+  return add_frame_impl(c, d_left, c->st_disp, true, ret);
+}
+// ... and fed by the rectification in front of it (c_api.h "rectification on the device"): the raw pair becomes the rectified pair in the
+// front-end's own image buffers — one launch for both sides, no host synchronisation, no copy —, which the front-end then reads where they lie
+static int rect_side_missing(bpvo_hip_ctx* c, int seq, int side)
+{
+  c->err = (seq < 0 ? std::string() : "sequence " + std::to_string(seq) + ": ") + (side ? "no rectification of the right side" : "no rectification of the left side");
+  return BPVO_ERR_NO_DATA;
+}
+int bpvo_hip_add_frame_stereo_raw(bpvo_hip_ctx* c, const uint8_t* left_raw, const uint8_t* right_raw, const bpvo_hip_stereo_params* sp, bpvo_hip_result* ret)
+{
+  CHECK_CTX(c);
+  if(!left_raw || !right_raw) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr image");
+  for(int side = 0; side < 2; ++side)
+    if(!rect_map_of(c, -1, side)) return rect_side_missing(c, -1, side);
+  const StereoSize size{c->rows, c->cols};
+  int rc = stereo_check_sizes(c, 1, &size, sp, nullptr);
+  if(rc) return rc;
+  (void) hipSetDevice(c->device);
+  rc = stereo_reserve(c, c->geom[0].npix);
+  if(rc) return rc;
+  const RectSide sides[2] = {{0, left_raw, c->st_left}, {1, right_raw, c->st_right}};
+  rc = rectify_queue(c, 1, nullptr, 2, sides, false);
+  if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
+  const uint8_t* d_left = nullptr;
+  rc = stereo_run(c, 1, c->st_left, c->st_right, true, sp, &d_left);
+  if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
   return add_frame_impl(c, d_left, c->st_disp, true, ret);
 }
 static void slot_clear(bpvo_hip_ctx* c, int slot) { c->frames[slot].has_data = false; c->frames[slot].has_template = false; }
@@ -546,7 +572,6 @@ int bpvo_hip_get_trajectory(bpvo_hip_ctx* c, float* poses) { CHECK_CTX(c); vo_ge
 // sequence sees the same kernels on the same inputs as the single path's addFrame (the frame stages, the estimate and the counts do not depend
 // on the batch a frame or pair is in), and the host decides with the same float code — every decision and every change of a sequence's state
 // is a call into vo_state.h that performs the calls add_frame_impl makes —: the results are the single path's, bit for bit.
-static int seq_capacity(const bpvo_hip_ctx* c) { return std::max(0, std::min(c->n_frames / 3, c->n_pairs)); }
 static void seq_reset_state(bpvo_hip_ctx* c, int s)
 {
   vo_reset(c->seqs[s], 3 * s);
@@ -1135,6 +1160,38 @@ int bpvo_hip_add_frames_stereo(bpvo_hip_ctx* c, int n, const int* seq, const uin
   if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
   return add_frames_run(c, false, ids, d_left, c->st_disp, true, results);
 }
+// ... and from raw pairs: every sequence's pair rectified into the front-end's image buffers by ONE launch, then the call above's two steps on
+// device input.  Raw images from host memory are uploaded once.
+int bpvo_hip_add_frames_stereo_raw(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* left_raw, const uint8_t* right_raw, int on_device,
+                                   const bpvo_hip_stereo_params* sp, bpvo_hip_result* results)
+{
+  CHECK_CTX(c);
+  std::vector<int> ids;
+  int rc = add_frames_check(c, false, n, seq, left_raw, right_raw, "nullptr image", results, ids);
+  if(rc) return rc;
+  for(int i = 0; i < n; ++i)
+    for(int side = 0; side < 2; ++side)
+      if(!rect_map_of(c, ids[i], side)) return rect_side_missing(c, ids[i], side);
+  std::vector<StereoSize> sz((size_t) n);
+  size_t npix = 0;
+  for(int i = 0; i < n; ++i) {
+    const LevelGeom& g = slot_geom(c, c->frames[3 * ids[i]], 0);
+    sz[i] = StereoSize{g.rows, g.cols};
+    npix += g.npix;
+  }
+  rc = stereo_check_sizes(c, n, sz.data(), sp, ids.data());
+  if(rc) return rc;
+  (void) hipSetDevice(c->device);
+  rc = stereo_reserve(c, npix);
+  if(rc) return rc;
+  const RectSide sides[2] = {{0, left_raw, c->st_left}, {1, right_raw, c->st_right}};
+  rc = rectify_queue(c, n, ids.data(), 2, sides, on_device != 0);
+  if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
+  const uint8_t* d_left = nullptr;
+  rc = stereo_run_sizes(c, n, sz.data(), c->st_left, c->st_right, true, sp, &d_left);
+  if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
+  return add_frames_run(c, false, ids, d_left, c->st_disp, true, results);
+}
 int bpvo_hip_stereo_frames(bpvo_hip_ctx* c, int n, const bpvo_hip_camera* cams, const uint8_t* left, const uint8_t* right, int on_device,
                            const bpvo_hip_stereo_params* sp, float* disparity, int disparity_on_device)
 {
@@ -1316,6 +1373,8 @@ int bpvo_hip_seq_set_camera(bpvo_hip_ctx* c, int seq, const bpvo_hip_camera* cam
     if(g[l].cap > c->geom[l].cap)
       return seq_fail(c, BPVO_ERR_UNSUPPORTED, seq, ("camera needs a template capacity of " + std::to_string(g[l].cap) + " points at level " + std::to_string(l) +
                                                      ", the context holds " + std::to_string(c->geom[l].cap)).c_str());
+  rc = rect_clear(c, seq);      // (its rectification was made for the camera that goes: the destination size and K' may have changed)
+  if(rc) return rc;
   assign_camera(c, seq, g);
   c->vo_mode = 2;      // a context with per-sequence cameras serves bpvo_hip_add_frames
   return BPVO_OK;

@@ -451,6 +451,76 @@ int bpvo_hip_stereo_frames(bpvo_hip_ctx* ctx, int n, const bpvo_hip_camera* cams
 int bpvo_hip_add_frames_stereo(bpvo_hip_ctx* ctx, int n, const int* seq /*[n] distinct ids, NULL = 0..n-1*/, const uint8_t* left,
                                const uint8_t* right, int on_device, const bpvo_hip_stereo_params* sp, bpvo_hip_result* results /*[n]*/);
 
+/* ---- rectification on the device (an extension: the reference expects rectified input and uses cv::remap only to warp descriptors,
+ * bpvo/photo_error.cc:60).  Raw — distorted, unrectified — 8-bit images go in; on the device they become rectified images of a camera of
+ * the context, bit for bit what the integer rule below gives (bpvo_amd/csrc/rectify_math.h states it as code), and the raw entry points hand
+ * them to the stereo front-end and the VO driver without a visit to the host.
+ *
+ * THE MAP.  A camera side (0 left, 1 right) has a map with one entry per destination pixel: the source coordinates (x, y) in the raw image,
+ * in f64, as xq = (int32) nearbyint(x * 32.0) and yq likewise (1/32 pixel, ties to even).  A coordinate that is not finite, or with
+ * |x * 32| >= 2^20, makes the entry "outside": the pixel is stored as 0.  The map is built on the host by a set call and uploaded once.
+ *   The lens map (bpvo_hip_lens): Brown-Conrady with the coefficients dist = k1 k2 p1 p2 k3 k4 k5 k6, the raw intrinsics fx fy cx cy, the
+ *   rotation R (row-major) from the raw camera to the rectified camera.  The new intrinsics fx' fy' cx' cy' are the camera's K (K[0], K[4],
+ *   K[2], K[5]) widened to f64.  For the integer destination (u, v), in f64, one operation per statement in this order, no fused multiply-add:
+ *     a = (u - cx') / fx'          b = (v - cy') / fy'
+ *     X = (R00 a + R10 b) + R20    Y = (R01 a + R11 b) + R21    W = (R02 a + R12 b) + R22        (R^T (a, b, 1): no matrix inverse)
+ *     x = X / W    y = Y / W    x2 = x x    y2 = y y    r2 = x2 + y2    xy = x y
+ *     rad = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2)
+ *     xd = (x rad + (2 p1) xy) + p2 (r2 + 2 x2)        yd = (y rad + p1 (r2 + 2 y2)) + (2 p2) xy
+ *     xs = fx xd + cx              ys = fy yd + cy
+ *   The caller's maps (the _maps calls): two f32 arrays mapx, mapy of the camera's size, as cv::initUndistortRectifyMap or any fisheye model
+ *   gives them; each value is widened to f64 and quantised by the same rule.
+ * THE PIXEL.  With ix = xq >> 5 (arithmetic shift), fx = xq & 31, iy and fy likewise, the taps are p(iy + dy, ix + dx), dy, dx in {0, 1}; a tap
+ * outside [0, raw_rows) x [0, raw_cols) reads 0 (cv::remap's BORDER_CONSTANT); then
+ *     out = ((32 - fy) ((32 - fx) p00 + fx p01) + fy ((32 - fx) p10 + fx p11) + 512) >> 10
+ * in plain integer arithmetic.  This is NOT OpenCV's fixed-point table (weights rounded to 1/32768): parity with cv::remap is unpinned —
+ * OpenCV is not part of the reference tree.  A destination pixel is OUTSIDE if its entry is "outside" or a tap with a non-zero weight lies
+ * outside the raw image; the info calls count them.
+ *
+ * bpvo_hip_seq_set_rectification(_maps): the map of sequence seq's side, for the sequence's camera as it is now.  bpvo_hip_seq_set_camera
+ * clears the sequence's rectification (the destination size and K' may have changed); bpvo_hip_seq_clear_rectification does so on request.
+ * bpvo_hip_set_rectification(_maps) / bpvo_hip_clear_rectification / bpvo_hip_rectification_info: the same for the context's own camera, which
+ * bpvo_hip_add_frame_stereo_raw reads.  Errors, every check before anything changes:
+ *   a raw call or an info call on a sequence or side without a rectification                                            BPVO_ERR_NO_DATA
+ *   lens values that are not finite; fx or fy <= 0; max |R^T R - I| > 1e-6; a raw size under 2; a NULL pointer; a bad side   BPVO_ERR_INVALID_ARG
+ *   a raw size above 32767; a camera with skew (K[1] != 0)                                                              BPVO_ERR_UNSUPPORTED
+ * A set call that replaces a map waits for the context's stream first.  Maps, raw staging and tables are acquired at their first use: a
+ * context that never rectifies holds nothing of them. */
+typedef struct bpvo_hip_lens {
+  double fx, fy, cx, cy;           /* the raw camera's intrinsics */
+  double dist[8];                  /* k1 k2 p1 p2 k3 k4 k5 k6 */
+  double R[9];                     /* raw camera -> rectified camera, row-major */
+  int raw_rows, raw_cols;          /* the raw image: 2 .. 32767 each */
+} bpvo_hip_lens;
+int bpvo_hip_seq_set_rectification(bpvo_hip_ctx* ctx, int seq, int side /*0 left, 1 right*/, const bpvo_hip_lens* lens);
+int bpvo_hip_seq_set_rectification_maps(bpvo_hip_ctx* ctx, int seq, int side, int raw_rows, int raw_cols, const float* mapx /*[rows*cols] of the camera*/,
+                                        const float* mapy);
+int bpvo_hip_seq_clear_rectification(bpvo_hip_ctx* ctx, int seq);
+int bpvo_hip_seq_rectification_info(bpvo_hip_ctx* ctx, int seq, int side, int* raw_rows, int* raw_cols, uint64_t* outside_pixels /*each may be NULL*/);
+int bpvo_hip_set_rectification(bpvo_hip_ctx* ctx, int side, const bpvo_hip_lens* lens);
+int bpvo_hip_set_rectification_maps(bpvo_hip_ctx* ctx, int side, int raw_rows, int raw_cols, const float* mapx, const float* mapy);
+int bpvo_hip_clear_rectification(bpvo_hip_ctx* ctx);
+int bpvo_hip_rectification_info(bpvo_hip_ctx* ctx, int side, int* raw_rows, int* raw_cols, uint64_t* outside_pixels);
+/* n raw frames of one side -> n rectified frames, ONE launch whatever the frames' sizes.  Frame i is a raw image of raw_rows x raw_cols of
+ * seq[i]'s side (seq NULL: n frames of the context's own camera), the raw frames back to back in call order (host or device); the outputs lie
+ * back to back in the cameras' sizes (host or device) — the packing of bpvo_hip_add_frames_stereo.  A sequence may appear more than once.
+ * Returns with the outputs in place.  Rigs are served by composition: this call with device output for each side, bpvo_hip_stereo_frames with
+ * device output, then bpvo_hip_add_frames_rig(s) with device input. */
+int bpvo_hip_rectify_frames(bpvo_hip_ctx* ctx, int n, const int* seq /*[n] or NULL*/, int side, const uint8_t* raw, int on_device, uint8_t* out,
+                            int out_on_device);
+/* bpvo_hip_add_frames_stereo / bpvo_hip_add_frame_stereo from raw pairs: both sides of every frame are rectified by one launch into the stereo
+ * front-end's own image buffers, which the front-end and the frame stages then read where they lie — no host synchronisation and no copy in
+ * between; raw images from host memory are uploaded once.  The results are, bit for bit, those of the rectified entry point fed the images the
+ * rule above gives.  Every check of the rectified entry point, and a rectification of both sides of every sequence of the call
+ * (BPVO_ERR_NO_DATA, the sequence named in bpvo_hip_last_error), come before anything changes. */
+int bpvo_hip_add_frames_stereo_raw(bpvo_hip_ctx* ctx, int n, const int* seq /*[n] distinct ids, NULL = 0..n-1*/, const uint8_t* left_raw,
+                                   const uint8_t* right_raw, int on_device, const bpvo_hip_stereo_params* sp, bpvo_hip_result* results /*[n]*/);
+int bpvo_hip_add_frame_stereo_raw(bpvo_hip_ctx* ctx, const uint8_t* left_raw, const uint8_t* right_raw, const bpvo_hip_stereo_params* sp,
+                                  bpvo_hip_result* result);
+/* the rectification launches of the context so far and the destination pixels they made (the kernel has no class in
+ * bpvo_hip_get_kernel_stats: this is its counter) */
+int bpvo_hip_rectify_counts(bpvo_hip_ctx* ctx, uint64_t* launches, uint64_t* pixels);
+
 /* ---- rig mode: the cameras of a rigid rig estimated as ONE 6-DoF body pose, from all cameras' residuals at once.
  * Twists are ordered (omega, v).  The body pose T maps key-frame body coordinates to current body coordinates (the role T plays for one
  * camera).  Member p has the extrinsic X_p, camera_from_body (x_cam = X_p x_body; rigid), and runs at the pose T_p = X_p T X_p^-1 (f64,
@@ -782,6 +852,8 @@ int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* ctx, uint64_t out[4]);
  *                                      frame after the other, k = at most k.  Same maps.
  *   "stereo_frames_per_launch_seen" (read-only) the frames per launch the last SGM call used
  *   "stereo_free_mib_seen"   (read-only) the free device memory, MiB, the rule above saw when this context first needed the SGM scratch
+ *   "rectify_last_kernel_ms" (read-only) the duration, ms, of the last rectification launch between two events on the context's stream; -1 unless
+ *                                      bpvo_hip_profiling was on when it was queued (measurement: scripts/rectify_bench.py)
  *   "normalization_form"     4         the sequential (reference-order) Hartley sums: 1 = hand-scheduled DPP add chains (170 us for a 1241x376 template,
  *                                      2.28 ms for a dense 640x480 one); 0 = the compiler's DPP form (281 us / 3.6 ms); 2 = every lane of a row reads the same
  *                                      four consecutive elements from LDS and adds them with plain adds — no cross-lane traffic, no asm (311 us / 4.0 ms);

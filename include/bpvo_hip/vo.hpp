@@ -419,6 +419,23 @@ class VisualOdometry {
     return makeResult(r);
   }
 
+  /* Raw (distorted, unrectified) pairs (an extension; c_api.h "rectification on the device"): the map of a side (0 left, 1 right) from a lens
+   * or from the caller's f32 maps of the camera's size; addFrameRaw rectifies the pair on the device and runs the call above on the result,
+   * which never visits the host. */
+  void setRectification(int side, const bpvo_hip_lens& lens) { _dev->check(bpvo_hip_set_rectification(_dev->ctx(), side, &lens)); }
+  void setRectificationMaps(int side, int rawRows, int rawCols, const float* mapx, const float* mapy)
+  {
+    _dev->check(bpvo_hip_set_rectification_maps(_dev->ctx(), side, rawRows, rawCols, mapx, mapy));
+  }
+  void clearRectification() { _dev->check(bpvo_hip_clear_rectification(_dev->ctx())); }
+  Result addFrameRaw(const uint8_t* leftRaw, const uint8_t* rightRaw, const StereoParameters& stereo)
+  {
+    if(leftRaw == nullptr || rightRaw == nullptr) throw Error("nullptr image");
+    bpvo_hip_result r;
+    _dev->check(bpvo_hip_add_frame_stereo_raw(_dev->ctx(), leftRaw, rightRaw, &stereo, &r));
+    return makeResult(r);
+  }
+
   int numPointsAtLevel(int level = -1) const                     // bpvo/vo.h:86
   {
     int n = 0;
@@ -561,6 +578,27 @@ class VisualOdometrySequences {
     if(n < 0) n = numSequences();
     std::vector<bpvo_hip_result> r((size_t) n);
     _dev->check(bpvo_hip_add_frames_stereo(_dev->ctx(), n, seq, left, right, 0, &stereo, r.data()));
+    std::vector<Result> ret;
+    for(int i = 0; i < n; ++i) ret.push_back(makeResult(seq ? seq[i] : i, r[i]));
+    return ret;
+  }
+
+  /* ... and from raw (distorted, unrectified) pairs (an extension; c_api.h "rectification on the device"): the map of side `side` (0 left, 1
+   * right) of sequence s from a lens or from the caller's f32 maps of the camera's size — setCamera(s, ...) clears both sides —; addFramesRaw
+   * rectifies every pair of the call in one launch (pair i of the raw sizes of sequence seq[i]'s sides, the raw images back to back) and runs
+   * the call above on the result, which never visits the host (bpvo_hip_add_frames_stereo_raw). */
+  void setRectification(int s, int side, const bpvo_hip_lens& lens) { _dev->check(bpvo_hip_seq_set_rectification(_dev->ctx(), s, side, &lens)); }
+  void setRectificationMaps(int s, int side, int rawRows, int rawCols, const float* mapx, const float* mapy)
+  {
+    _dev->check(bpvo_hip_seq_set_rectification_maps(_dev->ctx(), s, side, rawRows, rawCols, mapx, mapy));
+  }
+  void clearRectification(int s) { _dev->check(bpvo_hip_seq_clear_rectification(_dev->ctx(), s)); }
+  std::vector<Result> addFramesRaw(const uint8_t* leftRaw, const uint8_t* rightRaw, const StereoParameters& stereo, const int* seq = nullptr, int n = -1)
+  {
+    if(leftRaw == nullptr || rightRaw == nullptr) throw Error("nullptr image");
+    if(n < 0) n = numSequences();
+    std::vector<bpvo_hip_result> r((size_t) n);
+    _dev->check(bpvo_hip_add_frames_stereo_raw(_dev->ctx(), n, seq, leftRaw, rightRaw, 0, &stereo, r.data()));
     std::vector<Result> ret;
     for(int i = 0; i < n; ++i) ret.push_back(makeResult(seq ? seq[i] : i, r[i]));
     return ret;
