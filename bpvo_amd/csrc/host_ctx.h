@@ -1,11 +1,13 @@
 // libbpvo_hip, host side: the context and what its translation units share (internal header; the interface is include/bpvo_hip/c_api.h).
 //   context.hip   create / destroy, storage, job tables, per-context options            frames.hip    setData / setTemplate stages + accessors
 //   estimate.hip  estimatePose: the Gauss-Newton drivers (chain, persistent, team)       batch.hip     pair batches, the upload pipeline
-//   vo.hip        the addFrame drivers (one frame, many sequences), point cloud,          measure.hip   profiling, counters, diagnostics
-//                 stereo front-end                                                       vo_state.h    addFrame's state machine (host only, no HIP)
+//   vo.hip        the addFrame drivers (one frame, many sequences), point cloud           measure.hip   profiling, counters, diagnostics
+//                                                                                        vo_state.h    addFrame's state machine (host only, no HIP)
 //                                                                                        gn_rounds.h   the chain's pipelined rounds (host only, no HIP)
 //   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)      frame_plan.h  the frame stage's decisions (host only, no HIP)
 //   rectify.hip   rectification on the device: the maps of the camera sides, the launch in front of the stereo front-end (kernels_rectify.hip, rectify_math.h)
+//   stereo.hip    the stereo front-end: parameter checks, buffers, the matchers' launches over the frames of a call, stereo_front for the addFrame drivers
+//                 (kernels_stereo.hip, kernels_sgm.hip, kernels_sgbm.hip; sg_scanline.h: the semi-global matchers' scanline walk)
 //   device_owned.h  the owners of every device buffer, pinned buffer, stream and event below (the only place that acquires or releases one)
 // The host keeps bpvo's object model (frames with a descriptor pyramid and a template pyramid, a pose estimator with per-level
 // Gauss-Newton runs, the VisualOdometry keyframe state machine) but every O(pixels) / O(points) array lives in HBM; per GN iteration the
@@ -441,24 +443,11 @@ namespace bpvo_hip_host {
     }                                                                                       \
   } while(0)
 
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 // the automatic pyramid level count of an image size (numPyramidLevels <= 0; bpvo/vo.cc:101-105)
 inline int auto_pyramid_levels(int rows, int cols, int minImageDimensionForPyramid)
 {
   return 1 + (int) std::round(std::log2(std::min(rows, cols) / (double) minImageDimensionForPyramid));
 }
-
-struct Carver {
-  unsigned char* base;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t count)
-  {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += align_up(count * sizeof(T));
-    return p;
-  }
-};
 
 // HIP events around a kernel class on a lane's stream (measurement; resolved by resolve_events)
 Event take_event(Lane* ln);
@@ -701,6 +690,16 @@ const RectMap* rect_map_of(const bpvo_hip_ctx* c, int seq, int side);
 struct RectSide { int side; const uint8_t* raw; uint8_t* dst; };
 int rectify_queue(bpvo_hip_ctx* c, int n, const int* seq /*null: the context's own camera*/, int n_sides, const RectSide* sides, bool on_device);
 int rect_clear(bpvo_hip_ctx* c, int seq);
+// The stereo front-end of an addFrame call (stereo.hip): n pairs, pair i of sz[i] pixels for sequence ids[i] (ids null: the context's own camera), the
+// images of a side back to back at left / right, in host or device memory; raw: unrectified pairs, which go through rectify_queue first.  In order: the
+// raw path's map check, the parameter checks per size, (raw) buffers and rectification, the matcher.  The disparities end up in c->st_disp and the
+// rectified left images at *d_left, both on the device, nothing synchronised; after a failure behind the checks the stream has been drained.
+struct StereoSize { int rows, cols; };
+int stereo_front(bpvo_hip_ctx* c, int n, const StereoSize* sz, const int* ids, const uint8_t* left, const uint8_t* right, bool raw, bool on_device,
+                 const bpvo_hip_stereo_params* sp, const uint8_t** d_left);
+// the failures of sequence `seq` that vo.hip and stereo.hip share (vo.hip)
+int seq_fail(bpvo_hip_ctx* c, int code, int seq, const char* what);
+int camera_too_large(bpvo_hip_ctx* c, int seq, int rows, int cols);
 int set_option(bpvo_hip_ctx* c, const std::string& key, double v);
 int apply_options_string(bpvo_hip_ctx* c, const char* str);
 struct OptionDef { const char* key; double lo, hi; std::function<double(bpvo_hip_ctx*)> get; std::function<int(bpvo_hip_ctx*, double)> set; };

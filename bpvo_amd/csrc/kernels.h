@@ -48,6 +48,21 @@ static inline bool dispatch_wide_channels(int C, F&& f)
 
 namespace bpvo_hip {
 
+// Views carved from one allocation, each rounded up to 256 bytes: a layout is written once as a sequence of take<T>(count) steps — on a null
+// base the views are null and `off` ends as the layout's size (the slabs of host_ctx.h, the scratch of the semi-global matchers).
+inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+struct Carver {
+  unsigned char* base;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t count)
+  {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += align_up(count * sizeof(T));
+    return p;
+  }
+};
+
 // A Gaussian smoothing kernel of cv::GaussianBlur as the descriptors use it: n taps (odd; 0 = no smoothing), k the f32 taps
 // of cv::getGaussianKernel, ki their 8-bit fixed-point form cvRound(k * 256) for u8 images.  n = 5 runs the small-kernel
 // forms of OpenCV's filter engine, n >= 7 the generic ones (kernels_frame.hip, df_plane_kernel).

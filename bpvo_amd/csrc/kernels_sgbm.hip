@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "sg_scanline.h"
 
 namespace bpvo_hip {
 
@@ -179,23 +180,11 @@ __host__ __device__ inline int sgbm_family_lines(int fam, int rows, int width1)
   return (fam == 0 || fam == 4) ? rows : fam == 2 ? width1 : width1 + rows - 1;
 }
 
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ s16x2 pk(unsigned u) { return __builtin_bit_cast(s16x2, u); }
-__device__ __forceinline__ unsigned bits(s16x2 v) { return __builtin_bit_cast(unsigned, v); }
-#ifndef SGBM_PRIO_VALUE
-#define SGBM_PRIO_VALUE 1
-#endif
-#ifndef SGBM_PF_VALUE
-#define SGBM_PF_VALUE 16
-#endif
-// L(p, d) = C(p, d) + min(L'(d), L'(d - 1) + P1, L'(d + 1) + P1, min L' + P2) - (min L' + P2); L' = 0, min L' = 0 ahead of the first step.
-// A lane holds 2 NP consecutive disparities as pairs of int16 (v_pk_* with clamp: the values stay inside int16 — sgbm limits — so the
-// saturating forms equal the original's int arithmetic); neighbours by DPP wave shifts, the wave minimum by the DPP ladder.  The cost
-// words of SGBM_PF steps are requested back to back, the steps run on registers, the path costs are stored back to back.
+// A path starts from L = 0, min L = 0 (the zeroed borders of the original's buffers); the values stay inside int16 — sgbm_serves' limits —
+// so the saturating forms of the walk (sg_scanline.h) equal the original's int arithmetic.
 template <int NP>
 __global__ __launch_bounds__(64) void sgbm_path_kernel(const int16_t* __restrict__ cost, int16_t* __restrict__ Lvol, int rows, int width1, int D, int P1, int P2)
 {
-  constexpr int PF = SGBM_PF_VALUE, V = 2 * NP;
   // dispatch order: the long chains (the rows, both ways) first, then the columns, then the diagonals
   int fam = 0, l = blockIdx.x;
   {
@@ -209,95 +198,16 @@ __global__ __launch_bounds__(64) void sgbm_path_kernel(const int16_t* __restrict
     fam = order[min(k, 4)];
   }
   const SgbmLine ln = sgbm_line(fam, l, rows, width1);
-#if SGBM_PRIO_VALUE
+#if SG_PRIO_VALUE
   // The launch lasts as long as its longest chains — the rows, `width1` dependent steps against at most `rows` for everything else — while
   // every SIMD time-slices four or five lines: the rows get the issue priority, the short lines fill the gaps.
   if(fam == 0 || fam == 4) __builtin_amdgcn_s_setprio(3);
 #endif
   const size_t vol = (size_t) rows * width1 * D;
   int16_t* __restrict__ L = Lvol + (size_t) fam * vol;
-  const int lane = threadIdx.x;
-  const int d0 = lane * V;
-  const bool live = d0 < D;
-  const int d0_load = live ? d0 : 0;
   const long long step_stride = ((long long) ln.dy * width1 + ln.dx) * D;
   const long long base = ((long long) ln.y0 * width1 + ln.x0) * D;
-  unsigned prev[NP];
-#pragma unroll
-  for(int j = 0; j < NP; ++j) prev[j] = 0u;
-  int prev_min = 0;
-  const s16x2 P1v = {(short) P1, (short) P1};
-  using word_t = typename std::conditional<NP == 1, uint32_t, uint64_t>::type;
-#ifndef SGBM_PIPE_VALUE
-#define SGBM_PIPE_VALUE 0
-#endif
-  // SGBM_PIPE_VALUE 1: the cost words of the NEXT batch requested before the steps of this one run.  Measured: 0.719 against 0.715 ms per
-  // 1241 x 376 x 128 frame — no gain (the batch's own 16 loads are consumed with partial waits as they arrive; the chain of dependent steps
-  // is what a line costs), so the plain form is the default.
-  word_t cnext[PF];
-  if(SGBM_PIPE_VALUE) {
-#pragma unroll
-    for(int i = 0; i < PF; ++i) cnext[i] = *reinterpret_cast<const word_t*>(cost + base + (long long) min(i, ln.n - 1) * step_stride + d0_load);
-  }
-  for(int s0 = 0; s0 < ln.n; s0 += PF) {
-    word_t cw[PF], ow[PF];
-    if(SGBM_PIPE_VALUE) {
-#pragma unroll
-      for(int i = 0; i < PF; ++i) cw[i] = cnext[i];
-      if(s0 + PF < ln.n) {
-#pragma unroll
-        for(int i = 0; i < PF; ++i) cnext[i] = *reinterpret_cast<const word_t*>(cost + base + (long long) min(s0 + PF + i, ln.n - 1) * step_stride + d0_load);
-      }
-    } else {
-#pragma unroll
-      for(int i = 0; i < PF; ++i) cw[i] = *reinterpret_cast<const word_t*>(cost + base + (long long) min(s0 + i, ln.n - 1) * step_stride + d0_load);
-    }
-#pragma unroll
-    for(int i = 0; i < PF; ++i) {
-      const word_t cword = cw[i];
-      const short pm = (short) (prev_min + P2);
-      const s16x2 pmv = {pm, pm};
-      const unsigned left = (unsigned) __builtin_amdgcn_update_dpp((int) 0x7fff0000u, (int) prev[NP - 1], 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
-      const unsigned right = (unsigned) __builtin_amdgcn_update_dpp((int) 0x00007fffu, (int) prev[0], 0x130 /*wave_shl:1*/, 0xf, 0xf, false);
-      unsigned cur[NP];
-      int mn = 32767;
-#pragma unroll
-      for(int j = 0; j < NP; ++j) {
-        const unsigned below = j > 0 ? prev[j - 1] : left;
-        unsigned above = j < NP - 1 ? prev[j + 1] : right;
-        if(d0 + 2 * j + 2 >= D) above = 0x7fffu;              // the sentinel behind the last disparity
-        const s16x2 lm = pk((below >> 16) | (prev[j] << 16));
-        const s16x2 lp = pk((prev[j] >> 16) | (above << 16));
-        const s16x2 c = pk((unsigned) (cword >> (32 * j)));
-        s16x2 a = __builtin_elementwise_min(pk(prev[j]), __builtin_elementwise_add_sat(lm, P1v));
-        a = __builtin_elementwise_min(a, __builtin_elementwise_add_sat(lp, P1v));
-        a = __builtin_elementwise_min(a, pmv);
-        a = __builtin_elementwise_add_sat(__builtin_elementwise_sub_sat(a, pmv), c);
-        cur[j] = bits(a);
-        if(live) mn = min(mn, min((int) a.x, (int) a.y));
-      }
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x111 /*row_shr:1*/, 0xf, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x112 /*row_shr:2*/, 0xf, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x114 /*row_shr:4*/, 0xf, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x118 /*row_shr:8*/, 0xf, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x142 /*row_bcast:15*/, 0xa, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x143 /*row_bcast:31*/, 0xc, 0xf, false));
-      word_t out = 0;
-#pragma unroll
-      for(int j = 0; j < NP; ++j) out |= (word_t) cur[j] << (32 * j);
-      ow[i] = out;
-      if(s0 + i < ln.n) {
-        prev_min = __builtin_amdgcn_readlane(mn, 63);
-#pragma unroll
-        for(int j = 0; j < NP; ++j) prev[j] = cur[j];
-      }
-    }
-    if(live) {
-#pragma unroll
-      for(int i = 0; i < PF; ++i)
-        if(s0 + i < ln.n) *reinterpret_cast<word_t*>(L + base + (long long) (s0 + i) * step_stride + d0) = ow[i];
-    }
-  }
+  sg_walk_line<NP>(cost, L, base, step_stride, ln.n, D, P1, P2);
 }
 
 // ---- selection in two launches that fill the chip.
@@ -463,14 +373,44 @@ bool sgbm_serves(const SgbmLaunch& g, const char** why)
   return true;
 }
 
-size_t sgbm_scratch_bytes(int rows, int cols, int min_disp, int D)
+// The scratch, carved in one place: the launcher uses the pointers, sgbm_scratch_bytes is the same walk on a null base.  The volumes have
+// max(width1, 1) cost columns (an image narrower than its disparity range has none and runs no volume kernel).
+struct SgbmScratch {
+  uint8_t *planes_l, *planes_r;  // [2][rows][cols]: clipped x-Sobel, raw
+  uint8_t* pix;                  // pixel-wise cost [rows][width1][D]
+  int16_t* cost;                 // window sums
+  int16_t* Lvol;                 // path costs: [family][rows][width1][D]
+  uint16_t* hs;                  // = Lvol: the row sums borrow the first path volume (the scanline kernel overwrites it later)
+  int16_t *d16a, *d16b;          // the map before and behind the median
+  uint16_t* shifted;             // the speckle filter's view of it (invalid = 0)
+  int *lab, *size;               // the speckle filter's labels and region sizes
+  int* cand;                     // = lab, votes = size: candidates and votes borrow the speckle filter's planes (consumed before that filter runs)
+  unsigned* votes;
+  size_t bytes;
+};
+static SgbmScratch sgbm_layout(int rows, int cols, int min_disp, int D, unsigned char* base)
 {
   const size_t npix = (size_t) rows * cols;
-  const int width1 = std::max(cols - (min_disp + D), 1);
-  const size_t nvol = (size_t) rows * width1 * D;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  return 2 * up(2 * npix) + up(nvol) + up(nvol * 2) + up(5 * nvol * 2) + 2 * up(npix * 2) + up(npix * 2) + 2 * up(npix * 4);
+  const size_t nvol = (size_t) rows * std::max(cols - (min_disp + D), 1) * D;
+  Carver w{base};
+  SgbmScratch m;
+  m.planes_l = w.take<uint8_t>(2 * npix);
+  m.planes_r = w.take<uint8_t>(2 * npix);
+  m.pix = w.take<uint8_t>(nvol);
+  m.cost = w.take<int16_t>(nvol);
+  m.Lvol = w.take<int16_t>(5 * nvol);
+  m.hs = reinterpret_cast<uint16_t*>(m.Lvol);
+  m.d16a = w.take<int16_t>(npix);
+  m.d16b = w.take<int16_t>(npix);
+  m.shifted = w.take<uint16_t>(npix);
+  m.lab = w.take<int>(npix);
+  m.size = w.take<int>(npix);
+  m.cand = m.lab;
+  m.votes = reinterpret_cast<unsigned*>(m.size);
+  m.bytes = w.off;
+  return m;
 }
+size_t sgbm_scratch_bytes(int rows, int cols, int min_disp, int D) { return sgbm_layout(rows, cols, min_disp, D, nullptr).bytes; }
 
 // StereoSGBM::operator() + the conversion of StereoAlgorithm::run, for `nframes` rectified pairs one after the other on the stream
 bool launch_stereo_sgbm(hipStream_t s, const SgbmLaunch& g)
@@ -485,60 +425,43 @@ bool launch_stereo_sgbm(hipStream_t s, const SgbmLaunch& g)
   const int d12 = g.disp12_max_diff > 0 ? g.disp12_max_diff : 1;
   const int P1 = g.P1 > 0 ? g.P1 : 2, P2 = std::max(g.P2 > 0 ? g.P2 : 5, P1 + 1);
   const int invalid_scaled = (minD - 1) * 16;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t nvol = (size_t) rows * std::max(width1, 1) * D;
-  unsigned char* w = (unsigned char*) g.scratch;
-  uint8_t* planes_l = w; w += up(2 * npix);
-  uint8_t* planes_r = w; w += up(2 * npix);
-  uint8_t* pix = w; w += up(nvol);
-  int16_t* cost = (int16_t*) w; w += up(nvol * 2);
-  int16_t* Lvol = (int16_t*) w; w += up(5 * nvol * 2);
-  int16_t* d16a = (int16_t*) w; w += up(npix * 2);
-  int16_t* d16b = (int16_t*) w; w += up(npix * 2);
-  uint16_t* shifted = (uint16_t*) w; w += up(npix * 2);
-  int* lab = (int*) w; w += up(npix * 4);
-  int* size = (int*) w; w += up(npix * 4);
+  const SgbmScratch m = sgbm_layout(rows, cols, minD, D, (unsigned char*) g.scratch);
   const unsigned nb = (unsigned) ((npix + 255) / 256);
   for(int f = 0; f < g.nframes; ++f) {
     const uint8_t* L = g.left + npix * f;
     const uint8_t* R = g.right + npix * f;
     if(width1 > 0) {
       const dim3 gpl((cols + 255) / 256, rows);
-      hipLaunchKernelGGL(sgbm_planes_kernel, gpl, dim3(256), 0, s, L, planes_l, rows, cols, ftzero);
-      hipLaunchKernelGGL(sgbm_planes_kernel, gpl, dim3(256), 0, s, R, planes_r, rows, cols, ftzero);
+      hipLaunchKernelGGL(sgbm_planes_kernel, gpl, dim3(256), 0, s, L, m.planes_l, rows, cols, ftzero);
+      hipLaunchKernelGGL(sgbm_planes_kernel, gpl, dim3(256), 0, s, R, m.planes_r, rows, cols, ftzero);
       const size_t lds = sizeof(unsigned) * (size_t) (2 * PC_TX + 2 * (PC_TX + D - 1));
-      hipLaunchKernelGGL(sgbm_pixel_cost_kernel, dim3((width1 + PC_TX - 1) / PC_TX, rows), dim3(256), lds, s, planes_l, planes_r, pix, rows, cols, minD, D, minX1, width1);
-      {
-        uint16_t* hs = reinterpret_cast<uint16_t*>(Lvol);      // (the row sums borrow the first path volume: the scanline kernel overwrites it later)
-        const unsigned nbq = (unsigned) (((size_t) rows * width1 * (D / 4) + 255) / 256);
-        hipLaunchKernelGGL(sgbm_box_rows_kernel, dim3(nbq), dim3(256), 0, s, pix, hs, rows, width1, D, SW2);
-        hipLaunchKernelGGL(sgbm_box_cols_kernel, dim3(nbq), dim3(256), 0, s, hs, cost, rows, width1, D, SW2);
-      }
+      hipLaunchKernelGGL(sgbm_pixel_cost_kernel, dim3((width1 + PC_TX - 1) / PC_TX, rows), dim3(256), lds, s, m.planes_l, m.planes_r, m.pix, rows, cols, minD, D, minX1, width1);
+      const unsigned nbq = (unsigned) (((size_t) rows * width1 * (D / 4) + 255) / 256);
+      hipLaunchKernelGGL(sgbm_box_rows_kernel, dim3(nbq), dim3(256), 0, s, m.pix, m.hs, rows, width1, D, SW2);
+      hipLaunchKernelGGL(sgbm_box_cols_kernel, dim3(nbq), dim3(256), 0, s, m.hs, m.cost, rows, width1, D, SW2);
       int lines = 0;
       for(int fam = 0; fam < 5; ++fam) lines += sgbm_family_lines(fam, rows, width1);
-      if(D <= 128) hipLaunchKernelGGL(sgbm_path_kernel<1>, dim3((unsigned) lines), dim3(64), 0, s, cost, Lvol, rows, width1, D, P1, P2);
-      else hipLaunchKernelGGL(sgbm_path_kernel<2>, dim3((unsigned) lines), dim3(64), 0, s, cost, Lvol, rows, width1, D, P1, P2);
-      // (candidates and votes borrow the speckle filter's label / size planes: they are consumed before that filter runs)
-      int* cand = lab;
-      unsigned* votes = reinterpret_cast<unsigned*>(size);
-      hipLaunchKernelGGL(sgbm_init_select_kernel, dim3(nb), dim3(256), 0, s, cand, votes, npix, invalid_scaled);
-      const dim3 gw((unsigned) (((size_t) rows * width1 + 3) / 4));
-      if(D <= 64) hipLaunchKernelGGL(sgbm_wta_kernel<1>, gw, dim3(256), 0, s, Lvol, cand, votes, rows, cols, width1, D, minD, minX1, uniq);
-      else if(D <= 128) hipLaunchKernelGGL(sgbm_wta_kernel<2>, gw, dim3(256), 0, s, Lvol, cand, votes, rows, cols, width1, D, minD, minX1, uniq);
-      else hipLaunchKernelGGL(sgbm_wta_kernel<4>, gw, dim3(256), 0, s, Lvol, cand, votes, rows, cols, width1, D, minD, minX1, uniq);
-      hipLaunchKernelGGL(sgbm_lr_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, cand, votes, d16a, rows, cols, width1, minD, minX1, d12);
+      dispatch_path_width(D, [&](auto np) {
+        hipLaunchKernelGGL(sgbm_path_kernel<decltype(np)::value>, dim3((unsigned) lines), dim3(64), 0, s, m.cost, m.Lvol, rows, width1, D, P1, P2);
+      });
+      hipLaunchKernelGGL(sgbm_init_select_kernel, dim3(nb), dim3(256), 0, s, m.cand, m.votes, npix, invalid_scaled);
+      dispatch_wta_width(D, [&](auto v) {
+        hipLaunchKernelGGL(sgbm_wta_kernel<decltype(v)::value>, dim3((unsigned) (((size_t) rows * width1 + 3) / 4)), dim3(256), 0, s, m.Lvol, m.cand, m.votes, rows, cols,
+                           width1, D, minD, minX1, uniq);
+      });
+      hipLaunchKernelGGL(sgbm_lr_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, m.cand, m.votes, m.d16a, rows, cols, width1, minD, minX1, d12);
     } else {
       // no cost column at all (the image is narrower than the disparity range): every pixel invalid
-      hipLaunchKernelGGL(sgbm_fill_kernel, dim3(nb), dim3(256), 0, s, d16a, npix, (int16_t) invalid_scaled);
+      hipLaunchKernelGGL(sgbm_fill_kernel, dim3(nb), dim3(256), 0, s, m.d16a, npix, (int16_t) invalid_scaled);
     }
     const bool speckle = g.speckle_window > 0;
-    hipLaunchKernelGGL(sgbm_median3_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, d16a, d16b, speckle ? shifted : (uint16_t*) nullptr, rows, cols, invalid_scaled);
+    hipLaunchKernelGGL(sgbm_median3_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, s, m.d16a, m.d16b, speckle ? m.shifted : (uint16_t*) nullptr, rows, cols, invalid_scaled);
     if(speckle) {
       // filterSpeckles(disp, (minDisparity - 1) * 16, speckleWindowSize, 16 * speckleRange): on the map shifted so that invalid = 0
-      launch_speckle_filter_u16(s, shifted, lab, size, rows, cols, 16 * g.speckle_range, g.speckle_window);
-      hipLaunchKernelGGL(sgbm_to_float_kernel, dim3(nb), dim3(256), 0, s, d16b, shifted, g.disp + npix * f, npix, invalid_scaled);
+      launch_speckle_filter_u16(s, m.shifted, m.lab, m.size, rows, cols, 16 * g.speckle_range, g.speckle_window);
+      hipLaunchKernelGGL(sgbm_to_float_kernel, dim3(nb), dim3(256), 0, s, m.d16b, m.shifted, g.disp + npix * f, npix, invalid_scaled);
     } else {
-      hipLaunchKernelGGL(sgbm_to_float_kernel, dim3(nb), dim3(256), 0, s, d16b, (const uint16_t*) nullptr, g.disp + npix * f, npix, invalid_scaled);
+      hipLaunchKernelGGL(sgbm_to_float_kernel, dim3(nb), dim3(256), 0, s, m.d16b, (const uint16_t*) nullptr, g.disp + npix * f, npix, invalid_scaled);
     }
   }
   return true;

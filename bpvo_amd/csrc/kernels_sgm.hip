@@ -13,7 +13,7 @@
 //   sgm_right_cost     the right image's cost volume: right(x, d) = left(x + d, d), clamped                                  per (y, x, d)
 //   sgm_path_packed    one scanline (a row for the horizontal paths, a column for the vertical ones) per wavefront, lanes = pairs of
 //                      disparities, sequential along the line: L(p, d) = min(L'(d), L'(d +- 1) + P1, min L' + P2) - (min L' + P2) +
-//                      C(p, d) in packed int16 saturating arithmetic, neighbours and the wave minimum by DPP                   per line
+//                      C(p, d) in packed int16 saturating arithmetic, neighbours and the wave minimum by DPP (sg_scanline.h)   per line
 //   sgm_wta            winner takes all + the original's sub-pixel expression in double                                      per pixel
 //   speckle filter     connected components (|difference| <= 2 * factor between 4-neighbours) by lock-free union-find over run labels, sizes by
 //                      atomics, regions of <= 100 pixels zeroed — the flood fill of the original finds the same components
@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "sg_scanline.h"
 
 namespace bpvo_hip {
 
@@ -254,28 +255,11 @@ __global__ __launch_bounds__(256) void sgm_right_cost_tile_kernel(const uint16_t
 // One scanline per wavefront.  The four directions of a cost volume — along the rows left to right and back, along the columns down and
 // up — depend on the cost volume alone, and so do the two volumes (left, right image): ALL EIGHT sets of scanlines run in ONE launch,
 // 2 * (2 rows + 2 cols) wavefronts, every direction writing its path costs L into a volume of its own (the original adds them into one
-// sum volume as it goes; the winner-takes-all kernel adds the four in the original's order).
-// L(p, d) = min(L'(d), L'(d +- 1) + P1, min L' + P2) - (min L' + P2) + C(p, d) in int16 saturating arithmetic.  A lane holds 2 NP
-// consecutive disparities as PAIRS of 16-bit values in 32-bit registers: v_pk_add_i16 / v_pk_sub_i16 with clamp and v_pk_min_i16 do two
-// disparities per instruction and the saturation for free (the costs are below 2^15: stereo_check rejects window radii whose box sums
-// are not).  What is sequential is a step's dependent chain — neighbours across lanes, the recurrence, the wave minimum that the next
-// step needs — so the chain is kept on the VALU: neighbours by DPP wave shifts, the minimum by the DPP row ladder + v_readlane (__shfl
-// compiles to ds_bpermute, an LDS round trip each, eight in a row per step).  Memory: batches of SGM_PF steps, see the loop.
-#ifndef SGM_PRIO_VALUE
-#define SGM_PRIO_VALUE 1
-#endif
-#ifndef SGM_PF_VALUE
-#define SGM_PF_VALUE 16
-#endif
-constexpr int SGM_PF = SGM_PF_VALUE;
-typedef short sgm_s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ sgm_s16x2 sgm_pk(unsigned u) { return __builtin_bit_cast(sgm_s16x2, u); }
-__device__ __forceinline__ unsigned sgm_bits(sgm_s16x2 v) { return __builtin_bit_cast(unsigned, v); }
+// sum volume as it goes; the winner-takes-all kernel adds the four in the original's order).  The walk itself: sg_scanline.h.
 template <int NP>
 __global__ __launch_bounds__(64) void sgm_path_packed_kernel(const uint16_t* __restrict__ cost_l, const uint16_t* __restrict__ cost_r, int16_t* __restrict__ Lvol,
                                                              int rows, int cols, int D, int P1, int P2, size_t fs)
 {
-  constexpr int PF = SGM_PF, V = 2 * NP;
   cost_l = sgm_frame(cost_l, fs, blockIdx.y); cost_r = sgm_frame(cost_r, fs, blockIdx.y); Lvol = sgm_frame(Lvol, fs, blockIdx.y);
   // dispatch order: the rows of both cost volumes first (with cols > rows the longest chains of the launch), then the columns
   int side, path, line;
@@ -285,90 +269,17 @@ __global__ __launch_bounds__(64) void sgm_path_packed_kernel(const uint16_t* __r
     else { q -= 4 * rows; side = q / (2 * cols); q -= side * 2 * cols; path = q < cols ? 1 : 3; line = q < cols ? q : q - cols; }
   }
   const int vertical = path & 1, dir = path < 2 ? 1 : -1;
-#if SGM_PRIO_VALUE
-  if(!vertical && cols > rows) __builtin_amdgcn_s_setprio(3);      // the longest chains of the launch first (kernels_sgbm.hip, sgbm_path_kernel)
+#if SG_PRIO_VALUE
+  if(!vertical && cols > rows) __builtin_amdgcn_s_setprio(3);      // the longest chains of the launch first (sg_scanline.h)
 #endif
   const uint16_t* __restrict__ cost = side ? cost_r : cost_l;
   const size_t vol = (size_t) rows * cols * D;
   int16_t* __restrict__ L = Lvol + (size_t) (side * 4 + path) * vol;
-
-  const int lane = threadIdx.x;
   const int nsteps = vertical ? rows : cols;
-  const size_t step_stride = (vertical ? (size_t) cols * D : (size_t) D);
-  const size_t base = vertical ? (size_t) line * D : (size_t) line * cols * D;
-  const int d0 = lane * V;
-  const bool live = d0 < D;                                    // (D is a multiple of 16 and V divides it: a lane is all in or all out)
-  unsigned prev[NP];
-#pragma unroll
-  for(int j = 0; j < NP; ++j) prev[j] = 0u;
-  int prev_min = 0;
-  const sgm_s16x2 P1v = {(short) P1, (short) P1};
-  auto offset = [&](int st) { return base + (size_t) (dir > 0 ? st : nsteps - 1 - st) * step_stride + d0; };
-  // The cost loads are UNCONDITIONAL — the step clamped to the line's last one, the lanes beyond D reading disparity 0: a load inside a
-  // branch makes the compiler wait for it at the end of the branch (s_waitcnt vmcnt(0) right behind every load: the first version of this
-  // kernel spent a full memory round trip per step, 1241 of them per row — that, not arithmetic or shuffles, was its 1.1 ms).
-  const int d0_load = live ? d0 : 0;
-  auto load_offset = [&](int st) { st = min(st, nsteps - 1); return base + (size_t) (dir > 0 ? st : nsteps - 1 - st) * step_stride + d0_load; };
-  using word_t = typename std::conditional<NP == 1, uint32_t, uint64_t>::type;
-  // A scanline is walked in BATCHES of PF steps: the PF cost words of a batch are requested back to back, the PF steps run on registers,
-  // the PF words of path costs are stored back to back.  Loads and stores share one counter on this hardware and may complete out of
-  // order with respect to each other, so the compiler can only wait for "everything" (vmcnt(0)) once both kinds are in flight: a load per
-  // step next to a store per step — the software pipeline of the first versions — degenerates into one full memory round trip per STEP
-  // (1241 of them per row).  In batches the round trip is paid once per PF steps.
-  for(int s0 = 0; s0 < nsteps; s0 += PF) {
-    word_t cw[PF], ow[PF];
-#pragma unroll
-    for(int i = 0; i < PF; ++i) cw[i] = *reinterpret_cast<const word_t*>(cost + load_offset(s0 + i));
-#pragma unroll
-    for(int i = 0; i < PF; ++i) {
-      const word_t cword = cw[i];
-      const short pm = (short) (prev_min + P2);
-      const sgm_s16x2 pmv = {pm, pm};
-      // neighbours by DPP wave shifts (a VALU move: ~10 cycles; ds_bpermute, what __shfl compiles to, is an LDS round trip of ~120): lane
-      // 0 / lane 63 keep the `old` operand — the sentinel 32767 below disparity 0 / (for D = 64 V) behind the last one
-      const unsigned left = (unsigned) __builtin_amdgcn_update_dpp((int) 0x7fff0000u, (int) prev[NP - 1], 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
-      const unsigned right = (unsigned) __builtin_amdgcn_update_dpp((int) 0x00007fffu, (int) prev[0], 0x130 /*wave_shl:1*/, 0xf, 0xf, false);
-      unsigned cur[NP];
-      int mn = 32767;
-#pragma unroll
-      for(int j = 0; j < NP; ++j) {
-        const unsigned below = j > 0 ? prev[j - 1] : left;
-        unsigned above = j < NP - 1 ? prev[j + 1] : right;
-        if(d0 + 2 * j + 2 >= D) above = 0x7fffu;              // the sentinel behind the last disparity
-        const sgm_s16x2 lm = sgm_pk((below >> 16) | (prev[j] << 16));      // (d - 1) of both halves
-        const sgm_s16x2 lp = sgm_pk((prev[j] >> 16) | (above << 16));      // (d + 1) of both halves
-        const sgm_s16x2 c = sgm_pk((unsigned) (cword >> (32 * j)));
-        sgm_s16x2 a = __builtin_elementwise_min(sgm_pk(prev[j]), __builtin_elementwise_add_sat(lm, P1v));
-        a = __builtin_elementwise_min(a, __builtin_elementwise_add_sat(lp, P1v));
-        a = __builtin_elementwise_min(a, pmv);
-        a = __builtin_elementwise_add_sat(__builtin_elementwise_sub_sat(a, pmv), c);
-        cur[j] = sgm_bits(a);
-        if(live) mn = min(mn, min((int) a.x, (int) a.y));
-      }
-      // wave minimum by the DPP ladder (row shifts inside the rows of 16 lanes, then the two row broadcasts): lane 63 ends up with it
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x111 /*row_shr:1*/, 0xf, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x112 /*row_shr:2*/, 0xf, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x114 /*row_shr:4*/, 0xf, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x118 /*row_shr:8*/, 0xf, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x142 /*row_bcast:15*/, 0xa, 0xf, false));
-      mn = min(mn, __builtin_amdgcn_update_dpp(mn, mn, 0x143 /*row_bcast:31*/, 0xc, 0xf, false));
-      word_t out = 0;
-#pragma unroll
-      for(int j = 0; j < NP; ++j) out |= (word_t) cur[j] << (32 * j);
-      ow[i] = out;
-      // (steps past the end of the line — the last batch of a ragged line — leave the state alone: nothing follows them)
-      if(s0 + i < nsteps) {
-        prev_min = __builtin_amdgcn_readlane(mn, 63);
-#pragma unroll
-        for(int j = 0; j < NP; ++j) prev[j] = cur[j];
-      }
-    }
-    if(live) {
-#pragma unroll
-      for(int i = 0; i < PF; ++i)
-        if(s0 + i < nsteps) *reinterpret_cast<word_t*>(L + offset(s0 + i)) = ow[i];
-    }
-  }
+  const long long stride = vertical ? (long long) cols * D : (long long) D;
+  const long long first = vertical ? (long long) line * D : (long long) line * cols * D;
+  // (a backward path walks from the line's last element with the stride negated)
+  sg_walk_line<NP>(cost, L, dir > 0 ? first : first + (nsteps - 1) * stride, dir > 0 ? stride : -stride, nsteps, D, P1, P2);
 }
 
 // winner takes all (first minimum) + the sub-pixel expression of the original in double.  A wavefront per pixel: the D sums are read
@@ -574,12 +485,43 @@ void launch_speckle_filter_u16(hipStream_t s, uint16_t* img, int* lab, int* size
   hipLaunchKernelGGL(sgm_cc_apply_kernel, nb, dim3(256), 0, s, img, lab, size, (int) npix, max_size, frame_bytes);
 }
 
-size_t sgm_scratch_bytes(int rows, int cols, int D)
+// The scratch of ONE frame, carved in one place: the launcher uses the pointers, sgm_scratch_bytes is the same walk on a null base — the
+// stride from a frame's slice to the next (sgm_frame), so the two cannot disagree.
+struct SgmScratch {
+  int pitch;                     // row pitch of the Sobel planes: cols rounded up to 16
+  uint8_t *sob_l, *sob_r;        // [rows][pitch]
+  int *cen_l, *cen_r;            // census codes [rows][cols]
+  uint8_t* pc;                   // pixel-wise cost [rows][cols][D]
+  uint16_t *cost_l, *cost_r;     // box-summed cost volumes
+  int16_t* Lvol;                 // path costs: [side][direction][rows][cols][D]
+  uint16_t* rowsum;              // = Lvol: the row sums borrow the first path-cost volume (the scanline kernel overwrites it later on the same stream)
+  uint16_t *disp_l, *disp_r;
+  int *lab, *size;               // the speckle filter's labels and region sizes
+  size_t bytes;                  // the whole layout, a multiple of 256
+};
+static SgmScratch sgm_layout(int rows, int cols, int D, unsigned char* base)
 {
-  const size_t npix = (size_t) rows * cols, pitch = (size_t) cols + 15 - (cols - 1) % 16;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  return 2 * up(pitch * rows) + 2 * up(npix * 4) + up(npix * D) + 2 * up(npix * D * 2) + up(8 * npix * D * 2) + 2 * up(npix * 2) + 2 * up(npix * 4);
+  const size_t npix = (size_t) rows * cols;
+  Carver w{base};
+  SgmScratch m;
+  m.pitch = cols + 15 - (cols - 1) % 16;
+  m.sob_l = w.take<uint8_t>((size_t) m.pitch * rows);
+  m.sob_r = w.take<uint8_t>((size_t) m.pitch * rows);
+  m.cen_l = w.take<int>(npix);
+  m.cen_r = w.take<int>(npix);
+  m.pc = w.take<uint8_t>(npix * D);
+  m.cost_l = w.take<uint16_t>(npix * D);
+  m.cost_r = w.take<uint16_t>(npix * D);
+  m.Lvol = w.take<int16_t>(8 * npix * D);
+  m.rowsum = reinterpret_cast<uint16_t*>(m.Lvol);
+  m.disp_l = w.take<uint16_t>(npix);
+  m.disp_r = w.take<uint16_t>(npix);
+  m.lab = w.take<int>(npix);
+  m.size = w.take<int>(npix);
+  m.bytes = w.off;
+  return m;
 }
+size_t sgm_scratch_bytes(int rows, int cols, int D) { return sgm_layout(rows, cols, D, nullptr).bytes; }
 
 // SGMStereo::compute (utils/sgm.cc:250-285) for `nframes` rectified pairs of one size, in chunks of `frames_per_launch` frames: every kernel
 // takes a chunk in one launch, frame f of it on the f-th slice of the scratch (sgm_frame).  One frame per launch is one frame after the other
@@ -590,22 +532,9 @@ bool launch_stereo_sgm(hipStream_t s, const SgmLaunch& g)
   const int rows = g.rows, cols = g.cols, D = g.ndisp;
   if(D <= 0 || D % 16 || D > 256) return false;
   const size_t npix = (size_t) rows * cols;
-  const int pitch = cols + 15 - (cols - 1) % 16;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  unsigned char* w = (unsigned char*) g.scratch;
-  uint8_t* sob_l = w; w += up((size_t) pitch * rows);
-  uint8_t* sob_r = w; w += up((size_t) pitch * rows);
-  int* cen_l = (int*) w; w += up(npix * 4);
-  int* cen_r = (int*) w; w += up(npix * 4);
-  uint8_t* pc = w; w += up(npix * D);
-  uint16_t* cost_l = (uint16_t*) w; w += up(npix * D * 2);
-  uint16_t* cost_r = (uint16_t*) w; w += up(npix * D * 2);
-  int16_t* Lvol = (int16_t*) w; w += up(8 * npix * D * 2);      // path costs: [side][direction][rows][cols][D]
-  uint16_t* disp_l = (uint16_t*) w; w += up(npix * 2);
-  uint16_t* disp_r = (uint16_t*) w; w += up(npix * 2);
-  int* lab = (int*) w; w += up(npix * 4);
-  int* size = (int*) w; w += up(npix * 4);
-  const size_t fs = sgm_scratch_bytes(rows, cols, D);           // = w - scratch: the stride from a frame's slice to the next
+  const SgmScratch m = sgm_layout(rows, cols, D, (unsigned char*) g.scratch);
+  const int pitch = m.pitch;
+  const size_t fs = m.bytes;                                    // the stride from a frame's slice to the next
   const int cap = (std::min(std::max(g.sobel_cap, 15), 127)) | 1;
   const int dthreads = (D + 63) / 64 * 64;
   const unsigned nb = (unsigned) ((npix + 255) / 256);
@@ -615,37 +544,31 @@ bool launch_stereo_sgm(hipStream_t s, const SgmLaunch& g)
     const uint8_t* L = g.left + npix * f0;
     const uint8_t* R = g.right + npix * f0;
     const dim3 gpix((pitch + 63) / 64, (rows + 3) / 4, F);
-    hipLaunchKernelGGL(sgm_census_sobel_kernel, gpix, dim3(256), 0, s, L, sob_l, cen_l, rows, cols, pitch, cap, g.census_radius, 0, fs);
-    hipLaunchKernelGGL(sgm_census_sobel_kernel, gpix, dim3(256), 0, s, R, sob_r, cen_r, rows, cols, pitch, cap, g.census_radius, 1, fs);
-    hipLaunchKernelGGL(sgm_pixel_cost_tile_kernel, dim3((cols + SPC_TX - 1) / SPC_TX, rows, F), dim3(256), 0, s, sob_l, sob_r, cen_l, cen_r, pc, rows, cols, pitch, D,
-                       g.census_weight, fs);
+    hipLaunchKernelGGL(sgm_census_sobel_kernel, gpix, dim3(256), 0, s, L, m.sob_l, m.cen_l, rows, cols, pitch, cap, g.census_radius, 0, fs);
+    hipLaunchKernelGGL(sgm_census_sobel_kernel, gpix, dim3(256), 0, s, R, m.sob_r, m.cen_r, rows, cols, pitch, cap, g.census_radius, 1, fs);
+    hipLaunchKernelGGL(sgm_pixel_cost_tile_kernel, dim3((cols + SPC_TX - 1) / SPC_TX, rows, F), dim3(256), 0, s, m.sob_l, m.sob_r, m.cen_l, m.cen_r, m.pc, rows, cols,
+                       pitch, D, g.census_weight, fs);
     {
-      // (the row sums borrow the first path-cost volume: the scanline kernel overwrites it later on the same stream)
-      uint16_t* rowsum = reinterpret_cast<uint16_t*>(Lvol);
       const dim3 nbq((unsigned) ((npix * (size_t) (D / 4) + 255) / 256), F);
-      hipLaunchKernelGGL(sgm_box_rows_kernel, nbq, dim3(256), 0, s, pc, rowsum, rows, cols, D, g.window_radius, fs);
-      hipLaunchKernelGGL(sgm_box_cols_kernel, nbq, dim3(256), 0, s, rowsum, cost_l, rows, cols, D, g.window_radius, fs);
+      hipLaunchKernelGGL(sgm_box_rows_kernel, nbq, dim3(256), 0, s, m.pc, m.rowsum, rows, cols, D, g.window_radius, fs);
+      hipLaunchKernelGGL(sgm_box_cols_kernel, nbq, dim3(256), 0, s, m.rowsum, m.cost_l, rows, cols, D, g.window_radius, fs);
     }
-    if(D <= SRC_MAXD) hipLaunchKernelGGL(sgm_right_cost_tile_kernel, dim3(8u * (unsigned) (((cols + SRC_TX - 1) / SRC_TX * rows + 7) / 8), F), dim3(256), 0, s, cost_l, cost_r, rows, cols, D, fs);
-    else hipLaunchKernelGGL(sgm_right_cost_kernel, dim3(cols, rows, F), dim3(dthreads), 0, s, cost_l, cost_r, rows, cols, D, fs);
-    {
-      const dim3 gp((unsigned) (2 * (2 * rows + 2 * cols)), F);
-      if(D <= 128) hipLaunchKernelGGL(sgm_path_packed_kernel<1>, gp, dim3(64), 0, s, cost_l, cost_r, Lvol, rows, cols, D, g.P1, g.P2, fs);
-      else hipLaunchKernelGGL(sgm_path_packed_kernel<2>, gp, dim3(64), 0, s, cost_l, cost_r, Lvol, rows, cols, D, g.P1, g.P2, fs);
-    }
+    if(D <= SRC_MAXD) hipLaunchKernelGGL(sgm_right_cost_tile_kernel, dim3(8u * (unsigned) (((cols + SRC_TX - 1) / SRC_TX * rows + 7) / 8), F), dim3(256), 0, s, m.cost_l, m.cost_r, rows, cols, D, fs);
+    else hipLaunchKernelGGL(sgm_right_cost_kernel, dim3(cols, rows, F), dim3(dthreads), 0, s, m.cost_l, m.cost_r, rows, cols, D, fs);
+    dispatch_path_width(D, [&](auto np) {
+      hipLaunchKernelGGL(sgm_path_packed_kernel<decltype(np)::value>, dim3((unsigned) (2 * (2 * rows + 2 * cols)), F), dim3(64), 0, s, m.cost_l, m.cost_r, m.Lvol, rows, cols,
+                         D, g.P1, g.P2, fs);
+    });
     for(int side = 0; side < 2; ++side) {
-      uint16_t* disp = side == 0 ? disp_l : disp_r;
-      const int16_t* L4 = Lvol + (size_t) side * 4 * npix * D;
-      {
-        const dim3 gw((unsigned) ((npix + 3) / 4), F);
-        if(D <= 64) hipLaunchKernelGGL(sgm_wta_kernel<1>, gw, dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor, fs);
-        else if(D <= 128) hipLaunchKernelGGL(sgm_wta_kernel<2>, gw, dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor, fs);
-        else hipLaunchKernelGGL(sgm_wta_kernel<4>, gw, dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor, fs);
-      }
+      uint16_t* disp = side == 0 ? m.disp_l : m.disp_r;
+      const int16_t* L4 = m.Lvol + (size_t) side * 4 * npix * D;
+      dispatch_wta_width(D, [&](auto v) {
+        hipLaunchKernelGGL(sgm_wta_kernel<decltype(v)::value>, dim3((unsigned) ((npix + 3) / 4), F), dim3(256), 0, s, L4, disp, npix, D, g.disparity_factor, fs);
+      });
       // speckleFilter(100, 2 * factor) (utils/sgm.cc:898)
-      launch_speckle_filter_u16(s, disp, lab, size, rows, cols, (int) (2 * g.disparity_factor), 100, (int) F, fs);
+      launch_speckle_filter_u16(s, disp, m.lab, m.size, rows, cols, (int) (2 * g.disparity_factor), 100, (int) F, fs);
     }
-    hipLaunchKernelGGL(sgm_lr_check_kernel, dim3(nb, F), dim3(256), 0, s, disp_l, disp_r, g.disp + npix * f0, rows, cols, g.disparity_factor, g.consistency_threshold, fs);
+    hipLaunchKernelGGL(sgm_lr_check_kernel, dim3(nb, F), dim3(256), 0, s, m.disp_l, m.disp_r, g.disp + npix * f0, rows, cols, g.disparity_factor, g.consistency_threshold, fs);
   }
   return true;
 }

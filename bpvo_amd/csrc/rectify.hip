@@ -1,6 +1,6 @@
 // libbpvo_hip, host side: rectification on the device (include/bpvo_hip/c_api.h; the rule: rectify_math.h; the kernel: kernels_rectify.hip).
 // A set call builds the map of one camera side on the host — 467 k entries for a KITTI frame, once — and uploads it; a call rectifies all its
-// frames, both sides, in one launch from a table of frames (rectify_queue), which the raw entry points of vo.hip put in front of the stereo
+// frames, both sides, in one launch from a table of frames (rectify_queue), which stereo_front (stereo.hip) puts in front of the stereo
 // front-end.  No existing call launches, allocates or reads anything of this file.
 #include "host_ctx.h"
 #include "rectify_math.h"

@@ -342,7 +342,8 @@ def np_sgm(L, R, ndisp, cap, crad, wrad, p1, p2, thr, factor, cw):
 
 
 @pytest.mark.parametrize("rows,cols,kw", [(40, 72, dict(ndisp=16)), (33, 61, dict(ndisp=32, crad=1, wrad=1, p1=60, p2=900)),
-                                          (36, 50, dict(ndisp=16, cap=40, thr=2, cw=0.5, factor=16.0))])
+                                          (36, 50, dict(ndisp=16, cap=40, thr=2, cw=0.5, factor=16.0)),
+                                          (15, 40, dict(ndisp=16))])                                              # columns shorter than a 16-step batch of the device's scanline walk
 def test_sgm_oracle_against_a_numpy_evaluation_of_the_definition(orc, rows, cols, kw):
     d = synth.make_stereo_pair(rows, cols, 6, z0=2.5)
     rng = np.random.default_rng(rows)
@@ -387,7 +388,8 @@ def _sgm_params(ctx, **kw):
                                           (50, 70, dict(ndisp=16, wrad=3)),
                                           # the largest window and Sobel cap the device path admits: box sums up to 121 * 255 = 30855, just
                                           # below the int16 range in which the original's saturating additions would start to clip
-                                          (90, 160, dict(ndisp=32, wrad=5, cap=127, cw=1.0 / 6.0)), (80, 140, dict(ndisp=144, wrad=4, cap=99))])
+                                          (90, 160, dict(ndisp=32, wrad=5, cap=127, cw=1.0 / 6.0)), (80, 140, dict(ndisp=144, wrad=4, cap=99)),
+                                          (15, 40, dict(ndisp=16))])      # vertical lines shorter than one 16-step batch of the scanline walk (sg_scanline.h)
 def test_hip_sgm_bit_exact(hip, orc, rows, cols, kw):
     d = synth.make_stereo_pair(rows, cols, 4, z0=8.0 if cols > 700 else 4.0)
     rng = np.random.default_rng(cols)
@@ -582,7 +584,8 @@ def _sgbm_pair(rows, cols, seed, z0=4.0):
                                           (33, 75, dict(ndisp=32, wsz=3, p1=8, p2=32, uniq=10, d12=1)),
                                           (36, 96, dict(ndisp=16, wsz=5, p1=24, p2=96, cap=31, uniq=5, spw=20, spr=2)),
                                           (30, 80, dict(ndisp=16, wsz=9, mind=3, p1=50, p2=200, uniq=15, d12=2, spw=1)),
-                                          (28, 70, dict(ndisp=16, wsz=0, uniq=-1, d12=-1, cap=63))])
+                                          (28, 70, dict(ndisp=16, wsz=0, uniq=-1, d12=-1, cap=63)),
+                                          (15, 30, dict(ndisp=16, wsz=3))])                                       # 14 cost columns, 15 rows: every line shorter than a 16-step batch
 def test_sgbm_oracle_against_a_numpy_evaluation_of_the_definition(orc, rows, cols, kw):
     left, right, _ = _sgbm_pair(rows, cols, 7)
     got = orc_sgbm(orc, left, right, **kw)
@@ -622,7 +625,8 @@ def _hip_sgbm_params(ctx, **kw):
                                           (64, 300, dict(ndisp=256, wsz=5, p1=10, p2=120, uniq=5)),
                                           (50, 70, dict(ndisp=16, wsz=0, uniq=-1, d12=-1, cap=63)),
                                           (40, 90, dict(ndisp=16, wsz=11, p1=3, p2=4)),
-                                          (33, 60, dict(ndisp=64, wsz=3))])                                      # no cost column: every pixel invalid
+                                          (33, 60, dict(ndisp=64, wsz=3)),                                       # no cost column: every pixel invalid
+                                          (15, 30, dict(ndisp=16, wsz=3))])                                      # width1 = 14 and 15 rows: every line of every family shorter than one batch
 def test_hip_sgbm_bit_exact(hip, orc, rows, cols, kw):
     left, right, d = _sgbm_pair(rows, cols, 4, z0=8.0 if cols > 700 else 4.0)
     p = hip.default_params(); p.numPyramidLevels = 2; p.verbosity = capi.VERB_SILENT
