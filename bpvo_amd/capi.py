@@ -762,6 +762,17 @@ class Context:
         self._ck(self.b.fn("seq_get_params")(self.h, int(s), C.byref(p)))
         return p
 
+    # -- normalised intensity (an extension: no reference member)
+    def set_intensity_normalization(self, radius):
+        """bpvo_hip_set_intensity_normalization: -1 off (the default), 0 whole image (median / MAD), 1 .. 15 local ((2 R + 1)^2 window); only
+        on an Intensity context and while no frame slot holds data."""
+        self.call("set_intensity_normalization", int(radius))
+
+    def get_intensity_normalization(self):
+        r = C.c_int()
+        self._ck(self.b.fn("get_intensity_normalization")(self.h, C.byref(r)))
+        return int(r.value)
+
     # -- point budget (an extension: no reference member)
     @staticmethod
     def _budget_arg(max_points):

@@ -112,6 +112,7 @@ FrameJob make_frame_job(bpvo_hip_ctx* c, FrameSlot& f, int l)
   j.cen = f.cen[l];
   j.ch0 = (f.ch0_valid && f.lazy[l] != 2) ? f.ch0[l] : nullptr;      // (a census-only level has no channel-0 plane)
   j.scratch = f.scratch;
+  j.inorm = c->d_inorm ? c->d_inorm + ((size_t) (&f - c->frames.data()) * c->L + l) : nullptr;
   j.desc = f.desc[l];
   j.sal = f.sal_state[l] == FrameSlot::SAL_STORED ? f.sal[l] : nullptr;      // (null: the selection does not store the map)
   j.flag = f.flag[l];

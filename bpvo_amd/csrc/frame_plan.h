@@ -11,27 +11,29 @@ namespace bpvo_hip_host {
 // of the smoothed image (SMOOTHED_CENSUS: the census-and-blur kernel, then the blur of the planes) or the planes stay UNSMOOTHED (the census
 // kernel — of the smoothed image where sigmaPriorToCensusTransform > 0 —, then the plain bit-planes kernel)
 enum DescriptorForm { DF_BITPLANES_FUSED, DF_BITPLANES_SMOOTHED_CENSUS, DF_BITPLANES_UNSMOOTHED, DF_INTENSITY, DF_LAPLACIAN, DF_GRADIENT,
-                      DF_FIELDS_1ST, DF_FIELDS_2ND, DF_CENTRAL_DIFFERENCE, DF_LATCH };
-inline DescriptorForm descriptor_form(const bpvo_hip_params& p, int C)
+                      DF_FIELDS_1ST, DF_FIELDS_2ND, DF_CENTRAL_DIFFERENCE, DF_LATCH, DF_INTENSITY_NORM };
+// intensity_norm_radius: bpvo_hip_set_intensity_normalization (-1: off).  It is a mode of the Intensity descriptor: where the parameters ask for
+// Intensity and the mode is on the plane is the normalised one (DF_INTENSITY_NORM, kernels_intensity_norm.hip), every other form ignores it
+inline DescriptorForm descriptor_form(const bpvo_hip_params& p, int C, int intensity_norm_radius = -1)
 {
   if(p.descriptor == BPVO_DESC_CENTRAL_DIFFERENCE) return DF_CENTRAL_DIFFERENCE;
   if(p.descriptor == BPVO_DESC_LATCH) return DF_LATCH;
   if(C == 5) return DF_FIELDS_1ST;
   if(C == 10) return DF_FIELDS_2ND;
   if(C == 3) return DF_GRADIENT;
-  if(C == 1) return p.descriptor == BPVO_DESC_LAPLACIAN ? DF_LAPLACIAN : DF_INTENSITY;
+  if(C == 1) return p.descriptor == BPVO_DESC_LAPLACIAN ? DF_LAPLACIAN : (intensity_norm_radius >= 0 ? DF_INTENSITY_NORM : DF_INTENSITY);
   if(!(p.sigmaBitPlanes > 0.0f)) return DF_BITPLANES_UNSMOOTHED;
   return p.sigmaPriorToCensusTransform > 0.0f ? DF_BITPLANES_SMOOTHED_CENSUS : DF_BITPLANES_FUSED;
 }
 
 // ---- levels in one launch (kernels_frame.hip level_job).  Few frames: every per-level launch is a latency floor, so a stage of at most
 // merge_levels_max_frames frames (option "levels_in_one_launch_max_frames") with more than one tested level runs them in one — where the
-// stage's kernels can: the descriptor kernels that read the level from the job (the two blurred bit-planes forms, intensity), the selection
+// stage's kernels can: the descriptor kernels that read the level from the job (the two blurred bit-planes forms, intensity, normalised intensity), the selection
 // when EVERY level is on the tiled path (NMS radius <= 1), the template build always.
 inline bool few_frames(int count, int merge_levels_max_frames, int tested_levels) { return count <= merge_levels_max_frames && tested_levels > 1; }
 inline bool merge_descriptor_levels(int count, int merge_levels_max_frames, int tested_levels, DescriptorForm form)
 {
-  return (form == DF_BITPLANES_FUSED || form == DF_BITPLANES_SMOOTHED_CENSUS || form == DF_INTENSITY) && few_frames(count, merge_levels_max_frames, tested_levels);
+  return (form == DF_BITPLANES_FUSED || form == DF_BITPLANES_SMOOTHED_CENSUS || form == DF_INTENSITY || form == DF_INTENSITY_NORM) && few_frames(count, merge_levels_max_frames, tested_levels);
 }
 inline bool merge_selection_levels(int count, int merge_levels_max_frames, int tested_levels, bool every_level_tiled)
 {

@@ -1,6 +1,7 @@
 // libbpvo_hip, host side: the per-frame stages — VisualOdometryFrame::setData (pyramid, descriptors) and setTemplate (saliency, selection, points,
 // normalisation, template pixels and gradients) for batches of frames — and the accessors of their results.
 #include "host_ctx.h"
+#include "intensity_norm_math.h"
 
 using namespace bpvo_hip;
 using namespace bpvo_hip_host;
@@ -63,7 +64,7 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
   if(!geom) return BPVO_ERR_INVALID_ARG;
   const size_t npix = geom[0].npix;
   const bpvo_hip_params& p = c->params;
-  const DescriptorForm form = descriptor_form(p, c->C);
+  const DescriptorForm form = descriptor_form(p, c->C, c->inorm_radius);
   hipStream_t s = fr.stream;
   if(!on_device) {
     for(int i = 0; i < count; ++i) {
@@ -148,6 +149,7 @@ int frames_set_data_slots(bpvo_hip_ctx* c, const int* slots, int count, const ui
           launch_bitplanes(s, f, p.sigmaBitPlanes, c->gauss_k, 0);
           break;
         case DF_INTENSITY: launch_intensity(s, f); break;
+        case DF_INTENSITY_NORM: launch_intensity_norm(s, f, c->inorm_radius); break;
         case DF_LAPLACIAN: launch_laplacian(s, f.jobs, f.W, f.R, count, p.laplacianKernelSize); break;
         case DF_GRADIENT: launch_gradient_descriptor(s, f.jobs, f.W, f.R, count, c->grad_pre); break;
         case DF_FIELDS_1ST:
@@ -393,6 +395,39 @@ int check_point_budget(bpvo_hip_ctx* c, const int* max_points, int n_levels)
 }  // namespace bpvo_hip_host
 
 extern "C" {
+
+// ---- normalised intensity (an extension: no reference member) ----------------------------------------------------------
+int bpvo_hip_set_intensity_normalization(bpvo_hip_ctx* c, int radius)
+{
+  CHECK_CTX(c);
+  if(descriptor_form(c->params, c->C) != DF_INTENSITY)
+    return fail(c, BPVO_ERR_UNSUPPORTED, "intensity normalization: a mode of the Intensity descriptor, this context has another");
+  if(radius < kInormOff || radius > kInormMaxRadius)
+    return fail(c, BPVO_ERR_INVALID_ARG, "intensity normalization: radius -1 (off), 0 (whole image) or 1 .. 15 (local)");
+  // the setting fixes what the stored planes mean: not while any holds data (frame slots, and through them every sequence and rig member)
+  for(const FrameSlot& f : c->frames)
+    if(f.has_data || f.has_template)
+      return fail(c, BPVO_ERR_INVALID_ARG, "intensity normalization: a frame slot holds data; set it before the first frame or once every slot is cleared");
+  (void) hipSetDevice(c->device);
+  if(radius == 0 && !c->d_inorm) {
+    // bins and tickets are zero between stages: once here, by the kernels from then on
+    const size_t n = (size_t) c->n_frames * c->L;
+    HIP_CK(c, c->d_inorm.alloc(n));
+    HIP_CK(c, hipMemsetAsync(c->d_inorm, 0, n * sizeof(InormScratch), c->stream));
+    HIP_CK(c, hipStreamSynchronize(c->stream));
+  } else if(radius != 0 && c->d_inorm) {
+    HIP_CK(c, hipStreamSynchronize(c->stream));
+    c->d_inorm.reset();
+  }
+  c->inorm_radius = radius;
+  return BPVO_OK;
+}
+int bpvo_hip_get_intensity_normalization(const bpvo_hip_ctx* c, int* radius)
+{
+  if(!c || !radius) return BPVO_ERR_INVALID_ARG;
+  *radius = c->inorm_radius;
+  return BPVO_OK;
+}
 
 // ---- point budget (an extension: no reference member) -----------------------------------------------------------------
 int bpvo_hip_set_point_budget(bpvo_hip_ctx* c, const int* max_points, int n_levels)

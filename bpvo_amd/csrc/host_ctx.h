@@ -218,6 +218,10 @@ struct bpvo_hip_ctx {
 
   bpvo_hip_params params;
   int point_budget[kMaxLevels] = {};   // bpvo_hip_set_point_budget: template points a level keeps at most, the most salient first (0: no budget)
+  // bpvo_hip_set_intensity_normalization: -1 off, 0 whole image, 1 .. 15 local (intensity_norm_math.h); d_inorm [n_frames][L]: the whole-image
+  // form's scratch per (slot, level), held only while the radius is 0
+  int inorm_radius = -1;
+  DeviceBuf<InormScratch> d_inorm;
   bpvo_hip_start_policy start_policy = {BPVO_START_KEYFRAME_POSE, -1, 0.0f};   // bpvo_hip_set_start_policy: where the addFrame drivers start (vo_state.h); bodies without their own run it
   float K[9];
   float baseline;

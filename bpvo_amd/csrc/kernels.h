@@ -80,6 +80,9 @@ void launch_pyramid_levels(hipStream_t s, const FrameJob* src_row, int job_pitch
 // levels' row of the table [level][job_pitch] and W x R that level's size — the grid is sized for it.  Built in one place: host_ctx.h frame_launch
 struct FrameLaunch { const FrameJob* jobs; int W, R, nframes, nlevels, job_pitch; };
 void launch_intensity(hipStream_t s, const FrameLaunch& f);
+// normalised intensity (kernels_intensity_norm.hip): radius 0 — histogram + table, then the table applied (two launches; FrameJob::inorm);
+// radius 1 .. 15 — the local form, one launch
+void launch_intensity_norm(hipStream_t s, const FrameLaunch& f, int radius);
 void launch_gradient_descriptor(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, const GaussTaps& pre);   // (I, Ix, Iy), C = 3
 void launch_descriptor_fields(hipStream_t s, const FrameJob* jobs, int W, int R, int nframes, int second_order, const GaussTaps& g1,
                               const GaussTaps& g2);   // C = 5 / 10

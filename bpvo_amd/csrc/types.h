@@ -231,6 +231,11 @@ struct PairJob {
   float         good_thr;  // goodPointThreshold
 };
 
+// Normalised intensity, whole-image form (bpvo_hip_set_intensity_normalization, radius 0; kernels_intensity_norm.hip): the scratch of one
+// (frame slot, level) — the histogram's bins and the ticket of its workgroups, both zero between stages (the last workgroup clears them), and the
+// table the apply launch reads.  One per (slot, level): frame stages that run side by side on lanes or streams work on different slots.
+struct InormScratch { uint32_t bins[256]; float table[256]; uint32_t ticket; uint32_t pad[31]; };
+
 // selection / template-build job for one (frame, level)
 constexpr int kDfPlanes = 7;
 struct FrameJob {
@@ -240,6 +245,7 @@ struct FrameJob {
   GPtr<float> ch0;       // [rows*cols] copy of descriptor channel 0 (C = 8): the saliency map needs little else (Q7), and a
                             // compact plane spares it a strided pass over the 32-byte records
   GPtr<float> scratch;   // descriptor fields: kDfPlanes work planes of the level-0 size
+  GPtr<InormScratch> inorm;   // normalised intensity, radius 0: bins, ticket and table of this (slot, level); null otherwise
   GPtr<float> sal;       // [rows*cols]
   GPtr<uint8_t> flag;      // [rows*cols] candidate flags (NMS radius > 1)
   GPtr<unsigned long long> words;   // [rows * ceil(cols / 64)] candidate bits, the same storage (NMS radius <= 1)

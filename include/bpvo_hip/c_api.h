@@ -343,6 +343,33 @@ int bpvo_hip_seq_get_point_budget(const bpvo_hip_ctx* ctx, int seq, int* max_poi
  *   not bind; n_ties_kept = K - #{S > t}, the candidates with S == t that stayed (0 when the budget did not bind).  Outputs may be null. */
 int bpvo_hip_get_selection_info(bpvo_hip_ctx* ctx, int slot, int level, int* n_candidates, float* threshold, int* n_ties_kept);
 
+/* ---- Normalised intensity: a mode of the Intensity descriptor that survives exposure changes.  AN EXTENSION: the reference has no such member
+ * (its Intensity descriptor is float(I) and stands or falls with brightness constancy).  Off by default; while it is off nothing changes, and
+ * nothing is launched or allocated for it.  With the mode on, the descriptor plane of every pyramid level is computed on the device from THAT
+ * level's u8 image I (n_px pixels) by the rule below (as code: bpvo_amd/csrc/intensity_norm_math.h), and everything downstream — saliency,
+ * selection, point budget, templates, Gauss-Newton, scoring, covariance — reads the plane as it reads float(I).
+ * radius == 0, whole image: h = the 256-bin histogram of I; med = the smallest v with sum_{u <= v} h[u] >= (n_px + 1) / 2 (integer division: the
+ *   lower median); mad = the smallest k with #{|I - med| <= k} >= (n_px + 1) / 2, from the same histogram folded about med; m = max(mad, 1);
+ *   c = 32.0 / (1.4826 * m) in f64; D(x) = (float) ((double) (I(x) - med) * c): a 256-entry table applied to the image.
+ * radius R in 1 .. 15, local: the window of a pixel is [x - R, x + R] x [y - R, y + R] cut to the image, n pixels; S1 = sum I and S2 = sum I^2 over
+ *   it, integers; X = n * I(x, y) - S1 (32 bits); V = n * S2 - S1^2 (64 bits); Vf = max(V, 4 * n * n) — a floor of two grey levels on the window's
+ *   standard deviation, so that flat regions do not amplify noise; D = (float) (32.0 * (double) X / sqrt((double) Vf)), f64 product, square root
+ *   and quotient each correctly rounded.  The same R at every level.
+ * Units: both forms give 32 descriptor units per robust standard deviation (of the image, or of the window).  minSaliency and the tau of
+ *   bpvo_hip_score_poses are in those units while the mode is on, not in grey levels.
+ * Invariance: an exact affine map I' = a * I + b with a a power of two and no clipping leaves D unchanged bit for bit — in the local form wherever
+ *   the floor binds in neither image.
+ * bpvo_hip_set_intensity_normalization (an extension, no reference member): radius -1 off (the default), 0 whole image, 1 .. 15 local.  It is
+ *   context-wide — it fixes what the stored planes mean — and covers every entry point that runs a data stage: single frames from host or device
+ *   memory, bpvo_hip_add_frame, bpvo_hip_add_frames with per-sequence cameras, the stereo and raw-stereo entry points, rigs, bpvo_hip_batch_run
+ *   with any number of lanes.  Allowed only while no frame slot of the context holds data or a template (and so no sequence or rig member holds
+ *   frames: bpvo_hip_frame_clear, bpvo_hip_seq_reset and their like empty them): BPVO_ERR_INVALID_ARG otherwise.  Any other radius:
+ *   BPVO_ERR_INVALID_ARG.  A context whose descriptor is not Intensity: BPVO_ERR_UNSUPPORTED.  After a refusal bpvo_hip_last_error names the
+ *   cause and the setting is what it was.
+ * bpvo_hip_get_intensity_normalization (an extension, no reference member): the setting. */
+int bpvo_hip_set_intensity_normalization(bpvo_hip_ctx* ctx, int radius);
+int bpvo_hip_get_intensity_normalization(const bpvo_hip_ctx* ctx, int* radius);
+
 /* ---- batches of independent frame pairs (BASELINE.json config 5).
  * Pair p uses frame slots 2p (reference/template frame A) and 2p+1 (current frame B) and workspace p.
  * For each pair: A.setData, A.setTemplate, B.setData, estimatePose(A, B, Identity) -> poses[p].

@@ -180,6 +180,14 @@ inline AlgorithmParameters AlgorithmParametersFromFile(const std::string& filena
   return p;
 }
 
+/* key `intensityNormalizationRadius` (an extension, no reference key; default -1 = off): what setIntensityNormalization of the facade classes
+ * takes — vo.setIntensityNormalization(IntensityNormalizationRadiusFromFile(cfg)) next to AlgorithmParametersFromFile(cfg).  It is no field of
+ * AlgorithmParameters: those are the reference's 35 */
+inline int IntensityNormalizationRadiusFromFile(const std::string& filename)
+{
+  return ConfigFile(filename).get<int>("intensityNormalizationRadius", -1);
+}
+
 /* ToString (reference: bpvo/types.cc:109-264) — the strings the apps print, spelling included ("CenteralDifference") */
 inline std::string ToString(LossFunctionType t)
 {

@@ -211,6 +211,9 @@ class Device {
   /* the point budget (c_api.h bpvo_hip_set_point_budget; an extension, no counterpart in the reference): the context's, or sequence seq's own */
   void setPointBudget(const std::vector<int>& maxPoints) { check(bpvo_hip_set_point_budget(_ctx, maxPoints.data(), (int) maxPoints.size())); }
   void setPointBudget(int seq, const std::vector<int>& maxPoints) { check(bpvo_hip_seq_set_point_budget(_ctx, seq, maxPoints.data(), (int) maxPoints.size())); }
+  /* normalised intensity (c_api.h bpvo_hip_set_intensity_normalization; an extension, no counterpart in the reference) */
+  void setIntensityNormalization(int radius) { check(bpvo_hip_set_intensity_normalization(_ctx, radius)); }
+  int intensityNormalization() const { int r = -1; check(bpvo_hip_get_intensity_normalization(_ctx, &r)); return r; }
   /* finestLevel points at level 0 and a quarter of the level below at every level above it, rounded down to a multiple of 16, never below 256 */
   std::vector<int> quarteredPointBudget(int finestLevel) const
   {
@@ -275,6 +278,9 @@ class VisualOdometryFrame {
     if(!v.empty()) _dev->check(bpvo_hip_get_jacobians(_dev->ctx(), _slot, level, v.data()));
     return v;
   }
+  /* normalised intensity (an extension; c_api.h bpvo_hip_set_intensity_normalization): -1 off, 0 whole image, 1 .. 15 local; the frame's context's, while none of its frames holds data */
+  void setIntensityNormalization(int radius) { _dev->setIntensityNormalization(radius); }
+  int intensityNormalization() const { return _dev->intensityNormalization(); }
   int slot() const { return _slot; }
   const std::shared_ptr<detail::Device>& device() const { return _dev; }
  private:
@@ -323,6 +329,9 @@ class VisualOdometryPoseEstimator {
     for(const auto& s : st) ret.push_back(OptimizerStatistics(s));
     return ret;
   }
+  /* normalised intensity (an extension; c_api.h bpvo_hip_set_intensity_normalization): -1 off, 0 whole image, 1 .. 15 local; the estimator's context's, while none of its frames holds data */
+  void setIntensityNormalization(int radius) { _dev->setIntensityNormalization(radius); }
+  int intensityNormalization() const { return _dev->intensityNormalization(); }
   float getFractionOfGoodPoints(float thresh) const
   {
     float f = 0.0f;
@@ -451,6 +460,9 @@ class VisualOdometry {
   const Trajectory& trajectory() const { return _trajectory; }   // bpvo/vo.h:98
   /* scheduling options of the device context (c_api.h "Options"; the reference has none) */
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  /* normalised intensity (an extension; c_api.h bpvo_hip_set_intensity_normalization): -1 off, 0 whole image, 1 .. 15 local; before the first frame */
+  void setIntensityNormalization(int radius) { _dev->setIntensityNormalization(radius); }
+  int intensityNormalization() const { return _dev->intensityNormalization(); }
   /* at most maxPoints[l] template points at level l, the most salient first (an extension; c_api.h bpvo_hip_set_point_budget); from the next key frame on */
   void setPointBudget(const std::vector<int>& maxPoints) { _dev->setPointBudget(maxPoints); }
   /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
@@ -618,6 +630,9 @@ class VisualOdometrySequences {
     _trajectories.at((size_t) s)._poses.clear();
   }
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  /* normalised intensity (an extension; c_api.h bpvo_hip_set_intensity_normalization): -1 off, 0 whole image, 1 .. 15 local; before the first frame */
+  void setIntensityNormalization(int radius) { _dev->setIntensityNormalization(radius); }
+  int intensityNormalization() const { return _dev->intensityNormalization(); }
   /* at most maxPoints[l] template points at level l of sequence s, the most salient first (an extension; c_api.h bpvo_hip_seq_set_point_budget); an
    * empty list returns the sequence to the context's budget */
   void setPointBudget(int s, const std::vector<int>& maxPoints) { _dev->setPointBudget(s, maxPoints); }
@@ -741,6 +756,9 @@ class RigVisualOdometry {
     return n;
   }
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  /* normalised intensity (an extension; c_api.h bpvo_hip_set_intensity_normalization): -1 off, 0 whole image, 1 .. 15 local; before the first frame */
+  void setIntensityNormalization(int radius) { _dev->setIntensityNormalization(radius); }
+  int intensityNormalization() const { return _dev->intensityNormalization(); }
   /* at most maxPoints[l] template points at level l, the most salient first (an extension; c_api.h bpvo_hip_set_point_budget); from the next key frame on */
   void setPointBudget(const std::vector<int>& maxPoints) { _dev->setPointBudget(maxPoints); }
   /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
@@ -863,6 +881,9 @@ class RigsVisualOdometry {
     return n;
   }
   void setOption(const std::string& name, double value) { _dev->setOption(name, value); }
+  /* normalised intensity (an extension; c_api.h bpvo_hip_set_intensity_normalization): -1 off, 0 whole image, 1 .. 15 local; before the first frame */
+  void setIntensityNormalization(int radius) { _dev->setIntensityNormalization(radius); }
+  int intensityNormalization() const { return _dev->intensityNormalization(); }
   /* at most maxPoints[l] template points at level l, the most salient first (an extension; c_api.h bpvo_hip_set_point_budget); from the next key frame on */
   void setPointBudget(const std::vector<int>& maxPoints) { _dev->setPointBudget(maxPoints); }
   /* ... given for the finest level, a quarter of it per level above (multiples of 16, never below 256) */
