@@ -110,6 +110,21 @@ def _start_info_dict(r: StartInfo):
                 scores=scores)
 
 
+class DisparityFusion(C.Structure):
+    """bpvo_hip_disparity_fusion: mode (0 off, 1 on) and the filter's parameters, in disparity pixels (gate: standard deviations)."""
+    _fields_ = [("mode", C.c_int), ("measurement_sigma", C.c_float), ("process_sigma", C.c_float), ("gate", C.c_float), ("max_fill_sigma", C.c_float)]
+
+
+class DisparityFusionInfo(C.Structure):
+    """bpvo_hip_disparity_fusion_info: the class counts of a sequence's last fusion, whether it predicted, the slot it wrote, the motion it used."""
+    _fields_ = [("fused", C.c_uint32), ("replaced", C.c_uint32), ("measured", C.c_uint32), ("filled", C.c_uint32), ("none", C.c_uint32),
+                ("predicted", C.c_int), ("slot", C.c_int), ("reserved_", C.c_int), ("motion", C.c_float * 16)]
+
+
+def disparity_fusion(mode=1, measurement_sigma=0.0, process_sigma=0.0, gate=0.0, max_fill_sigma=0.0) -> DisparityFusion:
+    return DisparityFusion(int(mode), float(measurement_sigma), float(process_sigma), float(gate), float(max_fill_sigma))
+
+
 class Camera(C.Structure):
     """bpvo_hip_camera: one sequence's calibration and image size (bpvo_hip_create_sequences, bpvo_hip_seq_set_camera)."""
     _fields_ = [("K", C.c_float * 9), ("baseline", C.c_float), ("rows", C.c_int), ("cols", C.c_int)]
@@ -1153,6 +1168,96 @@ class Context:
         out = StartInfo()
         self.call("rigs_start_info", int(rig), int(which), C.byref(out))
         return _start_info_dict(out)
+
+    # -- disparity fusion (bpvo_hip_set_disparity_fusion ...; an extension: no reference member; HIP library only)
+    @staticmethod
+    def _fusion_arg(f):
+        if f is None or isinstance(f, DisparityFusion):
+            return f
+        if isinstance(f, dict):
+            return disparity_fusion(**f)
+        return disparity_fusion(*f)
+
+    @staticmethod
+    def _fusion_dict(f: DisparityFusion):
+        return dict(mode=int(f.mode), measurement_sigma=float(f.measurement_sigma), process_sigma=float(f.process_sigma), gate=float(f.gate),
+                    max_fill_sigma=float(f.max_fill_sigma))
+
+    @staticmethod
+    def _fusion_info_dict(r: DisparityFusionInfo):
+        return dict(fused=int(r.fused), replaced=int(r.replaced), measured=int(r.measured), filled=int(r.filled), none=int(r.none),
+                    predicted=bool(r.predicted), slot=int(r.slot), motion=np.array(r.motion, np.float32).reshape(4, 4))
+
+    def set_disparity_fusion(self, fusion):
+        """bpvo_hip_set_disparity_fusion: the context's setting — a DisparityFusion, a dict of its fields or a tuple in their order."""
+        f = self._fusion_arg(fusion)
+        self.call("set_disparity_fusion", C.byref(f))
+
+    def get_disparity_fusion(self):
+        f = DisparityFusion()
+        self._ck(self.b.fn("get_disparity_fusion")(self.h, C.byref(f)))
+        return self._fusion_dict(f)
+
+    def seq_set_disparity_fusion(self, s, fusion):
+        """bpvo_hip_seq_set_disparity_fusion: sequence s's own setting; None returns it to the context's."""
+        f = self._fusion_arg(fusion)
+        self.call("seq_set_disparity_fusion", int(s), None if f is None else C.byref(f))
+
+    def seq_get_disparity_fusion(self, s):
+        """(setting dict, True if it is the sequence's own)"""
+        f, own = DisparityFusion(), C.c_int()
+        self._ck(self.b.fn("seq_get_disparity_fusion")(self.h, int(s), C.byref(f), C.byref(own)))
+        return self._fusion_dict(f), bool(own.value)
+
+    def _fused_maps(self, name, args, shape):
+        D, V = np.empty(shape, np.float32), np.empty(shape, np.float32)
+        self.call(name, *args, D.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p))
+        return D, V
+
+    def vo_get_fused_disparity(self):
+        """bpvo_hip_vo_get_fused_disparity: (disparity, variance) [rows, cols] f32 that add_frame's sequence carries."""
+        return self._fused_maps("vo_get_fused_disparity", (), (self.rows, self.cols))
+
+    def seq_get_fused_disparity(self, s):
+        cam = self.seq_get_camera(int(s))
+        return self._fused_maps("seq_get_fused_disparity", (int(s),), (cam.rows, cam.cols))
+
+    def vo_disparity_fusion_info(self):
+        out = DisparityFusionInfo()
+        self.call("vo_disparity_fusion_info", C.byref(out))
+        return self._fusion_info_dict(out)
+
+    def seq_disparity_fusion_info(self, s):
+        out = DisparityFusionInfo()
+        self.call("seq_disparity_fusion_info", int(s), C.byref(out))
+        return self._fusion_info_dict(out)
+
+    def fuse_disparities(self, disps, poses, seq=None):
+        """bpvo_hip_fuse_disparities: the carried maps of sequence seq[i] (None: 0 .. n-1) advance by poses[i] [4, 4] with the measured map disps[i]
+        (2-D f32 of the sequence's camera size)."""
+        n = len(disps)
+        ids, p_ids = self._seq_ids(n, seq)
+        packed = np.concatenate([_f32(d).reshape(-1) for d in disps])
+        Tf = _f32(poses).reshape(n, 16)
+        self.call("fuse_disparities", n, p_ids, packed.ctypes.data_as(C.c_void_p), 0, Tf.ctypes.data_as(C.c_void_p))
+
+    def fuse_disparities_device(self, n, d_disps_ptr, poses, seq=None):
+        """fuse_disparities with the packed maps already in device memory."""
+        ids, p_ids = self._seq_ids(n, seq)
+        Tf = _f32(poses).reshape(n, 16)
+        self.call("fuse_disparities", int(n), p_ids, C.c_void_p(d_disps_ptr), 1, Tf.ctypes.data_as(C.c_void_p))
+
+    def get_disparity(self, slot, shape=None):
+        """bpvo_hip_get_disparity: frame slot `slot`'s disparity map (shape: the slot's camera size; None: the context's)."""
+        out = np.empty((self.rows, self.cols) if shape is None else tuple(shape), np.float32)
+        self.call("get_disparity", int(slot), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def disparity_fusion_counts(self):
+        """bpvo_hip_disparity_fusion_counts: (kernel launches, pixels updated) so far."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self.call("disparity_fusion_counts", C.byref(a), C.byref(b))
+        return a.value, b.value
 
     # -- batches
     def _stats_array(self, st, n_pairs):

@@ -328,6 +328,9 @@ const std::vector<OptionDef>& option_table()
                 if(!c->rect.timed || hipEventSynchronize(c->rect.t1) != hipSuccess || hipEventElapsedTime(&ms, c->rect.t0, c->rect.t1) != hipSuccess) return -1.0;
                 return (double) ms;
               }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
+    // read-only: the durations of the last disparity-fusion stage's two launches between events on the stream, ms; -1 unless bpvo_hip_profiling was on for it
+    OptionDef{"fusion_last_splat_ms", 0, 0, [](bpvo_hip_ctx* c) { return fusion_last_ms(c, 0); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
+    OptionDef{"fusion_last_update_ms", 0, 0, [](bpvo_hip_ctx* c) { return fusion_last_ms(c, 1); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
     OPT_INT("normalization_side_stream", nrm_side_stream, 0, 1),
     OPT_INT("normalization_form", nrm_dpp_asm, 0, 4),
     OPT_INT("small_batch_fused", small_batch_fused, 0, 1),

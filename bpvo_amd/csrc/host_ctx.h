@@ -6,6 +6,7 @@
 //                                                                                        gn_rounds.h   the chain's pipelined rounds (host only, no HIP)
 //   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)      frame_plan.h  the frame stage's decisions (host only, no HIP)
 //   rectify.hip   rectification on the device: the maps of the camera sides, the launch in front of the stereo front-end (kernels_rectify.hip, rectify_math.h)
+//   disparity_fusion.hip  disparity fusion: the maps a sequence carries between its frames, the stage in front of the template stage (kernels_disparity_fusion.hip, disparity_fusion_math.h)
 //   stereo.hip    the stereo front-end: parameter checks, buffers, the matchers' launches over the frames of a call, stereo_front for the addFrame drivers
 //                 (kernels_stereo.hip, kernels_sgm.hip, kernels_sgbm.hip; sg_scanline.h: the semi-global matchers' scanline walk)
 //   device_owned.h  the owners of every device buffer, pinned buffer, stream and event below (the only place that acquires or releases one)
@@ -163,6 +164,32 @@ struct RectState {
   Event tab_ev;
   uint64_t launches = 0, pixels = 0; // bpvo_hip_rectify_counts
   Event t0, t1; bool timed = false;   // while bpvo_hip_profiling is on: events around the last launch (option "rectify_last_kernel_ms")
+};
+
+// Disparity fusion (c_api.h "disparity fusion", disparity_fusion.hip): what a sequence carries between its frames — one slab, acquired when the
+// sequence first fuses: Dc and Vc (each padded to a multiple of four pixels, so that both are 16-byte aligned) and the u64 z-buffer, zeroed
+// once —, its own setting, and the record of its last fusion.  FusionState: the context's setting, the sequences (index 0 is also
+// bpvo_hip_add_frame's), the job table of a stage and the class counters it leaves; everything is acquired at its first use, so a context with
+// mode 0 everywhere holds nothing.
+struct FusionSeq {
+  bpvo_hip_disparity_fusion prm = {0, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool own = false;
+  DeviceBuf<unsigned char> slab;
+  size_t npix = 0;                 // the camera size the slab was made for
+  float* Dc = nullptr; float* Vc = nullptr; unsigned long long* zbuf = nullptr;
+  bool carried = false;            // the maps hold a frame (false: fresh, after bpvo_hip_seq_reset)
+  bpvo_hip_disparity_fusion_info info = {};
+};
+struct FusionState {
+  bpvo_hip_disparity_fusion prm = {0, 0.0f, 0.0f, 0.0f, 0.0f};
+  std::vector<FusionSeq> seq;      // [max(1, sequence capacity)], made by the first setter that turns mode 1 on
+  int n_on = 0;                    // sequences that run in mode 1 right now (0: no driver asks any further)
+  PinnedBuf<FusionJob> h_jobs; DeviceBuf<FusionJob> d_jobs;
+  PinnedBuf<unsigned> h_counts; DeviceBuf<unsigned> d_counts;      // [jobs][DF_CLASSES] of the last stage
+  Event done_ev;                   // behind the last stage's copy of the counters
+  std::vector<int> pending;        // the sequences of the last stage, whose counters are still on their way
+  uint64_t launches = 0, pixels = 0;
+  Event t0, t1, t2; bool timed = false;   // while bpvo_hip_profiling is on: events around the last stage's two launches
 };
 
 enum KernelClass { KC_PYRAMID = 0, KC_DESCRIPTOR, KC_SALIENCY_SELECT, KC_NORMALIZATION, KC_TEMPLATE, KC_WARP_RESIDUAL, KC_MEDIAN,
@@ -372,6 +399,7 @@ struct bpvo_hip_ctx {
   size_t st_sgm_budget = 0, st_free_seen = 0;
   int st_frames_per_launch_seen = 0;      // what the last SGM launch used (measurement: option "stereo_frames_per_launch_seen")
   RectState rect;                         // rectification on the device (rectify.hip)
+  FusionState fusion;                     // disparity fusion (disparity_fusion.hip)
   // Upload pipeline of pair batches handed over in HOST buffers (bpvo_hip_batch_run, on_device = 0): worker threads stage chunks of
   // kUploadChunkPairs pairs in pinned memory and copy them on a stream of their own into a device staging area, chunk after chunk in lane
   // order, while the lanes already work on the chunks that have landed (upload_pipeline below).  Option "upload_workers" (0 = off).
@@ -694,6 +722,15 @@ const RectMap* rect_map_of(const bpvo_hip_ctx* c, int seq, int side);
 struct RectSide { int side; const uint8_t* raw; uint8_t* dst; };
 int rectify_queue(bpvo_hip_ctx* c, int n, const int* seq /*null: the context's own camera*/, int n_sides, const RectSide* sides, bool on_device);
 int rect_clear(bpvo_hip_ctx* c, int seq);
+// Disparity fusion (disparity_fusion.hip).  fusion_stage: ONE splat and ONE update launch on the context's stream for the items of sequences in
+// mode 1 (the others are skipped; none: nothing is queued) — item: the sequence, the frame slot whose disparity is the measured map and becomes
+// the fused one, and the motion from the sequence's previous frame to this one ([16]; null: a first frame, nothing is predicted).  Nothing is
+// synchronised; the class counters are fetched when asked for.  fusion_seq_reset: the sequence carries nothing any more.
+struct FusionItem { int seq; int slot; const float* P; };
+bool fusion_on(const bpvo_hip_ctx* c, int seq);
+int fusion_stage(bpvo_hip_ctx* c, int n, const FusionItem* items);
+void fusion_seq_reset(bpvo_hip_ctx* c, int seq);
+double fusion_last_ms(bpvo_hip_ctx* c, int which);      // option "fusion_last_splat_ms" (0) / "fusion_last_update_ms" (1)
 // The stereo front-end of an addFrame call (stereo.hip): n pairs, pair i of sz[i] pixels for sequence ids[i] (ids null: the context's own camera), the
 // images of a side back to back at left / right, in host or device memory; raw: unrectified pairs, which go through rectify_queue first.  In order: the
 // raw path's map check, the parameter checks per size, (raw) buffers and rectification, the matcher.  The disparities end up in c->st_disp and the

@@ -136,6 +136,23 @@ bool launch_stereo_bm(hipStream_t s, const StereoLaunch& g);   // false: window 
 // of the rows x cols destination pixels (RectEntry per pixel), the rectified image at dst (any byte address).  One launch serves the table.
 struct RectifyFrame { int rows, cols, raw_rows, raw_cols; const int2* map; const uint8_t* src; uint8_t* dst; };
 void launch_rectify_frames(hipStream_t s, const RectifyFrame* frames /*device*/, int nframes, int max_rows, int max_cols);
+// Disparity fusion (kernels_disparity_fusion.hip; the rule: disparity_fusion_math.h): one sequence of a call — its camera and gate, the rule's
+// parameters, the motion's first three rows, the slot's disparity (the measured map in, the fused map out), the carried maps, the job's z-buffer
+// (u64 per pixel, all zero between calls) and its five class counters.  predict 0: the splat skips the job (nothing carried, or a motion that
+// is not finite).  One launch per stage serves the table.
+struct FusionJob {
+  int rows, cols, predict, pad_;
+  float fx, fy, cx, cy, b, lo, hi;
+  float r2, q2, gate, fill2;
+  float P[12];
+  float* slot;
+  float* Dc;
+  float* Vc;
+  unsigned long long* zbuf;
+  unsigned* counts;
+};
+void launch_fusion_splat(hipStream_t s, const FusionJob* jobs /*device*/, int njobs, size_t max_pixels);
+void launch_fusion_update(hipStream_t s, const FusionJob* jobs /*device*/, int njobs, size_t max_pixels);
 
 // semi-global matching (kernels_sgm.hip): the reference's in-tree SgmStereo (utils/sgm.cc)
 struct SgmLaunch {

@@ -63,6 +63,15 @@ int bpvo_hip_add_frame_stereo_raw(bpvo_hip_ctx* c, const uint8_t* left_raw, cons
   return add_frame_stereo(c, left_raw, right_raw, true, sp, ret);
 }
 static void slot_clear(bpvo_hip_ctx* c, int slot) { c->frames[slot].has_data = false; c->frames[slot].has_template = false; }
+// option disparity fusion (c_api.h; disparity_fusion.hip) for bpvo_hip_add_frame's sequence: the frame in `slot` is fused with the carried maps moved
+// by P, the motion from the previous frame (vo_state.h vo_frame_motion; null: the first frame).  Mode 0: nothing is computed or queued.
+static int fuse_frame(bpvo_hip_ctx* c, const SeqState& q, int slot, const M44& T_est, const M44* T_again, bool first)
+{
+  if(!fusion_on(c, 0)) return BPVO_OK;
+  const M44 P = first ? m44_identity() : vo_frame_motion(q, T_est, T_again);
+  const FusionItem it{0, slot, first ? nullptr : P.m};
+  return fusion_stage(c, 1, &it);
+}
 
 // ---- the start policy in the drivers (vo_state.h states the rule: "where an estimate starts") ----------------------------------------------
 // the policy a body runs: its own, or the context's
@@ -162,6 +171,7 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
   if(!c->frames[q.ref].has_template) {                // first frame (vo.cc:133-139)
     const int slot = vo_first_frame(q);
     rc = upload_now();                                 // (its template stage reads the disparity)
+    if(rc == BPVO_OK) rc = fuse_frame(c, q, slot, q.T_kf, nullptr, true);      // (carried = measurement; the slot keeps the caller's bits)
     if(rc == BPVO_OK) rc = frames_set_template(c, slot, 1, 1);
     if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
     vo_first_frame_done(q, ret);
@@ -209,6 +219,9 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
     const KeyFrameSlots kf = vo_keyframe(q, c->frames[q.prev].has_data, cloud_points, ret);
     if(kf.clear_slot >= 0) slot_clear(c, kf.clear_slot);
     if(!kf.reestimate) {                                // vo.cc:161-173
+      // (disparity fusion: the current frame becomes the key frame — fused before its template is built; T_kf moves in vo_finish only)
+      rc = fuse_frame(c, q, data_slot, T_est, nullptr, false);
+      if(rc) return rc;
       rc = frames_set_template(c, kf.template_slot, 1, 1);
       if(rc) return rc;
     } else {                                            // vo.cc:174-188
@@ -234,7 +247,13 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
         rc = pose_cov_pass(c, 1, 1, &ws0, &q.ref, &q.cur, nullptr, c->params.maxTestLevel, nullptr, nullptr, nullptr, &c->vo_cov);
         if(rc) return rc;
       }
+      // (disparity fusion: the new key frame is the previous frame, fused in its own call; the current frame with the re-estimate's motion)
+      rc = fuse_frame(c, q, data_slot, T_est, &T_again, false);
+      if(rc) return rc;
     }
+  } else {
+    rc = fuse_frame(c, q, data_slot, T_est, nullptr, false);      // (no key frame: at the end of the call)
+    if(rc) return rc;
   }
   vo_finish(q, T_est, again ? &T_again : nullptr, ret);
   if(c->pose_covariance) std::memcpy(ret->covariance, c->vo_cov.covariance, sizeof(ret->covariance));
@@ -570,6 +589,24 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
     return frames_set_data_slots(c, sl, count, images, disparities, on_device, fr, 0, off);
   });
   if(rc) return drain(rc);
+  // option disparity fusion (c_api.h; disparity_fusion.hip; sequences only — a context with a rig refuses mode 1): the frame of every sequence in
+  // mode 1 is fused with the sequence's carried maps, moved by the motion from its previous frame (vo_state.h vo_frame_motion), in ONE stage for
+  //   * the sequences whose current frame becomes the key frame, in front of the key frames' template stage (phase 6);
+  //   * all the others at the end of the call: first frames (nothing is predicted, the slot keeps the caller's bits), frames that are no key
+  //     frame, and key frames with re-estimation — their new key frame is the previous frame, fused in its own call.
+  // data_slot: where phase 2 put entry i's frame (the slot roles move below).  Mode 0 everywhere: nothing is computed or queued.
+  std::vector<int> data_slot;
+  std::vector<FusionItem> fuse_now, fuse_last;
+  std::vector<M44> fuse_P;
+  bool fusing = false;
+  if(!rig) {
+    for(const Entry& e : E) { data_slot.push_back(e.mem[0]->cur); fusing = fusing || fusion_on(c, e.seq[0]); }
+    fuse_P.reserve(E.size());      // (the items point into it)
+  }
+  auto fuse_item = [&](const Entry& e, const M44* P) {
+    if(P) fuse_P.push_back(*P);
+    return FusionItem{e.seq[0], data_slot[(size_t) (&e - E.data())], P ? fuse_P.back().m : nullptr};
+  };
 
   // 3. first frames (vo.cc:133-139): every member's template in one stage
   std::vector<const Entry*> est, firsts;      // the entries that estimate / that are at their first frame
@@ -583,9 +620,11 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
     rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
     for(const Entry* e : firsts) vo_rig_first_frame_done(*e->body, e->mem.data(), e->n, e->ret);
+    for(const Entry* e : firsts)
+      if(fusing) fuse_last.push_back(fuse_item(*e, nullptr));
   }
   const int m = (int) est.size();
-  if(m == 0) return BPVO_OK;
+  if(m == 0) return fusing ? fusion_stage(c, (int) fuse_last.size(), fuse_last.data()) : BPVO_OK;
 
   // 4. estimatePose(ref, cur, T_kf) of the others, each from its body's T_kf: one estimate
   bool own = false;
@@ -677,6 +716,14 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
         slots.push_back(s.template_slot);
       }
       if(ks[0].reestimate) { re.push_back(k); again.push_back(&e); }
+      else if(fusing) {      // (its current frame is the new key frame: fused before the template stage; T_kf moves in vo_finish only)
+        const M44 P = vo_frame_motion(*e.body, T_est[k], nullptr);
+        fuse_now.push_back(fuse_item(e, &P));
+      }
+    }
+    if(!fuse_now.empty()) {
+      rc = fusion_stage(c, (int) fuse_now.size(), fuse_now.data());
+      if(rc) return drain(rc);
     }
     rc = for_each_size(c, slots, nullptr, template_stage);
     if(rc) return drain(rc);
@@ -699,6 +746,16 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
   // 7. per entry: the pose, T_kf and the trajectory of the body (a rig: every member's slots, and its cloud's pose), the covariance record
   std::vector<int> again_of((size_t) m, -1);
   for(size_t t = 0; t < re.size(); ++t) again_of[re[t]] = (int) t;
+  if(fusing) {
+    for(int k = 0; k < m; ++k) {
+      const Entry& e = *est[k];
+      if(e.ret->isKeyFrame && again_of[k] < 0) continue;      // (fused in front of its template stage)
+      const M44 P = vo_frame_motion(*e.body, T_est[k], again_of[k] >= 0 ? &T_again[again_of[k]] : nullptr);
+      fuse_last.push_back(fuse_item(e, &P));
+    }
+    rc = fusion_stage(c, (int) fuse_last.size(), fuse_last.data());
+    if(rc) return drain(rc);
+  }
   for(int k = 0; k < m; ++k) {
     const Entry& e = *est[k];
     vo_rig_finish(*e.body, e.mem.data(), e.X, e.n, T_est[k], again_of[k] >= 0 ? &T_again[again_of[k]] : nullptr, e.ret);
@@ -729,6 +786,7 @@ static int rigs_set_impl(bpvo_hip_ctx* c, int n_rigs, const int* count, const in
 {
   const std::string w(who);
   if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a rig's members are sequences of bpvo_hip_add_frames' kind");
+  if(c->fusion.n_on > 0) return fail(c, BPVO_ERR_UNSUPPORTED, (w + ": a context with disparity fusion in mode 1 does not serve rigs").c_str());
   const int S = seq_capacity(c);
   if(n_rigs < 1 || n_rigs > S) return fail(c, BPVO_ERR_INVALID_ARG, (w + ": n_rigs must be within 1 .. the sequence capacity").c_str());
   if(!count) return fail(c, BPVO_ERR_INVALID_ARG, (w + ": nullptr member counts").c_str());
@@ -901,6 +959,7 @@ int bpvo_hip_seq_reset(bpvo_hip_ctx* c, int seq)
 {
   CHECK_CTX(c); CHECK_SEQ(c, seq);
   if(!c->seqs.empty()) seq_reset_state(c, seq);
+  fusion_seq_reset(c, seq);      // (the carried maps go; the setting stays, like the parameters)
   return BPVO_OK;
 }
 // A sequence's own point budget (an extension: no reference member), kept on its three frame slots: it outlives bpvo_hip_seq_reset like the

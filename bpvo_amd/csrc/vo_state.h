@@ -147,18 +147,22 @@ inline KeyFrameSlots vo_keyframe(SeqState& q, bool prev_has_data, size_t cloud_p
 // The end of every addFrame but the first: the slot advance of a frame that is no key frame (vo.cc:149-155), the pose, T_kf, the trajectory and
 // the cloud's pose.  T_est: the estimate against the key frame the call began with; T_again: null, or the estimate against the new key frame
 // (KeyFrameSlots::reestimate).
+// The motion from the previous frame to this one, Result::pose, in every branch: the estimate against the key frame the call began with taken
+// off T_kf, or — a key frame with re-estimation — the estimate against the new key frame, which IS the previous frame.  Read before vo_finish
+// moves T_kf; vo_finish and the disparity fusion (vo.hip) both take it from here, so the result and the fusion see the same bits.
+inline M44 vo_frame_motion(const SeqState& q, const M44& T_est, const M44* T_again)
+{
+  return T_again ? *T_again : m44_mul(T_est, m44_inverse(q.T_kf));
+}
 inline void vo_finish(SeqState& q, const M44& T_est, const M44* T_again, bpvo_hip_result* ret)
 {
-  M44 pose;
+  const M44 pose = vo_frame_motion(q, T_est, ret->isKeyFrame ? T_again : nullptr);
   if(!ret->isKeyFrame) {
     std::swap(q.prev, q.cur);
-    pose = m44_mul(T_est, m44_inverse(q.T_kf));
     q.T_kf = T_est;
   } else if(!T_again) {
-    pose = m44_mul(T_est, m44_inverse(q.T_kf));
     q.T_kf = m44_identity();
   } else {
-    pose = *T_again;
     q.T_kf = *T_again;
   }
   std::memcpy(ret->pose, pose.m, 64);

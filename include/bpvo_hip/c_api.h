@@ -881,6 +881,9 @@ int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* ctx, uint64_t out[4]);
  *   "stereo_free_mib_seen"   (read-only) the free device memory, MiB, the rule above saw when this context first needed the SGM scratch
  *   "rectify_last_kernel_ms" (read-only) the duration, ms, of the last rectification launch between two events on the context's stream; -1 unless
  *                                      bpvo_hip_profiling was on when it was queued (measurement: scripts/rectify_bench.py)
+ *   "fusion_last_splat_ms"   (read-only) the duration, ms, of the last disparity-fusion stage's splat launch between two events on the context's stream
+ *   "fusion_last_update_ms"  (read-only) ... and of its update launch; -1 unless bpvo_hip_profiling was on when the stage was queued (measurement:
+ *                                      scripts/disparity_fusion_bench.py)
  *   "normalization_form"     4         the sequential (reference-order) Hartley sums: 1 = hand-scheduled DPP add chains (170 us for a 1241x376 template,
  *                                      2.28 ms for a dense 640x480 one); 0 = the compiler's DPP form (281 us / 3.6 ms); 2 = every lane of a row reads the same
  *                                      four consecutive elements from LDS and adds them with plain adds — no cross-lane traffic, no asm (311 us / 4.0 ms);
@@ -952,6 +955,68 @@ int bpvo_hip_debug_gn_state(bpvo_hip_ctx* ctx, int ws, float out[84]);
 /* diagnostics: what the library's contexts hold right now, process-wide: device buffers, pinned host buffers, streams, events (a
  * context that has been destroyed, or whose creation failed, has given back all it took) */
 int bpvo_hip_debug_live_resources(int counts[4]);
+
+/* ---- disparity fusion (an extension: no reference member; off by default) ---------------------------------------------------------
+ * A sequence in mode 1 carries, in the geometry of its latest frame, a disparity map Dc and a variance map Vc (f32, level-0 size; Vc < 0:
+ * the pixel carries nothing), outside its three frame slots.  Every frame, the maps are predicted into the new frame with the frame-to-frame
+ * motion the call estimated (Result::pose) and fused with the measured map M; the result replaces the carried maps AND the disparity of the
+ * frame's slot, in front of the template stage, so whichever frame becomes a key frame builds its template from the fused map.  It touches
+ * no Gauss-Newton kernel.  The rule (bpvo_amd/csrc/disparity_fusion_math.h states it as code, once, for host and device):
+ *   valid(d) := d >= lo && d <= hi with lo = minValidDisparity, hi = maxValidDisparity of the sequence's parameters (the template stage's gate).
+ *   1. Prediction, a forward splat with a z-buffer.  For every pixel (x, y) with Vc >= 0, in f64, each operation rounded on its own:
+ *      Z = fx b / d, X = (x - cx) Z / fx, Y = (y - cy) Z / fy, (X', Y', Z') = R (X, Y, Z) + t of the motion P (row-major 4x4, X_new = P X_old,
+ *      summed left to right); dropped unless Z' > 0; u = fx X' / Z' + cx, v = fy Y' / Z' + cy, dropped unless both are of magnitude below
+ *      2^30 (NaN fails); the target is (rint(u), rint(v)), ties to even, dropped outside the image; d' = (float)(fx b / Z'), dropped unless
+ *      d' > 0 and valid(d'); s = d' / d; v' = (float)(Vc s^2 s^2 + process_sigma^2), dropped unless finite.  A target keeps the candidate of
+ *      the LARGEST key bits(d') 2^32 + bits(v'): the nearest surface, then the larger variance — a pure function of the inputs, whatever
+ *      order the lanes arrive in.  A motion with a non-finite entry gives no prediction at all.
+ *   2. Update, per pixel in f32, every + - * / sqrt correctly rounded and none contracted; m = M[p], r2 = measurement_sigma^2, (pd, pv) the
+ *      candidate that arrived, if one did:
+ *        valid(m), candidate, |m - pd| <= gate sqrt(pv + r2)   D = pd + k (m - pd), k = pv / (pv + r2) (m if that leaves the gate), V = pv - k pv   "fused"
+ *        valid(m), candidate, not consistent                   D = m, V = r2                                                                    "replaced"
+ *        valid(m), no candidate                                D = m, V = r2                                                                    "measured"
+ *        not valid(m), candidate with pv <= max_fill_sigma^2   D = pd, V = pv                                                                   "filled"
+ *        otherwise                                             D = m (the caller's bits), V = -1                                                "none"
+ *      A measured-valid pixel stays valid.  On a sequence's first frame, after bpvo_hip_seq_reset, or with nothing carried, every pixel is
+ *      "measured" or "none" and the slot's disparity is the caller's, bit for bit.
+ * Units: disparity pixels; gate in standard deviations.  Mode 1 needs finite values, measurement_sigma > 0, process_sigma >= 0, gate > 0,
+ * max_fill_sigma >= 0 (0: never fill); anything else is BPVO_ERR_INVALID_ARG and changes nothing.  A context that declares a rig refuses
+ * mode 1 with BPVO_ERR_UNSUPPORTED (and a context with mode 1 somewhere refuses a rig).  Nothing is allocated and nothing is launched until
+ * a sequence has mode 1; with mode 0 everywhere every call is what it was. */
+typedef struct bpvo_hip_disparity_fusion {
+  int mode;                 /* 0 off, 1 on */
+  float measurement_sigma, process_sigma, gate, max_fill_sigma;
+} bpvo_hip_disparity_fusion;
+/* the last fusion of a sequence: the pixels of each class, whether the carried maps were predicted (0: first frame, nothing carried, or a
+ * motion that is not finite), the frame slot whose disparity it replaced, and the motion it was given */
+typedef struct bpvo_hip_disparity_fusion_info {
+  uint32_t fused, replaced, measured, filled, none;
+  int predicted;
+  int slot;
+  int reserved_;
+  float motion[16];
+} bpvo_hip_disparity_fusion_info;
+/* the context's setting (bpvo_hip_add_frame's sequence, and every sequence without its own) */
+int bpvo_hip_set_disparity_fusion(bpvo_hip_ctx* ctx, const bpvo_hip_disparity_fusion* fusion);
+int bpvo_hip_get_disparity_fusion(const bpvo_hip_ctx* ctx, bpvo_hip_disparity_fusion* fusion);
+/* a sequence's own (null: back to the context's); it outlives bpvo_hip_seq_reset like the parameters, the carried maps do not */
+int bpvo_hip_seq_set_disparity_fusion(bpvo_hip_ctx* ctx, int seq, const bpvo_hip_disparity_fusion* fusion);
+int bpvo_hip_seq_get_disparity_fusion(const bpvo_hip_ctx* ctx, int seq, bpvo_hip_disparity_fusion* fusion, int* own);
+/* the carried maps, to host memory, each of the camera's rows x cols floats; either may be null.  BPVO_ERR_NO_DATA while nothing is carried */
+int bpvo_hip_vo_get_fused_disparity(bpvo_hip_ctx* ctx, float* disparity, float* variance);
+int bpvo_hip_seq_get_fused_disparity(bpvo_hip_ctx* ctx, int seq, float* disparity, float* variance);
+int bpvo_hip_vo_disparity_fusion_info(bpvo_hip_ctx* ctx, bpvo_hip_disparity_fusion_info* info);
+int bpvo_hip_seq_disparity_fusion_info(bpvo_hip_ctx* ctx, int seq, bpvo_hip_disparity_fusion_info* info);
+/* The filter without the VO, for callers with a tracker of their own: the carried maps of the n sequences seq[i] (null: 0 .. n-1) advance
+ * by the caller's motions poses [n][16] with the measured maps `disparities`, packed back to back as for bpvo_hip_add_frames (each of its
+ * sequence's camera size; on_device: in device memory).  The fused map also replaces the disparity of the sequence's current frame slot.
+ * On a bpvo_hip_create context n = 1 serves the context's own state.  Every check runs before anything changes; every named sequence must
+ * be in mode 1. */
+int bpvo_hip_fuse_disparities(bpvo_hip_ctx* ctx, int n, const int* seq, const float* disparities, int on_device, const float* poses);
+/* a frame slot's disparity map (level-0 size of the slot's camera), to host memory */
+int bpvo_hip_get_disparity(bpvo_hip_ctx* ctx, int slot, float* out);
+/* measurement: kernel launches of the feature and pixels updated since the context was created */
+int bpvo_hip_disparity_fusion_counts(bpvo_hip_ctx* ctx, uint64_t* launches, uint64_t* pixels);
 
 #ifdef __cplusplus
 }

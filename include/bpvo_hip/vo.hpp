@@ -124,6 +124,22 @@ struct StartPolicy : public bpvo_hip_start_policy {
 };
 /* what an estimate of the last call started from (c_api.h bpvo_hip_start_info: n_candidates, chosen, kind, T_start, scores) */
 typedef bpvo_hip_start_info StartInfo;
+/* disparity fusion (c_api.h "disparity fusion", an extension with no reference member; off by default): a sequence carries a disparity and a
+ * variance map, predicted into every new frame with the estimated motion and fused with the measured map in front of the template stage.  Units:
+ * disparity pixels; gate in standard deviations; maxFillSigma 0: never fill.  No defaults are guessed: On(...) takes all four. */
+struct DisparityFusion : public bpvo_hip_disparity_fusion {
+  DisparityFusion() { mode = 0; measurement_sigma = process_sigma = gate = max_fill_sigma = 0.0f; }
+  static DisparityFusion On(float measurementSigma, float processSigma, float gate_, float maxFillSigma)
+  {
+    DisparityFusion f;
+    f.mode = 1; f.measurement_sigma = measurementSigma; f.process_sigma = processSigma; f.gate = gate_; f.max_fill_sigma = maxFillSigma;
+    return f;
+  }
+};
+/* the maps a sequence carries (row-major, the camera's size; variance < 0: the pixel carries nothing) */
+struct FusedDisparity { ImageSize size; std::vector<float> disparity, variance; };
+/* the last fusion of a sequence (c_api.h bpvo_hip_disparity_fusion_info: fused, replaced, measured, filled, none, predicted, slot, motion) */
+typedef bpvo_hip_disparity_fusion_info DisparityFusionInfo;
 inline std::vector<float> packPoses(const std::vector<Matrix44>& poses)
 {
   std::vector<float> M(16 * poses.size());
@@ -473,6 +489,18 @@ class VisualOdometry {
   void setStartPolicy(const StartPolicy& policy) { _dev->check(bpvo_hip_set_start_policy(_dev->ctx(), &policy)); }
   void setStartHints(const std::vector<Matrix44>& hints) { const std::vector<float> M = packPoses(hints); _dev->check(bpvo_hip_vo_set_start_hints(_dev->ctx(), (int) hints.size(), M.data())); }
   StartInfo startInfo(int which = 0) const { StartInfo r; _dev->check(bpvo_hip_vo_start_info(_dev->ctx(), which, &r)); return r; }
+  /* disparity fusion (an extension; c_api.h bpvo_hip_set_disparity_fusion): the setting, the carried maps, the record of the last frame's fusion */
+  void setDisparityFusion(const DisparityFusion& fusion) { _dev->check(bpvo_hip_set_disparity_fusion(_dev->ctx(), &fusion)); }
+  FusedDisparity fusedDisparity() const
+  {
+    FusedDisparity r;
+    r.size = _dev->imageSize();
+    r.disparity.resize((size_t) r.size.rows * (size_t) r.size.cols);
+    r.variance.resize(r.disparity.size());
+    _dev->check(bpvo_hip_vo_get_fused_disparity(_dev->ctx(), r.disparity.data(), r.variance.data()));
+    return r;
+  }
+  DisparityFusionInfo disparityFusionInfo() const { DisparityFusionInfo r; _dev->check(bpvo_hip_vo_disparity_fusion_info(_dev->ctx(), &r)); return r; }
   /* Result::covariance carries the covariance of the estimated pose (option "pose_covariance"); poseCovariance(): the last frame's record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
   PoseCovarianceEstimate poseCovariance() const
@@ -644,6 +672,22 @@ class VisualOdometrySequences {
   void setStartPolicy(int s, const StartPolicy& policy) { _dev->check(bpvo_hip_seq_set_start_policy(_dev->ctx(), s, &policy)); }
   void setStartHints(int s, const std::vector<Matrix44>& hints) { const std::vector<float> M = packPoses(hints); _dev->check(bpvo_hip_seq_set_start_hints(_dev->ctx(), s, (int) hints.size(), M.data())); }
   StartInfo startInfo(int s, int which = 0) const { StartInfo r; _dev->check(bpvo_hip_seq_start_info(_dev->ctx(), s, which, &r)); return r; }
+  /* disparity fusion (an extension; c_api.h bpvo_hip_set_disparity_fusion): every sequence's setting, or sequence s's own; the maps sequence s
+   * carries; the record of its last frame's fusion */
+  void setDisparityFusion(const DisparityFusion& fusion) { _dev->check(bpvo_hip_set_disparity_fusion(_dev->ctx(), &fusion)); }
+  void setDisparityFusion(int s, const DisparityFusion& fusion) { _dev->check(bpvo_hip_seq_set_disparity_fusion(_dev->ctx(), s, &fusion)); }
+  FusedDisparity fusedDisparity(int s) const
+  {
+    bpvo_hip_camera c;
+    _dev->check(bpvo_hip_seq_get_camera(_dev->ctx(), s, &c));
+    FusedDisparity r;
+    r.size = ImageSize(c.rows, c.cols);
+    r.disparity.resize((size_t) c.rows * (size_t) c.cols);
+    r.variance.resize(r.disparity.size());
+    _dev->check(bpvo_hip_seq_get_fused_disparity(_dev->ctx(), s, r.disparity.data(), r.variance.data()));
+    return r;
+  }
+  DisparityFusionInfo disparityFusionInfo(int s) const { DisparityFusionInfo r; _dev->check(bpvo_hip_seq_disparity_fusion_info(_dev->ctx(), s, &r)); return r; }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   /* Result::covariance of every sequence carries the covariance of its estimated pose (option "pose_covariance"); poseCovariance(s): sequence s's last record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
