@@ -125,6 +125,24 @@ def disparity_fusion(mode=1, measurement_sigma=0.0, process_sigma=0.0, gate=0.0,
     return DisparityFusion(int(mode), float(measurement_sigma), float(process_sigma), float(gate), float(max_fill_sigma))
 
 
+class MeasurementVariance(C.Structure):
+    """bpvo_hip_measurement_variance: mode (0 off, 1 on), the window's radius, the pixel noise (grey levels) and the clamp (disparity pixels)."""
+    _fields_ = [("mode", C.c_int), ("radius", C.c_int), ("noise_sigma", C.c_float), ("min_sigma", C.c_float), ("max_sigma", C.c_float)]
+
+
+class MeasurementVarianceInfo(C.Structure):
+    """bpvo_hip_measurement_variance_info: the class counts of a sequence's last measurement-variance map."""
+    _fields_ = [("invalid", C.c_uint32), ("border", C.c_uint32), ("flat", C.c_uint32), ("floor", C.c_uint32), ("ceiling", C.c_uint32),
+                ("model", C.c_uint32)]
+
+
+VARIANCE_CLASSES = ("invalid", "border", "flat", "floor", "ceiling", "model")
+
+
+def measurement_variance(mode=1, radius=0, noise_sigma=0.0, min_sigma=0.0, max_sigma=0.0) -> MeasurementVariance:
+    return MeasurementVariance(int(mode), int(radius), float(noise_sigma), float(min_sigma), float(max_sigma))
+
+
 class Camera(C.Structure):
     """bpvo_hip_camera: one sequence's calibration and image size (bpvo_hip_create_sequences, bpvo_hip_seq_set_camera)."""
     _fields_ = [("K", C.c_float * 9), ("baseline", C.c_float), ("rows", C.c_int), ("cols", C.c_int)]
@@ -1258,6 +1276,111 @@ class Context:
         a, b = C.c_uint64(), C.c_uint64()
         self.call("disparity_fusion_counts", C.byref(a), C.byref(b))
         return a.value, b.value
+
+    # -- measurement variance (bpvo_hip_set_measurement_variance ...; an extension: no reference member; HIP library only)
+    @staticmethod
+    def _variance_arg(v):
+        if v is None or isinstance(v, MeasurementVariance):
+            return v
+        if isinstance(v, dict):
+            return measurement_variance(**v)
+        return measurement_variance(*v)
+
+    @staticmethod
+    def _variance_dict(v: MeasurementVariance):
+        return dict(mode=int(v.mode), radius=int(v.radius), noise_sigma=float(v.noise_sigma), min_sigma=float(v.min_sigma), max_sigma=float(v.max_sigma))
+
+    @staticmethod
+    def _variance_info_dict(r: MeasurementVarianceInfo):
+        return {k: int(getattr(r, k)) for k in VARIANCE_CLASSES}
+
+    def set_measurement_variance(self, setting):
+        """bpvo_hip_set_measurement_variance: the context's setting — a MeasurementVariance, a dict of its fields or a tuple in their order."""
+        v = self._variance_arg(setting)
+        self.call("set_measurement_variance", C.byref(v))
+
+    def get_measurement_variance(self):
+        v = MeasurementVariance()
+        self._ck(self.b.fn("get_measurement_variance")(self.h, C.byref(v)))
+        return self._variance_dict(v)
+
+    def seq_set_measurement_variance(self, s, setting):
+        """bpvo_hip_seq_set_measurement_variance: sequence s's own setting; None returns it to the context's."""
+        v = self._variance_arg(setting)
+        self.call("seq_set_measurement_variance", int(s), None if v is None else C.byref(v))
+
+    def seq_get_measurement_variance(self, s):
+        """(setting dict, True if it is the sequence's own)"""
+        v, own = MeasurementVariance(), C.c_int()
+        self._ck(self.b.fn("seq_get_measurement_variance")(self.h, int(s), C.byref(v), C.byref(own)))
+        return self._variance_dict(v), bool(own.value)
+
+    def vo_get_measurement_variance(self):
+        """bpvo_hip_vo_get_measurement_variance: the map [rows, cols] f32 of add_frame_stereo's last frame."""
+        out = np.empty((self.rows, self.cols), np.float32)
+        self.call("vo_get_measurement_variance", out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def seq_get_measurement_variance_map(self, s):
+        cam = self.seq_get_camera(int(s))
+        out = np.empty((cam.rows, cam.cols), np.float32)
+        self.call("seq_get_measurement_variance_map", int(s), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def vo_measurement_variance_info(self):
+        out = MeasurementVarianceInfo()
+        self.call("vo_measurement_variance_info", C.byref(out))
+        return self._variance_info_dict(out)
+
+    def seq_measurement_variance_info(self, s):
+        out = MeasurementVarianceInfo()
+        self.call("seq_measurement_variance_info", int(s), C.byref(out))
+        return self._variance_info_dict(out)
+
+    def disparity_variance_frames(self, lefts, rights, disps, lo, hi, setting):
+        """bpvo_hip_disparity_variance_frames: the rule for the pairs (2-D u8 arrays) with the measured maps disps (2-D f32, each of its pair's
+        shape) under the gate lo .. hi: (list of f32 variance maps, list of class-count dicts)."""
+        n = len(lefts)
+        assert len(rights) == n and len(disps) == n, "one right image and one map per left image"
+        cams = self._camera_array([np.shape(l) for l in lefts])
+        left, shapes = pack_images(lefts)
+        right, _ = pack_images(rights)
+        disp = np.concatenate([_f32(d).reshape(-1) for d in disps])
+        assert right.size == left.size and disp.size == left.size, "a pair's images and its map have one shape"
+        v = self._variance_arg(setting)
+        out = np.empty(left.size, np.float32)
+        counts = np.zeros((n, 6), np.uint32)
+        self.call("disparity_variance_frames", n, cams, left.ctypes.data_as(C.c_void_p), right.ctypes.data_as(C.c_void_p), disp.ctypes.data_as(C.c_void_p), 0,
+                  C.c_float(lo), C.c_float(hi), C.byref(v), out.ctypes.data_as(C.c_void_p), 0, counts.ctypes.data_as(C.c_void_p))
+        maps, at = [], 0
+        for r, w in shapes:
+            maps.append(out[at:at + r * w].reshape(r, w))
+            at += r * w
+        return maps, [dict(zip(VARIANCE_CLASSES, (int(x) for x in row))) for row in counts]
+
+    def disparity_variance_frames_device(self, cams_or_sizes, d_left_ptr, d_right_ptr, d_disp_ptr, lo, hi, setting, d_out_ptr):
+        """disparity_variance_frames with the packed inputs in device memory, the packed maps written to device memory; no counts."""
+        cams = self._camera_array(cams_or_sizes)
+        v = self._variance_arg(setting)
+        self.call("disparity_variance_frames", len(cams), cams, C.c_void_p(d_left_ptr), C.c_void_p(d_right_ptr), C.c_void_p(d_disp_ptr), 1,
+                  C.c_float(lo), C.c_float(hi), C.byref(v), C.c_void_p(d_out_ptr), 1, None)
+
+    def fuse_disparities_var(self, disps, variances, poses, seq=None):
+        """bpvo_hip_fuse_disparities_var: fuse_disparities with the measurements' variance maps (2-D f32, each of its map's shape)."""
+        n = len(disps)
+        assert len(variances) == n
+        ids, p_ids = self._seq_ids(n, seq)
+        packed = np.concatenate([_f32(d).reshape(-1) for d in disps])
+        var = np.concatenate([_f32(v).reshape(-1) for v in variances])
+        assert var.size == packed.size
+        Tf = _f32(poses).reshape(n, 16)
+        self.call("fuse_disparities_var", n, p_ids, packed.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p), 0, Tf.ctypes.data_as(C.c_void_p))
+
+    def measurement_variance_counts(self):
+        """bpvo_hip_measurement_variance_counts: (launches, pixels, (tiles staged, tiles direct, tiles idle)) so far."""
+        a, b, t = C.c_uint64(), C.c_uint64(), (C.c_uint64 * 3)()
+        self.call("measurement_variance_counts", C.byref(a), C.byref(b), t)
+        return a.value, b.value, tuple(int(x) for x in t)
 
     # -- batches
     def _stats_array(self, st, n_pairs):

@@ -331,6 +331,8 @@ const std::vector<OptionDef>& option_table()
     // read-only: the durations of the last disparity-fusion stage's two launches between events on the stream, ms; -1 unless bpvo_hip_profiling was on for it
     OptionDef{"fusion_last_splat_ms", 0, 0, [](bpvo_hip_ctx* c) { return fusion_last_ms(c, 0); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
     OptionDef{"fusion_last_update_ms", 0, 0, [](bpvo_hip_ctx* c) { return fusion_last_ms(c, 1); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
+    // read-only: the duration of the last measurement-variance launch between events on the stream, ms; -1 unless bpvo_hip_profiling was on for it
+    OptionDef{"variance_last_kernel_ms", 0, 0, [](bpvo_hip_ctx* c) { return variance_last_ms(c); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
     OPT_INT("normalization_side_stream", nrm_side_stream, 0, 1),
     OPT_INT("normalization_form", nrm_dpp_asm, 0, 4),
     OPT_INT("small_batch_fused", small_batch_fused, 0, 1),

@@ -99,6 +99,7 @@ int fusion_stage(bpvo_hip_ctx* c, int n, const FusionItem* items)
     j.r2 = rule.r2; j.q2 = rule.q2; j.gate = rule.gate; j.fill2 = rule.fill2;
     if(it.P) std::memcpy(j.P, it.P, sizeof(j.P));
     j.slot = f.disp; j.Dc = q.Dc; j.Vc = q.Vc; j.zbuf = q.zbuf; j.counts = F.d_counts + DF_CLASSES * k;
+    j.R = it.R;
     any_predict = any_predict || j.predict;
     max_pixels = std::max(max_pixels, g.npix);
     pixels += g.npix;
@@ -182,6 +183,48 @@ static int fusion_get_info(bpvo_hip_ctx* c, int seq, bpvo_hip_disparity_fusion_i
   return BPVO_OK;
 }
 
+int fuse_disparities_impl(bpvo_hip_ctx* c, int n, const int* seq, const float* disparities, const float* variances, int on_device, const float* poses)
+{
+  const int limit = seq_capacity(c);
+  if(n < 1 || n > limit) return fail(c, BPVO_ERR_INVALID_ARG, "fuse_disparities: n must be within 1 .. the sequence capacity");
+  if(c->vo_mode == 1 && n != 1) return fail(c, BPVO_ERR_INVALID_ARG, "fuse_disparities: a context that runs bpvo_hip_add_frame has one sequence");
+  if(!disparities || !poses) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr disparity/pose");
+  std::vector<FusionItem> items((size_t) n);
+  std::vector<char> seen((size_t) limit, 0);
+  for(int i = 0; i < n; ++i) {
+    const int s = seq ? seq[i] : i;
+    if(s < 0 || s >= limit) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "no such sequence");
+    if(seen[(size_t) s]) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "appears twice in one call");
+    seen[(size_t) s] = 1;
+    if(!fusion_on(c, s)) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "fuse_disparities: the sequence is not in mode 1 (bpvo_hip_set_disparity_fusion)");
+    items[(size_t) i] = FusionItem{s, fusion_cur_slot(c, s), poses + 16 * (size_t) i};
+  }
+  (void) hipSetDevice(c->device);
+  size_t total = 0;
+  for(int i = 0; i < n; ++i) total += slot_geom(c, c->frames[items[(size_t) i].slot], 0).npix;
+  const float* d_var = variances;      // the caller's variance maps on the device (host maps: uploaded into a buffer of the feature's own)
+  if(variances && !on_device) {
+    DeviceBuf<float>& buf = c->variance.fuse_var;
+    if(total > buf.size()) {
+      HIP_CK(c, hipStreamSynchronize(c->stream));
+      HIP_CK(c, buf.reserve(total));
+    }
+    HIP_CK(c, hipMemcpyAsync(buf, variances, total * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    d_var = buf;
+  }
+  size_t at = 0;
+  for(int i = 0; i < n; ++i) {
+    const FrameSlot& f = c->frames[items[(size_t) i].slot];
+    const size_t npix = slot_geom(c, f, 0).npix;
+    HIP_CK(c, hipMemcpyAsync(f.disp, disparities + at, npix * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if(d_var) items[(size_t) i].R = d_var + at;
+    at += npix;
+  }
+  const int rc = fusion_stage(c, n, items.data());
+  HIP_CK(c, hipStreamSynchronize(c->stream));
+  return rc;
+}
+
 }  // namespace bpvo_hip_host
 
 extern "C" {
@@ -247,31 +290,7 @@ int bpvo_hip_seq_disparity_fusion_info(bpvo_hip_ctx* c, int seq, bpvo_hip_dispar
 int bpvo_hip_fuse_disparities(bpvo_hip_ctx* c, int n, const int* seq, const float* disparities, int on_device, const float* poses)
 {
   CHECK_CTX(c);
-  const int limit = seq_capacity(c);
-  if(n < 1 || n > limit) return fail(c, BPVO_ERR_INVALID_ARG, "fuse_disparities: n must be within 1 .. the sequence capacity");
-  if(c->vo_mode == 1 && n != 1) return fail(c, BPVO_ERR_INVALID_ARG, "fuse_disparities: a context that runs bpvo_hip_add_frame has one sequence");
-  if(!disparities || !poses) return fail(c, BPVO_ERR_INVALID_ARG, "nullptr disparity/pose");
-  std::vector<FusionItem> items((size_t) n);
-  std::vector<char> seen((size_t) limit, 0);
-  for(int i = 0; i < n; ++i) {
-    const int s = seq ? seq[i] : i;
-    if(s < 0 || s >= limit) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "no such sequence");
-    if(seen[(size_t) s]) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "appears twice in one call");
-    seen[(size_t) s] = 1;
-    if(!fusion_on(c, s)) return seq_fail(c, BPVO_ERR_INVALID_ARG, s, "fuse_disparities: the sequence is not in mode 1 (bpvo_hip_set_disparity_fusion)");
-    items[(size_t) i] = FusionItem{s, fusion_cur_slot(c, s), poses + 16 * (size_t) i};
-  }
-  (void) hipSetDevice(c->device);
-  size_t at = 0;
-  for(int i = 0; i < n; ++i) {
-    const FrameSlot& f = c->frames[items[(size_t) i].slot];
-    const size_t npix = slot_geom(c, f, 0).npix;
-    HIP_CK(c, hipMemcpyAsync(f.disp, disparities + at, npix * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    at += npix;
-  }
-  const int rc = fusion_stage(c, n, items.data());
-  HIP_CK(c, hipStreamSynchronize(c->stream));
-  return rc;
+  return fuse_disparities_impl(c, n, seq, disparities, nullptr, on_device, poses);
 }
 int bpvo_hip_get_disparity(bpvo_hip_ctx* c, int slot, float* out)
 {

@@ -7,6 +7,7 @@
 //   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)      frame_plan.h  the frame stage's decisions (host only, no HIP)
 //   rectify.hip   rectification on the device: the maps of the camera sides, the launch in front of the stereo front-end (kernels_rectify.hip, rectify_math.h)
 //   disparity_fusion.hip  disparity fusion: the maps a sequence carries between its frames, the stage in front of the template stage (kernels_disparity_fusion.hip, disparity_fusion_math.h)
+//   disparity_variance.hip  measurement variance: the per-pixel variance of a stereo frame's disparities, behind the matcher (kernels_disparity_variance.hip, disparity_variance_math.h)
 //   stereo.hip    the stereo front-end: parameter checks, buffers, the matchers' launches over the frames of a call, stereo_front for the addFrame drivers
 //                 (kernels_stereo.hip, kernels_sgm.hip, kernels_sgbm.hip; sg_scanline.h: the semi-global matchers' scanline walk)
 //   device_owned.h  the owners of every device buffer, pinned buffer, stream and event below (the only place that acquires or releases one)
@@ -190,6 +191,32 @@ struct FusionState {
   std::vector<int> pending;        // the sequences of the last stage, whose counters are still on their way
   uint64_t launches = 0, pixels = 0;
   Event t0, t1, t2; bool timed = false;   // while bpvo_hip_profiling is on: events around the last stage's two launches
+};
+
+// Measurement variance (c_api.h "measurement variance", disparity_variance.hip): the context's setting and the sequences' own (index 0 is also
+// bpvo_hip_add_frame_stereo's), where a sequence's last map lies in c->st_var, the job table of a launch and the counters it leaves.  Everything
+// is acquired at its first use: a context with mode 0 everywhere, or without fusion, holds nothing.
+struct VarianceSeq {
+  bpvo_hip_measurement_variance prm = {0, 0, 0.0f, 0.0f, 0.0f};
+  bool own = false;
+  bool has = false;                // a stereo call has made a map for the sequence since its last reset
+  size_t offset = 0, npix = 0;     // where in c->st_var, while serial is the state's
+  uint64_t serial = 0;
+  bpvo_hip_measurement_variance_info info = {};
+};
+struct VarianceState {
+  bpvo_hip_measurement_variance prm = {0, 0, 0.0f, 0.0f, 0.0f};
+  std::vector<VarianceSeq> seq;    // [max(1, sequence capacity)], made by the first setter that turns mode 1 on
+  int n_on = 0;                    // sequences whose setting is mode 1 right now
+  bool live = false;               // the stereo call under way has maps in c->st_var (variance_map_of)
+  uint64_t serial = 0;             // moves whenever c->st_var is rewritten
+  PinnedBuf<VarianceJob> h_jobs; DeviceBuf<VarianceJob> d_jobs;
+  PinnedBuf<unsigned> h_counts; DeviceBuf<unsigned> d_counts;      // [jobs][kVarianceCounters] of the last launch
+  Event done_ev;                   // behind the last launch's copy of the counters
+  std::vector<int> pending;        // the sequences of the last launch (-1: a stand-alone pair), whose counters are still on their way
+  DeviceBuf<float> fuse_var;       // bpvo_hip_fuse_disparities_var: a host caller's maps
+  uint64_t launches = 0, pixels = 0, tiles[3] = {0, 0, 0};
+  Event t0, t1; bool timed = false;   // while bpvo_hip_profiling is on: events around the last launch (option "variance_last_kernel_ms")
 };
 
 enum KernelClass { KC_PYRAMID = 0, KC_DESCRIPTOR, KC_SALIENCY_SELECT, KC_NORMALIZATION, KC_TEMPLATE, KC_WARP_RESIDUAL, KC_MEDIAN,
@@ -387,6 +414,7 @@ struct bpvo_hip_ctx {
   // stereo front-end scratch (st_pixels each: the most pixels a call has held, the sum over its frames): raw and pre-filtered u8 pairs, f32 disparities
   DeviceBuf<uint8_t> st_left, st_right, st_left_pre, st_right_pre;
   DeviceBuf<float> st_disp;
+  DeviceBuf<float> st_var;       // the measurement-variance maps of a call, packed like st_disp; acquired when the feature first runs (disparity_variance.hip)
   size_t st_pixels = 0;
   DeviceBuf<unsigned char> st_sgm;      // scratch of the semi-global matchers (cost volumes: the largest frame x disparity range x frames per launch seen)
   // calls whose frames differ in size: the block matcher's frame table (kernels.h StereoFrame), filled in pinned memory and copied on the
@@ -400,6 +428,7 @@ struct bpvo_hip_ctx {
   int st_frames_per_launch_seen = 0;      // what the last SGM launch used (measurement: option "stereo_frames_per_launch_seen")
   RectState rect;                         // rectification on the device (rectify.hip)
   FusionState fusion;                     // disparity fusion (disparity_fusion.hip)
+  VarianceState variance;                 // measurement variance (disparity_variance.hip)
   // Upload pipeline of pair batches handed over in HOST buffers (bpvo_hip_batch_run, on_device = 0): worker threads stage chunks of
   // kUploadChunkPairs pairs in pinned memory and copy them on a stream of their own into a device staging area, chunk after chunk in lane
   // order, while the lanes already work on the chunks that have landed (upload_pipeline below).  Option "upload_workers" (0 = off).
@@ -725,12 +754,27 @@ int rect_clear(bpvo_hip_ctx* c, int seq);
 // Disparity fusion (disparity_fusion.hip).  fusion_stage: ONE splat and ONE update launch on the context's stream for the items of sequences in
 // mode 1 (the others are skipped; none: nothing is queued) — item: the sequence, the frame slot whose disparity is the measured map and becomes
 // the fused one, and the motion from the sequence's previous frame to this one ([16]; null: a first frame, nothing is predicted).  Nothing is
-// synchronised; the class counters are fetched when asked for.  fusion_seq_reset: the sequence carries nothing any more.
-struct FusionItem { int seq; int slot; const float* P; };
+// synchronised; the class counters are fetched when asked for.  fusion_seq_reset: the sequence carries nothing any more.  R: null, or the
+// measurement's variance map on the device (kernels.h FusionJob::R).
+struct FusionItem { int seq; int slot; const float* P; const float* R = nullptr; };
 bool fusion_on(const bpvo_hip_ctx* c, int seq);
 int fusion_stage(bpvo_hip_ctx* c, int n, const FusionItem* items);
 void fusion_seq_reset(bpvo_hip_ctx* c, int seq);
 double fusion_last_ms(bpvo_hip_ctx* c, int which);      // option "fusion_last_splat_ms" (0) / "fusion_last_update_ms" (1)
+// Measurement variance (disparity_variance.hip).  variance_front: behind the matcher of a stereo call — pair i of sz[i] pixels for sequence
+// ids[i] (null: the context's own) at d_left / d_right (device), its disparities in c->st_disp —, ONE launch for the pairs whose sequence has
+// fusion AND the variance in mode 1, into c->st_var (none: nothing is queued or acquired); nothing is synchronised.  variance_map_of: where that
+// launch put the sequence's map, null unless the stereo call under way made one; variance_call_done: the call is over.
+struct StereoSize;
+int variance_front(bpvo_hip_ctx* c, int n, const StereoSize* sz, const int* ids, const uint8_t* d_left, const uint8_t* d_right);
+const float* variance_map_of(const bpvo_hip_ctx* c, int seq);
+inline void variance_call_done(bpvo_hip_ctx* c) { c->variance.live = false; }
+void variance_seq_reset(bpvo_hip_ctx* c, int seq);
+int variance_scratch_moved(bpvo_hip_ctx* c, size_t npix);      // stereo_reserve: c->st_var follows the front-end's scratch, if it exists
+int stereo_reserve(bpvo_hip_ctx* c, size_t npix);      // stereo.hip: the front-end's scratch holds a call of npix pixels
+double variance_last_ms(bpvo_hip_ctx* c);      // option "variance_last_kernel_ms"
+// bpvo_hip_fuse_disparities and bpvo_hip_fuse_disparities_var (disparity_fusion.hip); variances null: the constant
+int fuse_disparities_impl(bpvo_hip_ctx* c, int n, const int* seq, const float* disparities, const float* variances, int on_device, const float* poses);
 // The stereo front-end of an addFrame call (stereo.hip): n pairs, pair i of sz[i] pixels for sequence ids[i] (ids null: the context's own camera), the
 // images of a side back to back at left / right, in host or device memory; raw: unrectified pairs, which go through rectify_queue first.  In order: the
 // raw path's map check, the parameter checks per size, (raw) buffers and rectification, the matcher.  The disparities end up in c->st_disp and the

@@ -139,7 +139,8 @@ void launch_rectify_frames(hipStream_t s, const RectifyFrame* frames /*device*/,
 // Disparity fusion (kernels_disparity_fusion.hip; the rule: disparity_fusion_math.h): one sequence of a call — its camera and gate, the rule's
 // parameters, the motion's first three rows, the slot's disparity (the measured map in, the fused map out), the carried maps, the job's z-buffer
 // (u64 per pixel, all zero between calls) and its five class counters.  predict 0: the splat skips the job (nothing carried, or a motion that
-// is not finite).  One launch per stage serves the table.
+// is not finite).  R: null, or the measurement's variance per pixel — an entry within (0, FLT_MAX] is the update's r2 for its pixel, any other
+// entry takes the job's r2.  One launch per stage serves the table.
 struct FusionJob {
   int rows, cols, predict, pad_;
   float fx, fy, cx, cy, b, lo, hi;
@@ -150,9 +151,26 @@ struct FusionJob {
   float* Vc;
   unsigned long long* zbuf;
   unsigned* counts;
+  const float* R;
 };
 void launch_fusion_splat(hipStream_t s, const FusionJob* jobs /*device*/, int njobs, size_t max_pixels);
 void launch_fusion_update(hipStream_t s, const FusionJob* jobs /*device*/, int njobs, size_t max_pixels);
+// Measurement variance (kernels_disparity_variance.hip; the rule: disparity_variance_math.h): one rectified pair of a call — the u8 images, the
+// measured map, the variance map it writes (all rows x cols, any byte / 4-byte alignment), the gate, the radius and the three squares of the
+// setting, and its counters: the six classes, then the tiles that took the staged / the direct / no path.  One launch serves the table;
+// max_tiles: the largest disparity_variance_tiles(rows, cols) among the jobs.
+struct VarianceJob {
+  const uint8_t* L;
+  const uint8_t* R;
+  const float* M;
+  float* out;
+  unsigned* counts;      // [kVarianceCounters]
+  int rows, cols, radius, pad_;
+  float lo, hi, noise2, min2, max2;
+};
+constexpr int kVarianceCounters = 6 + 3;
+void launch_disparity_variance(hipStream_t s, const VarianceJob* jobs /*device*/, int njobs, int max_tiles);
+int disparity_variance_tiles(int rows, int cols);
 
 // semi-global matching (kernels_sgm.hip): the reference's in-tree SgmStereo (utils/sgm.cc)
 struct SgmLaunch {

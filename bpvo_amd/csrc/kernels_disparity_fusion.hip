@@ -1,5 +1,7 @@
 // libbpvo_hip, device side: disparity fusion — the carried disparity and variance maps of a sequence predicted into the new frame (splat) and
 // fused with the measured map (update).  disparity_fusion_math.h states the rule; disparity_fusion.hip keeps the maps and fills the job table.
+#include <cfloat>
+
 #include "kernels.h"
 #include "disparity_fusion_math.h"
 
@@ -57,8 +59,9 @@ __global__ __launch_bounds__(256) void fusion_splat_kernel(const FusionJob* __re
 // Update: per pixel, the measured disparity (the slot's) and the target's z-buffer word in, the fused disparity out to the slot and to the
 // carried map, the variance to the carried map, and ZERO back to a word that held a candidate — the buffer is all zero again when the launch
 // ends, so no memset runs per call.  A workgroup takes kUpdatePixels consecutive pixels, a lane every 256th of them (the slot's map is a view
-// into the slot's slab, of any 4-byte alignment): a wavefront instruction reads 256 or 512 contiguous bytes and writes 256.  The classes are
-// counted exactly, in integers: a ballot per class and pixel round into wave-uniform counts, the four wavefronts' counts summed in LDS, then
+// into the slot's slab, of any 4-byte alignment): a wavefront instruction reads 256 or 512 contiguous bytes and writes 256.
+// With a variance map (FusionJob::R) a pixel's r2 is its entry of the map, one more contiguous 256-byte read.  The classes are counted
+// exactly, in integers: a ballot per class and pixel round into wave-uniform counts, the four wavefronts' counts summed in LDS, then
 // one integer atomic per workgroup and class that occurred (a first form with one atomic per wavefront, class and 64 pixels spent its time
 // queueing on the five counters of a job: 69 us for one 640 x 480 map).
 constexpr int kUpdateRounds = 8;
@@ -72,8 +75,9 @@ __global__ __launch_bounds__(256) void fusion_update_kernel(const FusionJob* __r
   if(base >= npix) return;      // (the whole workgroup: no barrier has been passed)
   if(threadIdx.x < DF_CLASSES) block_counts[threadIdx.x] = 0;
   __syncthreads();
-  const DfRule rule{j.r2, j.q2, j.gate, j.fill2};
+  DfRule rule{j.r2, j.q2, j.gate, j.fill2};
   const float lo = j.lo, hi = j.hi;
+  const float* __restrict__ R = j.R;      // (null: the job's r2 for every pixel)
   unsigned counts[DF_CLASSES] = {};
 #pragma unroll
   for(int r = 0; r < kUpdateRounds; ++r) {
@@ -82,6 +86,10 @@ __global__ __launch_bounds__(256) void fusion_update_kernel(const FusionJob* __r
     if(i < npix) {
       const float m = j.slot[i];
       const unsigned long long word = j.zbuf[i];
+      if(R) {      // (the measurement's own variance where the map holds one; NaN fails the first comparison)
+        const float r = R[i];
+        rule.r2 = r > 0.0f && r <= FLT_MAX ? r : j.r2;
+      }
       float D, V;
       cls = df_update(rule, lo, hi, m, (uint64_t) word, &D, &V);
       j.slot[i] = D;

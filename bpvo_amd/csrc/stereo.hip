@@ -68,7 +68,7 @@ static int stereo_check(bpvo_hip_ctx* c, const bpvo_hip_stereo_params* sp, int r
   if(sp->minDisparity < 0 || sp->numberOfDisparities > 256) return fail(c, BPVO_ERR_UNSUPPORTED, "minDisparity >= 0 and numberOfDisparities <= 256 are on the device path");
   return BPVO_OK;
 }
-static int stereo_reserve(bpvo_hip_ctx* c, size_t npix)      // npix: the pixels of a call, the sum over its frames
+int stereo_reserve(bpvo_hip_ctx* c, size_t npix)      // npix: the pixels of a call, the sum over its frames
 {
   if(npix <= c->st_pixels) return BPVO_OK;
   HIP_CK(c, hipStreamSynchronize(c->stream));
@@ -78,6 +78,7 @@ static int stereo_reserve(bpvo_hip_ctx* c, size_t npix)      // npix: the pixels
   c->st_disp.reset();
   for(auto* b : u8) HIP_CK(c, b->alloc(npix));
   HIP_CK(c, c->st_disp.alloc(npix));
+  if(int rc = variance_scratch_moved(c, npix)) return rc;      // (the measurement-variance maps, where the feature has run)
   c->st_pixels = npix;
   return BPVO_OK;
 }
@@ -256,7 +257,11 @@ int stereo_front(bpvo_hip_ctx* c, int n, const StereoSize* sz, const int* ids, c
     if(rc) { (void) hipStreamSynchronize(c->stream); return rc; }
     left = c->st_left; right = c->st_right; on_device = true;
   }
-  rc = stereo_run_sizes(c, n, sz, left, right, on_device, sp, d_left);
+  const uint8_t* dl = nullptr;
+  rc = stereo_run_sizes(c, n, sz, left, right, on_device, sp, &dl);
+  if(d_left) *d_left = dl;
+  // option measurement variance (c_api.h; disparity_variance.hip): the variance maps of the frames that will be fused with one, behind the matcher
+  if(rc == BPVO_OK) rc = variance_front(c, n, sz, ids, dl, on_device ? right : c->st_right.get());
   if(rc) (void) hipStreamSynchronize(c->stream);
   return rc;
 }

@@ -52,7 +52,9 @@ static int add_frame_stereo(bpvo_hip_ctx* c, const uint8_t* left, const uint8_t*
   const StereoSize size{c->rows, c->cols};
   const uint8_t* d_left = nullptr;
   if(int rc = stereo_front(c, 1, &size, nullptr, left, right, raw, false, sp, &d_left)) return rc;
-  return add_frame_impl(c, d_left, c->st_disp, true, ret);
+  const int rc = add_frame_impl(c, d_left, c->st_disp, true, ret);
+  variance_call_done(c);      // (the front-end's measurement-variance map served this call's fusion only)
+  return rc;
 }
 int bpvo_hip_add_frame_stereo(bpvo_hip_ctx* c, const uint8_t* left, const uint8_t* right, const bpvo_hip_stereo_params* sp, bpvo_hip_result* ret)
 {
@@ -64,12 +66,13 @@ int bpvo_hip_add_frame_stereo_raw(bpvo_hip_ctx* c, const uint8_t* left_raw, cons
 }
 static void slot_clear(bpvo_hip_ctx* c, int slot) { c->frames[slot].has_data = false; c->frames[slot].has_template = false; }
 // option disparity fusion (c_api.h; disparity_fusion.hip) for bpvo_hip_add_frame's sequence: the frame in `slot` is fused with the carried maps moved
-// by P, the motion from the previous frame (vo_state.h vo_frame_motion; null: the first frame).  Mode 0: nothing is computed or queued.
+// by P, the motion from the previous frame (vo_state.h vo_frame_motion; null: the first frame).  Mode 0: nothing is computed or queued.  In a stereo
+// call whose front-end made a measurement-variance map for the frame (disparity_variance.hip), the item carries it.
 static int fuse_frame(bpvo_hip_ctx* c, const SeqState& q, int slot, const M44& T_est, const M44* T_again, bool first)
 {
   if(!fusion_on(c, 0)) return BPVO_OK;
   const M44 P = first ? m44_identity() : vo_frame_motion(q, T_est, T_again);
-  const FusionItem it{0, slot, first ? nullptr : P.m};
+  const FusionItem it{0, slot, first ? nullptr : P.m, variance_map_of(c, 0)};
   return fusion_stage(c, 1, &it);
 }
 
@@ -605,7 +608,8 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
   }
   auto fuse_item = [&](const Entry& e, const M44* P) {
     if(P) fuse_P.push_back(*P);
-    return FusionItem{e.seq[0], data_slot[(size_t) (&e - E.data())], P ? fuse_P.back().m : nullptr};
+    // (a stereo call whose front-end made a measurement-variance map for the frame: the item carries it — disparity_variance.hip)
+    return FusionItem{e.seq[0], data_slot[(size_t) (&e - E.data())], P ? fuse_P.back().m : nullptr, variance_map_of(c, e.seq[0])};
   };
 
   // 3. first frames (vo.cc:133-139): every member's template in one stage
@@ -936,7 +940,9 @@ static int add_frames_stereo(bpvo_hip_ctx* c, int n, const int* seq, const uint8
   const uint8_t* d_left = nullptr;
   rc = stereo_front(c, n, sz.data(), ids.data(), left, right, raw, on_device != 0, sp, &d_left);
   if(rc) return rc;
-  return add_frames_run(c, false, ids, d_left, c->st_disp, true, results);
+  rc = add_frames_run(c, false, ids, d_left, c->st_disp, true, results);
+  variance_call_done(c);      // (the front-end's measurement-variance maps served this call's fusion only)
+  return rc;
 }
 int bpvo_hip_add_frames_stereo(bpvo_hip_ctx* c, int n, const int* seq, const uint8_t* left, const uint8_t* right, int on_device,
                                const bpvo_hip_stereo_params* sp, bpvo_hip_result* results)
@@ -960,6 +966,7 @@ int bpvo_hip_seq_reset(bpvo_hip_ctx* c, int seq)
   CHECK_CTX(c); CHECK_SEQ(c, seq);
   if(!c->seqs.empty()) seq_reset_state(c, seq);
   fusion_seq_reset(c, seq);      // (the carried maps go; the setting stays, like the parameters)
+  variance_seq_reset(c, seq);
   return BPVO_OK;
 }
 // A sequence's own point budget (an extension: no reference member), kept on its three frame slots: it outlives bpvo_hip_seq_reset like the

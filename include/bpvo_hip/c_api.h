@@ -884,6 +884,8 @@ int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* ctx, uint64_t out[4]);
  *   "fusion_last_splat_ms"   (read-only) the duration, ms, of the last disparity-fusion stage's splat launch between two events on the context's stream
  *   "fusion_last_update_ms"  (read-only) ... and of its update launch; -1 unless bpvo_hip_profiling was on when the stage was queued (measurement:
  *                                      scripts/disparity_fusion_bench.py)
+ *   "variance_last_kernel_ms" (read-only) the duration, ms, of the last measurement-variance launch between two events on the context's stream; -1 unless
+ *                                      bpvo_hip_profiling was on when it was queued (measurement: scripts/disparity_variance_bench.py)
  *   "normalization_form"     4         the sequential (reference-order) Hartley sums: 1 = hand-scheduled DPP add chains (170 us for a 1241x376 template,
  *                                      2.28 ms for a dense 640x480 one); 0 = the compiler's DPP form (281 us / 3.6 ms); 2 = every lane of a row reads the same
  *                                      four consecutive elements from LDS and adds them with plain adds — no cross-lane traffic, no asm (311 us / 4.0 ms);
@@ -1017,6 +1019,69 @@ int bpvo_hip_fuse_disparities(bpvo_hip_ctx* ctx, int n, const int* seq, const fl
 int bpvo_hip_get_disparity(bpvo_hip_ctx* ctx, int slot, float* out);
 /* measurement: kernel launches of the feature and pixels updated since the context was created */
 int bpvo_hip_disparity_fusion_counts(bpvo_hip_ctx* ctx, uint64_t* launches, uint64_t* pixels);
+
+/* ---- measurement variance (an extension: no reference member; off by default) ---------------------------------------------------------
+ * The other half of the filter above: instead of the constant measurement_sigma^2 the update's r2 is, per pixel, the variance of the measured
+ * disparity, taken from the matching cost of the rectified pair around it (Matthies, Kanade and Szeliski).  The rule
+ * (bpvo_amd/csrc/disparity_variance_math.h states it as code, once, for host and device) for the rectified u8 pair L, R (level-0 size), the
+ * measured map M (x_right = x_left - d), the gate lo, hi of the sequence's parameters, the radius rho, n = (2 rho + 1)^2, and noise2, min2,
+ * max2 the f32 squares of noise_sigma, min_sigma, max_sigma; per pixel (x, y), in this order:
+ *   1. not valid(M) (the gate, as above)                                                     R2 = max2   "invalid"
+ *   2. d0 = (int) rint((double) M), ties to even
+ *   3. the left window, rows y - rho .. y + rho and columns x - rho .. x + rho, or the right windows' columns x - rho - d0 - 1 ..
+ *      x + rho - d0 + 1 not inside the image, or |M| >= 2^30                                   R2 = max2   "border"
+ *   4. S_k = sum over |i|, |j| <= rho of (L[y + j, x + i] - R[y + j, x + i - d0 - k])^2 for k = -1, 0, +1: exact integers below 2^24
+ *   5. a = S_-1 + S_+1 - 2 S_0; a <= 0                                                       R2 = max2   "flat"
+ *   6. v = (float) (2 max(2 n noise2, S_0) / (n a)), in f64: the products are exact, the division is the only rounding before the cast
+ *   7. v < min2: R2 = min2 "floor"; v > max2: R2 = max2 "ceiling"; otherwise R2 = v "model".
+ * (a / 2 is the curvature of the parabola through the three sums; with a pixel noise of variance s per image the variance of its minimum is
+ * 4 s / a, and s is the larger of noise_sigma^2 and the match's own residual S_0 / (2 n): the variance rises on weak texture and on bad
+ * matches.)  Every value the rule writes lies within (0, FLT_MAX].
+ * Units: noise_sigma in grey levels, min_sigma and max_sigma in disparity pixels.  Mode 1 needs radius 1 .. 7, finite values, noise_sigma > 0
+ * and 0 < min_sigma <= max_sigma whose f32 squares are positive and finite; no default is guessed; anything else is BPVO_ERR_INVALID_ARG and
+ * changes nothing.
+ * Where it runs: in the stereo drivers (bpvo_hip_add_frame_stereo, bpvo_hip_add_frames_stereo and their _raw forms), for every frame whose
+ * sequence has disparity fusion in mode 1 AND measurement variance in mode 1: one launch per call behind the matcher, and the frame's fusion
+ * — whichever of the call's stages runs it — takes r2 from the map.  A sequence with the variance on and fusion off does nothing.  Calls
+ * that bring their own disparities (bpvo_hip_add_frame, bpvo_hip_add_frames) have no pair: they use the constant measurement_sigma^2, as
+ * before; their composition with a variance map is bpvo_hip_fuse_disparities_var and a context in mode 0.  With mode 0 everywhere nothing is
+ * allocated or launched and every call is what it was. */
+typedef struct bpvo_hip_measurement_variance {
+  int mode;                 /* 0 off, 1 on */
+  int radius;               /* the window's, 1 .. 7 */
+  float noise_sigma, min_sigma, max_sigma;
+} bpvo_hip_measurement_variance;
+/* the pixels of each class in a sequence's last map */
+typedef struct bpvo_hip_measurement_variance_info {
+  uint32_t invalid, border, flat, floor, ceiling, model;
+} bpvo_hip_measurement_variance_info;
+/* the context's setting (bpvo_hip_add_frame_stereo's sequence, and every sequence without its own) */
+int bpvo_hip_set_measurement_variance(bpvo_hip_ctx* ctx, const bpvo_hip_measurement_variance* setting);
+int bpvo_hip_get_measurement_variance(const bpvo_hip_ctx* ctx, bpvo_hip_measurement_variance* setting);
+/* a sequence's own (null: back to the context's); it outlives bpvo_hip_seq_reset like the fusion setting */
+int bpvo_hip_seq_set_measurement_variance(bpvo_hip_ctx* ctx, int seq, const bpvo_hip_measurement_variance* setting);
+int bpvo_hip_seq_get_measurement_variance(const bpvo_hip_ctx* ctx, int seq, bpvo_hip_measurement_variance* setting, int* own);
+/* The map (to host memory, the camera's rows x cols floats) and the class counts the sequence's frame got in the last stereo call.
+ * BPVO_ERR_NO_DATA before the sequence's first such call, after bpvo_hip_seq_reset, and — the map only, which lives in the front-end's
+ * scratch — once a later call of the front-end's has reused the scratch without the sequence. */
+int bpvo_hip_vo_get_measurement_variance(bpvo_hip_ctx* ctx, float* variance);
+int bpvo_hip_seq_get_measurement_variance_map(bpvo_hip_ctx* ctx, int seq, float* variance);
+int bpvo_hip_vo_measurement_variance_info(bpvo_hip_ctx* ctx, bpvo_hip_measurement_variance_info* info);
+int bpvo_hip_seq_measurement_variance_info(bpvo_hip_ctx* ctx, int seq, bpvo_hip_measurement_variance_info* info);
+/* The rule alone: the variance maps of n rectified pairs of the n cameras' sizes with the measured maps `disparity`, images and maps packed
+ * back to back as for bpvo_hip_stereo_frames (on_device: all three in device memory), under the gate lo .. hi and the setting (mode 1), in
+ * ONE launch; variance_out packed alike (variance_on_device: in device memory); counts_out: null, or [n][6] class counts in the order of
+ * bpvo_hip_measurement_variance_info.  Touches no sequence (but the front-end's scratch, like bpvo_hip_stereo_frames). */
+int bpvo_hip_disparity_variance_frames(bpvo_hip_ctx* ctx, int n, const bpvo_hip_camera* cams, const uint8_t* left, const uint8_t* right,
+                                       const float* disparity, int on_device, float lo, float hi, const bpvo_hip_measurement_variance* setting,
+                                       float* variance_out, int variance_on_device, uint32_t* counts_out);
+/* bpvo_hip_fuse_disparities with the measurements' variances, packed like the maps (on_device: both in device memory): an entry within
+ * (0, FLT_MAX] is the update's r2 for its pixel, any other entry (0, negative, NaN, Inf) takes measurement_sigma^2 */
+int bpvo_hip_fuse_disparities_var(bpvo_hip_ctx* ctx, int n, const int* seq, const float* disparities, const float* variances, int on_device,
+                                  const float* poses);
+/* measurement: launches of the variance kernel and pixels it has served since the context was created, and (tiles: null, or [3]) the tiles
+ * whose right strip was staged in LDS, that read the right image directly (disparities spread too far), and that needed no sums at all */
+int bpvo_hip_measurement_variance_counts(bpvo_hip_ctx* ctx, uint64_t* launches, uint64_t* pixels, uint64_t* tiles);
 
 #ifdef __cplusplus
 }

@@ -140,6 +140,23 @@ struct DisparityFusion : public bpvo_hip_disparity_fusion {
 struct FusedDisparity { ImageSize size; std::vector<float> disparity, variance; };
 /* the last fusion of a sequence (c_api.h bpvo_hip_disparity_fusion_info: fused, replaced, measured, filled, none, predicted, slot, motion) */
 typedef bpvo_hip_disparity_fusion_info DisparityFusionInfo;
+/* measurement variance (c_api.h "measurement variance", an extension with no reference member; off by default): in the stereo addFrame calls of
+ * a sequence that fuses its disparities, the measurement's variance comes per pixel from the matching cost of the rectified pair instead of the
+ * constant measurement_sigma^2.  Units: noiseSigma in grey levels, minSigma / maxSigma in disparity pixels; radius 1 .. 7.  No defaults are
+ * guessed: On(...) takes all four. */
+struct MeasurementVariance : public bpvo_hip_measurement_variance {
+  MeasurementVariance() { mode = 0; radius = 0; noise_sigma = min_sigma = max_sigma = 0.0f; }
+  static MeasurementVariance On(int radius_, float noiseSigma, float minSigma, float maxSigma)
+  {
+    MeasurementVariance v;
+    v.mode = 1; v.radius = radius_; v.noise_sigma = noiseSigma; v.min_sigma = minSigma; v.max_sigma = maxSigma;
+    return v;
+  }
+};
+/* the variance map of a sequence's last stereo frame (row-major, the camera's size) */
+struct MeasurementVarianceMap { ImageSize size; std::vector<float> variance; };
+/* its class counts (c_api.h bpvo_hip_measurement_variance_info: invalid, border, flat, floor, ceiling, model) */
+typedef bpvo_hip_measurement_variance_info MeasurementVarianceInfo;
 inline std::vector<float> packPoses(const std::vector<Matrix44>& poses)
 {
   std::vector<float> M(16 * poses.size());
@@ -501,6 +518,17 @@ class VisualOdometry {
     return r;
   }
   DisparityFusionInfo disparityFusionInfo() const { DisparityFusionInfo r; _dev->check(bpvo_hip_vo_disparity_fusion_info(_dev->ctx(), &r)); return r; }
+  /* measurement variance (an extension; c_api.h bpvo_hip_set_measurement_variance): the setting, the last stereo frame's map and its class counts */
+  void setMeasurementVariance(const MeasurementVariance& setting) { _dev->check(bpvo_hip_set_measurement_variance(_dev->ctx(), &setting)); }
+  MeasurementVarianceMap measurementVariance() const
+  {
+    MeasurementVarianceMap r;
+    r.size = _dev->imageSize();
+    r.variance.resize((size_t) r.size.rows * r.size.cols);
+    _dev->check(bpvo_hip_vo_get_measurement_variance(_dev->ctx(), r.variance.data()));
+    return r;
+  }
+  MeasurementVarianceInfo measurementVarianceInfo() const { MeasurementVarianceInfo r; _dev->check(bpvo_hip_vo_measurement_variance_info(_dev->ctx(), &r)); return r; }
   /* Result::covariance carries the covariance of the estimated pose (option "pose_covariance"); poseCovariance(): the last frame's record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
   PoseCovarianceEstimate poseCovariance() const
@@ -688,6 +716,21 @@ class VisualOdometrySequences {
     return r;
   }
   DisparityFusionInfo disparityFusionInfo(int s) const { DisparityFusionInfo r; _dev->check(bpvo_hip_seq_disparity_fusion_info(_dev->ctx(), s, &r)); return r; }
+  /* measurement variance (an extension; c_api.h bpvo_hip_set_measurement_variance): every sequence's setting, or sequence s's own; the map of
+   * sequence s's last stereo frame and its class counts */
+  void setMeasurementVariance(const MeasurementVariance& setting) { _dev->check(bpvo_hip_set_measurement_variance(_dev->ctx(), &setting)); }
+  void setMeasurementVariance(int s, const MeasurementVariance& setting) { _dev->check(bpvo_hip_seq_set_measurement_variance(_dev->ctx(), s, &setting)); }
+  MeasurementVarianceMap measurementVariance(int s) const
+  {
+    bpvo_hip_camera c;
+    _dev->check(bpvo_hip_seq_get_camera(_dev->ctx(), s, &c));
+    MeasurementVarianceMap r;
+    r.size = ImageSize(c.rows, c.cols);
+    r.variance.resize((size_t) c.rows * c.cols);
+    _dev->check(bpvo_hip_seq_get_measurement_variance_map(_dev->ctx(), s, r.variance.data()));
+    return r;
+  }
+  MeasurementVarianceInfo measurementVarianceInfo(int s) const { MeasurementVarianceInfo r; _dev->check(bpvo_hip_seq_measurement_variance_info(_dev->ctx(), s, &r)); return r; }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   /* Result::covariance of every sequence carries the covariance of its estimated pose (option "pose_covariance"); poseCovariance(s): sequence s's last record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
