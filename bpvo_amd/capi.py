@@ -143,6 +143,27 @@ def measurement_variance(mode=1, radius=0, noise_sigma=0.0, min_sigma=0.0, max_s
     return MeasurementVariance(int(mode), int(radius), float(noise_sigma), float(min_sigma), float(max_sigma))
 
 
+class MotionStereo(C.Structure):
+    """bpvo_hip_motion_stereo: mode (0 off, 1 on), the window's radius, the hypotheses on either side of the prior, the least gain (pixels per
+    disparity pixel), the pixel noise (grey levels), the clamp (disparity pixels) and the gate (standard deviations)."""
+    _fields_ = [("mode", C.c_int), ("radius", C.c_int), ("steps", C.c_int), ("min_gain", C.c_float), ("noise_sigma", C.c_float),
+                ("min_sigma", C.c_float), ("max_sigma", C.c_float), ("gate", C.c_float)]
+
+
+class MotionStereoInfo(C.Structure):
+    """bpvo_hip_motion_stereo_info: the class counts of a sequence's last frame, whether a launch was made, the second view's slot, the motion Q."""
+    _fields_ = [("no_prior", C.c_uint32), ("low_parallax", C.c_uint32), ("border", C.c_uint32), ("edge", C.c_uint32), ("flat", C.c_uint32),
+                ("rejected", C.c_uint32), ("fused", C.c_uint32), ("launched", C.c_int), ("view_slot", C.c_int), ("reserved_", C.c_int * 3),
+                ("motion", C.c_float * 16)]
+
+
+MOTION_STEREO_CLASSES = ("no_prior", "low_parallax", "border", "edge", "flat", "rejected", "fused")
+
+
+def motion_stereo(mode=1, radius=0, steps=0, min_gain=0.0, noise_sigma=0.0, min_sigma=0.0, max_sigma=0.0, gate=0.0) -> MotionStereo:
+    return MotionStereo(int(mode), int(radius), int(steps), float(min_gain), float(noise_sigma), float(min_sigma), float(max_sigma), float(gate))
+
+
 class Camera(C.Structure):
     """bpvo_hip_camera: one sequence's calibration and image size (bpvo_hip_create_sequences, bpvo_hip_seq_set_camera)."""
     _fields_ = [("K", C.c_float * 9), ("baseline", C.c_float), ("rows", C.c_int), ("cols", C.c_int)]
@@ -1381,6 +1402,96 @@ class Context:
         a, b, t = C.c_uint64(), C.c_uint64(), (C.c_uint64 * 3)()
         self.call("measurement_variance_counts", C.byref(a), C.byref(b), t)
         return a.value, b.value, tuple(int(x) for x in t)
+
+    # -- motion stereo (bpvo_hip_set_motion_stereo ...; an extension: no reference member; HIP library only)
+    @staticmethod
+    def _motion_stereo_arg(v):
+        if v is None or isinstance(v, MotionStereo):
+            return v
+        if isinstance(v, dict):
+            return motion_stereo(**v)
+        return motion_stereo(*v)
+
+    @staticmethod
+    def _motion_stereo_dict(v: MotionStereo):
+        return dict(mode=int(v.mode), radius=int(v.radius), steps=int(v.steps), min_gain=float(v.min_gain), noise_sigma=float(v.noise_sigma),
+                    min_sigma=float(v.min_sigma), max_sigma=float(v.max_sigma), gate=float(v.gate))
+
+    @staticmethod
+    def _motion_stereo_info_dict(r: MotionStereoInfo):
+        out = {k: int(getattr(r, k)) for k in MOTION_STEREO_CLASSES}
+        out.update(launched=int(r.launched), view_slot=int(r.view_slot), motion=np.array(r.motion, np.float32).reshape(4, 4))
+        return out
+
+    def set_motion_stereo(self, setting):
+        """bpvo_hip_set_motion_stereo: the context's setting — a MotionStereo, a dict of its fields or a tuple in their order."""
+        v = self._motion_stereo_arg(setting)
+        self.call("set_motion_stereo", C.byref(v))
+
+    def get_motion_stereo(self):
+        v = MotionStereo()
+        self._ck(self.b.fn("get_motion_stereo")(self.h, C.byref(v)))
+        return self._motion_stereo_dict(v)
+
+    def seq_set_motion_stereo(self, s, setting):
+        """bpvo_hip_seq_set_motion_stereo: sequence s's own setting; None returns it to the context's."""
+        v = self._motion_stereo_arg(setting)
+        self.call("seq_set_motion_stereo", int(s), None if v is None else C.byref(v))
+
+    def seq_get_motion_stereo(self, s):
+        """(setting dict, True if it is the sequence's own)"""
+        v, own = MotionStereo(), C.c_int()
+        self._ck(self.b.fn("seq_get_motion_stereo")(self.h, int(s), C.byref(v), C.byref(own)))
+        return self._motion_stereo_dict(v), bool(own.value)
+
+    def vo_motion_stereo_info(self):
+        out = MotionStereoInfo()
+        self.call("vo_motion_stereo_info", C.byref(out))
+        return self._motion_stereo_info_dict(out)
+
+    def seq_motion_stereo_info(self, s):
+        out = MotionStereoInfo()
+        self.call("seq_motion_stereo_info", int(s), C.byref(out))
+        return self._motion_stereo_info_dict(out)
+
+    def motion_stereo_frames(self, cams, firsts, seconds, motions, prior_disparities, prior_variances):
+        """bpvo_hip_motion_stereo_frames: the rule under the context's setting for the image pairs (2-D u8 arrays) of the cameras (Camera, or
+        (K, baseline, rows, cols)), the motions [n, 4, 4] (X_second = Q X_first) and the prior maps (2-D f32; no prior where the variance < 0):
+        (list of f32 disparity maps, list of f32 variance maps, list of u8 class maps)."""
+        n = len(firsts)
+        assert len(seconds) == n and len(prior_disparities) == n and len(prior_variances) == n and len(cams) == n
+        cams = self._camera_array(cams)
+        first, shapes = pack_images(firsts)
+        second, _ = pack_images(seconds)
+        pd = np.concatenate([_f32(d).reshape(-1) for d in prior_disparities])
+        pv = np.concatenate([_f32(d).reshape(-1) for d in prior_variances])
+        assert second.size == first.size and pd.size == first.size and pv.size == first.size, "a pair's images and its priors have one shape"
+        Q = np.ascontiguousarray(_f32(motions).reshape(n, 16))
+        D, V, cls = np.empty(first.size, np.float32), np.empty(first.size, np.float32), np.empty(first.size, np.uint8)
+        self.call("motion_stereo_frames", n, cams, first.ctypes.data_as(C.c_void_p), second.ctypes.data_as(C.c_void_p), Q.ctypes.data_as(C.c_void_p),
+                  pd.ctypes.data_as(C.c_void_p), pv.ctypes.data_as(C.c_void_p), 0, D.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p),
+                  cls.ctypes.data_as(C.c_void_p))
+        Ds, Vs, Cs, at = [], [], [], 0
+        for r, w in shapes:
+            Ds.append(D[at:at + r * w].reshape(r, w))
+            Vs.append(V[at:at + r * w].reshape(r, w))
+            Cs.append(cls[at:at + r * w].reshape(r, w))
+            at += r * w
+        return Ds, Vs, Cs
+
+    def motion_stereo_frames_device(self, cams, d_first_ptr, d_second_ptr, motions, d_pd_ptr, d_pv_ptr, d_out_d_ptr, d_out_v_ptr, d_out_c_ptr=None):
+        """motion_stereo_frames with the packed inputs in device memory, the packed outputs written to device memory."""
+        cams = self._camera_array(cams)
+        Q = np.ascontiguousarray(_f32(motions).reshape(len(cams), 16))
+        self.call("motion_stereo_frames", len(cams), cams, C.c_void_p(d_first_ptr), C.c_void_p(d_second_ptr), Q.ctypes.data_as(C.c_void_p),
+                  C.c_void_p(d_pd_ptr), C.c_void_p(d_pv_ptr), 1, C.c_void_p(d_out_d_ptr), C.c_void_p(d_out_v_ptr),
+                  None if d_out_c_ptr is None else C.c_void_p(d_out_c_ptr))
+
+    def motion_stereo_counts(self):
+        """bpvo_hip_motion_stereo_counts: (launches, pixels, (tiles staged, tiles direct, tiles idle), class-count dict over all launches) so far."""
+        a, b, t, k = C.c_uint64(), C.c_uint64(), (C.c_uint64 * 3)(), (C.c_uint64 * 7)()
+        self.call("motion_stereo_counts", C.byref(a), C.byref(b), t, k)
+        return a.value, b.value, tuple(int(x) for x in t), dict(zip(MOTION_STEREO_CLASSES, (int(x) for x in k)))
 
     # -- batches
     def _stats_array(self, st, n_pairs):

@@ -333,6 +333,8 @@ const std::vector<OptionDef>& option_table()
     OptionDef{"fusion_last_update_ms", 0, 0, [](bpvo_hip_ctx* c) { return fusion_last_ms(c, 1); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
     // read-only: the duration of the last measurement-variance launch between events on the stream, ms; -1 unless bpvo_hip_profiling was on for it
     OptionDef{"variance_last_kernel_ms", 0, 0, [](bpvo_hip_ctx* c) { return variance_last_ms(c); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
+    // read-only: the duration of the last motion-stereo launch between events on the stream, ms; -1 unless bpvo_hip_profiling was on for it
+    OptionDef{"motion_stereo_last_kernel_ms", 0, 0, [](bpvo_hip_ctx* c) { return motion_stereo_last_ms(c); }, [](bpvo_hip_ctx*, double) { return BPVO_OK; }},
     OPT_INT("normalization_side_stream", nrm_side_stream, 0, 1),
     OPT_INT("normalization_form", nrm_dpp_asm, 0, 4),
     OPT_INT("small_batch_fused", small_batch_fused, 0, 1),

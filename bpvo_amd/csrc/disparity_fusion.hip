@@ -81,6 +81,7 @@ int fusion_stage(bpvo_hip_ctx* c, int n, const FusionItem* items)
   const size_t m = act.size();
   size_t max_pixels = 0, pixels = 0;
   bool any_predict = false;
+  std::vector<MotionStereoView> views;      // (motion stereo, motion_stereo.hip: the jobs' second views; stays empty unless a sequence has it on)
   for(size_t k = 0; k < m; ++k) {
     const FusionItem& it = *act[k];
     FusionSeq& q = F.seq[(size_t) it.seq];
@@ -101,6 +102,7 @@ int fusion_stage(bpvo_hip_ctx* c, int n, const FusionItem* items)
     j.slot = f.disp; j.Dc = q.Dc; j.Vc = q.Vc; j.zbuf = q.zbuf; j.counts = F.d_counts + DF_CLASSES * k;
     j.R = it.R;
     any_predict = any_predict || j.predict;
+    if(c->motion_stereo.n_on > 0) views.push_back(MotionStereoView{it.seq, it.slot, j.predict ? it.view_slot : -1, it.T_view, q.zbuf});
     max_pixels = std::max(max_pixels, g.npix);
     pixels += g.npix;
     q.info = bpvo_hip_disparity_fusion_info{};
@@ -120,6 +122,11 @@ int fusion_stage(bpvo_hip_ctx* c, int n, const FusionItem* items)
     HIP_CK(c, hipEventRecord(F.t0, c->stream));
   }
   if(any_predict) launch_fusion_splat(c->stream, F.d_jobs, (int) m, max_pixels);
+  // motion stereo: the predictions of the sequences that have it on, refined in place before the update reads them (one launch, or none; while
+  // profiling its duration counts into the splat's, and is its own option besides).  A failure there is returned behind the update: the update
+  // is what leaves the z-buffers all zero again.
+  bool refined = false;
+  const int refine_rc = views.empty() ? BPVO_OK : motion_stereo_stage(c, (int) views.size(), views.data(), &refined);
   if(c->profiling) HIP_CK(c, hipEventRecord(F.t1, c->stream));
   launch_fusion_update(c->stream, F.d_jobs, (int) m, max_pixels);
   HIP_CK(c, hipGetLastError());
@@ -132,7 +139,7 @@ int fusion_stage(bpvo_hip_ctx* c, int n, const FusionItem* items)
   for(size_t k = 0; k < m; ++k) F.pending.push_back(act[k]->seq);
   F.launches += any_predict ? 2 : 1;
   F.pixels += pixels;
-  return BPVO_OK;
+  return refine_rc;
 }
 
 double fusion_last_ms(bpvo_hip_ctx* c, int which)

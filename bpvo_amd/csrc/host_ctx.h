@@ -7,6 +7,7 @@
 //   pose_cov.hip  the pose-covariance pass behind an estimate (kernels_gn_cov.hip, pose_cov_math.h)      frame_plan.h  the frame stage's decisions (host only, no HIP)
 //   rectify.hip   rectification on the device: the maps of the camera sides, the launch in front of the stereo front-end (kernels_rectify.hip, rectify_math.h)
 //   disparity_fusion.hip  disparity fusion: the maps a sequence carries between its frames, the stage in front of the template stage (kernels_disparity_fusion.hip, disparity_fusion_math.h)
+//   motion_stereo.hip  motion stereo: the prediction of the fusion refined against the key frame, between the fusion stage's two launches (kernels_motion_stereo.hip, motion_stereo_math.h)
 //   disparity_variance.hip  measurement variance: the per-pixel variance of a stereo frame's disparities, behind the matcher (kernels_disparity_variance.hip, disparity_variance_math.h)
 //   stereo.hip    the stereo front-end: parameter checks, buffers, the matchers' launches over the frames of a call, stereo_front for the addFrame drivers
 //                 (kernels_stereo.hip, kernels_sgm.hip, kernels_sgbm.hip; sg_scanline.h: the semi-global matchers' scanline walk)
@@ -219,6 +220,27 @@ struct VarianceState {
   Event t0, t1; bool timed = false;   // while bpvo_hip_profiling is on: events around the last launch (option "variance_last_kernel_ms")
 };
 
+// Motion stereo (c_api.h "motion stereo", motion_stereo.hip): the context's setting and the sequences' own (index 0 is also bpvo_hip_add_frame's),
+// the record of a sequence's last frame, the job table of a launch and the counters it leaves.  Everything is acquired at its first use: a
+// context with mode 0 everywhere, or without fusion, holds nothing.
+struct MotionStereoSeq {
+  bpvo_hip_motion_stereo prm = {0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool own = false;
+  bpvo_hip_motion_stereo_info info = {};
+};
+struct MotionStereoState {
+  bpvo_hip_motion_stereo prm = {0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  std::vector<MotionStereoSeq> seq;   // [max(1, sequence capacity)], made by the first setter that turns mode 1 on
+  int n_on = 0;                       // sequences whose setting is mode 1 right now
+  PinnedBuf<MotionStereoJob> h_jobs; DeviceBuf<MotionStereoJob> d_jobs;
+  PinnedBuf<unsigned> h_counts; DeviceBuf<unsigned> d_counts;      // [jobs][kMotionStereoCounters] of the last launch
+  Event done_ev;                      // behind the last launch's copy of the counters
+  std::vector<int> pending;           // the sequences of the last launch (-1: a stand-alone pair), whose counters are still on their way
+  DeviceBuf<unsigned char> frames_in, frames_out;      // bpvo_hip_motion_stereo_frames: a host caller's inputs and outputs
+  uint64_t launches = 0, pixels = 0, tiles[3] = {0, 0, 0}, classes[7] = {0, 0, 0, 0, 0, 0, 0};
+  Event t0, t1; bool timed = false;   // while bpvo_hip_profiling is on: events around the last launch (option "motion_stereo_last_kernel_ms")
+};
+
 enum KernelClass { KC_PYRAMID = 0, KC_DESCRIPTOR, KC_SALIENCY_SELECT, KC_NORMALIZATION, KC_TEMPLATE, KC_WARP_RESIDUAL, KC_MEDIAN,
                    KC_IRLS_REDUCE, KC_GN_STEP, KC_POINT_BUDGET, KC_COUNT };
 static const char* const kKernelNames[KC_COUNT] = {"pyramid", "descriptor", "saliency_select", "normalization", "template_build", "warp_residual",
@@ -429,6 +451,7 @@ struct bpvo_hip_ctx {
   RectState rect;                         // rectification on the device (rectify.hip)
   FusionState fusion;                     // disparity fusion (disparity_fusion.hip)
   VarianceState variance;                 // measurement variance (disparity_variance.hip)
+  MotionStereoState motion_stereo;        // motion stereo (motion_stereo.hip)
   // Upload pipeline of pair batches handed over in HOST buffers (bpvo_hip_batch_run, on_device = 0): worker threads stage chunks of
   // kUploadChunkPairs pairs in pinned memory and copy them on a stream of their own into a device staging area, chunk after chunk in lane
   // order, while the lanes already work on the chunks that have landed (upload_pipeline below).  Option "upload_workers" (0 = off).
@@ -756,7 +779,9 @@ int rect_clear(bpvo_hip_ctx* c, int seq);
 // the fused one, and the motion from the sequence's previous frame to this one ([16]; null: a first frame, nothing is predicted).  Nothing is
 // synchronised; the class counters are fetched when asked for.  fusion_seq_reset: the sequence carries nothing any more.  R: null, or the
 // measurement's variance map on the device (kernels.h FusionJob::R).
-struct FusionItem { int seq; int slot; const float* P; const float* R = nullptr; };
+// view_slot, T_view: -1 / null, or the second view of motion stereo (motion_stereo.hip) — the frame slot of the key frame of the call's last
+// estimate and that estimate ([16], X_frame = T X_view); read only where the stage predicts and the sequence has motion stereo in mode 1.
+struct FusionItem { int seq; int slot; const float* P; const float* R = nullptr; int view_slot = -1; const float* T_view = nullptr; };
 bool fusion_on(const bpvo_hip_ctx* c, int seq);
 int fusion_stage(bpvo_hip_ctx* c, int n, const FusionItem* items);
 void fusion_seq_reset(bpvo_hip_ctx* c, int seq);
@@ -773,6 +798,18 @@ void variance_seq_reset(bpvo_hip_ctx* c, int seq);
 int variance_scratch_moved(bpvo_hip_ctx* c, size_t npix);      // stereo_reserve: c->st_var follows the front-end's scratch, if it exists
 int stereo_reserve(bpvo_hip_ctx* c, size_t npix);      // stereo.hip: the front-end's scratch holds a call of npix pixels
 double variance_last_ms(bpvo_hip_ctx* c);      // option "variance_last_kernel_ms"
+// Motion stereo (motion_stereo.hip).  motion_stereo_stage: called by fusion_stage between its splat and its update with one view per job of the
+// stage — the sequence, the frame's slot, the second view (slot -1 or T null: none, or the job does not predict) and the job's z-buffer —: ONE
+// launch on the context's stream for the views that have a second view, a finite motion and a sequence with the feature in mode 1 (none:
+// nothing is queued or acquired, and *launched stays false); the sequences of the other views get the record of "no launch".  The stream is
+// not synchronised, but the host waits for the PREVIOUS launch's counters (an event) before it rewrites the pinned job rows and the records
+// they belong to — in a call with two fusion stages that is the first stage's launch, as fusion_stage itself waits for its own.
+// motion_stereo_on: the sequence's setting is mode 1.
+struct MotionStereoView { int seq; int slot; int view_slot; const float* T; unsigned long long* zbuf; };
+bool motion_stereo_on(const bpvo_hip_ctx* c, int seq);
+int motion_stereo_stage(bpvo_hip_ctx* c, int n, const MotionStereoView* views, bool* launched);
+void motion_stereo_seq_reset(bpvo_hip_ctx* c, int seq);
+double motion_stereo_last_ms(bpvo_hip_ctx* c);      // option "motion_stereo_last_kernel_ms"
 // bpvo_hip_fuse_disparities and bpvo_hip_fuse_disparities_var (disparity_fusion.hip); variances null: the constant
 int fuse_disparities_impl(bpvo_hip_ctx* c, int n, const int* seq, const float* disparities, const float* variances, int on_device, const float* poses);
 // The stereo front-end of an addFrame call (stereo.hip): n pairs, pair i of sz[i] pixels for sequence ids[i] (ids null: the context's own camera), the

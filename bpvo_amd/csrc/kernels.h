@@ -171,6 +171,29 @@ struct VarianceJob {
 constexpr int kVarianceCounters = 6 + 3;
 void launch_disparity_variance(hipStream_t s, const VarianceJob* jobs /*device*/, int njobs, int max_tiles);
 int disparity_variance_tiles(int rows, int cols);
+// Motion stereo (kernels_motion_stereo.hip; the rule: motion_stereo_math.h): one pair of views of a call — the first image C and the second
+// image K (u8, rows x cols, any alignment), the geometry of the pair in f64 as ms_geometry forms it, the gate and the setting's numbers, and its
+// counters: the seven classes, then the tiles that took the staged / the direct / no path.  The prior and the result are EITHER the words of a
+// fusion z-buffer, rewritten in place where a pixel is fused (zbuf; a word 0 has no prior and stays 0), OR the caller's maps: pd, pv in and
+// out_d, out_v out (each may be null).  out_c: null, or the class of every pixel.  One launch serves the table; max_tiles: the largest
+// motion_stereo_tiles(rows, cols) among the jobs.
+struct MotionStereoJob {
+  const uint8_t* C;
+  const uint8_t* K;
+  unsigned long long* zbuf;
+  const float* pd;
+  const float* pv;
+  float* out_d;
+  float* out_v;
+  uint8_t* out_c;
+  unsigned* counts;      // [kMotionStereoCounters]
+  double fx, fy, cx, cy, R[9], e[3];
+  int rows, cols, radius, steps;
+  float lo, hi, min_gain, noise2, min2, max2, gate, pad_;
+};
+constexpr int kMotionStereoCounters = 7 + 3;
+void launch_motion_stereo(hipStream_t s, const MotionStereoJob* jobs /*device*/, int njobs, int max_tiles);
+int motion_stereo_tiles(int rows, int cols);
 
 // semi-global matching (kernels_sgm.hip): the reference's in-tree SgmStereo (utils/sgm.cc)
 struct SgmLaunch {

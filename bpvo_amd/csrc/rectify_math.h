@@ -23,7 +23,7 @@ constexpr int kRectMaxRaw = 32767;               // rows and cols of a raw image
 struct RectEntry { int32_t xq, yq; };
 
 // (x, y) -> the entry.  |x * 32| < 2^20 keeps nearbyint inside int32 and the tap indices inside +-32768
-inline RectEntry rect_quantise(double x, double y)
+BPVO_RECT_HD inline RectEntry rect_quantise(double x, double y)
 {
   const double sx = x * 32.0;
   const double sy = y * 32.0;

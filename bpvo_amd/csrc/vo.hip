@@ -67,12 +67,14 @@ int bpvo_hip_add_frame_stereo_raw(bpvo_hip_ctx* c, const uint8_t* left_raw, cons
 static void slot_clear(bpvo_hip_ctx* c, int slot) { c->frames[slot].has_data = false; c->frames[slot].has_template = false; }
 // option disparity fusion (c_api.h; disparity_fusion.hip) for bpvo_hip_add_frame's sequence: the frame in `slot` is fused with the carried maps moved
 // by P, the motion from the previous frame (vo_state.h vo_frame_motion; null: the first frame).  Mode 0: nothing is computed or queued.  In a stereo
-// call whose front-end made a measurement-variance map for the frame (disparity_variance.hip), the item carries it.
-static int fuse_frame(bpvo_hip_ctx* c, const SeqState& q, int slot, const M44& T_est, const M44* T_again, bool first)
+// call whose front-end made a measurement-variance map for the frame (disparity_variance.hip), the item carries it.  key_slot: the key frame the
+// call began with — with T_est the second view of motion stereo (motion_stereo.hip), or, behind a re-estimate, the new key frame q.ref with T_again.
+static int fuse_frame(bpvo_hip_ctx* c, const SeqState& q, int slot, const M44& T_est, const M44* T_again, bool first, int key_slot = -1)
 {
   if(!fusion_on(c, 0)) return BPVO_OK;
   const M44 P = first ? m44_identity() : vo_frame_motion(q, T_est, T_again);
-  const FusionItem it{0, slot, first ? nullptr : P.m, variance_map_of(c, 0)};
+  FusionItem it{0, slot, first ? nullptr : P.m, variance_map_of(c, 0)};
+  if(!first) { it.view_slot = T_again ? q.ref : key_slot; it.T_view = T_again ? T_again->m : T_est.m; }
   return fusion_stage(c, 1, &it);
 }
 
@@ -183,6 +185,7 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
 
   M44 T_est, T_again;
   const int ws0 = 0;
+  const int key_slot = q.ref;      // (the key frame of the first estimate: its image stays in its slot whatever the slot rotation below does)
   rc = check_template_not_empty(c, q.ref);
   if(rc) { (void) upload_now(); (void) hipStreamSynchronize(c->stream); return rc; }
   // the start (vo_state.h; the default policy: T_kf itself and no launch).  The scored mode's round trip lies here, in front of the estimate
@@ -223,7 +226,7 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
     if(kf.clear_slot >= 0) slot_clear(c, kf.clear_slot);
     if(!kf.reestimate) {                                // vo.cc:161-173
       // (disparity fusion: the current frame becomes the key frame — fused before its template is built; T_kf moves in vo_finish only)
-      rc = fuse_frame(c, q, data_slot, T_est, nullptr, false);
+      rc = fuse_frame(c, q, data_slot, T_est, nullptr, false, key_slot);
       if(rc) return rc;
       rc = frames_set_template(c, kf.template_slot, 1, 1);
       if(rc) return rc;
@@ -251,11 +254,11 @@ static int add_frame_impl(bpvo_hip_ctx* c, const uint8_t* image, const float* di
         if(rc) return rc;
       }
       // (disparity fusion: the new key frame is the previous frame, fused in its own call; the current frame with the re-estimate's motion)
-      rc = fuse_frame(c, q, data_slot, T_est, &T_again, false);
+      rc = fuse_frame(c, q, data_slot, T_est, &T_again, false, key_slot);
       if(rc) return rc;
     }
   } else {
-    rc = fuse_frame(c, q, data_slot, T_est, nullptr, false);      // (no key frame: at the end of the call)
+    rc = fuse_frame(c, q, data_slot, T_est, nullptr, false, key_slot);      // (no key frame: at the end of the call)
     if(rc) return rc;
   }
   vo_finish(q, T_est, again ? &T_again : nullptr, ret);
@@ -598,18 +601,27 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
   //   * all the others at the end of the call: first frames (nothing is predicted, the slot keeps the caller's bits), frames that are no key
   //     frame, and key frames with re-estimation — their new key frame is the previous frame, fused in its own call.
   // data_slot: where phase 2 put entry i's frame (the slot roles move below).  Mode 0 everywhere: nothing is computed or queued.
-  std::vector<int> data_slot;
+  // key_slot: the key frame entry i's first estimate runs against.  Motion stereo (motion_stereo.hip) takes the second view of a frame from the
+  // call's last estimate: (key_slot, T_est), or, behind a re-estimate, the new key frame — the body's ref by then — with T_again.  The old key
+  // frame's image stays in its slot until a later call's data stage; every stage of this call is queued before.
+  std::vector<int> data_slot, key_slot;
   std::vector<FusionItem> fuse_now, fuse_last;
   std::vector<M44> fuse_P;
   bool fusing = false;
   if(!rig) {
-    for(const Entry& e : E) { data_slot.push_back(e.mem[0]->cur); fusing = fusing || fusion_on(c, e.seq[0]); }
-    fuse_P.reserve(E.size());      // (the items point into it)
+    for(const Entry& e : E) { data_slot.push_back(e.mem[0]->cur); key_slot.push_back(e.mem[0]->ref); fusing = fusing || fusion_on(c, e.seq[0]); }
+    fuse_P.reserve(2 * E.size());      // (the items point into it)
   }
-  auto fuse_item = [&](const Entry& e, const M44* P) {
+  auto fuse_item = [&](const Entry& e, const M44* P, const M44* T_view = nullptr, bool view_is_new_key = false) {
     if(P) fuse_P.push_back(*P);
     // (a stereo call whose front-end made a measurement-variance map for the frame: the item carries it — disparity_variance.hip)
-    return FusionItem{e.seq[0], data_slot[(size_t) (&e - E.data())], P ? fuse_P.back().m : nullptr, variance_map_of(c, e.seq[0])};
+    FusionItem it{e.seq[0], data_slot[(size_t) (&e - E.data())], P ? fuse_P.back().m : nullptr, variance_map_of(c, e.seq[0])};
+    if(T_view) {
+      fuse_P.push_back(*T_view);
+      it.view_slot = view_is_new_key ? e.mem[0]->ref : key_slot[(size_t) (&e - E.data())];
+      it.T_view = fuse_P.back().m;
+    }
+    return it;
   };
 
   // 3. first frames (vo.cc:133-139): every member's template in one stage
@@ -722,7 +734,7 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
       if(ks[0].reestimate) { re.push_back(k); again.push_back(&e); }
       else if(fusing) {      // (its current frame is the new key frame: fused before the template stage; T_kf moves in vo_finish only)
         const M44 P = vo_frame_motion(*e.body, T_est[k], nullptr);
-        fuse_now.push_back(fuse_item(e, &P));
+        fuse_now.push_back(fuse_item(e, &P, &T_est[k]));
       }
     }
     if(!fuse_now.empty()) {
@@ -755,7 +767,8 @@ static int add_frames_run(bpvo_hip_ctx* c, bool rig, const std::vector<int>& ids
       const Entry& e = *est[k];
       if(e.ret->isKeyFrame && again_of[k] < 0) continue;      // (fused in front of its template stage)
       const M44 P = vo_frame_motion(*e.body, T_est[k], again_of[k] >= 0 ? &T_again[again_of[k]] : nullptr);
-      fuse_last.push_back(fuse_item(e, &P));
+      if(again_of[k] >= 0) fuse_last.push_back(fuse_item(e, &P, &T_again[again_of[k]], true));
+      else fuse_last.push_back(fuse_item(e, &P, &T_est[k]));
     }
     rc = fusion_stage(c, (int) fuse_last.size(), fuse_last.data());
     if(rc) return drain(rc);
@@ -791,6 +804,7 @@ static int rigs_set_impl(bpvo_hip_ctx* c, int n_rigs, const int* count, const in
   const std::string w(who);
   if(c->vo_mode == 1) return fail(c, BPVO_ERR_INVALID_ARG, "this context runs bpvo_hip_add_frame: a rig's members are sequences of bpvo_hip_add_frames' kind");
   if(c->fusion.n_on > 0) return fail(c, BPVO_ERR_UNSUPPORTED, (w + ": a context with disparity fusion in mode 1 does not serve rigs").c_str());
+  if(c->motion_stereo.n_on > 0) return fail(c, BPVO_ERR_UNSUPPORTED, (w + ": a context with motion stereo in mode 1 does not serve rigs").c_str());
   const int S = seq_capacity(c);
   if(n_rigs < 1 || n_rigs > S) return fail(c, BPVO_ERR_INVALID_ARG, (w + ": n_rigs must be within 1 .. the sequence capacity").c_str());
   if(!count) return fail(c, BPVO_ERR_INVALID_ARG, (w + ": nullptr member counts").c_str());
@@ -967,6 +981,7 @@ int bpvo_hip_seq_reset(bpvo_hip_ctx* c, int seq)
   if(!c->seqs.empty()) seq_reset_state(c, seq);
   fusion_seq_reset(c, seq);      // (the carried maps go; the setting stays, like the parameters)
   variance_seq_reset(c, seq);
+  motion_stereo_seq_reset(c, seq);
   return BPVO_OK;
 }
 // A sequence's own point budget (an extension: no reference member), kept on its three frame slots: it outlives bpvo_hip_seq_reset like the

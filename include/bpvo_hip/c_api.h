@@ -883,9 +883,12 @@ int bpvo_hip_tap_cache_counts(bpvo_hip_ctx* ctx, uint64_t out[4]);
  *                                      bpvo_hip_profiling was on when it was queued (measurement: scripts/rectify_bench.py)
  *   "fusion_last_splat_ms"   (read-only) the duration, ms, of the last disparity-fusion stage's splat launch between two events on the context's stream
  *   "fusion_last_update_ms"  (read-only) ... and of its update launch; -1 unless bpvo_hip_profiling was on when the stage was queued (measurement:
- *                                      scripts/disparity_fusion_bench.py)
+ *                                      scripts/disparity_fusion_bench.py); a stage that runs motion stereo has its launch between the two, inside the
+ *                                      splat's figure
  *   "variance_last_kernel_ms" (read-only) the duration, ms, of the last measurement-variance launch between two events on the context's stream; -1 unless
  *                                      bpvo_hip_profiling was on when it was queued (measurement: scripts/disparity_variance_bench.py)
+ *   "motion_stereo_last_kernel_ms" (read-only) the duration, ms, of the last motion-stereo launch between two events on the context's stream; -1 unless
+ *                                      bpvo_hip_profiling was on when it was queued (measurement: scripts/motion_stereo_bench.py)
  *   "normalization_form"     4         the sequential (reference-order) Hartley sums: 1 = hand-scheduled DPP add chains (170 us for a 1241x376 template,
  *                                      2.28 ms for a dense 640x480 one); 0 = the compiler's DPP form (281 us / 3.6 ms); 2 = every lane of a row reads the same
  *                                      four consecutive elements from LDS and adds them with plain adds — no cross-lane traffic, no asm (311 us / 4.0 ms);
@@ -1082,6 +1085,80 @@ int bpvo_hip_fuse_disparities_var(bpvo_hip_ctx* ctx, int n, const int* seq, cons
 /* measurement: launches of the variance kernel and pixels it has served since the context was created, and (tiles: null, or [3]) the tiles
  * whose right strip was staged in LDS, that read the right image directly (disparities spread too far), and that needed no sums at all */
 int bpvo_hip_measurement_variance_counts(bpvo_hip_ctx* ctx, uint64_t* launches, uint64_t* pixels, uint64_t* tiles);
+
+/* ---- motion stereo (an extension: no reference member; off by default) ---------------------------------------------------------------
+ * Every addFrame estimates the motion between two images of ONE camera, the key frame and the current frame: a second baseline beside the
+ * stereo one, which grows with the motion and exists where the matcher returned nothing.  Motion stereo refines the PREDICTION of disparity
+ * fusion — the z-buffer word (pd, pv) of a pixel, between the filter's splat and its update — by a short search along the pixel's epipolar
+ * line in the key frame.  The rule (bpvo_amd/csrc/motion_stereo_math.h states it as code, once, for host and device) for a pixel (x, y) of
+ * the first image C (u8, level 0), the second image K of the same camera and size, the motion Q (row-major, X_K = Q X_C; R its rotation,
+ * t its translation), the camera fx, fy, cx, cy, b, the gate lo, hi of the sequence's parameters, and noise2, min2, max2 the f32 squares of
+ * noise_sigma, min_sigma, max_sigma; in this order:
+ *   1. no prior (a word 0, pv < 0 or NaN), or not lo <= pd <= hi                                                        "no_prior"
+ *   2. in f64, every operation rounded on its own: a = (x - cx) / fx, bq = (y - cy) / fy, h = (R_i0 a + R_i1 bq) + R_i2, e = t / (fx b);
+ *      N0(d) = h0 + d e0, N1(d) = h1 + d e1, D(d) = h2 + d e2; u(d) = (fx N0) / D + cx, v(d) = (fy N1) / D + cy: the epipolar curve.  At
+ *      d = pd: u' = (fx (e0 D - N0 e2)) / (D D), v' = (fy (e1 D - N1 e2)) / (D D), the gain g = sqrt(u' u' + v' v'), in pixels of K per pixel
+ *      of disparity.  g not finite or g < min_gain (pure rotation, a pixel next to the epipole)                         "low_parallax"
+ *      delta = 1 / g: one pixel along the line.
+ *   3. the hypotheses d_j = pd + j delta, j = -steps .. steps.  Each needs d_j > 0, D(d_j) > 0 and |u|, |v| < 2^20; its centre is quantised
+ *      to 1/32 pixel, xq = nearbyint(32 u), ties to even, likewise yq (the rectification's entry).  The window of (2 radius + 1)^2 pixels
+ *      around (x, y) must lie inside C, and every sample of the window around the centre inside K with all four taps: columns
+ *      (xq >> 5) - radius .. (xq >> 5) + radius + 1, rows likewise.  Any hypothesis fails any of these                  "border"
+ *   4. S_j = sum over |ii|, |jj| <= radius of (C[y + jj][x + ii] - k)^2 with k the rectification's pixel of K at (xq + 32 ii, yq + 32 jj):
+ *      four taps with integer weights of 1/32, + 512 >> 10.  Exact integers.
+ *   5. j* the first minimum (the lowest j on ties); |j*| = steps                                                        "edge"
+ *      a2 = S_{j*-1} + S_{j*+1} - 2 S_{j*}; a2 <= 0                                                                     "flat"
+ *      (as j* is the FIRST minimum and lies inside, S_{j*-1} > S_{j*}: a2 >= 1, the class is a guard that no input reaches)
+ *   6. in f64: o = (S_{j*-1} - S_{j*+1}) / (2 a2), dt = (float) (pd + (j* + o) delta); vt = (float) ((2 max(2 n noise2, S_{j*}) / (n a2))
+ *      (delta delta)), n = (2 radius + 1)^2, clamped to [min2, max2] — the measurement variance's model with one step in place of one pixel
+ *   7. in f32, the "fused" arithmetic of disparity fusion: s = pv + vt; |dt - pd| > gate sqrt(s), or the fused value not positive or outside
+ *      the gate: the prior stays                                                                                        "rejected"
+ *      k = pv / s, pd' = pd + k (dt - pd), pv' = pv - k pv                                                              "fused"
+ * Every class but "fused" keeps the prior's own bits.
+ * Units: min_gain in pixels per disparity pixel, noise_sigma in grey levels, min_sigma and max_sigma in disparity pixels, gate in standard
+ * deviations.  Mode 1 needs radius 1 .. 3, steps 1 .. 8, finite values, min_gain > 0, noise_sigma > 0, 0 < min_sigma <= max_sigma and
+ * gate > 0; no default is guessed; anything else is BPVO_ERR_INVALID_ARG, names the field in bpvo_hip_last_error and changes nothing.  A
+ * context that declares a rig refuses mode 1 with BPVO_ERR_UNSUPPORTED (and a context with mode 1 somewhere refuses a rig).
+ * Where it runs: in every addFrame driver (bpvo_hip_add_frame, bpvo_hip_add_frames, their stereo and raw stereo forms), for every frame
+ * whose sequence has disparity fusion in mode 1 AND motion stereo in mode 1, whose fusion predicts (not a first frame) and whose estimate is
+ * finite: ONE launch per fusion stage between the splat and the update.  C is the frame, K the key frame of the call's last estimate T
+ * (X_C = T X_K) — the key frame the call began with, or, at a key frame with re-estimation, the new key frame —, Q = T^-1 (the library's f32
+ * cofactor inverse).  A sequence with motion stereo on and fusion off does nothing.  With mode 0 everywhere nothing is allocated or launched
+ * and every call is what it was. */
+typedef struct bpvo_hip_motion_stereo {
+  int mode;                 /* 0 off, 1 on */
+  int radius;               /* the window's, 1 .. 3 */
+  int steps;                /* hypotheses on either side of the prior, 1 .. 8 */
+  float min_gain, noise_sigma, min_sigma, max_sigma, gate;
+} bpvo_hip_motion_stereo;
+/* the last frame of a sequence: the pixels of each class (all 0 when no launch was made for it), whether a launch was made, the frame slot of
+ * the second view, and the motion Q the rule was given */
+typedef struct bpvo_hip_motion_stereo_info {
+  uint32_t no_prior, low_parallax, border, edge, flat, rejected, fused;
+  int launched;
+  int view_slot;
+  int reserved_[3];
+  float motion[16];
+} bpvo_hip_motion_stereo_info;
+/* the context's setting (bpvo_hip_add_frame's sequence, and every sequence without its own) */
+int bpvo_hip_set_motion_stereo(bpvo_hip_ctx* ctx, const bpvo_hip_motion_stereo* setting);
+int bpvo_hip_get_motion_stereo(const bpvo_hip_ctx* ctx, bpvo_hip_motion_stereo* setting);
+/* a sequence's own (null: back to the context's); it outlives bpvo_hip_seq_reset like the fusion setting */
+int bpvo_hip_seq_set_motion_stereo(bpvo_hip_ctx* ctx, int seq, const bpvo_hip_motion_stereo* setting);
+int bpvo_hip_seq_get_motion_stereo(const bpvo_hip_ctx* ctx, int seq, bpvo_hip_motion_stereo* setting, int* own);
+int bpvo_hip_vo_motion_stereo_info(bpvo_hip_ctx* ctx, bpvo_hip_motion_stereo_info* info);
+int bpvo_hip_seq_motion_stereo_info(bpvo_hip_ctx* ctx, int seq, bpvo_hip_motion_stereo_info* info);
+/* The rule alone, under the context's setting (mode 1) and the gate of the context's parameters: n pairs of views of the n cameras (K,
+ * baseline and size are read), the first and the second images packed back to back as for bpvo_hip_stereo_frames, motions [n][16] (Q, X_second
+ * = Q X_first), and the priors packed alike — a pixel has no prior where prior_variance < 0 (on_device: all four in device memory, and so are
+ * the outputs).  out_disparity, out_variance (f32) and out_class (u8), packed alike; each may be null.  ONE launch; touches no sequence. */
+int bpvo_hip_motion_stereo_frames(bpvo_hip_ctx* ctx, int n, const bpvo_hip_camera* cams, const uint8_t* first, const uint8_t* second,
+                                  const float* motions, const float* prior_disparity, const float* prior_variance, int on_device,
+                                  float* out_disparity, float* out_variance, uint8_t* out_class);
+/* measurement: launches of the kernel and pixels it has served since the context was created; tiles: null, or [3], the tiles whose K box was
+ * staged in LDS, that read K directly (the samples spread too far), and that needed no sums at all; classes: null, or [7], the pixels of each
+ * class over all launches, in the order of bpvo_hip_motion_stereo_info */
+int bpvo_hip_motion_stereo_counts(bpvo_hip_ctx* ctx, uint64_t* launches, uint64_t* pixels, uint64_t* tiles, uint64_t* classes);
 
 #ifdef __cplusplus
 }

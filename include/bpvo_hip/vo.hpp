@@ -157,6 +157,22 @@ struct MeasurementVariance : public bpvo_hip_measurement_variance {
 struct MeasurementVarianceMap { ImageSize size; std::vector<float> variance; };
 /* its class counts (c_api.h bpvo_hip_measurement_variance_info: invalid, border, flat, floor, ceiling, model) */
 typedef bpvo_hip_measurement_variance_info MeasurementVarianceInfo;
+/* Motion stereo (an extension: no reference member; c_api.h bpvo_hip_set_motion_stereo).  mode 0: off, every call is what it was.  mode 1: in
+ * a sequence that fuses its disparities, the prediction of every pixel is refined by a short search along its epipolar line in the key frame of
+ * the call's last estimate.  Units: minGain in pixels per disparity pixel, noiseSigma in grey levels, minSigma / maxSigma in disparity pixels,
+ * gate in standard deviations; radius 1 .. 3, steps 1 .. 8.  No defaults are guessed: On(...) takes all seven. */
+struct MotionStereo : public bpvo_hip_motion_stereo {
+  MotionStereo() { mode = 0; radius = steps = 0; min_gain = noise_sigma = min_sigma = max_sigma = gate = 0.0f; }
+  static MotionStereo On(int radius_, int steps_, float minGain, float noiseSigma, float minSigma, float maxSigma, float gate_)
+  {
+    MotionStereo v;
+    v.mode = 1; v.radius = radius_; v.steps = steps_; v.min_gain = minGain; v.noise_sigma = noiseSigma; v.min_sigma = minSigma; v.max_sigma = maxSigma;
+    v.gate = gate_;
+    return v;
+  }
+};
+/* the last frame's class counts, whether a launch was made, the second view's slot and motion (c_api.h bpvo_hip_motion_stereo_info) */
+typedef bpvo_hip_motion_stereo_info MotionStereoInfo;
 inline std::vector<float> packPoses(const std::vector<Matrix44>& poses)
 {
   std::vector<float> M(16 * poses.size());
@@ -529,6 +545,15 @@ class VisualOdometry {
     return r;
   }
   MeasurementVarianceInfo measurementVarianceInfo() const { MeasurementVarianceInfo r; _dev->check(bpvo_hip_vo_measurement_variance_info(_dev->ctx(), &r)); return r; }
+  /* motion stereo (an extension; c_api.h bpvo_hip_set_motion_stereo): the setting and the last frame's record */
+  void setMotionStereo(const MotionStereo& setting) { _dev->check(bpvo_hip_set_motion_stereo(_dev->ctx(), &setting)); }
+  MotionStereo motionStereo() const
+  {
+    MotionStereo r;
+    _dev->check(bpvo_hip_get_motion_stereo(_dev->ctx(), &r));
+    return r;
+  }
+  MotionStereoInfo motionStereoInfo() const { MotionStereoInfo r; _dev->check(bpvo_hip_vo_motion_stereo_info(_dev->ctx(), &r)); return r; }
   /* Result::covariance carries the covariance of the estimated pose (option "pose_covariance"); poseCovariance(): the last frame's record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
   PoseCovarianceEstimate poseCovariance() const
@@ -731,6 +756,16 @@ class VisualOdometrySequences {
     return r;
   }
   MeasurementVarianceInfo measurementVarianceInfo(int s) const { MeasurementVarianceInfo r; _dev->check(bpvo_hip_seq_measurement_variance_info(_dev->ctx(), s, &r)); return r; }
+  /* motion stereo (an extension; c_api.h bpvo_hip_set_motion_stereo): every sequence's setting, or sequence s's own; sequence s's last record */
+  void setMotionStereo(const MotionStereo& setting) { _dev->check(bpvo_hip_set_motion_stereo(_dev->ctx(), &setting)); }
+  void setMotionStereo(int s, const MotionStereo& setting) { _dev->check(bpvo_hip_seq_set_motion_stereo(_dev->ctx(), s, &setting)); }
+  MotionStereo motionStereo(int s) const
+  {
+    MotionStereo r;
+    _dev->check(bpvo_hip_seq_get_motion_stereo(_dev->ctx(), s, &r, nullptr));
+    return r;
+  }
+  MotionStereoInfo motionStereoInfo(int s) const { MotionStereoInfo r; _dev->check(bpvo_hip_seq_motion_stereo_info(_dev->ctx(), s, &r)); return r; }
   double getOption(const std::string& name) const { return _dev->getOption(name); }
   /* Result::covariance of every sequence carries the covariance of its estimated pose (option "pose_covariance"); poseCovariance(s): sequence s's last record */
   void setPoseCovariance(bool on) { _dev->setOption("pose_covariance", on ? 1.0 : 0.0); }
